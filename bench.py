@@ -12,6 +12,10 @@ synthetic pairs (20,000 clones, Zipf 1.1, 30 % noise, k=35 mf=3 
 With N GPUs every rank holds its own pool of that size and the k-mer partial aggregates are exchanged by
 hash prefix through the C driver of `vdjer --gpus N` (vdjer_amd/libvdjmgpu.so, vdjer_amd/mgpu.py): weak scaling.
 
+A plain run sets up, warms up, times --steps steps, writes the last step's outputs (--dump-outputs DIR) and prints its line;
+everything else below (per-kernel pass and roofline, parity gates, host-fed / read-index / two-in-flight legs, CPU baselines)
+runs with --full only.
+
 Prints ONE JSON line (rank 0).  `roofline` prices the dominant HBM-streaming kernel of the step (the longest
 kernel of the k-mer build; HIP events on the library's stream) against HBM peak, `roofline_by_kernel` every
 kernel with a stated job size (the window scorer's inputs are cache resident: its figure is not an HBM one); `cpu_baseline` times the REFERENCE ITSELF (oracle/_ref/vdjer_ref, the
@@ -442,6 +446,51 @@ def traffic_source(args=None, world: int = 1) -> dict | None:
     return {"file": os.path.relpath(f, ROOT), "commit": tj.get("commit"), "note": "PMC passes are separate runs of the same command (profiles/prof_step.sh)"}
 
 
+DUMP_ROWS = 1 << 17              # rows per chain of an output written whole; above, a seeded sample (--dump-outputs stays below 64 MB)
+DUMP_MAX_BYTES = 64_000_000
+GRAPH_FIELDS = ("first_inst", "gated_count", "freq", "has_v", "has_j", "to_deg", "to_ids", "from_deg", "from_ids", "kmers")
+
+
+def dump_outputs(out_dir: str, chains: list, seed: int) -> int:
+    """--dump-outputs: chains = [(file prefix, Graph, {name: array})] -- what the last timed step returned, chain by chain in step order.
+    Every array becomes <prefix><name>.npy: float32 where exact (8/16-bit fields), float64 otherwise (ids, counts; first_inst < 2^53), the
+    mapped pairs as rows of PAIR_DTYPE's fields; <prefix>counts.npy holds the full sizes.  Above DUMP_ROWS / chains rows: the rows of a
+    sorted sample drawn with `seed`, the same rows for every array of that length.  A result whose page-locked buffer a later chain of the
+    step reused (--config4) is not the chain's any more: skipped.  Returns the bytes written."""
+    os.makedirs(out_dir, exist_ok=True)
+    cap = DUMP_ROWS // max(1, len(chains))
+    samples, files = {}, {}
+
+    def rows(n):
+        if n <= cap:
+            return slice(None)
+        if n not in samples:
+            samples[n] = np.sort(np.random.default_rng(seed).choice(n, cap, replace=False))
+        return samples[n]
+
+    def as_float(a):
+        if a.dtype.names:                                  # structured (mapped pairs): one column per field
+            return np.stack([a[f].astype(np.float64) for f in a.dtype.names], axis=-1).reshape(-1, len(a.dtype.names))
+        return a.astype(np.float32 if a.dtype.itemsize <= 2 else np.float64)
+
+    flat = [(prefix, {**{"graph_" + f: getattr(g, f) for f in GRAPH_FIELDS}, **res}) for prefix, g, res in chains]
+    for i, (prefix, arrays) in enumerate(flat):
+        for name, a in arrays.items():
+            if any(np.may_share_memory(a, b) for _, later in flat[i + 1:] for b in later.values()):     # (any field: layouts differ by size)
+                print(f"--dump-outputs: {prefix}{name} was overwritten by a later chain of the step: not written", file=sys.stderr)
+                continue
+            files[prefix + name] = as_float(np.asarray(a)[rows(a.shape[0])])
+        g = chains[i][1]
+        files[prefix + "counts"] = np.array([g.n, g.pre_nodes, g.n_roots, len(arrays["window_valid"]), int(arrays["window_valid"].sum()),
+                                             len(arrays["contig_offsets"]) - 1, arrays["pairs"].shape[0]], np.float64)
+    total = sum(a.nbytes for a in files.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes, more than {DUMP_MAX_BYTES}")
+    for name, a in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return total
+
+
 # the HBM-streaming kernels of the k-mer build: the roofline kernel is the longest of them
 BUILD_KERNELS = ("k_pool_pack", "k_gated_hist", "k_part_records", "k_part_tuples", "k_seg_hist", "k_gated_reduce", "k_gated_local",
                  "k_walk_items", "k_part_items", "k_recount")
@@ -497,6 +546,12 @@ def main():
                          "second host thread, the steps dealt alternately: what the host waits and kernel tails of one step leave idle is filled by the other "
                          "(reported as value_two_in_flight; never `value`)")
     ap.add_argument("--no-index-leg", action="store_true", help="skip value_with_read_index (profiles/prof_step.sh: the process then ends with the timed steps)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: the per-kernel pass and roofline, the parity gates, the host-fed, read-index and two-in-flight legs, "
+                         "and the CPU baselines.  Without it the line holds the headline figures only (the rest null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64; float32 for 8/16-bit fields): graph, root "
+                         "verdicts, window verdicts and pair counts, contig offsets, mapped pairs -- arrays above a cap as a sample of rows seeded by --seed")
     args = ap.parse_args()
     if args.gpus == 8 and not args.no_config4:
         args.config4 = True
@@ -630,16 +685,18 @@ def main():
     def build_index():
         ctx.read_index_build_device(p_index, ri_dev[0].data_ptr(), ri_dev[1].data_ptr(), ri_dev[2].data_ptr(), ri_dev[3].data_ptr(), pool.n_pairs)
     build_index()                       # (first call: allocations)
-    ctx.profile(True)
-    ctx.profile_reset()
-    for _ in range(3):
-        t_ix = time.perf_counter()
-        build_index()
-        ix_times.append(time.perf_counter() - t_ix)
-    ri_prof = ctx.profile_get()
-    ctx.profile(False)
-    ctx.profile_reset()
-    host_side["read_index_build_s"] = round(min(ix_times), 4)
+    ri_prof = {}
+    if args.full:
+        ctx.profile(True)
+        ctx.profile_reset()
+        for _ in range(3):
+            t_ix = time.perf_counter()
+            build_index()
+            ix_times.append(time.perf_counter() - t_ix)
+        ri_prof = ctx.profile_get()
+        ctx.profile(False)
+        ctx.profile_reset()
+    host_side["read_index_build_s"] = round(min(ix_times), 4) if ix_times else None
     host_side["read_index"] = {n_: ctx.stat("read_index_" + n_) for n_ in ("classes", "r1_members", "r1_distinct", "rank_order")}
     host_side["read_index_kernels_ms"] = {k_: round(v[0] / 3, 4) for k_, v in ri_prof.items()}
     scorer_src = ("one 486-nt window per clone from the generator (the window the reference derives for that clone's transcript) and, as contigs, the "
@@ -714,6 +771,7 @@ def main():
         return time.perf_counter()
 
     host_fwd = {}
+    last_out = {}                      # chain index -> (graph, the other results) of its latest step: what --dump-outputs writes
 
     def step(from_host: bool = False):
         for w_ in W:
@@ -790,6 +848,7 @@ def main():
                          valid=int(valid.sum()), contigs=n_contigs if world == 1 else None, mapped_this_rank=int(pairs.shape[0]),
                          window_pairs_this_rank=int(npairs.sum()), n_contigs_rank=n_contigs)
         state.setdefault("per_chain", {})[w_["chain"]] = per_chain
+        last_out[w_["ci"]] = (g, dict(root_ids=root_ids, root_ok=ok, window_valid=valid, window_npairs=npairs, contig_offsets=offs, pairs=pairs))
         if w_["ci"] == 0:
             state.update(per_chain)
             state.update(graph=g, last=dict(root_ids=root_ids, ok=ok, valid=valid, npairs=npairs, offs=offs, pairs=pairs))
@@ -817,7 +876,8 @@ def main():
     # busy fraction, and the name of the roofline kernel (the longest HBM-streaming kernel of the build); (2) the timed region with that
     # ONE kernel bracketed (vdjx_profile_only): roofline.achieved is measured live inside the timed region, on the stream the kernel is
     # launched on.  VDJX_BENCH_ALL_EVENTS=1: every kernel inside the timed region, as in rounds 1-4; VDJX_BENCH_NO_EVENTS=1: none anywhere.
-    no_events = os.environ.get("VDJX_BENCH_NO_EVENTS") == "1"
+    # Without --full: none anywhere (the per-kernel figures are --full's).
+    no_events = os.environ.get("VDJX_BENCH_NO_EVENTS") == "1" or not args.full
     all_events = os.environ.get("VDJX_BENCH_ALL_EVENTS") == "1"
     prof_full, prof_ms_step, n_prof, dom_name = None, None, 0, None
     if not no_events and not all_events:
@@ -854,6 +914,8 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     gc.enable()
+    if args.dump_outputs and rank == 0:          # (before anything else reuses the page-locked result buffers)
+        dump_outputs(args.dump_outputs, [("" if w_["ci"] == 0 else w_["chain"] + "_", *last_out[w_["ci"]]) for w_ in W], args.seed)
     prof_timed = ctx.profile_get()
     ctx.profile(False)
     ctx.profile_only(None)
@@ -867,7 +929,7 @@ def main():
     # flags name that workload; (2) a small sample of the same generator re-checked against the oracle itself.
     timed_check = None
     dg_path = os.path.join(ROOT, "tests", "golden", "fullsize_digests.json")
-    if rank == 0 and world == 1 and not args.config4 and os.path.exists(dg_path):          # (--force-shard too: the C driver's one-rank build and scorers against the same digests)
+    if args.full and rank == 0 and world == 1 and not args.config4 and os.path.exists(dg_path):          # (--force-shard too: the C driver's one-rank build and scorers against the same digests)
         import hashlib
         dg = json.load(open(dg_path))
         case = {(35, 3, 90, 30): "k35", (25, 2, 60, 20): "k25", (35, 3, 60, 30): "k35_mq60"}.get((args.k, args.mf, args.mq, args.mrs))
@@ -900,7 +962,7 @@ def main():
     # ---- the same step fed from the HOST (never `value`): the reads as extracted (one 101-byte record per read; the reverse
     # complement records are derived on the chip) in page-locked memory, uploaded in chunks beside the packing
     e2e = None
-    if world == 1 and not args.no_e2e:
+    if args.full and world == 1 and not args.no_e2e:
         def host_fed(packed: bool):
             """the step of `value` fed from page-locked HOST memory: the reads as extracted (forward records only; the reverse complement
             records are derived on the chip), as 101-byte ASCII records or in the packed host format (vdjx_pool_load_packed: 64 bytes per read)"""
@@ -953,7 +1015,7 @@ def main():
     # ---- the same step with the read index of its pool built inside it (row a-8's index, quick_map3.c:126-149: the reference
     # builds it during extraction, bam_read.c:228,243, once per pool -- like a command line that sees every pool once)
     with_index = None
-    if world == 1 and not args.force_shard and not args.no_index_leg:
+    if args.full and world == 1 and not args.force_shard and not args.no_index_leg:
         n_wi = max(2, min(args.steps, 10))
         wall_keep = dict(wall)
 
@@ -981,7 +1043,7 @@ def main():
         wall.update(wall_keep)
     # ---- two batches in flight (never `value`): how much of the step is the device waiting for the host and for kernel tails
     two = None
-    if world == 1 and engine is None and not args.no_two_in_flight and not args.no_index_leg:
+    if args.full and world == 1 and engine is None and not args.no_two_in_flight and not args.no_index_leg:
         import threading
         cx2 = api.Context(local_rank, pinned_results=True)
         cx2.anchor_sets_load(vc, jc)
@@ -1051,7 +1113,7 @@ def main():
                        "of `value` is one batch alone on the device"}
         p_index2.free()
         cx2.close()
-    if world == 1 and engine is not None and not args.no_two_in_flight and not args.no_index_leg:
+    if args.full and world == 1 and engine is not None and not args.no_two_in_flight and not args.no_index_leg:
         # the same through the C driver (--force-shard / --config4 on one GPU): a second context WITH a second one-rank driver; the chains of
         # the steps (config4: IGH, IGK, IGL, IGH, ...) dealt alternately to two host threads -- chain i + 1's packing, index and build under
         # chain i's scorers, which is what two `vdjer --gpus N` runs side by side on the same devices would do
@@ -1146,7 +1208,7 @@ def main():
     # ---- parity gate, part 2 (part 1, the timed step's own outputs, ran right after the timed loop): a small sample of the same
     # generator re-checked against the oracle itself
     parity = None
-    if rank == 0 and args.parity_sample > 0 and world == 1:
+    if args.full and rank == 0 and args.parity_sample > 0 and world == 1:
         from oracle import oracle
         from vdjer_amd import synth
         n_s = min(args.parity_sample, args.pairs)
@@ -1277,7 +1339,7 @@ def main():
                 "hot_path_frac_gated": round((2 * ab["input"] + 32 * ab["gated_per_pair"] + 16 * ab["P"]) * args.pairs * len(W) / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)}
     cpu = None
     cpu_port_legs = None
-    if not args.no_cpu and world == 1:
+    if args.full and not args.no_cpu and world == 1:
         ncores = min(os.cpu_count() or 1, 100)          # `thread_info threads[100]`, A2:1285
         cpu = cpu_reference(min(args.cpu_sample, args.pairs), args.seed, args.k, args.mf, args.mq, args.mrs, args.ins, ncores)
         cpu_port_legs = [cpu_port(min(args.cpu_port_sample, args.pairs), args.seed, args.k, args.mf, args.mq, args.mrs, args.ins, o0)
@@ -1298,12 +1360,12 @@ def main():
                    "variant": "config4" if args.config4 else ("shard" if args.force_shard else ("k25" if args.k == 25 else "")),
                    "multi_gpu_input": "one independent library (own germline, clones, reads) per GPU; ONE k-mer table / graph / traversal over all of them",
                    "scorer_inputs": scorer_src},
-        "roofline": roof, "roofline_by_kernel": by_kernel, "cpu_baseline": cpu, "cpu_baseline_port_legs": cpu_port_legs,
+        "roofline": roof, "roofline_by_kernel": by_kernel or None, "cpu_baseline": cpu, "cpu_baseline_port_legs": cpu_port_legs,
         "speedup_vs_cpu_baseline": round(value / cpu["value"], 1) if cpu else None,
         "value_end_to_end": e2e, "value_with_read_index": with_index, "value_two_in_flight": two, "first_step_ms": round(first_step_ms, 3) if first_step_ms else None, "first_step_phases_ms": first_step_phases,
         "cli_end_to_end": cli_e2e, "cli_at_size": cli_size,
-        "kernels_ms_per_step": kern_ms, "kernels_sum_ms_per_step": round(sum(kern_ms.values()), 3),
-        "device_busy_frac": round(sum(kern_ms.values()) / prof_ms_step, 4) if prof_ms_step else None,
+        "kernels_ms_per_step": kern_ms or None, "kernels_sum_ms_per_step": round(sum(kern_ms.values()), 3) if kern_ms else None,
+        "device_busy_frac": round(sum(kern_ms.values()) / prof_ms_step, 4) if prof_ms_step and kern_ms else None,
         "instrumentation": ({"timed_region_events": f"{dom_name} only (the roofline kernel: roofline.avg_launch_ms / achieved / frac are measured inside the timed region)",
                              "per_kernel_pass": f"{n_prof} untimed steps before the timed region with every kernel bracketed by HIP events: kernels_ms_per_step, "
                                                 "roofline_by_kernel, device_busy_frac (against that pass's own wall time)",

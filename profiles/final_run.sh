@@ -5,13 +5,13 @@ TAG=${1:-r06f}
 bash profiles/r06_prof_all.sh $TAG > gpurun_out/prof_all_$TAG.log 2>&1; tail -4 gpurun_out/prof_all_$TAG.log
 M=gpurun_out/${TAG}m
 mkdir -p $M
-python bench.py > $M/default.json 2> $M/default.err
-python bench.py --pairs 1000000 --steps 200 > $M/1M.json 2> $M/1M.err
-python bench.py --k 25 --mf 2 --mq 60 --mrs 20 --steps 30 > $M/k25.json 2> $M/k25.err
-python bench.py --force-shard --steps 30 > $M/shard.json 2> $M/shard.err
-python bench.py --pairs 100000 --steps 200 --no-cpu > $M/100k.json 2>/dev/null
-python bench.py --config4 --gpus 1 --steps 5 --warmup 1 --no-cpu > $M/config4_1gpu.json 2> $M/config4_1gpu.err
-python bench.py --repertoire private --cli-at-size --steps 30 --no-cpu --no-e2e > $M/private_10M.json 2> $M/private_10M.err
+python bench.py --full > $M/default.json 2> $M/default.err
+python bench.py --full --pairs 1000000 --steps 200 > $M/1M.json 2> $M/1M.err
+python bench.py --full --k 25 --mf 2 --mq 60 --mrs 20 --steps 30 > $M/k25.json 2> $M/k25.err
+python bench.py --full --force-shard --steps 30 > $M/shard.json 2> $M/shard.err
+python bench.py --full --pairs 100000 --steps 200 --no-cpu > $M/100k.json 2>/dev/null
+python bench.py --full --config4 --gpus 1 --steps 5 --warmup 1 --no-cpu > $M/config4_1gpu.json 2> $M/config4_1gpu.err
+python bench.py --full --repertoire private --cli-at-size --steps 30 --no-cpu --no-e2e > $M/private_10M.json 2> $M/private_10M.err
 python - <<PY
 import json
 for n in ("default","1M","k25","shard","100k","config4_1gpu","private_10M"):

@@ -96,14 +96,17 @@ def _rdv_worker(d, me, G, mesh, q):
 
 
 @pytest.mark.parametrize("G,mesh", [(2, 0), (3, 1), (4, 0), (5, 1)])
-def test_comm_rendezvous_of_started_ranks(G, mesh, tmp_path):
+def test_comm_rendezvous_of_started_ranks(G, mesh, tmp_path, monkeypatch):
     """vdjx_comm_rendezvous: ranks that are processes already (bench.py under torch.distributed.run) meet in a directory and get the
     socket row vdjx_comm_sockets would have given them before a fork -- control pairs with rank 0 only (mesh 0: the RCCL transport) or
     the full mesh (the host transport).  No GPU involved."""
     import multiprocessing as mp
+    # a socket path holds at most 107 bytes and tmp_path can be deeper than that: the ranks (which inherit the working directory)
+    # meet in a directory named relative to it
+    monkeypatch.chdir(tmp_path)
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    ps = [ctx.Process(target=_rdv_worker, args=(str(tmp_path / "rdv"), r, G, mesh, q)) for r in range(G)]
+    ps = [ctx.Process(target=_rdv_worker, args=("rdv", r, G, mesh, q)) for r in range(G)]
     for p in reversed(ps):                         # (the listeners start last: the callers retry until they are there)
         p.start()
     res = sorted(q.get(timeout=120) for _ in range(G))

@@ -289,13 +289,35 @@ int vdjx_sam_blocks(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const
                     uint64_t* n_blocks, uint64_t* n_bytes, const void** d_keys, const void** d_lens, const void** d_text);
 int vdjx_sam_merge(vdjx_ctx* ctx, uint64_t n_blocks, uint64_t n_bytes, const void* d_keys, const void* d_lens, const void* d_text,
                    const char** out_text, uint64_t* out_bytes);
+/* ---- contig abundances: the step the reference's workflow runs after every vdjer run ---------------------------------------------
+ * replaces: `samtools view -bS vdjer.sam`, a name sort, `rsem-prepare-reference vdj_contigs.fa` and `rsem-calculate-expression
+ * --paired-end` (demo/quant_demo.bash; post_process/post_processing.readme.txt), of whose output post_process/collect_vdjer_stats.py
+ * reads only expected_count.  The placements are vdjx_map_emit's pairs for `contigs` (the SAM records of vdjx_sam_text), kept on the
+ * device; every placement of a pair is one alignment.  RSEM's core paired-end model in float64:
+ *   fragment lengths  P(f) = (h(f) + 1) / sum(h + 1) over f in [50, 400] (MIN_INSERT / MAX_INSERT, quick_map3.c:23-24), h = inserts of
+ *                     the pairs placed exactly once; an alignment of insert f weighs g(f) = P(f) / (len - f + 1)
+ *   start             N_c = placed pairs / contigs with a placement (0 for the others, for good)
+ *   iteration         E: r_a = N_c(a) g(f_a) / sum over the pair's alignments;  M: N_c = sum of r_a over the alignments on c
+ *   stop              after iteration t when max_c |N_c(t) - N_c(t-1)| / max(N_c(t), 1) < tol, or at t = max_iter (tol 0: max_iter)
+ * out_counts[n] = N (RSEM's expected_count; TPM, FPKM and IsoPct follow from it and info->eff_len = sum_{f <= len} P(f) (len - f + 1)).
+ * NOT modelled: RSEM's noise transcript, read qualities and mismatches (a placement here is exact), fragment-length tails outside
+ * [50, 400], Gibbs sampling and credibility intervals, gene-level grouping (every contig is its own gene).  Bitwise reproducible
+ * (no floating-point atomics).  n = 0 and pools that place no pair give zeros.  Contigs of unequal length (a NUL inside the n*len
+ * characters), max_iter < 1 and tol < 0 are VDJX_EINVAL; fewer than 2^20 contigs of fewer than 4096 bases per call (vdjx_sam_blocks'
+ * limit).  Scratch comes from the context's workspace; the text of an earlier vdjx_sam_text stays valid.  One GPU only (a pool sharded
+ * by pair would need a per-iteration all-reduce of N). */
+typedef struct { int max_iter; double tol; } vdjx_quant_params;
+typedef struct { uint64_t pairs, alignments, unique_pairs; uint32_t iterations, converged; double eff_len; } vdjx_quant_info;
+int vdjx_quant(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const vdjx_quant_params* params, double* out_counts, vdjx_quant_info* info);
+
 /* rows of `row` bytes on the device: row d_pos[i] of d_dst = row i of d_src.  (The records of a pool sharded by pair on their way to
  * the ranks that hold their slice of the scan order for the k-mer build, A2:1388-1390: every record arrives with its place.) */
 int vdjx_rows_scatter(vdjx_ctx* ctx, void* d_dst, const void* d_src, const uint32_t* d_pos, size_t n, size_t row);
 
 /* counters of the most recent scorer calls, by name: "window_hits" (read instances matched by the last
  * vdjx_window_score call, summed over windows), "window_hits_max", "window_pairs", "window_work_items",
- * "map_hits", "root_dp_items".  Unknown names return 0.  Used by bench.py to price the scorers' algorithmic bytes. */
+ * "map_hits", "root_dp_items".  Unknown names return 0.  Used by bench.py to price the scorers' algorithmic bytes.  vdjx_quant's last
+ * call: "quant_map_us", "quant_setup_us", "quant_em_us" (host clock, each phase ending in a wait for the device), "quant_contigs_placed". */
 uint64_t vdjx_stat(vdjx_ctx* ctx, const char* name);
 
 /* ---- profiling hooks (HIP events on the context's stream) ---------------------------------------*/

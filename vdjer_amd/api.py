@@ -4,7 +4,8 @@ The names follow the reference's call sites: a `Context` owns the 
 (vjf_init), the V-region index (score_seq_init) and the read index (add_read_info); `kmer_build`
 stands where build_pre_graph/prune_pre_graph/build_graph2 stand in assemble() (A2:1388-1408);
 `root_score` is score_seq (A2:1103); `window_score` is quick_map_process_contig + coverage_is_valid
-(A2:841-847); `map_emit` is quick_map_process_contig_file (A2:912).
+(A2:841-847); `map_emit` is quick_map_process_contig_file (A2:912); `quant` is the RSEM step the reference's workflow runs
+on vdjer.sam afterwards (demo/quant_demo.bash).
 Everything computes on the GPU through libvdjx.so; nothing here falls back to a CPU path.
 """
 from __future__ import annotations
@@ -594,6 +595,22 @@ class Context:
         # (C.string_at takes a C int: the text of 10 M pairs is 3 GB)
         addr = C.cast(txt, C.c_void_p).value
         return bytes((C.c_char * nb.value).from_address(addr)) if nb.value else b""
+
+    def quant(self, contigs, max_iter: int = 10000, tol: float = 1e-5):
+        """vdjx_quant: expected read pairs per contig (RSEM's paired-end EM over map_emit's placements, on the device)
+        -> (counts float64[n], info dict: pairs, alignments, unique_pairs, iterations, converged, eff_len)"""
+        if isinstance(contigs, tuple):
+            raw, n, ln = contigs
+        else:
+            if len({len(s_) for s_ in contigs}) > 1:
+                raise VdjxError("vdjx_quant: contigs of unequal length")
+            raw, n, ln = self.pack_strings(contigs)
+        counts = np.zeros(n, np.float64)
+        info = _lib.QuantInfo()
+        prm = _lib.QuantParams(int(max_iter), float(tol))
+        check(self.L.vdjx_quant(self.h, raw, n, ln, C.byref(prm), _p(counts), C.byref(info)), "vdjx_quant")
+        return counts, dict(pairs=int(info.pairs), alignments=int(info.alignments), unique_pairs=int(info.unique_pairs),
+                            iterations=int(info.iterations), converged=bool(info.converged), eff_len=float(info.eff_len))
 
     def stat(self, name: str) -> int:
         return int(self.L.vdjx_stat(self.h, name.encode()))

@@ -3,8 +3,9 @@
  * vdjh (serial host stage).  Plain C; talks to the GPU only through the C ABI of include/vdjx.h.
  *
  *   vdjer --in <reads> --chain IGH|IGK|IGL --ref-dir <dir> --ins <n> [--t --k --mf --mq --mcs --am --miw --maw
- *         --jc --ws -jext --rf --vk --mrs --rs --ms --e0 --e1 --wo --vf --jf --rms]
- * writes ./vdj_contigs.fa and ./vdjer.dot, SAM on stdout, log on stderr; exit 0 on success.
+ *         --jc --ws -jext --rf --vk --mrs --rs --ms --e0 --e1 --wo --vf --jf --rms] [--gpus N] [--quant <file>]
+ * writes ./vdj_contigs.fa and ./vdjer.dot, SAM on stdout, log on stderr; exit 0 on success.  --quant <file>: the contigs' abundances
+ * (vdjx_quant, RSEM's isoforms.results columns) into <file> as well.
  *
  * --in: a BAM with its .bai (extraction as bam_read.c:264-446, restated over zlib in bamx.c), or -- recognised by its
  * content -- the extracted read pool as text, one read per line in extraction order:
@@ -40,6 +41,7 @@ typedef struct {
 	char v_region[64], c_region[64];       /* set_chain_info, params.c:8-35 (hg38 coordinates); --vr / --cr override */
 	int anchor_mismatches, threads;
 	int gpus;                              /* --gpus N (not in the reference): the k-mer build sharded over N GPUs of this node */
+	const char* quant;                     /* --quant <file> (not in the reference): the RSEM step of demo/quant_demo.bash, on the device */
 	int have_chain, have_ref;
 } cli;
 
@@ -52,7 +54,8 @@ static void usage(void) {
 	                "\t--vk <vregion kmer size (default: 15)>\n\t--mrs <min source node homology score (default: 30)\n"
 	                "\t--rs <read span distance (default: 35)>\n\t--ms <mate span distance (default: 48)>\n"
 	                "\t--e0/--e1 <start/stop position for contig filtering (default: 52/411)>\n\t--wo <window overlap check size>\n"
-	                "\t--gpus <GPUs of this node to shard the k-mer table over (default: 1)>\n");
+	                "\t--gpus <GPUs of this node to shard the k-mer table over (default: 1)>\n"
+	                "\t--quant <file: expected read pairs per contig, an RSEM isoforms.results table (one GPU only)>\n");
 }
 
 static int file_exists(const char* f) { struct stat b; return stat(f, &b) == 0; }
@@ -90,6 +93,7 @@ static int parse(int argc, char** argv, cli* c) {
 		else if (!strcmp(a, "--mcs")) c->hp.min_contig_score = (float) atof(v);
 		else if (!strcmp(a, "--t")) c->threads = atoi(v);
 		else if (!strcmp(a, "--gpus")) c->gpus = atoi(v);
+		else if (!strcmp(a, "--quant")) c->quant = v;
 		else if (!strcmp(a, "--vf")) snprintf(c->v_anchors, sizeof c->v_anchors, "%s", v);
 		else if (!strcmp(a, "--jf")) snprintf(c->j_anchors, sizeof c->j_anchors, "%s", v);
 		else if (!strcmp(a, "--am")) c->anchor_mismatches = atoi(v);
@@ -448,7 +452,12 @@ static int load_vregion(const char* path, char*** lines, size_t* n) {
 /* ------------------------------------------------------------------------------------------ */
 /* hooks onto libvdjx                                                                          */
 /* ------------------------------------------------------------------------------------------ */
-typedef struct { vdjx_ctx* gx; const reads_t* r; const vdjh_params* p; vdjx_mgpu* mg; } hook_ud;
+typedef struct {
+	vdjx_ctx* gx; const reads_t* r; const vdjh_params* p; vdjx_mgpu* mg;
+	const char* quant;                  /* --quant <file>: the table is written after the SAM body */
+	int quant_done;
+	vdjx_quant_info qi;
+} hook_ud;
 
 static int h_root_score(void* ud, const char* kmers, size_t n, int k, int thr, uint8_t* out) {
 	hook_ud* u = (hook_ud*) ud;
@@ -480,7 +489,7 @@ static const uint8_t* rec_ptr(const reads_t* r, uint32_t rec) {
 
 /* output_mapping, quick_map3.c:152-181: mapped and formatted on the device (vdjx_sam_text); VDJX_SAM_HOST=1 formats the pairs of
  * vdjx_map_emit here instead (the same bytes; kept as the cross-check of the formatting kernel) */
-static int h_sam_body(void* ud, const char* const* ids, const char* contigs, size_t n, int len, FILE* out) {
+static int sam_records(void* ud, const char* const* ids, const char* contigs, size_t n, int len, FILE* out) {
 	hook_ud* u = (hook_ud*) ud;
 	const reads_t* r = u->r;
 	if (u->mg || !getenv("VDJX_SAM_HOST")) {
@@ -528,6 +537,35 @@ static int h_sam_body(void* ud, const char* const* ids, const char* contigs, siz
 	free(offs);
 	free(pairs);
 	return 0;
+}
+
+/* --quant: rsem-calculate-expression's <prefix>.isoforms.results (demo/quant_demo.bash) for the final contigs, in vdj_contigs.fa order:
+ * every contig is its own gene, all have length `len`; TPM = 1e6 N / sum N, FPKM = 1e9 N / (eff_len sum N), IsoPct 100 or 0 */
+static int quant_table(hook_ud* u, const char* const* ids, const char* contigs, size_t n, int len) {
+	double* cnt = (double*) calloc(n + 1, sizeof(double));
+	const vdjx_quant_params qp = {10000, 1e-5};
+	int rc = vdjx_quant(u->gx, contigs, n, len, &qp, cnt, &u->qi);
+	if (rc) { fprintf(stderr, "vdjx_quant: %s\n", vdjx_last_error()); free(cnt); return rc; }
+	FILE* fp = fopen(u->quant, "w");
+	if (!fp) { fprintf(stderr, "cannot write %s\n", u->quant); free(cnt); return -1; }
+	double sum = 0.0;
+	for (size_t i = 0; i < n; i++) sum += cnt[i];
+	const double eff = u->qi.eff_len;
+	fprintf(fp, "transcript_id\tgene_id\tlength\teffective_length\texpected_count\tTPM\tFPKM\tIsoPct\n");
+	for (size_t i = 0; i < n; i++) {
+		const double tpm = sum > 0.0 ? 1e6 * cnt[i] / sum : 0.0, fpkm = sum > 0.0 && eff > 0.0 ? cnt[i] * 1e9 / (eff * sum) : 0.0;
+		fprintf(fp, "%s\t%s\t%d\t%.2f\t%.2f\t%.2f\t%.2f\t%.2f\n", ids[i], ids[i], len, eff, cnt[i], tpm, fpkm, cnt[i] > 0.0 ? 100.0 : 0.0);
+	}
+	free(cnt);
+	if (fclose(fp)) { fprintf(stderr, "cannot write %s\n", u->quant); return -1; }
+	u->quant_done = 1;
+	return 0;
+}
+
+static int h_sam_body(void* ud, const char* const* ids, const char* contigs, size_t n, int len, FILE* out) {
+	hook_ud* u = (hook_ud*) ud;
+	const int rc = sam_records(ud, ids, contigs, n, len, out);
+	return rc || !u->quant ? rc : quant_table(u, ids, contigs, n, len);
 }
 
 static void h_status(void* ud, const char* desc) { (void) ud; status(desc); }
@@ -603,6 +641,10 @@ int main(int argc, char** argv) {
 	int rank = 0;
 	if (c.gpus < 1 || c.gpus > 256) { fprintf(stderr, "--gpus must be in [1,256]\n"); return 255; }
 	const int use_mgpu = c.gpus > 1 || getenv("VDJX_FORCE_MGPU") != NULL;      /* (the variable: a one-rank run of the same code path) */
+	if (c.quant && use_mgpu) {
+		fprintf(stderr, "--quant runs on one GPU only: it cannot be combined with --gpus N > 1 (or VDJX_FORCE_MGPU)\n");
+		return 255;
+	}
 	/* ranks that share ONE device (the multi-rank tests on a one-GPU box; RCCL refuses two ranks on a device): bytes move through the
 	 * host.  Otherwise rank r drives GPU r and the bytes move by RCCL over xGMI. */
 	const int one_device = getenv("VDJX_MGPU_ONE_DEVICE") != NULL;
@@ -779,13 +821,16 @@ int main(int argc, char** argv) {
 	VX(vdjx_graph_export(gg, NULL, NULL, freq, hv, hj, td, ti, fd, fi, kmers));
 	hg.kmers = kmers; hg.freq = freq; hg.has_v = hv; hg.has_j = hj; hg.to_deg = td; hg.to_ids = ti; hg.from_deg = fd; hg.from_ids = fi;
 
-	hook_ud ud = {gx, &rd, &c.hp, mg};
+	hook_ud ud;
+	memset(&ud, 0, sizeof ud);
+	ud.gx = gx; ud.r = &rd; ud.p = &c.hp; ud.mg = mg; ud.quant = c.quant;
 	vdjh_hooks hk = {&ud, h_root_score, h_window_score, h_sam_body, vc, nv, jc, nj, h_status};
 	vdjh_stats st;
 	if (vdjh_assemble(&c.hp, &hg, &hk, "vdj_contigs.fa", "vdjer.dot", stdout, &st)) {
 		fprintf(stderr, "%s\n", vdjh_last_error());
 		return 1;
 	}
+	if (c.quant && !ud.quant_done && quant_table(&ud, NULL, NULL, 0, 0)) return 1;         /* (no contig: the header alone) */
 	fprintf(stderr, "num root nodes: %zu\nProcessed roots: %zu\ncontig_candidates: %zu\nwindows scored: %zu valid: %zu\ncontigs: %zu\n",
 	        st.n_roots, st.n_roots_accepted, st.n_contig_candidates, st.n_windows_scored, st.n_windows_valid, st.n_contigs_out);
 	if (mg) {
@@ -811,6 +856,10 @@ int main(int argc, char** argv) {
 		if (g_kid_state[r] != 1) { fprintf(stderr, "rank %d failed\n", r); return 1; }
 	}
 	status("FINIS");
+	if (c.quant)
+		fprintf(stderr, "quant: %llu pairs placed (%llu once), %llu alignments, %u EM iterations, %s; table in %s\n", (unsigned long long) ud.qi.pairs,
+		        (unsigned long long) ud.qi.unique_pairs, (unsigned long long) ud.qi.alignments, ud.qi.iterations,
+		        ud.qi.converged ? "converged" : "stopped at the iteration limit", c.quant);
 	fflush(stdout);
 	fflush(stderr);
 	/* the outputs are written; the orderly teardown of a context that holds gigabytes (unmapping the workspaces piece by piece, the

@@ -2432,6 +2432,18 @@ extern "C" int vdjx_map_emit_begin(vdjx_ctx* c, const char* contigs, size_t n, i
 	return map_emit_impl(c, contigs, n, len, offsets, pairs, true);
 }
 
+// the mapped pairs of `contigs` left on the device for vdjx_quant (vdjx_quant.hip): contig after contig in vdjx_map_emit's order in
+// c->me_dense, queued on the context's stream; offsets[n + 1] as vdjx_map_emit fills them
+int vdjx_map_emit_device(vdjx_ctx* c, const char* contigs, size_t n, int len, uint64_t* offsets, const vdjx_pair** d_pairs) {
+	*d_pairs = nullptr;
+	int rc = map_emit_impl(c, contigs, n, len, offsets, nullptr, false);
+	if (rc || !n || !offsets[n]) return rc;
+	rc = map_emit_impl(c, contigs, n, len, offsets, (vdjx_pair*) 1, false, true);
+	if (rc) return rc;
+	*d_pairs = (const vdjx_pair*) c->me_dense;
+	return VDJX_OK;
+}
+
 extern "C" int vdjx_map_emit_end(vdjx_ctx* c) {
 	if (!c) { vdjx_set_error("vdjx_map_emit_end: ctx is NULL"); return VDJX_EINVAL; }
 	HIP_TRY(hipSetDevice(c->device));

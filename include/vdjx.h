@@ -310,6 +310,51 @@ typedef struct { int max_iter; double tol; } vdjx_quant_params;
 typedef struct { uint64_t pairs, alignments, unique_pairs; uint32_t iterations, converged; double eff_len; } vdjx_quant_info;
 int vdjx_quant(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const vdjx_quant_params* params, double* out_counts, vdjx_quant_info* info);
 
+/* ---- contig annotation: V/J calls, identity and CIGARs against the germline segments (the ref-dir's ig_vdj.fa) -----------------------
+ * replaces the IMGT HighV-QUEST round trip of the reference's post_process/ (collect_vdjer_stats.py reads the V gene, the J gene, the
+ * V-region identity and the CDR3 from it).  All arithmetic is integer: the device's results are bitwise the model's.
+ *   germlines   vdjx_germline_load: record r is seqs[off[r] .. off[r+1]) of class cls[r] ('V', 'J'; anything else is counted and
+ *               skipped).  The caller parses the FASTA: the name is the header's first token, or its second '|' field when the token has
+ *               one (IMGT/GENE-DB); the class is the name's 4th character for IG[HKL]* / TR[ABDG]* names, its 1st otherwise; sequences
+ *               uppercased, '.' and whitespace dropped.  The set stays on the device until the next load or vdjx_shutdown.
+ *   scoring     Smith-Waterman with affine gaps (Gotoh), contig row i in 1..m, germline column j in 1..g; a gap of k bases costs
+ *               open + k ext; s(i,j) = +match when both bases are equal and in ACGT (upper case), -mismatch otherwise (N included):
+ *                 E[i][j] = max(E[i][j-1] - ext, H[i][j-1] - open - ext)     (D: germline base j missing from the contig)
+ *                 F[i][j] = max(F[i-1][j] - ext, H[i-1][j] - open - ext)     (I: contig base i not in the germline)
+ *                 H[i][j] = max(0, H[i-1][j-1] + s(i,j), E[i][j], F[i][j]);  H = 0 on row 0 and column 0, E = F = -inf there
+ *   score       S = max H; the end cell is the first cell in row-major order (smallest i, then smallest j) that holds S
+ *   calls       per class: the primary hit is the germline of highest S, the lowest record index on a tie; n_tied counts the germlines at
+ *               that S and tied[] lists the first 8 of them in index order (AIRR's comma-joined v_call).  No call (gene -1, n_tied 0)
+ *               when S < min_v_score / min_j_score, or when the class has no record; score is S all the same.
+ *   traceback   the primary hit only, from the end cell in state H:
+ *                 H at (i,j): H == 0: stop (the alignment begins at (i+1, j+1)); H == H[i-1][j-1] + s: align, to H (i-1,j-1);
+ *                             else H == E: to E at (i,j); else to F at (i,j)
+ *                 E: emit D; E[i][j] == H[i][j-1] - open - ext (a gap open): to H (i,j-1), else to E (i,j-1)
+ *                 F: emit I; F[i][j] == H[i-1][j] - open - ext (a gap open): to H (i-1,j), else to F (i-1,j)
+ *               seq_/germ_start and _end are 1-based closed; matches + mismatches are the aligned pairs; ins / del the I / D bases; opens
+ *               the gap opens the traceback took (so S = match*matches - mismatch*mismatches - open*opens - ext*(ins + del)).  runs[] are
+ *               the M/I/D runs 5' to 3' as len << 4 | op (op 0 M, 1 I, 2 D: BAM's codes); n_runs counts them all, runs[] holds them only
+ *               when n_runs <= 64 (otherwise zeros: the CIGAR is written empty, stat "annot_cigar_truncated").  S = 0: no traceback
+ *               (coordinates and counts 0).  identity = matches / (matches + mismatches + ins + del).
+ * NOT modelled: D calls; IMGT-gapped sequence_alignment / germline_alignment; isotype (the ref-dir has no constant regions); reverse-
+ * complement contigs (a contig is always V to J); IgBLAST's or V-QUEST's own identity definitions.
+ * VDJX_EINVAL: contigs of unequal length (a NUL inside the n*len characters), len >= 4096, a V/J germline of 0 or >= 2048 bases, 2^20
+ * records or more, match outside 1..15 or mismatch / gap_open / gap_extend outside 0..31 (every H then fits int16); vdjx_annotate before
+ * any vdjx_germline_load is VDJX_ESTATE.  n = 0 returns at once.  Scratch comes from the context's workspace; no floating-point atomics,
+ * two runs are bitwise equal.  VDJX_ANNOT_PAIRS (environment, read once): (contig, germline) pairs per scoring launch. */
+#define VDJX_ANNOT_TIED 8
+#define VDJX_ANNOT_RUNS 64
+typedef struct { int match, mismatch, gap_open, gap_extend, min_v_score, min_j_score; } vdjx_annot_params;
+typedef struct {
+	int32_t gene, score, n_tied, tied[VDJX_ANNOT_TIED];
+	int32_t seq_start, seq_end, germ_start, germ_end;
+	int32_t matches, mismatches, ins, del, opens, n_runs;
+	uint32_t runs[VDJX_ANNOT_RUNS];
+} vdjx_annot_hit;                                              /* 340 bytes */
+int vdjx_germline_load(vdjx_ctx* ctx, const char* seqs, const uint64_t* off, const char* cls, size_t n);
+int vdjx_annotate(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const vdjx_annot_params* params, vdjx_annot_hit* out_v,
+                  vdjx_annot_hit* out_j);
+
 /* rows of `row` bytes on the device: row d_pos[i] of d_dst = row i of d_src.  (The records of a pool sharded by pair on their way to
  * the ranks that hold their slice of the scan order for the k-mer build, A2:1388-1390: every record arrives with its place.) */
 int vdjx_rows_scatter(vdjx_ctx* ctx, void* d_dst, const void* d_src, const uint32_t* d_pos, size_t n, size_t row);
@@ -317,7 +362,8 @@ int vdjx_rows_scatter(vdjx_ctx* ctx, void* d_dst, const void* d_src, const uint3
 /* counters of the most recent scorer calls, by name: "window_hits" (read instances matched by the last
  * vdjx_window_score call, summed over windows), "window_hits_max", "window_pairs", "window_work_items",
  * "map_hits", "root_dp_items".  Unknown names return 0.  Used by bench.py to price the scorers' algorithmic bytes.  vdjx_quant's last
- * call: "quant_map_us", "quant_setup_us", "quant_em_us" (host clock, each phase ending in a wait for the device), "quant_contigs_placed". */
+ * call: "quant_map_us", "quant_setup_us", "quant_em_us" (host clock, each phase ending in a wait for the device), "quant_contigs_placed".
+ * vdjx_annotate's last call: "annot_cells" (DP cells of the scoring phase), "annot_score_us", "annot_trace_us", "annot_cigar_truncated". */
 uint64_t vdjx_stat(vdjx_ctx* ctx, const char* name);
 
 /* ---- profiling hooks (HIP events on the context's stream) ---------------------------------------*/

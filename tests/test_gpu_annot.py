@@ -1,0 +1,289 @@
+"""vdjx_annotate on the GPU: V/J calls, alignments and CIGAR runs against the integer model of tests/annot_model.py (field for field), at
+size against the private repertoire, and `vdjer --airr` on every e2e golden.  The API checks run in child processes, once per knob
+setting (the suite's and the shipped ones, as tests/test_gpu_quant.py runs them), since VDJX_ANNOT_PAIRS is read once per process."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from tests import annot_model as A
+from tests import golden_util as G
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+E2E = ["e2e_tiled", "e2e_mixed", "e2e_k25", "e2e_igk", "e2e_igl", "e2e_rl100", "e2e_rl151"]
+KNOBS = ["suite", "shipped"]
+# make_repertoire's arguments of every e2e golden (tests/golden/make_golden.py, make_golden_chains.py, make_golden_longreads.py)
+RECIPES = {"e2e_tiled": dict(n_clones=3, seed=11), "e2e_mixed": dict(n_clones=6, seed=31), "e2e_k25": dict(n_clones=6, seed=31),
+           "e2e_igk": dict(n_clones=3, seed=131, chain="IGK", zipf_s=0.2), "e2e_igl": dict(n_clones=3, seed=151, chain="IGL", zipf_s=0.2),
+           "e2e_rl100": dict(n_clones=3, seed=171, zipf_s=0.2), "e2e_rl151": dict(n_clones=3, seed=191, zipf_s=0.2)}
+
+
+def _child_env(knobs: str, **extra):
+    env = dict(os.environ, **extra)
+    if knobs == "shipped":
+        env.pop("VDJX_HIT_CHUNK", None)
+        env.pop("VDJX_GROUP_MIN", None)
+        env.pop("VDJX_ANNOT_PAIRS", None)
+    return env
+
+
+def _run_child(fn, arg, env, timeout=900):
+    code = f"import json; from tests.test_gpu_annot import {fn}; print('ANNOT', json.dumps({fn}({arg!r})))"
+    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=timeout, env=env)
+    assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-4000:])
+    return json.loads(next(l for l in r.stdout.splitlines() if l.startswith("ANNOT ")).split(" ", 1)[1])
+
+
+def _same(dev, model, what):
+    for cls in ("v", "j"):
+        for f in A.FIELDS:
+            a, b = np.asarray(dev[cls][f]).astype(np.int64), np.asarray(model[cls][f]).astype(np.int64)
+            assert np.array_equal(a, b), (what, cls, f, np.argwhere(a != b)[:5].tolist(), a.ravel()[:12].tolist(), b.ravel()[:12].tolist())
+
+
+def _rand(rng, n, alpha="ACGT"):
+    return "".join(rng.choice(list(alpha), int(n)))
+
+
+def _mutate(rng, s, k):
+    s = list(s)
+    for _ in range(k):
+        q = int(rng.integers(0, len(s)))
+        op = int(rng.integers(0, 3))
+        if op == 0:
+            s[q] = "ACGT"[int(rng.integers(0, 4))]
+        elif op == 1 and len(s) > 2:
+            del s[q]
+        else:
+            s.insert(q, "ACGT"[int(rng.integers(0, 4))])
+    return "".join(s)
+
+
+def _random_case(seed, m, n=9):
+    """contigs of length m built from V + junk + J with mutations and indels; germlines of 1 .. 2047 bases, duplicates (forced ties),
+    N bases, lower-case bases and records of other classes"""
+    rng = np.random.default_rng(seed)
+    V = [_rand(rng, rng.integers(60, 320)) for _ in range(7)] + ["A", "AC", _rand(rng, 2047), _rand(rng, 2046, "ACGTN")]
+    J = [_rand(rng, rng.integers(20, 70)) for _ in range(4)] + ["G"]
+    V.append(V[2])                                                 # (a tie with record 2)
+    J.append(J[1])
+    contigs = []
+    for c in range(n):
+        v, j = V[int(rng.integers(0, 7))], J[int(rng.integers(0, 4))]
+        body = _mutate(rng, v[int(rng.integers(0, 30)):], int(rng.integers(0, 12))) + _rand(rng, 20) + _mutate(rng, j, int(rng.integers(0, 3)))
+        if c == n - 1:
+            body = V[9][100:100 + m]                                 # (a contig inside the 2047-base germline)
+        body = (body + _rand(rng, m))[:m]
+        if c % 4 == 3:
+            body = body[:10] + "N" + body[11:40] + "n" + body[41:]
+        contigs.append(body)
+    recs, classes, germs = [], [], []
+    for k, s in enumerate(V):
+        recs.append((f"V{k} x", s.lower() if k == 3 else s))
+    for k, s in enumerate(J):
+        recs.append((f"IGHJ{k}*01", s))
+    recs.insert(4, ("IGHD1-1*01", "GGTACAAC"))
+    recs.insert(9, ("C1", "ACGT" * 700))                              # (a class not scored: may be longer than 2047)
+    from vdjer_amd import annot
+    for h, s in recs:
+        nm, cl, sq = annot.parse_record(h, s)
+        classes.append(cl)
+        germs.append(sq)
+    return contigs, recs, germs, classes
+
+
+def _api_checks(tag):
+    from vdjer_amd import api
+    from vdjer_amd._lib import VdjxError
+    ctx = api.Context(0)
+    out = {}
+    with pytest.raises(VdjxError):
+        ctx.annotate(["ACGT"])                                       # (no germline set yet)
+    for seed, m, prm in ((1, 200, A.DEFAULT), (2, 130, dict(match=1, mismatch=1, gap_open=0, gap_extend=1, min_v_score=10, min_j_score=5)),
+                         (3, 64, A.DEFAULT), (4, 65, dict(match=15, mismatch=31, gap_open=31, gap_extend=31, min_v_score=0, min_j_score=0)),
+                         (5, 360, dict(match=3, mismatch=2, gap_open=2, gap_extend=1, min_v_score=40, min_j_score=20))):
+        contigs, recs, germs, classes = _random_case(seed, m)
+        info = ctx.germline_load(recs)
+        assert info["skipped"] == {"D": 1, "C": 1}
+        dev = ctx.annotate(contigs, **prm)
+        model = A.annotate(contigs, germs, classes, prm)
+        _same(dev, model, (seed, m))
+        again = ctx.annotate(contigs, **prm)
+        for cls in ("v", "j"):
+            for f in A.FIELDS:
+                assert np.asarray(again[cls][f]).tobytes() == np.asarray(dev[cls][f]).tobytes()
+        out[f"seed{seed}"] = dict(v=int((dev["v"]["gene"] >= 0).sum()), j=int((dev["j"]["gene"] >= 0).sum()), cells=ctx.stat("annot_cells"))
+        assert ctx.stat("annot_cells") == len(contigs) * m * sum(len(g) for g, c in zip(germs, classes) if c in "VJ")
+    # a CIGAR of more than 64 runs: counts exact, runs zero, counted
+    rng = np.random.default_rng(9)
+    g = _rand(rng, 900)
+    cont = "".join(g[q:q + 6] + ("" if (q // 6) % 2 else "T") for q in range(0, 900, 6))[:700]
+    ctx.germline_load([("V0", g), ("J0", g[:50])])
+    dev = ctx.annotate([cont], gap_open=0, gap_extend=1)
+    model = A.annotate([cont], [g, g[:50]], ["V", "J"], dict(A.DEFAULT, gap_open=0, gap_extend=1))
+    _same(dev, model, "long")
+    assert dev["v"]["n_runs"][0] > 64 and not dev["v"]["runs"][0].any() and ctx.stat("annot_cigar_truncated") >= 1
+    # no contig; refusals
+    r0 = ctx.annotate([])
+    assert r0["v"]["gene"].shape == (0,)
+    for bad in (dict(match=0), dict(match=16), dict(mismatch=32), dict(gap_open=-1), dict(gap_extend=32)):
+        with pytest.raises(VdjxError):
+            ctx.annotate([cont], **bad)
+    with pytest.raises(VdjxError):
+        ctx.annotate(["ACGT", "ACG"])
+    with pytest.raises(VdjxError):
+        ctx.annotate((b"ACG\0ACGT", 2, 4))
+    with pytest.raises(VdjxError):
+        ctx.annotate(["A" * 4096])
+    for recs in ([("V0", "")], [("V0", "A" * 2048)], [("J0", "")]):
+        with pytest.raises(VdjxError):
+            ctx.germline_load(recs)
+    with pytest.raises(VdjxError):
+        ctx.germline_load([("D0", "A")] * (1 << 20))
+    ctx.close()
+    return out
+
+
+@pytest.mark.parametrize("knobs", KNOBS)
+def test_annot_api_vs_model(knobs):
+    res = _run_child("_api_checks", "x", _child_env(knobs))
+    assert res["seed1"]["v"] > 0 and res["seed1"]["j"] > 0
+
+
+def test_annot_multi_launch_small_pairs():
+    """VDJX_ANNOT_PAIRS=3: chunks of at most one germline, one workgroup per launch -- the results are the model's all the same"""
+    res = _run_child("_api_checks", "x", _child_env("suite", VDJX_ANNOT_PAIRS="3"))
+    assert res["seed1"]["v"] > 0
+
+
+def at_size_contigs(n=2172, n_clones=20000):
+    """(ids, contigs, repertoire): windows of make_repertoire(n_clones, private_v=True, private_j=True) cut to the 360 bases a contig keeps
+    (--e0/--e1 52..411), named vjf_<n>_<junction>"""
+    from vdjer_amd import synth
+    rep = synth.make_repertoire(n_clones, private_v=True, private_j=True)
+    ids, seqs, clone = [], [], []
+    for ci, (w, j) in enumerate(zip(rep.windows(), rep.cdr3s())):
+        if w is None:
+            continue
+        ids.append(f"vjf_{len(ids)}_{j}")
+        seqs.append(w[52:412])
+        clone.append(ci)
+        if len(ids) == n:
+            break
+    return ids, seqs, rep, clone
+
+
+def _at_size(_):
+    import time
+    from vdjer_amd import api
+    ids, seqs, rep, clone = at_size_contigs()
+    ctx = api.Context(0)
+    recs = [(f"V{i}", v) for i, v in enumerate(rep.v_germ)] + [(f"J{i}", j) for i, j in enumerate(rep.j_germ)]
+    info = ctx.germline_load(recs)
+    t0 = time.perf_counter()
+    h = ctx.annotate(seqs)
+    wall = time.perf_counter() - t0
+    nv = len(rep.v_germ)
+    rows = A.airr_rows(ids, seqs, h, info["names"])
+    for c, cl in enumerate(clone):
+        assert rep.clones[cl].find(seqs[c]) >= 0
+        tv = h["v"]["tied"][c][:min(8, h["v"]["n_tied"][c])].tolist()
+        tj = h["j"]["tied"][c][:min(8, h["j"]["n_tied"][c])].tolist()
+        assert rep.clone_v[cl] in tv and nv + rep.clone_j[cl] in tj, (c, tv, tj)
+        assert rows[c][3] == "T", rows[c]
+        for k in ("v", "j"):
+            x = {f: int(h[k][f][c]) for f in ("score", "matches", "mismatches", "ins", "del", "opens")}
+            assert 2 * x["matches"] - 3 * x["mismatches"] - 5 * x["opens"] - 2 * (x["ins"] + x["del"]) == x["score"], (c, k, x)
+    return dict(contigs=len(seqs), cells=ctx.stat("annot_cells"), score_us=ctx.stat("annot_score_us"), trace_us=ctx.stat("annot_trace_us"),
+                wall_s=round(wall, 3))
+
+
+def test_annot_at_size_private_repertoire():
+    res = _run_child("_at_size", "x", _child_env("shipped"), timeout=1800)
+    print(res)
+    assert res["contigs"] == 2172 and res["cells"] > 10 ** 12
+
+
+# ---- vdjer --airr ----------------------------------------------------------------------------------------------------------------------
+def _write_inputs(tag, d):
+    from vdjer_amd import synth
+    c = G.Case(tag)
+    rep = synth.make_repertoire(**RECIPES[tag])
+    assert rep.clones == c.clones and rep.v_region == c.v_region
+    os.makedirs(os.path.join(d, "ref"), exist_ok=True)
+    c.pool.write_reads_file(os.path.join(d, "reads.txt"))
+    synth.write_ref_dir(rep, os.path.join(d, "ref"))
+    for fn, codes in (("v_index", c.v_codes), ("j_index", c.j_codes)):          # (the golden's own index files)
+        with open(os.path.join(d, "ref", fn), "w") as f:
+            f.write("".join(f"{int(x)}\t0\n" for x in codes))
+    return rep
+
+
+def _argv(tag):
+    m = G.manifest()
+    info = m["e2e"][tag] if tag in m["e2e"] else m["e2e_chains"][tag]
+    return ["--in", "reads.txt", "--chain", info.get("chain", "IGH"), "--ref-dir", "ref", "--ins", str(info.get("ins", 175)), "--t", "1"] + info["flags"]
+
+
+def _vdjer(tmp, tag, extra, env):
+    exe = os.path.join(ROOT, "vdjer_amd", "vdjer")
+    r = subprocess.run([exe] + _argv(tag) + extra, cwd=tmp, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, env=env)
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert (tmp / "vdj_contigs.fa").read_text() == G.text(f"{tag}.contigs.fa.gz")
+    assert r.stdout == G.text(f"{tag}.sam.gz")
+    assert (tmp / "vdjer.dot").read_text() == G.text(f"{tag}.dot.gz")
+    return r
+
+
+@pytest.mark.parametrize("knobs", KNOBS)
+@pytest.mark.parametrize("tag", E2E)
+def test_vdjer_cli_airr_table(tag, knobs, tmp_path):
+    rep = _write_inputs(tag, str(tmp_path))
+    r = _vdjer(tmp_path, tag, ["--airr", "a.tsv"], _child_env(knobs))
+    lines = r.stderr.splitlines()
+    marks = [l.split("\t")[1] for l in lines if l.startswith("ELAPSED_SECS\t")]
+    assert len(marks) == 17
+    a_at = next(i for i, l in enumerate(lines) if l.startswith("airr: "))
+    assert a_at > max(i for i, l in enumerate(lines) if l.startswith("ELAPSED_SECS\t"))
+    head, rows = A.read_table(tmp_path / "a.tsv")
+    assert head == A.AIRR_COLUMNS
+    fa = G.text(f"{tag}.contigs.fa.gz").splitlines()
+    ids, seqs = [fa[i][1:] for i in range(0, len(fa), 2)], [fa[i + 1] for i in range(0, len(fa), 2)]
+    germs = rep.v_germ + rep.j_germ
+    names = [f"V{i}" for i in range(len(rep.v_germ))] + [f"J{i}" for i in range(len(rep.j_germ))]
+    hits = A.annotate(seqs, germs, ["V"] * len(rep.v_germ) + ["J"] * len(rep.j_germ))
+    assert rows == A.airr_rows(ids, seqs, hits, names)
+    verbatim = 0
+    for row, s in zip(rows, seqs):
+        for cl, v, j in zip(rep.clones, rep.clone_v, rep.clone_j):
+            if cl.find(s) >= 0:
+                verbatim += 1
+                assert f"V{v}" in row[4].split(",") and f"J{j}" in row[6].split(","), row[4:7]
+                assert row[3] == "T"
+                break
+    assert verbatim > 0
+    assert f"{len(ids)} contigs" in lines[a_at] and "0 CIGARs truncated" in lines[a_at]
+
+
+@pytest.mark.parametrize("tag", E2E)
+def test_vdjer_cli_airr_with_quant_and_gpus2(tag, tmp_path):
+    _write_inputs(tag, str(tmp_path))
+    _vdjer(tmp_path, tag, ["--airr", "a.tsv", "--quant", "q.tsv"], _child_env("shipped"))
+    head, rows = A.read_table(tmp_path / "a.tsv")
+    assert head == A.AIRR_COLUMNS + ["expected_count"]
+    qrows = [l.split("\t") for l in (tmp_path / "q.tsv").read_text().splitlines()[1:]]
+    assert [r_[-1] for r_ in rows] == [q[4] for q in qrows] and [r_[0] for r_ in rows] == [q[0] for q in qrows]
+    plain = tmp_path / "one"
+    plain.mkdir()
+    _write_inputs(tag, str(plain))
+    _vdjer(plain, tag, ["--airr", "a.tsv"], _child_env("shipped"))
+    multi = tmp_path / "two"
+    multi.mkdir()
+    _write_inputs(tag, str(multi))
+    _vdjer(multi, tag, ["--gpus", "2", "--airr", "a.tsv"], _child_env("shipped", VDJX_MGPU_ONE_DEVICE="1", VDJX_MGPU_TIMEOUT_S="120"))
+    assert (multi / "a.tsv").read_bytes() == (plain / "a.tsv").read_bytes()
+    assert [r_[:-1] for r_ in rows] == A.read_table(plain / "a.tsv")[1]

@@ -5,7 +5,8 @@ The names follow the reference's call sites: a `Context` owns the 
 stands where build_pre_graph/prune_pre_graph/build_graph2 stand in assemble() (A2:1388-1408);
 `root_score` is score_seq (A2:1103); `window_score` is quick_map_process_contig + coverage_is_valid
 (A2:841-847); `map_emit` is quick_map_process_contig_file (A2:912); `quant` is the RSEM step the reference's workflow runs
-on vdjer.sam afterwards (demo/quant_demo.bash).
+on vdjer.sam afterwards (demo/quant_demo.bash); `germline_load` / `annotate` stand for the IMGT HighV-QUEST run over
+vdj_contigs.fa that the reference's post_process/collect_vdjer_stats.py reads.
 Everything computes on the GPU through libvdjx.so; nothing here falls back to a CPU path.
 """
 from __future__ import annotations
@@ -611,6 +612,45 @@ class Context:
         check(self.L.vdjx_quant(self.h, raw, n, ln, C.byref(prm), _p(counts), C.byref(info)), "vdjx_quant")
         return counts, dict(pairs=int(info.pairs), alignments=int(info.alignments), unique_pairs=int(info.unique_pairs),
                             iterations=int(info.iterations), converged=bool(info.converged), eff_len=float(info.eff_len))
+
+    def germline_load(self, names_or_records):
+        """vdjx_germline_load: a germline FASTA (path) or a list of (FASTA header, sequence) records -> dict(names, classes, skipped).
+        Names, classes and sequences as include/vdjx.h states (vdjer_amd/annot.py); the set stays on the device."""
+        from . import annot
+        recs = annot.read_fasta(names_or_records) if isinstance(names_or_records, str) else list(names_or_records)
+        parsed = [annot.parse_record(h, q) for h, q in recs]
+        names = [x[0] for x in parsed]
+        cls = "".join(x[1] if x[1] in "VJ" else "-" for x in parsed)
+        seqs = [x[2] for x in parsed]
+        off = np.zeros(len(seqs) + 1, np.uint64)
+        off[1:] = np.cumsum([len(q) for q in seqs], dtype=np.uint64)
+        check(self.L.vdjx_germline_load(self.h, "".join(seqs).encode(), _p(off), cls.encode(), len(seqs)), "vdjx_germline_load")
+        skipped = {}
+        for x in parsed:
+            if x[1] not in "VJ":
+                skipped[x[1]] = skipped.get(x[1], 0) + 1
+        self._germ_names = names
+        return dict(names=names, classes=[x[1] for x in parsed], skipped=skipped)
+
+    ANNOT_HIT = np.dtype([("gene", "<i4"), ("score", "<i4"), ("n_tied", "<i4"), ("tied", "<i4", (8,)), ("seq_start", "<i4"),
+                          ("seq_end", "<i4"), ("germ_start", "<i4"), ("germ_end", "<i4"), ("matches", "<i4"), ("mismatches", "<i4"),
+                          ("ins", "<i4"), ("del", "<i4"), ("opens", "<i4"), ("n_runs", "<i4"), ("runs", "<u4", (64,))])
+
+    def annotate(self, contigs, match: int = 2, mismatch: int = 3, gap_open: int = 5, gap_extend: int = 2, min_v_score: int = 40,
+                 min_j_score: int = 20):
+        """vdjx_annotate: V and J hits of every contig against the loaded germlines -> {"v": {field: array}, "j": {...}}, the fields of
+        vdjx_annot_hit (tied: [n, 8], runs: [n, 64])"""
+        if isinstance(contigs, tuple):
+            raw, n, ln = contigs
+        else:
+            if len({len(s_) for s_ in contigs}) > 1:
+                raise VdjxError("vdjx_annotate: contigs of unequal length")
+            raw, n, ln = self.pack_strings(contigs)
+        hv = np.zeros(n, self.ANNOT_HIT)
+        hj = np.zeros(n, self.ANNOT_HIT)
+        prm = _lib.AnnotParams(int(match), int(mismatch), int(gap_open), int(gap_extend), int(min_v_score), int(min_j_score))
+        check(self.L.vdjx_annotate(self.h, raw, n, ln, C.byref(prm), _p(hv), _p(hj)), "vdjx_annotate")
+        return {k: {f: h[f].copy() for f in self.ANNOT_HIT.names} for k, h in (("v", hv), ("j", hj))}
 
     def stat(self, name: str) -> int:
         return int(self.L.vdjx_stat(self.h, name.encode()))

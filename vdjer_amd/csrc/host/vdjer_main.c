@@ -3,9 +3,10 @@
  * vdjh (serial host stage).  Plain C; talks to the GPU only through the C ABI of include/vdjx.h.
  *
  *   vdjer --in <reads> --chain IGH|IGK|IGL --ref-dir <dir> --ins <n> [--t --k --mf --mq --mcs --am --miw --maw
- *         --jc --ws -jext --rf --vk --mrs --rs --ms --e0 --e1 --wo --vf --jf --rms] [--gpus N] [--quant <file>]
+ *         --jc --ws -jext --rf --vk --mrs --rs --ms --e0 --e1 --wo --vf --jf --rms] [--gpus N] [--quant <file>] [--airr <file>]
  * writes ./vdj_contigs.fa and ./vdjer.dot, SAM on stdout, log on stderr; exit 0 on success.  --quant <file>: the contigs' abundances
- * (vdjx_quant, RSEM's isoforms.results columns) into <file> as well.
+ * (vdjx_quant, RSEM's isoforms.results columns) into <file> as well.  --airr <file>: the contigs' V/J annotation (vdjx_annotate against
+ * the germlines of ig_vdj.fa / --vdjf) as an AIRR Rearrangement TSV.
  *
  * --in: a BAM with its .bai (extraction as bam_read.c:264-446, restated over zlib in bamx.c), or -- recognised by its
  * content -- the extracted read pool as text, one read per line in extraction order:
@@ -15,6 +16,7 @@
  * graph build are ONE device call here, so the markers between PRE_PRE_GRAPH1 and POST_BUILD_GRAPH2 follow it back to back.
  */
 #define _GNU_SOURCE
+#include <ctype.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -42,6 +44,7 @@ typedef struct {
 	int anchor_mismatches, threads;
 	int gpus;                              /* --gpus N (not in the reference): the k-mer build sharded over N GPUs of this node */
 	const char* quant;                     /* --quant <file> (not in the reference): the RSEM step of demo/quant_demo.bash, on the device */
+	const char* airr;                      /* --airr <file> (not in the reference): the HighV-QUEST step of post_process/, on the device */
 	int have_chain, have_ref;
 } cli;
 
@@ -55,7 +58,8 @@ static void usage(void) {
 	                "\t--rs <read span distance (default: 35)>\n\t--ms <mate span distance (default: 48)>\n"
 	                "\t--e0/--e1 <start/stop position for contig filtering (default: 52/411)>\n\t--wo <window overlap check size>\n"
 	                "\t--gpus <GPUs of this node to shard the k-mer table over (default: 1)>\n"
-	                "\t--quant <file: expected read pairs per contig, an RSEM isoforms.results table (one GPU only)>\n");
+	                "\t--quant <file: expected read pairs per contig, an RSEM isoforms.results table (one GPU only)>\n"
+	                "\t--airr <file: V/J calls of every contig against ig_vdj.fa, an AIRR Rearrangement table>\n");
 }
 
 static int file_exists(const char* f) { struct stat b; return stat(f, &b) == 0; }
@@ -94,6 +98,7 @@ static int parse(int argc, char** argv, cli* c) {
 		else if (!strcmp(a, "--t")) c->threads = atoi(v);
 		else if (!strcmp(a, "--gpus")) c->gpus = atoi(v);
 		else if (!strcmp(a, "--quant")) c->quant = v;
+		else if (!strcmp(a, "--airr")) c->airr = v;
 		else if (!strcmp(a, "--vf")) snprintf(c->v_anchors, sizeof c->v_anchors, "%s", v);
 		else if (!strcmp(a, "--jf")) snprintf(c->j_anchors, sizeof c->j_anchors, "%s", v);
 		else if (!strcmp(a, "--am")) c->anchor_mismatches = atoi(v);
@@ -457,6 +462,11 @@ typedef struct {
 	const char* quant;                  /* --quant <file>: the table is written after the SAM body */
 	int quant_done;
 	vdjx_quant_info qi;
+	double* qcnt;                       /* its counts (the --airr table's expected_count) */
+	const char* airr;                   /* --airr <file>: written after the SAM body (and the quant table) */
+	const char* vdjf;
+	int airr_done;
+	size_t a_contigs, a_v, a_j, a_prod, a_trunc, a_skip_d, a_skip_other;
 } hook_ud;
 
 static int h_root_score(void* ud, const char* kmers, size_t n, int k, int thr, uint8_t* out) {
@@ -548,6 +558,7 @@ static int quant_table(hook_ud* u, const char* const* ids, const char* contigs, 
 	if (rc) { fprintf(stderr, "vdjx_quant: %s\n", vdjx_last_error()); free(cnt); return rc; }
 	FILE* fp = fopen(u->quant, "w");
 	if (!fp) { fprintf(stderr, "cannot write %s\n", u->quant); free(cnt); return -1; }
+	free(u->qcnt);
 	double sum = 0.0;
 	for (size_t i = 0; i < n; i++) sum += cnt[i];
 	const double eff = u->qi.eff_len;
@@ -556,16 +567,192 @@ static int quant_table(hook_ud* u, const char* const* ids, const char* contigs, 
 		const double tpm = sum > 0.0 ? 1e6 * cnt[i] / sum : 0.0, fpkm = sum > 0.0 && eff > 0.0 ? cnt[i] * 1e9 / (eff * sum) : 0.0;
 		fprintf(fp, "%s\t%s\t%d\t%.2f\t%.2f\t%.2f\t%.2f\t%.2f\n", ids[i], ids[i], len, eff, cnt[i], tpm, fpkm, cnt[i] > 0.0 ? 100.0 : 0.0);
 	}
-	free(cnt);
+	u->qcnt = cnt;
 	if (fclose(fp)) { fprintf(stderr, "cannot write %s\n", u->quant); return -1; }
 	u->quant_done = 1;
 	return 0;
 }
 
+/* ---- --airr: the germline FASTA, the junction-derived fields and the table (the model: include/vdjx.h, vdjx_annotate) ---------------- */
+typedef struct { char* seqs; uint64_t* off; char* cls; char** names; size_t n, cap, bytes, bcap; } germ_set;
+
+static void germ_free(germ_set* g) {
+	for (size_t i = 0; i < g->n; i++) free(g->names[i]);
+	free(g->seqs); free(g->off); free(g->cls); free(g->names);
+	memset(g, 0, sizeof *g);
+}
+
+/* the record's name: the header's first token, or its second '|' field when the token has one; its class: the 4th character of
+ * IG[HKL]* / TR[ABDG]* names, the 1st otherwise */
+static void germ_name(const char* head, char** name, char* cls) {
+	size_t a = 0;
+	while (head[a] && isspace((unsigned char) head[a])) a++;
+	size_t b = a;
+	while (head[b] && !isspace((unsigned char) head[b])) b++;
+	const char* t = head + a;
+	size_t tl = b - a;
+	const char* bar = memchr(t, '|', tl);
+	if (bar) {
+		const char* s2 = bar + 1;
+		const char* e2 = memchr(s2, '|', (size_t) (t + tl - s2));
+		tl = (size_t) ((e2 ? e2 : t + tl) - s2);
+		t = s2;
+	}
+	*name = strndup(t, tl);
+	const char* nm = *name;
+	const int imgt = tl >= 4 && ((nm[0] == 'I' && nm[1] == 'G' && strchr("HKL", nm[2])) || (nm[0] == 'T' && nm[1] == 'R' && strchr("ABDG", nm[2])));
+	*cls = imgt ? nm[3] : tl ? nm[0] : '?';
+}
+
+static int germ_read(const char* path, germ_set* g) {
+	memset(g, 0, sizeof *g);
+	FILE* fp = fopen(path, "r");
+	if (!fp) { fprintf(stderr, "--airr: cannot read the germline FASTA %s\n", path); return -1; }
+	char* line = NULL;
+	size_t lcap = 0;
+	ssize_t ln;
+	while ((ln = getline(&line, &lcap, fp)) >= 0) {
+		if (line[0] == '>') {
+			if (g->n + 2 > g->cap) {
+				g->cap = g->cap ? 2 * g->cap : 256;
+				g->off = (uint64_t*) realloc(g->off, (g->cap + 1) * sizeof(uint64_t));
+				g->cls = (char*) realloc(g->cls, g->cap);
+				g->names = (char**) realloc(g->names, g->cap * sizeof(char*));
+			}
+			g->off[g->n] = g->bytes;
+			germ_name(line + 1, &g->names[g->n], &g->cls[g->n]);
+			g->n++;
+			continue;
+		}
+		if (!g->n) continue;
+		for (ssize_t k = 0; k < ln; k++) {
+			const unsigned char ch = (unsigned char) line[k];
+			if (ch == '.' || isspace(ch)) continue;
+			if (g->bytes + 1 > g->bcap) { g->bcap = g->bcap ? 2 * g->bcap : 65536; g->seqs = (char*) realloc(g->seqs, g->bcap); }
+			g->seqs[g->bytes++] = (char) toupper(ch);
+		}
+	}
+	free(line);
+	fclose(fp);
+	if (!g->off) g->off = (uint64_t*) calloc(1, sizeof(uint64_t));
+	g->off[g->n] = g->bytes;
+	if (!g->seqs) g->seqs = (char*) calloc(1, 1);
+	return 0;
+}
+
+static char codon_aa(const char* c) {
+	static const char* B = "TCAG";
+	static const char* AA = "FFLLSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG";
+	int v = 0;
+	for (int k = 0; k < 3; k++) {
+		const char* q = strchr(B, c[k]);
+		if (!c[k] || !q) return 'X';
+		v = 4 * v + (int) (q - B);
+	}
+	return AA[v];
+}
+
+static void put_aa(FILE* fp, const char* s, size_t n) { for (size_t q = 0; q + 3 <= n; q += 3) fputc(codon_aa(s + q), fp); }
+
+static void put_call(FILE* fp, const vdjx_annot_hit* h, const germ_set* g) {
+	if (h->gene < 0) return;
+	for (int k = 0; k < h->n_tied && k < VDJX_ANNOT_TIED; k++) fprintf(fp, "%s%s", k ? "," : "", g->names[h->tied[k]]);
+}
+
+static void put_cigar(FILE* fp, const vdjx_annot_hit* h, int m) {
+	if (h->gene < 0 || h->score <= 0 || h->n_runs > VDJX_ANNOT_RUNS) return;
+	if (h->seq_start > 1) fprintf(fp, "%dS", h->seq_start - 1);
+	if (h->germ_start > 1) fprintf(fp, "%dN", h->germ_start - 1);
+	for (int k = 0; k < h->n_runs; k++) fprintf(fp, "%u%c", h->runs[k] >> 4, "MID"[h->runs[k] & 15u]);
+	if (h->seq_end < m) fprintf(fp, "%dS", m - h->seq_end);
+}
+
+static void put_hit(FILE* fp, const vdjx_annot_hit* h) {
+	if (h->gene < 0) { fputs("\t\t\t\t\t\t", fp); return; }
+	fprintf(fp, "\t%d", h->score);
+	if (h->score <= 0) { fputs("\t\t\t\t\t", fp); return; }
+	const int d = h->matches + h->mismatches + h->ins + h->del;
+	fprintf(fp, "\t%.4f\t%d\t%d\t%d\t%d", (double) h->matches / d, h->seq_start, h->seq_end, h->germ_start, h->germ_end);
+}
+
+static int airr_table(hook_ud* u, const char* const* ids, const char* contigs, size_t n, int len) {
+	germ_set g;
+	if (germ_read(u->vdjf, &g)) return -1;
+	for (size_t r = 0; r < g.n; r++) {
+		if (g.cls[r] == 'V' || g.cls[r] == 'J') continue;
+		if (g.cls[r] == 'D') u->a_skip_d++; else u->a_skip_other++;
+	}
+	vdjx_annot_hit* hv = (vdjx_annot_hit*) calloc(n + 1, sizeof(vdjx_annot_hit));
+	vdjx_annot_hit* hj = (vdjx_annot_hit*) calloc(n + 1, sizeof(vdjx_annot_hit));
+	const vdjx_annot_params ap = {2, 3, 5, 2, 40, 20};
+	int rc = vdjx_germline_load(u->gx, g.seqs, g.off, g.cls, g.n);
+	if (!rc && n) rc = vdjx_annotate(u->gx, contigs, n, len, &ap, hv, hj);
+	FILE* fp = rc ? NULL : fopen(u->airr, "w");
+	if (rc) fprintf(stderr, "--airr: %s\n", vdjx_last_error());
+	else if (!fp) { fprintf(stderr, "cannot write %s\n", u->airr); rc = -1; }
+	if (fp) {
+		fputs("sequence_id\tsequence\trev_comp\tproductive\tv_call\td_call\tj_call\tsequence_alignment\tgermline_alignment\tjunction\tjunction_aa\t"
+		      "cdr3\tcdr3_aa\tvj_in_frame\tstop_codon\tv_cigar\td_cigar\tj_cigar\tv_score\tv_identity\tv_sequence_start\tv_sequence_end\t"
+		      "v_germline_start\tv_germline_end\tj_score\tj_identity\tj_sequence_start\tj_sequence_end\tj_germline_start\tj_germline_end", fp);
+		fputs(u->quant ? "\texpected_count\n" : "\n", fp);
+		for (size_t i = 0; i < n; i++) {
+			const char* s = contigs + i * (size_t) len;
+			const vdjx_annot_hit *v = hv + i, *j = hj + i;
+			/* the junction: the text after the id's second '_', at its first occurrence in the contig */
+			const char* u1 = strchr(ids[i], '_');
+			const char* jn = u1 ? strchr(u1 + 1, '_') : NULL;
+			jn = jn && jn[1] ? jn + 1 : NULL;
+			const size_t jl = jn ? strlen(jn) : 0;
+			long p = -1;
+			if (jn && jl <= (size_t) len)
+				for (long q = 0; q + (long) jl <= len; q++)
+					if (!memcmp(s + q, jn, jl)) { p = q; break; }
+			const size_t JL = p >= 0 ? jl : 0;
+			const int hasv = v->gene >= 0 && v->score > 0, hasj = j->gene >= 0 && j->score > 0;
+			const int inframe = p >= 0 && hasv && JL % 3 == 0 && (p - (v->seq_start - 1) + (v->germ_start - 1)) % 3 == 0;
+			int stop = 0;
+			if (p >= 0 && hasv && hasj)
+				for (long q = p % 3; q + 2 <= j->seq_end - 1; q += 3)
+					if (q >= v->seq_start - 1 && codon_aa(s + q) == '*') { stop = 1; break; }
+			const int prod = hasv && hasj && inframe && !stop;
+			u->a_contigs++;
+			u->a_v += v->gene >= 0;
+			u->a_j += j->gene >= 0;
+			u->a_prod += prod;
+			u->a_trunc += (v->gene >= 0 && v->n_runs > VDJX_ANNOT_RUNS) + (j->gene >= 0 && j->n_runs > VDJX_ANNOT_RUNS);
+			fprintf(fp, "%s\t%.*s\tF\t%c\t", ids[i], len, s, prod ? 'T' : 'F');
+			put_call(fp, v, &g);
+			fputs("\t\t", fp);
+			put_call(fp, j, &g);
+			fputs("\t\t\t", fp);
+			fprintf(fp, "%.*s\t", (int) JL, p >= 0 ? s + p : "");
+			put_aa(fp, p >= 0 ? s + p : "", JL);
+			const size_t cl = JL >= 6 ? JL - 6 : 0;
+			fprintf(fp, "\t%.*s\t", (int) cl, cl ? s + p + 3 : "");
+			put_aa(fp, cl ? s + p + 3 : "", cl);
+			fprintf(fp, "\t%c\t%c\t", inframe ? 'T' : 'F', stop ? 'T' : 'F');
+			put_cigar(fp, v, len);
+			fputs("\t\t", fp);
+			put_cigar(fp, j, len);
+			put_hit(fp, v);
+			put_hit(fp, j);
+			if (u->quant) fprintf(fp, "\t%.2f", u->qcnt ? u->qcnt[i] : 0.0);
+			fputc('\n', fp);
+		}
+		if (fclose(fp)) { fprintf(stderr, "cannot write %s\n", u->airr); rc = -1; }
+	}
+	free(hv); free(hj);
+	germ_free(&g);
+	if (!rc) u->airr_done = 1;
+	return rc;
+}
+
 static int h_sam_body(void* ud, const char* const* ids, const char* contigs, size_t n, int len, FILE* out) {
 	hook_ud* u = (hook_ud*) ud;
-	const int rc = sam_records(ud, ids, contigs, n, len, out);
-	return rc || !u->quant ? rc : quant_table(u, ids, contigs, n, len);
+	int rc = sam_records(ud, ids, contigs, n, len, out);
+	if (!rc && u->quant) rc = quant_table(u, ids, contigs, n, len);
+	if (!rc && u->airr) rc = airr_table(u, ids, contigs, n, len);
+	return rc;
 }
 
 static void h_status(void* ud, const char* desc) { (void) ud; status(desc); }
@@ -823,7 +1010,7 @@ int main(int argc, char** argv) {
 
 	hook_ud ud;
 	memset(&ud, 0, sizeof ud);
-	ud.gx = gx; ud.r = &rd; ud.p = &c.hp; ud.mg = mg; ud.quant = c.quant;
+	ud.gx = gx; ud.r = &rd; ud.p = &c.hp; ud.mg = mg; ud.quant = c.quant; ud.airr = c.airr; ud.vdjf = c.vdj_fasta;
 	vdjh_hooks hk = {&ud, h_root_score, h_window_score, h_sam_body, vc, nv, jc, nj, h_status};
 	vdjh_stats st;
 	if (vdjh_assemble(&c.hp, &hg, &hk, "vdj_contigs.fa", "vdjer.dot", stdout, &st)) {
@@ -831,6 +1018,7 @@ int main(int argc, char** argv) {
 		return 1;
 	}
 	if (c.quant && !ud.quant_done && quant_table(&ud, NULL, NULL, 0, 0)) return 1;         /* (no contig: the header alone) */
+	if (c.airr && !ud.airr_done && airr_table(&ud, NULL, NULL, 0, 0)) return 1;
 	fprintf(stderr, "num root nodes: %zu\nProcessed roots: %zu\ncontig_candidates: %zu\nwindows scored: %zu valid: %zu\ncontigs: %zu\n",
 	        st.n_roots, st.n_roots_accepted, st.n_contig_candidates, st.n_windows_scored, st.n_windows_valid, st.n_contigs_out);
 	if (mg) {
@@ -860,6 +1048,9 @@ int main(int argc, char** argv) {
 		fprintf(stderr, "quant: %llu pairs placed (%llu once), %llu alignments, %u EM iterations, %s; table in %s\n", (unsigned long long) ud.qi.pairs,
 		        (unsigned long long) ud.qi.unique_pairs, (unsigned long long) ud.qi.alignments, ud.qi.iterations,
 		        ud.qi.converged ? "converged" : "stopped at the iteration limit", c.quant);
+	if (c.airr)
+		fprintf(stderr, "airr: %zu contigs, %zu V called, %zu J called, %zu productive, %zu CIGARs truncated; germline records skipped: %zu D, %zu other; table in %s\n",
+		        ud.a_contigs, ud.a_v, ud.a_j, ud.a_prod, ud.a_trunc, ud.a_skip_d, ud.a_skip_other, c.airr);
 	fflush(stdout);
 	fflush(stderr);
 	/* the outputs are written; the orderly teardown of a context that holds gigabytes (unmapping the workspaces piece by piece, the

@@ -226,6 +226,14 @@ struct vdjx_ctx {
 	void* h_sam_merge = nullptr;      // vdjx_sam_merge: the merged text (page-locked)
 	size_t sam_merge_cap = 0;
 	u32 n_pairs = 0, n_classes = 0;
+	// vdjx_germline_load (vdjx_annot.hip): per class (0 V, 1 J) the records' base codes back to back, each after a reset column
+	uint8_t* d_gl_cols = nullptr;     // [gl_cols]: class V's columns, then class J's
+	size_t gl_cols_cap = 0;
+	bool gl_loaded = false;
+	std::vector<u32> gl_gene[2];      // record index of every germline of the class, in index order
+	std::vector<u64> gl_at[2];        // its reset column in d_gl_cols (its bases follow)
+	std::vector<u32> gl_len[2];
+	u64 gl_class_at[3] = {};          // class c's columns are [gl_class_at[c], gl_class_at[c + 1])
 	std::map<std::string, uint64_t> stats;
 };
 

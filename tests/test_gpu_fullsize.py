@@ -41,6 +41,7 @@ def _full_compare(n_pairs, n_clones, k, mf, mq):
     np.testing.assert_array_equal(g.has_j, og.has_j)
     np.testing.assert_array_equal(g.to_ids, og.to_ids)
     np.testing.assert_array_equal(g.from_ids, og.from_ids)
+    g.recount = (ctx.stat("recount_items"), ctx.stat("recount_instances"))      # (the knob cases below prove their path from these)
     p.free()
     ctx.close()
     return g
@@ -283,7 +284,7 @@ def test_pool_duplication_property_2M_pairs():
 
 
 _KNOB_CASE = r'''
-import sys
+import os, sys
 sys.path.insert(0, %r)
 from tests.test_gpu_fullsize import _full_compare
 from vdjer_amd import api, shard, synth
@@ -297,7 +298,7 @@ pool = synth.make_reads(rep, 120000, noise_frac=0.3, seed=20261002 + 7919)
 vc = np.array(sorted({synth.seq_to_int(a) for a in rep.v_anchors}), dtype=np.uint32)
 jc = np.array(sorted({synth.seq_to_int(a) for a in rep.j_anchors}), dtype=np.uint32)
 half = pool.primary.shape[0] // 2
-dist, out, errs = ThreadDist(2), [None, None], []
+dist, out, errs, recounts = ThreadDist(2), [None, None], [], [None, None]
 def work(r):
     try:
         dist.set_rank(r)
@@ -309,6 +310,7 @@ def work(r):
             pri = np.concatenate([pri, pad])            # equal strides: the union scan order stays the single-pool order
         p = c.pool_load(pri, np.zeros((0, 101), np.uint8), 50)
         out[r] = shard.ShardedHotPath(c, dist, torch.device("cuda", 0)).kmer_build(p, int(sys.argv[1]), int(sys.argv[2]), int(sys.argv[3]))
+        recounts[r] = (c.stat("recount_items"), c.stat("recount_instances"))
         p.free(); c.close()
     except Exception as e:
         errs.append(e); dist.barrier.abort()
@@ -320,6 +322,16 @@ for s in out:
     np.testing.assert_array_equal(s.freq, g.freq); np.testing.assert_array_equal(s.gated_count, g.gated_count)
     np.testing.assert_array_equal(s.to_ids, g.to_ids); np.testing.assert_array_equal(s.from_ids, g.from_ids)
     np.testing.assert_array_equal(s.kmers, g.kmers)
+# VDJX_RC_LEN_BITS: the forced item layout ran, on one GPU and on both ranks.  An item is a run of at most 2^bits instances of consecutive
+# survivors, so instances <= items << bits; with 0 bits every item is one instance (the mirrored walk writes the second record's items
+# itself, one by one as well), which no pool with a chain of two nodes meets at the default of 4 bits
+lb = os.environ.get("VDJX_RC_LEN_BITS")
+if lb is not None:
+    for items, inst in [g.recount] + recounts:
+        print("recount items", items, "instances", inst)
+        assert 0 < items <= inst <= items << int(lb), (lb, items, inst)
+        if lb == "0":
+            assert items == inst, (items, inst)
 print("KNOB_CASE_OK", g.n, g.pre_nodes)
 '''
 

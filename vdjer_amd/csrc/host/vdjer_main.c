@@ -148,9 +148,10 @@ static void* init_thread(void* p) {
 
 static time_t t_start, t_prev;
 static int g_rank;                             /* --gpus N: only rank 0 writes the stage log */
+static int g_times;                            /* VDJX_TIMES (main reads it): more marks, each with its milliseconds */
 static void status(const char* desc) {         /* status.c:22-32 without the /proc dumps */
 	if (g_rank) return;
-	if (getenv("VDJX_TIMES")) {                 /* (diagnostic: milliseconds since the process started, beside the reference's whole seconds) */
+	if (g_times) {                 /* (diagnostic: milliseconds since the process started, beside the reference's whole seconds) */
 		static struct timespec t0;
 		struct timespec t;
 		clock_gettime(CLOCK_MONOTONIC, &t);
@@ -458,7 +459,7 @@ static int load_vregion(const char* path, char*** lines, size_t* n) {
 /* hooks onto libvdjx                                                                          */
 /* ------------------------------------------------------------------------------------------ */
 typedef struct {
-	vdjx_ctx* gx; const reads_t* r; const vdjh_params* p; vdjx_mgpu* mg;
+	vdjx_ctx* gx; const vdjh_params* p; vdjx_mgpu* mg;
 	const char* quant;                  /* --quant <file>: the table is written after the SAM body */
 	int quant_done;
 	vdjx_quant_info qi;
@@ -492,60 +493,21 @@ static int h_window_score(void* ud, const char* windows, size_t n, int len, uint
 	return rc;
 }
 
-static const uint8_t* rec_ptr(const reads_t* r, uint32_t rec) {
-	const size_t sz = 2 * (size_t) r->rl + 1;
-	return rec < r->n_primary ? r->primary + rec * sz : r->secondary + (rec - r->n_primary) * sz;
-}
-
-/* output_mapping, quick_map3.c:152-181: mapped and formatted on the device (vdjx_sam_text); VDJX_SAM_HOST=1 formats the pairs of
- * vdjx_map_emit here instead (the same bytes; kept as the cross-check of the formatting kernel) */
+/* output_mapping, quick_map3.c:152-181: mapped and formatted on the device (vdjx_sam_text) */
 static int sam_records(void* ud, const char* const* ids, const char* contigs, size_t n, int len, FILE* out) {
 	hook_ud* u = (hook_ud*) ud;
-	const reads_t* r = u->r;
-	if (u->mg || !getenv("VDJX_SAM_HOST")) {
-		uint32_t* id_off = (uint32_t*) calloc(n + 1, 4);
-		size_t tot = 0;
-		for (size_t c = 0; c < n; c++) { tot += strlen(ids[c]); id_off[c + 1] = (uint32_t) tot; }
-		char* cat = (char*) malloc(tot + 1);
-		for (size_t c = 0; c < n; c++) memcpy(cat + id_off[c], ids[c], id_off[c + 1] - id_off[c]);
-		const char* text = NULL;
-		uint64_t nb = 0;
-		int rc = u->mg ? vdjx_mgpu_sam_body(u->mg, u->gx, contigs, n, len, cat, id_off, &text, &nb) : vdjx_sam_text(u->gx, contigs, n, len, cat, id_off, &text, &nb);
-		free(cat);
-		free(id_off);
-		if (rc) { fprintf(stderr, "%s: %s\n", u->mg ? "vdjx_mgpu_sam_body" : "vdjx_sam_text", u->mg ? vdjx_mgpu_last_error() : vdjx_last_error()); return rc; }
-		if (nb && fwrite(text, 1, (size_t) nb, out) != (size_t) nb) { fprintf(stderr, "short write of the SAM records\n"); return -1; }
-		return 0;
-	}
-	uint64_t* offs = (uint64_t*) calloc(n + 1, 8);
-	int rc = vdjx_map_emit(u->gx, contigs, n, len, offs, NULL);
-	vdjx_pair* pairs = NULL;
-	if (!rc) {
-		pairs = (vdjx_pair*) malloc((offs[n] + 1) * sizeof(vdjx_pair));
-		rc = vdjx_map_emit(u->gx, contigs, n, len, offs, pairs);
-	}
-	if (rc) { fprintf(stderr, "vdjx_map_emit: %s\n", vdjx_last_error()); free(offs); free(pairs); return rc; }
-	const int rl = r->rl;
-	for (size_t c = 0; c < n; c++) {
-		char cid[256];
-		strncpy(cid, ids[c], 255);
-		cid[255] = 0;
-		for (uint64_t i = offs[c]; i < offs[c + 1]; i++) {
-			const vdjx_pair* q = &pairs[i];
-			const char* name = r->names[q->pair_id];
-			if (name[0] == '@') name++;
-			const int flag1 = 0x1 | 0x2 | (q->rc1 ? 0x10 : 0x20) | 0x40;
-			const int flag2 = 0x1 | 0x2 | (q->rc2 ? 0x10 : 0x20) | 0x80;
-			const uint8_t* r1 = rec_ptr(r, q->rec1);
-			const uint8_t* r2 = rec_ptr(r, q->rec2);
-			fprintf(out, "%s\t%d\t%s\t%d\t255\t%dM\t=\t%d\t%d\t%.*s\t%.*s\n", name, flag1, cid, (int) q->pos1, rl, (int) q->pos2, (int) q->insert,
-			        rl, (const char*) r1 + 1, rl, (const char*) r1 + 1 + rl);
-			fprintf(out, "%s\t%d\t%s\t%d\t255\t%dM\t=\t%d\t%d\t%.*s\t%.*s\n", name, flag2, cid, (int) q->pos2, rl, (int) q->pos1, (int) q->insert,
-			        rl, (const char*) r2 + 1, rl, (const char*) r2 + 1 + rl);
-		}
-	}
-	free(offs);
-	free(pairs);
+	uint32_t* id_off = (uint32_t*) calloc(n + 1, 4);
+	size_t tot = 0;
+	for (size_t c = 0; c < n; c++) { tot += strlen(ids[c]); id_off[c + 1] = (uint32_t) tot; }
+	char* cat = (char*) malloc(tot + 1);
+	for (size_t c = 0; c < n; c++) memcpy(cat + id_off[c], ids[c], id_off[c + 1] - id_off[c]);
+	const char* text = NULL;
+	uint64_t nb = 0;
+	int rc = u->mg ? vdjx_mgpu_sam_body(u->mg, u->gx, contigs, n, len, cat, id_off, &text, &nb) : vdjx_sam_text(u->gx, contigs, n, len, cat, id_off, &text, &nb);
+	free(cat);
+	free(id_off);
+	if (rc) { fprintf(stderr, "%s: %s\n", u->mg ? "vdjx_mgpu_sam_body" : "vdjx_sam_text", u->mg ? vdjx_mgpu_last_error() : vdjx_last_error()); return rc; }
+	if (nb && fwrite(text, 1, (size_t) nb, out) != (size_t) nb) { fprintf(stderr, "short write of the SAM records\n"); return -1; }
 	return 0;
 }
 
@@ -799,7 +761,7 @@ static void on_sigchld(int sig) {
 }
 
 static void report_share(int rank, const reads_t* rd) {
-	if (!getenv("VDJX_REPORT_SHARE")) return;
+	if (!vdjx_env_set("VDJX_REPORT_SHARE")) return;
 	struct rusage ru;
 	getrusage(RUSAGE_SELF, &ru);
 	fprintf(stderr, "share\trank\t%d\trecords\t%zu\tof\t%llu\tpairs\t%u\thost_pool_bytes\t%zu\tmaxrss_kb\t%ld\n", rank, rd->n_primary + rd->n_secondary,
@@ -808,16 +770,18 @@ static void report_share(int rank, const reads_t* rd) {
 
 int main(int argc, char** argv) {
 	t_start = t_prev = time(NULL);
+	g_times = vdjx_times();
 	cli c;
 	if (parse(argc, argv, &c)) return 255;                  /* the reference exits with -1 */
 	/* --gpus N: one process per GPU.  The parent is rank 0; ranks 1..N-1 are forked BEFORE anything touches a GPU.  Every rank reads
 	 * the input and keeps ITS share of the pool (the pairs whose name hashes to it), the ranks deal the k-mer build's slices out to
 	 * each other on the devices, build the graph together, and the others then serve rank 0's scorer calls (vdjx_mgpu.h) while it
 	 * runs the serial traversal. */
-	if (getenv("VDJX_DUMP_SHARE")) {            /* (test hook, no GPU: "rank,nranks" -> that rank's share: its records on stdout, their places on stderr) */
+	const char* dump_share = vdjx_env_str("VDJX_DUMP_SHARE");
+	if (dump_share) {            /* (test hook, no GPU: "rank,nranks" -> that rank's share: its records on stdout, their places on stderr) */
 		int rk = 0, nr = 1;
 		reads_t sh;
-		if (sscanf(getenv("VDJX_DUMP_SHARE"), "%d,%d", &rk, &nr) != 2 || nr < 1 || rk < 0 || rk >= nr || load_reads(&c, &sh, rk, nr, nr > 1)) return 255;
+		if (sscanf(dump_share, "%d,%d", &rk, &nr) != 2 || nr < 1 || rk < 0 || rk >= nr || load_reads(&c, &sh, rk, nr, nr > 1)) return 255;
 		const size_t R = sh.n_primary + sh.n_secondary;
 		fprintf(stderr, "share\t%d\t%d\trl\t%d\trecords\t%zu\ttotal\t%llu\tpairs\t%u\n", rk, nr, sh.rl, R, (unsigned long long) sh.total_records, sh.n_pairs);
 		for (size_t i = 0; i < R; i++) fprintf(stderr, "rec\t%u\t%u\t%u\t%d\t%d\t%s\n", sh.scan_index[i], sh.reg_rank[i], sh.pair_id[i], sh.read_num[i], sh.is_rc[i], sh.names[sh.pair_id[i]]);
@@ -827,15 +791,15 @@ int main(int argc, char** argv) {
 	}
 	int rank = 0;
 	if (c.gpus < 1 || c.gpus > 256) { fprintf(stderr, "--gpus must be in [1,256]\n"); return 255; }
-	const int use_mgpu = c.gpus > 1 || getenv("VDJX_FORCE_MGPU") != NULL;      /* (the variable: a one-rank run of the same code path) */
+	const int use_mgpu = c.gpus > 1 || vdjx_env_set("VDJX_FORCE_MGPU");      /* (the variable: a one-rank run of the same code path) */
 	if (c.quant && use_mgpu) {
 		fprintf(stderr, "--quant runs on one GPU only: it cannot be combined with --gpus N > 1 (or VDJX_FORCE_MGPU)\n");
 		return 255;
 	}
 	/* ranks that share ONE device (the multi-rank tests on a one-GPU box; RCCL refuses two ranks on a device): bytes move through the
 	 * host.  Otherwise rank r drives GPU r and the bytes move by RCCL over xGMI. */
-	const int one_device = getenv("VDJX_MGPU_ONE_DEVICE") != NULL;
-	const char* transport = one_device ? "host" : (getenv("VDJX_MGPU_TRANSPORT") ? getenv("VDJX_MGPU_TRANSPORT") : "rccl");
+	const int one_device = vdjx_env_set("VDJX_MGPU_ONE_DEVICE");
+	const char* transport = one_device ? "host" : (vdjx_env_str("VDJX_MGPU_TRANSPORT") ? vdjx_env_str("VDJX_MGPU_TRANSPORT") : "rccl");
 	int* fds = NULL;
 	if (c.gpus > 1) {
 		fds = (int*) malloc((size_t) c.gpus * (size_t) c.gpus * sizeof(int));
@@ -878,7 +842,7 @@ int main(int argc, char** argv) {
 	memset(&ij, 0, sizeof ij);
 	ij.device = device;
 	pthread_t init_th;
-	const int init_threaded = getenv("VDJX_INIT_SERIAL") == NULL && pthread_create(&init_th, NULL, init_thread, &ij) == 0;
+	const int init_threaded = pthread_create(&init_th, NULL, init_thread, &ij) == 0;
 	reads_t rd;
 	/* an input error between here and the join below must not run exit() and its handlers while the HIP runtime is still coming up on the
 	 * other thread: wait for that thread, then leave with the documented code */
@@ -899,12 +863,12 @@ int main(int argc, char** argv) {
 #undef BAIL
 
 	vdjx_ctx* gx = NULL;
-	if (getenv("VDJX_TIMES")) status("(inputs read)");
+	if (g_times) status("(inputs read)");
 	if (init_threaded) pthread_join(init_th, NULL);
 	else init_thread(&ij);
 	if (ij.rc) { fprintf(stderr, "vdjx_init: %s\n", ij.err); return 1; }
 	gx = ij.gx;
-	if (getenv("VDJX_TIMES")) status("(vdjx_init done)");
+	if (g_times) status("(vdjx_init done)");
 	vdjx_mgpu* mg = NULL;
 	if (use_mgpu) {
 		unsigned char id[VDJX_COMM_ID_BYTES];
@@ -938,13 +902,12 @@ int main(int argc, char** argv) {
 	vdjx_pool* px = NULL;
 	if (!use_mgpu) {
 		VX(vdjx_pool_load(gx, rd.primary, rd.n_primary, rd.secondary, rd.n_secondary, rd.rl, &px));
-		if (getenv("VDJX_TIMES")) status("(pool loaded)");
+		if (g_times) status("(pool loaded)");
 		/* the read index (add_read_info, quick_map3.c:126-149) is begun on the library's index stream and built BESIDE the k-mer build below:
 		 * both only read the packed pool, and nothing needs the index before the traversal's first window (A2:841).  It is ended after
-		 * the build (VDJX_INDEX_SERIAL=1: built here, waited for, as until round 5) */
-		if (getenv("VDJX_INDEX_SERIAL")) VX(vdjx_read_index_build(gx, px, rd.pair_id, rd.read_num, rd.is_rc, rd.reg_rank, rd.n_pairs));
-		else VX(vdjx_read_index_build_begin(gx, px, rd.pair_id, rd.read_num, rd.is_rc, rd.reg_rank, rd.n_pairs));
-		if (getenv("VDJX_TIMES")) status(getenv("VDJX_INDEX_SERIAL") ? "(read index built)" : "(read index begun)");
+		 * the build */
+		VX(vdjx_read_index_build_begin(gx, px, rd.pair_id, rd.read_num, rd.is_rc, rd.reg_rank, rd.n_pairs));
+		if (g_times) status("(read index begun)");
 	} else if (vdjx_mgpu_load(mg, gx, rd.primary, rd.n_primary, rd.rl, rd.scan_index, rd.pair_id, rd.read_num, rd.is_rc, rd.reg_rank, rd.n_pairs, rd.total_records)) {
 		fprintf(stderr, "%s\n", vdjx_mgpu_last_error());
 		return 1;
@@ -974,9 +937,9 @@ int main(int argc, char** argv) {
 	status("PRE_PRE_GRAPH1");                  /* A2:1387 */
 	if (!use_mgpu) {
 		VX(vdjx_kmer_build(gx, px, c.hp.k, c.hp.min_node_freq, c.hp.min_base_quality, &gg));
-		if (getenv("VDJX_TIMES")) status("(k-mer build done)");
+		if (g_times) status("(k-mer build done)");
 		VX(vdjx_read_index_build_end(gx));
-		if (getenv("VDJX_TIMES")) status("(read index ended)");
+		if (g_times) status("(read index ended)");
 	} else {
 		if (vdjx_mgpu_kmer_build(mg, gx, c.hp.k, c.hp.min_node_freq, c.hp.min_base_quality, &gg)) { fprintf(stderr, "%s\n", vdjx_mgpu_last_error()); return 1; }
 		if (rank == 0) fprintf(stderr, "k-mer table sharded over %d GPUs (%s): %llu bytes sent by rank 0 so far\n", c.gpus, transport, (unsigned long long) vdjx_mgpu_bytes_sent(mg));
@@ -1010,7 +973,7 @@ int main(int argc, char** argv) {
 
 	hook_ud ud;
 	memset(&ud, 0, sizeof ud);
-	ud.gx = gx; ud.r = &rd; ud.p = &c.hp; ud.mg = mg; ud.quant = c.quant; ud.airr = c.airr; ud.vdjf = c.vdj_fasta;
+	ud.gx = gx; ud.p = &c.hp; ud.mg = mg; ud.quant = c.quant; ud.airr = c.airr; ud.vdjf = c.vdj_fasta;
 	vdjh_hooks hk = {&ud, h_root_score, h_window_score, h_sam_body, vc, nv, jc, nj, h_status};
 	vdjh_stats st;
 	if (vdjh_assemble(&c.hp, &hg, &hk, "vdj_contigs.fa", "vdjer.dot", stdout, &st)) {
@@ -1056,7 +1019,7 @@ int main(int argc, char** argv) {
 	/* the outputs are written; the orderly teardown of a context that holds gigabytes (unmapping the workspaces piece by piece, the
 	 * runtime's own exit handlers) took 160 ms of a 530 ms run at 400 k pairs -- the process ends instead and the driver reclaims what
 	 * it held, as for any process.  VDJX_CLEAN_EXIT=1 keeps the teardown (leak checks). */
-	if (!getenv("VDJX_CLEAN_EXIT")) _exit(0);
+	if (!vdjx_env_set("VDJX_CLEAN_EXIT")) _exit(0);
 	vdjx_graph_free(gg);
 	if (mg) vdjx_mgpu_free(mg);
 	vdjx_pool_free(px);

@@ -3,6 +3,7 @@
 #include "vdjh.h"
 #include <pthread.h>
 #include "sph.h"
+#include "../vdjx_env.h"
 
 #include <math.h>
 #include <stdarg.h>
@@ -504,7 +505,7 @@ static int traverse_roots(const vdjh_params* p, const vdjh_hooks* h, hnode** roo
 	trav_job job;
 	memset(&job, 0, sizeof job);
 	job.p = p; job.h = h; job.roots = roots; job.accepted = accepted; job.nroots = nroots;
-	job.progress = getenv("VDJH_PROGRESS") != NULL;
+	job.progress = vdjx_env_set("VDJH_PROGRESS");
 	job.per_root = (wincoll*) calloc(nroots + 1, sizeof(wincoll));
 	pthread_t* th = (pthread_t*) calloc((size_t) nthreads, sizeof(pthread_t));
 	int started = 0;
@@ -578,8 +579,9 @@ int vdjh_assemble(const vdjh_params* p, const vdjh_graph* g, const vdjh_hooks* h
 	uint8_t* valid = NULL;
 	char* wbuf = NULL;
 	if (nroots && h->root_score(h->ud, rk, nroots, p->k, p->min_source_homology_score, accepted_root)) { set_err("root scorer failed"); goto done; }
-	if (getenv("VDJH_ROOT_LOG")) {       /* (diagnostic: "<root k-mer>\t<verdict>" in dispatch order; bench.py sets it beside the reference's own log) */
-		FILE* rl = fopen(getenv("VDJH_ROOT_LOG"), "w");
+	const char* root_log = vdjx_env_str("VDJH_ROOT_LOG");
+	if (root_log) {       /* (diagnostic: "<root k-mer>\t<verdict>" in dispatch order; bench.py sets it beside the reference's own log) */
+		FILE* rl = fopen(root_log, "w");
 		if (rl) {
 			for (size_t i = 0; i < nroots; i++) { fwrite(rk + i * (size_t) p->k, 1, (size_t) p->k, rl); fprintf(rl, "\t%d\n", (int) accepted_root[i]); }
 			fclose(rl);

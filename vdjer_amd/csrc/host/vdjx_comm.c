@@ -2,6 +2,7 @@
 #define _GNU_SOURCE
 #include "vdjx_comm.h"
 #include "vdjx_a2a_plan.h"
+#include "../vdjx_env.h"
 
 #include <errno.h>
 #include <fcntl.h>
@@ -99,12 +100,14 @@ static int connect_to(const char* path, double deadline_s) {
 	}
 }
 
+/* VDJX_MGPU_TIMEOUT_S (whole seconds): how long a rank waits for another, at the rendezvous and in every exchange after it */
+static double timeout_s(long long dflt) { return (double) vdjx_env_num("VDJX_MGPU_TIMEOUT_S", dflt, 1, 7 * 86400); }
+
 int vdjx_comm_rendezvous(const char* dir, int me, int G, int mesh, int* fds_row) {
 	for (int j = 0; j < G; j++) fds_row[j] = -1;
 	if (G <= 1) return 0;
 	if (mesh && G > VDJX_COMM_MAX_MESH) return fail(-1, "the host transport takes up to %d ranks", VDJX_COMM_MAX_MESH);
-	double deadline = 120;
-	if (getenv("VDJX_MGPU_TIMEOUT_S") && atof(getenv("VDJX_MGPU_TIMEOUT_S")) > 0) deadline = atof(getenv("VDJX_MGPU_TIMEOUT_S"));
+	const double deadline = timeout_s(120);
 	(void) mkdir(dir, 0700);
 	char path[108];
 	int lfd = -1, expect = 0;
@@ -225,8 +228,7 @@ int vdjx_comm_init(const char* transport, int rank, int G, int device, const int
 	c->rank = rank; c->G = G; c->device = device; c->is_rccl = is_rccl;
 	c->fds = (int*) malloc((size_t) G * sizeof(int));
 	for (int j = 0; j < G; j++) c->fds[j] = fds_row ? fds_row[j] : -1;
-	c->timeout_s = 600;
-	if (getenv("VDJX_MGPU_TIMEOUT_S") && atof(getenv("VDJX_MGPU_TIMEOUT_S")) > 0) c->timeout_s = atof(getenv("VDJX_MGPU_TIMEOUT_S"));
+	c->timeout_s = timeout_s(600);
 	hipError_t e = hipSetDevice(device);
 	if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
 	if (e != hipSuccess) { fail(E_HIP, "rank %d, device %d: %s", rank, device, hipGetErrorString(e)); free(c->fds); free(c); return E_HIP; }

@@ -102,7 +102,7 @@ int vdjx_mgpu_init(vdjx_comm* cm, int device, vdjx_mgpu** out) {
 	vdjx_mgpu* m = (vdjx_mgpu*) calloc(1, sizeof *m);
 	if (!m) return fail(VDJX_EINVAL, "out of memory");
 	m->cm = cm; m->rank = vdjx_comm_rank(cm); m->nranks = vdjx_comm_size(cm); m->device = device;
-	m->timing = getenv("VDJX_TIMES") != NULL;
+	m->timing = vdjx_times();
 	*out = m;
 	return 0;
 }
@@ -197,6 +197,9 @@ done:
 /* ------------------------------------------------------------------------------------------------------------------ */
 /* the k-mer build                                                                                                     */
 /* ------------------------------------------------------------------------------------------------------------------ */
+/* a lone rank skips the exchanges that would hand it its own data back (VDJX_MGPU_SELF_COLLECTIVES=1 keeps them: the one-rank RCCL test) */
+static int lone_rank(int G) { return G == 1 && !vdjx_env_set("VDJX_MGPU_SELF_COLLECTIVES"); }
+
 static int kmer_build_any(vdjx_mgpu* m, vdjx_ctx* ctx, const vdjx_pool* pool, int k, int mf, int mq, uint64_t rec_stride, const uint32_t* d_scan, uint64_t total_records, vdjx_graph** out) {
 	int rc = 0;
 	const int G = m->nranks, me = m->rank;
@@ -210,8 +213,7 @@ static int kmer_build_any(vdjx_mgpu* m, vdjx_ctx* ctx, const vdjx_pool* pool, in
 	if (!send_counts || !recv_counts || !q_out || !q_in || !eq || !meta) { rc = fail(VDJX_EINVAL, "out of memory"); goto done; }
 	const size_t W0 = vdjx_shard_record_bytes(0), W1 = vdjx_shard_record_bytes(1), W2 = vdjx_shard_record_bytes(2), W3 = vdjx_shard_record_bytes(3);
 	HIPC(hipSetDevice(m->device));
-	/* a lone rank skips the exchanges that would hand it its own data back (VDJX_MGPU_SELF_COLLECTIVES=1 keeps them: the one-rank RCCL test) */
-	const int alone = G == 1 && getenv("VDJX_MGPU_SELF_COLLECTIVES") == NULL;
+	const int alone = lone_rank(G);
 	lap_start(m);
 	if (d_scan) VX(vdjx_shard_begin_share(ctx, pool, k, mf, mq, me, G, d_scan, total_records, &sh));
 	else VX(vdjx_shard_begin(ctx, pool, k, mf, mq, me, G, rec_stride, &sh));
@@ -380,7 +382,7 @@ static int do_window_score(vdjx_mgpu* m, vdjx_ctx* ctx, const char* windows, siz
 		}
 	WSG(WS_A, sum64(send_counts, G) * 8 + 16, &d_send);
 	VX(vdjx_window_pairs_fetch(ctx, send_ids, n, d_send));
-	if (G == 1 && !getenv("VDJX_MGPU_SELF_COLLECTIVES")) d_recv = d_send;          /* (a lone rank's lists are the union already) */
+	if (lone_rank(G)) d_recv = d_send;          /* (a lone rank's lists are the union already) */
 	else {
 		WSG(WS_B, sum64(recv_counts, G) * 8 + 16, &d_recv);
 		CX(vdjx_comm_a2av(m->cm, d_send, send_counts, d_recv, recv_counts, 8));
@@ -427,8 +429,7 @@ static int do_sam(vdjx_mgpu* m, vdjx_ctx* ctx, const char* contigs, size_t n, in
 	CX(vdjx_comm_allgather_host(m->cm, cnt, n * 8, all_cnt));
 	for (size_t i = 0; i < n; i++) { uint64_t s = 0; for (int r = 0; r < G; r++) s += all_cnt[(size_t) r * n + i]; cnt[i] = s; }
 	lap(m, "sam: counting pass");
-	uint64_t budget = 8u << 20;
-	if (getenv("VDJX_MGPU_SAM_PAIRS") && atoll(getenv("VDJX_MGPU_SAM_PAIRS")) > 0) budget = (uint64_t) atoll(getenv("VDJX_MGPU_SAM_PAIRS"));
+	const uint64_t budget = (uint64_t) vdjx_env_num("VDJX_MGPU_SAM_PAIRS", 8 << 20, 1, 1ll << 40);
 	for (size_t a = 0; a < n;) {
 		size_t b = a;
 		uint64_t in_run = 0;

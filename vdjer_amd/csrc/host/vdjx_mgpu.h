@@ -20,6 +20,10 @@
 
 #include "../../../include/vdjx.h"
 #include "vdjx_comm.h"
+#include "../vdjx_env.h"
+
+/* VDJX_TIMES: the command line marks more stages, each with its milliseconds, and every rank's driver reports its phases */
+static inline int vdjx_times(void) { return vdjx_env_set("VDJX_TIMES"); }
 
 #ifdef __cplusplus
 extern "C" {

@@ -247,7 +247,7 @@ __global__ __launch_bounds__(64) void k_an_trace(const char* __restrict__ contig
 }
 
 static u32 an_pairs_knob() {
-	static const u32 v = getenv("VDJX_ANNOT_PAIRS") && atol(getenv("VDJX_ANNOT_PAIRS")) > 0 ? (u32) atol(getenv("VDJX_ANNOT_PAIRS")) : AN_PAIRS;
+	static const u32 v = (u32) vdjx_env_num("VDJX_ANNOT_PAIRS", AN_PAIRS, 1, 0xFFFFFFFFll);
 	return v;
 }
 

@@ -12,6 +12,7 @@
 #include <utility>
 
 #include "../../include/vdjx.h"
+#include "vdjx_env.h"
 
 typedef unsigned long long u64;
 typedef unsigned int u32;
@@ -209,11 +210,6 @@ struct vdjx_ctx {
 	uint32_t* root_pending_ids = nullptr;
 	uint8_t* root_pending_out = nullptr;
 	hipEvent_t ev_root_done = nullptr;
-	// round 6: a begun root scoring runs on a stream and out of a workspace of its own -- its kernels are small (tens of thousands of roots,
-	// a wave per seed hit) and wait on dependent loads; the window scorer's kernels, which do not need the verdicts, run beside them
-	hipStream_t root_stream = nullptr;
-	hipEvent_t ev_root_go = nullptr;
-	vdjx_arena root_arena;
 	// SAM text (vdjx_sam_text): read names by pair id on the device, the text buffers
 	char* d_sam_names = nullptr;
 	u64* d_sam_noff = nullptr;
@@ -308,8 +304,7 @@ struct vdjx_prof_scope {
 	vdjx_ctx* c;
 	const char* name;
 	hipEvent_t a = nullptr, b = nullptr;
-	hipStream_t st = nullptr;                             // the stream the launch goes to (null: the context's)
-	vdjx_prof_scope(vdjx_ctx* ctx, const char* nm, hipStream_t stream = nullptr);      // ctx == nullptr: nothing is bracketed (another THREAD's launches)
+	vdjx_prof_scope(vdjx_ctx* ctx, const char* nm);      // ctx == nullptr: nothing is bracketed (another THREAD's launches)
 	~vdjx_prof_scope();
 };
 void vdjx_prof_collect(vdjx_ctx* ctx, bool force = true);
@@ -319,7 +314,7 @@ struct vdjx_laps {
 	vdjx_ctx* c;
 	bool on;
 	std::chrono::steady_clock::time_point t;
-	explicit vdjx_laps(vdjx_ctx* ctx) : c(ctx) { static const bool e = getenv("VDJX_LAPS") != nullptr; on = e; if (on) t = std::chrono::steady_clock::now(); }
+	explicit vdjx_laps(vdjx_ctx* ctx) : c(ctx) { static const bool e = vdjx_env_set("VDJX_LAPS"); on = e; if (on) t = std::chrono::steady_clock::now(); }
 	void mark(const char* name) {
 		if (!on) return;
 		const auto n = std::chrono::steady_clock::now();

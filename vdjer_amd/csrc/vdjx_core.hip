@@ -52,8 +52,6 @@ extern "C" int vdjx_init(int device, vdjx_ctx** out) {
 	if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_plan, hipEventDisableTiming);
 	if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_root_done, hipEventDisableTiming);
 	if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->ri_stream, hipStreamNonBlocking);
-	if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->root_stream, hipStreamNonBlocking);
-	if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_root_go, hipEventDisableTiming);
 	if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_ri_go, hipEventDisableTiming);
 	if (e == hipSuccess) e = hipHostMalloc(&c->h_pin, VDJX_HPIN_BYTES, hipHostMallocDefault);
 	if (e != hipSuccess) { delete c; vdjx_set_error("hipStreamCreate: %s", hipGetErrorString(e)); return VDJX_EHIP; }
@@ -112,9 +110,6 @@ extern "C" void vdjx_shutdown(vdjx_ctx* c) {
 	if (c->ri_stream) { (void) hipStreamSynchronize(c->ri_stream); (void) hipStreamDestroy(c->ri_stream); }
 	if (c->ev_ri_go) (void) hipEventDestroy(c->ev_ri_go);
 	c->ri_arena.release(true);
-	if (c->root_stream) { (void) hipStreamSynchronize(c->root_stream); (void) hipStreamDestroy(c->root_stream); }
-	if (c->ev_root_go) (void) hipEventDestroy(c->ev_root_go);
-	c->root_arena.release(true);
 	free_dev(c->d_vbits); free_dev(c->d_jbits); free_dev(c->d_anchor_tmp);
 	free_dev(c->d_vtext); free_dev(c->d_line_off); free_dev(c->d_seed_code); free_dev(c->d_seed_pos);
 	free_dev(c->d_ri_tab); free_dev(c->d_ri_start); free_dev(c->d_ri_recs); free_dev(c->d_ri_csr8); free_dev(c->d_ri_csr_pair);
@@ -161,10 +156,8 @@ extern "C" int vdjx_trim(vdjx_ctx* c) {
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	HIP_TRY(hipStreamSynchronize(c->copy_stream));
 	if (c->pairs_stream) HIP_TRY(hipStreamSynchronize(c->pairs_stream));
-	if (c->root_stream) HIP_TRY(hipStreamSynchronize(c->root_stream));
 	c->arena.release(false);
 	c->ri_arena.release(false);
-	c->root_arena.release(false);
 	if (!c->live_shard) c->shard_arena.release(false);
 	c->blocks.drop();
 	// the scorers' result buffers (grow-only between calls: the pair lists of the last window batch, the mapped pairs and the SAM
@@ -217,7 +210,7 @@ extern "C" int vdjx_device_copy(vdjx_ctx* c, void* d_dst, const void* d_src, siz
 	return VDJX_OK;
 }
 
-static bool arena_trace() { static const bool t = getenv("VDJX_ARENA_TRACE") != nullptr; return t; }     // diagnostic: every growth of a workspace
+static bool arena_trace() { static const bool t = vdjx_env_set("VDJX_ARENA_TRACE"); return t; }     // diagnostic: every growth of a workspace
 
 // back the range up to `upto` bytes: pieces of at most 4 GB (a single 38 GB allocation is what took seconds)
 bool vdjx_arena::grow(size_t upto) {
@@ -261,7 +254,7 @@ void* vdjx_arena::alloc(size_t bytes) {
 		// one range, if the runtime manages virtual memory on this device (VDJX_ARENA_CHUNKS=1: the chunk list, for comparison)
 		mode = 2;
 		int dev = 0, vmm = 0;
-		static const bool force_chunks = getenv("VDJX_ARENA_CHUNKS") != nullptr;
+		static const bool force_chunks = vdjx_env_set("VDJX_ARENA_CHUNKS");
 		if (!force_chunks && hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&vmm, hipDeviceAttributeVirtualMemoryManagementSupported, dev) == hipSuccess && vmm) {
 			hipMemAllocationProp prop = {};
 			prop.type = hipMemAllocationTypePinned;
@@ -346,21 +339,20 @@ extern "C" int vdjx_sync(vdjx_ctx* c) {
 // ----------------------------------------------------------------------------------------------
 // profiling
 // ----------------------------------------------------------------------------------------------
-vdjx_prof_scope::vdjx_prof_scope(vdjx_ctx* ctx, const char* nm, hipStream_t stream) : c(ctx), name(nm), st(stream) {
+vdjx_prof_scope::vdjx_prof_scope(vdjx_ctx* ctx, const char* nm) : c(ctx), name(nm) {
 	if (!c || !c->profiling) return;
-	if (!st) st = c->stream;
 	if (!c->prof_only.empty() && c->prof_only != nm) return;          // (vdjx_profile_only: one scope is bracketed, the others cost nothing)
 	auto take = [&](hipEvent_t* e) {
 		if (!c->ev_free.empty()) { *e = c->ev_free.back(); c->ev_free.pop_back(); return true; }
 		return hipEventCreate(e) == hipSuccess;
 	};
 	if (!take(&a) || !take(&b)) { a = b = nullptr; return; }
-	(void) hipEventRecord(a, st);
+	(void) hipEventRecord(a, c->stream);
 }
 
 vdjx_prof_scope::~vdjx_prof_scope() {
 	if (!c || !c->profiling || !a) return;
-	(void) hipEventRecord(b, st);
+	(void) hipEventRecord(b, c->stream);
 	c->prof_pending.push_back({name, a, b});
 }
 
@@ -896,7 +888,7 @@ static void pack_launch(vdjx_ctx* c, hipStream_t st, vdjx_pool* p, const uint8_t
 	else hipLaunchKernelGGL((k_pool_pack<false, false>), grid, dim3(PACK_RECS), lds, st, d_ascii, n, p->rl, rec0, p->d_bases, p->d_nmask, p->d_lowq, q, p->qstride, d_bad);
 }
 
-static bool sym_wanted() { static const bool on = getenv("VDJX_NO_SYM") == nullptr; return on; }
+static bool sym_wanted() { static const bool on = !vdjx_env_set("VDJX_NO_SYM"); return on; }      // (the one reader: no pool is marked sym, so no build takes the couples)
 
 static int pool_finish(vdjx_ctx* c, vdjx_pool* p, u32* d_bad, vdjx_pool** out, bool fwd = false) {
 	u32* both = (u32*) c->h_pin;

@@ -12,11 +12,9 @@
 //   K2c k_part_records /   LDS-staged counting sort per round: tuples {key_lo, key_hi, inst|gated} written as
 //       k_part_tuples      coalesced bucket runs (256 coarse buckets, then 128 fine ones inside each; large pools:
 //                          2^(T-10) coarse, a counting pass, 1024 fine); positions inside a bucket from cursor bumps
-//   K3a k_bucket_aggregate LDS open-addressing table per bucket: gated count + first instance per
-//                          distinct k-mer; keys with count >= max(mf,2) become candidates, their
-//                          tuples are compacted in place (noise singletons die here)
-//   K3b k_bucket_finalize  direct-indexed LDS arrays per bucket: distinct-read flag, quality sums
-//                          (only for low-count keys, see TLOW), ungated recount -> survivors
+//   K3  k_gated_reduce     LDS open-addressing table per bucket: gated count, first instance, distinct-read flag and (for low-count
+//                          keys, see TLOW) quality sums per distinct k-mer -> survivors; sharded: k_gated_local + k_bucket_merge
+//   K4  k_walk_items / k_recount   the ungated recount: runs of surviving k-mers along the records, counted per survivor range
 //   K5  k_surv_table / k_graph_edges / k_node_flags   survivor lookup table, ordered edges, V/J flags
 #include "vdjx_common.h"
 
@@ -27,17 +25,10 @@
 #include <stdlib.h>
 
 #define HIST_THREADS 512
-#define K3_THREADS 512
-#define K3_SLOTS 1024u              // LDS table slots per sub-pass of k_bucket_aggregate (28 KB with u32 key_hi): ~100 distinct gated k-mers per bucket
-#define LOCAL_SLOTS 2048u           // k_bucket_local keeps every distinct k-mer of the bucket, gated or not (~600)
-#define K3_UNR 8
+#define HIST_BLOCKS 512u            // workgroups of k_gated_hist at most (4,096 records each below that)
+#define LOCAL_SLOTS 2048u           // k_gated_local keeps every distinct k-mer of the bucket, gated or not (~600)
 #define K3_SUB_TUPLES g_sub_tuples  // first split only for very large buckets: hot k-mers make buckets long, not wide (an overflow splits further)
 __device__ u32 g_sub_tuples = 262144u;
-#define K3B_THREADS 256
-#define K3B_CH 1024u                // candidates per chunk
-#define K3B_A 128u                  // quality-sum rows per round
-#define K3B_KW 25u                  // u32 words per row (2 x u16 sums each), k <= 50
-#define K3B_Q 1536u                 // remembered low-count instances per chunk (more: the quality rounds rescan the bucket)
 #define NONE32 0xFFFFFFFFu
 #define INST_MASK 0x7FFFFFFFu
 
@@ -112,6 +103,7 @@ __global__ __launch_bounds__(1024) void k_bucket_scan(const u32* __restrict__ bu
 #define PART_THREADS 1024
 #define PART_LDS_BYTES 131072
 #define PART_MAXB 1024
+#define PART_SLICES 8u              // workgroups per coarse bucket in the second pass (k_seg_hist_g, k_part_tuples_g)
 
 // exclusive scan of cnt[0..n) (n <= 1024) into base[0..n], base[n] = total; all PART_THREADS threads call it.
 // Two counts per thread, DPP prefix sums inside the waves, one wave for the wave totals: three barriers instead of twenty.
@@ -151,7 +143,7 @@ __global__ void k_init_cursors(const u32* __restrict__ bucket_start, u32 n, u32 
 // ----------------------------------------------------------------------------------------------
 // K3a: LDS hash aggregation per bucket
 // ----------------------------------------------------------------------------------------------
-template <typename THI, u32 SLOTS = K3_SLOTS>
+template <typename THI, u32 SLOTS>
 __device__ inline int lds_insert(u64* s_klo, THI* s_khi, u64 lo, THI hi, u32 h) {
 	const THI EMPTY = (THI) ~(THI) 0, LOCKED = (THI) (EMPTY - 1);
 	u32 slot = h & (SLOTS - 1);
@@ -178,7 +170,7 @@ __device__ inline int lds_insert(u64* s_klo, THI* s_khi, u64 lo, THI hi, u32 h) 
 	return -1;
 }
 
-template <typename THI, u32 SLOTS = K3_SLOTS>
+template <typename THI, u32 SLOTS>
 __device__ inline int lds_lookup(const u64* s_klo, const THI* s_khi, u64 lo, THI hi, u32 h) {
 	const THI EMPTY = (THI) ~(THI) 0;
 	u32 slot = h & (SLOTS - 1);
@@ -242,7 +234,6 @@ __device__ inline u64 vdjx_clean_offsets(u64 bad, int k, int P) {
 // The offset of a listed instance differs from lane to lane: the k-mer is cut out with vdjx_kmer_at_lane (vdjx_common.h: the plain
 // 128-bit shift by a per-lane amount gave wrong k-mers on gfx950 when the amounts of a wave lay on both sides of 64).
 #define GL_WAVE_BYTES 3072u         // per wave: 64 x 16-byte packed bases, 1024 x 2-byte entries (lane << 6 | offset)
-#define GL_WAVE_BYTES_SYM GL_WAVE_BYTES
 
 // long reads (W words per read, vdjx_pool): a lane's record in LDS is W + 2 words (two zero words behind it: the k-mer extraction
 // reads three words from the k-mer's first), entries are lane << 8 | offset
@@ -306,7 +297,7 @@ __global__ __launch_bounds__(HIST_THREADS) void k_gated_hist(const u64* __restri
 	for (u32 i = threadIdx.x; i < NB; i += HIST_THREADS) hist[i] = 0;
 	__syncthreads();
 	static_assert(!(LONG && SYM), "SYM is the short-read form");
-	uint8_t* wv = (uint8_t*) (hist + NB) + (threadIdx.x >> 6) * (LONG ? GL_WAVE_BYTES_LONG : SYM ? GL_WAVE_BYTES_SYM : GL_WAVE_BYTES);
+	uint8_t* wv = (uint8_t*) (hist + NB) + (threadIdx.x >> 6) * (LONG ? GL_WAVE_BYTES_LONG : GL_WAVE_BYTES);
 	ulonglong2* wb = (ulonglong2*) wv;
 	u64* wrow = (u64*) wv;
 	uint16_t* wl = (uint16_t*) (wv + (LONG ? 64u * GL_ROW_LONG * 8u : 1024u));
@@ -382,7 +373,7 @@ __global__ __launch_bounds__(PART_THREADS) void k_part_records_g(const u64* __re
 	const u32 mask = nbk - 1;
 	const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
 	static_assert(!(LONG && SYM), "SYM is the short-read form");
-	uint8_t* wv = smem + wave * (LONG ? GL_WAVE_BYTES_LONG : SYM ? GL_WAVE_BYTES_SYM : GL_WAVE_BYTES);
+	uint8_t* wv = smem + wave * (LONG ? GL_WAVE_BYTES_LONG : GL_WAVE_BYTES);
 	ulonglong2* wb = (ulonglong2*) wv;
 	u64* wrow = (u64*) wv;
 	uint16_t* wl = (uint16_t*) (wv + (LONG ? 64u * GL_ROW_LONG * 8u : 1024u));
@@ -2534,11 +2525,6 @@ struct PersistAlloc {
 
 struct PoolView { const u64* bases; const u64* nmask; vdjx_qrows quals; int rl; int ob; };
 
-size_t tune(const char* name, size_t dflt) {      // undocumented tuning knobs for experiments (profiles/README.md)
-	const char* v = getenv(name);
-	return v && atol(v) > 0 ? (size_t) atol(v) : dflt;
-}
-
 // ==============================================================================================
 // round-2 host driver
 // ==============================================================================================
@@ -2557,10 +2543,10 @@ struct SurvivorsG {
 
 inline u32 ceil_log2_u64(u64 x) { u32 b = 0; while ((1ull << b) < x) b++; return b; }
 
-// VDJX_SYNC_DEBUG=1: wait for the stream after every stage and say so (which launch faulted)
+// VDJX_SYNC_DEBUG=1: wait for the stream after every stage and say so (which launch faulted); the stages check more and say more
+static bool sync_debug() { static const bool on = vdjx_env_set("VDJX_SYNC_DEBUG"); return on; }
 static void dbg_sync(vdjx_ctx* c, const char* what) {
-	static const bool on = getenv("VDJX_SYNC_DEBUG") != nullptr;
-	if (!on) return;
+	if (!sync_debug()) return;
 	const hipError_t e = hipStreamSynchronize(c->stream);
 	fprintf(stderr, "[vdjx] %s: %s\n", what, hipGetErrorString(e));
 }
@@ -2572,17 +2558,19 @@ struct GatedHist { u32 HB = 0, NBH = 0, N = 0; u32* hstart = nullptr; bool sym =
 // sym: the pool's records come in couples (record, its reverse complement: vdjx_pool::sym) and k is odd: the kernels walk the couples
 // and move one tuple per pair of mirrored instances (k_gated_hist SYM)
 static bool build_sym(const vdjx_pool* pool, int k) {
-	static const bool on = getenv("VDJX_NO_SYM") == nullptr;
-	return on && pool->sym && pool->W == 2 && (k & 1) && pool->n_records % 2 == 0;
+	return pool->sym && pool->W == 2 && (k & 1) && pool->n_records % 2 == 0;      // (VDJX_NO_SYM: no pool is marked sym, vdjx_core.hip)
 }
+// VDJX_NO_SYM_WALK: phase B walks every record even where phase A went over the couples
+static bool sym_walk_wanted() { static const bool on = !vdjx_env_set("VDJX_NO_SYM_WALK"); return on; }
+// gated tuples per bucket where the caller names no size: about a third are distinct k-mers (RD_SLOTS).  The histogram and the cut ask here
+static size_t gated_bucket_default() { static const size_t v = (size_t) vdjx_env_num("VDJX_GATED_BUCKET", 3072, 1, 1ll << 32); return v; }
 template <typename A>
 int stage_gated_hist(vdjx_ctx* c, A& db, const vdjx_pool* pool, int k, size_t per_bucket, u64 geometry_instances, GatedHist* gh, bool sym = false) {
 	hipStream_t st = c->stream;
 	const size_t R = sym ? pool->n_records / 2 : pool->n_records;           // (sym: couples)
 	const int P = pool->rl - k + 1;
 	const u64 NI = geometry_instances ? geometry_instances : (u64) R * (u64) P;
-	static const size_t dflt = tune("VDJX_GATED_BUCKET", 3072);     // gated tuples per bucket: about a third are distinct k-mers (RD_SLOTS)
-	const size_t per = per_bucket ? per_bucket : dflt;
+	const size_t per = per_bucket ? per_bucket : gated_bucket_default();
 	// histogram resolution: every bucket count the build could choose is a prefix of it (<= 2^15: 128 KB of LDS; 2^14 for long reads,
 	// whose waves stage 5.6 KB of records each beside the histogram: 2^15 asked for 173 KB and every build of more than ~1 M pairs of
 	// 2 x 100 bp failed -- the parity tests' pools were too small to get there; profiles/longreads.py now runs them at size)
@@ -2590,9 +2578,12 @@ int stage_gated_hist(vdjx_ctx* c, A& db, const vdjx_pool* pool, int k, size_t pe
 	u32 HB = ceil_log2_u64((NI + per - 1) / per);
 	HB = std::max(8u, std::min(hb_max, HB));
 	const u32 NBH = 1u << HB;
-	static const u32 hist_dbg = (u32) tune("VDJX_HIST_DBG", 0);      // (ablation build only: profiles/histdbg.py)
-	static const size_t hist_blocks = tune("VDJX_HIST_BLOCKS", 512);
-	u32 nblk = (u32) std::min<size_t>(hist_blocks, (R + 4095) / 4096);
+#ifdef VDJX_ABLATE
+	static const u32 hist_dbg = (u32) vdjx_env_num("VDJX_HIST_DBG", 0, 0, 4);      // profiles/histdbg.py: the kernel stops after a phase
+#else
+	constexpr u32 hist_dbg = 0;
+#endif
+	u32 nblk = (u32) std::min<size_t>(HIST_BLOCKS, (R + 4095) / 4096);
 	if (nblk == 0) nblk = 1;
 	size_t rpb = (R + nblk - 1) / nblk;
 	u32 *hcnt, *hstart;
@@ -2600,7 +2591,7 @@ int stage_gated_hist(vdjx_ctx* c, A& db, const vdjx_pool* pool, int k, size_t pe
 	HIP_TRY(db.alloc(&hstart, NBH + 1));
 	HIP_TRY(hipMemsetAsync(hcnt, 0, (size_t) NBH * 4, st));
 	const bool lng = pool->W > 2;
-	const size_t lds_hist = (size_t) NBH * 4 + (HIST_THREADS / 64) * (lng ? GL_WAVE_BYTES_LONG : sym ? GL_WAVE_BYTES_SYM : GL_WAVE_BYTES);
+	const size_t lds_hist = (size_t) NBH * 4 + (HIST_THREADS / 64) * (lng ? GL_WAVE_BYTES_LONG : GL_WAVE_BYTES);
 	HIP_TRY(hipFuncSetAttribute((const void*) k_gated_hist<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_hist));
 	HIP_TRY(hipFuncSetAttribute((const void*) k_gated_hist<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_hist));
 	HIP_TRY(hipFuncSetAttribute((const void*) k_gated_hist<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_hist));
@@ -2633,8 +2624,7 @@ int stage_gated_cut(vdjx_ctx* c, A& db, const vdjx_pool* pool, u64 rec_base, int
 	const bool sym = gh.sym;
 	const size_t R = sym ? pool->n_records / 2 : pool->n_records;           // (sym: couples, stage_gated_hist)
 	const int P = pool->rl - k + 1;
-	static const size_t dflt = tune("VDJX_GATED_BUCKET", 3072);
-	const size_t per = per_bucket ? per_bucket : dflt;
+	const size_t per = per_bucket ? per_bucket : gated_bucket_default();
 	const u32 hb_max = pool->W > 2 ? 14u : 15u;
 	const bool lng = pool->W > 2;
 	const u32 HB = gh.HB, NBH = gh.NBH, N = gh.N;
@@ -2642,7 +2632,7 @@ int stage_gated_cut(vdjx_ctx* c, A& db, const vdjx_pool* pool, u64 rec_base, int
 	size_t rpb;
 	out->N = N;
 	const u64 Ng = geometry_instances ? geometry_instances : (u64) N;
-	static const size_t refine = tune("VDJX_REFINE_TUPLES", 4096);
+	static const size_t refine = (size_t) vdjx_env_num("VDJX_REFINE_TUPLES", 4096, 1, 1ll << 32);
 	u32 T = 8;
 	while (T < HB && ((u64) per << T) < Ng) T++;
 	u32 extra = 0;
@@ -2693,7 +2683,7 @@ int stage_gated_cut(vdjx_ctx* c, A& db, const vdjx_pool* pool, u64 rec_base, int
 	HIP_TRY(db.alloc(&tstart, NBt + 1));
 	out->NB = NBt;
 	out->bucket_start = tstart;
-	static const u32 slices = (u32) tune("VDJX_PART_SLICES", 8);
+	constexpr u32 slices = PART_SLICES;
 	if (extra) {
 		u32* fine_cnt;
 		HIP_TRY(db.alloc(&fine_cnt, NBt));
@@ -2723,17 +2713,31 @@ int stage_gated_partition(vdjx_ctx* c, A& db, const vdjx_pool* pool, u64 rec_bas
 	return stage_gated_cut<TUP>(c, db, pool, rec_base, k, per_bucket, geometry_instances, gh, out);
 }
 
+// VDJX_SUB_TUPLES into the module's g_sub_tuples: the same for every context of the process, set again by each once
+static int set_sub_tuples(vdjx_ctx* c) {
+	static const u32 sub = (u32) vdjx_env_num("VDJX_SUB_TUPLES", 262144, 1, 0xFFFFFFFFll);
+	if (c->sub_tuples_set != sub) {
+		HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_sub_tuples), &sub, 4, 0, hipMemcpyHostToDevice, c->stream));
+		c->sub_tuples_set = sub;
+	}
+	return VDJX_OK;
+}
+// the order the bucket kernels take their buckets in: by size, largest first, from 1,024 buckets up (fewer: null, as they come)
+template <typename TUP, typename A>
+int bucket_order(vdjx_ctx* c, A& db, const GTuples<TUP>& t, u32** order) {
+	*order = nullptr;
+	if (t.NB < 1024) return VDJX_OK;
+	HIP_TRY(db.alloc(order, t.NB));
+	hipLaunchKernelGGL(k_bucket_order, dim3(1), dim3(1024), 0, c->stream, t.bucket_start, t.NB, *order);
+	return VDJX_OK;
+}
+
 // Phase A, table + prune per bucket
 template <typename TUP, typename A>
 int stage_gated_reduce(vdjx_ctx* c, A& db, const GTuples<TUP>& t, const PoolView& pv, u64 rec_base, int k, int mf, int mq, SurvivorsG* sv, bool sym = false) {
 	hipStream_t st = c->stream;
-	{
-		static const u32 sub = (u32) tune("VDJX_SUB_TUPLES", 262144);
-		if (c->sub_tuples_set != sub) {            // (the module's variable: the same for every context of the process, set again by each once)
-			HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_sub_tuples), &sub, 4, 0, hipMemcpyHostToDevice, st));
-			c->sub_tuples_set = sub;
-		}
-	}
+	int rc = set_sub_tuples(c);
+	if (rc) return rc;
 	if (mq >= 255) mq = 254;                                        // A2:1514-1516
 	const u32 mqq = (u32) (mq < 0 ? 0 : (mq > 214 ? 214 : mq));      // a sum >= 214 reads as 255 (A2:356-360)
 	const u32 tlow = 1 + (mqq + 19) / 20;                           // see k_bucket_finalize
@@ -2749,15 +2753,11 @@ int stage_gated_reduce(vdjx_ctx* c, A& db, const GTuples<TUP>& t, const PoolView
 	u32* n_real = g_err + 2;
 	HIP_TRY(hipMemsetAsync(g_distinct, 0, (64 * 16 + 2) * 8, st));
 	SurvOutG so{sv->lo, sv->hi, sv->gcnt, sv->gfirst, n_surv, cap, n_real};
-	static const u32 rd_dbg = (u32) tune("VDJX_RD_DBG", 0);        // profiles/reducedbg.py: the kernel stops after a phase
+	static const u32 rd_dbg = (u32) vdjx_env_num("VDJX_RD_DBG", 0, 0, 9);        // profiles/reducedbg.py: the kernel stops after a phase (shipped library: 9 only, the tests' way into the rescan)
 	if (t.N) {
 		vdjx_prof_scope ps(c, "k_gated_reduce");
-		static const bool by_size = tune("VDJX_RD_ORDER", 1) == 1;
-		u32* order = nullptr;
-		if (by_size && t.NB >= 1024) {
-			HIP_TRY(db.alloc(&order, t.NB));
-			hipLaunchKernelGGL(k_bucket_order, dim3(1), dim3(1024), 0, st, t.bucket_start, t.NB, order);
-		}
+		u32* order;
+		if ((rc = bucket_order(c, db, t, &order))) return rc;
 		if (sym) hipLaunchKernelGGL((k_gated_reduce<TUP, true>), dim3(t.NB), dim3(RD_THREADS), 0, st, t.t, t.bucket_start, pv.bases, pv.nmask, pv.quals, pv.rl, pv.ob, k, rec_base,
 		                            mfu, cmin, mqq, tlow, so, g_distinct, g_err, rd_dbg, (const u32*) order);
 		else hipLaunchKernelGGL(k_gated_reduce<TUP>, dim3(t.NB), dim3(RD_THREADS), 0, st, t.t, t.bucket_start, pv.bases, pv.nmask, pv.quals, pv.rl, pv.ob, k, rec_base,
@@ -2867,7 +2867,7 @@ int stage_recount(vdjx_ctx* c, A& db, const vdjx_pool* pool, u64 rec_base, int k
 		hipLaunchKernelGGL(k_chain_words, gs, bs, 0, st, succ, skey, ns, k, linw, fbw, (const u32*) partner);
 	}
 	dbg_sync(c, "k_chain_order");
-	if (getenv("VDJX_SYNC_DEBUG")) {              // the new numbering is a permutation, and every key finds itself
+	if (sync_debug()) {              // the new numbering is a permutation, and every key finds itself
 		std::vector<u32> ni(ns), seen(ns, 0);
 		(void) hipMemcpy(ni.data(), newidx, (size_t) ns * 4, hipMemcpyDeviceToHost);
 		u32 dup = 0, oob = 0;
@@ -2889,7 +2889,7 @@ int stage_recount(vdjx_ctx* c, A& db, const vdjx_pool* pool, u64 rec_base, int k
 	ItemFmt f;
 	{
 		const u32 sb = ceil_log2_u64(ns);
-		static const u32 force_lb = (u32) tune("VDJX_RC_LEN_BITS", 4);      // (test knob: the shorter runs of pools with more than 2^22 survivors)
+		static const u32 force_lb = (u32) vdjx_env_num("VDJX_RC_LEN_BITS", 4, 0, 4);      // (test knob: the shorter runs of pools with more than 2^22 survivors; 0: one item per instance)
 		const u32 lb = std::min(std::min(4u, 26u - sb), force_lb);
 		const u32 pb = 26u - lb;
 		f.pmask = (1u << pb) - 1u;
@@ -2906,10 +2906,10 @@ int stage_recount(vdjx_ctx* c, A& db, const vdjx_pool* pool, u64 rec_base, int k
 	const u32 nsp = (f.bmask + 1u) << 4;                               // scattered index space
 	// ranges of the scattered space (one recount workgroup each, LDS arrays indexed by position - range start): the smallest range
 	// size that keeps the ranges <= 1024 (one partition pass); beyond the largest size a second partition level
-	static const bool force_wide = tune("VDJX_RC_WIDE", 0) != 0;                    // (test knobs: the paths of very large pools on small ones)
-	static const u32 cap_shift = (u32) tune("VDJX_RC_MAX_SHIFT", 12);
+	static const bool force_wide = vdjx_env_num("VDJX_RC_WIDE", 0, 0, 1) != 0;                   // (test knobs: the paths of very large pools on small ones)
+	static const u32 cap_shift = (u32) vdjx_env_num("VDJX_RC_MAX_SHIFT", 12, 8, 12);
 	const bool narrow = R < (1ull << (32 - pool->ob)) && !force_wide;            // local instance ids (+15) fit 32 bits
-	static const u32 max_ranges = (u32) std::min<size_t>(PART_MAXB, std::max<size_t>(2, tune("VDJX_RC_MAX_RANGES", PART_MAXB)));
+	static const u32 max_ranges = (u32) vdjx_env_num("VDJX_RC_MAX_RANGES", PART_MAXB, 2, PART_MAXB);
 	const u32 max_shift = std::max(8u, std::min(narrow ? 11u : 10u, cap_shift));
 	u32 range_shift = 8;
 	while (range_shift < max_shift && (nsp >> range_shift) > max_ranges) range_shift++;
@@ -2922,16 +2922,16 @@ int stage_recount(vdjx_ctx* c, A& db, const vdjx_pool* pool, u64 rec_base, int k
 	const u32 n_coarse = (n_ranges + (1u << l2bits) - 1) >> l2bits;
 	const u32 n_ranges_p = n_coarse << l2bits;                      // padded: every coarse segment has 2^l2bits ranges
 	// raw item blocks
-	static const size_t walk_blocks = tune("VDJX_WALK_BLOCKS", 7168);      // (seven waves per SIMD are resident: 28 blocks per CU = one resident set x 4; measured 4096 2.45 ms, 7168 2.32, 16384 2.52)
+	constexpr size_t walk_blocks = 7168;      // (seven waves per SIMD are resident: 28 blocks per CU = one resident set x 4; measured 4096 2.45 ms, 7168 2.32, 16384 2.52)
 	const size_t Rw = sym_walk ? R / 2 : R;                          // what the walk's lanes take: records, or couples of them
 	u32 nblk = (u32) std::min<size_t>(walk_blocks, (Rw + WALK_THREADS * 8 - 1) / (WALK_THREADS * 8));
 	// (1,536 blocks are resident at once -- six waves per SIMD --: a pool that asks for a few more pays a second, nearly empty round with
 	// the latency of a full one.  1 M pairs, 1,953 blocks asked: 0.41 ms; 1,500: 0.36; 1,700: 0.40.  3 M pairs: 3,000 0.77, 5,000 0.81)
-	static const u32 walk_resident = (u32) tune("VDJX_WALK_RESIDENT", 1536);
-	if (walk_resident && nblk > walk_resident && nblk < walk_blocks) nblk = nblk / walk_resident * walk_resident;
+	constexpr u32 walk_resident = 1536;
+	if (nblk > walk_resident && nblk < walk_blocks) nblk = nblk / walk_resident * walk_resident;
 	// (a pool too small to fill one resident set at eight rows of records per wave takes fewer rows per wave, down to one: 100 k pairs
 	// were 98 blocks -- a wave per SIMD on a third of the CUs, every lookup's latency in the open -- and 0.119 ms)
-	if (walk_resident && nblk < walk_resident) nblk = (u32) std::min<size_t>(walk_resident, (Rw + WALK_THREADS - 1) / WALK_THREADS);
+	if (nblk < walk_resident) nblk = (u32) std::min<size_t>(walk_resident, (Rw + WALK_THREADS - 1) / WALK_THREADS);
 	if (nblk == 0) nblk = 1;
 	const size_t nwaves = (size_t) nblk * (WALK_THREADS / 64);
 	const size_t NI = R * (size_t) P;
@@ -2963,7 +2963,7 @@ int stage_recount(vdjx_ctx* c, A& db, const vdjx_pool* pool, u64 rec_base, int k
 	// VDJX_WALK_DBG (profiles/walkdbg.sh): an ABLATED copy of the walk runs first into scratch outputs, timed as k_walk_dbg; the real
 	// one follows untouched.  Bits: 1 no item stores, 2 no range histogram, 8 no filter / table / key loads at run starts.
 #ifdef VDJX_ABLATE
-	static const u32 walk_dbg = (u32) tune("VDJX_WALK_DBG", 0);
+	static const u32 walk_dbg = (u32) vdjx_env_num("VDJX_WALK_DBG", 0, 0, 63);
 #else
 	constexpr u32 walk_dbg = 0;
 #endif
@@ -2993,11 +2993,11 @@ int stage_recount(vdjx_ctx* c, A& db, const vdjx_pool* pool, u64 rec_base, int k
 	if (R) {
 		vdjx_prof_scope ps(c, "k_walk_items");
 		if (lng) hipLaunchKernelGGL(k_walk_items<true>, dim3(nblk), dim3(WALK_THREADS), lds_walk, st, pool->d_bases, pool->d_nmask, R, pool->rl, pool->ob, k, tb, succ, linw, f, range_shift,
-		                            n_ranges_p, raw, raw_cap, blk_items, g_cursor, range_cnt, g_err, (u32) tune("VDJX_WALK_FLAGS", 0), (const u32*) nullptr);
+		                            n_ranges_p, raw, raw_cap, blk_items, g_cursor, range_cnt, g_err, 0u, (const u32*) nullptr);
 		else if (sym_walk) hipLaunchKernelGGL((k_walk_items<false, true>), dim3(nblk), dim3(WALK_THREADS), lds_walk, st, pool->d_bases, pool->d_nmask, R / 2, pool->rl, pool->ob, k, tb, succ, linw, f, range_shift,
-		                                      n_ranges_p, raw, raw_cap, blk_items, g_cursor, range_cnt, g_err, (u32) tune("VDJX_WALK_FLAGS", 0), (const u32*) partner);
+		                                      n_ranges_p, raw, raw_cap, blk_items, g_cursor, range_cnt, g_err, 0u, (const u32*) partner);
 		else hipLaunchKernelGGL(k_walk_items<false>, dim3(nblk), dim3(WALK_THREADS), lds_walk, st, pool->d_bases, pool->d_nmask, R, pool->rl, pool->ob, k, tb, succ, linw, f, range_shift,
-		                        n_ranges_p, raw, raw_cap, blk_items, g_cursor, range_cnt, g_err, (u32) tune("VDJX_WALK_FLAGS", 0), (const u32*) nullptr);
+		                        n_ranges_p, raw, raw_cap, blk_items, g_cursor, range_cnt, g_err, 0u, (const u32*) nullptr);
 	}
 	dbg_sync(c, "k_walk_items");
 	hipLaunchKernelGGL(k_bucket_scan, dim3(1), dim3(1024), 0, st, range_cnt, n_ranges_p, range_start);
@@ -3062,7 +3062,7 @@ int stage_recount(vdjx_ctx* c, A& db, const vdjx_pool* pool, u64 rec_base, int k
 		HIP_TRY(hipMemsetAsync(ro.edge_first, 0xFF, (size_t) ns * 32, st));
 		hipLaunchKernelGGL(k_edges_from_in, dim3((ns * 4 + 255) / 256), dim3(256), 0, st, tb, ns, k, ro.in_first, ro.in_from, ro.edge_first, ro.edge_to);
 	}
-	if (defer && !getenv("VDJX_SYNC_DEBUG")) {         // the caller reads the status when it waits anyway
+	if (defer && !sync_debug()) {         // the caller reads the status when it waits anyway
 		defer->g_err = g_err; defer->n_items = range_start + n_ranges_p; defer->n_inst = n_inst; defer->ns = ns;
 		return VDJX_OK;
 	}
@@ -3079,7 +3079,7 @@ int stage_recount(vdjx_ctx* c, A& db, const vdjx_pool* pool, u64 rec_base, int k
 	const unsigned long long inst = *(const unsigned long long*) (hp + 4);
 	if (err[0]) { vdjx_set_error("k_walk_items: item buffer too small (%u waves stopped)", err[0]); return VDJX_EHIP; }
 	if (err[1]) {
-		if (getenv("VDJX_SYNC_DEBUG")) {          // name the k-mers
+		if (sync_debug()) {          // name the k-mers
 			std::vector<u64> uf(ns), lo(ns), hi(ns), gf(ns);
 			std::vector<u32> gc(ns);
 			(void) hipMemcpy(uf.data(), ro.ufirst, (size_t) ns * 8, hipMemcpyDeviceToHost);
@@ -3217,9 +3217,8 @@ int kmer_build_impl2(vdjx_ctx* c, const vdjx_pool* pool, int k, int mf, int mq, 
 		// phase B: over the couples' first records when the survivor set came out of phase A closed under reverse complement (sym); should
 		// the chains turn out not to be mirror images after all (they are, by construction: k_succ_links2) the walk is done again over
 		// every record -- a survivor set with shadows is as good an input to that one
-		static const bool sym_walk_on = getenv("VDJX_NO_SYM_WALK") == nullptr;
 		for (int attempt = 0; attempt < 2; attempt++) {
-			const bool sym_walk = sym && sym_walk_on && attempt == 0;
+			const bool sym_walk = sym && sym_walk_wanted() && attempt == 0;
 			c->stats["kmer_build_sym_walk"] = sym_walk ? 1 : 0;
 			RecountStatus rs;
 			rc = stage_recount(c, db, pool, 0, k, sv, ro, true, nullptr, &rs, sym_walk);
@@ -3427,21 +3426,11 @@ static int shard_local_impl(vdjx_shard* s) {
 	if ((size_t) s->NBf + 1 > nb_max) { vdjx_set_error("vdjx_shard_local: %u buckets", s->NBf); return VDJX_ELIMIT; }
 	HIP_TRY(hipMemsetAsync(g_err, 0, 4, st));
 	if (s->NBf > t.NB) HIP_TRY(hipMemsetAsync(s->nd + t.NB, 0, (size_t) (s->NBf - t.NB) * 4, st));
-	{
-		static const u32 sub = (u32) tune("VDJX_SUB_TUPLES", 262144);
-		if (c->sub_tuples_set != sub) {            // (the module's variable: the same for every context of the process, set again by each once)
-			HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_sub_tuples), &sub, 4, 0, hipMemcpyHostToDevice, st));
-			c->sub_tuples_set = sub;
-		}
-	}
+	if ((rc = set_sub_tuples(c))) return rc;
 	{
 		vdjx_prof_scope ps(c, "k_gated_local");
-		static const bool by_size = tune("VDJX_RD_ORDER", 1) == 1;
-		u32* order = nullptr;
-		if (by_size && t.NB >= 1024) {
-			HIP_TRY(db.alloc(&order, t.NB));
-			hipLaunchKernelGGL(k_bucket_order, dim3(1), dim3(1024), 0, st, t.bucket_start, t.NB, order);
-		}
+		u32* order;
+		if ((rc = bucket_order(c, db, t, &order))) return rc;
 		if (s->sym) hipLaunchKernelGGL((k_gated_local<TUP, true>), dim3(t.NB), dim3(LG_THREADS), 0, st, t.t, t.bucket_start, s->pool->d_bases, s->pool->d_nmask, rec_base,
 		                               s->k, s->pool->rl, s->pool->ob, s->tlow, sparse, sparse_ref, s->nd, s->low_inst, g_err, (const u32*) order);
 		else hipLaunchKernelGGL(k_gated_local<TUP>, dim3(t.NB), dim3(LG_THREADS), 0, st, t.t, t.bucket_start, s->pool->d_bases, s->pool->d_nmask, rec_base,
@@ -3786,8 +3775,7 @@ extern "C" int vdjx_shard_edges(vdjx_shard* s, const void* d_surv_all, uint64_t 
 	// the walk takes the couples' first records only, as in the one-GPU build.  Should it find chains that are not mirror images (it
 	// cannot, by construction), this rank walks every record instead -- from the SAME survivor list, so that its numbering stays the
 	// one the other ranks use
-	static const bool sym_walk_on = getenv("VDJX_NO_SYM_WALK") == nullptr;
-	const bool sym_walk = s->sym && sym_walk_on;
+	const bool sym_walk = s->sym && sym_walk_wanted();
 	c->stats["kmer_build_sym_walk"] = sym_walk ? 1 : 0;
 	const SurvivorsG a_in = a;
 	int rc = stage_recount(c, db, s->pool, s->rec_base(), s->k, a, ro, false, &s->tb, nullptr, sym_walk);
@@ -3932,7 +3920,6 @@ extern "C" void vdjx_graph_free(vdjx_graph* g) {
 		(void) hipSetDevice(g->device);
 		if (vdjx_ctx_alive(g->ctx)) {
 			(void) hipStreamSynchronize(g->ctx->copy_stream);      // an export that was begun and never ended
-			if (g->ctx->root_pending && g->ctx->root_pending_g == g && g->ctx->root_stream) (void) hipStreamSynchronize(g->ctx->root_stream);      // a root scoring begun on this graph and never ended
 			g->ctx->blocks.release(g->d_block, g->block_cap);
 		}
 		else (void) hipFree(g->d_block);

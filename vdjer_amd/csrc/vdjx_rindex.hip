@@ -607,7 +607,7 @@ int read_index_build_dev(vdjx_ctx* c, vdjx_work& db, const vdjx_pool* pool, cons
                          const u32* d_reg, u32 n_pairs, hipStream_t st, vdjx_ctx* pc, std::map<std::string, uint64_t>& stats) {
 	if (pool->n_records > ((size_t) 1 << 29)) { vdjx_set_error("vdjx_read_index_build: %zu records on one GPU (limit 2^29): shard the pool by pair", pool->n_records); return VDJX_ELIMIT; }
 	const u32 R = (u32) pool->n_records;
-	const bool sym_on = getenv("VDJX_NO_SYM_INDEX") == nullptr;       // (read per build: the tests build one pool both ways)
+	const bool sym_on = !vdjx_env_set("VDJX_NO_SYM_INDEX");      // (read per build: the tests build one pool both ways)
 	const bool sym = sym_on && pool->sym && pool->W == 2 && R % 2 == 0;      // couples: k_ri_insert_sym
 	stats["read_index_sym"] = sym ? 1 : 0;
 	const size_t RK = sym ? R / 2 : R;                     // what the build's table holds: records, or couples
@@ -870,8 +870,6 @@ int ri_begin(vdjx_ctx* c, const vdjx_pool* pool, const uint32_t* pair_id, const 
 	vdjx_ri_job* j = new vdjx_ri_job();
 	c->ri_job = j;
 	const int device = c->device;
-	static const bool gated = !(getenv("VDJX_RI_GATE") && getenv("VDJX_RI_GATE")[0] == '0');      // (VDJX_RI_GATE=0: start at once, beside whatever comes)
-	j->go = !gated;
 	j->th = std::thread([=]() {
 		{
 			std::unique_lock<std::mutex> lk(j->mu);

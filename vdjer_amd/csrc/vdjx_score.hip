@@ -321,8 +321,8 @@ __global__ __launch_bounds__(DPW_THREADS) void k_root_dp_wave(const char* __rest
 // begin: queue everything, wait for nothing -- possible when the last call's item count is at hand as a guess (root_dp_hint) and the
 // threshold is positive; *begun says whether it was (else the call ran to its end as ever).  vdjx_root_score_graph_end waits, and
 // repeats the call the ordinary way should the guess have fallen short.
-static int root_score_device(vdjx_ctx* c, vdjx_work& db, const char* d_k, size_t n, int k, int threshold, uint8_t* out, bool* begun = nullptr, hipStream_t st = nullptr) {
-	if (!st) st = c->stream;
+static int root_score_device(vdjx_ctx* c, vdjx_work& db, const char* d_k, size_t n, int k, int threshold, uint8_t* out, bool* begun = nullptr) {
+	hipStream_t st = c->stream;
 	if (begun) *begun = false;
 	const int stop = k - c->vk;
 	u32 *d_lo, *d_cnt, *d_pre;
@@ -334,7 +334,7 @@ static int root_score_device(vdjx_ctx* c, vdjx_work& db, const char* d_k, size_t
 	HIP_TRY(db.alloc(&d_out, n));
 	HIP_TRY(hipMemsetAsync(d_out, 0, n, st));
 	{
-		vdjx_prof_scope ps(c, "k_seed_count", st);
+		vdjx_prof_scope ps(c, "k_seed_count");
 		hipLaunchKernelGGL(k_seed_count, dim3((ng + 255) / 256), dim3(256), 0, st, d_k, (u32) n, k, c->vk, c->d_seed_code, (u32) c->n_seeds, d_lo, d_cnt);
 	}
 	{
@@ -352,9 +352,9 @@ static int root_score_device(vdjx_ctx* c, vdjx_work& db, const char* d_k, size_t
 	HIP_TRY(hipMemcpyAsync(h_run, d_pre + ng, 4, hipMemcpyDeviceToHost, st));
 	if (!begun) HIP_TRY(hipEventRecord(c->ev_plan, st));
 	// few items: a wave each (k_root_dp_wave); many: a thread each
-	static const u32 dp_wave_max = getenv("VDJX_DP_WAVE_MAX") ? (u32) atol(getenv("VDJX_DP_WAVE_MAX")) : 32768u;      // (measured: 10 k items 0.043 against 0.110 ms, 25 k 0.087 / 0.111, 77 k 0.234 / 0.130, 252 k 0.74 / 0.18)
+	constexpr u32 dp_wave_max = 32768u;      // (measured: 10 k items 0.043 against 0.110 ms, 25 k 0.087 / 0.111, 77 k 0.234 / 0.130, 252 k 0.74 / 0.18)
 	auto launch_dp = [&](u32 first, u32 count) -> u32 {        // -> items covered from `first` on (whole workgroups)
-		vdjx_prof_scope ps(c, "k_root_dp", st);
+		vdjx_prof_scope ps(c, "k_root_dp");
 		if (count <= dp_wave_max && k <= 64) {
 			const u32 per = DPW_THREADS / 64;
 			hipLaunchKernelGGL(k_root_dp_wave, dim3((count + per - 1) / per), dim3(DPW_THREADS), 0, st, d_k, k, threshold,
@@ -493,29 +493,22 @@ extern "C" int vdjx_root_score_graph_begin(vdjx_ctx* c, const vdjx_graph* g, int
 	if (k - c->vk <= 0 || c->n_seeds == 0 || threshold <= 0 || !c->root_dp_hint) return vdjx_root_score_graph(c, g, threshold, first, stride, root_ids, out);
 	HIP_TRY(hipSetDevice(c->device));
 	vdjx_clear_errors();
-	// VDJX_ROOT_STREAM=1: on a stream and out of a workspace of its own, behind everything the context's stream holds so far, BESIDE what the
-	// caller queues on the context afterwards (the window scorer).  Measured at 10 M pairs (round 6): the step got SLOWER, 10.87 -> 11.10 ms --
-	// the begin call costs the host 0.25 ms instead of 0.07 (event record + cross-stream wait + a second queue to feed) and the window
-	// scorer gains 0.09 ms: the root kernels are 0.23 ms of small launches that the scorer's kernels, which fill the machine, do not
-	// run beside but around.  1 M pairs: 1.955 -> 1.964 ms.  So the default stays the context's stream (the calls in between run behind it)
-	static const bool own_stream = getenv("VDJX_ROOT_STREAM") && getenv("VDJX_ROOT_STREAM")[0] == '1';
-	hipStream_t st = own_stream ? c->root_stream : c->stream;
-	if (own_stream) {
-		HIP_TRY(hipEventRecord(c->ev_root_go, c->stream));
-		HIP_TRY(hipStreamWaitEvent(st, c->ev_root_go, 0));
-	}
-	vdjx_work db(c, own_stream ? &c->root_arena : &c->arena);      // (its own workspace: the calls in between reset and reuse the context's)
+	// (on the context's stream, the calls in between behind it.  A stream and a workspace of its own, beside the window scorer, made the
+	// step SLOWER at 10 M pairs, 10.87 -> 11.10 ms: 0.25 ms of host time for the begin call instead of 0.07, for 0.09 ms gained by a
+	// scorer whose kernels fill the machine and run around the small root launches, not beside them)
+	hipStream_t st = c->stream;
+	vdjx_work db(c);
 	char* d_k;
 	u32* d_ids;
 	HIP_TRY(db.alloc(&d_k, n * k));
 	HIP_TRY(db.alloc(&d_ids, n));
 	{
-		vdjx_prof_scope ps(c, "k_root_gather", st);
+		vdjx_prof_scope ps(c, "k_root_gather");
 		hipLaunchKernelGGL(k_root_gather, dim3((unsigned) ((n * 16 + 255) / 256)), dim3(256), 0, st, g->d_kmers, g->d_roots, first, stride, (u32) n, k, d_k, d_ids);
 	}
 	HIP_TRY(hipMemcpyAsync(root_ids, d_ids, n * 4, hipMemcpyDeviceToHost, st));
 	bool begun = false;
-	rc = root_score_device(c, db, d_k, n, k, threshold, out, &begun, st);
+	rc = root_score_device(c, db, d_k, n, k, threshold, out, &begun);
 	if (rc || !begun) return rc;
 	HIP_TRY(hipEventRecord(c->ev_root_done, st));
 	c->root_pending = true;
@@ -1132,8 +1125,15 @@ __device__ inline bool gp_entry_present(const GroupImg& L, const u64 e) {
 
 __global__ __launch_bounds__(GP_THREADS, GP_WAVES) void k_group_pairs(ReadIndexDev ix, const uint4* __restrict__ prep, const u32* __restrict__ hits, u32 n, int len,
                                                               const u32* __restrict__ gorder, const u64* __restrict__ pair_off, u64* __restrict__ pair_buf,
-                                                              u32* __restrict__ pair_cnt, u32* __restrict__ pair_np, u32* __restrict__ done, unsigned long long* __restrict__ gstat, u32 dbg,
+                                                              u32* __restrict__ pair_cnt, u32* __restrict__ pair_np, u32* __restrict__ done, unsigned long long* __restrict__ gstat, u32 dbg_in,
                                                               u64 cap) {
+	// the ablation switch (VDJX_GP_DBG: 1 no full tests, 2 images only -- wrong verdicts on purpose) exists only in the -DVDJX_ABLATE build
+#ifdef VDJX_ABLATE
+	const u32 dbg = dbg_in;
+#else
+	(void) dbg_in;
+	constexpr u32 dbg = 0u;
+#endif
 	if (pair_off[n] + 1 > cap) return;                  // (launched before the host knew the lists' total size: they do not fit, it will come again)
 	const long long t_begin = clock64();
 	__shared__ GroupImg L;
@@ -1882,9 +1882,8 @@ static int classify_and_plan(vdjx_ctx* c, vdjx_work& db, const ReadIndexDev& ix,
 	// ... unless they lie in page-locked host memory of the context's own (vdjx_host_alloc): then the
 	// kernel reads them where they are -- every character is read exactly once, 64 consecutive bytes per wave, and the other workgroups
 	// of a CU classify while one waits for its string; no copy, no pieces, nothing for the stream to wait for
-	static const bool zero_copy = !(getenv("VDJX_STRINGS_IN_PLACE") && atoi(getenv("VDJX_STRINGS_IN_PLACE")) == 0);
 	const char* d_src = nullptr;
-	if (zero_copy && vdjx_host_block_holds(c, strings, n * (size_t) len)) d_src = strings;      // (asking the runtime about a foreign pointer costs more than the copy saves)
+	if (vdjx_host_block_holds(c, strings, n * (size_t) len)) d_src = strings;      // (asking the runtime about a foreign pointer costs more than the copy saves)
 	const u32 pieces = d_src ? 1u : n * (size_t) len >= (2u << 20) ? 4u : 1u;
 	if (pieces > 1) {
 		HIP_TRY(hipEventRecord(c->ev_up[0], st));                  // (the arena's last users are on `st`)
@@ -1946,20 +1945,24 @@ static int window_pairs_run(vdjx_ctx* c, vdjx_work& db, const ReadIndexDev& ix, 
                             u32** d_cnt_out, MapPlan* mp, u64 budget = 0, u64* need = nullptr) {
 	hipStream_t st = c->stream;
 	u32 *d_np, *d_cnt;
-	static const u32 hit_chunk = getenv("VDJX_HIT_CHUNK") && atol(getenv("VDJX_HIT_CHUNK")) > 0 ? (u32) atol(getenv("VDJX_HIT_CHUNK")) : HIT_CHUNK;
+	static const u32 hit_chunk = (u32) vdjx_env_num("VDJX_HIT_CHUNK", HIT_CHUNK, 1, 0xFFFFFFFFll);
 	// VDJX_WINDOW_GROUP=0: every window on its own (k_window_pairs only)
-	static const u32 gp_dbg = getenv("VDJX_GP_DBG") ? (u32) atol(getenv("VDJX_GP_DBG")) : 0u;      // ablation (profiles/): 1 no full tests, 2 images only
-	static const bool group_on = !(getenv("VDJX_WINDOW_GROUP") && atol(getenv("VDJX_WINDOW_GROUP")) == 0);
+	static const bool group_on = vdjx_env_num("VDJX_WINDOW_GROUP", 1, 0, 1) != 0;
+#ifdef VDJX_ABLATE
+	static const u32 gp_dbg = (u32) vdjx_env_num("VDJX_GP_DBG", 0, 0, 2);      // ablation build only (k_group_pairs)
+#else
+	constexpr u32 gp_dbg = 0;
+#endif
 	// (few windows are mapped one by one: a group is one workgroup for eight windows, and below a few thousand windows the groups
 	// leave most of the chip idle -- 200 windows: 0.14 ms in groups + left-overs, 0.08 one by one; 2,000: 0.29 against 0.23; 20,000: 1.1 against 3.5)
-	static const size_t group_min = getenv("VDJX_GROUP_MIN") ? (size_t) atol(getenv("VDJX_GROUP_MIN")) : 4096;
+	static const size_t group_min = (size_t) vdjx_env_num("VDJX_GROUP_MIN", 4096, 0, 1ll << 40);
 	const bool grouped = group_on && len - ix.rl <= GP_NOFF && n >= group_min;
 	// With a pair buffer from an earlier call the groups are mapped BEFORE the host knows the plan's totals (the kernel returns at once
 	// if the lists would not fit): the host's wait for the totals and its next launches hide behind that kernel.
 	// (grouped: k_window_pairs only gets the windows of the few groups whose classes did not fit one image -- unrelated windows, each as
 	// deep as a window gets, and nothing else is running by then: their hits in small slices over many workgroups.  Two such groups of
 	// the bench workload: 0.135 ms in slices of 524,288 hits)
-	static const u32 left_chunk = getenv("VDJX_LEFT_CHUNK") && atol(getenv("VDJX_LEFT_CHUNK")) > 0 ? (u32) atol(getenv("VDJX_LEFT_CHUNK")) : 32768u;
+	constexpr u32 left_chunk = 32768u;
 	int rc = classify_and_plan(c, db, ix, windows, n, len, true, grouped && left_chunk < hit_chunk ? left_chunk : hit_chunk, mp, grouped, false);
 	if (rc) return rc;
 	// (one block, cleared by one call: a fill is 5 us of a small pool's step whatever its size)
@@ -2036,7 +2039,7 @@ static int window_score_slice(vdjx_ctx* c, const ReadIndexDev& ix, const char* w
 	{
 		vdjx_prof_scope ps(c, "k_window_cover");
 		u64* d_clk = nullptr;
-		static const bool cover_clocks = getenv("VDJX_COVER_CLOCKS") != nullptr;       // profiling aid: the slowest windows of the call to stderr
+		static const bool cover_clocks = vdjx_env_set("VDJX_COVER_CLOCKS");       // profiling aid: the slowest windows of the call to stderr
 		if (cover_clocks) HIP_TRY(db.alloc(&d_clk, n));
 		hipLaunchKernelGGL(k_window_cover, dim3((u32) n), dim3(MAP_THREADS), 0, st, len, ix.rl, *p, mp.d_order, mp.d_off, (const u64*) c->wp_buf, d_cnt, d_valid, d_clk);
 		if (cover_clocks) {
@@ -2116,7 +2119,7 @@ extern "C" int vdjx_window_score(vdjx_ctx* c, const char* windows, size_t n, int
 	// The pair lists of a call are sized by its windows' hits (8 bytes each; reads of a shared V germline hit every window that has
 	// it: the sum grows with windows x pool).  What does not fit the device is done in slices of windows, every slice like a call of
 	// its own (400 k windows over 10 M pairs ask for 600 GB at once).  VDJX_WP_BUDGET_MB: the tests' way into the slices.
-	static const u64 budget_env = getenv("VDJX_WP_BUDGET_MB") && atol(getenv("VDJX_WP_BUDGET_MB")) > 0 ? (u64) atol(getenv("VDJX_WP_BUDGET_MB")) << 20 : 0;
+	static const u64 budget_env = (u64) vdjx_env_num("VDJX_WP_BUDGET_MB", 0, 0, 1ll << 40) << 20;
 	u64 budget = budget_env;
 	if (!budget) {
 		size_t fr = 0, tt = 0;
@@ -2297,7 +2300,7 @@ static int map_emit_impl(vdjx_ctx* c, const char* contigs, size_t n, int len, ui
 	uint64_t key = fnv1a(contigs, n * (size_t) len, 0xcbf29ce484222325ull ^ (uint64_t) n * 1315423911ull ^ (uint64_t) len);
 	if (!key) key = 1;
 	lp.mark("me_key");
-	static const u32 slice_env = getenv("VDJX_MAP_SLICE") && atol(getenv("VDJX_MAP_SLICE")) > 0 ? (u32) std::min<long>(atol(getenv("VDJX_MAP_SLICE")), (long) MAP_SLICE_MAX) : 0u;
+	static const u32 slice_env = (u32) std::min<long long>(vdjx_env_num("VDJX_MAP_SLICE", 0, 0, 0xFFFFFFFFll), (long long) MAP_SLICE_MAX);
 	if (!pairs) c->me_key = 0;               // a counting call never reuses an earlier mapping
 	if (c->me_key != key || c->me_cnt.size() != n || c->me_src != (const void*) contigs) {
 		c->me_key = 0;

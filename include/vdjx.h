@@ -336,8 +336,8 @@ int vdjx_quant(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const vdjx
  *               the M/I/D runs 5' to 3' as len << 4 | op (op 0 M, 1 I, 2 D: BAM's codes); n_runs counts them all, runs[] holds them only
  *               when n_runs <= 64 (otherwise zeros: the CIGAR is written empty, stat "annot_cigar_truncated").  S = 0: no traceback
  *               (coordinates and counts 0).  identity = matches / (matches + mismatches + ins + del).
- * NOT modelled: D calls; IMGT-gapped sequence_alignment / germline_alignment; isotype (the ref-dir has no constant regions); reverse-
- * complement contigs (a contig is always V to J); IgBLAST's or V-QUEST's own identity definitions.
+ * NOT modelled: D calls; IMGT-gapped sequence_alignment / germline_alignment; reverse-complement contigs (a contig is always V to J);
+ * IgBLAST's or V-QUEST's own identity definitions.  The isotype is a call of its own against a constant-region set: vdjx_isotype below.
  * VDJX_EINVAL: contigs of unequal length (a NUL inside the n*len characters), len >= 4096, a V/J germline of 0 or >= 2048 bases, 2^20
  * records or more, match outside 1..15 or mismatch / gap_open / gap_extend outside 0..31 (every H then fits int16); vdjx_annotate before
  * any vdjx_germline_load is VDJX_ESTATE.  n = 0 returns at once.  Scratch comes from the context's workspace; no floating-point atomics,
@@ -355,6 +355,37 @@ int vdjx_germline_load(vdjx_ctx* ctx, const char* seqs, const uint64_t* off, con
 int vdjx_annotate(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const vdjx_annot_params* params, vdjx_annot_hit* out_v,
                   vdjx_annot_hit* out_j);
 
+/* ---- isotype calls: the contigs' 3' ends against the constant regions ------------------------------------------------------------------
+ * replaces the isotype step of the reference's post_process/ (call_isotypes.bash: get_cseq.py cuts the last 48 bases of every contig,
+ * isotypes_star.bash maps them to the whole genome with STAR, call_isotypes.py looks the hit up in igh_constant_func.bed) by a local
+ * alignment against the constant-region sequences themselves.  All arithmetic is integer: the device's results are bitwise the model's.
+ *   constants   vdjx_constant_load: record r is seqs[off[r] .. off[r+1]), cleaned by the caller exactly as for vdjx_germline_load (upper
+ *               case, '.' and whitespace dropped).  Every record is a constant record whatever its name.  0 .. 4096 records of 1 .. 2047
+ *               bases.  The set lives in a device buffer of its own, independent of the germline set, until the next
+ *               vdjx_constant_load or vdjx_shutdown.
+ *   query       the tail of a contig: its last T = min(tail, len) bases, tail in 16 .. 64 (48: get_cseq.py).  (64: one wave holds one
+ *               tail row per lane.)
+ *   score       vdjx_annotate's recurrences and scoring rule, unchanged (Gotoh, integer, N never matches), tail row i in 1..T, record
+ *               r's column j in 1..g_r: S(contig, r) = max H.  out_scores (may be NULL) receives every S, out_scores[contig * C + r]
+ *               (a runner-up score is what tells IGHG1 from IGHG2).
+ *   call        the primary hit is the record of highest S, the lowest index on a tie; n_tied counts the records at that S and tied[]
+ *               lists the first 8 of them in index order.  No call (gene -1, n_tied 0, tied[] -1) when S < min_score or C = 0; score is
+ *               S all the same (0 when C = 0).
+ *   traceback   the primary hit only, by vdjx_annotate's rules and preference order (the end cell: the first in row-major order that
+ *               holds S); every field of vdjx_annot_hit means what it means there.  seq_start / seq_end are in CONTIG coordinates (tail
+ *               coordinate + len - T); S = 0: no traceback.
+ * Defaults (what `vdjer --isotypes` uses): match 2, mismatch 3, gap_open 5, gap_extend 2, min_score 48, tail 48.  min_score 48 is half
+ * the score of a perfect 48-base tail: 400 random 48-mers against 9 random records of 1,000 bases reach at most 29 (median 19), a true
+ * tail with three substitutions scores 81.  It is a parameter of the model, not a tolerance.
+ * VDJX_EINVAL: contigs of unequal length (a NUL inside the n*len characters), len >= 4096, n >= 2^20, tail outside 16 .. 64, match
+ * outside 1..15 or mismatch / gap_open / gap_extend outside 0..31, min_score < 0; more than 4096 records or a record of 0 or >= 2048
+ * bases (vdjx_constant_load).  vdjx_isotype before any vdjx_constant_load is VDJX_ESTATE.  n = 0 returns at once.  Scratch (the score
+ * matrix included) comes from the context's workspace; no floating point, no atomics: two calls give the same bits. */
+typedef struct { int match, mismatch, gap_open, gap_extend, min_score, tail; } vdjx_isotype_params;   /* 24 bytes */
+int vdjx_constant_load(vdjx_ctx* ctx, const char* seqs, const uint64_t* off, size_t n);
+int vdjx_isotype(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const vdjx_isotype_params* params, vdjx_annot_hit* out_c,
+                 int32_t* out_scores);
+
 /* rows of `row` bytes on the device: row d_pos[i] of d_dst = row i of d_src.  (The records of a pool sharded by pair on their way to
  * the ranks that hold their slice of the scan order for the k-mer build, A2:1388-1390: every record arrives with its place.) */
 int vdjx_rows_scatter(vdjx_ctx* ctx, void* d_dst, const void* d_src, const uint32_t* d_pos, size_t n, size_t row);
@@ -363,7 +394,8 @@ int vdjx_rows_scatter(vdjx_ctx* ctx, void* d_dst, const void* d_src, const uint3
  * vdjx_window_score call, summed over windows), "window_hits_max", "window_pairs", "window_work_items",
  * "map_hits", "root_dp_items".  Unknown names return 0.  Used by bench.py to price the scorers' algorithmic bytes.  vdjx_quant's last
  * call: "quant_map_us", "quant_setup_us", "quant_em_us" (host clock, each phase ending in a wait for the device), "quant_contigs_placed".
- * vdjx_annotate's last call: "annot_cells" (DP cells of the scoring phase), "annot_score_us", "annot_trace_us", "annot_cigar_truncated". */
+ * vdjx_annotate's last call: "annot_cells" (DP cells of the scoring phase), "annot_score_us", "annot_trace_us", "annot_cigar_truncated".
+ * vdjx_isotype's last call: "iso_cells" (DP cells of the scoring phase), "iso_score_us", "iso_trace_us" (host clock, each ending in a wait). */
 uint64_t vdjx_stat(vdjx_ctx* ctx, const char* name);
 
 /* ---- profiling hooks (HIP events on the context's stream) ---------------------------------------*/

@@ -1,5 +1,6 @@
 """Germline records for contig annotation (vdjx_germline_load, include/vdjx.h): the FASTA reader and the name / class rules that
-`vdjer --airr` applies in C (vdjer_main.c) as well."""
+`vdjer --airr` applies in C (vdjer_main.c) as well; and the three rules `vdjer --isotypes` / `--clones` apply to the called names (the
+reference's post_process/call_isotypes.py and collect_vdjer_stats.py)."""
 from __future__ import annotations
 
 
@@ -44,3 +45,28 @@ def parse_record(header: str, seq: str):
     """(name, class, sequence) of a FASTA record"""
     name = parse_name(header)
     return name, parse_class(name), clean_seq(seq)
+
+
+def gene_of(name: str) -> str:
+    """the gene of an allele name: the text before the first '*' (IGHG1*01 -> IGHG1)"""
+    return name.split("*", 1)[0]
+
+
+def _distinct(items) -> str:
+    out = []
+    for x in items:
+        if x not in out:
+            out.append(x)
+    return ",".join(out)
+
+
+def subtypes(names) -> str:
+    """the isotype of a call: the distinct first four characters of the genes (IGHG1 -> IGHG), in order of first appearance"""
+    return _distinct(gene_of(x)[:4] for x in names)
+
+
+def vq_gene(names) -> str:
+    """get_vq_gene's normalisation (collect_vdjer_stats.py): per name the text before '*', every 'D' deleted (IGHV1-69D -> IGHV1-69,
+    IGKV1D-39 -> IGKV1-39), then what lies before a second '-' (IGHV3-30-5 -> IGHV3-30); the distinct results in order of first
+    appearance"""
+    return _distinct("-".join(gene_of(x).replace("D", "").split("-")[:2]) for x in names)

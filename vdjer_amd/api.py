@@ -6,7 +6,8 @@ stands where build_pre_graph/prune_pre_graph/build_graph2 stand in assemble() (A
 `root_score` is score_seq (A2:1103); `window_score` is quick_map_process_contig + coverage_is_valid
 (A2:841-847); `map_emit` is quick_map_process_contig_file (A2:912); `quant` is the RSEM step the reference's workflow runs
 on vdjer.sam afterwards (demo/quant_demo.bash); `germline_load` / `annotate` stand for the IMGT HighV-QUEST run over
-vdj_contigs.fa that the reference's post_process/collect_vdjer_stats.py reads.
+vdj_contigs.fa that the reference's post_process/collect_vdjer_stats.py reads.  `constant_load` / `isotype` stand for its isotype step
+(call_isotypes.bash: STAR over the contigs' last 48 bases).
 Everything computes on the GPU through libvdjx.so; nothing here falls back to a CPU path.
 """
 from __future__ import annotations
@@ -651,6 +652,37 @@ class Context:
         prm = _lib.AnnotParams(int(match), int(mismatch), int(gap_open), int(gap_extend), int(min_v_score), int(min_j_score))
         check(self.L.vdjx_annotate(self.h, raw, n, ln, C.byref(prm), _p(hv), _p(hj)), "vdjx_annotate")
         return {k: {f: h[f].copy() for f in self.ANNOT_HIT.names} for k, h in (("v", hv), ("j", hj))}
+
+    def constant_load(self, fasta_path_or_records):
+        """vdjx_constant_load: a constant-region FASTA (path) or a list of (FASTA header, sequence) records -> dict(names).  Names and
+        sequences as for germline_load (vdjer_amd/annot.py); every record is a constant record.  The set stays on the device, beside the
+        germline set."""
+        from . import annot
+        recs = annot.read_fasta(fasta_path_or_records) if isinstance(fasta_path_or_records, str) else list(fasta_path_or_records)
+        names = [annot.parse_name(h) for h, _ in recs]
+        seqs = [annot.clean_seq(q) for _, q in recs]
+        off = np.zeros(len(seqs) + 1, np.uint64)
+        off[1:] = np.cumsum([len(q) for q in seqs], dtype=np.uint64)
+        check(self.L.vdjx_constant_load(self.h, "".join(seqs).encode(), _p(off), len(seqs)), "vdjx_constant_load")
+        self._const_n = len(seqs)
+        return dict(names=names)
+
+    def isotype(self, contigs, tail: int = 48, match: int = 2, mismatch: int = 3, gap_open: int = 5, gap_extend: int = 2,
+                min_score: int = 48, scores: bool = True):
+        """vdjx_isotype: the last `tail` bases of every contig against the loaded constant set -> {"c": {field: array}, "scores":
+        int32[n, C] | None}, the fields of vdjx_annot_hit (seq_start / seq_end in contig coordinates)"""
+        if isinstance(contigs, tuple):
+            raw, n, ln = contigs
+        else:
+            if len({len(s_) for s_ in contigs}) > 1:
+                raise VdjxError("vdjx_isotype: contigs of unequal length")
+            raw, n, ln = self.pack_strings(contigs)
+        hc = np.zeros(n, self.ANNOT_HIT)
+        nc = getattr(self, "_const_n", 0)
+        sc = np.zeros((n, nc), np.int32) if scores else None
+        prm = _lib.IsotypeParams(int(match), int(mismatch), int(gap_open), int(gap_extend), int(min_score), int(tail))
+        check(self.L.vdjx_isotype(self.h, raw, n, ln, C.byref(prm), _p(hc), _p(sc) if scores and sc.size else None), "vdjx_isotype")
+        return {"c": {f: hc[f].copy() for f in self.ANNOT_HIT.names}, "scores": sc}
 
     def stat(self, name: str) -> int:
         return int(self.L.vdjx_stat(self.h, name.encode()))

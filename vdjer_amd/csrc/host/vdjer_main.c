@@ -4,9 +4,12 @@
  *
  *   vdjer --in <reads> --chain IGH|IGK|IGL --ref-dir <dir> --ins <n> [--t --k --mf --mq --mcs --am --miw --maw
  *         --jc --ws -jext --rf --vk --mrs --rs --ms --e0 --e1 --wo --vf --jf --rms] [--gpus N] [--quant <file>] [--airr <file>]
+ *         [--cfa <fasta>] [--isotypes <file>] [--clones <file>] [--sample <name>] [--total-count <n>]
  * writes ./vdj_contigs.fa and ./vdjer.dot, SAM on stdout, log on stderr; exit 0 on success.  --quant <file>: the contigs' abundances
  * (vdjx_quant, RSEM's isoforms.results columns) into <file> as well.  --airr <file>: the contigs' V/J annotation (vdjx_annotate against
- * the germlines of ig_vdj.fa / --vdjf) as an AIRR Rearrangement TSV.
+ * the germlines of ig_vdj.fa / --vdjf) as an AIRR Rearrangement TSV.  --cfa <fasta>: constant-region sequences; --isotypes <file>: the
+ * isotype call of every contig against them (vdjx_isotype); --clones <file>: the per-sample table of the reference's post_process/
+ * (collect_vdjer_stats.py | cluster_results.py) from the three device steps (one GPU only).
  *
  * --in: a BAM with its .bai (extraction as bam_read.c:264-446, restated over zlib in bamx.c), or -- recognised by its
  * content -- the extracted read pool as text, one read per line in extraction order:
@@ -45,6 +48,11 @@ typedef struct {
 	int gpus;                              /* --gpus N (not in the reference): the k-mer build sharded over N GPUs of this node */
 	const char* quant;                     /* --quant <file> (not in the reference): the RSEM step of demo/quant_demo.bash, on the device */
 	const char* airr;                      /* --airr <file> (not in the reference): the HighV-QUEST step of post_process/, on the device */
+	const char* cfa;                       /* --cfa <fasta> (not in the reference): the constant-region sequences of --isotypes / --clones */
+	const char* isotypes;                  /* --isotypes <file> (not in the reference): call_isotypes.bash of post_process/, on the device */
+	const char* clones;                    /* --clones <file> (not in the reference): collect_vdjer_stats.py | cluster_results.py */
+	const char* sample;                    /* --sample <name>: the clone table's first column (default: --in's base name up to its first '.') */
+	const char* total_count;               /* --total-count <n>: the clone table's total_count column (default: N/A) */
 	int have_chain, have_ref;
 } cli;
 
@@ -59,7 +67,12 @@ static void usage(void) {
 	                "\t--e0/--e1 <start/stop position for contig filtering (default: 52/411)>\n\t--wo <window overlap check size>\n"
 	                "\t--gpus <GPUs of this node to shard the k-mer table over (default: 1)>\n"
 	                "\t--quant <file: expected read pairs per contig, an RSEM isoforms.results table (one GPU only)>\n"
-	                "\t--airr <file: V/J calls of every contig against ig_vdj.fa, an AIRR Rearrangement table>\n");
+	                "\t--airr <file: V/J calls of every contig against ig_vdj.fa, an AIRR Rearrangement table>\n"
+	                "\t--cfa <constant-region FASTA for --isotypes / --clones>\n"
+	                "\t--isotypes <file: isotype call of every contig's last 48 bases against --cfa>\n"
+	                "\t--clones <file: the clustered clone table of this sample (one GPU only)>\n"
+	                "\t--sample <name in the clone table (default: the input's base name up to its first '.')>\n"
+	                "\t--total-count <whole number for the clone table's total_count column (default: N/A)>\n");
 }
 
 static int file_exists(const char* f) { struct stat b; return stat(f, &b) == 0; }
@@ -99,6 +112,11 @@ static int parse(int argc, char** argv, cli* c) {
 		else if (!strcmp(a, "--gpus")) c->gpus = atoi(v);
 		else if (!strcmp(a, "--quant")) c->quant = v;
 		else if (!strcmp(a, "--airr")) c->airr = v;
+		else if (!strcmp(a, "--cfa")) c->cfa = v;
+		else if (!strcmp(a, "--isotypes")) c->isotypes = v;
+		else if (!strcmp(a, "--clones")) c->clones = v;
+		else if (!strcmp(a, "--sample")) c->sample = v;
+		else if (!strcmp(a, "--total-count")) c->total_count = v;
 		else if (!strcmp(a, "--vf")) snprintf(c->v_anchors, sizeof c->v_anchors, "%s", v);
 		else if (!strcmp(a, "--jf")) snprintf(c->j_anchors, sizeof c->j_anchors, "%s", v);
 		else if (!strcmp(a, "--am")) c->anchor_mismatches = atoi(v);
@@ -133,6 +151,16 @@ static int parse(int argc, char** argv, cli* c) {
 	if (!c->source_sim_file[0]) { fprintf(stderr, "source_sim_file file must be specified\n"); ok = 0; }
 	if (c->hp.j_conserved != 'W' && c->hp.j_conserved != 'F') { fprintf(stderr, "Conserved J AA must be W or F: %c\n", c->hp.j_conserved); ok = 0; }
 	if (c->hp.insert_len <= 0) { fprintf(stderr, "insert_len must be specified and > 0\n"); ok = 0; }
+	if (c->isotypes && !c->cfa) { fprintf(stderr, "--isotypes needs the constant-region sequences: --cfa <fasta>\n"); ok = 0; }
+	if (c->cfa) {
+		FILE* fp = fopen(c->cfa, "r");
+		if (!fp) { fprintf(stderr, "--cfa: cannot read the constant-region FASTA %s\n", c->cfa); ok = 0; }
+		else fclose(fp);
+	}
+	if (c->total_count && (!c->total_count[0] || strspn(c->total_count, "0123456789") != strlen(c->total_count))) {
+		fprintf(stderr, "--total-count must be a whole decimal number: %s\n", c->total_count);
+		ok = 0;
+	}
 	if (!ok) { usage(); return -1; }
 	if (c->hp.min_base_quality >= 255) c->hp.min_base_quality = 254;      /* A2:1514-1516 */
 	return 0;
@@ -468,6 +496,12 @@ typedef struct {
 	const char* vdjf;
 	int airr_done;
 	size_t a_contigs, a_v, a_j, a_prod, a_trunc, a_skip_d, a_skip_other;
+	/* --isotypes / --clones: what the steps above and vdjx_isotype found is kept until the last table is written */
+	const char *cfa, *isotypes, *clones, *sample, *total_count;
+	struct germ_set* germ; vdjx_annot_hit *hv, *hj;      /* the germline records and the V / J hits (annot_run) */
+	struct germ_set* cst; vdjx_annot_hit* hc;            /* the constant records and the isotype hits (iso_run) */
+	int iso_done, clones_done;
+	size_t i_contigs, i_called, c_rows, c_clusters;
 } hook_ud;
 
 static int h_root_score(void* ud, const char* kmers, size_t n, int k, int thr, uint8_t* out) {
@@ -518,6 +552,7 @@ static int quant_table(hook_ud* u, const char* const* ids, const char* contigs, 
 	const vdjx_quant_params qp = {10000, 1e-5};
 	int rc = vdjx_quant(u->gx, contigs, n, len, &qp, cnt, &u->qi);
 	if (rc) { fprintf(stderr, "vdjx_quant: %s\n", vdjx_last_error()); free(cnt); return rc; }
+	if (!u->quant) { free(u->qcnt); u->qcnt = cnt; u->quant_done = 1; return 0; }      /* (--clones alone: the counts, no table) */
 	FILE* fp = fopen(u->quant, "w");
 	if (!fp) { fprintf(stderr, "cannot write %s\n", u->quant); free(cnt); return -1; }
 	free(u->qcnt);
@@ -536,13 +571,7 @@ static int quant_table(hook_ud* u, const char* const* ids, const char* contigs, 
 }
 
 /* ---- --airr: the germline FASTA, the junction-derived fields and the table (the model: include/vdjx.h, vdjx_annotate) ---------------- */
-typedef struct { char* seqs; uint64_t* off; char* cls; char** names; size_t n, cap, bytes, bcap; } germ_set;
-
-static void germ_free(germ_set* g) {
-	for (size_t i = 0; i < g->n; i++) free(g->names[i]);
-	free(g->seqs); free(g->off); free(g->cls); free(g->names);
-	memset(g, 0, sizeof *g);
-}
+typedef struct germ_set { char* seqs; uint64_t* off; char* cls; char** names; size_t n, cap, bytes, bcap; } germ_set;
 
 /* the record's name: the header's first token, or its second '|' field when the token has one; its class: the 4th character of
  * IG[HKL]* / TR[ABDG]* names, the 1st otherwise */
@@ -566,10 +595,10 @@ static void germ_name(const char* head, char** name, char* cls) {
 	*cls = imgt ? nm[3] : tl ? nm[0] : '?';
 }
 
-static int germ_read(const char* path, germ_set* g) {
+static int germ_read(const char* path, germ_set* g, const char* what) {
 	memset(g, 0, sizeof *g);
 	FILE* fp = fopen(path, "r");
-	if (!fp) { fprintf(stderr, "--airr: cannot read the germline FASTA %s\n", path); return -1; }
+	if (!fp) { fprintf(stderr, "%s %s\n", what, path); return -1; }
 	char* line = NULL;
 	size_t lcap = 0;
 	ssize_t ln;
@@ -637,21 +666,45 @@ static void put_hit(FILE* fp, const vdjx_annot_hit* h) {
 	fprintf(fp, "\t%.4f\t%d\t%d\t%d\t%d", (double) h->matches / d, h->seq_start, h->seq_end, h->germ_start, h->germ_end);
 }
 
-static int airr_table(hook_ud* u, const char* const* ids, const char* contigs, size_t n, int len) {
-	germ_set g;
-	if (germ_read(u->vdjf, &g)) return -1;
-	for (size_t r = 0; r < g.n; r++) {
-		if (g.cls[r] == 'V' || g.cls[r] == 'J') continue;
-		if (g.cls[r] == 'D') u->a_skip_d++; else u->a_skip_other++;
+/* the junction: the text after the id's second '_', at its first occurrence in the contig -> its 0-based start (or -1); *jn, *jl: the text */
+static long junction_at(const char* id, const char* s, int len, const char** jn_out, size_t* jl_out) {
+	const char* u1 = strchr(id, '_');
+	const char* jn = u1 ? strchr(u1 + 1, '_') : NULL;
+	jn = jn && jn[1] ? jn + 1 : NULL;
+	const size_t jl = jn ? strlen(jn) : 0;
+	long p = -1;
+	if (jn && jl <= (size_t) len)
+		for (long q = 0; q + (long) jl <= len; q++)
+			if (!memcmp(s + q, jn, jl)) { p = q; break; }
+	*jn_out = jn;
+	*jl_out = jl;
+	return p;
+}
+
+/* the V / J hits of every contig (vdjx_annotate against the germlines of ig_vdj.fa / --vdjf), kept for the tables */
+static int annot_run(hook_ud* u, const char* contigs, size_t n, int len) {
+	u->germ = (germ_set*) calloc(1, sizeof(germ_set));
+	if (germ_read(u->vdjf, u->germ, u->airr ? "--airr: cannot read the germline FASTA" : "--clones: cannot read the germline FASTA")) return -1;
+	const germ_set* g = u->germ;
+	for (size_t r = 0; r < g->n; r++) {
+		if (g->cls[r] == 'V' || g->cls[r] == 'J') continue;
+		if (g->cls[r] == 'D') u->a_skip_d++; else u->a_skip_other++;
 	}
-	vdjx_annot_hit* hv = (vdjx_annot_hit*) calloc(n + 1, sizeof(vdjx_annot_hit));
-	vdjx_annot_hit* hj = (vdjx_annot_hit*) calloc(n + 1, sizeof(vdjx_annot_hit));
+	u->hv = (vdjx_annot_hit*) calloc(n + 1, sizeof(vdjx_annot_hit));
+	u->hj = (vdjx_annot_hit*) calloc(n + 1, sizeof(vdjx_annot_hit));
 	const vdjx_annot_params ap = {2, 3, 5, 2, 40, 20};
-	int rc = vdjx_germline_load(u->gx, g.seqs, g.off, g.cls, g.n);
-	if (!rc && n) rc = vdjx_annotate(u->gx, contigs, n, len, &ap, hv, hj);
-	FILE* fp = rc ? NULL : fopen(u->airr, "w");
-	if (rc) fprintf(stderr, "--airr: %s\n", vdjx_last_error());
-	else if (!fp) { fprintf(stderr, "cannot write %s\n", u->airr); rc = -1; }
+	int rc = vdjx_germline_load(u->gx, g->seqs, g->off, g->cls, g->n);
+	if (!rc && n) rc = vdjx_annotate(u->gx, contigs, n, len, &ap, u->hv, u->hj);
+	if (rc) fprintf(stderr, "%s: %s\n", u->airr ? "--airr" : "--clones", vdjx_last_error());
+	return rc;
+}
+
+static int airr_table(hook_ud* u, const char* const* ids, const char* contigs, size_t n, int len) {
+	const germ_set g = *u->germ;
+	const vdjx_annot_hit *hv = u->hv, *hj = u->hj;
+	int rc = 0;
+	FILE* fp = fopen(u->airr, "w");
+	if (!fp) { fprintf(stderr, "cannot write %s\n", u->airr); rc = -1; }
 	if (fp) {
 		fputs("sequence_id\tsequence\trev_comp\tproductive\tv_call\td_call\tj_call\tsequence_alignment\tgermline_alignment\tjunction\tjunction_aa\t"
 		      "cdr3\tcdr3_aa\tvj_in_frame\tstop_codon\tv_cigar\td_cigar\tj_cigar\tv_score\tv_identity\tv_sequence_start\tv_sequence_end\t"
@@ -660,15 +713,9 @@ static int airr_table(hook_ud* u, const char* const* ids, const char* contigs, s
 		for (size_t i = 0; i < n; i++) {
 			const char* s = contigs + i * (size_t) len;
 			const vdjx_annot_hit *v = hv + i, *j = hj + i;
-			/* the junction: the text after the id's second '_', at its first occurrence in the contig */
-			const char* u1 = strchr(ids[i], '_');
-			const char* jn = u1 ? strchr(u1 + 1, '_') : NULL;
-			jn = jn && jn[1] ? jn + 1 : NULL;
-			const size_t jl = jn ? strlen(jn) : 0;
-			long p = -1;
-			if (jn && jl <= (size_t) len)
-				for (long q = 0; q + (long) jl <= len; q++)
-					if (!memcmp(s + q, jn, jl)) { p = q; break; }
+			const char* jn;
+			size_t jl;
+			const long p = junction_at(ids[i], s, len, &jn, &jl);
 			const size_t JL = p >= 0 ? jl : 0;
 			const int hasv = v->gene >= 0 && v->score > 0, hasj = j->gene >= 0 && j->score > 0;
 			const int inframe = p >= 0 && hasv && JL % 3 == 0 && (p - (v->seq_start - 1) + (v->germ_start - 1)) % 3 == 0;
@@ -703,17 +750,170 @@ static int airr_table(hook_ud* u, const char* const* ids, const char* contigs, s
 		}
 		if (fclose(fp)) { fprintf(stderr, "cannot write %s\n", u->airr); rc = -1; }
 	}
-	free(hv); free(hj);
-	germ_free(&g);
 	if (!rc) u->airr_done = 1;
+	return rc;
+}
+
+/* ---- --isotypes / --clones (the model: include/vdjx.h, vdjx_isotype; the name rules: vdjer_amd/annot.py) ----------------------------- */
+/* a comma-joined list of distinct items in order of first appearance */
+typedef struct { char* s; size_t n, cap, cnt; } slist;
+
+static void sl_add(slist* b, const char* item, size_t il) {
+	size_t at = 0;
+	for (size_t k = 0; k < b->cnt; k++) {
+		size_t e = at;
+		while (e < b->n && b->s[e] != ',') e++;
+		if (e - at == il && !memcmp(b->s + at, item, il)) return;
+		at = e + 1;
+	}
+	if (b->n + il + 2 > b->cap) { b->cap = 2 * (b->n + il + 2); b->s = (char*) realloc(b->s, b->cap); }
+	if (b->cnt) b->s[b->n++] = ',';
+	memcpy(b->s + b->n, item, il);
+	b->n += il;
+	b->s[b->n] = 0;
+	b->cnt++;
+}
+
+static const char* sl_str(const slist* b) { return b->s ? b->s : ""; }
+
+/* subtypes: per called name the first four characters of the text before its first '*' (IGHG1*01 -> IGHG) */
+static void subtypes_of(const vdjx_annot_hit* h, const germ_set* g, slist* out) {
+	out->n = out->cnt = 0;
+	if (out->s) out->s[0] = 0;
+	if (h->gene < 0) return;
+	for (int k = 0; k < h->n_tied && k < VDJX_ANNOT_TIED; k++) {
+		const char* nm = g->names[h->tied[k]];
+		size_t l = strcspn(nm, "*");
+		sl_add(out, nm, l < 4 ? l : 4);
+	}
+}
+
+/* get_vq_gene (collect_vdjer_stats.py): per called name the text before '*', every 'D' deleted, then what lies before a second '-' */
+static void vq_gene_of(const vdjx_annot_hit* h, const germ_set* g, slist* out) {
+	out->n = out->cnt = 0;
+	if (out->s) out->s[0] = 0;
+	if (h->gene < 0) return;
+	for (int k = 0; k < h->n_tied && k < VDJX_ANNOT_TIED; k++) {
+		const char* nm = g->names[h->tied[k]];
+		const size_t l = strcspn(nm, "*");
+		char* t = (char*) malloc(l + 1);
+		size_t tl = 0;
+		int dashes = 0;
+		for (size_t q = 0; q < l; q++) {
+			if (nm[q] == 'D') continue;
+			if (nm[q] == '-' && ++dashes == 2) break;
+			t[tl++] = nm[q];
+		}
+		sl_add(out, t, tl);
+		free(t);
+	}
+}
+
+/* the isotype hits of every contig (vdjx_isotype against the records of --cfa), kept for the tables */
+static int iso_run(hook_ud* u, const char* contigs, size_t n, int len) {
+	u->cst = (germ_set*) calloc(1, sizeof(germ_set));
+	if (germ_read(u->cfa, u->cst, "--cfa: cannot read the constant-region FASTA")) return -1;
+	u->hc = (vdjx_annot_hit*) calloc(n + 1, sizeof(vdjx_annot_hit));
+	const vdjx_isotype_params ip = {2, 3, 5, 2, 48, 48};
+	int rc = vdjx_constant_load(u->gx, u->cst->seqs, u->cst->off, u->cst->n);
+	if (!rc && n) rc = vdjx_isotype(u->gx, contigs, n, len, &ip, u->hc, NULL);
+	if (rc) fprintf(stderr, "%s: %s\n", u->isotypes ? "--isotypes" : "--clones", vdjx_last_error());
+	for (size_t i = 0; !rc && i < n; i++) { u->i_contigs++; u->i_called += u->hc[i].gene >= 0; }
+	return rc;
+}
+
+static int isotypes_table(hook_ud* u, const char* const* ids, size_t n, int len) {
+	FILE* fp = fopen(u->isotypes, "w");
+	if (!fp) { fprintf(stderr, "cannot write %s\n", u->isotypes); return -1; }
+	fputs("sequence_id\tisotype\tc_call\tc_score\tc_identity\tc_sequence_start\tc_sequence_end\tc_germline_start\tc_germline_end\tc_cigar\n", fp);
+	slist sub;
+	memset(&sub, 0, sizeof sub);
+	for (size_t i = 0; i < n; i++) {
+		const vdjx_annot_hit* h = u->hc + i;
+		subtypes_of(h, u->cst, &sub);
+		fprintf(fp, "%s\t%s\t", ids[i], sl_str(&sub));
+		put_call(fp, h, u->cst);
+		put_hit(fp, h);
+		fputc('\t', fp);
+		put_cigar(fp, h, len);
+		fputc('\n', fp);
+	}
+	free(sub.s);
+	if (fclose(fp)) { fprintf(stderr, "cannot write %s\n", u->isotypes); return -1; }
+	u->iso_done = 1;
+	return 0;
+}
+
+/* --clones: the table collect_vdjer_stats.py | cluster_results.py make of RSEM's, V-QUEST's and the isotype step's outputs, for this
+ * sample: a row per contig whose printed expected_count is >= 1, that has a V call and whose junction is found in it with a non-empty
+ * translation; a cluster id per distinct (isotype, aa cdr3, vgene, jgene) in order of first appearance */
+static int clones_table(hook_ud* u, const char* const* ids, const char* contigs, size_t n, int len) {
+	FILE* fp = fopen(u->clones, "w");
+	if (!fp) { fprintf(stderr, "cannot write %s\n", u->clones); return -1; }
+	fputs("sample\tsequence\tcdr3\texpected_counts\tseq_id\tisotype\tvregion_identity\taa_cdr3\tvgene\tjgene\ttotal_count\tcluster\n", fp);
+	slist sub, vg, jg;
+	memset(&sub, 0, sizeof sub); memset(&vg, 0, sizeof vg); memset(&jg, 0, sizeof jg);
+	char** keys = NULL;
+	size_t nkeys = 0, kcap = 0;
+	for (size_t i = 0; i < n; i++) {
+		const char* s = contigs + i * (size_t) len;
+		const vdjx_annot_hit *v = u->hv + i, *j = u->hj + i;
+		char cnt[64];
+		snprintf(cnt, sizeof cnt, "%.2f", u->qcnt ? u->qcnt[i] : 0.0);
+		const char* jn;
+		size_t jl;
+		const long p = junction_at(ids[i], s, len, &jn, &jl);
+		if (!(atof(cnt) >= 1.0) || v->gene < 0 || p < 0 || jl < 3) continue;
+		const int d = v->matches + v->mismatches + v->ins + v->del;
+		char* aa = (char*) malloc(jl / 3 + 1);
+		size_t al = 0;
+		for (size_t q = 0; q + 3 <= jl; q += 3) aa[al++] = codon_aa(s + p + q);
+		aa[al] = 0;
+		const int called = u->hc && u->hc[i].gene >= 0;
+		if (called) subtypes_of(u->hc + i, u->cst, &sub);
+		const char* iso = called ? sl_str(&sub) : "N/A";
+		vq_gene_of(v, u->germ, &vg);
+		vq_gene_of(j, u->germ, &jg);
+		const char* jgene = j->gene >= 0 ? sl_str(&jg) : "N/A";
+		const size_t kl = strlen(iso) + al + strlen(sl_str(&vg)) + strlen(jgene) + 4;
+		char* key = (char*) malloc(kl);
+		snprintf(key, kl, "%s\t%s\t%s\t%s", iso, aa, sl_str(&vg), jgene);
+		size_t k = 0;
+		while (k < nkeys && strcmp(keys[k], key)) k++;
+		if (k == nkeys) {
+			if (nkeys + 1 > kcap) { kcap = kcap ? 2 * kcap : 64; keys = (char**) realloc(keys, kcap * sizeof(char*)); }
+			keys[nkeys++] = key;
+		} else free(key);
+		fprintf(fp, "%s\t%.*s\t%s\t%s\t%s\t%s\t", u->sample, len, s, jn, cnt, ids[i], iso);
+		if (d > 0) fprintf(fp, "%.2f", 100.0 * ((double) v->matches / d)); else fputs("N/A", fp);
+		fprintf(fp, "\t%s\t%s\t%s\t%s\tcls_%zu\n", aa, sl_str(&vg), jgene, u->total_count ? u->total_count : "N/A", k + 1);
+		free(aa);
+		u->c_rows++;
+	}
+	u->c_clusters = nkeys;
+	for (size_t k = 0; k < nkeys; k++) free(keys[k]);
+	free(keys); free(sub.s); free(vg.s); free(jg.s);
+	if (fclose(fp)) { fprintf(stderr, "cannot write %s\n", u->clones); return -1; }
+	u->clones_done = 1;
+	return 0;
+}
+
+/* the tables after the SAM body: every device step runs once, whichever tables ask for it */
+static int tables(hook_ud* u, const char* const* ids, const char* contigs, size_t n, int len) {
+	int rc = 0;
+	if (!rc && (u->quant || u->clones)) rc = quant_table(u, ids, contigs, n, len);
+	if (!rc && (u->airr || u->clones)) rc = annot_run(u, contigs, n, len);
+	if (!rc && u->airr) rc = airr_table(u, ids, contigs, n, len);
+	if (!rc && u->cfa && (u->isotypes || u->clones)) rc = iso_run(u, contigs, n, len);
+	if (!rc && u->isotypes) rc = isotypes_table(u, ids, n, len);
+	if (!rc && u->clones) rc = clones_table(u, ids, contigs, n, len);
 	return rc;
 }
 
 static int h_sam_body(void* ud, const char* const* ids, const char* contigs, size_t n, int len, FILE* out) {
 	hook_ud* u = (hook_ud*) ud;
 	int rc = sam_records(ud, ids, contigs, n, len, out);
-	if (!rc && u->quant) rc = quant_table(u, ids, contigs, n, len);
-	if (!rc && u->airr) rc = airr_table(u, ids, contigs, n, len);
+	if (!rc) rc = tables(u, ids, contigs, n, len);
 	return rc;
 }
 
@@ -794,6 +994,10 @@ int main(int argc, char** argv) {
 	const int use_mgpu = c.gpus > 1 || vdjx_env_set("VDJX_FORCE_MGPU");      /* (the variable: a one-rank run of the same code path) */
 	if (c.quant && use_mgpu) {
 		fprintf(stderr, "--quant runs on one GPU only: it cannot be combined with --gpus N > 1 (or VDJX_FORCE_MGPU)\n");
+		return 255;
+	}
+	if (c.clones && use_mgpu) {
+		fprintf(stderr, "--clones runs on one GPU only (its counts are --quant's): it cannot be combined with --gpus N > 1 (or VDJX_FORCE_MGPU)\n");
 		return 255;
 	}
 	/* ranks that share ONE device (the multi-rank tests on a one-GPU box; RCCL refuses two ranks on a device): bytes move through the
@@ -974,14 +1178,23 @@ int main(int argc, char** argv) {
 	hook_ud ud;
 	memset(&ud, 0, sizeof ud);
 	ud.gx = gx; ud.p = &c.hp; ud.mg = mg; ud.quant = c.quant; ud.airr = c.airr; ud.vdjf = c.vdj_fasta;
+	ud.cfa = c.cfa; ud.isotypes = c.isotypes; ud.clones = c.clones; ud.total_count = c.total_count;
+	char sample_buf[4096];
+	if (c.sample) ud.sample = c.sample;
+	else {                                  /* the input's base name up to its first '.' */
+		const char* b = strrchr(c.in, '/');
+		snprintf(sample_buf, sizeof sample_buf, "%s", b ? b + 1 : c.in);
+		sample_buf[strcspn(sample_buf, ".")] = 0;
+		ud.sample = sample_buf;
+	}
 	vdjh_hooks hk = {&ud, h_root_score, h_window_score, h_sam_body, vc, nv, jc, nj, h_status};
 	vdjh_stats st;
 	if (vdjh_assemble(&c.hp, &hg, &hk, "vdj_contigs.fa", "vdjer.dot", stdout, &st)) {
 		fprintf(stderr, "%s\n", vdjh_last_error());
 		return 1;
 	}
-	if (c.quant && !ud.quant_done && quant_table(&ud, NULL, NULL, 0, 0)) return 1;         /* (no contig: the header alone) */
-	if (c.airr && !ud.airr_done && airr_table(&ud, NULL, NULL, 0, 0)) return 1;
+	/* (no contig: the headers alone) */
+	if (!ud.quant_done && !ud.airr_done && !ud.iso_done && !ud.clones_done && tables(&ud, NULL, NULL, 0, 0)) return 1;
 	fprintf(stderr, "num root nodes: %zu\nProcessed roots: %zu\ncontig_candidates: %zu\nwindows scored: %zu valid: %zu\ncontigs: %zu\n",
 	        st.n_roots, st.n_roots_accepted, st.n_contig_candidates, st.n_windows_scored, st.n_windows_valid, st.n_contigs_out);
 	if (mg) {
@@ -1014,6 +1227,11 @@ int main(int argc, char** argv) {
 	if (c.airr)
 		fprintf(stderr, "airr: %zu contigs, %zu V called, %zu J called, %zu productive, %zu CIGARs truncated; germline records skipped: %zu D, %zu other; table in %s\n",
 		        ud.a_contigs, ud.a_v, ud.a_j, ud.a_prod, ud.a_trunc, ud.a_skip_d, ud.a_skip_other, c.airr);
+	if (c.isotypes)
+		fprintf(stderr, "isotypes: %zu contigs, %zu called against %zu constant records of %s; table in %s\n", ud.i_contigs, ud.i_called,
+		        ud.cst ? ud.cst->n : (size_t) 0, c.cfa, c.isotypes);
+	if (c.clones)
+		fprintf(stderr, "clones: %zu rows in %zu clusters, isotypes %s; table in %s\n", ud.c_rows, ud.c_clusters, c.cfa ? "called" : "N/A (no --cfa)", c.clones);
 	fflush(stdout);
 	fflush(stderr);
 	/* the outputs are written; the orderly teardown of a context that holds gigabytes (unmapping the workspaces piece by piece, the

@@ -230,6 +230,12 @@ struct vdjx_ctx {
 	std::vector<u64> gl_at[2];        // its reset column in d_gl_cols (its bases follow)
 	std::vector<u32> gl_len[2];
 	u64 gl_class_at[3] = {};          // class c's columns are [gl_class_at[c], gl_class_at[c + 1])
+	// vdjx_constant_load (vdjx_iso.hip): the constant records' base codes back to back, each after a reset column, one more at the end
+	uint8_t* d_cs_cols = nullptr;
+	size_t cs_cols_cap = 0;
+	bool cs_loaded = false;
+	std::vector<u64> cs_at;           // record r's reset column in d_cs_cols (its bases follow); cs_at[C]: the last reset column
+	std::vector<u32> cs_len;
 	std::map<std::string, uint64_t> stats;
 };
 

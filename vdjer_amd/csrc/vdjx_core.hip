@@ -142,6 +142,7 @@ extern "C" void vdjx_shutdown(vdjx_ctx* c) {
 	if (c->h_sam_text) (void) hipHostFree(c->h_sam_text);
 	free_dev(c->d_sam_text); free_dev(c->d_sam_names); free_dev(c->d_sam_noff);
 	free_dev(c->d_gl_cols);
+	free_dev(c->d_cs_cols);
 	(void) hipStreamDestroy(c->stream);
 	delete c;
 }

@@ -1,6 +1,7 @@
 """vdjx_annotate on the GPU: V/J calls, alignments and CIGAR runs against the integer model of tests/annot_model.py (field for field), at
 size against the private repertoire, and `vdjer --airr` on every e2e golden.  The API checks run in child processes, once per knob
 setting (the suite's and the shipped ones, as tests/test_gpu_quant.py runs them), since VDJX_ANNOT_PAIRS is read once per process."""
+import functools
 import json
 import os
 import subprocess
@@ -158,6 +159,73 @@ def test_annot_multi_launch_small_pairs():
     """VDJX_ANNOT_PAIRS=3: chunks of at most one germline, one workgroup per launch -- the results are the model's all the same"""
     res = _run_child("_api_checks", "x", _child_env("suite", VDJX_ANNOT_PAIRS="3"))
     assert res["seed1"]["v"] > 0
+
+
+ROW_LENS = [1, 65, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4095]     # one per instantiated rows-per-lane count, both ends of the range
+
+
+def _row_count_case():
+    """(records, {m: two contigs}): short germlines (the model's traceback is plain Python) -- V of 60, 40 and 1 bases and a copy of the
+    first (a forced tie), J of 30 and 20; from 193 bases on, a V prefix + 10 random bases + a J lie at a random offset in the first
+    half of contig 0 and in the second half of contig 1"""
+    rng = np.random.default_rng(2026)
+    V = [_rand(rng, 60), _rand(rng, 40), "A"]
+    V.append(V[0])
+    J = [_rand(rng, 30), _rand(rng, 20)]
+    recs = [(f"V{k}", s) for k, s in enumerate(V)] + [(f"J{k}", s) for k, s in enumerate(J)]
+    contigs = {}
+    for m in ROW_LENS:
+        pair = [_rand(rng, m), _rand(rng, m)]
+        if m >= 193:
+            for c in range(2):
+                body = V[0][:50] + _rand(rng, 10) + J[0]
+                half = (m - len(body)) // 2
+                o = int(rng.integers(0, half + 1)) + c * (m - len(body) - half)
+                pair[c] = pair[c][:o] + body + pair[c][o + len(body):]
+        assert all(len(s) == m for s in pair)
+        contigs[m] = pair
+    return recs, contigs
+
+
+PRM0 = dict(A.DEFAULT, min_v_score=0, min_j_score=0)
+
+
+@functools.lru_cache(maxsize=None)
+def _row_count_model():
+    recs, contigs = _row_count_case()
+    germs, classes = [s for _, s in recs], [h[0] for h, _ in recs]
+    return {m: A.annotate(contigs[m], germs, classes, PRM0) for m in ROW_LENS}
+
+
+def _row_count_device(_):
+    from vdjer_amd import api
+    recs, contigs = _row_count_case()
+    ctx = api.Context(0)
+    ctx.germline_load(recs)
+    out = {}
+    for m in ROW_LENS:
+        dev = ctx.annotate(contigs[m], **PRM0)
+        out[str(m)] = {cls: {f: np.asarray(dev[cls][f]).tolist() for f in A.FIELDS} for cls in ("v", "j")}
+    ctx.close()
+    return out
+
+
+@pytest.mark.parametrize("knobs", KNOBS)
+def test_annot_every_row_count(knobs):
+    """every instantiation of the scoring kernel (1 .. 64 rows per lane) and the traceback with its LDS sized to queries of up to 4095
+    bases: every field equals the model's"""
+    res = _run_child("_row_count_device", "x", _child_env(knobs))
+    model = _row_count_model()
+    for m in ROW_LENS:
+        dev = res[str(m)]
+        _same(dev, model[m], m)
+        v, j = ({f: np.asarray(dev[cls][f]) for f in A.FIELDS} for cls in ("v", "j"))
+        if m == 1:
+            assert (v["gene"] >= 0).all() and (v["score"] == 2).all(), (m, v["gene"], v["score"])
+        if m >= 193:
+            assert v["n_tied"][0] == 2, (m, v["n_tied"])
+            for h in (v, j):
+                assert (h["gene"] >= 0).all() and (h["n_runs"] > 0).all() and (h["seq_end"] <= m).all(), (m, h["gene"], h["n_runs"], h["seq_end"])
 
 
 def at_size_contigs(n=2172, n_clones=20000):

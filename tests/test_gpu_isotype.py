@@ -10,7 +10,7 @@ from tests import annot_model as A
 from tests import golden_util as G
 from tests import isotype_model as M
 from tests import quant_model as Q
-from tests.test_gpu_annot import E2E, KNOBS, RECIPES, _argv, _child_env, _vdjer, _write_inputs, at_size_contigs
+from tests.test_gpu_annot import E2E, KNOBS, RECIPES, _argv, _child_env, _mutate, _rand, _vdjer, _write_inputs, at_size_contigs
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -26,24 +26,6 @@ def _run_child(fn, arg, env, timeout=1500):
     r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=timeout, env=env)
     assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-4000:])
     return json.loads(next(l for l in r.stdout.splitlines() if l.startswith("ISO ")).split(" ", 1)[1])
-
-
-def _rand(rng, n, alpha="ACGT"):
-    return "".join(rng.choice(list(alpha), int(n)))
-
-
-def _mutate(rng, s, k):
-    s = list(s)
-    for _ in range(k):
-        q = int(rng.integers(0, len(s)))
-        op = int(rng.integers(0, 3))
-        if op == 0:
-            s[q] = "ACGT"[int(rng.integers(0, 4))]
-        elif op == 1 and len(s) > 2:
-            del s[q]
-        else:
-            s.insert(q, "ACGT"[int(rng.integers(0, 4))])
-    return "".join(s)
 
 
 def _random_case(seed):

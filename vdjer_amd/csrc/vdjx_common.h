@@ -113,6 +113,18 @@ struct vdjx_block_cache {
 	void drop();
 };
 
+// a set of records to align against (vdjx_align.hip): per class the records' base codes back to back, each after a reset column, one more
+// reset column at the end
+struct vdjx_recset {
+	uint8_t* d_cols = nullptr;        // class 0's columns, then class 1's (kept until the next load or vdjx_shutdown)
+	size_t cap = 0;                   // bytes behind d_cols
+	bool loaded = false;
+	int ncls = 0;
+	std::vector<u32> rec[2];          // per class: the record index of every record of the class, ascending
+	std::vector<u64> at[2];           // its reset column in d_cols (its bases follow); one more entry: the class's last reset column
+	std::vector<u32> len[2];
+};
+
 struct vdjx_ctx {
 	int device = 0;
 	vdjx_arena arena;
@@ -222,20 +234,7 @@ struct vdjx_ctx {
 	void* h_sam_merge = nullptr;      // vdjx_sam_merge: the merged text (page-locked)
 	size_t sam_merge_cap = 0;
 	u32 n_pairs = 0, n_classes = 0;
-	// vdjx_germline_load (vdjx_annot.hip): per class (0 V, 1 J) the records' base codes back to back, each after a reset column
-	uint8_t* d_gl_cols = nullptr;     // [gl_cols]: class V's columns, then class J's
-	size_t gl_cols_cap = 0;
-	bool gl_loaded = false;
-	std::vector<u32> gl_gene[2];      // record index of every germline of the class, in index order
-	std::vector<u64> gl_at[2];        // its reset column in d_gl_cols (its bases follow)
-	std::vector<u32> gl_len[2];
-	u64 gl_class_at[3] = {};          // class c's columns are [gl_class_at[c], gl_class_at[c + 1])
-	// vdjx_constant_load (vdjx_iso.hip): the constant records' base codes back to back, each after a reset column, one more at the end
-	uint8_t* d_cs_cols = nullptr;
-	size_t cs_cols_cap = 0;
-	bool cs_loaded = false;
-	std::vector<u64> cs_at;           // record r's reset column in d_cs_cols (its bases follow); cs_at[C]: the last reset column
-	std::vector<u32> cs_len;
+	vdjx_recset germline, constant;   // vdjx_germline_load (classes V, J) / vdjx_constant_load (one class): independent of each other
 	std::map<std::string, uint64_t> stats;
 };
 

@@ -141,8 +141,7 @@ extern "C" void vdjx_shutdown(vdjx_ctx* c) {
 	if (c->h_pin) (void) hipHostFree(c->h_pin);
 	if (c->h_sam_text) (void) hipHostFree(c->h_sam_text);
 	free_dev(c->d_sam_text); free_dev(c->d_sam_names); free_dev(c->d_sam_noff);
-	free_dev(c->d_gl_cols);
-	free_dev(c->d_cs_cols);
+	free_dev(c->germline.d_cols); free_dev(c->constant.d_cols);
 	(void) hipStreamDestroy(c->stream);
 	delete c;
 }

@@ -390,6 +390,11 @@ int vdjx_isotype(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const vd
  * the ranks that hold their slice of the scan order for the k-mer build, A2:1388-1390: every record arrives with its place.) */
 int vdjx_rows_scatter(vdjx_ctx* ctx, void* d_dst, const void* d_src, const uint32_t* d_pos, size_t n, size_t row);
 
+/* For the test suite only: the exclusive prefix sum every stage of the device code shares (csrc/vdjx_scan.h), on its own.
+ * host_out[i] = host_in[0] + ... + host_in[i - 1] for i = 0 .. n (n + 1 elements of 4 bytes, or of 8 if out_is_u64; 4-byte sums wrap);
+ * launches: 1 = one workgroup, 3 = the device-wide form.  VDJX_EINVAL: n >= 2^31, launches neither 1 nor 3. */
+int vdjx_scan_u32(vdjx_ctx* ctx, const uint32_t* host_in, size_t n, int out_is_u64, int launches, void* host_out);
+
 /* counters of the most recent scorer calls, by name: "window_hits" (read instances matched by the last
  * vdjx_window_score call, summed over windows), "window_hits_max", "window_pairs", "window_work_items",
  * "map_hits", "root_dp_items".  Unknown names return 0.  Used by bench.py to price the scorers' algorithmic bytes.  vdjx_quant's last

@@ -155,6 +155,45 @@ def test_quant_api_multi_mapping_vs_numpy(tag, knobs):
     assert info["alignments"] > info["pairs"] > 0
 
 
+def _block_edge_checks(P):
+    """e2e_mixed cut down to its first P pairs: with P one below and one above the block of the device-wide scan (vdjx_scan.h) the
+    degree scan ends inside its first block or one element into its second, and the pairs no contig places have degree zero"""
+    from vdjer_amd import synth
+    c = G.Case("e2e_mixed")
+    pl = c.pool
+    keep = pl.pair_id < P
+    npri = pl.primary.shape[0]
+    rank = np.argsort(np.argsort(pl.reg_rank[keep], kind="stable"), kind="stable").astype(np.uint32)     # (dense again; a read's two records stay neighbours)
+    pool = synth.ReadPool(pl.rl, pl.primary[keep[:npri]], pl.secondary[keep[npri:]], pl.pair_id[keep], pl.read_num[keep], pl.is_rc[keep], rank, P)
+    ctx, p = _context(pool)
+    _, seqs = _golden_contigs("e2e_mixed")
+    S = _multi_set(seqs, c.clones)
+    offs, pairs = ctx.map_emit(S)
+    pr, ct, ins = _triples(offs, pairs)
+    placed = np.unique(pr)
+    assert 0 < placed.size < P and int(placed.max()) < P, (placed.size, P)            # some pairs of degree zero
+    assert placed.size < placed.max() + 1, "no pair of degree zero before the last placed one"
+    N, info = ctx.quant(S, tol=0, max_iter=50)
+    Nm, im = Q.quant(pr, ct, ins, len(S), 360, tol=0, max_iter=50)
+    np.testing.assert_allclose(N, Nm, rtol=1e-9, atol=1e-12)
+    assert (info["pairs"], info["alignments"], info["unique_pairs"]) == (im["pairs"], im["alignments"], im["unique_pairs"])
+    assert info["pairs"] == placed.size
+    p.free()
+    ctx.close()
+    return info
+
+
+@pytest.mark.parametrize("side", [-1, 1])
+def test_quant_pair_count_around_a_scan_block(side):
+    from tests.scan_shapes import BLOCK
+    code = f"import json; from tests.test_gpu_quant import _block_edge_checks; print('QUANT', json.dumps(_block_edge_checks({BLOCK + side})))"
+    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600,
+                       env=_child_env("suite"))
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    info = json.loads(next(l for l in r.stdout.splitlines() if l.startswith("QUANT ")).split(" ", 1)[1])
+    assert info["alignments"] > info["pairs"] > 0
+
+
 def _write_inputs(c, d):
     os.makedirs(os.path.join(d, "ref"), exist_ok=True)
     c.pool.write_reads_file(os.path.join(d, "reads.txt"))

@@ -7,6 +7,7 @@
 // (512 MiB each), a probe is one 4-byte load.  Code 0 (poly-A) is the sets' empty key and can never
 // be a member (vj_filter.c:317-318).
 #include "vdjx_common.h"
+#include "vdjx_scan.h"
 
 __global__ void k_bitmap_set(const u32* __restrict__ codes, size_t n, u32* __restrict__ bits) {
 	size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
@@ -161,25 +162,6 @@ __global__ __launch_bounds__(IDX_THREADS) void k_index_dist(const u32* __restric
 	if (threadIdx.x == 0) block_cnt[blockIdx.x] = s_cnt;
 }
 
-__global__ __launch_bounds__(1024) void k_index_scan(const u32* __restrict__ cnt, u32 n, u32* __restrict__ start_out) {
-	__shared__ u32 part[1024];
-	const u32 per = (n + 1023) / 1024;
-	const u32 lo = threadIdx.x * per, hi = lo + per < n ? lo + per : n;
-	u32 s = 0;
-	for (u32 i = lo; i < hi; i++) s += cnt[i];
-	part[threadIdx.x] = s;
-	__syncthreads();
-	for (u32 d = 1; d < 1024; d <<= 1) {
-		const u32 v = threadIdx.x >= d ? part[threadIdx.x - d] : 0;
-		__syncthreads();
-		part[threadIdx.x] += v;
-		__syncthreads();
-	}
-	u32 run = threadIdx.x ? part[threadIdx.x - 1] : 0;
-	for (u32 i = lo; i < hi; i++) { start_out[i] = run; run += cnt[i]; }
-	if (threadIdx.x == 1023) start_out[n] = part[1023];
-}
-
 // rows in ascending code order (the order process_kmers prints them)
 __global__ __launch_bounds__(IDX_THREADS) void k_index_emit(const u32* __restrict__ dist4, u64 start, u64 count, u32 max_dist,
                                                             const u32* __restrict__ block_start, u32* __restrict__ codes,
@@ -239,7 +221,7 @@ extern "C" int vdjx_index_generate(vdjx_ctx* c, const uint32_t* anchors, size_t 
 			vdjx_prof_scope ps(c, "k_index_dist");
 			hipLaunchKernelGGL(k_index_dist, dim3(nblk), dim3(IDX_THREADS), 0, st, d_anchors, (u32) n_anchors, s0, count, md, d_dist4, d_bcnt);
 		}
-		hipLaunchKernelGGL(k_index_scan, dim3(1), dim3(1024), 0, st, d_bcnt, nblk, d_bstart);
+		vdjx_scan_one(st, d_bcnt, nblk, d_bstart);
 		u32 rows = 0;
 		HIP_TRY(hipMemcpyAsync(&rows, d_bstart + nblk, 4, hipMemcpyDeviceToHost, st));
 		HIP_TRY(hipStreamSynchronize(st));

@@ -314,6 +314,11 @@ struct vdjx_prof_scope {
 };
 void vdjx_prof_collect(vdjx_ctx* ctx, bool force = true);
 
+// radix sort of (u64 key, u32 value) pairs by the key's bits [0, end_bit) (vdjx_rindex.hip); _raw: for a caller with its own allocator,
+// tmp == nullptr asks for the scratch size
+int vdjx_sort_pairs(vdjx_work& db, hipStream_t st, u64* k_in, u64* k_out, u32* v_in, u32* v_out, u32 n, unsigned end_bit);
+int vdjx_sort_pairs_raw(void* tmp, size_t* tmp_bytes, hipStream_t st, u64* k_in, u64* k_out, u32* v_in, u32* v_out, u32 n, unsigned end_bit);
+
 // host-side laps (VDJX_LAPS=1): microseconds between two marks of a call, summed into vdjx_stat("us_<name>")
 struct vdjx_laps {
 	vdjx_ctx* c;
@@ -557,6 +562,21 @@ __device__ inline int vdjx_wave_scan_add(int v) {
 	v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);      // row_shr:8
 	v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);      // row_bcast:15 -> rows 1, 3
 	v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);      // row_bcast:31 -> rows 2, 3
+	return v;
+}
+// ... of 8-byte values: the two halves move through the same six steps and are added as one number
+template <int CTRL, int ROWS> __device__ inline u64 vdjx_dpp_move64(u64 v) {
+	const u32 lo = (u32) __builtin_amdgcn_update_dpp(0, (int) (u32) v, CTRL, ROWS, 0xf, false);
+	const u32 hi = (u32) __builtin_amdgcn_update_dpp(0, (int) (u32) (v >> 32), CTRL, ROWS, 0xf, false);
+	return ((u64) hi << 32) | lo;
+}
+__device__ inline u64 vdjx_wave_scan_add(u64 v) {
+	v += vdjx_dpp_move64<0x111, 0xf>(v);
+	v += vdjx_dpp_move64<0x112, 0xf>(v);
+	v += vdjx_dpp_move64<0x114, 0xf>(v);
+	v += vdjx_dpp_move64<0x118, 0xf>(v);
+	v += vdjx_dpp_move64<0x142, 0xa>(v);
+	v += vdjx_dpp_move64<0x143, 0xc>(v);
 	return v;
 }
 

@@ -8,7 +8,7 @@
 // MFMA applies.
 //
 //   K2a k_kmer_hist        per-workgroup LDS histogram of bucket sizes over a slice of the pool, added to the global counts
-//   K2b k_bucket_scan      exclusive bucket starts
+//   K2b vdjx_scan_one      exclusive bucket starts (vdjx_scan.h)
 //   K2c k_part_records /   LDS-staged counting sort per round: tuples {key_lo, key_hi, inst|gated} written as
 //       k_part_tuples      coalesced bucket runs (256 coarse buckets, then 128 fine ones inside each; large pools:
 //                          2^(T-10) coarse, a counting pass, 1024 fine); positions inside a bucket from cursor bumps
@@ -17,6 +17,7 @@
 //   K4  k_walk_items / k_recount   the ungated recount: runs of surviving k-mers along the records, counted per survivor range
 //   K5  k_surv_table / k_graph_edges / k_node_flags   survivor lookup table, ordered edges, V/J flags
 #include "vdjx_common.h"
+#include "vdjx_scan.h"
 
 #include <algorithm>
 #include <numeric>
@@ -47,47 +48,6 @@ __device__ inline RecView load_rec(const u64* __restrict__ bases, const u64* __r
 	v.nm = nmask[r];
 	v.lq = lowq ? lowq[r] : 0ull;
 	return v;
-}
-
-// exclusive scan of bucket_cnt[NB] -> bucket_start[NB+1], one 1024-thread workgroup.  Tiles of 8,192 counters go through LDS: read and
-// written with consecutive lanes on consecutive addresses, summed eight per thread from a padded layout (index i at i + i/32: the 32
-// lanes of a half-wave on 32 banks).  (A thread reading its own 32 consecutive counters from global memory made 2^15 counters a chain
-// of 32 dependent line fills: 52 us at 10 M pairs, between the histogram and the partition.)
-#define SCAN_TILE 8192u
-__global__ __launch_bounds__(1024) void k_bucket_scan(const u32* __restrict__ bucket_cnt, u32 NB, u32* __restrict__ bucket_start) {
-	__shared__ u32 buf[SCAN_TILE + SCAN_TILE / 32];
-	__shared__ u32 wsum[16];
-	__shared__ u32 s_carry;
-	const u32 t = threadIdx.x, lane = t & 63u, wv = t >> 6;
-	if (t == 0) s_carry = 0;
-	__syncthreads();
-	for (u32 base = 0; base < NB; base += SCAN_TILE) {
-#pragma unroll
-		for (u32 j = 0; j < 8; j++) {
-			const u32 i = j * 1024u + t;
-			buf[i + (i >> 5)] = base + i < NB ? bucket_cnt[base + i] : 0u;
-		}
-		__syncthreads();
-		u32 v[8], sum = 0;
-#pragma unroll
-		for (u32 e = 0; e < 8; e++) { const u32 i = 8u * t + e; v[e] = buf[i + (i >> 5)]; sum += v[e]; }
-		const u32 incl = (u32) vdjx_wave_scan_add((int) sum);
-		if (lane == 63) wsum[wv] = incl;
-		__syncthreads();
-		u32 run = s_carry + incl - sum;
-		for (u32 w = 0; w < wv; w++) run += wsum[w];
-#pragma unroll
-		for (u32 e = 0; e < 8; e++) { const u32 i = 8u * t + e; buf[i + (i >> 5)] = run; run += v[e]; }
-		__syncthreads();
-#pragma unroll
-		for (u32 j = 0; j < 8; j++) {
-			const u32 i = j * 1024u + t;
-			if (base + i < NB) bucket_start[base + i] = buf[i + (i >> 5)];
-		}
-		if (t == 1023) s_carry = run;                         // (thread 1023's running sum is the tile's end)
-		__syncthreads();
-	}
-	if (t == 0) bucket_start[NB] = s_carry;
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -1133,7 +1093,7 @@ __global__ __launch_bounds__(256) void k_compact_partials(const Partial* __restr
 // One workgroup per source: exclusive scan of its NBo counts.
 __global__ __launch_bounds__(1024) void k_seg_offsets(const u32* __restrict__ seg_cnt, const u32* __restrict__ src_base, u32 G, u32 NBo,
                                                       u32* __restrict__ seg_off) {
-	__shared__ u32 part[1024];
+	__shared__ u32 tmp[16];
 	const u32 s = blockIdx.x;
 	const u32* cnt = seg_cnt + (size_t) s * NBo;
 	u32* off = seg_off + (size_t) s * (NBo + 1);
@@ -1142,17 +1102,10 @@ __global__ __launch_bounds__(1024) void k_seg_offsets(const u32* __restrict__ se
 	const u32 hi = lo + per < NBo ? lo + per : NBo;
 	u32 sum = 0;
 	for (u32 i = lo; i < hi; i++) sum += cnt[i];
-	part[threadIdx.x] = sum;
-	__syncthreads();
-	for (u32 d = 1; d < 1024; d <<= 1) {
-		const u32 v = threadIdx.x >= d ? part[threadIdx.x - d] : 0;
-		__syncthreads();
-		part[threadIdx.x] += v;
-		__syncthreads();
-	}
-	u32 run = src_base[s] + (threadIdx.x ? part[threadIdx.x - 1] : 0);
+	u32 total;
+	u32 run = src_base[s] + vdjx_block_scan(sum, tmp, total);
 	for (u32 i = lo; i < hi; i++) { off[i] = run; run += cnt[i]; }
-	if (threadIdx.x == 1023) off[NBo] = src_base[s] + part[1023];
+	if (threadIdx.x == 1023) off[NBo] = src_base[s] + total;
 }
 
 struct PendOut { u64* lo; u64* hi; u32* cg; u64* mg; u32* need; u32* n; u32 cap; u64* mgr; };      // (mgr: SYM, the reverse complement's first gated instance)
@@ -1539,7 +1492,6 @@ __global__ void k_node_flags(const u64* __restrict__ s_lo, const u64* __restrict
 #define IT_INST_BITS 35
 #define IT_INST_MASK ((1ull << IT_INST_BITS) - 1ull)
 #define IT_SURV_SHIFT 38
-int vdjx_sort_pairs_raw(void* tmp, size_t* tmp_bytes, hipStream_t st, u64* k_in, u64* k_out, u32* v_in, u32* v_out, u32 n, unsigned end_bit);     // vdjx_rindex.hip
 #define IT_HOLE 0xFFFFFFFFFFFFFFFFull
 #define WALK_THREADS 256
 
@@ -1705,32 +1657,6 @@ __global__ void k_chain_len(const u64* __restrict__ pd, u32 n, u32* __restrict__
 	u32 h, d;
 	chain_of(pd, v, h, d);
 	atomicAdd(&len[h], 1u);
-}
-
-// exclusive scan of a[0..n) in three launches: block sums (SCAN_BLOCK per workgroup), their scan (k_bucket_scan), the blocks again
-#define SCAN_BLOCK 4096u
-__global__ __launch_bounds__(256) void k_scan_sums(const u32* __restrict__ a, u32 n, u32* __restrict__ sums) {
-	__shared__ u32 part[4];
-	const u32 b0 = blockIdx.x * SCAN_BLOCK;
-	u32 s = 0;
-	for (u32 i = threadIdx.x; i < SCAN_BLOCK; i += 256) s += b0 + i < n ? a[b0 + i] : 0u;
-	s = (u32) vdjx_wave_scan_add((int) s);
-	if ((threadIdx.x & 63) == 63) part[threadIdx.x >> 6] = s;
-	__syncthreads();
-	if (threadIdx.x == 0) sums[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
-}
-__global__ __launch_bounds__(256) void k_scan_apply(const u32* __restrict__ a, u32 n, const u32* __restrict__ sum_start, u32* __restrict__ out) {
-	__shared__ u32 part[5];
-	const u32 b0 = blockIdx.x * SCAN_BLOCK + threadIdx.x * 16;
-	u32 loc[16];
-	u32 s = 0;
-	for (int i = 0; i < 16; i++) { loc[i] = s; s += b0 + i < n ? a[b0 + i] : 0u; }
-	const u32 incl = (u32) vdjx_wave_scan_add((int) s);
-	if ((threadIdx.x & 63) == 63) part[threadIdx.x >> 6] = incl;
-	__syncthreads();
-	u32 base = sum_start[blockIdx.x] + incl - s;
-	for (u32 w = 0; w < (threadIdx.x >> 6); w++) base += part[w];
-	for (int i = 0; i < 16; i++) if (b0 + i < n) out[b0 + i] = base + loc[i];
 }
 
 // the new index of every survivor, and the arrays in the new order
@@ -2602,7 +2528,7 @@ int stage_gated_hist(vdjx_ctx* c, A& db, const vdjx_pool* pool, int k, size_t pe
 		else hipLaunchKernelGGL(k_gated_hist<false>, dim3(nblk), dim3(HIST_THREADS), lds_hist, st, pool->d_bases, pool->d_nmask, pool->d_lowq, R, pool->rl, k, HB, rpb, hcnt, hist_dbg);
 	}
 	dbg_sync(c, "k_gated_hist");
-	hipLaunchKernelGGL(k_bucket_scan, dim3(1), dim3(1024), 0, st, hcnt, NBH, hstart);
+	vdjx_scan_one(st, hcnt, NBH, hstart);
 	HIP_TRY(hipMemcpyAsync(c->h_pin, hstart + NBH, 4, hipMemcpyDeviceToHost, st));
 	HIP_TRY(hipStreamSynchronize(st));
 	HIP_TRY(hipGetLastError());
@@ -2690,7 +2616,7 @@ int stage_gated_cut(vdjx_ctx* c, A& db, const vdjx_pool* pool, u64 rec_base, int
 		HIP_TRY(hipMemsetAsync(fine_cnt, 0, (size_t) NBt * 4, st));
 		vdjx_prof_scope ps(c, "k_seg_hist");
 		hipLaunchKernelGGL(k_seg_hist_g<TUP>, dim3(NBc * slices), dim3(512), 0, st, l1, hstart, HB - cbits, slices, 64 - Tt, fbits, fine_cnt);
-		hipLaunchKernelGGL(k_bucket_scan, dim3(1), dim3(1024), 0, st, fine_cnt, NBt, tstart);
+		vdjx_scan_one(st, fine_cnt, NBt, tstart);
 	} else {
 		hipLaunchKernelGGL(k_pick_u32, dim3((NBt + 1 + 255) / 256), dim3(256), 0, st, hstart, 1u << (HB - Tt), NBt + 1, tstart);
 	}
@@ -2810,13 +2736,12 @@ int stage_recount(vdjx_ctx* c, A& db, const vdjx_pool* pool, u64 rec_base, int k
 	while ((size_t) tmask + 1 < (size_t) ns * 2) tmask = tmask * 2 + 1;
 	unsigned long long* pred;
 	ulonglong2* table;
-	u32 *succ0, *succ, *bloom, *clen, *coff, *csum, *csum_start, *newidx, *jump_open, *fbw, *gcnt2, *bestsucc, *partner = nullptr;
+	u32 *succ0, *succ, *bloom, *clen, *coff, *newidx, *jump_open, *fbw, *gcnt2, *bestsucc, *partner = nullptr;
 	u64 *pd, *lo2, *hi2, *gfirst2, *linw;
 	ulonglong2 *skey0, *skey;
 	u32 bloom_bits = 1u << 16;
 	while (bloom_bits < (1u << 30) && (size_t) bloom_bits < (size_t) ns * 16) bloom_bits <<= 1;
 	const u32 nb16 = (ns + 15u) >> 4;
-	const u32 n_scan = (ns + SCAN_BLOCK - 1) / SCAN_BLOCK;
 	const u32 n_jump = (ceil_log2_u64((u64) ns + 1) + 4) / 5 + 1;      // launches that resolve every chain of up to `ns` nodes (32x each at least)
 	// what has to start as zeros lies in one block, cleared by one launch (six small clears cost the stream their turn-arounds)
 	{
@@ -2836,8 +2761,7 @@ int stage_recount(vdjx_ctx* c, A& db, const vdjx_pool* pool, u64 rec_base, int k
 	}
 	HIP_TRY(db.alloc(&skey0, ns)); HIP_TRY(db.alloc(&skey, ns));
 	HIP_TRY(db.alloc(&succ0, (size_t) ns * 4)); HIP_TRY(db.alloc(&succ, (size_t) ns * 4));
-	HIP_TRY(db.alloc(&pd, ns)); HIP_TRY(db.alloc(&coff, ns));
-	HIP_TRY(db.alloc(&csum, n_scan)); HIP_TRY(db.alloc(&csum_start, n_scan + 1)); HIP_TRY(db.alloc(&newidx, ns));
+	HIP_TRY(db.alloc(&pd, ns)); HIP_TRY(db.alloc(&coff, (size_t) ns + 1)); HIP_TRY(db.alloc(&newidx, ns));
 	HIP_TRY(db.alloc(&lo2, ns)); HIP_TRY(db.alloc(&hi2, ns)); HIP_TRY(db.alloc(&gcnt2, ns)); HIP_TRY(db.alloc(&gfirst2, ns));
 	HIP_TRY(db.alloc(&fbw, nb16));
 	HIP_TRY(db.alloc(&bestsucc, ns));
@@ -2857,9 +2781,7 @@ int stage_recount(vdjx_ctx* c, A& db, const vdjx_pool* pool, u64 rec_base, int k
 		hipLaunchKernelGGL(k_chain_init, gs, bs, 0, st, pred, bestsucc, ns, pd);
 		for (u32 j = 0; j < n_jump; j++) hipLaunchKernelGGL(k_chain_jump, gs, bs, 0, st, pd, ns, j ? jump_open + j - 1 : (const u32*) nullptr, jump_open + j);
 		hipLaunchKernelGGL(k_chain_len, gs, bs, 0, st, pd, ns, clen);
-		hipLaunchKernelGGL(k_scan_sums, dim3(n_scan), dim3(256), 0, st, clen, ns, csum);
-		hipLaunchKernelGGL(k_bucket_scan, dim3(1), dim3(1024), 0, st, csum, n_scan, csum_start);
-		hipLaunchKernelGGL(k_scan_apply, dim3(n_scan), dim3(256), 0, st, clen, ns, csum_start, coff);
+		{ const int rc_ = vdjx_scan_wide(db, st, clen, ns, coff); if (rc_) return rc_; }
 		hipLaunchKernelGGL(k_chain_place, gs, bs, 0, st, pd, coff, ns, newidx);
 		hipLaunchKernelGGL(k_chain_permute, gs, bs, 0, st, newidx, ns, sv.lo, sv.hi, sv.gcnt, sv.gfirst, succ0, lo2, hi2, gcnt2, gfirst2, skey, succ);
 		hipLaunchKernelGGL(k_table_remap, dim3(tmask / 256 + 1), bs, 0, st, table, tmask + 1, newidx);
@@ -3000,7 +2922,7 @@ int stage_recount(vdjx_ctx* c, A& db, const vdjx_pool* pool, u64 rec_base, int k
 		                        n_ranges_p, raw, raw_cap, blk_items, g_cursor, range_cnt, g_err, 0u, (const u32*) nullptr);
 	}
 	dbg_sync(c, "k_walk_items");
-	hipLaunchKernelGGL(k_bucket_scan, dim3(1), dim3(1024), 0, st, range_cnt, n_ranges_p, range_start);
+	vdjx_scan_one(st, range_cnt, n_ranges_p, range_start);
 	// the partitioned items: at most one per instance.  A build that waits for this stage anyway (the sharded one: `defer` is null)
 	// asks how many the walk made and sizes the two partition buffers by that (a tenth of the bound: 12 GB less per rank at 12.5 M
 	// pairs); the one-GPU build does not stop for it.
@@ -3180,7 +3102,7 @@ int stage_finish2(vdjx_ctx* c, A& db, const SurvivorsG& sv, const RecountOut& ro
 		HIP_TRY(db.alloc(&rb_start, nrb + 1));
 		vdjx_prof_scope ps(c, "k_root_list");
 		if (nrb) hipLaunchKernelGGL(k_root_count, dim3(nrb), dim3(256), 0, st, no.from_deg, nr, rb_cnt);
-		hipLaunchKernelGGL(k_bucket_scan, dim3(1), dim3(1024), 0, st, rb_cnt, nrb, rb_start);
+		vdjx_scan_one(st, rb_cnt, nrb, rb_start);
 		if (nrb) hipLaunchKernelGGL(k_root_list, dim3(nrb), dim3(256), 0, st, no.from_deg, nr, rb_start, g->d_roots);
 		HIP_TRY(hipMemcpyAsync(c->h_pin, rb_start + nrb, 4, hipMemcpyDeviceToHost, st));
 	}
@@ -3436,7 +3358,7 @@ static int shard_local_impl(vdjx_shard* s) {
 		else hipLaunchKernelGGL(k_gated_local<TUP>, dim3(t.NB), dim3(LG_THREADS), 0, st, t.t, t.bucket_start, s->pool->d_bases, s->pool->d_nmask, rec_base,
 		                        s->k, s->pool->rl, s->pool->ob, s->tlow, sparse, sparse_ref, s->nd, s->low_inst, g_err, (const u32*) order);
 	}
-	hipLaunchKernelGGL(k_bucket_scan, dim3(1), dim3(1024), 0, st, s->nd, s->NBf, s->dstart);
+	vdjx_scan_one(st, s->nd, s->NBf, s->dstart);
 	u32* d_pick;
 	const u32 G = (u32) s->nranks;
 	HIP_TRY(db.alloc(&d_pick, G + 1));

@@ -13,6 +13,7 @@
 //   stop         k_q_mfin counts the iteration and sets the flag; every kernel of the iteration returns at entry once it is set.  The
 //                host enqueues Q_BATCH iterations and looks at the flag once per batch: no grid-wide barrier, no persistent kernel.
 #include "vdjx_common.h"
+#include "vdjx_scan.h"
 
 #include <algorithm>
 #include <math.h>
@@ -24,9 +25,6 @@
 #define Q_LIGHT 32                       // a pair with more alignments is reduced by the whole wave
 #define Q_CHUNK 2048u                    // alignments per workgroup of the M step
 #define Q_BATCH 32                       // iterations enqueued between two looks at the flag
-#define QS_T 256
-#define QS_PER 8
-#define QS_TILE (QS_T * QS_PER)
 
 struct QState {
 	u32 done, iters;
@@ -41,57 +39,11 @@ __global__ void k_q_degree(const vdjx_pair* __restrict__ pairs, u32 A, u32 P, u3
 	if (p < P) atomicAdd(&deg[p], 1u);
 }
 
-// exclusive prefix of (degree > 0) << 32 | degree over the pairs: the CSR start of a pair in the low word, its slot among the placed
-// pairs in the high word; excl[P] = the totals
-__device__ inline u64 q_deg_key(u32 d) { return d ? (1ull << 32) | d : 0ull; }
-__global__ __launch_bounds__(QS_T) void k_q_scan_tile(const u32* __restrict__ deg, u32 P, u64* __restrict__ excl, u64* __restrict__ tile_sum) {
-	__shared__ u64 s[QS_T];
-	const u64 base = (u64) blockIdx.x * QS_TILE + (u64) threadIdx.x * QS_PER;
-	u64 v[QS_PER], t = 0;
-#pragma unroll
-	for (int k = 0; k < QS_PER; k++) { v[k] = base + k < P ? q_deg_key(deg[base + k]) : 0ull; t += v[k]; }
-	s[threadIdx.x] = t;
-	__syncthreads();
-	for (u32 d = 1; d < QS_T; d <<= 1) {
-		const u64 x = threadIdx.x >= d ? s[threadIdx.x - d] : 0ull;
-		__syncthreads();
-		s[threadIdx.x] += x;
-		__syncthreads();
-	}
-	u64 run = s[threadIdx.x] - t;
-#pragma unroll
-	for (int k = 0; k < QS_PER; k++) { if (base + k < P) excl[base + k] = run; run += v[k]; }
-	if (threadIdx.x == QS_T - 1) tile_sum[blockIdx.x] = s[threadIdx.x];
-}
-// the tile sums' exclusive prefix in place (one workgroup), their total to *total
-__global__ __launch_bounds__(1024) void k_q_scan_sums(u64* __restrict__ ts, u32 nt, u64* __restrict__ total) {
-	__shared__ u64 s[1024];
-	__shared__ u64 carry;
-	if (threadIdx.x == 0) carry = 0;
-	__syncthreads();
-	for (u32 b = 0; b < nt; b += 1024) {
-		const u32 i = b + threadIdx.x;
-		const u64 v = i < nt ? ts[i] : 0ull;
-		s[threadIdx.x] = v;
-		__syncthreads();
-		for (u32 d = 1; d < 1024; d <<= 1) {
-			const u64 x = threadIdx.x >= d ? s[threadIdx.x - d] : 0ull;
-			__syncthreads();
-			s[threadIdx.x] += x;
-			__syncthreads();
-		}
-		const u64 c0 = carry;
-		if (i < nt) ts[i] = c0 + s[threadIdx.x] - v;
-		__syncthreads();
-		if (threadIdx.x == 1023) carry = c0 + s[1023];
-		__syncthreads();
-	}
-	if (threadIdx.x == 0) *total = carry;
-}
-__global__ void k_q_scan_add(u64* __restrict__ excl, u32 P, const u64* __restrict__ tile_pre) {
-	const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i < P) excl[i] += tile_pre[i / QS_TILE];
-}
+// what the scan over the pairs sums (vdjx_scan_wide's load functor): (degree > 0) << 32 | degree.  The exclusive prefix holds the CSR
+// start of a pair in the low word, its slot among the placed pairs in the high word; excl[P] = the totals
+struct q_deg_key {
+	__device__ u64 operator()(u32 d) const { return d ? (1ull << 32) | d : 0ull; }
+};
 
 // seg[q] = first slot of placed pair q, seg[placed] = A
 __global__ void k_q_csr(const u32* __restrict__ deg, const u64* __restrict__ excl, u32 P, u32* __restrict__ seg) {
@@ -318,14 +270,12 @@ extern "C" int vdjx_quant(vdjx_ctx* c, const char* contigs, size_t n, int len, c
 
 	vdjx_work db(c);
 	u32 *d_deg, *d_seg, *d_tmp, *d_perm, *d_hist, *d_ct, *d_cstart;
-	u64 *d_excl, *d_tiles, *d_off;
+	u64 *d_excl, *d_off;
 	double *d_gtab, *d_g, *d_r, *d_N, *d_part;
 	uint2* d_chunks;
 	QState* d_st;
-	const u32 ntiles = (P + QS_TILE - 1) / QS_TILE;
 	HIP_TRY(db.alloc(&d_deg, (size_t) P + 1));
 	HIP_TRY(db.alloc(&d_excl, (size_t) P + 1));
-	HIP_TRY(db.alloc(&d_tiles, (size_t) ntiles + 1));
 	HIP_TRY(db.alloc(&d_seg, (size_t) P + 1));
 	HIP_TRY(db.alloc(&d_tmp, (size_t) A));
 	HIP_TRY(db.alloc(&d_perm, (size_t) A));
@@ -350,9 +300,7 @@ extern "C" int vdjx_quant(vdjx_ctx* c, const char* contigs, size_t n, int len, c
 	{
 		vdjx_prof_scope ps(c, "k_quant_setup");
 		hipLaunchKernelGGL(k_q_degree, dim3(gA), dim3(256), 0, st, d_pairs, A, P, d_deg);
-		if (ntiles) hipLaunchKernelGGL(k_q_scan_tile, dim3(ntiles), dim3(QS_T), 0, st, (const u32*) d_deg, P, d_excl, d_tiles);
-		hipLaunchKernelGGL(k_q_scan_sums, dim3(1), dim3(1024), 0, st, d_tiles, ntiles, d_excl + P);
-		if (P) hipLaunchKernelGGL(k_q_scan_add, dim3(gP), dim3(256), 0, st, d_excl, P, (const u64*) d_tiles);
+		{ const int rc_ = vdjx_scan_wide(db, st, (const u32*) d_deg, P, d_excl, q_deg_key()); if (rc_) return rc_; }
 		hipLaunchKernelGGL(k_q_csr, dim3(gP ? gP : 1), dim3(256), 0, st, (const u32*) d_deg, (const u64*) d_excl, P, d_seg);
 		hipLaunchKernelGGL(k_q_scatter, dim3(gA), dim3(256), 0, st, d_pairs, A, P, (const u64*) d_excl, d_deg, d_tmp);
 	}

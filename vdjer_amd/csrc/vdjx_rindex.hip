@@ -15,6 +15,7 @@
 // Everything is counting, scanning and two key sorts (class-major: registration order inside a class for the CSR, a hash of the
 // info for the folding); no host pass over the records.  Round 2 did this on the host: 3.8 s at 10 M pairs.
 #include "vdjx_common.h"
+#include "vdjx_scan.h"
 
 #include <string.h>
 #include <thread>
@@ -38,55 +39,7 @@ template <typename T> hipError_t ri_keep(T** p, size_t* cap, size_t bytes) {
 	return e;
 }
 
-// ---- exclusive scan of u32 counts (n up to 2^31): out[0..n], out[n] = total -------------------------------------------------
-#define RS_BLOCK 2048u
-__global__ __launch_bounds__(256) void k_rs_local(const u32* __restrict__ cnt, u32 n, u32* __restrict__ pre, u32* __restrict__ bsum) {
-	__shared__ u32 part[4];
-	const u32 base = blockIdx.x * RS_BLOCK + threadIdx.x * 8u;
-	u32 v[8], s = 0;
-#pragma unroll
-	for (int i = 0; i < 8; i++) { v[i] = base + i < n ? cnt[base + i] : 0u; s += v[i]; }
-	const u32 incl = (u32) vdjx_wave_scan_add((int) s);
-	if ((threadIdx.x & 63u) == 63u) part[threadIdx.x >> 6] = incl;
-	__syncthreads();
-	u32 run = incl - s;
-	for (u32 w = 0; w < (threadIdx.x >> 6); w++) run += part[w];
-#pragma unroll
-	for (int i = 0; i < 8; i++) { if (base + i < n) pre[base + i] = run; run += v[i]; }
-	if (threadIdx.x == 255) bsum[blockIdx.x] = run;
-}
-// block sums -> their exclusive prefix, one workgroup (up to a few million block sums)
-__global__ __launch_bounds__(1024) void k_rs_top(const u32* __restrict__ cnt, u32 n, u32* __restrict__ pre) {
-	__shared__ u32 part[16];
-	const u32 per = (n + 1023) / 1024;
-	const u32 lo = threadIdx.x * per;
-	const u32 hi = lo + per < n ? lo + per : n;
-	u32 s = 0;
-	for (u32 i = lo; i < hi && lo < n; i++) s += cnt[i];
-	const u32 incl = (u32) vdjx_wave_scan_add((int) s);
-	if ((threadIdx.x & 63u) == 63u) part[threadIdx.x >> 6] = incl;
-	__syncthreads();
-	u32 run = incl - s;
-	for (u32 w = 0; w < (threadIdx.x >> 6); w++) run += part[w];
-	for (u32 i = lo; i < hi && lo < n; i++) { pre[i] = run; run += cnt[i]; }
-	if (threadIdx.x == 1023) pre[n] = run;
-}
-__global__ void k_rs_add(u32* __restrict__ pre, u32 n, const u32* __restrict__ bpre) {
-	const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i < n) pre[i] += bpre[i / RS_BLOCK];
-	if (i == 0) pre[n] = bpre[(n + RS_BLOCK - 1) / RS_BLOCK];
-}
-
-int scan_u32(vdjx_work& db, hipStream_t st, const u32* d_cnt, u32 n, u32* d_pre) {
-	const u32 nb = (n + RS_BLOCK - 1) / RS_BLOCK;
-	u32 *bsum, *bpre;
-	HIP_TRY(db.alloc(&bsum, nb + 1));
-	HIP_TRY(db.alloc(&bpre, nb + 1));
-	if (nb) hipLaunchKernelGGL(k_rs_local, dim3(nb), dim3(256), 0, st, d_cnt, n, d_pre, bsum);
-	hipLaunchKernelGGL(k_rs_top, dim3(1), dim3(1024), 0, st, bsum, nb, bpre);
-	hipLaunchKernelGGL(k_rs_add, dim3(n / 256 + 1), dim3(256), 0, st, d_pre, n, bpre);
-	return VDJX_OK;
-}
+#define RI_SB 2048u        // table slots per workgroup of k_ri_occ / k_ri_number*: 8 per thread, one count per workgroup
 
 // ---- the table ------------------------------------------------------------------------------------------------------------------
 // slots name a representative record (claiming a slot is one 32-bit CAS).  Records holding an 'N' are left out: contigs are
@@ -158,7 +111,7 @@ __global__ void k_ri_insert_sym(const u64* __restrict__ bases, const u64* __rest
 // neighbour; none for a sequence that is its own reverse complement)
 __global__ __launch_bounds__(256) void k_ri_number_sym(u32* __restrict__ slots, u32 nslots, const u32* __restrict__ bpre, u32* __restrict__ rep) {
 	__shared__ u32 part[4];
-	const u32 base = blockIdx.x * RS_BLOCK + threadIdx.x * 8u;
+	const u32 base = blockIdx.x * RI_SB + threadIdx.x * 8u;
 	u32 v[8], s = 0;
 #pragma unroll
 	for (int i = 0; i < 8; i++) { v[i] = base + i < nslots ? slots[base + i] : 0u; s += v[i] != 0; }
@@ -179,7 +132,7 @@ __global__ __launch_bounds__(256) void k_ri_number_sym(u32* __restrict__ slots, 
 // classes are numbered in slot order (any numbering serves: a class id is an identity, never an order)
 __global__ __launch_bounds__(256) void k_ri_occ(const u32* __restrict__ slots, u32 nslots, u32* __restrict__ bcnt) {
 	__shared__ u32 part[4];
-	const u32 base = blockIdx.x * RS_BLOCK + threadIdx.x * 8u;
+	const u32 base = blockIdx.x * RI_SB + threadIdx.x * 8u;
 	u32 s = 0;
 	if (base + 8 <= nslots) {
 		const uint4 a = *(const uint4*) &slots[base], b = *(const uint4*) &slots[base + 4];
@@ -193,7 +146,7 @@ __global__ __launch_bounds__(256) void k_ri_occ(const u32* __restrict__ slots, u
 }
 __global__ __launch_bounds__(256) void k_ri_number(u32* __restrict__ slots, u32 nslots, const u32* __restrict__ bpre, u32* __restrict__ rep) {
 	__shared__ u32 part[4];
-	const u32 base = blockIdx.x * RS_BLOCK + threadIdx.x * 8u;
+	const u32 base = blockIdx.x * RI_SB + threadIdx.x * 8u;
 	u32 v[8], s = 0;
 #pragma unroll
 	for (int i = 0; i < 8; i++) { v[i] = base + i < nslots ? slots[base + i] : 0u; s += v[i] != 0; }
@@ -638,7 +591,7 @@ int read_index_build_dev(vdjx_ctx* c, vdjx_work& db, const vdjx_pool* pool, cons
 		else hipLaunchKernelGGL((k_ri_insert<VDJX_LONG_W, VDJX_LONG_M>), gR, b256, 0, st, pool->d_bases, pool->d_nmask, R, d_slots, mask, d_rec_slot);
 	}
 	// classes
-	const u32 nsb = (u32) ((nslots + RS_BLOCK - 1) / RS_BLOCK);
+	const u32 nsb = (u32) ((nslots + RI_SB - 1) / RI_SB);
 	u32 *d_bcnt, *d_bpre;
 	HIP_TRY(db.alloc(&d_bcnt, nsb + 1));
 	HIP_TRY(db.alloc(&d_bpre, nsb + 1));
@@ -646,9 +599,9 @@ int read_index_build_dev(vdjx_ctx* c, vdjx_work& db, const vdjx_pool* pool, cons
 		vdjx_prof_scope ps(pc, "k_ri_number");
 		hipLaunchKernelGGL(k_ri_occ, dim3(nsb), b256, 0, st, d_slots, (u32) nslots, d_bcnt);
 	}
-	// (two levels: one workgroup over the 32,768 block counts of a 10 M-pair pool's table was 56 us)
-	if (nsb > 4096) { const int rc_ = scan_u32(db, st, d_bcnt, nsb, d_bpre); if (rc_) return rc_; }
-	else hipLaunchKernelGGL(k_rs_top, dim3(1), dim3(1024), 0, st, d_bcnt, nsb, d_bpre);
+	// (two levels for the 32,768 block counts of a 10 M-pair pool's table: vdjx_scan.h)
+	if (nsb > 4096) { const int rc_ = vdjx_scan_wide(db, st, d_bcnt, nsb, d_bpre); if (rc_) return rc_; }
+	else vdjx_scan_one(st, d_bcnt, nsb, d_bpre);
 	u32 ncls = 0;
 	HIP_TRY(hipMemcpyAsync(&ncls, d_bpre + nsb, 4, hipMemcpyDeviceToHost, st));
 	HIP_TRY(hipStreamSynchronize(st));
@@ -690,7 +643,7 @@ int read_index_build_dev(vdjx_ctx* c, vdjx_work& db, const vdjx_pool* pool, cons
 		vdjx_prof_scope ps(pc, "k_ri_records");
 		if (nrb && sym) hipLaunchKernelGGL(k_ri_records<true>, dim3(nrb), b256, 0, st, d_rec_slot, d_slots, R, d_pair, d_rnum, d_rc, d_reg, n_pairs, d_rec_cls, d_r2key, d_err, d_rbcnt);
 		else if (nrb) hipLaunchKernelGGL(k_ri_records<false>, dim3(nrb), b256, 0, st, d_rec_slot, d_slots, R, d_pair, d_rnum, d_rc, d_reg, n_pairs, d_rec_cls, d_r2key, d_err, d_rbcnt);
-		hipLaunchKernelGGL(k_rs_top, dim3(1), dim3(1024), 0, st, d_rbcnt, nrb, d_rbpre);
+		vdjx_scan_one(st, d_rbcnt, nrb, d_rbpre);
 		hipLaunchKernelGGL(k_ri_split, dim3(1), b256, 0, st, d_err, d_rec_cls, d_rnum, d_pair, R, n_pairs, d_rbpre, d_split);
 	}
 	u32 h_err[4] = {0, 0, 0, 0}, n1 = 0, n1p = 0;
@@ -713,7 +666,7 @@ int read_index_build_dev(vdjx_ctx* c, vdjx_work& db, const vdjx_pool* pool, cons
 		vdjx_prof_scope ps(pc, "k_ri_members");
 		if (nrb) hipLaunchKernelGGL(k_ri_members, dim3(nrb), b256, 0, st, d_rec_cls, d_rnum, d_reg, d_pair, d_r2key, c->d_pair_r2, R, n_pairs, d_rbpre, c->d_ri_cnt1, d_mkey, d_mreg, d_mpack);
 	}
-	int rc = scan_u32(db, st, c->d_ri_cnt1, ncls + 1, c->d_ri_start);         // (cnt1[ncls] = 0: start[ncls] = start[ncls + 1] = members)
+	int rc = vdjx_scan_wide(db, st, c->d_ri_cnt1, ncls + 1, c->d_ri_start);         // (cnt1[ncls] = 0: start[ncls] = start[ncls + 1] = members)
 	if (rc) return rc;
 	// CSR order = (class, registration rank)
 	HIP_TRY(ri_keep(&c->d_ri_recs, &c->ri_cap[5], ((size_t) n1 + 1) * 4));
@@ -810,6 +763,29 @@ int vdjx_sort_pairs_raw(void* tmp, size_t* tmp_bytes, hipStream_t st, u64* k_in,
 // (the scorers sort their strings with the same helper: vdjx_score.hip)
 int vdjx_sort_pairs(vdjx_work& db, hipStream_t st, u64* k_in, u64* k_out, u32* v_in, u32* v_out, u32 n, unsigned end_bit) {
 	return sort_pairs(db, st, k_in, k_out, v_in, v_out, n, end_bit);
+}
+
+// the scan primitive on its own, for the test suite (include/vdjx.h)
+extern "C" int vdjx_scan_u32(vdjx_ctx* c, const uint32_t* host_in, size_t n, int out_is_u64, int launches, void* host_out) {
+	if (!c || !host_out || (n && !host_in) || n >= (1ull << 31) || (launches != 1 && launches != 3)) { vdjx_set_error("vdjx_scan_u32: bad argument"); return VDJX_EINVAL; }
+	HIP_TRY(hipSetDevice(c->device));
+	vdjx_clear_errors();
+	hipStream_t st = c->stream;
+	vdjx_work db(c);
+	u32* d_in;
+	u64* d_out;                  // (room for either width)
+	HIP_TRY(db.alloc(&d_in, n));
+	HIP_TRY(db.alloc(&d_out, n + 1));
+	if (n) HIP_TRY(hipMemcpyAsync(d_in, host_in, n * 4, hipMemcpyHostToDevice, st));
+	int rc = VDJX_OK;
+	if (launches == 1 && out_is_u64) vdjx_scan_one(st, (const u32*) d_in, (u32) n, d_out);
+	else if (launches == 1) vdjx_scan_one(st, (const u32*) d_in, (u32) n, (u32*) d_out);
+	else rc = out_is_u64 ? vdjx_scan_wide(db, st, (const u32*) d_in, (u32) n, d_out) : vdjx_scan_wide(db, st, (const u32*) d_in, (u32) n, (u32*) d_out);
+	if (rc) return rc;
+	HIP_TRY(hipMemcpyAsync(host_out, d_out, (n + 1) * (out_is_u64 ? 8 : 4), hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipStreamSynchronize(st));
+	HIP_TRY(hipGetLastError());
+	return VDJX_OK;
 }
 
 // ---- a build begun and ended (the index beside the k-mer build) -----------------------------------------------------------------

@@ -8,6 +8,7 @@
 // None of this is a dense contraction: the DP is a max-plus recurrence on int8 cells, the mapper is
 // exact-match hashing, the validator is counting.  They run on the VALU/LDS; MFMA does not apply.
 #include "vdjx_common.h"
+#include "vdjx_scan.h"
 
 #include <algorithm>
 #include <numeric>
@@ -127,63 +128,6 @@ __global__ void k_seed_count(const char* __restrict__ kmers, u32 n, int k, int v
 	}
 	hit_lo[w] = lo;
 	hit_cnt[w] = cnt;
-}
-
-// exclusive scan of cnt[n] -> pre[n+1], one 1024-thread workgroup (n up to a few million)
-__global__ __launch_bounds__(1024) void k_scan_u32(const u32* __restrict__ cnt, u32 n, u32* __restrict__ pre) {
-	__shared__ u32 part[1024];
-	const u32 per = (n + 1023) / 1024;
-	const u32 lo = threadIdx.x * per;
-	const u32 hi = lo + per < n ? lo + per : n;
-	u32 s = 0;
-	for (u32 i = lo; i < hi; i++) s += cnt[i];
-	part[threadIdx.x] = s;
-	__syncthreads();
-	for (u32 d = 1; d < 1024; d <<= 1) {
-		u32 v = threadIdx.x >= d ? part[threadIdx.x - d] : 0;
-		__syncthreads();
-		part[threadIdx.x] += v;
-		__syncthreads();
-	}
-	u32 run = threadIdx.x ? part[threadIdx.x - 1] : 0;
-	for (u32 i = lo; i < hi; i++) { pre[i] = run; run += cnt[i]; }
-	if (threadIdx.x == 1023) pre[n] = part[1023];
-}
-
-// coalesced two-level exclusive scan: per-workgroup local scan of 2048 elements + block sums
-__global__ __launch_bounds__(256) void k_scan_local(const u32* __restrict__ cnt, u32 n, u32* __restrict__ pre, u32* __restrict__ bsum) {
-	__shared__ u32 part[256];
-	const u32 base = blockIdx.x * 2048u + threadIdx.x * 8u;
-	u32 v[8], s = 0;
-#pragma unroll
-	for (int i = 0; i < 8; i++) { v[i] = base + i < n ? cnt[base + i] : 0u; s += v[i]; }
-	part[threadIdx.x] = s;
-	__syncthreads();
-	for (u32 d = 1; d < 256; d <<= 1) {
-		u32 x = threadIdx.x >= d ? part[threadIdx.x - d] : 0;
-		__syncthreads();
-		part[threadIdx.x] += x;
-		__syncthreads();
-	}
-	u32 run = part[threadIdx.x] - s;
-#pragma unroll
-	for (int i = 0; i < 8; i++) { if (base + i < n) pre[base + i] = run; run += v[i]; }
-	if (threadIdx.x == 255) bsum[blockIdx.x] = part[255];
-}
-
-// (the tiling of k_scan_local: 2,048 elements per workgroup, eight consecutive ones per thread, one block prefix per workgroup; a
-// thread per element with its own bpre[i / 2048] took 197 us for 1.8 M elements)
-__global__ __launch_bounds__(256) void k_scan_add(u32* __restrict__ pre, u32 n, const u32* __restrict__ bpre) {
-	const u32 add = bpre[blockIdx.x];
-	const u32 base = blockIdx.x * 2048u + threadIdx.x * 8u;
-	if (base + 8u <= n) {
-		uint4* p = (uint4*) (pre + base);
-		uint4 a = p[0], b = p[1];
-		a.x += add; a.y += add; a.z += add; a.w += add; b.x += add; b.y += add; b.z += add; b.w += add;
-		p[0] = a; p[1] = b;
-	} else
-		for (u32 i = base; i < n; i++) pre[i] += add;
-	if (blockIdx.x == 0 && threadIdx.x == 0) pre[n] = bpre[(n + 2047u) / 2048u];
 }
 
 // one thread per (root, seed offset, hit): for every line run the (k+1) x (2k+1) DP (seq_score.c:76-116) on
@@ -337,15 +281,7 @@ static int root_score_device(vdjx_ctx* c, vdjx_work& db, const char* d_k, size_t
 		vdjx_prof_scope ps(c, "k_seed_count");
 		hipLaunchKernelGGL(k_seed_count, dim3((ng + 255) / 256), dim3(256), 0, st, d_k, (u32) n, k, c->vk, c->d_seed_code, (u32) c->n_seeds, d_lo, d_cnt);
 	}
-	{
-		const u32 nb = (ng + 2047u) / 2048u;
-		u32 *d_bsum, *d_bpre;
-		HIP_TRY(db.alloc(&d_bsum, nb));
-		HIP_TRY(db.alloc(&d_bpre, nb + 1));
-		hipLaunchKernelGGL(k_scan_local, dim3(nb), dim3(256), 0, st, d_cnt, ng, d_pre, d_bsum);
-		hipLaunchKernelGGL(k_scan_u32, dim3(1), dim3(1024), 0, st, d_bsum, nb, d_bpre);
-		hipLaunchKernelGGL(k_scan_add, dim3(nb), dim3(256), 0, st, d_pre, ng, d_bpre);
-	}
+	{ const int rc_ = vdjx_scan_wide(db, st, d_cnt, ng, d_pre); if (rc_) return rc_; }
 	// the DP is launched for as many items as the last call had before the host knows this call's number (its copy is queued first:
 	// the host waits for that event only, and adds a launch for what is beyond the guess)
 	u32* h_run = begun ? (u32*) c->h_pin + VDJX_HPIN_ROOT_RUN : (u32*) c->h_pin;          // (a begun call's number waits in a place no other call writes: vdjx_common.h)
@@ -819,17 +755,6 @@ __device__ inline u32 slice_contig(const u32* __restrict__ slice_start, u32 n, u
 #define MAP_SLICE_MAX 32768u     // ... and at most: as long as ~8 k slices remain (every slice loads its contig's image once)
 struct PlanOut { u64 total_hits, inst_total; u32 inst_max, chunk, nwork, pad; };
 
-__device__ inline u32 plan_block_scan(u32 v, u32* tmp, u32& total) {       // exclusive prefix over the threads of the workgroup (all call it; at most 1024)
-	const u32 incl = (u32) vdjx_wave_scan_add((int) v);
-	__syncthreads();
-	if ((threadIdx.x & 63u) == 63u) tmp[threadIdx.x >> 6] = incl;
-	__syncthreads();
-	u32 base = 0, tot = 0;
-	for (u32 w = 0; w < blockDim.x / 64; w++) { const u32 x = tmp[w]; if (w < (threadIdx.x >> 6)) base += x; tot += x; }
-	total = tot;
-	return base + incl - v;
-}
-
 // One workgroup: off[i] = hits before string i (u64), order[] = strings by descending bit length of their hit count (sorted) or as
 // they come, wstart[j] = work items before position j of that order, where string i has ceil(hits / chunk) of them (at least one if
 // min_one).  chunk_fixed == 0: the slice length of k_map_emit, chosen from the total.  A stable_sort of 20,000 windows on the host,
@@ -845,7 +770,7 @@ __global__ __launch_bounds__(1024) void k_plan(const u32* __restrict__ hits_g, c
 		__syncthreads();
 	}
 	const u32* hits = staged ? hits_l : hits_g;
-	__shared__ u64 part[1024];
+	__shared__ u64 tmp64[16];
 	__shared__ u32 tmp[16];
 	__shared__ u64 s_inst;
 	__shared__ u32 s_imax, s_chunk;
@@ -858,16 +783,8 @@ __global__ __launch_bounds__(1024) void k_plan(const u32* __restrict__ hits_g, c
 	u32 im = 0;
 	for (u32 i = lo; i < hi; i++) s += hits[i];
 	for (u32 i = tid; i < n; i += 1024) { const u32 x = inst[i]; is += x; im = im > x ? im : x; }      // (sum and maximum: any order)
-	part[tid] = s;
-	__syncthreads();
-	for (u32 d = 1; d < 1024; d <<= 1) {
-		const u64 v = tid >= d ? part[tid - d] : 0;
-		__syncthreads();
-		part[tid] += v;
-		__syncthreads();
-	}
-	const u64 total = part[1023];
-	u64 run = part[tid] - s;
+	u64 total;
+	u64 run = vdjx_block_scan(s, tmp64, total);
 	for (u32 i = lo; i < hi; i++) { off[i] = run; run += hits[i]; }
 	if (is) atomicAdd((unsigned long long*) &s_inst, (unsigned long long) is);
 	if (im) atomicMax(&s_imax, im);
@@ -906,7 +823,7 @@ __global__ __launch_bounds__(1024) void k_plan(const u32* __restrict__ hits_g, c
 		wc += (min_one && !it) ? 1u : it;
 	}
 	u32 wtot;
-	u32 wrun = plan_block_scan(wc, tmp, wtot);
+	u32 wrun = vdjx_block_scan(wc, tmp, wtot);
 	for (u32 j = lo; j < hi; j++) {
 		const u32 h = hits[sorted ? order[j] : j];
 		const u32 it = (h + chunk - 1) / chunk;
@@ -1220,8 +1137,8 @@ __global__ __launch_bounds__(GP_THREADS, GP_WAVES) void k_group_pairs(ReadIndexD
 			hs += hv[j]; cs += cv[j];
 		}
 		u32 htot, ctot;
-		u32 hx = plan_block_scan(hs, s_tmp, htot);
-		u32 cx = plan_block_scan(cs, s_tmp, ctot);
+		u32 hx = vdjx_block_scan(hs, s_tmp, htot);
+		u32 cx = vdjx_block_scan(cs, s_tmp, ctot);
 		__syncthreads();
 #pragma unroll
 		for (u32 j = 0; j < PER; j++) {
@@ -1739,26 +1656,7 @@ __global__ __launch_bounds__(MAP_THREADS, ME_WAVES) void k_map_emit(ReadIndexDev
 	if (tid == 0) slice_cnt[blockIdx.x] = s_cnt;
 }
 
-// exclusive u64 prefix of the slice counts (one workgroup) and, from it, the pairs of every contig
-__global__ __launch_bounds__(1024) void k_slice_scan(const u32* __restrict__ cnt, u32 n, u64* __restrict__ pre) {
-	__shared__ u64 part[1024];
-	const u32 per = (n + 1023) / 1024;
-	const u32 lo = threadIdx.x * per;
-	const u32 hi = lo + per < n ? lo + per : n;
-	u64 s = 0;
-	for (u32 i = lo; i < hi; i++) s += cnt[i];
-	part[threadIdx.x] = s;
-	__syncthreads();
-	for (u32 d = 1; d < 1024; d <<= 1) {
-		const u64 v = threadIdx.x >= d ? part[threadIdx.x - d] : 0;
-		__syncthreads();
-		part[threadIdx.x] += v;
-		__syncthreads();
-	}
-	u64 run = threadIdx.x ? part[threadIdx.x - 1] : 0;
-	for (u32 i = lo; i < hi; i++) { pre[i] = run; run += cnt[i]; }
-	if (threadIdx.x == 1023) pre[n] = part[1023];
-}
+// the pairs of every contig from the exclusive u64 prefix of the slice counts
 __global__ void k_contig_counts(const u64* __restrict__ slice_pre, const u32* __restrict__ slice_start, u32 n, u64* __restrict__ out) {
 	const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i < n) out[i] = slice_pre[slice_start[i + 1]] - slice_pre[slice_start[i]];
@@ -1840,7 +1738,6 @@ struct MapPlan {
 	bool gstat = false;
 	PlanOut tot{};
 };
-int vdjx_sort_pairs(vdjx_work& db, hipStream_t st, u64* k_in, u64* k_out, u32* v_in, u32* v_out, u32 n, unsigned end_bit);     // vdjx_rindex.hip
 // the plan's totals once they have come down: the host waits for the EVENT behind their copy, not for the stream (work launched behind
 // the plan keeps the device busy meanwhile)
 static int plan_finish(vdjx_ctx* c, MapPlan* mp) {
@@ -2349,7 +2246,7 @@ static int map_emit_impl(vdjx_ctx* c, const char* contigs, size_t n, int len, ui
 				else
 					hipLaunchKernelGGL(k_map_emit<MAP_MAXOFF>, dim3((u32) nsl), dim3(MAP_THREADS), 0, st, ix, mp.d_prep, (u32) n, len, slice_hits, b_sstart, b_off, (vdjx_pair*) c->me_pairs, (u32*) c->me_hit, b_bits, b_scnt);
 			}
-			hipLaunchKernelGGL(k_slice_scan, dim3(1), dim3(1024), 0, st, b_scnt, (u32) nsl, b_pre);
+			vdjx_scan_one(st, b_scnt, (u32) nsl, b_pre);
 			hipLaunchKernelGGL(k_contig_counts, dim3((u32) (n + 255) / 256), dim3(256), 0, st, b_pre, b_sstart, (u32) n, b_cnt);
 			HIP_TRY(hipMemcpyAsync(c->me_cnt.data(), b_cnt, n * 8, hipMemcpyDeviceToHost, st));
 			HIP_TRY(hipEventRecord(c->ev_plan, st));
@@ -2624,7 +2521,7 @@ static int sam_text_device(vdjx_ctx* c, vdjx_work& db, const char* contigs, size
 	{
 		vdjx_prof_scope ps(c, "k_sam_text");
 		hipLaunchKernelGGL(k_sam_len, dim3((u32) ((total + 255) / 256)), dim3(256), 0, st, s, total, d_len);
-		hipLaunchKernelGGL(k_slice_scan, dim3(1), dim3(1024), 0, st, d_len, (u32) total, d_at);
+		vdjx_scan_one(st, d_len, (u32) total, d_at);
 		HIP_TRY(hipMemcpyAsync(&nbytes, d_at + total, 8, hipMemcpyDeviceToHost, st));
 		HIP_TRY(hipStreamSynchronize(st));           // (also: `offs` and the ids have left the host)
 		HIP_TRY(hipGetLastError());
@@ -2745,13 +2642,13 @@ extern "C" int vdjx_sam_merge(vdjx_ctx* c, uint64_t n_blocks, uint64_t n_bytes, 
 	HIP_TRY(db.alloc(&d_l2, (size_t) nb + 1));
 	HIP_TRY(db.alloc(&d_out, (size_t) n_bytes + 16));
 	// where every block starts in the text as it came (source after source, every source's blocks in its own order: one running sum)
-	hipLaunchKernelGGL(k_slice_scan, dim3(1), dim3(1024), 0, st, (const u32*) d_lens, nb, d_from);
+	vdjx_scan_one(st, (const u32*) d_lens, nb, d_from);
 	HIP_TRY(hipMemcpyAsync(d_kin, d_keys, (size_t) nb * 8, hipMemcpyDeviceToDevice, st));       // (the sort may use its input as scratch)
 	hipLaunchKernelGGL(k_iota_u32, dim3(nb / 256 + 1), dim3(256), 0, st, d_idx, nb);
 	int rc = vdjx_sort_pairs(db, st, d_kin, d_k2, d_idx, d_idx2, nb, 64u);
 	if (rc) return rc;
 	hipLaunchKernelGGL(k_take_u32, dim3(nb / 256 + 1), dim3(256), 0, st, (const u32*) d_lens, d_idx2, nb, d_l2);
-	hipLaunchKernelGGL(k_slice_scan, dim3(1), dim3(1024), 0, st, d_l2, nb, d_at);
+	vdjx_scan_one(st, d_l2, nb, d_at);
 	u64 tot_in = 0, tot_out = 0;
 	HIP_TRY(hipMemcpyAsync(&tot_in, d_from + nb, 8, hipMemcpyDeviceToHost, st));
 	HIP_TRY(hipMemcpyAsync(&tot_out, d_at + nb, 8, hipMemcpyDeviceToHost, st));

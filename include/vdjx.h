@@ -400,7 +400,12 @@ int vdjx_scan_u32(vdjx_ctx* ctx, const uint32_t* host_in, size_t n, int out_is_u
  * "map_hits", "root_dp_items".  Unknown names return 0.  Used by bench.py to price the scorers' algorithmic bytes.  vdjx_quant's last
  * call: "quant_map_us", "quant_setup_us", "quant_em_us" (host clock, each phase ending in a wait for the device), "quant_contigs_placed".
  * vdjx_annotate's last call: "annot_cells" (DP cells of the scoring phase), "annot_score_us", "annot_trace_us", "annot_cigar_truncated".
- * vdjx_isotype's last call: "iso_cells" (DP cells of the scoring phase), "iso_score_us", "iso_trace_us" (host clock, each ending in a wait). */
+ * vdjx_isotype's last call: "iso_cells" (DP cells of the scoring phase), "iso_score_us", "iso_trace_us" (host clock, each ending in a wait).
+ * What the context keeps from call to call outside its workspaces (anchor bitmaps, V region, read index, the scorers' result and SAM
+ * buffers, upload staging, germline / constant sets), counted when asked: "kept_device_bytes", "kept_pinned_bytes" (page-locked host
+ * memory) and "kept_allocs" (allocations made for them since vdjx_init: unchanged by a call that fitted what was there).  vdjx_trim
+ * and vdjx_read_index_drop lower the byte counts.  Defined while no begun read-index build is in flight (it grows the index's arrays
+ * on a thread of its own). */
 uint64_t vdjx_stat(vdjx_ctx* ctx, const char* name);
 
 /* ---- profiling hooks (HIP events on the context's stream) ---------------------------------------*/

@@ -289,13 +289,7 @@ static int an_set_load(vdjx_ctx* c, vdjx_recset& s, int ncls, const char* seqs, 
 	}
 	HIP_TRY(hipSetDevice(c->device));
 	HIP_TRY(hipStreamSynchronize(c->stream));
-	if (h.size() > s.cap) {
-		if (s.d_cols) HIP_TRY(hipFree(s.d_cols));
-		s.d_cols = nullptr;
-		s.cap = 0;
-		HIP_TRY(hipMalloc(&s.d_cols, h.size()));
-		s.cap = h.size();
-	}
+	HIP_TRY(s.d_cols.reserve(h.size(), 0));
 	HIP_TRY(hipMemcpy(s.d_cols, h.data(), h.size(), hipMemcpyHostToDevice));
 	s.loaded = true;
 	return VDJX_OK;

@@ -42,14 +42,14 @@ __global__ void k_anchor_probe(const char* __restrict__ contig, int len, const u
 
 // the set's codes go up into a buffer the context keeps (no hipMalloc / hipFree -- the latter waits for the whole device -- per load: a
 // --config4 step loads a new chain's sets with every pool), behind the clearing of its bitmap on the same stream; the caller waits once
-static int load_set(vdjx_ctx* c, const u32* codes, size_t n, u32** d_bits, size_t tmp_at) {
+static int load_set(vdjx_ctx* c, const u32* codes, size_t n, vdjx_buf<u32>& d_bits, size_t tmp_at) {
 	const size_t words = (size_t) 1 << 27;
-	if (!*d_bits) HIP_TRY(hipMalloc(d_bits, words * 4));
-	HIP_TRY(hipMemsetAsync(*d_bits, 0, words * 4, c->stream));
+	HIP_TRY(d_bits.reserve(words * 4, 0));
+	HIP_TRY(hipMemsetAsync(d_bits, 0, words * 4, c->stream));
 	if (n) {
 		u32* d_codes = c->d_anchor_tmp + tmp_at;
 		HIP_TRY(hipMemcpyAsync(d_codes, codes, n * 4, hipMemcpyHostToDevice, c->stream));
-		hipLaunchKernelGGL(k_bitmap_set, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, c->stream, d_codes, n, *d_bits);
+		hipLaunchKernelGGL(k_bitmap_set, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, c->stream, d_codes, n, (u32*) d_bits);
 	}
 	return VDJX_OK;
 }
@@ -59,16 +59,13 @@ extern "C" int vdjx_anchor_sets_load(vdjx_ctx* c, const uint32_t* v_codes, size_
 	HIP_TRY(hipSetDevice(c->device));
 	vdjx_clear_errors();
 	const size_t need = (nv + nj + 2) * 4;
-	if (need > c->anchor_tmp_cap) {
+	if (need > c->d_anchor_tmp.bytes) {
 		HIP_TRY(hipStreamSynchronize(c->stream));
-		if (c->d_anchor_tmp) (void) hipFree(c->d_anchor_tmp);
-		c->d_anchor_tmp = nullptr; c->anchor_tmp_cap = 0;
-		HIP_TRY(hipMalloc(&c->d_anchor_tmp, need + need / 4));
-		c->anchor_tmp_cap = need + need / 4;
+		HIP_TRY(c->d_anchor_tmp.reserve(need, need / 4));
 	}
-	int rc = load_set(c, v_codes, nv, &c->d_vbits, 0);
+	int rc = load_set(c, v_codes, nv, c->d_vbits, 0);
 	if (rc) return rc;
-	rc = load_set(c, j_codes, nj, &c->d_jbits, nv + 1);
+	rc = load_set(c, j_codes, nj, c->d_jbits, nv + 1);
 	if (rc) return rc;
 	HIP_TRY(hipStreamSynchronize(c->stream));            // (the codes have left the caller's arrays)
 	HIP_TRY(hipGetLastError());
@@ -271,10 +268,10 @@ __global__ void k_ball_bits(const u32* __restrict__ anchors, u32 n_anchors, u32 
 	if (code) atomicOr(&bits[code >> 5], 1u << (code & 31));      // code 0 is the sets' empty key (vj_filter.c:317-318)
 }
 
-static int ball_set(vdjx_ctx* c, const u32* anchors, size_t n, u32 thr, u32** d_bits) {
+static int ball_set(vdjx_ctx* c, const u32* anchors, size_t n, u32 thr, vdjx_buf<u32>& d_bits) {
 	const size_t words = (size_t) 1 << 27;
-	if (!*d_bits) HIP_TRY(hipMalloc(d_bits, words * 4));
-	HIP_TRY(hipMemsetAsync(*d_bits, 0, words * 4, c->stream));
+	HIP_TRY(d_bits.reserve(words * 4, 0));
+	HIP_TRY(hipMemsetAsync(d_bits, 0, words * 4, c->stream));
 	if (!n) return VDJX_OK;
 	u32 binom[17][7] = {};
 	for (int i = 0; i <= 16; i++)
@@ -293,7 +290,7 @@ static int ball_set(vdjx_ctx* c, const u32* anchors, size_t n, u32 thr, u32** d_
 	const u64 total = (u64) n * ball;
 	{
 		vdjx_prof_scope ps(c, "k_ball_bits");
-		hipLaunchKernelGGL(k_ball_bits, dim3((unsigned) ((total + 255) / 256)), dim3(256), 0, c->stream, d_a, (u32) n, ball, thr, d_level, *d_bits);
+		hipLaunchKernelGGL(k_ball_bits, dim3((unsigned) ((total + 255) / 256)), dim3(256), 0, c->stream, d_a, (u32) n, ball, thr, d_level, (u32*) d_bits);
 	}
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	HIP_TRY(hipGetLastError());
@@ -306,13 +303,13 @@ extern "C" int vdjx_anchor_sets_from_anchors(vdjx_ctx* c, const uint32_t* v_anch
 	HIP_TRY(hipSetDevice(c->device));
 	vdjx_clear_errors();
 	if (am < 0) {                                            // no row has a distance <= am: empty sets
-		int rc = load_set(c, nullptr, 0, &c->d_vbits, 0);
-		if (!rc) rc = load_set(c, nullptr, 0, &c->d_jbits, 0);
+		int rc = load_set(c, nullptr, 0, c->d_vbits, 0);
+		if (!rc) rc = load_set(c, nullptr, 0, c->d_jbits, 0);
 		if (rc) return rc;
 	} else {
 		const u32 thr = (u32) (am > 5 ? 5 : am);             // the index files stop at MAX_DIST 5 (seq_dist.c:9)
-		int rc = ball_set(c, v_anchors, nv, thr, &c->d_vbits);
-		if (!rc) rc = ball_set(c, j_anchors, nj, thr, &c->d_jbits);
+		int rc = ball_set(c, v_anchors, nv, thr, c->d_vbits);
+		if (!rc) rc = ball_set(c, j_anchors, nj, thr, c->d_jbits);
 		if (rc) return rc;
 	}
 	HIP_TRY(hipStreamSynchronize(c->stream));

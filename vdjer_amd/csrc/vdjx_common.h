@@ -111,13 +111,49 @@ struct vdjx_block_cache {
 	hipError_t acquire(size_t need, char** out, size_t* cap);
 	void release(char* p, size_t cap);
 	void drop();
+	static void discard(char* p) { if (p) (void) hipFree(p); }      // a block that outlived its context
 };
+
+// A device or page-locked buffer that a context keeps from call to call and replaces only when a call needs more (hipMalloc / hipFree
+// cost milliseconds each and hipFree waits for the whole device).  Nothing here waits for a stream: whoever calls reserve() or release()
+// has made sure that nothing in flight still uses the memory.  vdjx_ctx::each_kept lists every one of them.
+struct vdjx_kept {
+	void* p = nullptr;
+	size_t bytes = 0;                 // behind p
+	const bool pinned;                // page-locked host memory (else device memory)
+	u32 allocs = 0;                   // allocations made so far
+	explicit vdjx_kept(bool pinned_ = false) : pinned(pinned_) {}
+	vdjx_kept(const vdjx_kept&) = delete;
+	vdjx_kept& operator=(const vdjx_kept&) = delete;
+	template <typename T> T* as() const { return (T*) p; }
+	// room for `need` bytes: kept if large enough, else replaced by need + margin bytes (contents undefined); empty on failure
+	hipError_t reserve(size_t need, size_t margin) {
+		if (need <= bytes) return hipSuccess;
+		release();
+		const hipError_t e = pinned ? hipHostMalloc(&p, need + margin, hipHostMallocDefault) : hipMalloc(&p, need + margin);
+		if (e != hipSuccess) { p = nullptr; return e; }
+		bytes = need + margin;
+		allocs++;
+		return hipSuccess;
+	}
+	void release() {
+		if (p) (void) (pinned ? hipHostFree(p) : hipFree(p));
+		p = nullptr;
+		bytes = 0;
+	}
+};
+// ... of elements T: stands for its pointer wherever one is expected (a cast names another element type)
+template <typename T> struct vdjx_buf : vdjx_kept {
+	using vdjx_kept::vdjx_kept;
+	operator T*() const { return (T*) p; }
+	template <typename U> explicit operator U*() const { return (U*) p; }
+};
+enum vdjx_kept_tag { VDJX_KEPT_INDEX, VDJX_KEPT_RESULT, VDJX_KEPT_OTHER };      // the read index's arrays / the scorers' result buffers (vdjx_trim) / the rest
 
 // a set of records to align against (vdjx_align.hip): per class the records' base codes back to back, each after a reset column, one more
 // reset column at the end
 struct vdjx_recset {
-	uint8_t* d_cols = nullptr;        // class 0's columns, then class 1's (kept until the next load or vdjx_shutdown)
-	size_t cap = 0;                   // bytes behind d_cols
+	vdjx_buf<uint8_t> d_cols;         // class 0's columns, then class 1's (kept until the next load or vdjx_shutdown)
 	bool loaded = false;
 	int ncls = 0;
 	std::vector<u32> rec[2];          // per class: the record index of every record of the class, ascending
@@ -141,10 +177,9 @@ struct vdjx_ctx {
 	hipStream_t stream = nullptr;
 	hipStream_t copy_stream = nullptr;   // result copies that may run beside the next kernels (vdjx_graph_export_begin)
 	hipStream_t pairs_stream = nullptr;  // the mapped pairs' copy (vdjx_map_emit_begin): a stream of its own, so that waiting for one result is not waiting for the other
-	void* h_pin = nullptr;                          // 16 KB of page-locked memory: where the small numbers a call waits for come down (a copy into
+	vdjx_buf<void> h_pin{true};                     // 16 KB of page-locked memory: where the small numbers a call waits for come down (a copy into
 	                                                // pageable memory goes through a staging buffer of the runtime: tens of microseconds per read)
-	void* d_stage[2] = {nullptr, nullptr};          // vdjx_pool_load: upload staging (two chunks in flight)
-	size_t stage_cap = 0;
+	vdjx_buf<void> d_stage[2];                      // vdjx_pool_load: upload staging (two chunks in flight)
 	hipEvent_t ev_copied[2] = {nullptr, nullptr}, ev_packed[2] = {nullptr, nullptr};
 	bool profiling = false;
 	std::string prof_only;            // vdjx_profile_only: the one scope name that is bracketed (empty: all)
@@ -154,59 +189,53 @@ struct vdjx_ctx {
 	std::vector<pending_ev> prof_pending;
 	std::vector<hipEvent_t> ev_free;                     // events are recycled: creating two per launch costs as much as recording them
 	// a-6 anchor bitmaps (2^32 bits each)
-	u32* d_vbits = nullptr;
-	u32* d_jbits = nullptr;
+	vdjx_buf<u32> d_vbits, d_jbits;
 	bool anchors_loaded = false;
 	u32 sub_tuples_set = 0;           // the value of the device's g_sub_tuples this context has set (vdjx_kmer.hip: once, not per build)
-	u32* d_anchor_tmp = nullptr;      // the codes of a set on their way into its bitmap (kept: a new chain's ref-dir comes with every pool at configs[4])
-	size_t anchor_tmp_cap = 0, vtext_cap = 0, line_off_cap = 0, seed_cap = 0;      // bytes behind d_anchor_tmp / d_vtext / d_line_off / d_seed_code and d_seed_pos
+	vdjx_buf<u32> d_anchor_tmp;       // the codes of a set on their way into its bitmap (kept: a new chain's ref-dir comes with every pool at configs[4])
 	// a-7 V-region index
-	char* d_vtext = nullptr;          // all lines concatenated
-	u32* d_line_off = nullptr;        // [n_lines+1]
-	u32* d_seed_code = nullptr;       // sorted vk-mer codes
-	u32* d_seed_pos = nullptr;        // position within its line
+	vdjx_buf<char> d_vtext;           // all lines concatenated
+	vdjx_buf<u32> d_line_off;         // [n_lines+1]
+	vdjx_buf<u32> d_seed_code;        // sorted vk-mer codes
+	vdjx_buf<u32> d_seed_pos;         // position within its line
 	size_t n_lines = 0, n_seeds = 0;
 	int vk = 0;
 	std::vector<u32> h_line_off;
 	// a-8 read index
 	const vdjx_pool* ri_pool = nullptr;
-	void* d_ri_tab = nullptr;         // slots {read sequence, class + 1 | members, CSR start | weighted entries} (k_ri_tab; VDJX_RI_SLOT_WORDS)
+	vdjx_buf<void> d_ri_tab;          // slots {read sequence, class + 1 | members, CSR start | weighted entries} (k_ri_tab; VDJX_RI_SLOT_WORDS)
 	u32 ri_tab_mask = 0;
 	u32 ri_tab_epoch = 0;             // k_ri_tab_canon: a slot is taken iff the top 7 bits of its claim word hold the build's number (1 .. 127; 0: the table
 	                                  // has to be cleared first) -- clearing a gigabyte per build was 0.15 ms of 4.8
 	bool ri_canon = false;            // the table holds one 64-byte slot per pair {sequence, reverse complement} under the smaller of the two (k_ri_tab_canon: pools of couples)
-	u32* d_ri_start = nullptr;        // class -> CSR start [ncls+1]
-	u32* d_ri_cnt1 = nullptr;         // class -> number of read-1 members (the CSR lists those only)
-	u32* d_ri_recs = nullptr;         // CSR: read-1 records in registration order
-	u64* d_ri_csr8 = nullptr;         // CSR: the member's 8-byte entry (ri_entry)
-	u32* d_ri_csr_pair = nullptr;     // CSR: the member's pair id
-	u32* d_pair_r2 = nullptr;         // pair -> its two read-2 records in registration order (or ~0u)
-	u32* d_ri_dstart = nullptr;       // class -> first of its DISTINCT read-1 entries (window scoring counts, it does not name pairs)
-	u64* d_ri_d8 = nullptr;           // those entries, with multiplicities
-	size_t ri_cap[9] = {};            // bytes behind the nine arrays above (kept from build to build, vdjx_rindex.hip ri_keep)
+	vdjx_buf<u32> d_ri_start;         // class -> CSR start [ncls+1]
+	vdjx_buf<u32> d_ri_cnt1;          // class -> number of read-1 members (the CSR lists those only)
+	vdjx_buf<u32> d_ri_recs;          // CSR: read-1 records in registration order
+	vdjx_buf<u64> d_ri_csr8;          // CSR: the member's 8-byte entry (ri_entry)
+	vdjx_buf<u32> d_ri_csr_pair;      // CSR: the member's pair id
+	vdjx_buf<u32> d_pair_r2;          // pair -> its two read-2 records in registration order (or ~0u)
+	vdjx_buf<u32> d_ri_dstart;        // class -> first of its DISTINCT read-1 entries (window scoring counts, it does not name pairs)
+	vdjx_buf<u64> d_ri_d8;            // those entries, with multiplicities
 	std::vector<std::pair<const char*, size_t>> host_blocks;     // vdjx_host_alloc's page-locked blocks (the scorers read strings that lie in one of them in place)
 	std::mutex host_blocks_mu;
 	// cached result of the last vdjx_map_emit count call (the write call of the two-call protocol reuses it)
 	uint64_t me_key = 0;
 	const void* me_src = nullptr;     // the batch the cached mapping belongs to
-	void* me_pairs = nullptr;         // vdjx_pair[me_cap], per-contig regions at the contigs' hit offsets
-	void* me_hit = nullptr;           // u32[me_cap]: the hit (inside its slice) every stored pair belongs to
-	size_t me_cap = 0;
+	vdjx_buf<void> me_pairs;          // vdjx_pair per hit, per-contig regions at the contigs' hit offsets
+	vdjx_buf<void> me_hit;            // u32 per hit: the hit (inside its slice) every stored pair belongs to
 	// the (weighted) mapped-pair lists of the last window batch: (multiplicity << 32 | pos1 << 16 | pos2), window i at wp_off[i]
-	void* wp_buf = nullptr;
-	size_t wp_cap = 0, wp_n = 0;
+	vdjx_buf<void> wp_buf;
+	size_t wp_n = 0;
 	std::vector<u64> wp_off;
 	std::vector<u32> wp_cnt;
-	void* me_dense = nullptr;         // the pairs laid end to end for the copy to the host (kept: the copy may be asynchronous)
-	size_t me_dense_cap = 0;
+	vdjx_buf<void> me_dense;          // the pairs laid end to end for the copy to the host (kept: the copy may be asynchronous)
 	size_t me_gathered_cap = 0;       // capacity the counting call's gather (launched ahead of the total) ran against; 0: it did not run
 	std::vector<u64> me_cnt;          // pairs per contig
-	void* h_plan = nullptr;           // page-locked scratch: the plan's totals come down here (vdjx_score.hip classify_and_plan)
-	size_t h_plan_cap = 0;
-	void* h_res = nullptr;            // page-locked, grows: small per-call results come down here in one go (a copy into the caller's pageable
-	size_t h_res_cap = 0;             // arrays blocks the host per copy) and are handed over after the call's one wait
-	void* me_book = nullptr;          // device bookkeeping between the counting and the writing call (vdjx_score.hip map_emit_impl)
-	size_t me_book_cap = 0, me_nsl = 0;
+	vdjx_buf<void> h_plan{true};      // page-locked scratch: the plan's totals come down here (vdjx_score.hip classify_and_plan)
+	vdjx_buf<void> h_res{true};       // page-locked, grows: small per-call results come down here in one go (a copy into the caller's pageable
+	                                  // arrays blocks the host per copy) and are handed over after the call's one wait
+	vdjx_buf<void> me_book;           // device bookkeeping between the counting and the writing call (vdjx_score.hip map_emit_impl)
+	size_t me_nsl = 0;
 	u32 me_slice_hits = 0;
 	hipEvent_t ev_gathered = nullptr;
 	hipStream_t up_stream = nullptr;        // the scorers' strings on their way up, in pieces (classify_and_plan)
@@ -223,19 +252,27 @@ struct vdjx_ctx {
 	uint8_t* root_pending_out = nullptr;
 	hipEvent_t ev_root_done = nullptr;
 	// SAM text (vdjx_sam_text): read names by pair id on the device, the text buffers
-	char* d_sam_names = nullptr;
-	u64* d_sam_noff = nullptr;
+	vdjx_buf<char> d_sam_names;
+	vdjx_buf<u64> d_sam_noff;
 	u32 sam_pairs = 0;
-	void* d_sam_text = nullptr;
-	void* h_sam_text = nullptr;
-	size_t sam_text_cap = 0;
-	void *d_sam_keys = nullptr, *d_sam_lens = nullptr;      // vdjx_sam_blocks: per mapped pair its ordering key and the bytes of its two lines
-	size_t sam_blk_cap = 0;
-	void* h_sam_merge = nullptr;      // vdjx_sam_merge: the merged text (page-locked)
-	size_t sam_merge_cap = 0;
+	vdjx_buf<void> d_sam_text;
+	vdjx_buf<void> h_sam_text{true};
+	vdjx_buf<void> d_sam_keys, d_sam_lens;                  // vdjx_sam_blocks: per mapped pair its ordering key and the bytes of its two lines
+	vdjx_buf<void> h_sam_merge{true}; // vdjx_sam_merge: the merged text (page-locked)
 	u32 n_pairs = 0, n_classes = 0;
 	vdjx_recset germline, constant;   // vdjx_germline_load (classes V, J) / vdjx_constant_load (one class): independent of each other
 	std::map<std::string, uint64_t> stats;
+	// every kept buffer of the context, each once: the ONE list behind vdjx_shutdown, vdjx_trim, vdjx_read_index_drop and the kept_*
+	// statistics.  A fixed list over members: a buffer that grows (the index's arrays do on the read-index thread) changes nothing here.
+	template <typename F> void each_kept(F f) {
+		vdjx_kept* const index[] = {&d_ri_tab, &d_ri_start, &d_ri_cnt1, &d_ri_recs, &d_ri_csr8, &d_ri_csr_pair, &d_ri_dstart, &d_ri_d8, &d_pair_r2};
+		vdjx_kept* const result[] = {&wp_buf, &me_pairs, &me_hit, &me_dense, &me_book, &d_sam_text, &h_sam_text, &d_sam_keys, &d_sam_lens};
+		vdjx_kept* const other[] = {&h_pin, &d_stage[0], &d_stage[1], &d_vbits, &d_jbits, &d_anchor_tmp, &d_vtext, &d_line_off, &d_seed_code, &d_seed_pos,
+		                            &h_plan, &h_res, &d_sam_names, &d_sam_noff, &h_sam_merge, &germline.d_cols, &constant.d_cols};
+		for (vdjx_kept* b : index) f(*b, VDJX_KEPT_INDEX);
+		for (vdjx_kept* b : result) f(*b, VDJX_KEPT_RESULT);
+		for (vdjx_kept* b : other) f(*b, VDJX_KEPT_OTHER);
+	}
 };
 
 // Two record formats.  Reads of up to 64 bases (W = 2, M = 1, ob = 6): the read as ONE 2*rl-bit integer in two words (hi, lo), first base

@@ -53,7 +53,7 @@ extern "C" int vdjx_init(int device, vdjx_ctx** out) {
 	if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_root_done, hipEventDisableTiming);
 	if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->ri_stream, hipStreamNonBlocking);
 	if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_ri_go, hipEventDisableTiming);
-	if (e == hipSuccess) e = hipHostMalloc(&c->h_pin, VDJX_HPIN_BYTES, hipHostMallocDefault);
+	if (e == hipSuccess) e = c->h_pin.reserve(VDJX_HPIN_BYTES, 0);
 	if (e != hipSuccess) { delete c; vdjx_set_error("hipStreamCreate: %s", hipGetErrorString(e)); return VDJX_EHIP; }
 	{
 		std::lock_guard<std::mutex> lk(g_ctx_mu);
@@ -62,8 +62,6 @@ extern "C" int vdjx_init(int device, vdjx_ctx** out) {
 	*out = c;
 	return VDJX_OK;
 }
-
-static void free_dev(void* p) { if (p) (void) hipFree(p); }
 
 hipError_t vdjx_block_cache::acquire(size_t need, char** out, size_t* cap) {
 	need = (need + 4095) & ~(size_t) 4095;
@@ -110,14 +108,7 @@ extern "C" void vdjx_shutdown(vdjx_ctx* c) {
 	if (c->ri_stream) { (void) hipStreamSynchronize(c->ri_stream); (void) hipStreamDestroy(c->ri_stream); }
 	if (c->ev_ri_go) (void) hipEventDestroy(c->ev_ri_go);
 	c->ri_arena.release(true);
-	free_dev(c->d_vbits); free_dev(c->d_jbits); free_dev(c->d_anchor_tmp);
-	free_dev(c->d_vtext); free_dev(c->d_line_off); free_dev(c->d_seed_code); free_dev(c->d_seed_pos);
-	free_dev(c->d_ri_tab); free_dev(c->d_ri_start); free_dev(c->d_ri_recs); free_dev(c->d_ri_csr8); free_dev(c->d_ri_csr_pair);
-	free_dev(c->d_pair_r2);
-	free_dev(c->d_sam_keys); free_dev(c->d_sam_lens);
-	if (c->h_sam_merge) (void) hipHostFree(c->h_sam_merge);
-	free_dev(c->me_pairs); free_dev(c->me_hit); free_dev(c->me_dense); free_dev(c->me_book); free_dev(c->wp_buf); free_dev(c->d_ri_cnt1); free_dev(c->d_ri_dstart); free_dev(c->d_ri_d8);
-	for (int i = 0; i < 2; i++) { free_dev(c->d_stage[i]); if (c->ev_copied[i]) (void) hipEventDestroy(c->ev_copied[i]); if (c->ev_packed[i]) (void) hipEventDestroy(c->ev_packed[i]); }
+	for (int i = 0; i < 2; i++) { if (c->ev_copied[i]) (void) hipEventDestroy(c->ev_copied[i]); if (c->ev_packed[i]) (void) hipEventDestroy(c->ev_packed[i]); }
 	c->arena.release(true);
 	c->shard_arena.release(true);
 	c->blocks.drop();
@@ -136,12 +127,7 @@ extern "C" void vdjx_shutdown(vdjx_ctx* c) {
 	if (c->ev_pairs_copied) (void) hipEventDestroy(c->ev_pairs_copied);
 	if (c->ev_plan) (void) hipEventDestroy(c->ev_plan);
 	if (c->ev_root_done) (void) hipEventDestroy(c->ev_root_done);
-	if (c->h_plan) (void) hipHostFree(c->h_plan);
-	if (c->h_res) (void) hipHostFree(c->h_res);
-	if (c->h_pin) (void) hipHostFree(c->h_pin);
-	if (c->h_sam_text) (void) hipHostFree(c->h_sam_text);
-	free_dev(c->d_sam_text); free_dev(c->d_sam_names); free_dev(c->d_sam_noff);
-	free_dev(c->germline.d_cols); free_dev(c->constant.d_cols);
+	c->each_kept([](vdjx_kept& b, vdjx_kept_tag) { b.release(); });
 	(void) hipStreamDestroy(c->stream);
 	delete c;
 }
@@ -162,20 +148,9 @@ extern "C" int vdjx_trim(vdjx_ctx* c) {
 	c->blocks.drop();
 	// the scorers' result buffers (grow-only between calls: the pair lists of the last window batch, the mapped pairs and the SAM
 	// records of the last contigs): results the caller has taken; the next call allocates what it needs
-	auto drop = [](void*& p, size_t& cap) { if (p) (void) hipFree(p); p = nullptr; cap = 0; };
-	drop(c->wp_buf, c->wp_cap);
+	c->each_kept([](vdjx_kept& b, vdjx_kept_tag t) { if (t == VDJX_KEPT_RESULT) b.release(); });
 	c->wp_n = 0;
-	drop(c->me_pairs, c->me_cap);
-	if (c->me_hit) { (void) hipFree(c->me_hit); c->me_hit = nullptr; }
-	drop(c->me_dense, c->me_dense_cap);
 	c->me_gathered_cap = 0;
-	drop(c->me_book, c->me_book_cap);
-	if (c->d_sam_text) { (void) hipFree(c->d_sam_text); c->d_sam_text = nullptr; }
-	if (c->h_sam_text) { (void) hipHostFree(c->h_sam_text); c->h_sam_text = nullptr; }
-	c->sam_text_cap = 0;
-	if (c->d_sam_keys) { (void) hipFree(c->d_sam_keys); c->d_sam_keys = nullptr; }
-	if (c->d_sam_lens) { (void) hipFree(c->d_sam_lens); c->d_sam_lens = nullptr; }
-	c->sam_blk_cap = 0;
 	c->me_key = 0;          // (the cached counting call of vdjx_map_emit pointed into the workspace)
 	c->me_src = nullptr;
 	return VDJX_OK;
@@ -188,11 +163,7 @@ extern "C" int vdjx_read_index_drop(vdjx_ctx* c) {
 	HIP_TRY(hipSetDevice(c->device));
 	(void) vdjx_ri_join(c);
 	HIP_TRY(hipStreamSynchronize(c->stream));
-	free_dev(c->d_ri_tab); free_dev(c->d_ri_start); free_dev(c->d_ri_cnt1); free_dev(c->d_ri_dstart); free_dev(c->d_pair_r2);
-	free_dev(c->d_ri_recs); free_dev(c->d_ri_csr8); free_dev(c->d_ri_csr_pair); free_dev(c->d_ri_d8);
-	c->d_ri_tab = nullptr; c->d_ri_start = nullptr; c->d_ri_cnt1 = nullptr; c->d_ri_dstart = nullptr; c->d_pair_r2 = nullptr;
-	c->d_ri_recs = nullptr; c->d_ri_csr8 = nullptr; c->d_ri_csr_pair = nullptr; c->d_ri_d8 = nullptr;
-	for (auto& cap : c->ri_cap) cap = 0;
+	c->each_kept([](vdjx_kept& b, vdjx_kept_tag t) { if (t == VDJX_KEPT_INDEX) b.release(); });
 	c->ri_pool = nullptr;
 	c->me_key = 0;
 	return VDJX_OK;
@@ -376,6 +347,13 @@ void vdjx_prof_collect(vdjx_ctx* c, bool force) {
 
 extern "C" uint64_t vdjx_stat(vdjx_ctx* c, const char* name) {
 	if (!c || !name) return 0;
+	if (!strncmp(name, "kept_", 5)) {            // what the context holds from call to call, counted when asked (include/vdjx.h)
+		uint64_t dev = 0, pin = 0, allocs = 0;
+		c->each_kept([&](const vdjx_kept& b, vdjx_kept_tag) { (b.pinned ? pin : dev) += b.bytes; allocs += b.allocs; });
+		if (!strcmp(name, "kept_device_bytes")) return dev;
+		if (!strcmp(name, "kept_pinned_bytes")) return pin;
+		if (!strcmp(name, "kept_allocs")) return allocs;
+	}
 	auto it = c->stats.find(name);
 	return it == c->stats.end() ? 0 : it->second;
 }
@@ -958,18 +936,18 @@ static int pool_load_host(vdjx_ctx* c, const uint8_t* primary, size_t n_primary,
 	*out = nullptr;
 	const size_t reclen = packed_in ? (size_t) vdjx_packed_bytes(rl) : 2 * (size_t) rl + 1;      // bytes per input record
 	const size_t stage_bytes = (size_t) LOAD_CHUNK_RECS * (2 * (size_t) rl + 1) + 16;           // (sized for the ASCII form: the larger one)
-	if (stage_bytes > c->stage_cap) {              // (sized for the longest records seen so far)
+	if (stage_bytes > c->d_stage[0].bytes || stage_bytes > c->d_stage[1].bytes) {              // (sized for the longest records seen so far)
 		(void) hipStreamSynchronize(c->copy_stream);
 		(void) hipStreamSynchronize(c->stream);
 		for (int i = 0; i < 2; i++) {
-			if (c->d_stage[i]) (void) hipFree(c->d_stage[i]);
-			c->d_stage[i] = nullptr;
-			hipError_t e = hipMalloc(&c->d_stage[i], stage_bytes);
+			hipError_t e = c->d_stage[i].reserve(stage_bytes, 0);
 			if (e == hipSuccess && !c->ev_copied[i]) e = hipEventCreateWithFlags(&c->ev_copied[i], hipEventDisableTiming);
 			if (e == hipSuccess && !c->ev_packed[i]) e = hipEventCreateWithFlags(&c->ev_packed[i], hipEventDisableTiming);
-			if (e != hipSuccess) { c->stage_cap = 0; vdjx_set_error("pool staging: %s", hipGetErrorString(e)); vdjx_pool_free(p); return VDJX_EHIP; }
+			if (e != hipSuccess) {            // (both go: the next load starts over, events included)
+				c->d_stage[0].release(); c->d_stage[1].release();
+				vdjx_set_error("pool staging: %s", hipGetErrorString(e)); vdjx_pool_free(p); return VDJX_EHIP;
+			}
 		}
-		c->stage_cap = stage_bytes;
 	}
 	if (async) {
 		// the whole load on the copy stream (chunk after chunk: copy, pack), so that the main stream keeps computing on another pool;
@@ -1126,7 +1104,7 @@ extern "C" void vdjx_pool_free(vdjx_pool* p) {
 			if (p->pending_bad) (void) hipStreamSynchronize(p->ctx->copy_stream);
 			p->ctx->blocks.release(p->d_block, p->block_cap);
 		} else
-			free_dev(p->d_block);
+			vdjx_block_cache::discard(p->d_block);
 	}
 	delete p;
 }

@@ -3844,7 +3844,7 @@ extern "C" void vdjx_graph_free(vdjx_graph* g) {
 			(void) hipStreamSynchronize(g->ctx->copy_stream);      // an export that was begun and never ended
 			g->ctx->blocks.release(g->d_block, g->block_cap);
 		}
-		else (void) hipFree(g->d_block);
+		else vdjx_block_cache::discard(g->d_block);
 	}
 	delete g;
 }

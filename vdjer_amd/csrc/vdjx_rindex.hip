@@ -27,17 +27,6 @@
 #define NONE64 0xFFFFFFFFFFFFFFFFull
 
 namespace {
-template <typename T> void free_set(T*& p) { if (p) (void) hipFree(p); p = nullptr; }
-// *p holds at least `bytes` bytes (contents undefined): kept if large enough, replaced (with a margin) if not
-template <typename T> hipError_t ri_keep(T** p, size_t* cap, size_t bytes) {
-	if (*p && *cap >= bytes) return hipSuccess;
-	if (*p) (void) hipFree(*p);
-	*p = nullptr; *cap = 0;
-	const size_t want = bytes + bytes / 8 + 256;
-	const hipError_t e = hipMalloc((void**) p, want);
-	if (e == hipSuccess) *cap = want;
-	return e;
-}
 
 #define RI_SB 2048u        // table slots per workgroup of k_ri_occ / k_ri_number*: 8 per thread, one count per workgroup
 
@@ -618,16 +607,16 @@ int read_index_build_dev(vdjx_ctx* c, vdjx_work& db, const vdjx_pool* pool, cons
 	const size_t slot_bytes = sym ? 64 : (size_t) (pool->W == 2 ? VDJX_RI_SLOT_WORDS(2) : VDJX_RI_SLOT_WORDS(VDJX_LONG_W)) * 8;
 	// the index's arrays are kept from build to build and only replaced when one needs more (hipMalloc / hipFree of gigabytes per pool
 	// cost more than the kernels that fill them)
-	const void* tab_before = c->d_ri_tab;
-	const size_t tab_cap_before = c->ri_cap[0];
-	HIP_TRY(ri_keep(&c->d_ri_tab, &c->ri_cap[0], ((size_t) tmask + 1) * slot_bytes));
-	if (c->d_ri_tab != tab_before || c->ri_cap[0] != tab_cap_before || !sym || c->ri_tab_epoch >= 127u) c->ri_tab_epoch = 0;        // a new buffer, another slot format, the numbers used up: clear
-	HIP_TRY(ri_keep(&c->d_ri_start, &c->ri_cap[1], ((size_t) ncls + 2) * 4));
-	HIP_TRY(ri_keep(&c->d_ri_cnt1, &c->ri_cap[2], ((size_t) ncls + 2) * 4));
-	HIP_TRY(ri_keep(&c->d_ri_dstart, &c->ri_cap[3], ((size_t) ncls + 2) * 4));          // (weighted entries per class: k_ri_fold's dcnt)
-	HIP_TRY(ri_keep(&c->d_pair_r2, &c->ri_cap[4], ((size_t) n_pairs * 2 + 2) * 4));
-	HIP_TRY(hipMemsetAsync(c->d_ri_cnt1, 0, ((size_t) ncls + 2) * 4, st));
-	if (c->ri_tab_epoch == 0) HIP_TRY(hipMemsetAsync(c->d_ri_tab, 0, c->ri_cap[0], st));          // (all of it: a later build may use more of the buffer)
+	const u32 tab_allocs_before = c->d_ri_tab.allocs;
+	const size_t tab_bytes = ((size_t) tmask + 1) * slot_bytes, cls_bytes = ((size_t) ncls + 2) * 4, r2_bytes = ((size_t) n_pairs * 2 + 2) * 4;
+	HIP_TRY(c->d_ri_tab.reserve(tab_bytes, tab_bytes / 8 + 256));
+	if (c->d_ri_tab.allocs != tab_allocs_before || !sym || c->ri_tab_epoch >= 127u) c->ri_tab_epoch = 0;        // a new buffer, another slot format, the numbers used up: clear
+	HIP_TRY(c->d_ri_start.reserve(cls_bytes, cls_bytes / 8 + 256));
+	HIP_TRY(c->d_ri_cnt1.reserve(cls_bytes, cls_bytes / 8 + 256));
+	HIP_TRY(c->d_ri_dstart.reserve(cls_bytes, cls_bytes / 8 + 256));          // (weighted entries per class: k_ri_fold's dcnt)
+	HIP_TRY(c->d_pair_r2.reserve(r2_bytes, r2_bytes / 8 + 256));
+	HIP_TRY(hipMemsetAsync(c->d_ri_cnt1, 0, cls_bytes, st));
+	if (c->ri_tab_epoch == 0) HIP_TRY(hipMemsetAsync(c->d_ri_tab, 0, c->d_ri_tab.bytes, st));          // (all of it: a later build may use more of the buffer)
 	if (sym) c->ri_tab_epoch++;
 	{
 		vdjx_prof_scope ps(pc, "k_ri_number");
@@ -666,13 +655,14 @@ int read_index_build_dev(vdjx_ctx* c, vdjx_work& db, const vdjx_pool* pool, cons
 		vdjx_prof_scope ps(pc, "k_ri_members");
 		if (nrb) hipLaunchKernelGGL(k_ri_members, dim3(nrb), b256, 0, st, d_rec_cls, d_rnum, d_reg, d_pair, d_r2key, c->d_pair_r2, R, n_pairs, d_rbpre, c->d_ri_cnt1, d_mkey, d_mreg, d_mpack);
 	}
-	int rc = vdjx_scan_wide(db, st, c->d_ri_cnt1, ncls + 1, c->d_ri_start);         // (cnt1[ncls] = 0: start[ncls] = start[ncls + 1] = members)
+	int rc = vdjx_scan_wide(db, st, (const u32*) c->d_ri_cnt1, ncls + 1, (u32*) c->d_ri_start);         // (cnt1[ncls] = 0: start[ncls] = start[ncls + 1] = members)
 	if (rc) return rc;
 	// CSR order = (class, registration rank)
-	HIP_TRY(ri_keep(&c->d_ri_recs, &c->ri_cap[5], ((size_t) n1 + 1) * 4));
-	HIP_TRY(ri_keep(&c->d_ri_csr8, &c->ri_cap[6], ((size_t) n1 + 1) * 8));
-	HIP_TRY(ri_keep(&c->d_ri_csr_pair, &c->ri_cap[7], ((size_t) n1 + 1) * 4));
-	HIP_TRY(ri_keep(&c->d_ri_d8, &c->ri_cap[8], ((size_t) n1 + 1) * 8));
+	const size_t m4 = ((size_t) n1 + 1) * 4, m8 = ((size_t) n1 + 1) * 8;
+	HIP_TRY(c->d_ri_recs.reserve(m4, m4 / 8 + 256));
+	HIP_TRY(c->d_ri_csr8.reserve(m8, m8 / 8 + 256));
+	HIP_TRY(c->d_ri_csr_pair.reserve(m4, m4 / 8 + 256));
+	HIP_TRY(c->d_ri_d8.reserve(m8, m8 / 8 + 256));
 	unsigned long long nd = 0;
 	u64* d_by_class = nullptr;
 	if (n1) {
@@ -713,7 +703,7 @@ int read_index_build_dev(vdjx_ctx* c, vdjx_work& db, const vdjx_pool* pool, cons
 		const u32 max_giant = n1 / (RI_FOLD_WAVE + 1) + 1;
 		u32* d_giant;
 		HIP_TRY(db.alloc(&d_giant, (size_t) max_giant + 1));
-		HIP_TRY(hipMemsetAsync(c->d_ri_dstart, 0, ((size_t) ncls + 2) * 4, st));          // (a class without read-1 members has no entries)
+		HIP_TRY(hipMemsetAsync(c->d_ri_dstart, 0, cls_bytes, st));          // (a class without read-1 members has no entries)
 		if (n1) hipLaunchKernelGGL(k_ri_fold_members, dim3(n1 / RI_FM_PER + 1), b256, 0, st, (const u64*) d_by_class, n1, c->d_ri_start, c->d_ri_cnt1, c->d_ri_csr8, c->d_ri_d8, c->d_ri_dstart, d_nent,
 		                           d_giant, d_split + 1);
 		hipLaunchKernelGGL(k_ri_fold_big, dim3(max_giant < 2048u ? max_giant : 2048u), dim3(RI_FOLD_BIG_THREADS), 0, st, d_giant, d_split + 1, c->d_ri_start, c->d_ri_cnt1, c->d_ri_csr8, c->d_ri_d8, c->d_ri_dstart, d_nent);
@@ -740,7 +730,7 @@ int read_index_build_dev(vdjx_ctx* c, vdjx_work& db, const vdjx_pool* pool, cons
 	return VDJX_OK;
 }
 
-// the index is gone (its arrays stay for the next build: ri_keep)
+// the index is gone (its arrays stay for the next build)
 void drop_index(vdjx_ctx* c) {
 	c->ri_pool = nullptr;
 	c->me_key = 0;

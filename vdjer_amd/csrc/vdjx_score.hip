@@ -18,10 +18,6 @@
 
 #define NONE32 0xFFFFFFFFu
 
-namespace {
-template <typename T> void free_set(T*& p) { if (p) (void) hipFree(p); p = nullptr; }
-}  // namespace
-
 // ==============================================================================================
 // a-7 root scorer
 // ==============================================================================================
@@ -66,21 +62,11 @@ extern "C" int vdjx_vregion_load(vdjx_ctx* c, const char* const* lines, size_t n
 	// the four arrays are kept from load to load and only replaced when one needs more (a --config4 step loads a chain's V region with
 	// every pool: four hipFree + four hipMalloc + four waits each time were most of the call); one wait for the four copies
 	HIP_TRY(hipStreamSynchronize(c->stream));                // nothing in flight may still read the region that is replaced
-	auto keep = [](auto** p, size_t* cap, size_t bytes) -> hipError_t {
-		if (*p && *cap >= bytes) return hipSuccess;
-		if (*p) (void) hipFree(*p);
-		*p = nullptr; *cap = 0;
-		const hipError_t e = hipMalloc((void**) p, bytes + bytes / 4 + 64);
-		if (e == hipSuccess) *cap = bytes + bytes / 4 + 64;
-		return e;
-	};
-	HIP_TRY(keep(&c->d_vtext, &c->vtext_cap, text.size() + 16));
-	HIP_TRY(keep(&c->d_line_off, &c->line_off_cap, off.size() * 4));
-	{
-		size_t cap2 = c->seed_cap;
-		HIP_TRY(keep(&c->d_seed_code, &c->seed_cap, sc.size() * 4 + 4));
-		HIP_TRY(keep(&c->d_seed_pos, &cap2, sc.size() * 4 + 4));
-	}
+	const size_t text_bytes = text.size() + 16, off_bytes = off.size() * 4, seed_bytes = sc.size() * 4 + 4;
+	HIP_TRY(c->d_vtext.reserve(text_bytes, text_bytes / 4 + 64));
+	HIP_TRY(c->d_line_off.reserve(off_bytes, off_bytes / 4 + 64));
+	HIP_TRY(c->d_seed_code.reserve(seed_bytes, seed_bytes / 4 + 64));
+	HIP_TRY(c->d_seed_pos.reserve(seed_bytes, seed_bytes / 4 + 64));
 	HIP_TRY(hipMemcpyAsync(c->d_vtext, text.data(), text.size(), hipMemcpyHostToDevice, c->stream));
 	HIP_TRY(hipMemcpyAsync(c->d_line_off, off.data(), off.size() * 4, hipMemcpyHostToDevice, c->stream));
 	if (!sc.empty()) {
@@ -1812,10 +1798,7 @@ static int classify_and_plan(vdjx_ctx* c, vdjx_work& db, const ReadIndexDev& ix,
 		const int rc = vdjx_sort_pairs(db, st, d_gkey, d_gkey2, d_gidx, mp->d_gorder, (u32) n, 22);
 		if (rc) return rc;
 	}
-	if (!c->h_plan) {
-		HIP_TRY(hipHostMalloc(&c->h_plan, 256, hipHostMallocDefault));
-		c->h_plan_cap = 256;
-	}
+	HIP_TRY(c->h_plan.reserve(256, 0));
 	HIP_TRY(hipMemcpyAsync(c->h_plan, d_tot, sizeof(PlanOut), hipMemcpyDeviceToHost, st));
 	HIP_TRY(hipEventRecord(c->ev_plan, st));
 	lp.mark("plan_issue");
@@ -1875,27 +1858,24 @@ static int window_pairs_run(vdjx_ctx* c, vdjx_work& db, const ReadIndexDev& ix, 
 		if (!grouped) return VDJX_OK;
 		vdjx_prof_scope ps(c, "k_group_pairs");
 		hipLaunchKernelGGL(k_group_pairs, dim3((u32) ((n + GP_G - 1) / GP_G)), dim3(GP_THREADS), 0, st, ix, mp->d_prep, mp->d_hits, (u32) n, len, mp->d_gorder,
-		                   mp->d_off, (u64*) c->wp_buf, d_cnt, d_np, d_done, d_gstat, gp_dbg, (u64) c->wp_cap);
+		                   mp->d_off, (u64*) c->wp_buf, d_cnt, d_np, d_done, d_gstat, gp_dbg, (u64) (c->wp_buf.bytes / 8));
 		return VDJX_OK;
 	};
-	const bool early = grouped && c->wp_cap > 0;
+	const bool early = grouped && c->wp_buf.bytes > 0;
 	if (early && (rc = map_groups())) return rc;
 	if ((rc = plan_finish(c, mp))) return rc;
 	const u64 total = mp->tot.total_hits;
 	bool again = !early;
 	if (need) *need = 0;
-	if ((size_t) total + 1 > c->wp_cap && budget && n > 1 && (total + total / 4 + 1024) * 8 > budget) {
+	const size_t wp_need = ((size_t) total + 1) * 8;          // (the buffer is counted in bytes, its lists in 8-byte entries)
+	if (wp_need > c->wp_buf.bytes && budget && n > 1 && (total + total / 4 + 1024) * 8 > budget) {
 		HIP_TRY(hipStreamSynchronize(st));                  // (the early launch has returned without a write)
 		*need = (total + total / 4 + 1024) * 8;
 		return VDJX_OK;
 	}
-	if ((size_t) total + 1 > c->wp_cap) {
+	if (wp_need > c->wp_buf.bytes) {
 		HIP_TRY(hipStreamSynchronize(st));                  // (the early launch, if any, has returned without a write: wait before the buffer goes)
-		free_set(c->wp_buf);
-		c->wp_cap = 0;
-		const size_t want = (size_t) total + (size_t) total / 4 + 1024;
-		HIP_TRY(hipMalloc(&c->wp_buf, want * 8));
-		c->wp_cap = want;
+		HIP_TRY(c->wp_buf.reserve(wp_need, ((size_t) total / 4 + 1023) * 8));          // total + total / 4 + 1024 entries
 		again = true;
 	}
 	if (again && (rc = map_groups())) return rc;
@@ -1964,12 +1944,7 @@ static int window_score_slice(vdjx_ctx* c, const ReadIndexDev& ix, const char* w
 	}
 	// verdicts, pair counts and list lengths through the context's page-locked buffer: three asynchronous copies and one wait
 	const size_t nres = ((n + 15) & ~(size_t) 15) + 8 * n;
-	if (nres > c->h_res_cap) {
-		if (c->h_res) (void) hipHostFree(c->h_res);
-		c->h_res = nullptr; c->h_res_cap = 0;
-		HIP_TRY(hipHostMalloc(&c->h_res, nres + nres / 4, hipHostMallocDefault));
-		c->h_res_cap = nres + nres / 4;
-	}
+	HIP_TRY(c->h_res.reserve(nres, nres / 4));
 	uint8_t* hr_valid = (uint8_t*) c->h_res;
 	u32* hr_np = (u32*) (hr_valid + ((n + 15) & ~(size_t) 15));
 	u32* hr_cnt = hr_np + n;
@@ -2021,7 +1996,7 @@ extern "C" int vdjx_window_score(vdjx_ctx* c, const char* windows, size_t n, int
 	if (!budget) {
 		size_t fr = 0, tt = 0;
 		HIP_TRY(hipMemGetInfo(&fr, &tt));
-		budget = ((u64) fr + (u64) c->wp_cap * 8) / 10 * 8;            // (the buffer in hand is given back before a larger one is asked for)
+		budget = ((u64) fr + (u64) c->wp_buf.bytes) / 10 * 8;            // (the buffer in hand is given back before a larger one is asked for)
 	}
 	static const char* const summed[] = {"window_hits", "window_hits_distinct", "window_work_items", "group_hits_distinct", "group_overflows", "group_classes",
 	                                     "group_queued", "window_pairs", "window_pairs_entries"};
@@ -2206,13 +2181,9 @@ static int map_emit_impl(vdjx_ctx* c, const char* contigs, size_t n, int len, ui
 		if (rc) return rc;
 		lp.mark("me_plan");
 		const u64 total_hits = mp.tot.total_hits;
-		if (total_hits > c->me_cap) {
-			free_set(c->me_pairs);
-			free_set(c->me_hit);
-			c->me_cap = 0;
-			HIP_TRY(hipMalloc(&c->me_pairs, (size_t) total_hits * sizeof(vdjx_pair)));
-			HIP_TRY(hipMalloc(&c->me_hit, (size_t) total_hits * 4 + 4));
-			c->me_cap = (size_t) total_hits;
+		if (total_hits) {                                // (a batch without hits asks for nothing)
+			HIP_TRY(c->me_pairs.reserve((size_t) total_hits * sizeof(vdjx_pair), 0));
+			HIP_TRY(c->me_hit.reserve((size_t) total_hits * 4 + 4, 0));
 		}
 		const u32 slice_hits = mp.tot.chunk;
 		const size_t nsl = mp.tot.nwork;
@@ -2221,12 +2192,7 @@ static int map_emit_impl(vdjx_ctx* c, const char* contigs, size_t n, int len, ui
 		// contigs, the slices' bitmaps of mapped hits
 		const size_t nwords = ((size_t) slice_hits + 31) / 32;
 		const size_t need = (n + 1) * 4 + 8 + (n + 1) * 8 + nsl * 4 + 8 + (nsl + 1) * 8 + n * 8 + nsl * nwords * 4 + 64;
-		if (need > c->me_book_cap) {
-			free_set(c->me_book);
-			c->me_book_cap = 0;
-			HIP_TRY(hipMalloc(&c->me_book, need + need / 4));
-			c->me_book_cap = need + need / 4;
-		}
+		HIP_TRY(c->me_book.reserve(need, need / 4));
 		uint8_t* bk = (uint8_t*) c->me_book;
 		u64* b_off = (u64*) bk;                      bk += (n + 1) * 8;
 		u64* b_pre = (u64*) bk;                      bk += (nsl + 1) * 8;
@@ -2253,12 +2219,13 @@ static int map_emit_impl(vdjx_ctx* c, const char* contigs, size_t n, int len, ui
 			// the pairs are laid end to end while the host still waits for their number: into the buffer of the last call if it is
 			// large enough (the kernel looks), again by the writing call if it was not
 			c->me_gathered_cap = 0;
-			if (c->me_dense_cap) {
+			const size_t dense_cap = c->me_dense.bytes / sizeof(vdjx_pair);
+			if (dense_cap) {
 				HIP_TRY(hipStreamWaitEvent(st, c->ev_pairs_copied, 0));      // an earlier asynchronous copy may still be reading the buffer
 				vdjx_prof_scope ps(c, "k_gather_pairs");
 				hipLaunchKernelGGL(k_gather_pairs, dim3((u32) nsl), dim3(256), 0, st, (const vdjx_pair*) c->me_pairs, (const u32*) c->me_hit, (u32) n, slice_hits, b_sstart, b_off, b_bits, b_pre,
-				                   (vdjx_pair*) c->me_dense, (u64) c->me_dense_cap);
-				c->me_gathered_cap = c->me_dense_cap;
+				                   (vdjx_pair*) c->me_dense, (u64) dense_cap);
+				c->me_gathered_cap = dense_cap;
 			}
 			HIP_TRY(hipEventSynchronize(c->ev_plan));
 		} else
@@ -2289,18 +2256,15 @@ static int map_emit_impl(vdjx_ctx* c, const char* contigs, size_t n, int len, ui
 		lp.mark("me_prev_copy_wait");
 		const bool gathered = total <= c->me_gathered_cap;
 		c->me_gathered_cap = 0;
-		if (total > c->me_dense_cap) {
+		if ((size_t) total * sizeof(vdjx_pair) > c->me_dense.bytes) {
 			HIP_TRY(hipStreamSynchronize(st));           // (a gather launched ahead that found the buffer too small may still be queued)
-			free_set(c->me_dense);
-			c->me_dense_cap = 0;
-			HIP_TRY(hipMalloc(&c->me_dense, (size_t) (total + total / 4) * sizeof(vdjx_pair)));
-			c->me_dense_cap = (size_t) (total + total / 4);
+			HIP_TRY(c->me_dense.reserve((size_t) total * sizeof(vdjx_pair), (size_t) (total / 4) * sizeof(vdjx_pair)));
 		}
 		vdjx_pair* d_dense = (vdjx_pair*) c->me_dense;
 		if (nsl && !gathered) {
 			vdjx_prof_scope ps(c, "k_gather_pairs");
 			hipLaunchKernelGGL(k_gather_pairs, dim3((u32) nsl), dim3(256), 0, st, (const vdjx_pair*) c->me_pairs, (const u32*) c->me_hit, (u32) n, slice_hits, b_sstart, b_off, b_bits, b_pre, d_dense,
-			                   (u64) c->me_dense_cap);
+			                   (u64) (c->me_dense.bytes / sizeof(vdjx_pair)));
 		}
 		if (device_only) {
 			// (vdjx_sam_text: the pairs stay in c->me_dense, the stream is not waited for)
@@ -2460,12 +2424,16 @@ extern "C" int vdjx_sam_names_load(vdjx_ctx* c, const char* names, const uint64_
 	HIP_TRY(hipSetDevice(c->device));
 	vdjx_clear_errors();
 	HIP_TRY(hipStreamSynchronize(c->stream));
-	free_set(c->d_sam_names); free_set(c->d_sam_noff);
-	c->sam_pairs = 0;
-	for (uint32_t i = 0; i < n_pairs; i++) if (name_off[i + 1] < name_off[i]) { vdjx_set_error("vdjx_sam_names_load: offsets must not decrease"); return VDJX_EINVAL; }
+	c->sam_pairs = 0;                          // (no names until this load has succeeded; the two buffers stay and grow when a load needs more)
+	for (uint32_t i = 0; i < n_pairs; i++)
+		if (name_off[i + 1] < name_off[i]) {
+			c->d_sam_names.release(); c->d_sam_noff.release();          // (as ever: a refused load leaves no names behind)
+			vdjx_set_error("vdjx_sam_names_load: offsets must not decrease");
+			return VDJX_EINVAL;
+		}
 	const size_t nb = (size_t) name_off[n_pairs];
-	HIP_TRY(hipMalloc(&c->d_sam_names, nb + 16));
-	HIP_TRY(hipMalloc(&c->d_sam_noff, ((size_t) n_pairs + 1) * 8));
+	HIP_TRY(c->d_sam_names.reserve(nb + 16, 0));
+	HIP_TRY(c->d_sam_noff.reserve(((size_t) n_pairs + 1) * 8, 0));
 	if (nb) HIP_TRY(hipMemcpy(c->d_sam_names, names, nb, hipMemcpyHostToDevice));
 	HIP_TRY(hipMemcpy(c->d_sam_noff, name_off, ((size_t) n_pairs + 1) * 8, hipMemcpyHostToDevice));
 	c->sam_pairs = n_pairs;
@@ -2525,15 +2493,8 @@ static int sam_text_device(vdjx_ctx* c, vdjx_work& db, const char* contigs, size
 		HIP_TRY(hipMemcpyAsync(&nbytes, d_at + total, 8, hipMemcpyDeviceToHost, st));
 		HIP_TRY(hipStreamSynchronize(st));           // (also: `offs` and the ids have left the host)
 		HIP_TRY(hipGetLastError());
-		if (nbytes + 1 > c->sam_text_cap) {
-			if (c->h_sam_text) (void) hipHostFree(c->h_sam_text);
-			free_set(c->d_sam_text);
-			c->h_sam_text = nullptr; c->sam_text_cap = 0;
-			const size_t want = (size_t) nbytes + (size_t) nbytes / 8 + 4096;
-			HIP_TRY(hipMalloc(&c->d_sam_text, want));
-			HIP_TRY(hipHostMalloc(&c->h_sam_text, want, hipHostMallocDefault));
-			c->sam_text_cap = want;
-		}
+		HIP_TRY(c->d_sam_text.reserve((size_t) nbytes + 1, (size_t) nbytes / 8 + 4095));          // nbytes + nbytes / 8 + 4096 bytes
+		HIP_TRY(c->h_sam_text.reserve((size_t) nbytes + 1, (size_t) nbytes / 8 + 4095));
 		hipLaunchKernelGGL(k_sam_write, dim3((u32) ((total + 3) / 4)), dim3(256), 0, st, s, total, d_at, (char*) c->d_sam_text);
 	}
 	*src = s; *total_out = total; *nbytes_out = nbytes; *d_len_out = d_len;
@@ -2582,13 +2543,8 @@ extern "C" int vdjx_sam_blocks(vdjx_ctx* c, const char* contigs, size_t n, int l
 	int rc = sam_text_device(c, db, contigs, n, len, ids, id_off, &s, &total, &nbytes, &d_len);
 	if (rc || !total) return rc;
 	hipStream_t st = c->stream;
-	if (total > c->sam_blk_cap) {
-		free_set(c->d_sam_keys); free_set(c->d_sam_lens);
-		c->sam_blk_cap = 0;
-		HIP_TRY(hipMalloc(&c->d_sam_keys, (size_t) (total + total / 8 + 64) * 8));
-		HIP_TRY(hipMalloc(&c->d_sam_lens, (size_t) (total + total / 8 + 64) * 4));
-		c->sam_blk_cap = (size_t) (total + total / 8 + 64);
-	}
+	HIP_TRY(c->d_sam_keys.reserve((size_t) total * 8, (size_t) (total / 8 + 64) * 8));
+	HIP_TRY(c->d_sam_lens.reserve((size_t) total * 4, (size_t) (total / 8 + 64) * 4));
 	hipLaunchKernelGGL(k_sam_keys, dim3((u32) ((total + 255) / 256)), dim3(256), 0, st, s, total, d_reg_rank, (u64*) c->d_sam_keys);
 	HIP_TRY(hipMemcpyAsync(c->d_sam_lens, d_len, (size_t) total * 4, hipMemcpyDeviceToDevice, st));
 	HIP_TRY(hipStreamSynchronize(st));
@@ -2656,13 +2612,7 @@ extern "C" int vdjx_sam_merge(vdjx_ctx* c, uint64_t n_blocks, uint64_t n_bytes, 
 	HIP_TRY(hipStreamSynchronize(st));
 	HIP_TRY(hipGetLastError());
 	if (tot_in != n_bytes || tot_out != n_bytes) { vdjx_set_error("vdjx_sam_merge: the blocks' lengths add up to %llu bytes, the text has %llu", (unsigned long long) tot_in, (unsigned long long) n_bytes); return VDJX_EINVAL; }
-	if (n_bytes + 1 > c->sam_merge_cap) {
-		if (c->h_sam_merge) (void) hipHostFree(c->h_sam_merge);
-		c->h_sam_merge = nullptr; c->sam_merge_cap = 0;
-		const size_t want = (size_t) n_bytes + (size_t) n_bytes / 8 + 4096;
-		HIP_TRY(hipHostMalloc(&c->h_sam_merge, want, hipHostMallocDefault));
-		c->sam_merge_cap = want;
-	}
+	HIP_TRY(c->h_sam_merge.reserve((size_t) n_bytes + 1, (size_t) n_bytes / 8 + 4095));          // n_bytes + n_bytes / 8 + 4096 bytes
 	HIP_TRY(hipMemcpyAsync(c->h_sam_merge, d_out, (size_t) n_bytes, hipMemcpyDeviceToHost, st));
 	HIP_TRY(hipStreamSynchronize(st));
 	((char*) c->h_sam_merge)[n_bytes] = 0;

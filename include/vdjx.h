@@ -336,8 +336,9 @@ int vdjx_quant(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const vdjx
  *               the M/I/D runs 5' to 3' as len << 4 | op (op 0 M, 1 I, 2 D: BAM's codes); n_runs counts them all, runs[] holds them only
  *               when n_runs <= 64 (otherwise zeros: the CIGAR is written empty, stat "annot_cigar_truncated").  S = 0: no traceback
  *               (coordinates and counts 0).  identity = matches / (matches + mismatches + ins + del).
- * NOT modelled: D calls; IMGT-gapped sequence_alignment / germline_alignment; reverse-complement contigs (a contig is always V to J);
- * IgBLAST's or V-QUEST's own identity definitions.  The isotype is a call of its own against a constant-region set: vdjx_isotype below.
+ * NOT modelled: IMGT-gapped sequence_alignment / germline_alignment; reverse-complement contigs (a contig is always V to J);
+ * IgBLAST's or V-QUEST's own identity definitions.  The isotype is a call of its own against a constant-region set (vdjx_isotype below),
+ * the D gene a call of its own against the D records, between the V and the J hit (vdjx_dcall below).
  * VDJX_EINVAL: contigs of unequal length (a NUL inside the n*len characters), len >= 4096, a V/J germline of 0 or >= 2048 bases, 2^20
  * records or more, match outside 1..15 or mismatch / gap_open / gap_extend outside 0..31 (every H then fits int16); vdjx_annotate before
  * any vdjx_germline_load is VDJX_ESTATE.  n = 0 returns at once.  Scratch comes from the context's workspace; no floating-point atomics,
@@ -386,6 +387,44 @@ int vdjx_constant_load(vdjx_ctx* ctx, const char* seqs, const uint64_t* off, siz
 int vdjx_isotype(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const vdjx_isotype_params* params, vdjx_annot_hit* out_c,
                  int32_t* out_scores);
 
+/* ---- D calls: the bases between the V and the J hit against the D segments ------------------------------------------------------------
+ * gives `vdjer --airr` the d_call, the d_cigar and the N regions of a heavy-chain rearrangement (the part of the V-QUEST round trip that
+ * vdjx_annotate left open).  All arithmetic is integer: the device's results are bitwise the model's (tests/dcall_model.py).
+ *   D set       vdjx_dsegment_load: record r is seqs[off[r] .. off[r+1]), cleaned by the caller exactly as for vdjx_germline_load.  Every
+ *               record given is a D record whatever its name (vdjx_germline_load still counts and skips class 'D': the caller hands the
+ *               class-D records of the same FASTA to this call).  0 .. 4096 records of 1 .. 2047 bases.  The set lives in a device buffer
+ *               of its own, independent of the germline and the constant set, until the next vdjx_dsegment_load or vdjx_shutdown.
+ *   query       contig c's own window: contig[win_start[c] .. win_start[c] + win_len[c]), 0-based, given by the caller; win_len is
+ *               0 .. VDJX_DCALL_WINDOW = 256 (a wave holds four window rows per lane); the window lies inside the contig.
+ *   score       vdjx_annotate's recurrences and scoring rule, unchanged, window row i in 1..win_len[c], record r's column j in 1..g_r:
+ *               S(contig, r) = max H (0 for an empty window).  out_scores (may be NULL) receives every S, out_scores[contig * C + r].
+ *   call        the primary hit is the record of highest S, the lowest index on a tie; n_tied counts the records at that S and tied[]
+ *               lists the first 8 of them in index order.  No call (gene -1, n_tied 0, tied[] -1) when S < min_score, when C = 0 or
+ *               when win_len[c] = 0; score is S all the same.
+ *   traceback   the primary hit only, by vdjx_annotate's rules and preference order; every field of vdjx_annot_hit means what it means
+ *               there.  seq_start / seq_end are in CONTIG coordinates (window coordinate + win_start[c]); S = 0: no traceback.
+ *   the window `vdjer --airr --d-calls` uses (d_window in vdjer_main.c, vdjer_amd/annot.py and the model): with a V hit and a J hit
+ *               (gene >= 0 and score > 0, both), the bases strictly between them: start = v.seq_end, length = j.seq_start - 1 -
+ *               v.seq_end; a length <= 0 (the hits abut or overlap) is length 0; a length > 256 is length 0 and counted; no V hit or
+ *               no J hit is length 0.  A window of length 0 starts at 0.
+ * Defaults (what `vdjer --d-calls` uses): match 2, mismatch 3, gap_open 5, gap_extend 2, min_score 22: eleven matched bases.  Against 34
+ * random records of 11 .. 37 bases, 0.25 % of 400 random 24-base windows reach 22 (0.75 % reach 20; the highest S is 22), 0.5 % of 400
+ * random 45-base windows (3.0 % reach 20; highest 26) and 0.75 % of 400 random 64-base windows (3.5 % reach 20; highest 23); 200 exact
+ * cuts of 11 .. 16 bases, each planted in a random 45-base window, all score at least 22 and all are called for their own record
+ * (tests/test_dcall_cpu.py measures these again).  It is a parameter of the model, not a tolerance.
+ * NOT modelled: D genes in inverted orientation; a second D (D-D fusions); P nucleotides as distinct from N (np1 / np2 of the table are
+ * whatever lies between the hits); IgBLAST's or V-QUEST's own D scoring.
+ * VDJX_EINVAL: contigs of unequal length (a NUL inside the n*len characters), len >= 4096, n >= 2^20, match outside 1..15 or mismatch /
+ * gap_open / gap_extend outside 0..31, min_score < 0, a negative win_start or win_len, win_len > 256, a window past the contig's end; more
+ * than 4096 records or a record of 0 or >= 2048 bases (vdjx_dsegment_load).  vdjx_dcall before any vdjx_dsegment_load is VDJX_ESTATE.
+ * n = 0 returns at once.  A call is three kernel dispatches (score, merge, trace) whatever n and C are.  Scratch comes from the context's
+ * workspace; no floating point, no atomics: two calls give the same bits. */
+#define VDJX_DCALL_WINDOW 256
+typedef struct { int match, mismatch, gap_open, gap_extend, min_score; } vdjx_dcall_params;   /* 20 bytes */
+int vdjx_dsegment_load(vdjx_ctx* ctx, const char* seqs, const uint64_t* off, size_t n);
+int vdjx_dcall(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const int32_t* win_start, const int32_t* win_len,
+               const vdjx_dcall_params* params, vdjx_annot_hit* out_d, int32_t* out_scores);
+
 /* rows of `row` bytes on the device: row d_pos[i] of d_dst = row i of d_src.  (The records of a pool sharded by pair on their way to
  * the ranks that hold their slice of the scan order for the k-mer build, A2:1388-1390: every record arrives with its place.) */
 int vdjx_rows_scatter(vdjx_ctx* ctx, void* d_dst, const void* d_src, const uint32_t* d_pos, size_t n, size_t row);
@@ -401,8 +440,9 @@ int vdjx_scan_u32(vdjx_ctx* ctx, const uint32_t* host_in, size_t n, int out_is_u
  * call: "quant_map_us", "quant_setup_us", "quant_em_us" (host clock, each phase ending in a wait for the device), "quant_contigs_placed".
  * vdjx_annotate's last call: "annot_cells" (DP cells of the scoring phase), "annot_score_us", "annot_trace_us", "annot_cigar_truncated".
  * vdjx_isotype's last call: "iso_cells" (DP cells of the scoring phase), "iso_score_us", "iso_trace_us" (host clock, each ending in a wait).
+ * vdjx_dcall's last call: "dcall_cells" (the sum of win_len times the sum of the records' lengths), "dcall_score_us", "dcall_trace_us".
  * What the context keeps from call to call outside its workspaces (anchor bitmaps, V region, read index, the scorers' result and SAM
- * buffers, upload staging, germline / constant sets), counted when asked: "kept_device_bytes", "kept_pinned_bytes" (page-locked host
+ * buffers, upload staging, germline / constant / D sets), counted when asked: "kept_device_bytes", "kept_pinned_bytes" (page-locked host
  * memory) and "kept_allocs" (allocations made for them since vdjx_init: unchanged by a call that fitted what was there).  vdjx_trim
  * and vdjx_read_index_drop lower the byte counts.  Defined while no begun read-index build is in flight (it grows the index's arrays
  * on a thread of its own). */

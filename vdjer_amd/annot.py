@@ -47,6 +47,22 @@ def parse_record(header: str, seq: str):
     return name, parse_class(name), clean_seq(seq)
 
 
+DCALL_WINDOW = 256                                          # VDJX_DCALL_WINDOW (include/vdjx.h)
+
+
+def d_window(v, j):
+    """the window `vdjer --airr --d-calls` hands to vdjx_dcall, from the V and the J hits ({field: array} as Context.annotate returns
+    them) -> (start, length) int32 arrays: with a V and a J hit (gene >= 0 and score > 0) the bases strictly between them (0-based start
+    v.seq_end, length j.seq_start - 1 - v.seq_end); length 0 (and start 0) when the hits abut or overlap, when more than 256 bases lie
+    between them, or without a V hit or a J hit"""
+    import numpy as np
+    has = (np.asarray(v["gene"]) >= 0) & (np.asarray(v["score"]) > 0) & (np.asarray(j["gene"]) >= 0) & (np.asarray(j["score"]) > 0)
+    start = np.asarray(v["seq_end"]).astype(np.int64)
+    length = np.asarray(j["seq_start"]).astype(np.int64) - 1 - start
+    ok = has & (length > 0) & (length <= DCALL_WINDOW)
+    return np.where(ok, start, 0).astype(np.int32), np.where(ok, length, 0).astype(np.int32)
+
+
 def gene_of(name: str) -> str:
     """the gene of an allele name: the text before the first '*' (IGHG1*01 -> IGHG1)"""
     return name.split("*", 1)[0]

@@ -684,6 +684,46 @@ class Context:
         check(self.L.vdjx_isotype(self.h, raw, n, ln, C.byref(prm), _p(hc), _p(sc) if scores and sc.size else None), "vdjx_isotype")
         return {"c": {f: hc[f].copy() for f in self.ANNOT_HIT.names}, "scores": sc}
 
+    def dsegment_load(self, fasta_path_or_records):
+        """vdjx_dsegment_load: a germline FASTA (path) or a list of (FASTA header, sequence) records -> dict(names, skipped).  The records
+        whose class (vdjer_amd/annot.py parse_class) is D are kept and loaded, the others counted per class in `skipped`.  The set stays
+        on the device, beside the germline and the constant set."""
+        from . import annot
+        recs = annot.read_fasta(fasta_path_or_records) if isinstance(fasta_path_or_records, str) else list(fasta_path_or_records)
+        parsed = [annot.parse_record(h, q) for h, q in recs]
+        kept = [x for x in parsed if x[1] == "D"]
+        skipped = {}
+        for x in parsed:
+            if x[1] != "D":
+                skipped[x[1]] = skipped.get(x[1], 0) + 1
+        seqs = [x[2] for x in kept]
+        off = np.zeros(len(seqs) + 1, np.uint64)
+        off[1:] = np.cumsum([len(q) for q in seqs], dtype=np.uint64)
+        check(self.L.vdjx_dsegment_load(self.h, "".join(seqs).encode(), _p(off), len(seqs)), "vdjx_dsegment_load")
+        self._dseg_n = len(seqs)
+        return dict(names=[x[0] for x in kept], skipped=skipped)
+
+    def dcall(self, contigs, win_start, win_len, match: int = 2, mismatch: int = 3, gap_open: int = 5, gap_extend: int = 2,
+              min_score: int = 22, scores: bool = True):
+        """vdjx_dcall: contig c's window [win_start[c], win_start[c] + win_len[c]) (0-based, at most 256 bases) against the loaded D set
+        -> {"d": {field: array}, "scores": int32[n, C] | None}, the fields of vdjx_annot_hit (seq_start / seq_end in contig coordinates)"""
+        if isinstance(contigs, tuple):
+            raw, n, ln = contigs
+        else:
+            if len({len(s_) for s_ in contigs}) > 1:
+                raise VdjxError("vdjx_dcall: contigs of unequal length")
+            raw, n, ln = self.pack_strings(contigs)
+        ws = np.ascontiguousarray(win_start, np.int32)
+        wl = np.ascontiguousarray(win_len, np.int32)
+        if ws.shape != (n,) or wl.shape != (n,):
+            raise VdjxError(f"vdjx_dcall: {n} contigs, win_start of shape {ws.shape}, win_len of shape {wl.shape}")
+        hd = np.zeros(n, self.ANNOT_HIT)
+        nc = getattr(self, "_dseg_n", 0)
+        sc = np.zeros((n, nc), np.int32) if scores else None
+        prm = _lib.DcallParams(int(match), int(mismatch), int(gap_open), int(gap_extend), int(min_score))
+        check(self.L.vdjx_dcall(self.h, raw, n, ln, _p(ws), _p(wl), C.byref(prm), _p(hd), _p(sc) if scores and sc.size else None), "vdjx_dcall")
+        return {"d": {f: hd[f].copy() for f in self.ANNOT_HIT.names}, "scores": sc}
+
     def stat(self, name: str) -> int:
         return int(self.L.vdjx_stat(self.h, name.encode()))
 

@@ -4,10 +4,11 @@
  *
  *   vdjer --in <reads> --chain IGH|IGK|IGL --ref-dir <dir> --ins <n> [--t --k --mf --mq --mcs --am --miw --maw
  *         --jc --ws -jext --rf --vk --mrs --rs --ms --e0 --e1 --wo --vf --jf --rms] [--gpus N] [--quant <file>] [--airr <file>]
- *         [--cfa <fasta>] [--isotypes <file>] [--clones <file>] [--sample <name>] [--total-count <n>]
+ *         [--d-calls] [--cfa <fasta>] [--isotypes <file>] [--clones <file>] [--sample <name>] [--total-count <n>]
  * writes ./vdj_contigs.fa and ./vdjer.dot, SAM on stdout, log on stderr; exit 0 on success.  --quant <file>: the contigs' abundances
  * (vdjx_quant, RSEM's isoforms.results columns) into <file> as well.  --airr <file>: the contigs' V/J annotation (vdjx_annotate against
- * the germlines of ig_vdj.fa / --vdjf) as an AIRR Rearrangement TSV.  --cfa <fasta>: constant-region sequences; --isotypes <file>: the
+ * the germlines of ig_vdj.fa / --vdjf) as an AIRR Rearrangement TSV; with --d-calls (a flag: no value) the D gene between the V and the
+ * J hit as well (vdjx_dcall against the class-D records of the same FASTA), and the N regions around it.  --cfa <fasta>: constant-region sequences; --isotypes <file>: the
  * isotype call of every contig against them (vdjx_isotype); --clones <file>: the per-sample table of the reference's post_process/
  * (collect_vdjer_stats.py | cluster_results.py) from the three device steps (one GPU only).
  *
@@ -48,6 +49,7 @@ typedef struct {
 	int gpus;                              /* --gpus N (not in the reference): the k-mer build sharded over N GPUs of this node */
 	const char* quant;                     /* --quant <file> (not in the reference): the RSEM step of demo/quant_demo.bash, on the device */
 	const char* airr;                      /* --airr <file> (not in the reference): the HighV-QUEST step of post_process/, on the device */
+	int d_calls;                           /* --d-calls (not in the reference; no value): d_call, d_cigar and the N regions in the --airr table */
 	const char* cfa;                       /* --cfa <fasta> (not in the reference): the constant-region sequences of --isotypes / --clones */
 	const char* isotypes;                  /* --isotypes <file> (not in the reference): call_isotypes.bash of post_process/, on the device */
 	const char* clones;                    /* --clones <file> (not in the reference): collect_vdjer_stats.py | cluster_results.py */
@@ -68,6 +70,7 @@ static void usage(void) {
 	                "\t--gpus <GPUs of this node to shard the k-mer table over (default: 1)>\n"
 	                "\t--quant <file: expected read pairs per contig, an RSEM isoforms.results table (one GPU only)>\n"
 	                "\t--airr <file: V/J calls of every contig against ig_vdj.fa, an AIRR Rearrangement table>\n"
+	                "\t--d-calls (no value; with --airr: the D gene between the V and the J hit against the D records of ig_vdj.fa, and np1 / np2)\n"
 	                "\t--cfa <constant-region FASTA for --isotypes / --clones>\n"
 	                "\t--isotypes <file: isotype call of every contig's last 48 bases against --cfa>\n"
 	                "\t--clones <file: the clustered clone table of this sample (one GPU only)>\n"
@@ -87,6 +90,7 @@ static int parse(int argc, char** argv, cli* c) {
 	for (int i = 1; i < argc; i += 2) {
 		const char* a = argv[i];
 		if (!strcmp(a, "--help")) { usage(); exit(0); }
+		if (!strcmp(a, "--d-calls")) { c->d_calls = 1; i--; continue; }      /* (the one flag without a value) */
 		if (i + 1 >= argc) { fprintf(stderr, "Missing value for param: %s\n", a); usage(); return -1; }
 		const char* v = argv[i + 1];
 		if (!strcmp(a, "--in")) c->in = v;
@@ -151,6 +155,7 @@ static int parse(int argc, char** argv, cli* c) {
 	if (!c->source_sim_file[0]) { fprintf(stderr, "source_sim_file file must be specified\n"); ok = 0; }
 	if (c->hp.j_conserved != 'W' && c->hp.j_conserved != 'F') { fprintf(stderr, "Conserved J AA must be W or F: %c\n", c->hp.j_conserved); ok = 0; }
 	if (c->hp.insert_len <= 0) { fprintf(stderr, "insert_len must be specified and > 0\n"); ok = 0; }
+	if (c->d_calls && !c->airr) { fprintf(stderr, "--d-calls adds the D call to the --airr table: it needs --airr <file>\n"); ok = 0; }
 	if (c->isotypes && !c->cfa) { fprintf(stderr, "--isotypes needs the constant-region sequences: --cfa <fasta>\n"); ok = 0; }
 	if (c->cfa) {
 		FILE* fp = fopen(c->cfa, "r");
@@ -496,6 +501,9 @@ typedef struct {
 	const char* vdjf;
 	int airr_done;
 	size_t a_contigs, a_v, a_j, a_prod, a_trunc, a_skip_d, a_skip_other;
+	int d_calls;                        /* --d-calls: the D set (the class-D records of vdjf), the windows and the D hits (dcall_run) */
+	struct germ_set* dset; vdjx_annot_hit* hd;
+	size_t d_contigs, d_windows, d_over, d_called;
 	/* --isotypes / --clones: what the steps above and vdjx_isotype found is kept until the last table is written */
 	const char *cfa, *isotypes, *clones, *sample, *total_count;
 	struct germ_set* germ; vdjx_annot_hit *hv, *hj;      /* the germline records and the V / J hits (annot_run) */
@@ -699,6 +707,65 @@ static int annot_run(hook_ud* u, const char* contigs, size_t n, int len) {
 	return rc;
 }
 
+/* the window of --d-calls (include/vdjx.h, vdjx_dcall): the bases strictly between a V and a J hit -> its length (0: none), *start 0-based;
+ * *over: more than VDJX_DCALL_WINDOW bases lie between the hits (no window) */
+static int d_window(const vdjx_annot_hit* v, const vdjx_annot_hit* j, int32_t* start, int* over) {
+	*start = 0;
+	*over = 0;
+	if (!(v->gene >= 0 && v->score > 0 && j->gene >= 0 && j->score > 0)) return 0;
+	const int l = j->seq_start - 1 - v->seq_end;
+	if (l <= 0) return 0;
+	if (l > VDJX_DCALL_WINDOW) { *over = 1; return 0; }
+	*start = v->seq_end;
+	return l;
+}
+
+/* --d-calls: the D hits of every contig (vdjx_dcall: the window between its V and its J hit against the class-D records annot_run read) */
+static int dcall_run(hook_ud* u, const char* contigs, size_t n, int len) {
+	const germ_set* g = u->germ;
+	germ_set* d = u->dset = (germ_set*) calloc(1, sizeof(germ_set));
+	d->off = (uint64_t*) calloc(g->n + 1, sizeof(uint64_t));
+	d->names = (char**) calloc(g->n + 1, sizeof(char*));
+	d->seqs = (char*) malloc(g->bytes + 1);
+	for (size_t r = 0; r < g->n; r++) {
+		if (g->cls[r] != 'D') continue;
+		const size_t l = (size_t) (g->off[r + 1] - g->off[r]);
+		memcpy(d->seqs + d->bytes, g->seqs + g->off[r], l);
+		d->bytes += l;
+		d->names[d->n++] = g->names[r];
+		d->off[d->n] = d->bytes;
+	}
+	u->hd = (vdjx_annot_hit*) calloc(n + 1, sizeof(vdjx_annot_hit));
+	int32_t* ws = (int32_t*) calloc(n + 1, sizeof(int32_t));
+	int32_t* wl = (int32_t*) calloc(n + 1, sizeof(int32_t));
+	for (size_t i = 0; i < n; i++) {
+		int over;
+		wl[i] = d_window(u->hv + i, u->hj + i, ws + i, &over);
+		u->d_windows += wl[i] > 0;
+		u->d_over += (size_t) over;
+	}
+	const vdjx_dcall_params dp = {2, 3, 5, 2, 22};
+	int rc = vdjx_dsegment_load(u->gx, d->seqs, d->off, d->n);
+	if (!rc && n) rc = vdjx_dcall(u->gx, contigs, n, len, ws, wl, &dp, u->hd, NULL);
+	if (rc) fprintf(stderr, "--d-calls: %s\n", vdjx_last_error());
+	for (size_t i = 0; !rc && i < n; i++) { u->d_contigs++; u->d_called += u->hd[i].gene >= 0; }
+	free(ws);
+	free(wl);
+	return rc;
+}
+
+/* --d-calls: the ten columns after j_germline_end: the D hit's six cells, then np1 (V's end to D's start), np2 (D's end to J's start) and
+ * their lengths; without a D call np1 is the whole gap between the V and the J hit, without a V or a J hit the four cells are empty */
+static void put_np(FILE* fp, const char* s, const vdjx_annot_hit* v, const vdjx_annot_hit* d, const vdjx_annot_hit* j) {
+	put_hit(fp, d);
+	if (!(v->gene >= 0 && v->score > 0 && j->gene >= 0 && j->score > 0)) { fputs("\t\t\t\t", fp); return; }
+	const int hasd = d->gene >= 0 && d->score > 0;
+	const int a0 = v->seq_end, a1 = hasd ? d->seq_start - 1 : j->seq_start - 1;       /* np1: 0-based [a0, a1) */
+	const int b0 = hasd ? d->seq_end : 0, b1 = hasd ? j->seq_start - 1 : 0;            /* np2 */
+	const int l1 = a1 > a0 ? a1 - a0 : 0, l2 = b1 > b0 ? b1 - b0 : 0;
+	fprintf(fp, "\t%.*s\t%d\t%.*s\t%d", l1, s + a0, l1, l2, s + b0, l2);
+}
+
 static int airr_table(hook_ud* u, const char* const* ids, const char* contigs, size_t n, int len) {
 	const germ_set g = *u->germ;
 	const vdjx_annot_hit *hv = u->hv, *hj = u->hj;
@@ -709,6 +776,8 @@ static int airr_table(hook_ud* u, const char* const* ids, const char* contigs, s
 		fputs("sequence_id\tsequence\trev_comp\tproductive\tv_call\td_call\tj_call\tsequence_alignment\tgermline_alignment\tjunction\tjunction_aa\t"
 		      "cdr3\tcdr3_aa\tvj_in_frame\tstop_codon\tv_cigar\td_cigar\tj_cigar\tv_score\tv_identity\tv_sequence_start\tv_sequence_end\t"
 		      "v_germline_start\tv_germline_end\tj_score\tj_identity\tj_sequence_start\tj_sequence_end\tj_germline_start\tj_germline_end", fp);
+		if (u->d_calls)
+			fputs("\td_score\td_identity\td_sequence_start\td_sequence_end\td_germline_start\td_germline_end\tnp1\tnp1_length\tnp2\tnp2_length", fp);
 		fputs(u->quant ? "\texpected_count\n" : "\n", fp);
 		for (size_t i = 0; i < n; i++) {
 			const char* s = contigs + i * (size_t) len;
@@ -731,7 +800,9 @@ static int airr_table(hook_ud* u, const char* const* ids, const char* contigs, s
 			u->a_trunc += (v->gene >= 0 && v->n_runs > VDJX_ANNOT_RUNS) + (j->gene >= 0 && j->n_runs > VDJX_ANNOT_RUNS);
 			fprintf(fp, "%s\t%.*s\tF\t%c\t", ids[i], len, s, prod ? 'T' : 'F');
 			put_call(fp, v, &g);
-			fputs("\t\t", fp);
+			fputc('\t', fp);
+			if (u->d_calls) put_call(fp, u->hd + i, u->dset);
+			fputc('\t', fp);
 			put_call(fp, j, &g);
 			fputs("\t\t\t", fp);
 			fprintf(fp, "%.*s\t", (int) JL, p >= 0 ? s + p : "");
@@ -741,10 +812,13 @@ static int airr_table(hook_ud* u, const char* const* ids, const char* contigs, s
 			put_aa(fp, cl ? s + p + 3 : "", cl);
 			fprintf(fp, "\t%c\t%c\t", inframe ? 'T' : 'F', stop ? 'T' : 'F');
 			put_cigar(fp, v, len);
-			fputs("\t\t", fp);
+			fputc('\t', fp);
+			if (u->d_calls) put_cigar(fp, u->hd + i, len);
+			fputc('\t', fp);
 			put_cigar(fp, j, len);
 			put_hit(fp, v);
 			put_hit(fp, j);
+			if (u->d_calls) put_np(fp, s, v, u->hd + i, j);
 			if (u->quant) fprintf(fp, "\t%.2f", u->qcnt ? u->qcnt[i] : 0.0);
 			fputc('\n', fp);
 		}
@@ -903,6 +977,7 @@ static int tables(hook_ud* u, const char* const* ids, const char* contigs, size_
 	int rc = 0;
 	if (!rc && (u->quant || u->clones)) rc = quant_table(u, ids, contigs, n, len);
 	if (!rc && (u->airr || u->clones)) rc = annot_run(u, contigs, n, len);
+	if (!rc && u->d_calls) rc = dcall_run(u, contigs, n, len);
 	if (!rc && u->airr) rc = airr_table(u, ids, contigs, n, len);
 	if (!rc && u->cfa && (u->isotypes || u->clones)) rc = iso_run(u, contigs, n, len);
 	if (!rc && u->isotypes) rc = isotypes_table(u, ids, n, len);
@@ -1177,7 +1252,7 @@ int main(int argc, char** argv) {
 
 	hook_ud ud;
 	memset(&ud, 0, sizeof ud);
-	ud.gx = gx; ud.p = &c.hp; ud.mg = mg; ud.quant = c.quant; ud.airr = c.airr; ud.vdjf = c.vdj_fasta;
+	ud.gx = gx; ud.p = &c.hp; ud.mg = mg; ud.quant = c.quant; ud.airr = c.airr; ud.vdjf = c.vdj_fasta; ud.d_calls = c.d_calls;
 	ud.cfa = c.cfa; ud.isotypes = c.isotypes; ud.clones = c.clones; ud.total_count = c.total_count;
 	char sample_buf[4096];
 	if (c.sample) ud.sample = c.sample;
@@ -1227,6 +1302,9 @@ int main(int argc, char** argv) {
 	if (c.airr)
 		fprintf(stderr, "airr: %zu contigs, %zu V called, %zu J called, %zu productive, %zu CIGARs truncated; germline records skipped: %zu D, %zu other; table in %s\n",
 		        ud.a_contigs, ud.a_v, ud.a_j, ud.a_prod, ud.a_trunc, ud.a_skip_d, ud.a_skip_other, c.airr);
+	if (c.d_calls)
+		fprintf(stderr, "dcalls: %zu contigs, %zu windows, %zu over %d bases, %zu D called against %zu D records\n", ud.d_contigs, ud.d_windows, ud.d_over,
+		        VDJX_DCALL_WINDOW, ud.d_called, ud.dset ? ud.dset->n : (size_t) 0);
 	if (c.isotypes)
 		fprintf(stderr, "isotypes: %zu contigs, %zu called against %zu constant records of %s; table in %s\n", ud.i_contigs, ud.i_called,
 		        ud.cst ? ud.cst->n : (size_t) 0, c.cfa, c.isotypes);

@@ -1,7 +1,9 @@
-// vdjx_align.hip -- the local-alignment engine (affine gaps; the model is in include/vdjx.h, vdjx_annotate) and its two callers:
+// vdjx_align.hip -- the local-alignment engine (affine gaps; the model is in include/vdjx.h, vdjx_annotate) and its three callers:
 //   vdjx_germline_load / vdjx_annotate    whole contigs against the V and the J germlines (two classes, a call per class)
 //   vdjx_constant_load / vdjx_isotype     the last T bases of every contig against the constant records (one class, every score kept)
-// A query is a window of a contig (offset q0, m bases).  Every query is scored against every record of a set, the best records of each
+//   vdjx_dsegment_load / vdjx_dcall       a window of each contig's own (start, length <= 256) against the D records (one class, every score kept)
+// A query is a window of a contig (offset q0, m bases: one for all contigs, or -- the WIN forms of the kernels -- each contig's own, the
+// launch sized to the longest).  Every query is scored against every record of a set, the best records of each
 // class are kept, and the primary hit of each class is aligned again with direction bits and traced back.  Integer arithmetic
 // throughout, no atomics on results: bitwise reproducible.
 //
@@ -34,6 +36,7 @@
 #define AN_PAIRS 16777216u               // vdjx_annotate: (contig, germline) pairs per scoring launch (VDJX_ANNOT_PAIRS)
 #define ISO_CHUNK_COLS 2304u             // vdjx_isotype: columns per chunk at most (a record of 2047 bases and its two reset columns fit)
 #define ISO_MAX_RECORDS 4096u
+#define DC_CHUNK_COLS 2304u              // vdjx_dcall: columns per chunk at most (the widths tried)
 
 struct AnParams { int ma, mi, oe, ext; };
 struct AnChunk { u64 col0; u32 ncols, g0, ng; };
@@ -48,12 +51,15 @@ static inline uint8_t an_gcode(char ch) {               // record: A C G T -> 0.
 }
 
 // the query of contig c is queries[c * len .. + m) (the caller's pointer is at the window's offset in contig 0); MATRIX: scores[c * C + record] = S
-// of every record as well
-template <int R, bool MATRIX>
+// of every record as well.  WIN: the query of contig c is queries[c * len + win[c].x .. + win[c].y) instead, win[c].y <= 64 R (a row at or
+// past the wave's own length holds the base that matches nothing, as the rows past m do); a wave without a query (win[c].y == 0) writes its
+// zeros to the matrix and reports no record at all
+template <int R, bool MATRIX, bool WIN = false>
 __global__ __launch_bounds__(64 * AN_WAVES) void k_an_score(const char* __restrict__ queries, u32 n, u32 len, int m,
                                                            const uint8_t* __restrict__ cols, const AnChunk* __restrict__ chunks,
                                                            const u32* __restrict__ genes, const uint2* __restrict__ items, AnParams p, u32 C,
-                                                           int* __restrict__ scores, AnBest* __restrict__ res) {
+                                                           int* __restrict__ scores, AnBest* __restrict__ res,
+                                                           const int2* __restrict__ win = nullptr) {
 	__shared__ short ring[AN_WAVES][AN_RING][64];
 	__shared__ int tl[AN_WAVES][VDJX_ANNOT_TIED];
 	const u32 w = threadIdx.x >> 6, lane = threadIdx.x & 63u;
@@ -64,6 +70,11 @@ __global__ __launch_bounds__(64 * AN_WAVES) void k_an_score(const char* __restri
 	const u32* gn = genes + ch.g0;
 	const uint8_t* cc = cols + ch.col0;
 	const int T = (int) ch.ncols;
+	if (WIN) {
+		const int2 wn = win[c];
+		queries += wn.x;
+		m = wn.y;
+	}
 	int cb[R], H[R], E[R];
 #pragma unroll
 	for (int r = 0; r < R; r++) {
@@ -129,6 +140,7 @@ __global__ __launch_bounds__(64 * AN_WAVES) void k_an_score(const char* __restri
 	}
 	if (lane == 0) {
 		AnBest* o = res + (size_t) it.y * n + c;
+		if (WIN && m == 0) best = -1, ntied = 0;
 		o->score = best;
 		o->n_tied = ntied;
 		for (int q = 0; q < VDJX_ANNOT_TIED; q++) o->tied[q] = q < ntied ? tl[w][q] : -1;
@@ -255,14 +267,20 @@ __device__ __forceinline__ void an_trace_pair(const char* __restrict__ ct, int m
 }
 
 // the launch's dynamic LDS holds the six diagonals, `stride` shorts apart: STRIDE where the caller's queries have a fixed bound (a tail:
-// AN_TAIL_STRIDE, 792 bytes, and LDS addresses the compiler knows), else (STRIDE = 0) m + 1 for rows 0 .. m (48 KB at m = 4095)
-template <int STRIDE>
+// AN_TAIL_STRIDE, 792 bytes, and LDS addresses the compiler knows), else (STRIDE = 0) m + 1 for rows 0 .. m (48 KB at m = 4095).
+// WIN: the alignment's query is its contig's own window win[contig] = (q0, m) of at most the launch's m bases (the LDS is sized to that).
+template <int STRIDE, bool WIN = false>
 __global__ __launch_bounds__(64) void k_an_trace(const char* __restrict__ contigs, int len, int q0, int m, const uint8_t* __restrict__ cols,
                                                  const AnAlign* __restrict__ al, AnParams p, uint8_t* __restrict__ dirs, u32 n,
-                                                 vdjx_annot_hit* __restrict__ hits) {
+                                                 vdjx_annot_hit* __restrict__ hits, const int2* __restrict__ win = nullptr) {
 	extern __shared__ short diags[];
 	const int stride = STRIDE ? STRIDE : m + 1;
 	const AnAlign a = al[blockIdx.x];
+	if (WIN) {
+		const int2 wn = win[a.contig];
+		q0 = wn.x;
+		m = wn.y;
+	}
 	an_trace_pair(contigs + (size_t) a.contig * len + q0, m, cols + a.gat, a.g, p, dirs + a.dir, hits + (size_t) a.cls * n + a.contig, q0, diags,
 	              diags + 3 * stride, diags + 5 * stride, stride);
 }
@@ -320,6 +338,18 @@ extern "C" int vdjx_constant_load(vdjx_ctx* c, const char* seqs, const uint64_t*
 	return an_set_load(c, c->constant, 1, seqs, off, k.data(), n);
 }
 
+extern "C" int vdjx_dsegment_load(vdjx_ctx* c, const char* seqs, const uint64_t* off, size_t n) {
+	if (!c || (n && (!seqs || !off))) { vdjx_set_error("vdjx_dsegment_load: NULL argument"); return VDJX_EINVAL; }
+	if (n > ISO_MAX_RECORDS) { vdjx_set_error("vdjx_dsegment_load: %zu records (at most %u)", n, ISO_MAX_RECORDS); return VDJX_EINVAL; }
+	for (size_t r = 0; r < n; r++) {
+		if (off[r + 1] < off[r]) { vdjx_set_error("vdjx_dsegment_load: offsets of record %zu decrease", r); return VDJX_EINVAL; }
+		const u64 L = off[r + 1] - off[r];
+		if (L == 0 || L >= 2048) { vdjx_set_error("vdjx_dsegment_load: record %zu has %llu bases (1 .. 2047)", r, (unsigned long long) L); return VDJX_EINVAL; }
+	}
+	const std::vector<int8_t> k(n, 0);
+	return an_set_load(c, c->dsegment, 1, seqs, off, k.data(), n);
+}
+
 static int an_rows(int m) {                 // rows per lane: the smallest instantiated R with 64 R >= m
 	static const int rs[] = {1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 48, 64};
 	for (int r : rs)
@@ -336,10 +366,11 @@ struct AnCall {
 	const char* who;                     // the caller's name in messages
 	const vdjx_recset* set;
 	int tail;                            // the query: the last min(tail, len) bases of every contig (0: all of it)
+	const int32_t *win_start, *win_len;  // or, when not NULL, each contig's own window [n] (inside the contig, at most 256 bases: the caller checked)
 	int min_score[2];                    // per class: the smallest S that is a call
 	u32 chunk_cols, chunk_recs;          // a chunk's columns and records at most
 	u64 pairs;                           // (contig, record) pairs per scoring launch at most
-	bool matrix;                         // keep S of every (contig, record): the set's one class, a query of at most 64 bases
+	bool matrix;                         // keep S of every (contig, record): the set's one class, a query of at most 64 bases (256 with windows)
 	int32_t* out_scores;                 // [n][records], or NULL
 	const char *scope_score, *scope_trace;
 	vdjx_annot_hit* out[2];              // per class: [n]
@@ -355,7 +386,17 @@ static int an_run(vdjx_ctx* c, const char* contigs, size_t n, int len, AnParams 
 	if (memchr(contigs, 0, n * (size_t) len)) { vdjx_set_error("%s: contigs of unequal length (a NUL inside the %zu x %d characters)", a.who, n, len); return VDJX_EINVAL; }
 	const auto t0 = std::chrono::steady_clock::now();
 	const vdjx_recset& s = *a.set;
-	const int ncls = s.ncls, m = a.tail ? std::min(a.tail, len) : len, q0 = len - m;
+	const bool win = a.win_len != nullptr;
+	std::vector<int2> wins(win ? n : 0);
+	u64 rows = 0;                                          // query bases of all contigs
+	int wmax = 0;
+	for (size_t q = 0; q < wins.size(); q++) {
+		wins[q] = make_int2(a.win_start[q], a.win_len[q]);
+		rows += (u64) a.win_len[q];
+		wmax = std::max(wmax, a.win_len[q]);
+	}
+	const int ncls = s.ncls, m = win ? wmax : a.tail ? std::min(a.tail, len) : len, q0 = win ? 0 : len - m;
+	if (!win) rows = (u64) m * (u64) n;
 
 	// chunks: class by class; genes: the record index of every column run; items: chunk-major, AN_WAVES contigs each
 	std::vector<AnChunk> chunks;
@@ -373,7 +414,7 @@ static int an_run(vdjx_ctx* c, const char* contigs, size_t n, int len, AnParams 
 			x = y;
 		}
 		ck[k].y = (u32) chunks.size();
-		for (u32 x : s.len[k]) cells += (u64) x * (u64) m * (u64) n;
+		for (u32 x : s.len[k]) cells += (u64) x * rows;
 	}
 	const u32 ngroups = (u32) ((n + AN_WAVES - 1) / AN_WAVES);
 	std::vector<uint2> items;
@@ -399,29 +440,36 @@ static int an_run(vdjx_ctx* c, const char* contigs, size_t n, int len, AnParams 
 	hipStream_t st = c->stream;
 	vdjx_work wk(c);
 	char *d_ct, *d_tab;
+	int2* d_win;
 	int* d_scores;
 	AnBest* d_res;
 	vdjx_annot_hit* d_hits;
 	HIP_TRY(wk.alloc(&d_ct, n * (size_t) len));
 	HIP_TRY(wk.alloc(&d_tab, tab.size()));
+	HIP_TRY(wk.alloc(&d_win, wins.size()));
 	HIP_TRY(wk.alloc(&d_scores, a.matrix ? n * C : 0));
 	HIP_TRY(wk.alloc(&d_res, nck * n));
 	HIP_TRY(wk.alloc(&d_hits, ncls * n));
 	HIP_TRY(hipMemcpyAsync(d_ct, contigs, n * (size_t) len, hipMemcpyHostToDevice, st));
 	if (C) HIP_TRY(hipMemcpyAsync(d_tab, tab.data(), tab.size(), hipMemcpyHostToDevice, st));
+	if (win) HIP_TRY(hipMemcpyAsync(d_win, wins.data(), wins.size() * sizeof(int2), hipMemcpyHostToDevice, st));
 	HIP_TRY(hipMemsetAsync(d_hits, 0, ncls * n * sizeof(vdjx_annot_hit), st));
 	const AnChunk* d_ck = (const AnChunk*) d_tab;
 	const uint2* d_items = (const uint2*) (d_tab + b_ck);
 	const u32* d_genes = (const u32*) (d_tab + b_ck + b_it);
-#define AN_LAUNCH(RR, MX) hipLaunchKernelGGL((k_an_score<RR, MX>), dim3(nb), dim3(64 * AN_WAVES), 0, st, (const char*) d_ct + q0, (u32) n, (u32) len, m, \
-	(const uint8_t*) s.d_cols, d_ck, d_genes, d_items + b0, p, (u32) C, d_scores, d_res)
-#define AN_CASE(RR) case RR: AN_LAUNCH(RR, false); break;
+#define AN_LAUNCH(RR, MX, WN) hipLaunchKernelGGL((k_an_score<RR, MX, WN>), dim3(nb), dim3(64 * AN_WAVES), 0, st, (const char*) d_ct + q0, (u32) n, (u32) len, m, \
+	(const uint8_t*) s.d_cols, d_ck, d_genes, d_items + b0, p, (u32) C, d_scores, d_res, (const int2*) d_win)
+#define AN_CASE(RR) case RR: AN_LAUNCH(RR, false, false); break;
+#define AN_CASE_WIN(RR) case RR: AN_LAUNCH(RR, true, true); break;
 	{
 		vdjx_prof_scope ps(c, a.scope_score);
 		for (size_t L = 0; L + 1 < launch_at.size(); L++) {
 			const u32 b0 = launch_at[L], nb = launch_at[L + 1] - b0;
 			if (!nb) continue;
-			if (a.matrix) AN_LAUNCH(1, true);
+			if (win) switch (an_rows(m)) {                  // (m <= 256: 1 .. 4 rows per lane)
+				AN_CASE_WIN(1) AN_CASE_WIN(2) AN_CASE_WIN(3) AN_CASE_WIN(4)
+			}
+			else if (a.matrix) AN_LAUNCH(1, true, false);
 			else switch (an_rows(m)) {
 				AN_CASE(1) AN_CASE(2) AN_CASE(3) AN_CASE(4) AN_CASE(6) AN_CASE(8) AN_CASE(12) AN_CASE(16) AN_CASE(24) AN_CASE(32) AN_CASE(48) AN_CASE(64)
 			}
@@ -429,6 +477,7 @@ static int an_run(vdjx_ctx* c, const char* contigs, size_t n, int len, AnParams 
 		hipLaunchKernelGGL(k_an_merge, dim3((u32) ((ncls * n + 255) / 256)), dim3(256), 0, st, (const AnBest*) d_res, (u32) n, (u32) ncls, ck[0], ck[1],
 		                   a.min_score[0], a.min_score[1], d_hits);
 	}
+#undef AN_CASE_WIN
 #undef AN_CASE
 #undef AN_LAUNCH
 	std::vector<vdjx_annot_hit> hh(ncls * n);
@@ -448,7 +497,7 @@ static int an_run(vdjx_ctx* c, const char* contigs, size_t n, int len, AnParams 
 			const vdjx_annot_hit& h = hh[(size_t) k * n + q];
 			if (h.gene < 0 || h.score <= 0) continue;
 			const size_t slot = std::lower_bound(s.rec[k].begin(), s.rec[k].end(), (u32) h.gene) - s.rec[k].begin();
-			const u64 b = (u64) m * s.len[k][slot];
+			const u64 b = (u64) (win ? a.win_len[q] : m) * s.len[k][slot];
 			if (used && used + b > AN_DIR_BYTES) { at.push_back(al.size()); used = 0; }
 			al.push_back({(u32) q, (u32) k, used, s.at[k][slot], (int) s.len[k][slot]});
 			used += b;
@@ -462,11 +511,12 @@ static int an_run(vdjx_ctx* c, const char* contigs, size_t n, int len, AnParams 
 		HIP_TRY(wk.alloc(&d_dir, peak));
 		HIP_TRY(hipMemcpyAsync(d_al, al.data(), al.size() * sizeof(AnAlign), hipMemcpyHostToDevice, st));
 		vdjx_prof_scope ps(c, a.scope_trace);
-		const auto trace = a.matrix ? k_an_trace<AN_TAIL_STRIDE> : k_an_trace<0>;
-		const size_t lds = 6 * sizeof(short) * (a.matrix ? AN_TAIL_STRIDE : m + 1);
+		const bool fixed = a.matrix && !win;                // (a tail: at most 64 rows)
+		const auto trace = win ? k_an_trace<0, true> : fixed ? k_an_trace<AN_TAIL_STRIDE> : k_an_trace<0>;
+		const size_t lds = 6 * sizeof(short) * (fixed ? AN_TAIL_STRIDE : m + 1);
 		for (size_t L = 0; L + 1 < at.size(); L++)
 			hipLaunchKernelGGL(trace, dim3((u32) (at[L + 1] - at[L])), dim3(64), lds, st, (const char*) d_ct, len, q0, m, (const uint8_t*) s.d_cols,
-			                   (const AnAlign*) d_al + at[L], p, d_dir, (u32) n, d_hits);
+			                   (const AnAlign*) d_al + at[L], p, d_dir, (u32) n, d_hits, (const int2*) d_win);
 	}
 	for (int k = 0; k < ncls; k++) HIP_TRY(hipMemcpyAsync(a.out[k], d_hits + (size_t) k * n, n * sizeof(vdjx_annot_hit), hipMemcpyDeviceToHost, st));
 	HIP_TRY(hipStreamSynchronize(st));
@@ -490,7 +540,7 @@ extern "C" int vdjx_annotate(vdjx_ctx* c, const char* contigs, size_t n, int len
 	}
 	if (!c->germline.loaded) { vdjx_set_error("vdjx_annotate: no germline set is loaded (call vdjx_germline_load first)"); return VDJX_ESTATE; }
 	static const u32 pairs = (u32) vdjx_env_num("VDJX_ANNOT_PAIRS", AN_PAIRS, 1, 0xFFFFFFFFll);
-	AnCall a = {"vdjx_annotate", &c->germline, 0, {prm->min_v_score, prm->min_j_score}, AN_CHUNK_COLS, std::max<u32>(1u, pairs / AN_WAVES), pairs, false,
+	AnCall a = {"vdjx_annotate", &c->germline, 0, nullptr, nullptr, {prm->min_v_score, prm->min_j_score}, AN_CHUNK_COLS, std::max<u32>(1u, pairs / AN_WAVES), pairs, false,
 	            nullptr, "k_annot_score", "k_annot_trace", {out_v, out_j}};
 	const int rc = an_run(c, contigs, n, len, {prm->match, prm->mismatch, prm->gap_open + prm->gap_extend, prm->gap_extend}, a);
 	u64 trunc = 0;
@@ -512,11 +562,35 @@ extern "C" int vdjx_isotype(vdjx_ctx* c, const char* contigs, size_t n, int len,
 		return VDJX_EINVAL;
 	}
 	if (!c->constant.loaded) { vdjx_set_error("vdjx_isotype: no constant set is loaded (call vdjx_constant_load first)"); return VDJX_ESTATE; }
-	AnCall a = {"vdjx_isotype", &c->constant, prm->tail, {prm->min_score, 0}, ISO_CHUNK_COLS, ~0u, ~0ull, true, out_scores, "k_iso_score", "k_iso_trace",
+	AnCall a = {"vdjx_isotype", &c->constant, prm->tail, nullptr, nullptr, {prm->min_score, 0}, ISO_CHUNK_COLS, ~0u, ~0ull, true, out_scores, "k_iso_score", "k_iso_trace",
 	            {out_c, nullptr}};
 	const int rc = an_run(c, contigs, n, len, {prm->match, prm->mismatch, prm->gap_open + prm->gap_extend, prm->gap_extend}, a);
 	c->stats["iso_cells"] = a.cells;
 	c->stats["iso_score_us"] = a.us_score;
 	c->stats["iso_trace_us"] = a.us_trace;
+	return rc;
+}
+
+extern "C" int vdjx_dcall(vdjx_ctx* c, const char* contigs, size_t n, int len, const int32_t* win_start, const int32_t* win_len,
+                          const vdjx_dcall_params* prm, vdjx_annot_hit* out_d, int32_t* out_scores) {
+	if (!c || !prm || (n && (!contigs || !win_start || !win_len || !out_d))) { vdjx_set_error("vdjx_dcall: NULL argument"); return VDJX_EINVAL; }
+	if (!an_scores_ok(prm->match, prm->mismatch, prm->gap_open, prm->gap_extend) || prm->min_score < 0) {
+		vdjx_set_error("vdjx_dcall: parameters match=%d mismatch=%d gap_open=%d gap_extend=%d min_score=%d (match 1..15, mismatch and the gap "
+		               "costs 0..31, min_score >= 0)", prm->match, prm->mismatch, prm->gap_open, prm->gap_extend, prm->min_score);
+		return VDJX_EINVAL;
+	}
+	if (!c->dsegment.loaded) { vdjx_set_error("vdjx_dcall: no D set is loaded (call vdjx_dsegment_load first)"); return VDJX_ESTATE; }
+	for (size_t q = 0; q < n; q++)
+		if (win_start[q] < 0 || win_len[q] < 0 || win_len[q] > VDJX_DCALL_WINDOW || (int64_t) win_start[q] + win_len[q] > len) {
+			vdjx_set_error("vdjx_dcall: window %d + %d of contig %zu (start and length >= 0, at most %d bases, inside the %d bases of the contig)",
+			               win_start[q], win_len[q], q, VDJX_DCALL_WINDOW, len);
+			return VDJX_EINVAL;
+		}
+	AnCall a = {"vdjx_dcall", &c->dsegment, 0, win_start, win_len, {prm->min_score, 0}, DC_CHUNK_COLS, ~0u, ~0ull, true, out_scores, "k_dcall_score",
+	            "k_dcall_trace", {out_d, nullptr}};
+	const int rc = an_run(c, contigs, n, len, {prm->match, prm->mismatch, prm->gap_open + prm->gap_extend, prm->gap_extend}, a);
+	c->stats["dcall_cells"] = a.cells;
+	c->stats["dcall_score_us"] = a.us_score;
+	c->stats["dcall_trace_us"] = a.us_trace;
 	return rc;
 }

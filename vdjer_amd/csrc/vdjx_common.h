@@ -260,7 +260,7 @@ struct vdjx_ctx {
 	vdjx_buf<void> d_sam_keys, d_sam_lens;                  // vdjx_sam_blocks: per mapped pair its ordering key and the bytes of its two lines
 	vdjx_buf<void> h_sam_merge{true}; // vdjx_sam_merge: the merged text (page-locked)
 	u32 n_pairs = 0, n_classes = 0;
-	vdjx_recset germline, constant;   // vdjx_germline_load (classes V, J) / vdjx_constant_load (one class): independent of each other
+	vdjx_recset germline, constant, dsegment;   // vdjx_germline_load (classes V, J) / vdjx_constant_load / vdjx_dsegment_load (one class each): independent of each other
 	std::map<std::string, uint64_t> stats;
 	// every kept buffer of the context, each once: the ONE list behind vdjx_shutdown, vdjx_trim, vdjx_read_index_drop and the kept_*
 	// statistics.  A fixed list over members: a buffer that grows (the index's arrays do on the read-index thread) changes nothing here.
@@ -268,7 +268,7 @@ struct vdjx_ctx {
 		vdjx_kept* const index[] = {&d_ri_tab, &d_ri_start, &d_ri_cnt1, &d_ri_recs, &d_ri_csr8, &d_ri_csr_pair, &d_ri_dstart, &d_ri_d8, &d_pair_r2};
 		vdjx_kept* const result[] = {&wp_buf, &me_pairs, &me_hit, &me_dense, &me_book, &d_sam_text, &h_sam_text, &d_sam_keys, &d_sam_lens};
 		vdjx_kept* const other[] = {&h_pin, &d_stage[0], &d_stage[1], &d_vbits, &d_jbits, &d_anchor_tmp, &d_vtext, &d_line_off, &d_seed_code, &d_seed_pos,
-		                            &h_plan, &h_res, &d_sam_names, &d_sam_noff, &h_sam_merge, &germline.d_cols, &constant.d_cols};
+		                            &h_plan, &h_res, &d_sam_names, &d_sam_noff, &h_sam_merge, &germline.d_cols, &constant.d_cols, &dsegment.d_cols};
 		for (vdjx_kept* b : index) f(*b, VDJX_KEPT_INDEX);
 		for (vdjx_kept* b : result) f(*b, VDJX_KEPT_RESULT);
 		for (vdjx_kept* b : other) f(*b, VDJX_KEPT_OTHER);

@@ -434,6 +434,16 @@ int vdjx_rows_scatter(vdjx_ctx* ctx, void* d_dst, const void* d_src, const uint3
  * launches: 1 = one workgroup, 3 = the device-wide form.  VDJX_EINVAL: n >= 2^31, launches neither 1 nor 3. */
 int vdjx_scan_u32(vdjx_ctx* ctx, const uint32_t* host_in, size_t n, int out_is_u64, int launches, void* host_out);
 
+/* For the test suite only: the LDS-staged partition pass of the k-mer build (csrc/vdjx_part.h), on its own.  n elements of elem_bytes
+ * (8 or 16) go to host_out grouped by bucket, host_starts[0 .. nb] are the buckets' starts (their exclusive prefix sum); the order inside
+ * a bucket is arbitrary.  The bucket of an element is bits 40..63 of its first 8-byte word.  An 8-byte element of all ones is a hole:
+ * it is dropped, so host_out receives host_starts[nb] <= n elements.  levels 1: nb <= 1024 buckets in one pass, the input shared by
+ * `workgroups`.  levels 2: nb = coarse << fine_bits (coarse <= 1024, fine_bits <= 10), the first pass into `coarse` segments, the second
+ * inside every segment with `slices` workgroups.  VDJX_EINVAL: elem_bytes, levels, nb or fine_bits outside that, slices or workgroups
+ * zero (or above 1024 / 65536), an element whose bucket is not below nb, n >= 2^31. */
+int vdjx_part_u64(vdjx_ctx* ctx, const void* host_in, size_t n, int elem_bytes, uint32_t nb, int levels, uint32_t fine_bits, uint32_t slices,
+                  uint32_t workgroups, uint32_t* host_starts, void* host_out);
+
 /* counters of the most recent scorer calls, by name: "window_hits" (read instances matched by the last
  * vdjx_window_score call, summed over windows), "window_hits_max", "window_pairs", "window_work_items",
  * "map_hits", "root_dp_items".  Unknown names return 0.  Used by bench.py to price the scorers' algorithmic bytes.  vdjx_quant's last

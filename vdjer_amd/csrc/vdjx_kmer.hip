@@ -7,17 +7,19 @@
 // recount) is done bucket-locally in LDS.  All of it is integer/byte work bounded by HBM traffic; no
 // MFMA applies.
 //
-//   K2a k_kmer_hist        per-workgroup LDS histogram of bucket sizes over a slice of the pool, added to the global counts
+//   K2a k_gated_hist       per-workgroup LDS histogram of the gated instances' buckets over a slice of the pool, added to the global counts
 //   K2b vdjx_scan_one      exclusive bucket starts (vdjx_scan.h)
-//   K2c k_part_records /   LDS-staged counting sort per round: tuples {key_lo, key_hi, inst|gated} written as
-//       k_part_tuples      coalesced bucket runs (256 coarse buckets, then 128 fine ones inside each; large pools:
-//                          2^(T-10) coarse, a counting pass, 1024 fine); positions inside a bucket from cursor bumps
+//   K2c k_part_records_g / the LDS-staged partition (vdjx_part.h): tuples {key_lo, key_hi, inst|gated} written as coalesced bucket runs,
+//       k_part             at most 1,024 buckets per pass; more in a second pass inside each coarse bucket (k_seg_hist_g counts the fine
+//                          ones where the histogram's buckets are cut again); positions inside a bucket from cursor bumps
 //   K3  k_gated_reduce     LDS open-addressing table per bucket: gated count, first instance, distinct-read flag and (for low-count
 //                          keys, see TLOW) quality sums per distinct k-mer -> survivors; sharded: k_gated_local + k_bucket_merge
-//   K4  k_walk_items / k_recount   the ungated recount: runs of surviving k-mers along the records, counted per survivor range
-//   K5  k_surv_table / k_graph_edges / k_node_flags   survivor lookup table, ordered edges, V/J flags
+//   K4  k_walk_items / k_recount   the ungated recount: runs of surviving k-mers along the records, partitioned by survivor range
+//                          (vdjx_part.h again) and counted per range
+//   K5  k_surv_table2 / k_succ_links2 / k_node_emit2   survivor lookup table, successor links, the nodes in their order
 #include "vdjx_common.h"
 #include "vdjx_scan.h"
+#include "vdjx_part.h"
 
 #include <algorithm>
 #include <numeric>
@@ -50,55 +52,11 @@ __device__ inline RecView load_rec(const u64* __restrict__ bases, const u64* __r
 	return v;
 }
 
-// ----------------------------------------------------------------------------------------------
-// K2c: LDS-staged partition (software write combining).
-// A direct scatter into 2^15 buckets writes 4-16 B at a time to tens of millions of open write fronts;
-// rocprofv3 WRITE_SIZE showed 5.7x the algorithmic bytes reaching HBM (profiles/r01b_traffic.json).
-// Instead a workgroup stages PART_ROUND tuples per round in LDS, counting-sorts them by bucket there and
-// writes every bucket's run with consecutive lanes on consecutive addresses.  <= 1024 buckets per pass keep
-// the runs long; 2^15 buckets are reached in two passes (256 coarse x 128 fine), the second pass working
-// one coarse bucket (a few MB, cache resident) at a time.  Placement inside a bucket is arbitrary
-// (per-round global cursor bump): every per-k-mer reduction downstream is order-free.
-// ----------------------------------------------------------------------------------------------
-#define PART_THREADS 1024
-#define PART_LDS_BYTES 131072
-#define PART_MAXB 1024
-#define PART_SLICES 8u              // workgroups per coarse bucket in the second pass (k_seg_hist_g, k_part_tuples_g)
-
-// exclusive scan of cnt[0..n) (n <= 1024) into base[0..n], base[n] = total; all PART_THREADS threads call it.
-// Two counts per thread, DPP prefix sums inside the waves, one wave for the wave totals: three barriers instead of twenty.
-__device__ inline void part_scan(const u32* cnt, u32* base, u32* tmp, u32 n) {
-	const u32 t = threadIdx.x, lane = t & 63, wv = t >> 6;
-	const u32 a = 2 * t < n ? cnt[2 * t] : 0, b = 2 * t + 1 < n ? cnt[2 * t + 1] : 0;
-	const u32 incl = (u32) vdjx_wave_scan_add((int) (a + b));
-	if (lane == 63) tmp[wv] = incl;
-	__syncthreads();
-	if (wv == 0) {
-		const u32 w = lane < PART_THREADS / 64 ? tmp[lane] : 0;
-		const u32 wi = (u32) vdjx_wave_scan_add((int) w);
-		if (lane < PART_THREADS / 64) tmp[lane] = wi - w;          // exclusive offset of every wave
-		if (lane == 63) tmp[PART_THREADS / 64] = wi;               // grand total
-	}
-	__syncthreads();
-	const u32 excl = tmp[wv] + incl - (a + b);
-	if (2 * t < n) base[2 * t] = excl;
-	if (2 * t + 1 < n) base[2 * t + 1] = excl + a;
-	if (t == 0) base[n] = tmp[PART_THREADS / 64];
-	__syncthreads();
-}
-
 // out[i] = src[i*step]
 __global__ void k_pick_u32(const u32* __restrict__ src, u32 step, u32 n, u32* __restrict__ out) {
 	const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i < n) out[i] = src[(size_t) i * step];
 }
-
-// cursors of a partition pass: cur[i] = bucket_start[i << sh]
-__global__ void k_init_cursors(const u32* __restrict__ bucket_start, u32 n, u32 sh, u32* __restrict__ cur) {
-	u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i < n) cur[i] = bucket_start[(size_t) i << sh];
-}
-
 
 // ----------------------------------------------------------------------------------------------
 // K3a: LDS hash aggregation per bucket
@@ -309,7 +267,14 @@ __global__ __launch_bounds__(HIST_THREADS) void k_gated_hist(const u64* __restri
 	for (u32 i = threadIdx.x; i < NB; i += HIST_THREADS) if (hist[i]) atomicAdd(&bucket_cnt[i], hist[i]);
 }
 
-// K2c' pass 1: records -> gated tuples, LDS-staged counting sort into `nbk` coarse buckets (see K2c above).
+// the bucket of a tuple in a pass of the cut: `mask + 1` buckets from the hash bits above `shift`
+template <typename TUP> struct TupBucket {
+	u32 shift, mask;
+	__device__ inline u32 operator()(const TUP& t) const { return (u32) (vdjx_bucket_mix(t.lo, t.hi()) >> shift) & mask; }
+};
+
+// K2c' pass 1: records -> gated tuples, LDS-staged counting sort into `nbk` coarse buckets (a round of vdjx_part.h: the counting
+// and the placement are this kernel's, the rest is part_round's).
 // A round takes `rr0` records (the host sizes it from the gated fraction the histogram measured, so that the stage fills: with one
 // instance in six gated, rounds sized for the worst case spend their time in barriers); a round whose tuples do not fit is
 // simply retried with half the records.  The gated instances of a round are listed once (dense, see above) as descriptors
@@ -323,7 +288,7 @@ __global__ __launch_bounds__(PART_THREADS) void k_part_records_g(const u64* __re
 	extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
 	TUP* stage = (TUP*) smem;                                         // (the waves' instance lists live here while the round is counted)
 	u32* desc = (u32*) (smem + PARTR_STAGE_BYTES);
-	__shared__ u32 cnt[PART_MAXB], base[PART_MAXB + 1], cur[PART_MAXB], gbase[PART_MAXB], tmp[PART_THREADS];
+	__shared__ part_round pr;
 	__shared__ u32 s_n;
 	constexpr u32 ROUND = PARTR_STAGE_BYTES / sizeof(TUP);
 	constexpr int OB = LONG ? 8 : 6;                                  // offset bits (descriptor: record in the round << (OB + 10) | offset << 10 | bucket)
@@ -342,9 +307,8 @@ __global__ __launch_bounds__(PART_THREADS) void k_part_records_g(const u64* __re
 	size_t rs = r0;
 	while (rs < r1) {
 		const size_t re = rs + rr < r1 ? rs + rr : r1;
-		for (u32 i = threadIdx.x; i < nbk; i += PART_THREADS) cnt[i] = 0;
 		if (threadIdx.x == 0) s_n = 0;
-		__syncthreads();
+		pr.begin(nbk);
 		for (size_t rb = rs; rb < re; rb += PART_THREADS) {
 			const size_t r = rb + threadIdx.x;
 			u64 G = 0;
@@ -381,7 +345,7 @@ __global__ __launch_bounds__(PART_THREADS) void k_part_records_g(const u64* __re
 						vdjx_kmer_at_lane(bb.x, bb.y, rl, k, (int) (e & 63u), khi, klo);
 					}
 					const u32 b = (u32) (vdjx_bucket_mix(klo, khi) >> shift) & mask;
-					atomicAdd(&cnt[b], 1u);
+					pr.count(b);
 					if (dbase + i < ROUND) desc[dbase + i] = ((loc0 + (e >> OB)) << (OB + 10)) | ((e & ((1u << OB) - 1u)) << 10) | b;
 				}
 				vdjx_wave_lds_fence();
@@ -393,13 +357,7 @@ __global__ __launch_bounds__(PART_THREADS) void k_part_records_g(const u64* __re
 			__syncthreads();
 			continue;
 		}
-		part_scan(cnt, base, tmp, nbk);
-		for (u32 i = threadIdx.x; i < nbk; i += PART_THREADS) {
-			cur[i] = base[i];
-			gbase[i] = cnt[i] ? atomicAdd(&gcur[i], cnt[i]) : 0u;
-		}
-		__syncthreads();
-		const u32 n = base[nbk];
+		const u32 n = pr.reserve(nbk, gcur);
 		for (u32 i = threadIdx.x; i < n; i += PART_THREADS) {
 			const u32 d = desc[i];
 			const size_t r = rs + (d >> (OB + 10));
@@ -415,73 +373,15 @@ __global__ __launch_bounds__(PART_THREADS) void k_part_records_g(const u64* __re
 				const ulonglong2 bb = ((const ulonglong2*) bases)[r];
 				vdjx_kmer_at_lane(bb.x, bb.y, rl, k, (int) o, khi, klo);
 			}
-			TUP::store(&stage[atomicAdd(&cur[d & 1023u], 1u)], TUP::make(klo, khi, inst));
+			TUP::store(&stage[pr.slot(d & 1023u)], TUP::make(klo, khi, inst));
 		}
 		__syncthreads();
-		for (u32 i = threadIdx.x; i < n; i += PART_THREADS) {
-			const TUP t = TUP::load(&stage[i]);
-			const u32 b = (u32) (vdjx_bucket_mix(t.lo, t.hi()) >> shift) & mask;
-			TUP::store(&out[gbase[b] + (i - base[b])], t);
-		}
-		__syncthreads();
+		pr.flush(stage, n, out, TupBucket<TUP>{shift, mask});
 		rs = re;
 	}
 }
 
-// pass 2 (see k_part_tuples)
-template <typename TUP>
-__global__ __launch_bounds__(PART_THREADS) void k_part_tuples_g(const TUP* __restrict__ in, const u32* __restrict__ seg_start,
-                                                                u32 seg_shift, u32 slices, u32 shift, u32 sub_bits,
-                                                                u32* __restrict__ gcur, TUP* __restrict__ out) {
-	extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-	TUP* stage = (TUP*) smem;
-	__shared__ u32 cnt[PART_MAXB], base[PART_MAXB + 1], cur[PART_MAXB], gbase[PART_MAXB], tmp[PART_THREADS];
-	constexpr u32 PER = PART_LDS_BYTES / sizeof(TUP) / PART_THREADS;
-	constexpr u32 ROUND = PER * PART_THREADS;
-	const u32 seg = blockIdx.x / slices, sl = blockIdx.x % slices;
-	const u32 nbk = 1u << sub_bits, mask = nbk - 1;
-	const size_t s0 = seg_start[(size_t) seg << seg_shift], s1 = seg_start[((size_t) seg + 1) << seg_shift];
-	const size_t per = (s1 - s0 + slices - 1) / slices;
-	const size_t t0 = s0 + (size_t) sl * per;
-	const size_t t1 = t0 + per < s1 ? t0 + per : s1;
-	u32* gc = gcur + ((size_t) seg << sub_bits);
-	for (size_t ts = t0; ts < t1; ts += ROUND) {
-		const size_t te = ts + ROUND < t1 ? ts + ROUND : t1;
-		for (u32 i = threadIdx.x; i < nbk; i += PART_THREADS) cnt[i] = 0;
-		__syncthreads();
-		TUP r_t[PER];
-		u32 r_b[PER];
-#pragma unroll
-		for (u32 j = 0; j < PER; j++) {
-			const size_t t = ts + (size_t) j * PART_THREADS + threadIdx.x;
-			r_b[j] = NONE32;
-			if (t < te) {
-				r_t[j] = TUP::load(&in[t]);
-				r_b[j] = (u32) (vdjx_bucket_mix(r_t[j].lo, r_t[j].hi()) >> shift) & mask;
-			}
-		}
-#pragma unroll
-		for (u32 j = 0; j < PER; j++) if (r_b[j] != NONE32) atomicAdd(&cnt[r_b[j]], 1u);
-		__syncthreads();
-		part_scan(cnt, base, tmp, nbk);
-		for (u32 i = threadIdx.x; i < nbk; i += PART_THREADS) {
-			cur[i] = base[i];
-			gbase[i] = cnt[i] ? atomicAdd(&gc[i], cnt[i]) : 0u;
-		}
-		__syncthreads();
-#pragma unroll
-		for (u32 j = 0; j < PER; j++) if (r_b[j] != NONE32) stage[atomicAdd(&cur[r_b[j]], 1u)] = r_t[j];
-		__syncthreads();
-		const u32 n = base[nbk];
-		for (u32 i = threadIdx.x; i < n; i += PART_THREADS) {
-			const TUP x = stage[i];
-			const u32 b = (u32) (vdjx_bucket_mix(x.lo, x.hi()) >> shift) & mask;
-			TUP::store(&out[gbase[b] + (i - base[b])], x);
-		}
-		__syncthreads();
-	}
-}
-
+// the fine buckets' sizes where the second pass cuts more buckets than the histogram counted: the slices of the pass itself (part_slice)
 template <typename TUP>
 __global__ __launch_bounds__(512) void k_seg_hist_g(const TUP* __restrict__ in, const u32* __restrict__ seg_start, u32 seg_shift, u32 slices,
                                                     u32 shift, u32 sub_bits, u32* __restrict__ fine_cnt) {
@@ -489,11 +389,8 @@ __global__ __launch_bounds__(512) void k_seg_hist_g(const TUP* __restrict__ in, 
 	const u32 nbk = 1u << sub_bits;
 	for (u32 i = threadIdx.x; i < nbk; i += 512) h[i] = 0;
 	__syncthreads();
-	const u32 seg = blockIdx.x / slices, sl = blockIdx.x % slices;
-	const size_t s0 = seg_start[(size_t) seg << seg_shift], s1 = seg_start[((size_t) seg + 1) << seg_shift];
-	const size_t per = (s1 - s0 + slices - 1) / slices;
-	const size_t t0 = s0 + (size_t) sl * per;
-	const size_t t1 = t0 + per < s1 ? t0 + per : s1;
+	size_t t0, t1;
+	const u32 seg = part_slice(seg_start, seg_shift, slices, t0, t1);
 	for (size_t t = t0 + threadIdx.x; t < t1; t += 512) {
 		const TUP x = TUP::load(&in[t]);
 		atomicAdd(&h[(u32) (vdjx_bucket_mix(x.lo, x.hi()) >> shift) & (nbk - 1)], 1u);
@@ -2027,105 +1924,15 @@ __global__ __launch_bounds__(WALK_THREADS) void k_walk_items(const u64* __restri
 	for (u32 i = threadIdx.x; i < n_ranges; i += WALK_THREADS) if (hist[i]) atomicAdd(&range_cnt[i], hist[i]);
 }
 
-// items -> items grouped by survivor range (see k_part_tuples); holes are dropped.  `n_raw` is read from the device cursor.
-__global__ __launch_bounds__(PART_THREADS) void k_part_items(const u64* __restrict__ in, const unsigned long long* __restrict__ n_raw, ItemFmt f,
-                                                             u32 range_shift, u32 nbk, u32* __restrict__ gcur, u64* __restrict__ out) {
-	extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-	u64* stage = (u64*) smem;
-	__shared__ u32 cnt[PART_MAXB], base[PART_MAXB + 1], cur[PART_MAXB], gbase[PART_MAXB], tmp[PART_THREADS];
-	constexpr u32 PER = PART_LDS_BYTES / 8 / PART_THREADS;          // 16 items per thread per round
-	constexpr u32 ROUND = PER * PART_THREADS;
-	const size_t N = (size_t) *n_raw;
-	const size_t per = ((N + gridDim.x - 1) / gridDim.x + ROUND - 1) / ROUND * ROUND;
-	const size_t t0 = (size_t) blockIdx.x * per;
-	const size_t t1 = t0 + per < N ? t0 + per : N;
-	for (size_t ts = t0; ts < t1; ts += ROUND) {
-		const size_t te = ts + ROUND < t1 ? ts + ROUND : t1;
-		for (u32 i = threadIdx.x; i < nbk; i += PART_THREADS) cnt[i] = 0;
-		__syncthreads();
-		u64 r_it[PER];
-		u32 r_b[PER];
-#pragma unroll
-		for (u32 j = 0; j < PER; j += 2) {                            // 16-byte loads
-			const size_t t = ts + ((size_t) (j / 2) * PART_THREADS + threadIdx.x) * 2;
-			r_it[j] = IT_HOLE; r_it[j + 1] = IT_HOLE;
-			if (t + 1 < te) { const ulonglong2 v = *(const ulonglong2*) &in[t]; r_it[j] = v.x; r_it[j + 1] = v.y; }
-			else if (t < te) r_it[j] = in[t];
-		}
-#pragma unroll
-		for (u32 j = 0; j < PER; j++) {
-			r_b[j] = NONE32;
-			if (r_it[j] != IT_HOLE) { r_b[j] = it_scat(f, it_surv(f, r_it[j])) >> range_shift; atomicAdd(&cnt[r_b[j]], 1u); }
-		}
-		__syncthreads();
-		part_scan(cnt, base, tmp, nbk);
-		for (u32 i = threadIdx.x; i < nbk; i += PART_THREADS) {
-			cur[i] = base[i];
-			gbase[i] = cnt[i] ? atomicAdd(&gcur[i], cnt[i]) : 0u;
-		}
-		__syncthreads();
-#pragma unroll
-		for (u32 j = 0; j < PER; j++) if (r_b[j] != NONE32) stage[atomicAdd(&cur[r_b[j]], 1u)] = r_it[j];
-		__syncthreads();
-		const u32 n = base[nbk];
-		for (u32 i = threadIdx.x; i < n; i += PART_THREADS) {
-			const u64 x = stage[i];
-			const u32 b = it_scat(f, it_surv(f, x)) >> range_shift;
-			out[gbase[b] + (i - base[b])] = x;
-		}
-		__syncthreads();
-	}
-}
-
-// second level (more than 1024 survivor ranges): segment `seg` of the level-1 output is split over `slices` workgroups and cut
-// into 2^sub_bits ranges
-__global__ __launch_bounds__(PART_THREADS) void k_part_items2(const u64* __restrict__ in, const u32* __restrict__ seg_start, u32 seg_shift, u32 slices, ItemFmt f,
-                                                              u32 range_shift, u32 sub_bits, u32* __restrict__ gcur, u64* __restrict__ out) {
-	extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-	u64* stage = (u64*) smem;
-	__shared__ u32 cnt[PART_MAXB], base[PART_MAXB + 1], cur[PART_MAXB], gbase[PART_MAXB], tmp[PART_THREADS];
-	constexpr u32 PER = PART_LDS_BYTES / 8 / PART_THREADS;
-	constexpr u32 ROUND = PER * PART_THREADS;
-	const u32 seg = blockIdx.x / slices, sl = blockIdx.x % slices;
-	const u32 nbk = 1u << sub_bits, mask = nbk - 1;
-	const size_t s0 = seg_start[(size_t) seg << seg_shift], s1 = seg_start[((size_t) seg + 1) << seg_shift];
-	const size_t per = (s1 - s0 + slices - 1) / slices;
-	const size_t t0 = s0 + (size_t) sl * per;
-	const size_t t1 = t0 + per < s1 ? t0 + per : s1;
-	u32* gc = gcur + ((size_t) seg << sub_bits);
-	for (size_t ts = t0; ts < t1; ts += ROUND) {
-		const size_t te = ts + ROUND < t1 ? ts + ROUND : t1;
-		for (u32 i = threadIdx.x; i < nbk; i += PART_THREADS) cnt[i] = 0;
-		__syncthreads();
-		u64 r_it[PER];
-		u32 r_b[PER];
-#pragma unroll
-		for (u32 j = 0; j < PER; j++) {
-			const size_t t = ts + (size_t) j * PART_THREADS + threadIdx.x;
-			r_b[j] = NONE32;
-			if (t < te) { r_it[j] = in[t]; r_b[j] = (it_scat(f, it_surv(f, r_it[j])) >> range_shift) & mask; }
-		}
-#pragma unroll
-		for (u32 j = 0; j < PER; j++) if (r_b[j] != NONE32) atomicAdd(&cnt[r_b[j]], 1u);
-		__syncthreads();
-		part_scan(cnt, base, tmp, nbk);
-		for (u32 i = threadIdx.x; i < nbk; i += PART_THREADS) {
-			cur[i] = base[i];
-			gbase[i] = cnt[i] ? atomicAdd(&gc[i], cnt[i]) : 0u;
-		}
-		__syncthreads();
-#pragma unroll
-		for (u32 j = 0; j < PER; j++) if (r_b[j] != NONE32) stage[atomicAdd(&cur[r_b[j]], 1u)] = r_it[j];
-		__syncthreads();
-		const u32 n = base[nbk];
-		for (u32 i = threadIdx.x; i < n; i += PART_THREADS) {
-			const u64 x = stage[i];
-			const u32 b = (it_scat(f, it_surv(f, x)) >> range_shift) & mask;
-			out[gbase[b] + (i - base[b])] = x;
-		}
-		__syncthreads();
-	}
-}
+// the bucket of an item in a pass of vdjx_part.h: its survivor range (ranges of 2^range_shift scattered positions), masked to the
+// ranges of a coarse segment in the second level (more than 1,024 ranges).  The first level reads the raw items of the walk, two per
+// load, and drops the holes.
+static_assert(IT_HOLE == PART_HOLE, "the holes of the walk's blocks are what the partition drops");
+struct ItemRange {
+	ItemFmt f;
+	u32 range_shift, mask;
+	__device__ inline u32 operator()(u64 x) const { return (it_scat(f, it_surv(f, x)) >> range_shift) & mask; }
+};
 
 // ---- the recount ------------------------------------------------------------------------------
 // One workgroup per range of SB scattered positions (SB/16 blocks of survivors).  A run [a, e] inside a block (positions in the
@@ -2575,10 +2382,6 @@ int stage_gated_cut(vdjx_ctx* c, A& db, const vdjx_pool* pool, u64 rec_base, int
 	HIP_TRY(db.alloc(&out->t, (size_t) N + 1));
 	constexpr u32 stage_tuples = PARTR_STAGE_BYTES / (u32) sizeof(TUP);
 	constexpr u32 lds_partr = PARTR_STAGE_BYTES + stage_tuples * 4;
-	HIP_TRY(hipFuncSetAttribute((const void*) k_part_records_g<TUP, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_partr));
-	HIP_TRY(hipFuncSetAttribute((const void*) k_part_records_g<TUP, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_partr));
-	HIP_TRY(hipFuncSetAttribute((const void*) k_part_records_g<TUP, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_partr));
-	HIP_TRY(hipFuncSetAttribute((const void*) k_part_tuples_g<TUP>, hipFuncAttributeMaxDynamicSharedMemorySize, PART_LDS_BYTES));
 	// pass geometry: <= 1024 buckets in one pass; otherwise 256 coarse x the rest (large pools: 2^(Tt-10) coarse x 1024)
 	u32 cbits = Tt, fbits = 0;
 	if (Tt > 10) { cbits = extra ? Tt - 10 : 8; fbits = Tt - cbits; }
@@ -2592,17 +2395,13 @@ int stage_gated_cut(vdjx_ctx* c, A& db, const vdjx_pool* pool, u64 rec_base, int
 	if (fbits) HIP_TRY(db.alloc(&l1, (size_t) N + 1));
 	{
 		vdjx_prof_scope ps(c, "k_part_records");
-		hipLaunchKernelGGL(k_init_cursors, dim3((NBc + 255) / 256), dim3(256), 0, st, hstart, NBc, HB - cbits, gcur);
 		// records per round: three quarters of the stage at the measured gated fraction, in whole sweeps of the workgroup
 		const u64 NIl = (u64) R * (u64) P;
 		u64 rr = N ? (u64) stage_tuples * 3 / 4 * NIl / ((u64) N * (u64) P) : 1u << 16;
 		rr = std::max<u64>(PART_THREADS, std::min<u64>(rr / PART_THREADS * PART_THREADS, lng ? 1u << 14 : 1u << 16));      // (the descriptor's record field)
-		if (lng) hipLaunchKernelGGL((k_part_records_g<TUP, true>), dim3(nblk2), dim3(PART_THREADS), lds_partr, st, pool->d_bases, pool->d_nmask, pool->d_lowq, R, rec_base,
-		                            pool->rl, k, 64 - cbits, NBc, rpb, (u32) rr, gcur, l1);
-		else if (sym) hipLaunchKernelGGL((k_part_records_g<TUP, false, true>), dim3(nblk2), dim3(PART_THREADS), lds_partr, st, pool->d_bases, pool->d_nmask, pool->d_lowq, R, rec_base,
-		                                 pool->rl, k, 64 - cbits, NBc, rpb, (u32) rr, gcur, l1);
-		else hipLaunchKernelGGL((k_part_records_g<TUP, false>), dim3(nblk2), dim3(PART_THREADS), lds_partr, st, pool->d_bases, pool->d_nmask, pool->d_lowq, R, rec_base,
-		                        pool->rl, k, 64 - cbits, NBc, rpb, (u32) rr, gcur, l1);
+		auto* part_records = lng ? k_part_records_g<TUP, true> : sym ? k_part_records_g<TUP, false, true> : k_part_records_g<TUP, false>;
+		HIP_TRY(part_launch(st, part_records, nblk2, lds_partr, hstart, NBc, HB - cbits, gcur, l1, pool->d_bases, pool->d_nmask, pool->d_lowq, R, rec_base,
+		                    pool->rl, k, 64 - cbits, NBc, rpb, (u32) rr));
 	}
 	dbg_sync(c, "k_part_records");
 	u32* tstart;                                   // starts of the final buckets
@@ -2624,9 +2423,8 @@ int stage_gated_cut(vdjx_ctx* c, A& db, const vdjx_pool* pool, u64 rec_base, int
 		u32* gcur2;
 		HIP_TRY(db.alloc(&gcur2, NBt));
 		vdjx_prof_scope ps(c, "k_part_tuples");
-		hipLaunchKernelGGL(k_init_cursors, dim3((NBt + 255) / 256), dim3(256), 0, st, tstart, NBt, 0u, gcur2);
-		hipLaunchKernelGGL(k_part_tuples_g<TUP>, dim3(NBc * slices), dim3(PART_THREADS), PART_LDS_BYTES, st, l1, hstart, HB - cbits, slices, 64 - Tt, fbits,
-		                   gcur2, out->t);
+		HIP_TRY(part_launch(st, k_part<TUP, TupBucket<TUP>, part_segs>, NBc * slices, PART_LDS_BYTES, tstart, NBt, 0u, gcur2, out->t,
+		                    l1, part_segs{hstart, HB - cbits, slices, fbits}, TupBucket<TUP>{64 - Tt, (1u << fbits) - 1u}));
 	}
 	return VDJX_OK;
 }
@@ -2935,27 +2733,26 @@ int stage_recount(vdjx_ctx* c, A& db, const vdjx_pool* pool, u64 rec_base, int k
 		items_cap = (size_t) hp[0] + 1;
 	}
 	HIP_TRY(db.alloc(&items, items_cap));
-	HIP_TRY(hipFuncSetAttribute((const void*) k_part_items, hipFuncAttributeMaxDynamicSharedMemorySize, PART_LDS_BYTES));
 	HIP_TRY(db.alloc(&gcur, n_ranges_p));
 	{
 		vdjx_prof_scope ps(c, "k_part_items");
 		u32 npb = (u32) std::min<size_t>(1024, (NI / 4 + 65535) / 65536);
 		if (npb == 0) npb = 1;
+		const auto k_part_items = k_part<u64, ItemRange, part_share, true>;           // the raw items: two per load, holes dropped
 		if (!l2bits) {
-			hipLaunchKernelGGL(k_init_cursors, dim3((n_ranges_p + 255) / 256), dim3(256), 0, st, range_start, n_ranges_p, 0u, gcur);
-			hipLaunchKernelGGL(k_part_items, dim3(npb), dim3(PART_THREADS), PART_LDS_BYTES, st, raw, g_cursor, f, range_shift, n_ranges_p, gcur, items);
+			HIP_TRY(part_launch(st, k_part_items, npb, PART_LDS_BYTES, range_start, n_ranges_p, 0u, gcur, items, raw, part_share{g_cursor, n_ranges_p},
+			                    ItemRange{f, range_shift, ~0u}));
 		} else {
 			// level 1 into `n_coarse` segments (written over a second buffer), level 2 inside each segment
 			u64* l1;
 			u32* gcur1;
 			HIP_TRY(db.alloc(&l1, items_cap));
 			HIP_TRY(db.alloc(&gcur1, n_coarse));
-			HIP_TRY(hipFuncSetAttribute((const void*) k_part_items2, hipFuncAttributeMaxDynamicSharedMemorySize, PART_LDS_BYTES));
-			hipLaunchKernelGGL(k_init_cursors, dim3((n_coarse + 255) / 256), dim3(256), 0, st, range_start, n_coarse, l2bits, gcur1);
-			hipLaunchKernelGGL(k_part_items, dim3(npb), dim3(PART_THREADS), PART_LDS_BYTES, st, raw, g_cursor, f, range_shift + l2bits, n_coarse, gcur1, l1);
-			hipLaunchKernelGGL(k_init_cursors, dim3((n_ranges_p + 255) / 256), dim3(256), 0, st, range_start, n_ranges_p, 0u, gcur);
+			HIP_TRY(part_launch(st, k_part_items, npb, PART_LDS_BYTES, range_start, n_coarse, l2bits, gcur1, l1, raw, part_share{g_cursor, n_coarse},
+			                    ItemRange{f, range_shift + l2bits, ~0u}));
 			const u32 sl2 = std::max(8u, std::min(64u, 2048u / n_coarse));          // workgroups per coarse segment
-			hipLaunchKernelGGL(k_part_items2, dim3(n_coarse * sl2), dim3(PART_THREADS), PART_LDS_BYTES, st, l1, range_start, l2bits, sl2, f, range_shift, l2bits, gcur, items);
+			HIP_TRY(part_launch(st, k_part<u64, ItemRange, part_segs>, n_coarse * sl2, PART_LDS_BYTES, range_start, n_ranges_p, 0u, gcur, items,
+			                    l1, part_segs{range_start, l2bits, sl2, l2bits}, ItemRange{f, range_shift, (1u << l2bits) - 1u}));
 		}
 	}
 	dbg_sync(c, "k_part_items");
@@ -3849,3 +3646,75 @@ extern "C" void vdjx_graph_free(vdjx_graph* g) {
 	delete g;
 }
 
+// ---- the partition pass on its own, for the test suite (include/vdjx.h) ----------------------------------------------------------
+// k_part and part_launch as the build uses them; the bucket of an element is bits 40..63 of its first word, cut as the build's keys are:
+// the bits above `shift` in the first of two levels, the bits of `mask` in the second
+struct PartTestKey {
+	u32 shift, mask;
+	__device__ inline u32 operator()(u64 x) const { return ((u32) (x >> 40) >> shift) & mask; }
+	__device__ inline u32 operator()(const Tup16& t) const { return (*this)(t.lo); }
+};
+
+template <typename T, bool PAIRED>
+static int part_test(vdjx_ctx* c, const void* host_in, size_t n, const std::vector<u32>& cnt, int levels, u32 fine_bits, u32 slices, u32 workgroups,
+                     u32* host_starts, void* host_out) {
+	hipStream_t st = c->stream;
+	vdjx_work db(c);
+	const u32 nb = (u32) cnt.size(), coarse = nb >> fine_bits;
+	const unsigned long long n_raw = n;
+	T *d_in, *d_l1, *d_out;
+	u32 *d_cnt, *d_starts, *gcur, *gcur1;
+	unsigned long long* d_n;
+	HIP_TRY(db.alloc(&d_in, n + 1));
+	HIP_TRY(db.alloc(&d_l1, n + 1));
+	HIP_TRY(db.alloc(&d_out, n + 1));
+	HIP_TRY(db.alloc(&d_cnt, nb));
+	HIP_TRY(db.alloc(&d_starts, nb + 1));
+	HIP_TRY(db.alloc(&gcur, nb));
+	HIP_TRY(db.alloc(&gcur1, coarse));
+	HIP_TRY(db.alloc(&d_n, 1));
+	if (n) HIP_TRY(hipMemcpyAsync(d_in, host_in, n * sizeof(T), hipMemcpyHostToDevice, st));
+	HIP_TRY(hipMemcpyAsync(d_cnt, cnt.data(), (size_t) nb * 4, hipMemcpyHostToDevice, st));
+	HIP_TRY(hipMemcpyAsync(d_n, &n_raw, 8, hipMemcpyHostToDevice, st));
+	vdjx_scan_one(st, (const u32*) d_cnt, nb, d_starts);
+	const auto level1 = k_part<T, PartTestKey, part_share, PAIRED>;
+	if (levels == 1) {
+		HIP_TRY(part_launch(st, level1, workgroups, PART_LDS_BYTES, d_starts, nb, 0u, gcur, d_out, d_in, part_share{d_n, nb}, PartTestKey{0u, ~0u}));
+	} else {
+		HIP_TRY(part_launch(st, level1, workgroups, PART_LDS_BYTES, d_starts, coarse, fine_bits, gcur1, d_l1, d_in, part_share{d_n, coarse},
+		                    PartTestKey{fine_bits, ~0u}));
+		HIP_TRY(part_launch(st, k_part<T, PartTestKey, part_segs>, coarse * slices, PART_LDS_BYTES, d_starts, nb, 0u, gcur, d_out, d_l1,
+		                    part_segs{d_starts, fine_bits, slices, fine_bits}, PartTestKey{0u, (1u << fine_bits) - 1u}));
+	}
+	const size_t kept = std::accumulate(cnt.begin(), cnt.end(), (size_t) 0);
+	HIP_TRY(hipMemcpyAsync(host_starts, d_starts, ((size_t) nb + 1) * 4, hipMemcpyDeviceToHost, st));
+	if (kept) HIP_TRY(hipMemcpyAsync(host_out, d_out, kept * sizeof(T), hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipStreamSynchronize(st));
+	HIP_TRY(hipGetLastError());
+	return VDJX_OK;
+}
+
+extern "C" int vdjx_part_u64(vdjx_ctx* c, const void* host_in, size_t n, int elem_bytes, uint32_t nb, int levels, uint32_t fine_bits, uint32_t slices,
+                             uint32_t workgroups, uint32_t* host_starts, void* host_out) {
+	const auto refuse = [](const char* what) { vdjx_set_error("vdjx_part_u64: %s", what); return VDJX_EINVAL; };
+	if (!c || !host_starts || (n && (!host_in || !host_out)) || n >= (1ull << 31)) return refuse("bad argument");
+	if (elem_bytes != 8 && elem_bytes != 16) return refuse("elements of 8 or 16 bytes");
+	if (levels != 1 && levels != 2) return refuse("one level or two");
+	if (slices == 0 || slices > 1024 || workgroups == 0 || workgroups > 65536) return refuse("1 .. 1024 slices, 1 .. 65536 workgroups");
+	if (levels == 1) fine_bits = 0;
+	if (fine_bits > 10) return refuse("at most 10 fine bits");
+	if (nb == 0 || (nb >> fine_bits) > PART_MAXB || (nb >> fine_bits) << fine_bits != nb) return refuse("nb is at most 1024, or coarse << fine_bits with coarse <= 1024");
+	// the histogram, on the host: an 8-byte element of all ones is a hole and is counted nowhere
+	std::vector<u32> cnt(nb, 0u);
+	const u64* w = (const u64*) host_in;
+	for (size_t i = 0; i < n; i++) {
+		const u64 x = w[i * (size_t) (elem_bytes / 8)];
+		if (elem_bytes == 8 && x == PART_HOLE) continue;
+		if ((x >> 40) >= nb) return refuse("the bucket of an element is not below nb");
+		cnt[(size_t) (x >> 40)]++;
+	}
+	HIP_TRY(hipSetDevice(c->device));
+	vdjx_clear_errors();
+	if (elem_bytes == 8) return part_test<u64, true>(c, host_in, n, cnt, levels, fine_bits, slices, workgroups, host_starts, host_out);
+	return part_test<Tup16, false>(c, host_in, n, cnt, levels, fine_bits, slices, workgroups, host_starts, host_out);
+}

@@ -234,6 +234,22 @@ def test_cli_rejects_bad_input(tmp_path):
     assert r.returncode != 0 and "Invalid chain" in r.stderr
 
 
+@pytest.mark.parametrize("vk", ["1", "17"])
+def test_cli_rejects_vk_outside_the_library_range(vk, tmp_path):
+    """--vk goes straight to vdjx_vregion_load, which takes 2 to 16: the command line says so itself and stops before it reads its
+    input (no read length line, no stage mark), let alone loads a pool"""
+    from vdjer_amd import synth
+    exe = os.path.join(ROOT, "vdjer_amd", "vdjer")
+    rep = synth.make_repertoire(2, seed=3)
+    synth.make_reads(rep, 20, noise_frac=0.3, seed=4, clean=True).write_reads_file(os.path.join(tmp_path, "reads.txt"))
+    synth.write_ref_dir(rep, os.path.join(tmp_path, "ref"))
+    r = subprocess.run([exe, "--in", "reads.txt", "--chain", "IGH", "--ref-dir", "ref", "--ins", "175", "--vk", vk], cwd=tmp_path,
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120)
+    assert r.returncode != 0 and f"vregion k-mer size {vk} outside [2,16]" in r.stderr
+    assert "read length:" not in r.stderr and "ELAPSED_SECS" not in r.stderr and r.stdout == ""
+    assert not (tmp_path / "vdj_contigs.fa").exists()
+
+
 @pytest.mark.parametrize("tag", ["e2e_mixed"])
 def test_python_wiring_matches_reference(tag, tmp_path):
     from vdjer_amd import api, host

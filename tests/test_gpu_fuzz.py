@@ -228,6 +228,52 @@ def test_sharded_build_random_configurations_vs_single_gpu(ctx, seed, n):
                 assert np.array_equal(getattr(g, f), getattr(ref, f)), (cfg, f)
 
 
+@pytest.mark.parametrize("seed,n", [(501, 20)])
+def test_root_scorer_random_configurations_vs_oracle(ctx, seed, n):
+    """a-7 with k 3 ... 50 and vk 2 ... 16 at random (k <= vk among them: no seed can hit, everything is 0), one to four v-region lines
+    of 2k+1 (the shortest the scorer takes) to a few thousand characters, now and then with an N or a lower-case character, pure
+    ACGT queries (tests/root_queries.py) and three thresholds from -1 to k+1: verdicts against the oracle's score_seq
+    (seq_score.c:118-156).  With a small vk nearly every position of a line is a hit and the oracle runs a DP for each: the lines
+    are then kept short enough for a million or two cells per query."""
+    from oracle import oracle
+    from vdjer_amd import synth
+    from tests import root_queries as Q
+    rng = np.random.default_rng(seed + _SEED)
+    seen = {0: 0, 1: 0}
+    for it in range(n * _SCALE):
+        k = int(rng.integers(3, 51))
+        vk = int(rng.integers(2, 17))
+        if it % 5 == 4:                                     # (one in five on purpose at or below vk, one above by one)
+            k = max(3, vk - int(rng.integers(0, 3))) if it % 10 == 4 else min(50, vk + 1)
+        n_lines = int(rng.integers(1, 5))
+        vr = synth.make_repertoire(2, seed=int(rng.integers(0, 1 << 30))).v_region
+        cap = 3000 if vk > 6 else max(2 * k + 1, min(3000, 1_500_000 // (n_lines * 2 * k * k)))
+        lines = []
+        for _ in range(n_lines):
+            ln = 2 * k + 1 if rng.random() < 0.25 else int(rng.integers(2 * k + 1, cap + 1))
+            a = int(rng.integers(0, len(vr) - ln))
+            line = list(vr[a:a + ln])
+            if rng.random() < 0.3:
+                for p_ in rng.integers(0, ln, int(rng.integers(1, 5))):
+                    line[int(p_)] = "N" if rng.random() < 0.7 else line[int(p_)].lower()
+            lines.append("".join(line))
+        qs = Q.queries(rng, lines, k, 240)
+        thrs = [int(t) for t in rng.integers(-1, k + 2, 3)]
+        cfg = dict(it=it, k=k, vk=vk, line_lens=[len(l) for l in lines], n_queries=len(qs), thrs=thrs)
+        sc = oracle.RootScorer(lines, vk)
+        ctx.vregion_load(lines, vk)
+        for thr in thrs:
+            got = ctx.root_score(qs, k, thr).tolist()
+            want = [sc.score(q, thr) for q in qs]
+            bad = [i for i in range(len(qs)) if got[i] != want[i]]
+            assert not bad, (cfg, thr, [(qs[i], got[i], want[i]) for i in bad[:5]])
+            if k <= vk or thr > k:
+                assert not any(got), (cfg, thr)
+            seen[0] += got.count(0)
+            seen[1] += got.count(1)
+    assert seen[0] and seen[1], seen
+
+
 REF_BIN = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "vdjer_ref")
 
 
@@ -236,7 +282,7 @@ REF_BIN = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 def test_cli_end_to_end_random_pools_vs_the_compiled_reference(seed, n, tmp_path):
     """The whole command line against THE REFERENCE ITSELF (oracle/_ref/vdjer_ref: its own sources compiled where they lie, exactly
     how the goldens were made, tests/golden/make_golden.py) on pools drawn here: tiled clones (they pass the coverage test) or noisy
-    reads, k / mf / mq / mrs at random.  vdj_contigs.fa, the SAM on stdout and vdjer.dot byte for byte.  A run of the reference
+    reads, k / mf / mq / mrs / vk at random.  vdj_contigs.fa, the SAM on stdout and vdjer.dot byte for byte.  A run of the reference
     counts when it scored every root (its root threads race otherwise, as in make_golden.py).  Every pool also goes through
     `vdjer --gpus N` (N = 2..4 process-ranks on the one device): the sharded path from C against the reference's bytes."""
     import re
@@ -245,6 +291,7 @@ def test_cli_end_to_end_random_pools_vs_the_compiled_reference(seed, n, tmp_path
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     exe = os.path.join(root, "vdjer_amd", "vdjer")
     rng = np.random.default_rng(seed + _SEED)
+    rng_vk = np.random.default_rng([seed + _SEED, 1])      # (--vk from a stream of its own: every seed keeps the configurations it had)
     with_contigs = 0
     for it in range(n * _SCALE):
         n_clones = int(rng.integers(2, 7))
@@ -256,9 +303,10 @@ def test_cli_end_to_end_random_pools_vs_the_compiled_reference(seed, n, tmp_path
             pool = synth.make_reads(rep, int(rng.integers(3000, 9000)), noise_frac=float(rng.choice([0.1, 0.3])), seed=int(rng.integers(0, 1 << 30)))
         k = int(rng.choice([25, 31, 35]))
         flags = ["--k", str(k), "--mf", str(int(rng.integers(2, 4))), "--mq", str(int(rng.choice([60, 90]))), "--mrs", str(int(rng.choice([20, 30])))]
-        cfg = dict(it=it, chain=chain, clones=n_clones, pairs=pool.n_pairs, flags=flags)
         outs = {}
         gpus = int(rng.integers(2, 5))          # the same pool through `vdjer --gpus N` as well (N process-ranks sharing the one device: host transport)
+        flags += ["--vk", str(int(rng_vk.choice([11, 15, 15, 16])))]      # the v-region seed length (params.c:279), for both binaries; drawn last
+        cfg = dict(it=it, chain=chain, clones=n_clones, pairs=pool.n_pairs, flags=flags)
         for who, binary in (("ref", [REF_BIN, "run"]), ("hip", [exe]), ("hipN", [exe])):
             d = tmp_path / f"{it}_{who}"
             d.mkdir()

@@ -160,14 +160,21 @@ def test_hot_kmer_skew(ctx):
     assert int(hg.freq.max()) > 1000
 
 
-@pytest.mark.parametrize("tag", ["k35_t30", "k35_t25", "k35_t34", "k25_t20"])
+@pytest.mark.parametrize("tag", G.score_tags())
 def test_root_score_vs_reference_dump(ctx, tag):
-    c = G.Case("noisy")
-    info = G.manifest()["score"][tag]
-    ctx.vregion_load([c.v_region], 15)
-    rows = G.rows(f"score_{tag}.tsv.gz")
+    """the dump's own lines and vk (tests/golden/make_golden_score.py: k 17 ... 50 on both sides of the 64 reference characters one
+    register of k_root_dp_wave holds, vk 2 ... 16, k = vk + 1, one and three lines, N and lower case in the line): the verdicts
+    the compiled reference printed.  The vk 2 dumps hold 380,504 items (every position of the line is a hit), most of which go
+    to k_root_dp at k 50; the others stay below 32,768 and go to k_root_dp_wave unless an earlier call's guess was larger."""
+    lines, vk, info, rows = G.score_case(tag)
+    ctx.vregion_load(lines, vk)
     got = ctx.root_score([r[0] for r in rows], info["k"], info["thr"])
     assert got.tolist() == [int(r[1]) for r in rows]
+    if info["thr"] > 0:
+        items = ctx.stat("root_dp_items")
+        assert items > 0 and ctx.stat("root_dp_items_wave") + ctx.stat("root_dp_items_thread") == items
+        if vk == 2:
+            assert items == 380504 and ctx.stat("root_dp_items_thread") > 0
 
 
 def test_root_score_vs_oracle_multiline(ctx):
@@ -191,13 +198,89 @@ def test_root_score_vs_oracle_multiline(ctx):
         assert got.tolist() == [s.score(q, thr) for q in qs]
 
 
-@pytest.mark.parametrize("k,thr", [(35, 30), (25, 20), (35, 0)])
-def test_root_score_graph_on_device(ctx, k, thr):
-    """roots taken from the device-resident graph == roots of the exported graph pushed through vdjx_root_score == oracle"""
+def _both_kernels_case(k, vk, thr, n_pieces, seed):
+    """(lines, oracle scorer, Q, the oracle's verdicts): Q = pieces of the v-region, half of them as they are (a hit at every one of
+    the k - vk seed offsets), half with 0 .. k/4 substitutions, and one k-mer in twelve at random, which no line resembles"""
     from oracle import oracle
-    c = G.Case("noisy")
+    from vdjer_amd import synth
+    from tests import root_queries as RQ
+    rng = np.random.default_rng(seed)
+    lines = [synth.make_repertoire(5, seed=seed).v_region]
+    qs = RQ.pieces(rng, lines, k, n_pieces // 2, 0) + RQ.pieces(rng, lines, k, n_pieces // 2, k // 4) + RQ.random_kmers(rng, n_pieces // 12, k)
+    qs = [qs[int(i)] for i in rng.permutation(len(qs))]
+    sc = oracle.RootScorer(lines, vk)
+    want = [sc.score(q, thr) for q in qs]
+    assert 0 < sum(want) < len(want)                      # both verdicts
+    return lines, qs, want
+
+
+DP_WAVE_MAX = 32768          # vdjx_score.hip, root_score_device: calls of up to that many items go to k_root_dp_wave, larger ones to k_root_dp
+
+
+def _kernels(c):
+    return c.stat("root_dp_items"), c.stat("root_dp_items_wave"), c.stat("root_dp_items_thread")
+
+
+@pytest.mark.parametrize("k,vk,thr,n_pieces", [(35, 15, 30, 3400), (50, 8, 45, 1000), (20, 15, 15, 14000)])
+def test_root_scorer_both_dp_kernels_agree(k, vk, thr, n_pieces):
+    """The same roots through k_root_dp (one thread per item; a call of more than 32,768 items) and through k_root_dp_wave (one wave
+    per item; the call in quarters), told apart by vdjx_stat "root_dp_items_thread" / "root_dp_items_wave": verdicts equal to the
+    oracle's and to each other's.  k 35: one register of reference characters and six lanes of the second; k 50: thirty-six lanes
+    of the second; k 20: the first alone.  Contexts of their own, so that no earlier call's item count (root_dp_hint) decides the
+    launch.  k 35 also after a small call: the DP is then launched for the small call's count by the wave kernel and the remainder
+    follows from a non-zero base by the thread kernel -- and a small call after a large one (the guess beyond the call)."""
+    from vdjer_amd import api
+    lines, qs, want = _both_kernels_case(k, vk, thr, n_pieces, seed=7000 + k)
+    n = len(qs)
+    a = api.Context(0)                                    # whole: the thread kernel
+    a.vregion_load(lines, vk)
+    whole = a.root_score(qs, k, thr).tolist()
+    items, by_wave, by_thread = _kernels(a)
+    a.close()
+    assert DP_WAVE_MAX < items < 2 * DP_WAVE_MAX, items   # (a little above: every quarter stays below)
+    assert (by_wave, by_thread) == (0, items)
+    assert whole == want
+    b = api.Context(0)                                    # in quarters: the wave kernel
+    b.vregion_load(lines, vk)
+    parts, total = [], 0
+    for i in range(4):
+        parts += b.root_score(qs[i * n // 4:(i + 1) * n // 4], k, thr).tolist()
+        q_items, by_wave, by_thread = _kernels(b)
+        assert 0 < q_items <= DP_WAVE_MAX and (by_wave, by_thread) == (q_items, 0), (i, q_items, by_wave, by_thread)
+        total += q_items
+    b.close()
+    assert total == items
+    assert parts == whole
+    if k != 35:
+        return
+    c = api.Context(0)                                    # a small call, then Q: guessed launch (wave) + remainder from base > 0 (thread)
+    c.vregion_load(lines, vk)
+    small = c.root_score(qs[:40], k, thr).tolist()
+    s_items, by_wave, by_thread = _kernels(c)
+    assert small == want[:40] and 0 < s_items < 2000 and (by_wave, by_thread) == (s_items, 0)
+    again = c.root_score(qs, k, thr).tolist()
+    q_items, by_wave, by_thread = _kernels(c)
+    assert q_items == items and by_wave > 0 and by_thread > DP_WAVE_MAX and by_wave + by_thread == items, (by_wave, by_thread)
+    assert again == whole
+    small2 = c.root_score(qs[:40], k, thr).tolist()       # the guess (Q's count and a quarter) is beyond the call: the thread kernel, most of it idle
+    assert _kernels(c) == (s_items, 0, s_items)
+    assert small2 == small
+    c.close()
+
+
+_GRAPH_CASES = [pytest.param(35, 30, 15, id="35-30"), pytest.param(25, 20, 15, id="25-20"), pytest.param(35, 0, 15, id="35-0"),
+                (50, 40, 16), (50, 40, 8), (17, 12, 8), (17, 12, 16), (31, 25, 15), (31, 25, 8), (16, 12, 8), (15, 10, 16)]
+
+
+@pytest.mark.parametrize("k,thr,vk", _GRAPH_CASES)
+def test_root_score_graph_on_device(ctx, k, thr, vk):
+    """roots taken from the device-resident graph == roots of the exported graph pushed through vdjx_root_score == oracle.
+    k_root_gather copies a root with 16 lanes: k 16 (one character a lane), 17, 25, 31, 35, 50.  k 17 over vk 16: one seed offset;
+    k 15 over vk 16: no seed can hit, the ids are those of the roots all the same and every verdict is 0."""
+    from oracle import oracle
+    c = G.Case("noisy" if k < 50 else "e2e_rl100")          # (reads of 50 bases hold no 50-mer the build counts: the 100-base pool)
     ctx.anchor_sets_load(c.v_codes, c.j_codes)
-    ctx.vregion_load([c.v_region], 15)
+    ctx.vregion_load([c.v_region], vk)
     p = ctx.pool_load(c.pool.primary, c.pool.secondary, c.pool.rl)
     g = ctx.kmer_build(p, k, 3 if k == 35 else 2, 90 if k == 35 else 60, keep_device=True)
     p.free()
@@ -206,8 +289,10 @@ def test_root_score_graph_on_device(ctx, k, thr):
     ids, ok = ctx.root_score_graph(g, thr)
     assert ids.tolist() == want_ids.tolist()
     assert ok.tolist() == ctx.root_score(g.kmers[want_ids - 1], k, thr).tolist()
-    sc = oracle.RootScorer([c.v_region], 15)
+    sc = oracle.RootScorer([c.v_region], vk)
     assert ok.tolist() == [sc.score(g.kmer(int(i) - 1), thr) for i in ids]
+    if k <= vk:
+        assert not ok.any()
     # strided parts (what rank r of `world` ranks scores) tile the whole list
     parts = [ctx.root_score_graph(g, thr, r, 3) for r in range(3)]
     merged = np.zeros(g.n_roots, np.uint8)

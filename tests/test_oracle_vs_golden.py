@@ -60,16 +60,20 @@ def test_kmer_table_prune_graph(case, tag):
         assert list(g.from_ids[i, :g.from_deg[i]]) == fr
 
 
-@pytest.mark.parametrize("tag", ["k35_t30", "k35_t25", "k35_t34", "k25_t20"])
+@pytest.mark.parametrize("tag", G.score_tags())
 def test_root_scorer(tag):
-    c = G.Case("noisy")
-    info = G.manifest()["score"][tag]
-    s = oracle.RootScorer([c.v_region], 15)
-    rows = G.rows(f"score_{tag}.tsv.gz")
-    assert len(rows) == info["n"]
+    """the oracle, built with the dump's own lines and vk (make_golden_score.py: k 17 ... 50, vk 2 ... 16, one and three lines,
+    N and lower case in the line), against what the compiled reference printed"""
+    lines, vk, info, rows = G.score_case(tag)
+    s = oracle.RootScorer(lines, vk)
+    assert len(rows) == info["n"] and all(len(r[0]) == info["k"] for r in rows)
     got = [s.score(r[0], info["thr"]) for r in rows]
     assert got == [int(r[1]) for r in rows]
     assert sum(got) == info["ones"]
+    if info["thr"] > info["k"]:
+        assert info["ones"] == 0                          # (no cell can reach k + 1)
+    else:
+        assert 0 < info["ones"] < info["n"]               # both verdicts
 
 
 def parse_map(name):

@@ -155,6 +155,8 @@ static int parse(int argc, char** argv, cli* c) {
 	if (!c->source_sim_file[0]) { fprintf(stderr, "source_sim_file file must be specified\n"); ok = 0; }
 	if (c->hp.j_conserved != 'W' && c->hp.j_conserved != 'F') { fprintf(stderr, "Conserved J AA must be W or F: %c\n", c->hp.j_conserved); ok = 0; }
 	if (c->hp.insert_len <= 0) { fprintf(stderr, "insert_len must be specified and > 0\n"); ok = 0; }
+	/* (vdjx_vregion_load's limit, said here: before the input is read, let alone a pool loaded) */
+	if (c->hp.vregion_kmer_size < 2 || c->hp.vregion_kmer_size > 16) { fprintf(stderr, "--vk: vregion k-mer size %d outside [2,16]\n", c->hp.vregion_kmer_size); ok = 0; }
 	if (c->d_calls && !c->airr) { fprintf(stderr, "--d-calls adds the D call to the --airr table: it needs --airr <file>\n"); ok = 0; }
 	if (c->isotypes && !c->cfa) { fprintf(stderr, "--isotypes needs the constant-region sequences: --cfa <fasta>\n"); ok = 0; }
 	if (c->cfa) {

@@ -248,6 +248,7 @@ struct vdjx_ctx {
 	const vdjx_graph* root_pending_g = nullptr;
 	int root_pending_thr = 0;
 	uint32_t root_pending_first = 0, root_pending_stride = 1, root_pending_ahead = 0;
+	bool root_pending_by_wave = false;     // the begun call's guessed launch went to k_root_dp_wave (root_dp_items_wave / _thread)
 	uint32_t* root_pending_ids = nullptr;
 	uint8_t* root_pending_out = nullptr;
 	hipEvent_t ev_root_done = nullptr;

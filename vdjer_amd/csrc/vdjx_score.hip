@@ -247,6 +247,14 @@ __global__ __launch_bounds__(DPW_THREADS) void k_root_dp_wave(const char* __rest
 	}
 }
 
+// beside root_dp_items: how many of the call's `run` items each DP kernel took.  The guessed launch covers the items below `ahead`;
+// a remainder launch adds its own (root_score_device).  Nothing is launched for a threshold <= 0: both stay 0 then.
+static void root_dp_note(vdjx_ctx* c, u32 run, u32 ahead, bool ahead_by_wave) {
+	const u32 took = run < ahead ? run : ahead;
+	c->stats["root_dp_items_wave"] = ahead_by_wave ? took : 0;
+	c->stats["root_dp_items_thread"] = ahead_by_wave ? 0 : took;
+}
+
 // the scorer proper: d_k = n*k ASCII on the device, out = n host bytes
 // begin: queue everything, wait for nothing -- possible when the last call's item count is at hand as a guess (root_dp_hint) and the
 // threshold is positive; *begun says whether it was (else the call ran to its end as ever).  vdjx_root_score_graph_end waits, and
@@ -275,29 +283,34 @@ static int root_score_device(vdjx_ctx* c, vdjx_work& db, const char* d_k, size_t
 	if (!begun) HIP_TRY(hipEventRecord(c->ev_plan, st));
 	// few items: a wave each (k_root_dp_wave); many: a thread each
 	constexpr u32 dp_wave_max = 32768u;      // (measured: 10 k items 0.043 against 0.110 ms, 25 k 0.087 / 0.111, 77 k 0.234 / 0.130, 252 k 0.74 / 0.18)
+	bool by_wave = false;                                     // which kernel the last launch_dp went to
 	auto launch_dp = [&](u32 first, u32 count) -> u32 {        // -> items covered from `first` on (whole workgroups)
 		vdjx_prof_scope ps(c, "k_root_dp");
 		if (count <= dp_wave_max && k <= 64) {
 			const u32 per = DPW_THREADS / 64;
+			by_wave = true;
 			hipLaunchKernelGGL(k_root_dp_wave, dim3((count + per - 1) / per), dim3(DPW_THREADS), 0, st, d_k, k, threshold,
 			                   d_lo, d_pre, ng, (u32) stop, first, c->d_seed_pos, c->d_vtext, c->d_line_off, (u32) c->n_lines, d_out);
 			return (count + per - 1) / per * per;
 		}
+		by_wave = false;
 		hipLaunchKernelGGL(k_root_dp, dim3((unsigned) ((count + DP_THREADS - 1) / DP_THREADS)), dim3(DP_THREADS), 0, st, d_k, k, threshold,
 		                   d_lo, d_pre, ng, (u32) stop, first, c->d_seed_pos, c->d_vtext, c->d_line_off, (u32) c->n_lines, d_out);
 		return (count + DP_THREADS - 1) / DP_THREADS * DP_THREADS;
 	};
 	u32 ahead = 0;
 	if (threshold > 0 && c->root_dp_hint) ahead = launch_dp(0u, c->root_dp_hint);
+	const bool ahead_by_wave = by_wave;
 	// (the verdicts follow the guessed launch at once: when the guess covered the call -- every call but the first of a size -- the host
 	// wakes up once, with the verdicts there, instead of once for the number and again for the verdicts)
 	if (ahead) HIP_TRY(hipMemcpyAsync(out, d_out, n, hipMemcpyDeviceToHost, st));
-	if (begun && ahead && threshold > 0) { c->root_pending_ahead = ahead; *begun = true; return VDJX_OK; }      // (nothing waited for)
+	if (begun && ahead && threshold > 0) { c->root_pending_ahead = ahead; c->root_pending_by_wave = ahead_by_wave; *begun = true; return VDJX_OK; }      // (nothing waited for)
 	if (begun) HIP_TRY(hipEventRecord(c->ev_plan, st));
 	HIP_TRY(hipEventSynchronize(c->ev_plan));
 	const u32 run = *h_run;
 	c->root_dp_hint = run + run / 4 + 1024;
 	c->stats["root_dp_items"] = run;
+	root_dp_note(c, run, ahead, ahead_by_wave);
 	if (run >= (1u << 31)) { vdjx_set_error("too many seed hits in one call (%u)", run); return VDJX_ELIMIT; }
 	if (ahead && threshold > 0 && run <= ahead) {
 		HIP_TRY(hipStreamSynchronize(st));
@@ -312,7 +325,10 @@ static int root_score_device(vdjx_ctx* c, vdjx_work& db, const char* d_k, size_t
 		for (size_t r = 0; r < n; r++) out[r] = pre[(r + 1) * stop] > pre[r * stop];
 		return VDJX_OK;
 	}
-	if (run > ahead) (void) launch_dp(ahead, run - ahead);
+	if (run > ahead) {
+		(void) launch_dp(ahead, run - ahead);
+		c->stats[by_wave ? "root_dp_items_wave" : "root_dp_items_thread"] += run - ahead;
+	}
 	HIP_TRY(hipMemcpyAsync(out, d_out, n, hipMemcpyDeviceToHost, st));
 	HIP_TRY(hipStreamSynchronize(st));
 	HIP_TRY(hipGetLastError());
@@ -448,6 +464,7 @@ extern "C" int vdjx_root_score_graph_end(vdjx_ctx* c) {
 	const u32 run = *((const u32*) c->h_pin + VDJX_HPIN_ROOT_RUN);
 	c->root_dp_hint = run + run / 4 + 1024;
 	c->stats["root_dp_items"] = run;
+	root_dp_note(c, run, c->root_pending_ahead, c->root_pending_by_wave);
 	if (run <= c->root_pending_ahead) return VDJX_OK;
 	// the guess fell short (a pool unlike the last one): the call again, the ordinary way
 	return vdjx_root_score_graph(c, c->root_pending_g, c->root_pending_thr, c->root_pending_first, c->root_pending_stride, c->root_pending_ids, c->root_pending_out);

@@ -425,6 +425,39 @@ int vdjx_dsegment_load(vdjx_ctx* ctx, const char* seqs, const uint64_t* off, siz
 int vdjx_dcall(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const int32_t* win_start, const int32_t* win_len,
                const vdjx_dcall_params* params, vdjx_annot_hit* out_d, int32_t* out_scores);
 
+/* ---- clonal lineages: single linkage over the junctions' length-normalised Hamming distance ---------------------------------------------
+ * gives `vdjer --lineages` the clone_id of an AIRR rearrangement table: the grouping Change-O's DefineClones / SCOPer make of V'DJer's
+ * output in a second tool (same V gene, same J gene, same junction length, single linkage on the nucleotide junctions).  All pairs of a
+ * bucket are compared on the device.  All arithmetic is integer: the device's results are bitwise the model's (tests/lineage_model.py).
+ *   items       item i is junctions[off[i] .. off[i+1]) of length L_i; group[i] is a key the caller chose (a V-gene / J-gene pair).  An
+ *               item whose group is VDJX_LINEAGE_NONE takes no part: out_clone = -1, out_nearest = -1, any length, 0 included.
+ *   bucket      the participating items of equal group and equal L.  They may lie anywhere in the input: nothing has to be sorted.
+ *   distance    d(i, j) of two items of one bucket: the number of positions p in 0 .. L-1 at which the characters differ or either is not
+ *               one of ACGT.  N never matches, not even N (as in vdjx_annotate); lower case is not ACGT.
+ *   link        i and j are linked iff they share a bucket, i != j and d(i, j) * den <= num * L (exact: 255 * den fits 32 bits).
+ *   clone       a connected component of the link graph (single linkage).  out_clone[i] is 0-based: the components are numbered in the
+ *               order of their smallest member index.
+ *   nearest     out_nearest[i] (may be NULL) = the smallest d(i, j) > 0 over the other items j of i's bucket, -1 when there is none (a
+ *               bucket of one item, or of items all at distance 0): Change-O's distToNearest, left unnormalised.
+ *   info        (may be NULL; zeroed first, every field filled on success) items: participating items; buckets; largest_bucket: the
+ *               items of the largest; clones; pairs: the sum of m (m - 1) / 2 over the buckets of m items; links: unordered linked pairs.
+ * Defaults (what `vdjer --lineages` uses): num / den = 1500 / 10000, the 0.15 SCOPer documents as a starting point.  It is a parameter of
+ * the model, not a tolerance: out_nearest (the table's dist_nearest) is there so that a user can choose their own from its histogram.
+ * NOT modelled: amino-acid or substitution-model (HH_S5F) distances; N as a wildcard; average or complete linkage; clustering across
+ * samples; "first gene only" handling of tied V calls (the group is the caller's: `vdjer` keys on the whole normalised tie list).
+ * VDJX_EINVAL: n >= 2^20, a participating item of 0 or more than VDJX_LINEAGE_MAXLEN bases, offsets that decrease, den < 1, den > 10^6,
+ * num < 0, num > den, NULL out_clone.  n = 0 returns at once with a zeroed info.  The (group, L, index) keys are sorted on the host (per
+ * item); everything per pair runs on the device.  A call is five kernel dispatches (pack, pairs, flatten, number, out) whatever n and the
+ * number of buckets are.  Scratch comes from the context's workspace; no floating point.  The union-find of the pair pass uses integer
+ * atomics, and the larger root always goes under the smaller: the result does not depend on the order they land in, two calls give the
+ * same bits.  Stats: "lineage_work_items" ((bucket, row block, column slice) items of the pair pass), "lineage_us" (host clock). */
+#define VDJX_LINEAGE_NONE   0xFFFFFFFFu
+#define VDJX_LINEAGE_MAXLEN 255
+typedef struct { int num, den; } vdjx_lineage_params;                 /* 8 bytes  */
+typedef struct { uint32_t items, buckets, largest_bucket, clones; uint64_t pairs, links; } vdjx_lineage_info;  /* 32 bytes */
+int vdjx_lineage(vdjx_ctx* ctx, const char* junctions, const uint64_t* off, const uint32_t* group, size_t n,
+                 const vdjx_lineage_params* params, int32_t* out_clone, int32_t* out_nearest, vdjx_lineage_info* info);
+
 /* rows of `row` bytes on the device: row d_pos[i] of d_dst = row i of d_src.  (The records of a pool sharded by pair on their way to
  * the ranks that hold their slice of the scan order for the k-mer build, A2:1388-1390: every record arrives with its place.) */
 int vdjx_rows_scatter(vdjx_ctx* ctx, void* d_dst, const void* d_src, const uint32_t* d_pos, size_t n, size_t row);

@@ -86,3 +86,53 @@ def vq_gene(names) -> str:
     IGKV1D-39 -> IGKV1-39), then what lies before a second '-' (IGHV3-30-5 -> IGHV3-30); the distinct results in order of first
     appearance"""
     return _distinct("-".join(gene_of(x).replace("D", "").split("-")[:2]) for x in names)
+
+
+LINEAGE_NONE = 0xFFFFFFFF                                   # VDJX_LINEAGE_NONE (include/vdjx.h)
+LINEAGE_MAXLEN = 255                                        # VDJX_LINEAGE_MAXLEN
+
+
+def junction_of(seq_id: str, contig: str):
+    """junction_at of vdjer_main.c: the junction is the text after the id's second '_' (vjf_<n>_<junction>), looked for at its first
+    occurrence in the contig -> (its 0-based start or -1, the text; '' when the id has none)"""
+    parts = seq_id.split("_", 2)
+    text = parts[2] if len(parts) == 3 else ""
+    if not text or len(text) > len(contig):
+        return -1, text
+    return contig.find(text), text
+
+
+def parse_lineage_dist(text: str):
+    """--lineage-dist: a decimal in [0, 1] with at most four digits after the point, read exactly -> (num, 10000); ValueError otherwise
+    (digits, at most one point, at least one digit: "0.15", ".2", "1", "1.", "1.0000"; no sign, no exponent, no blanks)"""
+    whole, point, frac = text.partition(".")
+    ok = bool(whole or frac) and len(whole) <= 1 and len(frac) <= 4 and all(ch in "0123456789" for ch in whole + frac)
+    num = int(whole or "0") * 10000 + int((frac + "0000")[:4]) if ok else -1
+    if not ok or num > 10000:
+        raise ValueError(f"--lineage-dist must be a decimal in [0, 1] with at most four digits after the point: {text!r}")
+    return num, 10000
+
+
+def lineage_inputs(ids, contigs, v, j, names):
+    """what `vdjer --lineages` hands to vdjx_lineage, from the V and the J hits ({field: array} as Context.annotate returns them) and the
+    germline names -> (junctions, group uint32[n], vgene, jgene).  A contig is eligible when it has a V call and a J call (gene >= 0,
+    both) and its junction is found in it with 3 .. 255 bases; its group is the index, by first appearance, of its distinct
+    (vq_gene(V ties), vq_gene(J ties)) pair -- the strings --clones prints as vgene / jgene.  Every other contig gets LINEAGE_NONE and an
+    empty junction; vgene / jgene are '' without a call."""
+    import numpy as np
+    n = len(ids)
+    junctions, vgene, jgene = [], [], []
+    group = np.full(n, LINEAGE_NONE, np.uint32)
+    seen = {}
+    for c in range(n):
+        def gene(h):
+            return vq_gene(names[g] for g in h["tied"][c][:min(8, int(h["n_tied"][c]))]) if h["gene"][c] >= 0 else ""
+        vg, jg = gene(v), gene(j)
+        p, text = junction_of(ids[c], contigs[c])
+        ok = v["gene"][c] >= 0 and j["gene"][c] >= 0 and p >= 0 and 3 <= len(text) <= LINEAGE_MAXLEN
+        if ok:
+            group[c] = seen.setdefault((vg, jg), len(seen))
+        junctions.append(text if ok else "")
+        vgene.append(vg)
+        jgene.append(jg)
+    return junctions, group, vgene, jgene

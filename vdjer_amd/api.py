@@ -724,6 +724,28 @@ class Context:
         check(self.L.vdjx_dcall(self.h, raw, n, ln, _p(ws), _p(wl), C.byref(prm), _p(hd), _p(sc) if scores and sc.size else None), "vdjx_dcall")
         return {"d": {f: hd[f].copy() for f in self.ANNOT_HIT.names}, "scores": sc}
 
+    LINEAGE_NONE = 0xFFFFFFFF                                # VDJX_LINEAGE_NONE (include/vdjx.h)
+
+    def lineage(self, junctions, group, max_dist=(1500, 10000), nearest: bool = True):
+        """vdjx_lineage: single linkage inside the buckets of equal group and junction length; two junctions are linked when
+        d * max_dist[1] <= max_dist[0] * L (d: positions that differ or are not ACGT).  junctions: str or bytes per item; group: uint32[n],
+        LINEAGE_NONE for an item that takes no part -> {"clone": int32[n] (0-based, -1: no part), "nearest": int32[n] | None (smallest
+        non-zero distance inside the bucket, -1: none), "info": dict(items, buckets, largest_bucket, clones, pairs, links)}"""
+        enc = [s_ if isinstance(s_, (bytes, bytearray)) else s_.encode() for s_ in junctions]
+        n = len(enc)
+        grp = np.ascontiguousarray(group, np.uint32)
+        if grp.shape != (n,):
+            raise VdjxError(f"vdjx_lineage: {n} junctions, group of shape {grp.shape}")
+        off = np.zeros(n + 1, np.uint64)
+        off[1:] = np.cumsum([len(e) for e in enc], dtype=np.uint64)
+        clone = np.zeros(n, np.int32)
+        near = np.zeros(n, np.int32) if nearest else None
+        info = _lib.LineageInfo()
+        prm = _lib.LineageParams(int(max_dist[0]), int(max_dist[1]))
+        check(self.L.vdjx_lineage(self.h, b"".join(enc), _p(off), _p(grp), n, C.byref(prm), _p(clone), _p(near), C.byref(info)), "vdjx_lineage")
+        return {"clone": clone, "nearest": near,
+                "info": {f: int(getattr(info, f)) for f in ("items", "buckets", "largest_bucket", "clones", "pairs", "links")}}
+
     def stat(self, name: str) -> int:
         return int(self.L.vdjx_stat(self.h, name.encode()))
 

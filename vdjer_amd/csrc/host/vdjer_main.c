@@ -5,12 +5,15 @@
  *   vdjer --in <reads> --chain IGH|IGK|IGL --ref-dir <dir> --ins <n> [--t --k --mf --mq --mcs --am --miw --maw
  *         --jc --ws -jext --rf --vk --mrs --rs --ms --e0 --e1 --wo --vf --jf --rms] [--gpus N] [--quant <file>] [--airr <file>]
  *         [--d-calls] [--cfa <fasta>] [--isotypes <file>] [--clones <file>] [--sample <name>] [--total-count <n>]
+ *         [--lineages <file>] [--lineage-dist <x>]
  * writes ./vdj_contigs.fa and ./vdjer.dot, SAM on stdout, log on stderr; exit 0 on success.  --quant <file>: the contigs' abundances
  * (vdjx_quant, RSEM's isoforms.results columns) into <file> as well.  --airr <file>: the contigs' V/J annotation (vdjx_annotate against
  * the germlines of ig_vdj.fa / --vdjf) as an AIRR Rearrangement TSV; with --d-calls (a flag: no value) the D gene between the V and the
  * J hit as well (vdjx_dcall against the class-D records of the same FASTA), and the N regions around it.  --cfa <fasta>: constant-region sequences; --isotypes <file>: the
  * isotype call of every contig against them (vdjx_isotype); --clones <file>: the per-sample table of the reference's post_process/
- * (collect_vdjer_stats.py | cluster_results.py) from the three device steps (one GPU only).
+ * (collect_vdjer_stats.py | cluster_results.py) from the three device steps (one GPU only).  --lineages <file>: the contigs grouped into
+ * clonal lineages (vdjx_lineage: single linkage on the junctions' Hamming distance inside a V gene / J gene / junction length bucket,
+ * linked up to --lineage-dist, default 0.15 of the length); with --airr the table gets a clone_id column.
  *
  * --in: a BAM with its .bai (extraction as bam_read.c:264-446, restated over zlib in bamx.c), or -- recognised by its
  * content -- the extracted read pool as text, one read per line in extraction order:
@@ -55,6 +58,9 @@ typedef struct {
 	const char* clones;                    /* --clones <file> (not in the reference): collect_vdjer_stats.py | cluster_results.py */
 	const char* sample;                    /* --sample <name>: the clone table's first column (default: --in's base name up to its first '.') */
 	const char* total_count;               /* --total-count <n>: the clone table's total_count column (default: N/A) */
+	const char* lineages;                  /* --lineages <file> (not in the reference): Change-O DefineClones' grouping of the contigs, on the device */
+	const char* lineage_dist;              /* --lineage-dist <x>: its threshold, a decimal read exactly into lin_num / lin_den (default 1500 / 10000) */
+	int lin_num, lin_den;
 	int have_chain, have_ref;
 } cli;
 
@@ -75,10 +81,23 @@ static void usage(void) {
 	                "\t--isotypes <file: isotype call of every contig's last 48 bases against --cfa>\n"
 	                "\t--clones <file: the clustered clone table of this sample (one GPU only)>\n"
 	                "\t--sample <name in the clone table (default: the input's base name up to its first '.')>\n"
-	                "\t--total-count <whole number for the clone table's total_count column (default: N/A)>\n");
+	                "\t--total-count <whole number for the clone table's total_count column (default: N/A)>\n"
+	                "\t--lineages <file: clonal lineages of the contigs, single linkage on the junctions inside a V gene / J gene / length bucket>\n"
+	                "\t--lineage-dist <largest linked distance as a fraction of the junction length, in [0,1], at most 4 decimals (default: 0.15)>\n");
 }
 
 static int file_exists(const char* f) { struct stat b; return stat(f, &b) == 0; }
+
+/* --lineage-dist: a decimal in [0, 1] with at most four digits after the point, read exactly (no strtod): at most one digit before the
+ * point, at least one digit in all -> its numerator over 10000, or -1 (parse_lineage_dist of vdjer_amd/annot.py) */
+static int lineage_dist_num(const char* s) {
+	const char* dot = strchr(s, '.');
+	const size_t wl = dot ? (size_t) (dot - s) : strlen(s), fl = dot ? strlen(dot + 1) : 0;
+	if (wl + fl == 0 || wl > 1 || fl > 4 || strspn(s, "0123456789") != wl || (dot && strspn(dot + 1, "0123456789") != fl)) return -1;
+	int v = wl ? (s[0] - '0') * 10000 : 0;
+	for (size_t k = 0, scale = 1000; k < fl; k++, scale /= 10) v += (dot[1 + k] - '0') * (int) scale;
+	return v <= 10000 ? v : -1;
+}
 
 /* params.c:214-298: positional "--flag value" pairs; unknown flags only warn */
 static int parse(int argc, char** argv, cli* c) {
@@ -121,6 +140,8 @@ static int parse(int argc, char** argv, cli* c) {
 		else if (!strcmp(a, "--clones")) c->clones = v;
 		else if (!strcmp(a, "--sample")) c->sample = v;
 		else if (!strcmp(a, "--total-count")) c->total_count = v;
+		else if (!strcmp(a, "--lineages")) c->lineages = v;
+		else if (!strcmp(a, "--lineage-dist")) c->lineage_dist = v;
 		else if (!strcmp(a, "--vf")) snprintf(c->v_anchors, sizeof c->v_anchors, "%s", v);
 		else if (!strcmp(a, "--jf")) snprintf(c->j_anchors, sizeof c->j_anchors, "%s", v);
 		else if (!strcmp(a, "--am")) c->anchor_mismatches = atoi(v);
@@ -166,6 +187,13 @@ static int parse(int argc, char** argv, cli* c) {
 	}
 	if (c->total_count && (!c->total_count[0] || strspn(c->total_count, "0123456789") != strlen(c->total_count))) {
 		fprintf(stderr, "--total-count must be a whole decimal number: %s\n", c->total_count);
+		ok = 0;
+	}
+	c->lin_num = 1500;
+	c->lin_den = 10000;
+	if (c->lineage_dist && !c->lineages) { fprintf(stderr, "--lineage-dist is the threshold of the --lineages table: it needs --lineages <file>\n"); ok = 0; }
+	if (c->lineage_dist && (c->lin_num = lineage_dist_num(c->lineage_dist)) < 0) {
+		fprintf(stderr, "--lineage-dist must be a decimal in [0, 1] with at most four digits after the point: %s\n", c->lineage_dist);
 		ok = 0;
 	}
 	if (!ok) { usage(); return -1; }
@@ -512,6 +540,10 @@ typedef struct {
 	struct germ_set* cst; vdjx_annot_hit* hc;            /* the constant records and the isotype hits (iso_run) */
 	int iso_done, clones_done;
 	size_t i_contigs, i_called, c_rows, c_clusters;
+	/* --lineages: the clone of every contig (lineage_run; -1: not eligible), kept for the --airr table's clone_id */
+	const char* lineages; int lin_num, lin_den, lin_done;
+	int32_t* lin_clone; vdjx_lineage_info li;
+	size_t l_contigs, l_eligible;
 } hook_ud;
 
 static int h_root_score(void* ud, const char* kmers, size_t n, int k, int thr, uint8_t* out) {
@@ -694,7 +726,7 @@ static long junction_at(const char* id, const char* s, int len, const char** jn_
 /* the V / J hits of every contig (vdjx_annotate against the germlines of ig_vdj.fa / --vdjf), kept for the tables */
 static int annot_run(hook_ud* u, const char* contigs, size_t n, int len) {
 	u->germ = (germ_set*) calloc(1, sizeof(germ_set));
-	if (germ_read(u->vdjf, u->germ, u->airr ? "--airr: cannot read the germline FASTA" : "--clones: cannot read the germline FASTA")) return -1;
+	if (germ_read(u->vdjf, u->germ, u->airr ? "--airr: cannot read the germline FASTA" : u->clones ? "--clones: cannot read the germline FASTA" : "--lineages: cannot read the germline FASTA")) return -1;
 	const germ_set* g = u->germ;
 	for (size_t r = 0; r < g->n; r++) {
 		if (g->cls[r] == 'V' || g->cls[r] == 'J') continue;
@@ -705,7 +737,7 @@ static int annot_run(hook_ud* u, const char* contigs, size_t n, int len) {
 	const vdjx_annot_params ap = {2, 3, 5, 2, 40, 20};
 	int rc = vdjx_germline_load(u->gx, g->seqs, g->off, g->cls, g->n);
 	if (!rc && n) rc = vdjx_annotate(u->gx, contigs, n, len, &ap, u->hv, u->hj);
-	if (rc) fprintf(stderr, "%s: %s\n", u->airr ? "--airr" : "--clones", vdjx_last_error());
+	if (rc) fprintf(stderr, "%s: %s\n", u->airr ? "--airr" : u->clones ? "--clones" : "--lineages", vdjx_last_error());
 	return rc;
 }
 
@@ -780,6 +812,7 @@ static int airr_table(hook_ud* u, const char* const* ids, const char* contigs, s
 		      "v_germline_start\tv_germline_end\tj_score\tj_identity\tj_sequence_start\tj_sequence_end\tj_germline_start\tj_germline_end", fp);
 		if (u->d_calls)
 			fputs("\td_score\td_identity\td_sequence_start\td_sequence_end\td_germline_start\td_germline_end\tnp1\tnp1_length\tnp2\tnp2_length", fp);
+		if (u->lineages) fputs("\tclone_id", fp);
 		fputs(u->quant ? "\texpected_count\n" : "\n", fp);
 		for (size_t i = 0; i < n; i++) {
 			const char* s = contigs + i * (size_t) len;
@@ -821,6 +854,7 @@ static int airr_table(hook_ud* u, const char* const* ids, const char* contigs, s
 			put_hit(fp, v);
 			put_hit(fp, j);
 			if (u->d_calls) put_np(fp, s, v, u->hd + i, j);
+			if (u->lineages) { if (u->lin_clone[i] >= 0) fprintf(fp, "\tlin_%d", u->lin_clone[i] + 1); else fputc('\t', fp); }
 			if (u->quant) fprintf(fp, "\t%.2f", u->qcnt ? u->qcnt[i] : 0.0);
 			fputc('\n', fp);
 		}
@@ -974,12 +1008,95 @@ static int clones_table(hook_ud* u, const char* const* ids, const char* contigs,
 	return 0;
 }
 
+/* --lineages: the contigs grouped into clonal lineages (the model: include/vdjx.h, vdjx_lineage; the inputs: lineage_inputs of
+ * vdjer_amd/annot.py).  A contig is eligible when it has a V and a J call and its junction is found in it with 3 .. 255 bases; its group is
+ * the index, by first appearance, of its (vgene, jgene) pair as --clones prints them.  A row per contig: clone_id lin_<k>, vgene, jgene,
+ * junction_length, dist_nearest (the smallest non-zero distance inside the bucket over the length), clone_size and, when the quant step ran,
+ * clone_expected_count: the sum of the members' expected_count as printed (two decimals each), so that the tables add up */
+static int lineage_run(hook_ud* u, const char* const* ids, const char* contigs, size_t n, int len) {
+	FILE* fp = fopen(u->lineages, "w");
+	if (!fp) { fprintf(stderr, "cannot write %s\n", u->lineages); return -1; }
+	const int counted = u->quant || u->clones;
+	char* cat = (char*) malloc(n * (size_t) VDJX_LINEAGE_MAXLEN + 1);
+	uint64_t* off = (uint64_t*) calloc(n + 1, sizeof(uint64_t));
+	uint32_t* grp = (uint32_t*) calloc(n + 1, sizeof(uint32_t));
+	int32_t* near = (int32_t*) calloc(n + 1, sizeof(int32_t));
+	char** vgs = (char**) calloc(n + 1, sizeof(char*));
+	char** jgs = (char**) calloc(n + 1, sizeof(char*));
+	u->lin_clone = (int32_t*) calloc(n + 1, sizeof(int32_t));
+	slist vg, jg;
+	memset(&vg, 0, sizeof vg); memset(&jg, 0, sizeof jg);
+	char** keys = NULL;
+	size_t nkeys = 0, kcap = 0, tot = 0;
+	for (size_t i = 0; i < n; i++) {
+		const vdjx_annot_hit *v = u->hv + i, *j = u->hj + i;
+		vq_gene_of(v, u->germ, &vg);
+		vq_gene_of(j, u->germ, &jg);
+		vgs[i] = strdup(sl_str(&vg));
+		jgs[i] = strdup(sl_str(&jg));
+		const char* jn;
+		size_t jl;
+		const long p = junction_at(ids[i], contigs + i * (size_t) len, len, &jn, &jl);
+		grp[i] = VDJX_LINEAGE_NONE;
+		if (v->gene >= 0 && j->gene >= 0 && p >= 0 && jl >= 3 && jl <= VDJX_LINEAGE_MAXLEN) {
+			const size_t kl = strlen(vgs[i]) + strlen(jgs[i]) + 2;
+			char* key = (char*) malloc(kl);
+			snprintf(key, kl, "%s\t%s", vgs[i], jgs[i]);
+			size_t k = 0;
+			while (k < nkeys && strcmp(keys[k], key)) k++;
+			if (k == nkeys) {
+				if (nkeys + 1 > kcap) { kcap = kcap ? 2 * kcap : 64; keys = (char**) realloc(keys, kcap * sizeof(char*)); }
+				keys[nkeys++] = key;
+			} else free(key);
+			grp[i] = (uint32_t) k;
+			memcpy(cat + tot, jn, jl);
+			tot += jl;
+			u->l_eligible++;
+		}
+		off[i + 1] = tot;
+		u->l_contigs++;
+	}
+	const vdjx_lineage_params lp = {u->lin_num, u->lin_den};
+	int rc = vdjx_lineage(u->gx, cat, off, grp, n, &lp, u->lin_clone, near, &u->li);
+	if (rc) fprintf(stderr, "--lineages: %s\n", vdjx_last_error());
+	if (!rc) {
+		size_t* size = (size_t*) calloc((size_t) u->li.clones + 1, sizeof(size_t));
+		double* sum = (double*) calloc((size_t) u->li.clones + 1, sizeof(double));
+		for (size_t i = 0; i < n; i++) {
+			if (u->lin_clone[i] < 0) continue;
+			char cnt[64];
+			snprintf(cnt, sizeof cnt, "%.2f", u->qcnt ? u->qcnt[i] : 0.0);
+			size[u->lin_clone[i]]++;
+			sum[u->lin_clone[i]] += atof(cnt);
+		}
+		fprintf(fp, "sequence_id\tclone_id\tvgene\tjgene\tjunction_length\tdist_nearest\tclone_size%s\n", counted ? "\tclone_expected_count" : "");
+		for (size_t i = 0; i < n; i++) {
+			const int32_t k = u->lin_clone[i];
+			const uint64_t L = off[i + 1] - off[i];
+			if (k < 0) { fprintf(fp, "%s\t\t%s\t%s\t\t\t%s\n", ids[i], vgs[i], jgs[i], counted ? "\t" : ""); continue; }
+			fprintf(fp, "%s\tlin_%d\t%s\t%s\t%llu\t", ids[i], k + 1, vgs[i], jgs[i], (unsigned long long) L);
+			if (near[i] >= 0) fprintf(fp, "%.4f", (double) near[i] / (double) L);
+			fprintf(fp, "\t%zu", size[k]);
+			if (counted) fprintf(fp, "\t%.2f", sum[k]);
+			fputc('\n', fp);
+		}
+		free(size); free(sum);
+	}
+	for (size_t i = 0; i < n; i++) { free(vgs[i]); free(jgs[i]); }
+	for (size_t k = 0; k < nkeys; k++) free(keys[k]);
+	free(keys); free(vgs); free(jgs); free(vg.s); free(jg.s); free(cat); free(off); free(grp); free(near);
+	if (fclose(fp)) { fprintf(stderr, "cannot write %s\n", u->lineages); return -1; }
+	if (!rc) u->lin_done = 1;
+	return rc;
+}
+
 /* the tables after the SAM body: every device step runs once, whichever tables ask for it */
 static int tables(hook_ud* u, const char* const* ids, const char* contigs, size_t n, int len) {
 	int rc = 0;
 	if (!rc && (u->quant || u->clones)) rc = quant_table(u, ids, contigs, n, len);
-	if (!rc && (u->airr || u->clones)) rc = annot_run(u, contigs, n, len);
+	if (!rc && (u->airr || u->clones || u->lineages)) rc = annot_run(u, contigs, n, len);
 	if (!rc && u->d_calls) rc = dcall_run(u, contigs, n, len);
+	if (!rc && u->lineages) rc = lineage_run(u, ids, contigs, n, len);
 	if (!rc && u->airr) rc = airr_table(u, ids, contigs, n, len);
 	if (!rc && u->cfa && (u->isotypes || u->clones)) rc = iso_run(u, contigs, n, len);
 	if (!rc && u->isotypes) rc = isotypes_table(u, ids, n, len);
@@ -1256,6 +1373,7 @@ int main(int argc, char** argv) {
 	memset(&ud, 0, sizeof ud);
 	ud.gx = gx; ud.p = &c.hp; ud.mg = mg; ud.quant = c.quant; ud.airr = c.airr; ud.vdjf = c.vdj_fasta; ud.d_calls = c.d_calls;
 	ud.cfa = c.cfa; ud.isotypes = c.isotypes; ud.clones = c.clones; ud.total_count = c.total_count;
+	ud.lineages = c.lineages; ud.lin_num = c.lin_num; ud.lin_den = c.lin_den;
 	char sample_buf[4096];
 	if (c.sample) ud.sample = c.sample;
 	else {                                  /* the input's base name up to its first '.' */
@@ -1271,7 +1389,7 @@ int main(int argc, char** argv) {
 		return 1;
 	}
 	/* (no contig: the headers alone) */
-	if (!ud.quant_done && !ud.airr_done && !ud.iso_done && !ud.clones_done && tables(&ud, NULL, NULL, 0, 0)) return 1;
+	if (!ud.quant_done && !ud.airr_done && !ud.iso_done && !ud.clones_done && !ud.lin_done && tables(&ud, NULL, NULL, 0, 0)) return 1;
 	fprintf(stderr, "num root nodes: %zu\nProcessed roots: %zu\ncontig_candidates: %zu\nwindows scored: %zu valid: %zu\ncontigs: %zu\n",
 	        st.n_roots, st.n_roots_accepted, st.n_contig_candidates, st.n_windows_scored, st.n_windows_valid, st.n_contigs_out);
 	if (mg) {
@@ -1307,6 +1425,9 @@ int main(int argc, char** argv) {
 	if (c.d_calls)
 		fprintf(stderr, "dcalls: %zu contigs, %zu windows, %zu over %d bases, %zu D called against %zu D records\n", ud.d_contigs, ud.d_windows, ud.d_over,
 		        VDJX_DCALL_WINDOW, ud.d_called, ud.dset ? ud.dset->n : (size_t) 0);
+	if (c.lineages)
+		fprintf(stderr, "lineages: %zu contigs, %zu eligible, %u buckets (largest %u), %llu pairs, %llu links, %u lineages at %d/%d\n", ud.l_contigs, ud.l_eligible,
+		        ud.li.buckets, ud.li.largest_bucket, (unsigned long long) ud.li.pairs, (unsigned long long) ud.li.links, ud.li.clones, c.lin_num, c.lin_den);
 	if (c.isotypes)
 		fprintf(stderr, "isotypes: %zu contigs, %zu called against %zu constant records of %s; table in %s\n", ud.i_contigs, ud.i_called,
 		        ud.cst ? ud.cst->n : (size_t) 0, c.cfa, c.isotypes);

@@ -1,7 +1,8 @@
 """vdjx_lineage on the GPU: clone, nearest and every info field against the plain model of tests/lineage_model.py, exactly -- bucket sizes
 around the pair pass's row block and column tile (64), junction lengths around its 32-base words, interleaved buckets, a chain that only
 holds together link by link, two families one substitution past the threshold, characters that are not ACGT, seeded random repertoires,
-permutations, the refusals -- and `vdjer --lineages` on a heavy-chain and a light-chain golden against the model's table.  The API cases
+permutations, the refusals; buckets of 4,096 and 4,097 and eleven buckets whose column slices hold two tiles, a bucket of 1,000 equal junctions,
+2^20 - 1 items, offsets that start past zero -- and `vdjer --lineages` on a heavy-chain and a light-chain golden against the model's table.  The API cases
 run in one child process (as tests/test_gpu_dcall.py runs its own); every model result is computed once."""
 import functools
 import json
@@ -125,6 +126,72 @@ def cases():
                 grp.append(g if r.integers(0, 25) else M.NONE)
         order = r.permutation(len(js))
         out[f"random_{seed}"] = ([js[i] for i in order], [grp[i] for i in order], (int(r.choice(THRESHOLDS)), 10000))
+    out.update(_past_one_tile(np.random.default_rng(20241)))
+    return out
+
+
+def work_items(sizes):
+    """the work items vdjx_lineage makes of buckets of these sizes (vdjx_lineage.hip): row blocks of 64 times column slices of
+    max(64, ceil(cells / (64 * 4096) / 64) * 64) columns, cells the sum of the squared sizes -> (items, slice)"""
+    cells = sum(m * m for m in sizes)
+    per = -(-cells // (64 * 4096))
+    width = max(64, -(-per // 64) * 64)
+    return sum(-(-m // 64) * -(-m // width) for m in sizes), width
+
+
+BIG = ["bucket_4096", "bucket_4097", "slice_128_small_buckets", "all_equal_1000", "n_2_20_minus_1"]
+SMALL_BUCKETS = [1500, 100, 1500, 1500, 65, 1500, 1500, 1, 1500, 1500, 1500]      # bucket g has SMALL_BUCKETS[g] items
+
+
+def _step(s, k):
+    """s with position k mod len(s) moved on to the next base"""
+    q = k % len(s)
+    return s[:q] + "ACGT"[("ACGT".index(s[q]) + 1) % 4] + s[q + 1:]
+
+
+def _past_one_tile(rng):
+    """the cases whose column slices hold more than one tile of 64 (a slice is 64 wide until the squared bucket sizes pass 64 * 4096 * 64),
+    and those with item indices up to 2^20 - 2"""
+    out = {}
+    for m, md in ((4096, (1, 45)), (4097, M.DEFAULT)):
+        # one bucket of random junctions (none within reach of another at L = 45).  A chain of 131, each one substitution from the
+        # previous, lies at random rows: at 1/45 only neighbours are linked, so one clone exists only if every link across row blocks,
+        # tiles and slices is found.  Exact duplicates: row 0 and the last row (in the 4,097 case the only column of the last slice), and three more.
+        a = rng.integers(0, 4, (m, 45))
+        js = ["".join("ACGT"[x] for x in row) for row in a.tolist()]
+        at = (1 + rng.choice(m - 2, size=131 + 7, replace=False)).tolist()      # neither row 0 nor the last
+        for k in range(1, 131):
+            js[at[k]] = _step(js[at[k - 1]], k)
+        js[m - 1] = js[0]
+        for k in range(3):
+            js[at[131 + 2 * k]] = js[at[132 + 2 * k]]
+        js[at[137]] = js[at[60]]                                                  # (a copy of a member of the chain: linked to it and to its two neighbours)
+        out[f"bucket_{m}"] = (js, [11] * m, md)
+    # eleven buckets (one group each), interleaved: 8 x 1500^2 > 64 * 4096 * 64, so every bucket is cut into slices of 128, the 1,500 into
+    # eleven of them and 92 columns (a full tile and 28), the buckets of 100, 65 and 1 into one that is narrower than a slice
+    js, grp = [], []
+    for g, m in enumerate(SMALL_BUCKETS):
+        fams = []
+        while len(fams) < m:
+            fams += _family(rng, _rand(rng, 45), min(m - len(fams), int(rng.integers(1, 40))))
+        js += fams
+        grp += [g] * m
+    order = rng.permutation(len(js)).tolist()
+    out["slice_128_small_buckets"] = ([js[i] for i in order], [grp[i] for i in order], M.DEFAULT)
+    out["all_equal_1000"] = ([_rand(rng, 45)] * 1000, [0] * 1000, M.DEFAULT)     # every pair a link, every union onto one root
+    # 2^20 - 1 items, 300 of which take part: indices 0 .. 99, 2^19 - 50 .. 2^19 + 49 and 2^20 - 101 .. 2^20 - 2, in two groups; every family
+    # has members in all three ranges (the sort key keeps the index in its low 20 bits)
+    n = (1 << 20) - 1
+    where = list(range(100)) + list(range((1 << 19) - 50, (1 << 19) + 50)) + list(range(n - 100, n))
+    js, grp = [""] * n, [M.NONE] * n
+    members = []
+    for g in (3, 0xFFFFFFFE):
+        for _ in range(5):
+            members += [(g, s) for s in _family(rng, _rand(rng, 45), 30)]
+    for k, member in enumerate(members):                                        # member k goes to range k mod 3
+        i = where[(k % 3) * 100 + k // 3]
+        grp[i], js[i] = member
+    out["n_2_20_minus_1"] = (js, grp, M.DEFAULT)
     return out
 
 
@@ -144,9 +211,10 @@ def _device(_):
     from vdjer_amd._lib import VdjxError
     ctx = api.Context(0)
     kept0, allocs0 = ctx.stat("kept_device_bytes"), ctx.stat("kept_allocs")
-    out = dict(cases={}, perm={}, dispatches={})
+    out = dict(cases={}, perm={}, dispatches={}, work_items={}, raw={})
     for name, (js, grp, md) in cases().items():
         res = ctx.lineage(js, grp, md)
+        out["work_items"][name] = ctx.stat("lineage_work_items")
         again = ctx.lineage(js, grp, md)                                 # two calls give the same bits
         assert again["clone"].tobytes() == res["clone"].tobytes() and again["nearest"].tobytes() == res["nearest"].tobytes() and again["info"] == res["info"], name
         out["cases"][name] = _pack(res)
@@ -196,6 +264,16 @@ def _device(_):
     assert rc == -1 and b"2^20" in L.vdjx_last_error()
     rc = L.vdjx_lineage(h, None, None, None, 0, C.byref(prm), None, None, C.byref(info))      # n = 0 returns at once
     assert rc == 0 and [getattr(info, f) for f in FIELDS] == [0] * 6
+    # offsets that do not start at 0: seven bytes that belong to no item in front
+    js, grp, md = cases()["interleaved"]
+    text = "".join(js).encode()
+    ends = np.cumsum([0] + [len(s) for s in js]).astype(np.uint64)
+    prm = _lib.LineageParams(*md)
+    for first, buf in ((0, text), (7, b"GATTACA" + text)):
+        clone, near, info = np.zeros(len(js), np.int32), np.zeros(len(js), np.int32), _lib.LineageInfo()
+        rc = L.vdjx_lineage(h, buf, api._p(ends + np.uint64(first)), api._p(np.asarray(grp, np.uint32)), len(js), C.byref(prm), api._p(clone), api._p(near), C.byref(info))
+        assert rc == 0, L.vdjx_last_error()
+        out["raw"][str(first)] = _pack(dict(clone=clone, nearest=near, info={f: int(getattr(info, f)) for f in FIELDS}))
     ctx.close()
     return out
 
@@ -287,6 +365,44 @@ def test_lineage_permutation_keeps_the_partition():
         assert dev["info"] == base["info"], name
         js, grp, md = cases()[name]
         _same(dev, M.lineage([js[i] for i in order], [grp[i] for i in order], md), name + " permuted")
+
+
+@pytest.mark.parametrize("name", BIG)
+def test_lineage_past_one_column_tile(name):
+    """slices of more than one tile (the second trip of k_lin_pairs' tile loop, a partial last tile), a bucket that collapses into one root,
+    item indices up to 2^20 - 2.  The work items prove which slice width the call used."""
+    js, grp, md = cases()[name]
+    _same(device()["cases"][name], models()[name], name)
+    clone, near, info = models()[name]
+    sizes = {"bucket_4096": [4096], "bucket_4097": [4097], "slice_128_small_buckets": SMALL_BUCKETS, "all_equal_1000": [1000], "n_2_20_minus_1": [150, 150]}[name]
+    items, width = work_items(sizes)
+    assert device()["work_items"][name] == items, (name, device()["work_items"][name], items, width)
+    if name == "bucket_4096":
+        assert (items, width) == (64 * 64, 64)
+    if name == "bucket_4097":
+        assert (items, width) == (65 * 33, 128) and clone[4096] == clone[0] == 0
+    if name.startswith("bucket_"):
+        m = len(js)
+        assert info["largest_bucket"] == m and info["clones"] == m - 130 - 5 and np.bincount(clone).max() == 132 and (near == -1).sum() == 0
+        assert info["links"] == 130 + 1 + 3 + 3 if md == (1, 45) else info["links"] > 137
+    if name == "slice_128_small_buckets":
+        assert width == 128 and items == 8 * 24 * 12 + 2 + 2 + 1 and info["buckets"] == 11 and info["largest_bucket"] == 1500
+        assert sorted(np.bincount(np.asarray(grp)).tolist()) == sorted(SMALL_BUCKETS)
+    if name == "all_equal_1000":
+        assert clone.tolist() == [0] * 1000 and near.tolist() == [-1] * 1000 and info["links"] == 499500 == info["pairs"] and info["clones"] == 1
+    if name == "n_2_20_minus_1":
+        n = (1 << 20) - 1
+        assert len(js) == n and info["items"] == 300 and info["buckets"] == 2 and (clone >= 0).sum() == 300
+        for members in M.partition(clone):                               # the families reach across the three index ranges
+            if len(members) >= 20:
+                assert min(members) < 100 and max(members) >= n - 100 and any(abs(i - (1 << 19)) <= 50 for i in members)
+        assert sum(len(s) >= 20 for s in M.partition(clone)) >= 6
+
+
+def test_lineage_raw_call_with_offsets_that_start_past_zero():
+    raw = device()["raw"]
+    assert raw["7"] == raw["0"]
+    _same(raw["7"], models()["interleaved"], "off[0] = 7")
 
 
 def test_lineage_dispatches_do_not_depend_on_the_input():

@@ -458,6 +458,41 @@ typedef struct { uint32_t items, buckets, largest_bucket, clones; uint64_t pairs
 int vdjx_lineage(vdjx_ctx* ctx, const char* junctions, const uint64_t* off, const uint32_t* group, size_t n,
                  const vdjx_lineage_params* params, int32_t* out_clone, int32_t* out_nearest, vdjx_lineage_info* info);
 
+/* ---- lineage trees: the minimum spanning tree of every clone under the Hamming distance of its members' common window -------------------
+ * gives `vdjer --trees` what a repertoire user looks at inside a lineage (alakazam / dowser / Change-O BuildTrees): which member is
+ * closest to the germline, who descends from whom, how many mutations apart.  All pairs of a clone are compared on the device, over the
+ * whole window and not the junction alone.  All arithmetic is integer: the device's results are bitwise the model's (tests/tree_model.py).
+ *   items       contig i is contigs[i*len .. (i+1)*len).  clone[i] is any key >= 0 (typically out_clone of the lineage call above); an
+ *               item with clone[i] = -1 takes no part: out_parent = out_dist = out_depth = -1.  The members of a clone may lie anywhere
+ *               in the input: nothing has to be sorted.
+ *   window      anchor[i] in 0 .. len: where the junction starts in contig i.  The members of a clone are compared over their common
+ *               window around the anchor: with a = min anchor and b = min (len - anchor) over the clone's members, contig i contributes
+ *               contig_i[anchor[i] - a .. anchor[i] + b), w = a + b bases.  The shift between two members is arbitrary.
+ *   distance    d(i, j) of two members of one clone: the number of window positions at which the characters differ or either is not
+ *               one of ACGT: the rule of the lineage call (N never matches, not even N; lower case is not ACGT).
+ *   tree        the minimum spanning tree of the complete graph on a clone's members under the strict order of the keys
+ *               (d(i, j), min(i, j), max(i, j)), the indices the caller's.  The order is total: the tree is unique, and Boruvka's
+ *               rounds (every component takes the smallest edge that leaves it) cannot close a cycle.
+ *   root        the member with the smallest (prio[i], i); prio = NULL: the smallest index.  out_parent[i] is the next item on the tree
+ *               path to the root (-1 for the root), out_dist[i] = d(i, parent) (-1 for the root), out_depth[i] the edges to the root.
+ *   info        (may be NULL; zeroed first, every field filled on success) members: participating items; clones; largest_clone: the
+ *               members of the largest; edges = members - clones; weight: the sum of every out_dist >= 0; rounds = ceil(log2
+ *               largest_clone), the Boruvka passes launched: 0 when no clone has two members.
+ * NOT modelled: alignment of members that differ by an indel (the comparison is column by column); inferred intermediate nodes, maximum
+ * parsimony or likelihood; Newick output; a germline sequence as a node of its own: the root is an observed contig.
+ * VDJX_EINVAL: n >= 2^20, len < 1 or len >= 4096, contigs of unequal length (a NUL inside the n*len characters), clone[i] < -1, a member's
+ * anchor outside 0 .. len, an empty window (w = 0: a member anchored at 0 and one at len), NULL out_parent / out_dist / out_depth.  n = 0
+ * returns at once with a zeroed info.  The (clone, index) keys are sorted on the host (per item), which also computes the windows;
+ * everything per pair runs on the device: a call is 1 + 3 * rounds kernel dispatches (pack; per round min, hook, flat) whatever n and the
+ * number of clones are, and nothing is read back between the rounds.  The edges come back once; orienting them toward the roots and
+ * counting the depths is O(n) on the host.  Scratch comes from the context's workspace; no floating point.  Integer atomics are a
+ * minimum per component, the union-find of the lineage call and the slot of an appended edge, none of which the outputs depend on the
+ * order of: two calls give the same bits.  Stats: "tree_work_items" ((clone, row block, column slice) items of a round), "tree_rounds",
+ * "tree_us" (host clock). */
+typedef struct { uint32_t members, clones, largest_clone, rounds; uint64_t edges, weight; } vdjx_tree_info;   /* 32 bytes */
+int vdjx_tree(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const int32_t* clone, const int32_t* anchor, const uint32_t* prio,
+              int32_t* out_parent, int32_t* out_dist, int32_t* out_depth, vdjx_tree_info* info);
+
 /* rows of `row` bytes on the device: row d_pos[i] of d_dst = row i of d_src.  (The records of a pool sharded by pair on their way to
  * the ranks that hold their slice of the scan order for the k-mer build, A2:1388-1390: every record arrives with its place.) */
 int vdjx_rows_scatter(vdjx_ctx* ctx, void* d_dst, const void* d_src, const uint32_t* d_pos, size_t n, size_t row);

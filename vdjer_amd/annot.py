@@ -136,3 +136,19 @@ def lineage_inputs(ids, contigs, v, j, names):
         vgene.append(vg)
         jgene.append(jg)
     return junctions, group, vgene, jgene
+
+
+def tree_inputs(ids, contigs, v, clone):
+    """what `vdjer --trees` hands to vdjx_tree besides the contigs and the clones of the lineage step, from the V hits ({field: array} as
+    Context.annotate returns them) -> (anchor int32[n], prio uint32[n]).  For a contig with clone >= 0 the anchor is where its junction
+    starts (junction_of) and the priority its V hit's mismatches + ins + del: the member closest to its germline V becomes the root.
+    Every other contig gets anchor 0 and priority 0."""
+    import numpy as np
+    n = len(ids)
+    anchor, prio = np.zeros(n, np.int32), np.zeros(n, np.uint32)
+    for c in range(n):
+        if int(clone[c]) < 0:
+            continue
+        anchor[c] = junction_of(ids[c], contigs[c])[0]
+        prio[c] = int(v["mismatches"][c]) + int(v["ins"][c]) + int(v["del"][c])
+    return anchor, prio

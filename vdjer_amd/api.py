@@ -746,6 +746,29 @@ class Context:
         return {"clone": clone, "nearest": near,
                 "info": {f: int(getattr(info, f)) for f in ("items", "buckets", "largest_bucket", "clones", "pairs", "links")}}
 
+    TREE_FIELDS = ("members", "clones", "largest_clone", "rounds", "edges", "weight")
+
+    def tree(self, contigs, clone, anchor, prio=None):
+        """vdjx_tree: the minimum spanning tree of every clone under the Hamming distance over the members' common window around their
+        anchors, rooted at the member of smallest (prio, index).  contigs: equally long strings (or pack_strings' tuple); clone: int32[n],
+        -1 for an item that takes no part; anchor: int32[n], 0 .. len; prio: uint32[n] or None -> {"parent", "dist", "depth": int32[n]
+        (-1: no part; parent and dist -1 for a root), "info": dict(members, clones, largest_clone, rounds, edges, weight)}"""
+        if isinstance(contigs, tuple):
+            raw, n, ln = contigs
+        else:
+            if len({len(s_) for s_ in contigs}) > 1:
+                raise VdjxError("vdjx_tree: contigs of unequal length")
+            raw, n, ln = self.pack_strings(contigs)
+        cl = np.ascontiguousarray(clone, np.int32)
+        an = np.ascontiguousarray(anchor, np.int32)
+        pr = None if prio is None else np.ascontiguousarray(prio, np.uint32)
+        if cl.shape != (n,) or an.shape != (n,) or (pr is not None and pr.shape != (n,)):
+            raise VdjxError(f"vdjx_tree: {n} contigs, clone of shape {cl.shape}, anchor of shape {an.shape}")
+        parent, dist, depth = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        info = _lib.TreeInfo()
+        check(self.L.vdjx_tree(self.h, raw, n, ln, _p(cl), _p(an), _p(pr), _p(parent), _p(dist), _p(depth), C.byref(info)), "vdjx_tree")
+        return {"parent": parent, "dist": dist, "depth": depth, "info": {f: int(getattr(info, f)) for f in self.TREE_FIELDS}}
+
     def stat(self, name: str) -> int:
         return int(self.L.vdjx_stat(self.h, name.encode()))
 

@@ -5,7 +5,7 @@
  *   vdjer --in <reads> --chain IGH|IGK|IGL --ref-dir <dir> --ins <n> [--t --k --mf --mq --mcs --am --miw --maw
  *         --jc --ws -jext --rf --vk --mrs --rs --ms --e0 --e1 --wo --vf --jf --rms] [--gpus N] [--quant <file>] [--airr <file>]
  *         [--d-calls] [--cfa <fasta>] [--isotypes <file>] [--clones <file>] [--sample <name>] [--total-count <n>]
- *         [--lineages <file>] [--lineage-dist <x>]
+ *         [--lineages <file>] [--lineage-dist <x>] [--trees <file>]
  * writes ./vdj_contigs.fa and ./vdjer.dot, SAM on stdout, log on stderr; exit 0 on success.  --quant <file>: the contigs' abundances
  * (vdjx_quant, RSEM's isoforms.results columns) into <file> as well.  --airr <file>: the contigs' V/J annotation (vdjx_annotate against
  * the germlines of ig_vdj.fa / --vdjf) as an AIRR Rearrangement TSV; with --d-calls (a flag: no value) the D gene between the V and the
@@ -13,7 +13,9 @@
  * isotype call of every contig against them (vdjx_isotype); --clones <file>: the per-sample table of the reference's post_process/
  * (collect_vdjer_stats.py | cluster_results.py) from the three device steps (one GPU only).  --lineages <file>: the contigs grouped into
  * clonal lineages (vdjx_lineage: single linkage on the junctions' Hamming distance inside a V gene / J gene / junction length bucket,
- * linked up to --lineage-dist, default 0.15 of the length); with --airr the table gets a clone_id column.
+ * linked up to --lineage-dist, default 0.15 of the length); with --airr the table gets a clone_id column.  --trees <file> (with --lineages):
+ * the tree inside every lineage (vdjx_tree: the minimum spanning tree under the Hamming distance over the members' common window around
+ * the junction, rooted at the member closest to its germline V).
  *
  * --in: a BAM with its .bai (extraction as bam_read.c:264-446, restated over zlib in bamx.c), or -- recognised by its
  * content -- the extracted read pool as text, one read per line in extraction order:
@@ -61,6 +63,7 @@ typedef struct {
 	const char* lineages;                  /* --lineages <file> (not in the reference): Change-O DefineClones' grouping of the contigs, on the device */
 	const char* lineage_dist;              /* --lineage-dist <x>: its threshold, a decimal read exactly into lin_num / lin_den (default 1500 / 10000) */
 	int lin_num, lin_den;
+	const char* trees;                     /* --trees <file> (not in the reference): the tree inside every lineage of --lineages, on the device */
 	int have_chain, have_ref;
 } cli;
 
@@ -83,7 +86,8 @@ static void usage(void) {
 	                "\t--sample <name in the clone table (default: the input's base name up to its first '.')>\n"
 	                "\t--total-count <whole number for the clone table's total_count column (default: N/A)>\n"
 	                "\t--lineages <file: clonal lineages of the contigs, single linkage on the junctions inside a V gene / J gene / length bucket>\n"
-	                "\t--lineage-dist <largest linked distance as a fraction of the junction length, in [0,1], at most 4 decimals (default: 0.15)>\n");
+	                "\t--lineage-dist <largest linked distance as a fraction of the junction length, in [0,1], at most 4 decimals (default: 0.15)>\n"
+	                "\t--trees <file: with --lineages, the minimum spanning tree inside every lineage: parent, distance and depth of every contig>\n");
 }
 
 static int file_exists(const char* f) { struct stat b; return stat(f, &b) == 0; }
@@ -142,6 +146,7 @@ static int parse(int argc, char** argv, cli* c) {
 		else if (!strcmp(a, "--total-count")) c->total_count = v;
 		else if (!strcmp(a, "--lineages")) c->lineages = v;
 		else if (!strcmp(a, "--lineage-dist")) c->lineage_dist = v;
+		else if (!strcmp(a, "--trees")) c->trees = v;
 		else if (!strcmp(a, "--vf")) snprintf(c->v_anchors, sizeof c->v_anchors, "%s", v);
 		else if (!strcmp(a, "--jf")) snprintf(c->j_anchors, sizeof c->j_anchors, "%s", v);
 		else if (!strcmp(a, "--am")) c->anchor_mismatches = atoi(v);
@@ -196,6 +201,7 @@ static int parse(int argc, char** argv, cli* c) {
 		fprintf(stderr, "--lineage-dist must be a decimal in [0, 1] with at most four digits after the point: %s\n", c->lineage_dist);
 		ok = 0;
 	}
+	if (c->trees && !c->lineages) { fprintf(stderr, "--trees writes the tree inside every lineage of the --lineages table: it needs --lineages <file>\n"); ok = 0; }
 	if (!ok) { usage(); return -1; }
 	if (c->hp.min_base_quality >= 255) c->hp.min_base_quality = 254;      /* A2:1514-1516 */
 	return 0;
@@ -544,6 +550,8 @@ typedef struct {
 	const char* lineages; int lin_num, lin_den, lin_done;
 	int32_t* lin_clone; vdjx_lineage_info li;
 	size_t l_contigs, l_eligible;
+	/* --trees: the tree inside every lineage (tree_run, after lineage_run) */
+	const char* trees; vdjx_tree_info ti;
 } hook_ud;
 
 static int h_root_score(void* ud, const char* kmers, size_t n, int k, int thr, uint8_t* out) {
@@ -1090,6 +1098,53 @@ static int lineage_run(hook_ud* u, const char* const* ids, const char* contigs, 
 	return rc;
 }
 
+/* --trees: the tree inside every lineage (the model: include/vdjx.h, vdjx_tree; the inputs: tree_inputs of vdjer_amd/annot.py).  The clones
+ * are lineage_run's; a member's anchor is where its junction starts and its priority its V hit's mismatches + ins + del, so the member closest
+ * to its germline V is the root.  A row per contig: clone_id lin_<k>, parent_id, dist_parent (both empty for a root), depth, children,
+ * v_mutations, window_start (0-based, in this contig) and window_length of the lineage's common window; only sequence_id for a contig
+ * that is in no lineage */
+static int tree_run(hook_ud* u, const char* const* ids, const char* contigs, size_t n, int len) {
+	FILE* fp = fopen(u->trees, "w");
+	if (!fp) { fprintf(stderr, "cannot write %s\n", u->trees); return -1; }
+	fputs("sequence_id\tclone_id\tparent_id\tdist_parent\tdepth\tchildren\tv_mutations\twindow_start\twindow_length\n", fp);
+	int32_t* anchor = (int32_t*) calloc(n + 1, sizeof(int32_t));
+	uint32_t* prio = (uint32_t*) calloc(n + 1, sizeof(uint32_t));
+	int32_t* out = (int32_t*) calloc(3 * n + 1, sizeof(int32_t));
+	int32_t *parent = out, *dist = out + n, *depth = out + 2 * n;
+	const size_t nk = (size_t) u->li.clones + 1;
+	int32_t* before = (int32_t*) malloc(nk * sizeof(int32_t));       /* per lineage: the window's bases before the anchor, and from it on */
+	int32_t* after = (int32_t*) malloc(nk * sizeof(int32_t));
+	size_t* kids = (size_t*) calloc(n + 1, sizeof(size_t));
+	for (size_t k = 0; k < nk; k++) before[k] = after[k] = len;
+	for (size_t i = 0; i < n; i++) {
+		const int32_t k = u->lin_clone[i];
+		if (k < 0) continue;
+		const vdjx_annot_hit* v = u->hv + i;
+		const char* jn;
+		size_t jl;
+		anchor[i] = (int32_t) junction_at(ids[i], contigs + i * (size_t) len, len, &jn, &jl);
+		prio[i] = (uint32_t) (v->mismatches + v->ins + v->del);
+		if (anchor[i] < before[k]) before[k] = anchor[i];
+		if (len - anchor[i] < after[k]) after[k] = len - anchor[i];
+	}
+	int rc = vdjx_tree(u->gx, contigs, n, len, u->lin_clone, anchor, prio, parent, dist, depth, &u->ti);
+	if (rc) fprintf(stderr, "--trees: %s\n", vdjx_last_error());
+	if (!rc) {
+		for (size_t i = 0; i < n; i++)
+			if (parent[i] >= 0) kids[parent[i]]++;
+		for (size_t i = 0; i < n; i++) {
+			const int32_t k = u->lin_clone[i];
+			if (k < 0) { fprintf(fp, "%s\t\t\t\t\t\t\t\t\n", ids[i]); continue; }
+			fprintf(fp, "%s\tlin_%d\t", ids[i], k + 1);
+			if (parent[i] >= 0) fprintf(fp, "%s\t%d", ids[parent[i]], dist[i]); else fputc('\t', fp);
+			fprintf(fp, "\t%d\t%zu\t%u\t%d\t%d\n", depth[i], kids[i], prio[i], anchor[i] - before[k], before[k] + after[k]);
+		}
+	}
+	free(anchor); free(prio); free(out); free(before); free(after); free(kids);
+	if (fclose(fp)) { fprintf(stderr, "cannot write %s\n", u->trees); return -1; }
+	return rc;
+}
+
 /* the tables after the SAM body: every device step runs once, whichever tables ask for it */
 static int tables(hook_ud* u, const char* const* ids, const char* contigs, size_t n, int len) {
 	int rc = 0;
@@ -1097,6 +1152,7 @@ static int tables(hook_ud* u, const char* const* ids, const char* contigs, size_
 	if (!rc && (u->airr || u->clones || u->lineages)) rc = annot_run(u, contigs, n, len);
 	if (!rc && u->d_calls) rc = dcall_run(u, contigs, n, len);
 	if (!rc && u->lineages) rc = lineage_run(u, ids, contigs, n, len);
+	if (!rc && u->trees) rc = tree_run(u, ids, contigs, n, len);
 	if (!rc && u->airr) rc = airr_table(u, ids, contigs, n, len);
 	if (!rc && u->cfa && (u->isotypes || u->clones)) rc = iso_run(u, contigs, n, len);
 	if (!rc && u->isotypes) rc = isotypes_table(u, ids, n, len);
@@ -1373,7 +1429,7 @@ int main(int argc, char** argv) {
 	memset(&ud, 0, sizeof ud);
 	ud.gx = gx; ud.p = &c.hp; ud.mg = mg; ud.quant = c.quant; ud.airr = c.airr; ud.vdjf = c.vdj_fasta; ud.d_calls = c.d_calls;
 	ud.cfa = c.cfa; ud.isotypes = c.isotypes; ud.clones = c.clones; ud.total_count = c.total_count;
-	ud.lineages = c.lineages; ud.lin_num = c.lin_num; ud.lin_den = c.lin_den;
+	ud.lineages = c.lineages; ud.lin_num = c.lin_num; ud.lin_den = c.lin_den; ud.trees = c.trees;
 	char sample_buf[4096];
 	if (c.sample) ud.sample = c.sample;
 	else {                                  /* the input's base name up to its first '.' */
@@ -1428,6 +1484,9 @@ int main(int argc, char** argv) {
 	if (c.lineages)
 		fprintf(stderr, "lineages: %zu contigs, %zu eligible, %u buckets (largest %u), %llu pairs, %llu links, %u lineages at %d/%d\n", ud.l_contigs, ud.l_eligible,
 		        ud.li.buckets, ud.li.largest_bucket, (unsigned long long) ud.li.pairs, (unsigned long long) ud.li.links, ud.li.clones, c.lin_num, c.lin_den);
+	if (c.trees)
+		fprintf(stderr, "trees: %u contigs in %u lineages (largest %u), %llu edges, total distance %llu, %u rounds\n", ud.ti.members, ud.ti.clones, ud.ti.largest_clone,
+		        (unsigned long long) ud.ti.edges, (unsigned long long) ud.ti.weight, ud.ti.rounds);
 	if (c.isotypes)
 		fprintf(stderr, "isotypes: %zu contigs, %zu called against %zu constant records of %s; table in %s\n", ud.i_contigs, ud.i_called,
 		        ud.cst ? ud.cst->n : (size_t) 0, c.cfa, c.isotypes);

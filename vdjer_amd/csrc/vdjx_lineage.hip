@@ -15,7 +15,7 @@
 //                  so it is one v_lshl_or_b32 per half -- ten integer instructions per word and lane)
 //                  the lane keeps the smallest d > 0 (atomicMin per row at the end: the column slices of a row meet there) and, for the
 //                  pairs with column > row and d <= floor(num L / den), counts the link and unites the two items
-//   union-find     parent[] over the caller's item indices, lock-free: find with path halving (atomicMin: a parent only ever gets
+//   union-find     (vdjx_unionfind.h) parent[] over the caller's item indices, lock-free: find with path halving (atomicMin: a parent only ever gets
 //                  smaller), union by atomicCAS on the LARGER root, which is hooked under the smaller.  parent[x] <= x always holds, so
 //                  the trees stay trees and the root of a finished component is its smallest member whatever the interleaving was.
 //   k_lin_flatten  every item's root; a flag per root, in item order
@@ -24,6 +24,7 @@
 // No floating point.  Scratch comes from the context's workspace.
 #include "vdjx_common.h"
 #include "vdjx_scan.h"
+#include "vdjx_unionfind.h"
 
 #include <algorithm>
 #include <string.h>
@@ -55,32 +56,6 @@ __global__ __launch_bounds__(256) void k_lin_pack(const char* __restrict__ junc,
 	}
 	out[(size_t) r * LIN_ROW_WORDS + w] = make_ulonglong2(x, m);
 	if (w == 0) { row_item[r] = q.item; parent[q.item] = q.item; }
-}
-
-// a word another wave may be changing: read past this CU's L1
-__device__ inline u32 lin_peek(const u32* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ inline u32 lin_find(u32* parent, u32 x) {
-	for (;;) {
-		const u32 p = lin_peek(parent + x);
-		if (p == x) return x;
-		const u32 g = lin_peek(parent + p);
-		if (g != p) atomicMin(parent + x, g);          // (path halving; g is an ancestor of x and smaller than p)
-		x = g;
-	}
-}
-
-__device__ inline void lin_unite(u32* parent, u32 a, u32 b) {
-	for (;;) {
-		a = lin_find(parent, a);
-		b = lin_find(parent, b);
-		if (a == b) return;
-		const u32 hi = a > b ? a : b, lo = a > b ? b : a;
-		const u32 old = atomicCAS(parent + hi, hi, lo);
-		if (old == hi) return;                          // hooked (lo may have stopped being a root meanwhile: it is a member all the same)
-		a = old;                                        // somebody else hooked hi first: go on from where it hangs now
-		b = lo;
-	}
 }
 
 template <int W>

@@ -1,0 +1,393 @@
+// vdjx_tree.hip -- lineage trees: the minimum spanning tree of every clone under the Hamming distance of its members' common window
+// (gfx950 only, wave64).
+//
+//   vdjx_tree   the members of a clone are compared all against all over the window around their anchors; Boruvka's rounds pick, per
+//               component, the smallest edge that leaves it (the model: include/vdjx.h; in Python: tests/tree_model.py)
+//
+// The host sorts the (clone, index) keys -- per item --, computes each clone's window and lays the members out in clone order ("rows").
+// Inside a clone the rows are in index order, so the order of two rows is the order of the caller's indices: the edge keys carry ROW
+// numbers and compare as the model's (d, min(i, j), max(i, j)) do.  Per pair everything happens on the device, in 1 + 3 * rounds
+// dispatches, rounds = ceil(log2(largest clone)), whatever n and the number of clones are; nothing is read back between the rounds:
+//   k_tree_pack   a row = `words` pairs of 64-bit words {bases, mask} in k_lin_pack's encoding (vdjx_lineage.hip): 32 bases per word, 2 bits
+//                 each (A0 T1 C2 G3), the mask with the upper bit of a base's two set where it is not ACGT, bits past the window 0.  The
+//                 window is cut out of the contig at the member's own offset, character by character: any shift.  comp[r] = parent[r] = r.
+//   k_tree_min    one wave per work item (row block of 64 rows, column slice of the same clone).  Up to 16 words (512 bases) a lane keeps
+//                 its row in registers and the columns go through LDS in tiles, read back as one 16-byte broadcast per word, d as in
+//                 k_lin_pairs; wider windows walk the words in chunks of 16 against tiles of 8 columns, a running d per column.  Against
+//                 every column of another component the lane forms d << 40 | lo << 20 | hi and keeps the smallest; one atomicMin per
+//                 lane on best[comp[row]] at the end (a minimum: the order it lands in does not matter).
+//   k_tree_hook   per component with a best edge: the edge is appended (once: where both ends chose it, the smaller root does) and
+//                 its two ends are united in parent[] (vdjx_unionfind.h: the larger root goes under the smaller).  comp[] -- the
+//                 components this round began with -- is only read.
+//   k_tree_flat   comp[r] = the root of r in parent[]; best[r] = none.
+// The keys are distinct, so the chosen edges never close a cycle and the components at least halve per round.  The edges (members -
+// clones) come back once, in whatever order the appends landed; the host orients them toward each clone's root and counts the depths,
+// O(n), which does not depend on that order.  No floating point.  Scratch comes from the context's workspace.
+#include "vdjx_common.h"
+#include "vdjx_unionfind.h"
+
+#include <algorithm>
+#include <string.h>
+
+#define TREE_NONE 0xFFFFFFFFFFFFFFFFull
+#define TREE_TARGET_ITEMS 4096u          // work items aimed at: 4 waves on each of the 1,024 SIMDs
+#define TREE_ROWS 64u                    // rows per work item: one per lane
+#define TREE_REG_WORDS 16                // a row of up to 16 words (512 bases) stays in registers
+#define TREE_LDS 512u                    // {bases, mask} pairs of a tile: 8 KiB, 64 columns of up to 8 words or 32 of up to 16
+#define TREE_CH_COLS 8                   // the chunked path: columns per tile, each with a running distance in a register
+#define TREE_MA 0xAAAAAAAAu               // the upper bit of every base's two
+
+struct TreeRow { u64 at; u32 wbase, w; };                                      // where the window's characters start; the row's first word; bases
+struct TreeItem { u32 row0, row_end, col0, col_end, words, first, wbase, pad; };   // rows [row0, row_end) (at most 64) against columns [col0, col_end)
+                                                                                // of the clone whose first row is `first` and first word `wbase`
+static_assert(sizeof(TreeRow) == 16 && sizeof(TreeItem) == 32, "uploaded as they are");
+
+// one thread per {bases, mask} pair; ri[rows] is a sentinel whose wbase is the number of pairs
+__global__ __launch_bounds__(256) void k_tree_pack(const char* __restrict__ contigs, const TreeRow* __restrict__ ri, u32 rows, u32 total,
+                                                   ulonglong2* __restrict__ out, u32* __restrict__ comp, u32* __restrict__ parent,
+                                                   unsigned long long* __restrict__ best) {
+	const u32 t = blockIdx.x * 256u + threadIdx.x;
+	if (t >= total) return;
+	u32 lo = 0, hi = rows;                              // the row r with ri[r].wbase <= t < ri[r + 1].wbase
+	while (hi - lo > 1u) {
+		const u32 mid = (lo + hi) / 2u;
+		if (ri[mid].wbase <= t) lo = mid; else hi = mid;
+	}
+	const TreeRow q = ri[lo];
+	const u32 w = t - q.wbase;
+	u64 x = 0, m = 0;
+	for (u32 k = 0; k < 32u; k++) {
+		const u32 pos = w * 32u + k;
+		if (pos >= q.w) break;
+		const char ch = contigs[q.at + pos];
+		const u32 code = ch == 'A' ? 0u : ch == 'T' ? 1u : ch == 'C' ? 2u : ch == 'G' ? 3u : 4u;
+		if (code < 4u) x |= (u64) code << (2u * k);
+		else m |= 2ull << (2u * k);
+	}
+	out[t] = make_ulonglong2(x, m);
+	if (w == 0) { comp[lo] = lo; parent[lo] = lo; best[lo] = TREE_NONE; }
+}
+
+__device__ inline u32 tree_word(const u64 x, const u64 m, const ulonglong2 q) {
+	const u64 t = x ^ q.x, mm = m | q.y;
+	const u32 lo = (u32) t, hi = (u32) (t >> 32);
+	return (u32) __popc(((lo | (lo << 1)) & TREE_MA) | (u32) mm) + (u32) __popc(((hi | (hi << 1)) & TREE_MA) | (u32) (mm >> 32));
+}
+
+__device__ inline u64 tree_key(u32 d, u32 a, u32 b) { return (u64) d << 40 | (u64) (a < b ? a : b) << 20 | (u64) (a < b ? b : a); }
+
+// the register path: W words per row, tiles of TREE_LDS / W columns (a power of two of them)
+template <int W>
+__device__ inline void tree_item(const TreeItem it, const ulonglong2* __restrict__ words, const u32* __restrict__ comp, unsigned long long* best,
+                                 ulonglong2* tile, u32* tile_comp) {
+	constexpr u32 TC = W <= 8 ? 64u : 32u;
+	const u32 lane = threadIdx.x, myrow = it.row0 + lane;
+	const bool live = myrow < it.row_end;
+	const u32 r = live ? myrow : it.row0;
+	const ulonglong2* cw = words + it.wbase;             // the clone's rows, W pairs each
+	u64 x[W], m[W];
+#pragma unroll
+	for (int w = 0; w < W; w++) {
+		const ulonglong2 q = cw[(size_t) (r - it.first) * W + w];
+		x[w] = q.x;
+		m[w] = q.y;
+	}
+	const u32 mine = comp[r];
+	u64 bk = TREE_NONE;
+	for (u32 base = it.col0; base < it.col_end; base += TC) {
+		const u32 nc = min(TC, it.col_end - base);
+		const ulonglong2* src = cw + (size_t) (base - it.first) * W;      // (the tile's columns are contiguous)
+		for (u32 i = lane; i < nc * (u32) W; i += 64u) tile[i] = src[i];
+		if (lane < nc) tile_comp[lane] = comp[base + lane];
+		__syncthreads();
+		for (u32 c = 0; c < nc; c++) {
+			const bool other = live && tile_comp[c] != mine;
+			if (!__any(other)) continue;                   // (wave-uniform: a column of every lane's own component)
+			u32 d = 0;
+#pragma unroll
+			for (int w = 0; w < W; w++) d += tree_word(x[w], m[w], tile[c * (u32) W + w]);   // (every lane the same address: one broadcast read of 16 bytes)
+			if (other) {
+				const u64 k = tree_key(d, myrow, base + c);
+				bk = k < bk ? k : bk;
+			}
+		}
+		__syncthreads();
+	}
+	if (live && bk != TREE_NONE) atomicMin(best + mine, (unsigned long long) bk);
+}
+
+// the chunked path: any number of words.  Per tile of 8 columns the words go by in chunks of 16: the lane's chunk in registers, the
+// columns' in LDS, a running distance per column.  Words past the row's end count as 0 on both sides.
+__device__ inline void tree_item_wide(const TreeItem it, const ulonglong2* __restrict__ words, const u32* __restrict__ comp, unsigned long long* best,
+                                      ulonglong2* tile, u32* tile_comp) {
+	const u32 lane = threadIdx.x, myrow = it.row0 + lane, W = it.words;
+	const bool live = myrow < it.row_end;
+	const u32 r = live ? myrow : it.row0;
+	const ulonglong2* cw = words + it.wbase;
+	const ulonglong2* mw = cw + (size_t) (r - it.first) * W;
+	const u32 mine = comp[r];
+	u64 bk = TREE_NONE;
+	for (u32 base = it.col0; base < it.col_end; base += TREE_CH_COLS) {
+		const u32 nc = min((u32) TREE_CH_COLS, it.col_end - base);
+		u32 d[TREE_CH_COLS];
+#pragma unroll
+		for (int c = 0; c < TREE_CH_COLS; c++) d[c] = 0;
+		if (lane < nc) tile_comp[lane] = comp[base + lane];
+		for (u32 w0 = 0; w0 < W; w0 += TREE_REG_WORDS) {
+			u64 x[TREE_REG_WORDS], m[TREE_REG_WORDS];
+#pragma unroll
+			for (int w = 0; w < TREE_REG_WORDS; w++) {
+				const ulonglong2 q = w0 + (u32) w < W ? mw[w0 + (u32) w] : make_ulonglong2(0, 0);
+				x[w] = q.x;
+				m[w] = q.y;
+			}
+			for (u32 i = lane; i < TREE_CH_COLS * TREE_REG_WORDS; i += 64u) {
+				const u32 c = i / TREE_REG_WORDS, w = w0 + i % TREE_REG_WORDS;
+				tile[i] = c < nc && w < W ? cw[(size_t) (base + c - it.first) * W + w] : make_ulonglong2(0, 0);
+			}
+			__syncthreads();
+#pragma unroll
+			for (int c = 0; c < TREE_CH_COLS; c++)
+#pragma unroll
+				for (int w = 0; w < TREE_REG_WORDS; w++) d[c] += tree_word(x[w], m[w], tile[c * TREE_REG_WORDS + w]);
+			__syncthreads();
+		}
+#pragma unroll
+		for (int c = 0; c < TREE_CH_COLS; c++)
+			if ((u32) c < nc && live && tile_comp[c] != mine) {
+				const u64 k = tree_key(d[c], myrow, base + (u32) c);
+				bk = k < bk ? k : bk;
+			}
+		__syncthreads();                                    // (tile_comp is written again at the top)
+	}
+	if (live && bk != TREE_NONE) atomicMin(best + mine, (unsigned long long) bk);
+}
+
+// one wave per work item; the word count is the clone's, so it is uniform and every loop over words is unrolled
+__global__ __launch_bounds__(64) void k_tree_min(const TreeItem* __restrict__ items, const ulonglong2* __restrict__ words, const u32* __restrict__ comp,
+                                                 unsigned long long* best) {
+	__shared__ ulonglong2 tile[TREE_LDS];
+	__shared__ u32 tile_comp[64];
+	const TreeItem it = items[blockIdx.x];
+	switch (it.words) {
+		case 1: tree_item<1>(it, words, comp, best, tile, tile_comp); break;
+		case 2: tree_item<2>(it, words, comp, best, tile, tile_comp); break;
+		case 3: tree_item<3>(it, words, comp, best, tile, tile_comp); break;
+		case 4: tree_item<4>(it, words, comp, best, tile, tile_comp); break;
+		case 5: tree_item<5>(it, words, comp, best, tile, tile_comp); break;
+		case 6: tree_item<6>(it, words, comp, best, tile, tile_comp); break;
+		case 7: tree_item<7>(it, words, comp, best, tile, tile_comp); break;
+		case 8: tree_item<8>(it, words, comp, best, tile, tile_comp); break;
+		case 9: tree_item<9>(it, words, comp, best, tile, tile_comp); break;
+		case 10: tree_item<10>(it, words, comp, best, tile, tile_comp); break;
+		case 11: tree_item<11>(it, words, comp, best, tile, tile_comp); break;
+		case 12: tree_item<12>(it, words, comp, best, tile, tile_comp); break;
+		case 13: tree_item<13>(it, words, comp, best, tile, tile_comp); break;
+		case 14: tree_item<14>(it, words, comp, best, tile, tile_comp); break;
+		case 15: tree_item<15>(it, words, comp, best, tile, tile_comp); break;
+		case 16: tree_item<16>(it, words, comp, best, tile, tile_comp); break;
+		default: tree_item_wide(it, words, comp, best, tile, tile_comp); break;
+	}
+}
+
+// one thread per row; only the roots of the round's components act
+__global__ __launch_bounds__(256) void k_tree_hook(const u32* __restrict__ comp, const unsigned long long* __restrict__ best, u32 rows, u32* parent,
+                                                   unsigned long long* __restrict__ edges, u32 cap, u32* n_edges) {
+	const u32 r = blockIdx.x * 256u + threadIdx.x;
+	if (r >= rows || comp[r] != r) return;
+	const u64 k = best[r];
+	if (k == TREE_NONE) return;
+	const u32 lo = (u32) (k >> 20) & 0xFFFFFu, hi = (u32) k & 0xFFFFFu;
+	if (lo >= rows || hi >= rows) return;                 // (cannot be: k_tree_min made the key of two rows)
+	const u32 ca = comp[lo], cb = comp[hi], other = ca == r ? cb : ca;
+	if (best[other] == k && other < r) return;            // both ends chose this edge: the smaller root appends and unites
+	const u32 slot = atomicAdd(n_edges, 1u);
+	if (slot < cap) edges[slot] = k;
+	lin_unite(parent, lo, hi);
+}
+
+__global__ __launch_bounds__(256) void k_tree_flat(const u32* __restrict__ parent, u32 rows, u32* __restrict__ comp, unsigned long long* __restrict__ best) {
+	const u32 r = blockIdx.x * 256u + threadIdx.x;
+	if (r >= rows) return;
+	u32 x = parent[r];
+	for (u32 p = parent[x]; p != x; p = parent[x]) x = p;
+	comp[r] = x;
+	best[r] = TREE_NONE;
+}
+
+extern "C" int vdjx_tree(vdjx_ctx* c, const char* contigs, size_t n, int len, const int32_t* clone, const int32_t* anchor, const uint32_t* prio,
+                         int32_t* out_parent, int32_t* out_dist, int32_t* out_depth, vdjx_tree_info* info) {
+	if (info) memset(info, 0, sizeof *info);
+	if (!c) { vdjx_set_error("vdjx_tree: NULL argument"); return VDJX_EINVAL; }
+	if (n == 0) return VDJX_OK;
+	if (!contigs || !clone || !anchor || !out_parent || !out_dist || !out_depth) { vdjx_set_error("vdjx_tree: NULL argument"); return VDJX_EINVAL; }
+	if (n >= (1ull << 20)) { vdjx_set_error("vdjx_tree: %zu items (at most 2^20 - 1 per call)", n); return VDJX_EINVAL; }
+	if (len < 1 || len >= 4096) { vdjx_set_error("vdjx_tree: contigs of %d characters (1 .. 4095)", len); return VDJX_EINVAL; }
+	if (memchr(contigs, 0, n * (size_t) len)) { vdjx_set_error("vdjx_tree: contigs of unequal length (a NUL inside the %zu x %d characters)", n, len); return VDJX_EINVAL; }
+	const auto t0 = std::chrono::steady_clock::now();
+	std::vector<u64> keys;                                 // clone << 20 | index: the clone order, the members of a clone in index order
+	for (size_t i = 0; i < n; i++) {
+		if (clone[i] < -1) { vdjx_set_error("vdjx_tree: item %zu has clone %d (a key >= 0, or -1 for no part)", i, clone[i]); return VDJX_EINVAL; }
+		if (clone[i] < 0) continue;
+		if (anchor[i] < 0 || anchor[i] > len) { vdjx_set_error("vdjx_tree: item %zu has its anchor at %d (0 .. %d)", i, anchor[i], len); return VDJX_EINVAL; }
+		keys.push_back((u64) (u32) clone[i] << 20 | (u64) i);
+	}
+	const u32 rows = (u32) keys.size();
+	for (size_t i = 0; i < n; i++) out_parent[i] = out_dist[i] = out_depth[i] = -1;
+	vdjx_tree_info inf;
+	memset(&inf, 0, sizeof inf);
+	inf.members = rows;
+	if (rows == 0) {
+		if (info) *info = inf;
+		c->stats["tree_work_items"] = 0;
+		c->stats["tree_rounds"] = 0;
+		c->stats["tree_us"] = 0;
+		return VDJX_OK;
+	}
+	std::sort(keys.begin(), keys.end());
+	struct Clone { u32 first, m, words, wbase, root; };
+	std::vector<Clone> clones;
+	std::vector<TreeRow> ri(rows + 1);
+	std::vector<u32> row_item(rows);
+	u64 total = 0, cells = 0;                              // {bases, mask} pairs in all; the squared sizes of the clones of two and more
+	for (u32 r0 = 0; r0 < rows;) {
+		u32 r1 = r0;
+		int a = len, b = len;                               // the common window: a bases before the anchor, b from it on
+		while (r1 < rows && (keys[r1] >> 20) == (keys[r0] >> 20)) {
+			const u32 i = (u32) (keys[r1] & 0xFFFFFu);
+			a = std::min(a, (int) anchor[i]);
+			b = std::min(b, len - (int) anchor[i]);
+			r1++;
+		}
+		const u32 w = (u32) (a + b), m = r1 - r0;
+		if (w == 0) {
+			vdjx_set_error("vdjx_tree: clone %d has an empty window (a member's anchor at 0 and a member's at %d)", clone[keys[r0] & 0xFFFFFu], len);
+			return VDJX_EINVAL;
+		}
+		const u32 words = (w + 31u) / 32u;
+		if (total + (u64) m * words > 0xFFFFFFFFull) { vdjx_set_error("vdjx_tree: more than 2^32 packed words"); return VDJX_ELIMIT; }
+		u32 root = r0;
+		for (u32 r = r0; r < r1; r++) {
+			const u32 i = (u32) (keys[r] & 0xFFFFFu);
+			row_item[r] = i;
+			ri[r] = {(u64) i * (u64) len + (u64) (anchor[i] - a), (u32) total + (r - r0) * words, w};
+			if (prio && prio[i] < prio[row_item[root]]) root = r;      // (rows are in index order: a tie keeps the smaller index)
+		}
+		clones.push_back({r0, m, words, (u32) total, root});
+		total += (u64) m * words;
+		inf.largest_clone = std::max(inf.largest_clone, m);
+		if (m > 1) cells += (u64) m * m;
+		r0 = r1;
+	}
+	ri[rows] = {0, (u32) total, 0};
+	inf.clones = (u32) clones.size();
+	inf.edges = (u64) rows - clones.size();
+	while ((1ull << inf.rounds) < inf.largest_clone) inf.rounds++;
+	// the work items: (clone, row block, column slice), as vdjx_lineage sizes them: the slice is a whole number of 64 columns, as wide as
+	// it takes for about TREE_TARGET_ITEMS items in all.  A clone of one has none.
+	const u64 per = (cells + (u64) TREE_ROWS * TREE_TARGET_ITEMS - 1) / ((u64) TREE_ROWS * TREE_TARGET_ITEMS);
+	const u32 slice = (u32) std::max<u64>(TREE_ROWS, (per + TREE_ROWS - 1) / TREE_ROWS * TREE_ROWS);
+	std::vector<TreeItem> items;
+	for (const Clone& q : clones) {
+		if (q.m < 2) continue;
+		const u32 end = q.first + q.m;
+		for (u32 r0 = q.first; r0 < end; r0 += TREE_ROWS)
+			for (u32 c0 = q.first; c0 < end; c0 += slice)
+				items.push_back({r0, std::min(end, r0 + TREE_ROWS), c0, std::min(end, c0 + slice), q.words, q.first, q.wbase, 0u});
+	}
+	const u32 cap = (u32) inf.edges;
+	std::vector<u64> edges(cap ? cap : 1);
+	u32 n_edges = 0;
+	if (inf.rounds) {
+		HIP_TRY(hipSetDevice(c->device));
+		hipStream_t st = c->stream;
+		vdjx_work wk(c);
+		char* d_contigs;
+		TreeRow* d_ri;
+		TreeItem* d_items;
+		ulonglong2* d_words;
+		u32 *d_comp, *d_parent, *d_count;
+		unsigned long long *d_best, *d_edges;
+		HIP_TRY(wk.alloc(&d_contigs, n * (size_t) len));
+		HIP_TRY(wk.alloc(&d_ri, (size_t) rows + 1));
+		HIP_TRY(wk.alloc(&d_items, items.size()));
+		HIP_TRY(wk.alloc(&d_words, (size_t) total));
+		HIP_TRY(wk.alloc(&d_comp, rows));
+		HIP_TRY(wk.alloc(&d_parent, rows));
+		HIP_TRY(wk.alloc(&d_best, rows));
+		HIP_TRY(wk.alloc(&d_edges, cap));
+		HIP_TRY(wk.alloc(&d_count, 1));
+		HIP_TRY(hipMemcpyAsync(d_contigs, contigs, n * (size_t) len, hipMemcpyHostToDevice, st));
+		HIP_TRY(hipMemcpyAsync(d_ri, ri.data(), ((size_t) rows + 1) * sizeof(TreeRow), hipMemcpyHostToDevice, st));
+		HIP_TRY(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(TreeItem), hipMemcpyHostToDevice, st));
+		HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(u32), st));
+		const u32 nb = (rows + 255u) / 256u;
+		{
+			vdjx_prof_scope ps(c, "k_tree_pack");
+			hipLaunchKernelGGL(k_tree_pack, dim3((u32) ((total + 255) / 256)), dim3(256), 0, st, (const char*) d_contigs, (const TreeRow*) d_ri, rows, (u32) total,
+			                   d_words, d_comp, d_parent, d_best);
+		}
+		for (u32 round = 0; round < inf.rounds; round++) {
+			{
+				vdjx_prof_scope ps(c, round ? "k_tree_min" : "k_tree_min_first");      // (the first round skips no column: the pass to measure)
+				hipLaunchKernelGGL(k_tree_min, dim3((u32) items.size()), dim3(64), 0, st, (const TreeItem*) d_items, (const ulonglong2*) d_words,
+				                   (const u32*) d_comp, d_best);
+			}
+			{
+				vdjx_prof_scope ps(c, "k_tree_hook");
+				hipLaunchKernelGGL(k_tree_hook, dim3(nb), dim3(256), 0, st, (const u32*) d_comp, (const unsigned long long*) d_best, rows, d_parent, d_edges, cap,
+				                   d_count);
+			}
+			{
+				vdjx_prof_scope ps(c, "k_tree_flat");
+				hipLaunchKernelGGL(k_tree_flat, dim3(nb), dim3(256), 0, st, (const u32*) d_parent, rows, d_comp, d_best);
+			}
+		}
+		HIP_TRY(hipMemcpyAsync(&n_edges, d_count, sizeof n_edges, hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipMemcpyAsync(edges.data(), d_edges, (size_t) cap * sizeof(u64), hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipStreamSynchronize(st));
+		HIP_TRY(hipGetLastError());
+		vdjx_prof_collect(c, false);
+	}
+	if (n_edges != cap) { vdjx_set_error("vdjx_tree: %u edges for %u members in %u clones", n_edges, rows, inf.clones); return VDJX_ESTATE; }
+	// the edges toward the roots: adjacency lists over the rows, then a walk from every clone's root
+	std::vector<u32> deg(rows + 1, 0), adj(2 * (size_t) cap), adj_d(2 * (size_t) cap);
+	for (u32 e = 0; e < cap; e++) {
+		const u32 lo = (u32) (edges[e] >> 20) & 0xFFFFFu, hi = (u32) edges[e] & 0xFFFFFu;
+		if (lo >= rows || hi >= rows || lo == hi) { vdjx_set_error("vdjx_tree: an edge between rows %u and %u of %u", lo, hi, rows); return VDJX_ESTATE; }
+		deg[lo + 1]++;
+		deg[hi + 1]++;
+	}
+	for (u32 r = 0; r < rows; r++) deg[r + 1] += deg[r];
+	std::vector<u32> fill(deg.begin(), deg.end() - 1);
+	for (u32 e = 0; e < cap; e++) {
+		const u32 lo = (u32) (edges[e] >> 20) & 0xFFFFFu, hi = (u32) edges[e] & 0xFFFFFu, d = (u32) (edges[e] >> 40);
+		adj[fill[lo]] = hi; adj_d[fill[lo]++] = d;
+		adj[fill[hi]] = lo; adj_d[fill[hi]++] = d;
+	}
+	std::vector<u32> queue(rows);
+	u32 reached = 0;
+	for (const Clone& q : clones) {
+		u32 head = reached;
+		queue[reached++] = q.root;
+		out_depth[row_item[q.root]] = 0;
+		while (head < reached) {
+			const u32 r = queue[head++], i = row_item[r];
+			for (u32 k = deg[r]; k < deg[r + 1]; k++) {
+				const u32 s = adj[k], j = row_item[s];
+				if (out_depth[j] >= 0) continue;              // (its parent: the only neighbour seen before)
+				out_parent[j] = (int32_t) i;
+				out_dist[j] = (int32_t) adj_d[k];
+				out_depth[j] = out_depth[i] + 1;
+				inf.weight += adj_d[k];
+				if (reached < rows) queue[reached++] = s;
+			}
+		}
+	}
+	if (reached != rows) { vdjx_set_error("vdjx_tree: %u of %u members reached from the roots", reached, rows); return VDJX_ESTATE; }
+	if (info) *info = inf;
+	c->stats["tree_work_items"] = items.size();
+	c->stats["tree_rounds"] = inf.rounds;
+	c->stats["tree_us"] = (u64) std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
+	return VDJX_OK;
+}

@@ -493,6 +493,45 @@ typedef struct { uint32_t members, clones, largest_clone, rounds; uint64_t edges
 int vdjx_tree(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const int32_t* clone, const int32_t* anchor, const uint32_t* prio,
               int32_t* out_parent, int32_t* out_dist, int32_t* out_depth, vdjx_tree_info* info);
 
+/* ---- edge support for the lineage trees: the delete-half jackknife over the window's columns ------------------------------------------
+ * the tree above is unique, so it looks equally certain everywhere, though many of its edges are decided by one or two columns.  Every
+ * replicate keeps each window column with probability 1/2 and builds the trees again on the kept columns alone; an edge's support is
+ * the number of replicates whose tree still has it (Felsenstein's delete-half jackknife: deleting columns keeps the distance a popcount).
+ * All arithmetic is integer: the device's results are bitwise the model's (tests/tree_support_model.py).
+ *   items       contigs, n, len, clone[], anchor[] exactly as vdjx_tree takes them; the windows and (a, b) are as there.  Window position
+ *               q = 0 is the character at anchor[i] - a.
+ *   parent      parent[i]: for a member, the item whose edge to it is to be scored, or -1 (typically out_parent of vdjx_tree; it need not
+ *               be a minimum spanning tree).
+ *   keep rule   mix64(x) is splitmix64's output step in 64-bit wrap-around arithmetic: z = x + 0x9E3779B97F4A7C15;
+ *               z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; the result z ^ z >> 31
+ *               (mix64(0) = 0xE220A8397B1DCDAF).  Replicate r (1 .. replicates) keeps window position q when bit q & 31 of
+ *               mix64(seed ^ ((uint64_t) r << 32 | q >> 5)) is set: the rule depends on (seed, r, q) only, the same for every clone.
+ *   replicate   d_r(i, j): the number of KEPT window positions at which the two members differ or either is not one of ACGT.  The
+ *               replicate tree of a clone is the minimum spanning tree under the strict order of the keys (d_r, min(i, j), max(i, j)),
+ *               unique as above.  A replicate that keeps no position of a clone's window has all distances 0: the star at the
+ *               smallest index.
+ *   output      out_support[i], for a member with parent[i] >= 0: the number of replicates whose tree contains the undirected edge
+ *               {i, parent[i]}; -1 for every other item.
+ *   info        (may be NULL; zeroed first, every field filled on success) members, clones, largest_clone as vdjx_tree's; replicates;
+ *               batches: the groups of whole replicates the device ran side by side (0 when no clone has two members); rounds =
+ *               ceil(log2 largest_clone), Boruvka's rounds per batch; edges: the parent[i] >= 0; matched: the sum of the supports; full:
+ *               the edges with support = replicates.
+ * NOT modelled: support of splits (bipartitions) rather than of edges; the bootstrap with replacement.  An edge whose only differing
+ * columns are all deleted can still appear in a replicate through the index tie-break, so for such edges the support is an upper bound
+ * (a 12-member descent with dist_parent = 1 everywhere gave supports between 5/16 and 16/16: informative, not exact).
+ * VDJX_EINVAL: everything vdjx_tree refuses; replicates outside 1 .. 1024; a parent[i] that is i, outside -1 .. n-1 or in another clone;
+ * a parent[i] >= 0 on an item with clone[i] = -1; NULL parent or out_support.  n = 0 returns at once with a zeroed info.
+ * The host computes every replicate's ascending list of kept positions; a batch is max(1, floor(R / members of clones of two and more))
+ * whole replicates laid side by side (the edge keys carry row numbers below 2^20; R = VDJX_TREE_SUPPORT_ROWS, 1 .. 2^20 - 1, the
+ * default 2^20 - 1) and 1 + 3 * rounds + 1 dispatches (pack, the rounds of vdjx_tree, count) whatever n, the clones and the replicates
+ * in it are.  Per batch only the edge count is read back, the supports once at the end.  The count is an integer atomicAdd per edge:
+ * two calls give the same bits.  Stats: "tree_support_batches", "tree_support_work_items" (the work items of a round, summed over the
+ * batches), "tree_support_us" (host clock). */
+typedef struct { uint32_t replicates; uint64_t seed; } vdjx_tree_support_params;                                /* 16 bytes */
+typedef struct { uint32_t members, clones, largest_clone, replicates, batches, rounds; uint64_t edges, matched, full; } vdjx_tree_support_info;   /* 48 bytes */
+int vdjx_tree_support(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const int32_t* clone, const int32_t* anchor,
+                      const int32_t* parent, const vdjx_tree_support_params* params, int32_t* out_support, vdjx_tree_support_info* info);
+
 /* rows of `row` bytes on the device: row d_pos[i] of d_dst = row i of d_src.  (The records of a pool sharded by pair on their way to
  * the ranks that hold their slice of the scan order for the k-mer build, A2:1388-1390: every record arrives with its place.) */
 int vdjx_rows_scatter(vdjx_ctx* ctx, void* d_dst, const void* d_src, const uint32_t* d_pos, size_t n, size_t row);

@@ -152,3 +152,21 @@ def tree_inputs(ids, contigs, v, clone):
         anchor[c] = junction_of(ids[c], contigs[c])[0]
         prio[c] = int(v["mismatches"][c]) + int(v["ins"][c]) + int(v["del"][c])
     return anchor, prio
+
+
+def _mix64(x):
+    """splitmix64's output step, in 64-bit wrap-around arithmetic"""
+    m = (1 << 64) - 1
+    z = (x + 0x9E3779B97F4A7C15) & m
+    z = ((z ^ z >> 30) * 0xBF58476D1CE4E5B9) & m
+    z = ((z ^ z >> 27) * 0x94D049BB133111EB) & m
+    return z ^ z >> 31
+
+
+def jackknife_keep(seed, r, w):
+    """the keep rule of vdjx_tree_support (include/vdjx.h) in plain Python -> bool[w]: replicate r (1 .. replicates) keeps window position
+    q when bit q & 31 of mix64(seed ^ (r << 32 | q >> 5)) is set"""
+    import numpy as np
+    seed, r = int(seed), int(r)
+    assert 0 <= seed < 1 << 64 and 0 <= r < 1 << 32
+    return np.array([bool(_mix64(seed ^ (r << 32 | q >> 5)) >> (q & 31) & 1) for q in range(int(w))], bool)

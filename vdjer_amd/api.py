@@ -769,6 +769,32 @@ class Context:
         check(self.L.vdjx_tree(self.h, raw, n, ln, _p(cl), _p(an), _p(pr), _p(parent), _p(dist), _p(depth), C.byref(info)), "vdjx_tree")
         return {"parent": parent, "dist": dist, "depth": depth, "info": {f: int(getattr(info, f)) for f in self.TREE_FIELDS}}
 
+    TREE_SUPPORT_FIELDS = ("members", "clones", "largest_clone", "replicates", "batches", "rounds", "edges", "matched", "full")
+
+    def tree_support(self, contigs, clone, anchor, parent, replicates=100, seed=1):
+        """vdjx_tree_support: the delete-half jackknife over the window's columns.  contigs, clone, anchor as tree() takes them; parent:
+        int32[n], for every member the item whose edge to it is scored, or -1 (typically tree()'s "parent"); replicates: 1 .. 1024; seed:
+        any uint64 -> {"support": int32[n] (the replicates whose tree has the edge {i, parent[i]}; -1 where parent is), "info":
+        dict(members, clones, largest_clone, replicates, batches, rounds, edges, matched, full)}"""
+        if isinstance(contigs, tuple):
+            raw, n, ln = contigs
+        else:
+            if len({len(s_) for s_ in contigs}) > 1:
+                raise VdjxError("vdjx_tree_support: contigs of unequal length")
+            raw, n, ln = self.pack_strings(contigs)
+        cl = np.ascontiguousarray(clone, np.int32)
+        an = np.ascontiguousarray(anchor, np.int32)
+        pa = np.ascontiguousarray(parent, np.int32)
+        if cl.shape != (n,) or an.shape != (n,) or pa.shape != (n,):
+            raise VdjxError(f"vdjx_tree_support: {n} contigs, clone of shape {cl.shape}, anchor of shape {an.shape}, parent of shape {pa.shape}")
+        if not 0 <= int(replicates) < 1 << 32 or not 0 <= int(seed) < 1 << 64:
+            raise VdjxError(f"vdjx_tree_support: replicates {replicates}, seed {seed}")
+        params = _lib.TreeSupportParams(int(replicates), int(seed))
+        support = np.zeros(n, np.int32)
+        info = _lib.TreeSupportInfo()
+        check(self.L.vdjx_tree_support(self.h, raw, n, ln, _p(cl), _p(an), _p(pa), C.byref(params), _p(support), C.byref(info)), "vdjx_tree_support")
+        return {"support": support, "info": {f: int(getattr(info, f)) for f in self.TREE_SUPPORT_FIELDS}}
+
     def stat(self, name: str) -> int:
         return int(self.L.vdjx_stat(self.h, name.encode()))
 

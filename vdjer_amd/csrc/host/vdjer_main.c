@@ -5,7 +5,7 @@
  *   vdjer --in <reads> --chain IGH|IGK|IGL --ref-dir <dir> --ins <n> [--t --k --mf --mq --mcs --am --miw --maw
  *         --jc --ws -jext --rf --vk --mrs --rs --ms --e0 --e1 --wo --vf --jf --rms] [--gpus N] [--quant <file>] [--airr <file>]
  *         [--d-calls] [--cfa <fasta>] [--isotypes <file>] [--clones <file>] [--sample <name>] [--total-count <n>]
- *         [--lineages <file>] [--lineage-dist <x>] [--trees <file>]
+ *         [--lineages <file>] [--lineage-dist <x>] [--trees <file>] [--tree-support <B>] [--tree-seed <s>]
  * writes ./vdj_contigs.fa and ./vdjer.dot, SAM on stdout, log on stderr; exit 0 on success.  --quant <file>: the contigs' abundances
  * (vdjx_quant, RSEM's isoforms.results columns) into <file> as well.  --airr <file>: the contigs' V/J annotation (vdjx_annotate against
  * the germlines of ig_vdj.fa / --vdjf) as an AIRR Rearrangement TSV; with --d-calls (a flag: no value) the D gene between the V and the
@@ -15,7 +15,8 @@
  * clonal lineages (vdjx_lineage: single linkage on the junctions' Hamming distance inside a V gene / J gene / junction length bucket,
  * linked up to --lineage-dist, default 0.15 of the length); with --airr the table gets a clone_id column.  --trees <file> (with --lineages):
  * the tree inside every lineage (vdjx_tree: the minimum spanning tree under the Hamming distance over the members' common window around
- * the junction, rooted at the member closest to its germline V).
+ * the junction, rooted at the member closest to its germline V); --tree-support <B> (with --trees): a support column, the share of B
+ * delete-half jackknife replicates whose tree has the edge to the parent (vdjx_tree_support), the columns drawn from --tree-seed <s>.
  *
  * --in: a BAM with its .bai (extraction as bam_read.c:264-446, restated over zlib in bamx.c), or -- recognised by its
  * content -- the extracted read pool as text, one read per line in extraction order:
@@ -64,6 +65,8 @@ typedef struct {
 	const char* lineage_dist;              /* --lineage-dist <x>: its threshold, a decimal read exactly into lin_num / lin_den (default 1500 / 10000) */
 	int lin_num, lin_den;
 	const char* trees;                     /* --trees <file> (not in the reference): the tree inside every lineage of --lineages, on the device */
+	const char *tree_support, *tree_seed;  /* --tree-support <B>, --tree-seed <s>: the jackknife support of the trees' edges; read into ts_b (0: none) and ts_seed */
+	uint32_t ts_b; uint64_t ts_seed;
 	int have_chain, have_ref;
 } cli;
 
@@ -87,7 +90,9 @@ static void usage(void) {
 	                "\t--total-count <whole number for the clone table's total_count column (default: N/A)>\n"
 	                "\t--lineages <file: clonal lineages of the contigs, single linkage on the junctions inside a V gene / J gene / length bucket>\n"
 	                "\t--lineage-dist <largest linked distance as a fraction of the junction length, in [0,1], at most 4 decimals (default: 0.15)>\n"
-	                "\t--trees <file: with --lineages, the minimum spanning tree inside every lineage: parent, distance and depth of every contig>\n");
+	                "\t--trees <file: with --lineages, the minimum spanning tree inside every lineage: parent, distance and depth of every contig>\n"
+	                "\t--tree-support <B: with --trees, a support column from B delete-half jackknife replicates, a whole number in 1 .. 1024>\n"
+	                "\t--tree-seed <seed of the replicates' columns, a whole number below 2^64 (default: 1)>\n");
 }
 
 static int file_exists(const char* f) { struct stat b; return stat(f, &b) == 0; }
@@ -101,6 +106,20 @@ static int lineage_dist_num(const char* s) {
 	int v = wl ? (s[0] - '0') * 10000 : 0;
 	for (size_t k = 0, scale = 1000; k < fl; k++, scale /= 10) v += (dot[1 + k] - '0') * (int) scale;
 	return v <= 10000 ? v : -1;
+}
+
+/* the whole text as a decimal uint64: digits only, at least one, no overflow -> 0, or -1 */
+static int whole_u64(const char* s, uint64_t* out) {
+	uint64_t x = 0;
+	if (!s[0]) return -1;
+	for (; *s; s++) {
+		if (*s < '0' || *s > '9') return -1;
+		const uint64_t d = (uint64_t) (*s - '0');
+		if (x > (UINT64_MAX - d) / 10) return -1;
+		x = x * 10 + d;
+	}
+	*out = x;
+	return 0;
 }
 
 /* params.c:214-298: positional "--flag value" pairs; unknown flags only warn */
@@ -147,6 +166,8 @@ static int parse(int argc, char** argv, cli* c) {
 		else if (!strcmp(a, "--lineages")) c->lineages = v;
 		else if (!strcmp(a, "--lineage-dist")) c->lineage_dist = v;
 		else if (!strcmp(a, "--trees")) c->trees = v;
+		else if (!strcmp(a, "--tree-support")) c->tree_support = v;
+		else if (!strcmp(a, "--tree-seed")) c->tree_seed = v;
 		else if (!strcmp(a, "--vf")) snprintf(c->v_anchors, sizeof c->v_anchors, "%s", v);
 		else if (!strcmp(a, "--jf")) snprintf(c->j_anchors, sizeof c->j_anchors, "%s", v);
 		else if (!strcmp(a, "--am")) c->anchor_mismatches = atoi(v);
@@ -202,6 +223,19 @@ static int parse(int argc, char** argv, cli* c) {
 		ok = 0;
 	}
 	if (c->trees && !c->lineages) { fprintf(stderr, "--trees writes the tree inside every lineage of the --lineages table: it needs --lineages <file>\n"); ok = 0; }
+	c->ts_b = 0;
+	c->ts_seed = 1;
+	if (c->tree_support && !c->trees) { fprintf(stderr, "--tree-support adds the support column to the --trees table: it needs --trees <file>\n"); ok = 0; }
+	if (c->tree_seed && !c->tree_support) { fprintf(stderr, "--tree-seed is the seed of the --tree-support replicates: it needs --tree-support <B>\n"); ok = 0; }
+	if (c->tree_support) {
+		uint64_t b = 0;
+		if (whole_u64(c->tree_support, &b) || b < 1 || b > 1024) { fprintf(stderr, "--tree-support must be a whole decimal number in 1 .. 1024: %s\n", c->tree_support); ok = 0; }
+		else c->ts_b = (uint32_t) b;
+	}
+	if (c->tree_seed && whole_u64(c->tree_seed, &c->ts_seed)) {
+		fprintf(stderr, "--tree-seed must be a whole decimal number below 2^64: %s\n", c->tree_seed);
+		ok = 0;
+	}
 	if (!ok) { usage(); return -1; }
 	if (c->hp.min_base_quality >= 255) c->hp.min_base_quality = 254;      /* A2:1514-1516 */
 	return 0;
@@ -552,6 +586,8 @@ typedef struct {
 	size_t l_contigs, l_eligible;
 	/* --trees: the tree inside every lineage (tree_run, after lineage_run) */
 	const char* trees; vdjx_tree_info ti;
+	/* --tree-support: the jackknife support of the trees' edges (tree_run) */
+	uint32_t ts_b; uint64_t ts_seed; vdjx_tree_support_info tsi;
 } hook_ud;
 
 static int h_root_score(void* ud, const char* kmers, size_t n, int k, int thr, uint8_t* out) {
@@ -1102,15 +1138,16 @@ static int lineage_run(hook_ud* u, const char* const* ids, const char* contigs, 
  * are lineage_run's; a member's anchor is where its junction starts and its priority its V hit's mismatches + ins + del, so the member closest
  * to its germline V is the root.  A row per contig: clone_id lin_<k>, parent_id, dist_parent (both empty for a root), depth, children,
  * v_mutations, window_start (0-based, in this contig) and window_length of the lineage's common window; only sequence_id for a contig
- * that is in no lineage */
+ * that is in no lineage.  --tree-support B: one more column, support, the share of B jackknife replicates whose tree has the edge to
+ * parent_id (vdjx_tree_support on vdjx_tree's parents), empty for a root */
 static int tree_run(hook_ud* u, const char* const* ids, const char* contigs, size_t n, int len) {
 	FILE* fp = fopen(u->trees, "w");
 	if (!fp) { fprintf(stderr, "cannot write %s\n", u->trees); return -1; }
-	fputs("sequence_id\tclone_id\tparent_id\tdist_parent\tdepth\tchildren\tv_mutations\twindow_start\twindow_length\n", fp);
+	fprintf(fp, "sequence_id\tclone_id\tparent_id\tdist_parent\tdepth\tchildren\tv_mutations\twindow_start\twindow_length%s\n", u->ts_b ? "\tsupport" : "");
 	int32_t* anchor = (int32_t*) calloc(n + 1, sizeof(int32_t));
 	uint32_t* prio = (uint32_t*) calloc(n + 1, sizeof(uint32_t));
-	int32_t* out = (int32_t*) calloc(3 * n + 1, sizeof(int32_t));
-	int32_t *parent = out, *dist = out + n, *depth = out + 2 * n;
+	int32_t* out = (int32_t*) calloc(4 * n + 1, sizeof(int32_t));
+	int32_t *parent = out, *dist = out + n, *depth = out + 2 * n, *support = out + 3 * n;
 	const size_t nk = (size_t) u->li.clones + 1;
 	int32_t* before = (int32_t*) malloc(nk * sizeof(int32_t));       /* per lineage: the window's bases before the anchor, and from it on */
 	int32_t* after = (int32_t*) malloc(nk * sizeof(int32_t));
@@ -1129,15 +1166,23 @@ static int tree_run(hook_ud* u, const char* const* ids, const char* contigs, siz
 	}
 	int rc = vdjx_tree(u->gx, contigs, n, len, u->lin_clone, anchor, prio, parent, dist, depth, &u->ti);
 	if (rc) fprintf(stderr, "--trees: %s\n", vdjx_last_error());
+	if (!rc && u->ts_b) {
+		const vdjx_tree_support_params tp = {u->ts_b, u->ts_seed};
+		rc = vdjx_tree_support(u->gx, contigs, n, len, u->lin_clone, anchor, parent, &tp, support, &u->tsi);
+		if (rc) fprintf(stderr, "--tree-support: %s\n", vdjx_last_error());
+	}
 	if (!rc) {
 		for (size_t i = 0; i < n; i++)
 			if (parent[i] >= 0) kids[parent[i]]++;
 		for (size_t i = 0; i < n; i++) {
 			const int32_t k = u->lin_clone[i];
-			if (k < 0) { fprintf(fp, "%s\t\t\t\t\t\t\t\t\n", ids[i]); continue; }
+			if (k < 0) { fprintf(fp, "%s\t\t\t\t\t\t\t\t%s\n", ids[i], u->ts_b ? "\t" : ""); continue; }
 			fprintf(fp, "%s\tlin_%d\t", ids[i], k + 1);
 			if (parent[i] >= 0) fprintf(fp, "%s\t%d", ids[parent[i]], dist[i]); else fputc('\t', fp);
-			fprintf(fp, "\t%d\t%zu\t%u\t%d\t%d\n", depth[i], kids[i], prio[i], anchor[i] - before[k], before[k] + after[k]);
+			fprintf(fp, "\t%d\t%zu\t%u\t%d\t%d", depth[i], kids[i], prio[i], anchor[i] - before[k], before[k] + after[k]);
+			if (u->ts_b && parent[i] >= 0) fprintf(fp, "\t%.4f", (double) support[i] / (double) u->ts_b);
+			else if (u->ts_b) fputc('\t', fp);
+			fputc('\n', fp);
 		}
 	}
 	free(anchor); free(prio); free(out); free(before); free(after); free(kids);
@@ -1430,6 +1475,7 @@ int main(int argc, char** argv) {
 	ud.gx = gx; ud.p = &c.hp; ud.mg = mg; ud.quant = c.quant; ud.airr = c.airr; ud.vdjf = c.vdj_fasta; ud.d_calls = c.d_calls;
 	ud.cfa = c.cfa; ud.isotypes = c.isotypes; ud.clones = c.clones; ud.total_count = c.total_count;
 	ud.lineages = c.lineages; ud.lin_num = c.lin_num; ud.lin_den = c.lin_den; ud.trees = c.trees;
+	ud.ts_b = c.ts_b; ud.ts_seed = c.ts_seed;
 	char sample_buf[4096];
 	if (c.sample) ud.sample = c.sample;
 	else {                                  /* the input's base name up to its first '.' */
@@ -1487,6 +1533,10 @@ int main(int argc, char** argv) {
 	if (c.trees)
 		fprintf(stderr, "trees: %u contigs in %u lineages (largest %u), %llu edges, total distance %llu, %u rounds\n", ud.ti.members, ud.ti.clones, ud.ti.largest_clone,
 		        (unsigned long long) ud.ti.edges, (unsigned long long) ud.ti.weight, ud.ti.rounds);
+	if (c.ts_b)
+		fprintf(stderr, "tree support: %u replicates (seed %llu), %llu edges, %llu of %llu kept, %llu in every replicate, %u batches\n", c.ts_b,
+		        (unsigned long long) c.ts_seed, (unsigned long long) ud.tsi.edges, (unsigned long long) ud.tsi.matched,
+		        (unsigned long long) (ud.tsi.edges * c.ts_b), (unsigned long long) ud.tsi.full, ud.tsi.batches);
 	if (c.isotypes)
 		fprintf(stderr, "isotypes: %zu contigs, %zu called against %zu constant records of %s; table in %s\n", ud.i_contigs, ud.i_called,
 		        ud.cst ? ud.cst->n : (size_t) 0, c.cfa, c.isotypes);

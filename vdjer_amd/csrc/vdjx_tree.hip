@@ -23,6 +23,16 @@
 // The keys are distinct, so the chosen edges never close a cycle and the components at least halve per round.  The edges (members -
 // clones) come back once, in whatever order the appends landed; the host orients them toward each clone's root and counts the depths,
 // O(n), which does not depend on that order.  No floating point.  Scratch comes from the context's workspace.
+//
+//   vdjx_tree_support   the delete-half jackknife: every replicate keeps about half of the window's columns and builds the trees again
+//               on the kept columns alone; an edge's support is the number of replicates whose tree has it.  The rounds are the same
+//               routine (tree_rounds) on other rows:
+//   k_tree_pack_sel   as k_tree_pack, but a row's characters are gathered at the replicate's kept positions (a list per replicate, made
+//                 on the host), so a replicate's rows have about half the words and k_tree_min runs on them as it is.  A batch is as
+//                 many whole replicates side by side as fit below 2^20 rows (VDJX_TREE_SUPPORT_ROWS), replicate-major, each
+//                 (replicate, clone) a clone of its own to the rounds.
+//   k_tree_support    per edge of the batch's trees: the two rows back to the caller's items, one atomicAdd on the end whose scored parent
+//                 is the other.  Per batch only the edge count is read back; the supports once, at the end.
 #include "vdjx_common.h"
 #include "vdjx_unionfind.h"
 
@@ -215,23 +225,160 @@ __global__ __launch_bounds__(256) void k_tree_flat(const u32* __restrict__ paren
 	best[r] = TREE_NONE;
 }
 
+// the jackknife's pack: as k_tree_pack, but a row's characters are the replicate's kept window positions (sel: `stride` ascending
+// positions per replicate of the batch, of which the row uses its first q.w); the rows of a replicate are `per_rep` in a run
+__global__ __launch_bounds__(256) void k_tree_pack_sel(const char* __restrict__ contigs, const TreeRow* __restrict__ ri, u32 rows, u32 total,
+                                                       const uint16_t* __restrict__ sel, u32 stride, u32 per_rep, ulonglong2* __restrict__ out,
+                                                       u32* __restrict__ comp, u32* __restrict__ parent, unsigned long long* __restrict__ best) {
+	const u32 t = blockIdx.x * 256u + threadIdx.x;
+	if (t >= total) return;
+	u32 lo = 0, hi = rows;                              // the row r with ri[r].wbase <= t < ri[r + 1].wbase
+	while (hi - lo > 1u) {
+		const u32 mid = (lo + hi) / 2u;
+		if (ri[mid].wbase <= t) lo = mid; else hi = mid;
+	}
+	const TreeRow q = ri[lo];
+	const u32 w = t - q.wbase;
+	const uint16_t* mine = sel + (size_t) (lo / per_rep) * stride;
+	u64 x = 0, m = 0;
+	for (u32 k = 0; k < 32u; k++) {
+		const u32 pos = w * 32u + k;
+		if (pos >= q.w) break;                            // (a replicate that keeps nothing of this window: one word of zeros)
+		const char ch = contigs[q.at + mine[pos]];
+		const u32 code = ch == 'A' ? 0u : ch == 'T' ? 1u : ch == 'C' ? 2u : ch == 'G' ? 3u : 4u;
+		if (code < 4u) x |= (u64) code << (2u * k);
+		else m |= 2ull << (2u * k);
+	}
+	out[t] = make_ulonglong2(x, m);
+	if (w == 0) { comp[lo] = lo; parent[lo] = lo; best[lo] = TREE_NONE; }
+}
+
+// one thread per edge of the batch's replicate trees: row r is member r % per_rep of its replicate, item[] the caller's index of a member.
+// The edge {i, j} counts for the end whose scored parent is the other (a sum: the order of the atomics does not matter)
+__global__ __launch_bounds__(256) void k_tree_support(const unsigned long long* __restrict__ edges, const u32* __restrict__ n_edges, u32 cap, u32 rows,
+                                                      u32 per_rep, const u32* __restrict__ item, const int32_t* __restrict__ parent, u32* support) {
+	const u32 e = blockIdx.x * 256u + threadIdx.x;
+	if (e >= cap || e >= *n_edges) return;
+	const u64 k = edges[e];
+	const u32 lo = (u32) (k >> 20) & 0xFFFFFu, hi = (u32) k & 0xFFFFFu;
+	if (lo >= rows || hi >= rows) return;                 // (cannot be: k_tree_min made the key of two rows)
+	const u32 i = item[lo % per_rep], j = item[hi % per_rep];
+	if (parent[i] == (int32_t) j) atomicAdd(support + i, 1u);
+	if (parent[j] == (int32_t) i) atomicAdd(support + j, 1u);
+}
+
+struct TreeClone { u32 first, m, words, wbase, root, w; };                    // rows [first, first + m), `words` pairs each from pair `wbase` on; the root's row; bases
+
+// what both entries refuse about the contigs
+static int tree_check_contigs(const char* who, const char* contigs, size_t n, int len) {
+	if (n >= (1ull << 20)) { vdjx_set_error("%s: %zu items (at most 2^20 - 1 per call)", who, n); return VDJX_EINVAL; }
+	if (len < 1 || len >= 4096) { vdjx_set_error("%s: contigs of %d characters (1 .. 4095)", who, len); return VDJX_EINVAL; }
+	if (memchr(contigs, 0, n * (size_t) len)) { vdjx_set_error("%s: contigs of unequal length (a NUL inside the %zu x %d characters)", who, n, len); return VDJX_EINVAL; }
+	return VDJX_OK;
+}
+
+// clone << 20 | index of every member, sorted: the clone order, the members of a clone in index order
+static int tree_keys(const char* who, size_t n, int len, const int32_t* clone, const int32_t* anchor, std::vector<u64>& keys) {
+	for (size_t i = 0; i < n; i++) {
+		if (clone[i] < -1) { vdjx_set_error("%s: item %zu has clone %d (a key >= 0, or -1 for no part)", who, i, clone[i]); return VDJX_EINVAL; }
+		if (clone[i] < 0) continue;
+		if (anchor[i] < 0 || anchor[i] > len) { vdjx_set_error("%s: item %zu has its anchor at %d (0 .. %d)", who, i, anchor[i], len); return VDJX_EINVAL; }
+		keys.push_back((u64) (u32) clone[i] << 20 | (u64) i);
+	}
+	std::sort(keys.begin(), keys.end());
+	return VDJX_OK;
+}
+
+// the rows of the sorted keys: every clone's common window, where each member's window starts, the packed layout
+struct TreeLay {
+	std::vector<TreeClone> clones;
+	std::vector<TreeRow> ri;                              // rows + 1: the last is k_tree_pack's sentinel
+	std::vector<u32> row_item;
+	u64 total = 0, cells = 0;                             // {bases, mask} pairs in all; the squared sizes of the clones of two and more
+	u32 largest = 0;
+};
+static int tree_lay(const char* who, const std::vector<u64>& keys, int len, const int32_t* clone, const int32_t* anchor, const uint32_t* prio, TreeLay& L) {
+	const u32 rows = (u32) keys.size();
+	L.ri.resize(rows + 1);
+	L.row_item.resize(rows);
+	for (u32 r0 = 0; r0 < rows;) {
+		u32 r1 = r0;
+		int a = len, b = len;                               // the common window: a bases before the anchor, b from it on
+		while (r1 < rows && (keys[r1] >> 20) == (keys[r0] >> 20)) {
+			const u32 i = (u32) (keys[r1] & 0xFFFFFu);
+			a = std::min(a, (int) anchor[i]);
+			b = std::min(b, len - (int) anchor[i]);
+			r1++;
+		}
+		const u32 w = (u32) (a + b), m = r1 - r0;
+		if (w == 0) {
+			vdjx_set_error("%s: clone %d has an empty window (a member's anchor at 0 and a member's at %d)", who, clone[keys[r0] & 0xFFFFFu], len);
+			return VDJX_EINVAL;
+		}
+		const u32 words = (w + 31u) / 32u;
+		if (L.total + (u64) m * words > 0xFFFFFFFFull) { vdjx_set_error("%s: more than 2^32 packed words", who); return VDJX_ELIMIT; }
+		u32 root = r0;
+		for (u32 r = r0; r < r1; r++) {
+			const u32 i = (u32) (keys[r] & 0xFFFFFu);
+			L.row_item[r] = i;
+			L.ri[r] = {(u64) i * (u64) len + (u64) (anchor[i] - a), (u32) L.total + (r - r0) * words, w};
+			if (prio && prio[i] < prio[L.row_item[root]]) root = r;      // (rows are in index order: a tie keeps the smaller index)
+		}
+		L.clones.push_back({r0, m, words, (u32) L.total, root, w});
+		L.total += (u64) m * words;
+		L.largest = std::max(L.largest, m);
+		if (m > 1) L.cells += (u64) m * m;
+		r0 = r1;
+	}
+	L.ri[rows] = {0, (u32) L.total, 0};
+	return VDJX_OK;
+}
+
+// the work items: (clone, row block, column slice), as vdjx_lineage sizes them: the slice is a whole number of 64 columns, as wide as
+// it takes for about TREE_TARGET_ITEMS items in all.  A clone of one has none.
+static void tree_items(const std::vector<TreeClone>& clones, u64 cells, std::vector<TreeItem>& items) {
+	const u64 per = (cells + (u64) TREE_ROWS * TREE_TARGET_ITEMS - 1) / ((u64) TREE_ROWS * TREE_TARGET_ITEMS);
+	const u32 slice = (u32) std::max<u64>(TREE_ROWS, (per + TREE_ROWS - 1) / TREE_ROWS * TREE_ROWS);
+	for (const TreeClone& q : clones) {
+		if (q.m < 2) continue;
+		const u32 end = q.first + q.m;
+		for (u32 r0 = q.first; r0 < end; r0 += TREE_ROWS)
+			for (u32 c0 = q.first; c0 < end; c0 += slice)
+				items.push_back({r0, std::min(end, r0 + TREE_ROWS), c0, std::min(end, c0 + slice), q.words, q.first, q.wbase, 0u});
+	}
+}
+
+// Boruvka's rounds over laid-out rows (packed, comp = parent = the row, best = none): per round min, hook, flat; nothing is read back
+static void tree_rounds(vdjx_ctx* c, hipStream_t st, u32 rounds, const TreeItem* d_items, u32 n_items, const ulonglong2* d_words, u32 rows, u32* d_comp,
+                        u32* d_parent, unsigned long long* d_best, unsigned long long* d_edges, u32 cap, u32* d_count) {
+	const u32 nb = (rows + 255u) / 256u;
+	for (u32 round = 0; round < rounds; round++) {
+		{
+			vdjx_prof_scope ps(c, round ? "k_tree_min" : "k_tree_min_first");      // (the first round skips no column: the pass to measure)
+			hipLaunchKernelGGL(k_tree_min, dim3(n_items), dim3(64), 0, st, d_items, d_words, (const u32*) d_comp, d_best);
+		}
+		{
+			vdjx_prof_scope ps(c, "k_tree_hook");
+			hipLaunchKernelGGL(k_tree_hook, dim3(nb), dim3(256), 0, st, (const u32*) d_comp, (const unsigned long long*) d_best, rows, d_parent, d_edges, cap,
+			                   d_count);
+		}
+		{
+			vdjx_prof_scope ps(c, "k_tree_flat");
+			hipLaunchKernelGGL(k_tree_flat, dim3(nb), dim3(256), 0, st, (const u32*) d_parent, rows, d_comp, d_best);
+		}
+	}
+}
+
 extern "C" int vdjx_tree(vdjx_ctx* c, const char* contigs, size_t n, int len, const int32_t* clone, const int32_t* anchor, const uint32_t* prio,
                          int32_t* out_parent, int32_t* out_dist, int32_t* out_depth, vdjx_tree_info* info) {
 	if (info) memset(info, 0, sizeof *info);
 	if (!c) { vdjx_set_error("vdjx_tree: NULL argument"); return VDJX_EINVAL; }
 	if (n == 0) return VDJX_OK;
 	if (!contigs || !clone || !anchor || !out_parent || !out_dist || !out_depth) { vdjx_set_error("vdjx_tree: NULL argument"); return VDJX_EINVAL; }
-	if (n >= (1ull << 20)) { vdjx_set_error("vdjx_tree: %zu items (at most 2^20 - 1 per call)", n); return VDJX_EINVAL; }
-	if (len < 1 || len >= 4096) { vdjx_set_error("vdjx_tree: contigs of %d characters (1 .. 4095)", len); return VDJX_EINVAL; }
-	if (memchr(contigs, 0, n * (size_t) len)) { vdjx_set_error("vdjx_tree: contigs of unequal length (a NUL inside the %zu x %d characters)", n, len); return VDJX_EINVAL; }
+	if (int rc = tree_check_contigs("vdjx_tree", contigs, n, len)) return rc;
 	const auto t0 = std::chrono::steady_clock::now();
-	std::vector<u64> keys;                                 // clone << 20 | index: the clone order, the members of a clone in index order
-	for (size_t i = 0; i < n; i++) {
-		if (clone[i] < -1) { vdjx_set_error("vdjx_tree: item %zu has clone %d (a key >= 0, or -1 for no part)", i, clone[i]); return VDJX_EINVAL; }
-		if (clone[i] < 0) continue;
-		if (anchor[i] < 0 || anchor[i] > len) { vdjx_set_error("vdjx_tree: item %zu has its anchor at %d (0 .. %d)", i, anchor[i], len); return VDJX_EINVAL; }
-		keys.push_back((u64) (u32) clone[i] << 20 | (u64) i);
-	}
+	std::vector<u64> keys;
+	if (int rc = tree_keys("vdjx_tree", n, len, clone, anchor, keys)) return rc;
 	const u32 rows = (u32) keys.size();
 	for (size_t i = 0; i < n; i++) out_parent[i] = out_dist[i] = out_depth[i] = -1;
 	vdjx_tree_info inf;
@@ -244,57 +391,18 @@ extern "C" int vdjx_tree(vdjx_ctx* c, const char* contigs, size_t n, int len, co
 		c->stats["tree_us"] = 0;
 		return VDJX_OK;
 	}
-	std::sort(keys.begin(), keys.end());
-	struct Clone { u32 first, m, words, wbase, root; };
-	std::vector<Clone> clones;
-	std::vector<TreeRow> ri(rows + 1);
-	std::vector<u32> row_item(rows);
-	u64 total = 0, cells = 0;                              // {bases, mask} pairs in all; the squared sizes of the clones of two and more
-	for (u32 r0 = 0; r0 < rows;) {
-		u32 r1 = r0;
-		int a = len, b = len;                               // the common window: a bases before the anchor, b from it on
-		while (r1 < rows && (keys[r1] >> 20) == (keys[r0] >> 20)) {
-			const u32 i = (u32) (keys[r1] & 0xFFFFFu);
-			a = std::min(a, (int) anchor[i]);
-			b = std::min(b, len - (int) anchor[i]);
-			r1++;
-		}
-		const u32 w = (u32) (a + b), m = r1 - r0;
-		if (w == 0) {
-			vdjx_set_error("vdjx_tree: clone %d has an empty window (a member's anchor at 0 and a member's at %d)", clone[keys[r0] & 0xFFFFFu], len);
-			return VDJX_EINVAL;
-		}
-		const u32 words = (w + 31u) / 32u;
-		if (total + (u64) m * words > 0xFFFFFFFFull) { vdjx_set_error("vdjx_tree: more than 2^32 packed words"); return VDJX_ELIMIT; }
-		u32 root = r0;
-		for (u32 r = r0; r < r1; r++) {
-			const u32 i = (u32) (keys[r] & 0xFFFFFu);
-			row_item[r] = i;
-			ri[r] = {(u64) i * (u64) len + (u64) (anchor[i] - a), (u32) total + (r - r0) * words, w};
-			if (prio && prio[i] < prio[row_item[root]]) root = r;      // (rows are in index order: a tie keeps the smaller index)
-		}
-		clones.push_back({r0, m, words, (u32) total, root});
-		total += (u64) m * words;
-		inf.largest_clone = std::max(inf.largest_clone, m);
-		if (m > 1) cells += (u64) m * m;
-		r0 = r1;
-	}
-	ri[rows] = {0, (u32) total, 0};
+	TreeLay L;
+	if (int rc = tree_lay("vdjx_tree", keys, len, clone, anchor, prio, L)) return rc;
+	const std::vector<TreeClone>& clones = L.clones;
+	const std::vector<TreeRow>& ri = L.ri;
+	const std::vector<u32>& row_item = L.row_item;
+	const u64 total = L.total;
+	inf.largest_clone = L.largest;
 	inf.clones = (u32) clones.size();
 	inf.edges = (u64) rows - clones.size();
 	while ((1ull << inf.rounds) < inf.largest_clone) inf.rounds++;
-	// the work items: (clone, row block, column slice), as vdjx_lineage sizes them: the slice is a whole number of 64 columns, as wide as
-	// it takes for about TREE_TARGET_ITEMS items in all.  A clone of one has none.
-	const u64 per = (cells + (u64) TREE_ROWS * TREE_TARGET_ITEMS - 1) / ((u64) TREE_ROWS * TREE_TARGET_ITEMS);
-	const u32 slice = (u32) std::max<u64>(TREE_ROWS, (per + TREE_ROWS - 1) / TREE_ROWS * TREE_ROWS);
 	std::vector<TreeItem> items;
-	for (const Clone& q : clones) {
-		if (q.m < 2) continue;
-		const u32 end = q.first + q.m;
-		for (u32 r0 = q.first; r0 < end; r0 += TREE_ROWS)
-			for (u32 c0 = q.first; c0 < end; c0 += slice)
-				items.push_back({r0, std::min(end, r0 + TREE_ROWS), c0, std::min(end, c0 + slice), q.words, q.first, q.wbase, 0u});
-	}
+	tree_items(clones, L.cells, items);
 	const u32 cap = (u32) inf.edges;
 	std::vector<u64> edges(cap ? cap : 1);
 	u32 n_edges = 0;
@@ -321,28 +429,12 @@ extern "C" int vdjx_tree(vdjx_ctx* c, const char* contigs, size_t n, int len, co
 		HIP_TRY(hipMemcpyAsync(d_ri, ri.data(), ((size_t) rows + 1) * sizeof(TreeRow), hipMemcpyHostToDevice, st));
 		HIP_TRY(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(TreeItem), hipMemcpyHostToDevice, st));
 		HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(u32), st));
-		const u32 nb = (rows + 255u) / 256u;
 		{
 			vdjx_prof_scope ps(c, "k_tree_pack");
 			hipLaunchKernelGGL(k_tree_pack, dim3((u32) ((total + 255) / 256)), dim3(256), 0, st, (const char*) d_contigs, (const TreeRow*) d_ri, rows, (u32) total,
 			                   d_words, d_comp, d_parent, d_best);
 		}
-		for (u32 round = 0; round < inf.rounds; round++) {
-			{
-				vdjx_prof_scope ps(c, round ? "k_tree_min" : "k_tree_min_first");      // (the first round skips no column: the pass to measure)
-				hipLaunchKernelGGL(k_tree_min, dim3((u32) items.size()), dim3(64), 0, st, (const TreeItem*) d_items, (const ulonglong2*) d_words,
-				                   (const u32*) d_comp, d_best);
-			}
-			{
-				vdjx_prof_scope ps(c, "k_tree_hook");
-				hipLaunchKernelGGL(k_tree_hook, dim3(nb), dim3(256), 0, st, (const u32*) d_comp, (const unsigned long long*) d_best, rows, d_parent, d_edges, cap,
-				                   d_count);
-			}
-			{
-				vdjx_prof_scope ps(c, "k_tree_flat");
-				hipLaunchKernelGGL(k_tree_flat, dim3(nb), dim3(256), 0, st, (const u32*) d_parent, rows, d_comp, d_best);
-			}
-		}
+		tree_rounds(c, st, inf.rounds, d_items, (u32) items.size(), d_words, rows, d_comp, d_parent, d_best, d_edges, cap, d_count);
 		HIP_TRY(hipMemcpyAsync(&n_edges, d_count, sizeof n_edges, hipMemcpyDeviceToHost, st));
 		HIP_TRY(hipMemcpyAsync(edges.data(), d_edges, (size_t) cap * sizeof(u64), hipMemcpyDeviceToHost, st));
 		HIP_TRY(hipStreamSynchronize(st));
@@ -367,7 +459,7 @@ extern "C" int vdjx_tree(vdjx_ctx* c, const char* contigs, size_t n, int len, co
 	}
 	std::vector<u32> queue(rows);
 	u32 reached = 0;
-	for (const Clone& q : clones) {
+	for (const TreeClone& q : clones) {
 		u32 head = reached;
 		queue[reached++] = q.root;
 		out_depth[row_item[q.root]] = 0;
@@ -389,5 +481,181 @@ extern "C" int vdjx_tree(vdjx_ctx* c, const char* contigs, size_t n, int len, co
 	c->stats["tree_work_items"] = items.size();
 	c->stats["tree_rounds"] = inf.rounds;
 	c->stats["tree_us"] = (u64) std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
+	return VDJX_OK;
+}
+
+// splitmix64's output step (include/vdjx.h: the keep rule)
+static inline u64 tree_mix64(u64 x) {
+	u64 z = x + 0x9E3779B97F4A7C15ull;
+	z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+	z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+	return z ^ (z >> 31);
+}
+
+// vdjx_tree_support -- the delete-half jackknife over the window's columns.  The host lays the clones of two and more out once ("per
+// replicate": member p of M), computes every replicate's kept positions and, per batch of whole replicates, the rows (replicate-major:
+// row = replicate * M + p) with their kept counts and the work items; a batch is 1 + 3 * rounds + 1 dispatches: k_tree_pack_sel, the
+// rounds of vdjx_tree on rows of about half the words, k_tree_support.  Only the edge count comes back per batch.
+extern "C" int vdjx_tree_support(vdjx_ctx* c, const char* contigs, size_t n, int len, const int32_t* clone, const int32_t* anchor, const int32_t* parent,
+                                 const vdjx_tree_support_params* params, int32_t* out_support, vdjx_tree_support_info* info) {
+	static const char* who = "vdjx_tree_support";
+	if (info) memset(info, 0, sizeof *info);
+	if (!c) { vdjx_set_error("%s: NULL argument", who); return VDJX_EINVAL; }
+	if (n == 0) return VDJX_OK;
+	if (!contigs || !clone || !anchor || !params) { vdjx_set_error("%s: NULL argument", who); return VDJX_EINVAL; }
+	if (!parent) { vdjx_set_error("%s: NULL argument (parent)", who); return VDJX_EINVAL; }
+	if (!out_support) { vdjx_set_error("%s: NULL argument (out_support)", who); return VDJX_EINVAL; }
+	if (params->replicates < 1 || params->replicates > 1024) { vdjx_set_error("%s: %u replicates (1 .. 1024)", who, params->replicates); return VDJX_EINVAL; }
+	if (int rc = tree_check_contigs(who, contigs, n, len)) return rc;
+	const auto t0 = std::chrono::steady_clock::now();
+	const u32 B = params->replicates;
+	std::vector<u64> keys;
+	if (int rc = tree_keys(who, n, len, clone, anchor, keys)) return rc;
+	vdjx_tree_support_info inf;
+	memset(&inf, 0, sizeof inf);
+	for (size_t i = 0; i < n; i++) {
+		const int32_t p = parent[i];
+		if (p < -1 || (p >= 0 && (size_t) p >= n)) { vdjx_set_error("%s: parent of item %zu is %d (-1 .. %zu)", who, i, p, n - 1); return VDJX_EINVAL; }
+		if (p < 0) continue;
+		if (clone[i] < 0) { vdjx_set_error("%s: parent of item %zu is %d, but the item is in no clone", who, i, p); return VDJX_EINVAL; }
+		if ((size_t) p == i) { vdjx_set_error("%s: parent of item %zu is the item itself", who, i); return VDJX_EINVAL; }
+		if (clone[p] != clone[i]) { vdjx_set_error("%s: parent of item %zu is %d, of another clone (%d, not %d)", who, i, p, clone[p], clone[i]); return VDJX_EINVAL; }
+		inf.edges++;
+	}
+	const u32 rows = (u32) keys.size();
+	TreeLay L;
+	if (rows)
+		if (int rc = tree_lay(who, keys, len, clone, anchor, nullptr, L)) return rc;
+	for (size_t i = 0; i < n; i++) out_support[i] = parent[i] >= 0 ? 0 : -1;
+	inf.members = rows;
+	inf.clones = (u32) L.clones.size();
+	inf.largest_clone = L.largest;
+	inf.replicates = B;
+	while ((1ull << inf.rounds) < inf.largest_clone) inf.rounds++;
+	// per replicate: the members of the clones of two and more, in row order
+	struct Big { u32 first, m, w; };
+	std::vector<Big> big;
+	std::vector<u32> item;
+	std::vector<u64> at;
+	u32 maxw = 0;
+	for (const TreeClone& q : L.clones) {
+		if (q.m < 2) continue;
+		big.push_back({(u32) item.size(), q.m, q.w});
+		for (u32 r = q.first; r < q.first + q.m; r++) {
+			item.push_back(L.row_item[r]);
+			at.push_back(L.ri[r].at);
+		}
+		maxw = std::max(maxw, q.w);
+	}
+	const u32 M = (u32) item.size(), per_edges = M - (u32) big.size();
+	u64 work_items = 0;
+	if (M) {
+		const u32 row_budget = (u32) vdjx_env_num("VDJX_TREE_SUPPORT_ROWS", (1 << 20) - 1, 1, (1 << 20) - 1);
+		const u32 per_batch = std::max(1u, row_budget / M);
+		HIP_TRY(hipSetDevice(c->device));
+		hipStream_t st = c->stream;
+		vdjx_work wk(c);
+		char* d_contigs;
+		u32 *d_item, *d_support;
+		int32_t* d_scored;
+		HIP_TRY(wk.alloc(&d_contigs, n * (size_t) len));
+		HIP_TRY(wk.alloc(&d_item, M));
+		HIP_TRY(wk.alloc(&d_scored, n));
+		HIP_TRY(wk.alloc(&d_support, n));
+		HIP_TRY(hipMemcpyAsync(d_contigs, contigs, n * (size_t) len, hipMemcpyHostToDevice, st));
+		HIP_TRY(hipMemcpyAsync(d_item, item.data(), (size_t) M * sizeof(u32), hipMemcpyHostToDevice, st));
+		HIP_TRY(hipMemcpyAsync(d_scored, parent, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+		HIP_TRY(hipMemsetAsync(d_support, 0, n * sizeof(u32), st));
+		const vdjx_arena::mark_t mk = wk.mark();
+		std::vector<uint16_t> sel;
+		std::vector<TreeRow> ri;
+		std::vector<TreeClone> bc;
+		std::vector<TreeItem> items;
+		for (u32 r0 = 0; r0 < B; r0 += per_batch) {
+			const u32 reps = std::min(per_batch, B - r0), brows = reps * M, cap = reps * per_edges;
+			sel.assign((size_t) reps * maxw, 0);
+			ri.resize((size_t) brows + 1);
+			bc.clear();
+			items.clear();
+			u64 total = 0, cells = 0;
+			for (u32 k = 0; k < reps; k++) {
+				const u64 r = (u64) r0 + k + 1;                 // replicates count from 1
+				uint16_t* mine = sel.data() + (size_t) k * maxw;
+				u32 kept = 0;
+				u64 bits = 0;
+				for (u32 q = 0; q < maxw; q++) {
+					if ((q & 31u) == 0) bits = tree_mix64(params->seed ^ (r << 32 | (u64) (q >> 5)));
+					if (bits >> (q & 31u) & 1u) mine[kept++] = (uint16_t) q;
+				}
+				for (const Big& g : big) {
+					const u32 kw = (u32) (std::lower_bound(mine, mine + kept, (uint16_t) g.w) - mine);      // kept positions below the clone's w (w < 4096)
+					const u32 words = std::max(1u, (kw + 31u) / 32u), first = k * M + g.first;
+					if (total + (u64) g.m * words > 0xFFFFFFFFull) { vdjx_set_error("%s: more than 2^32 packed words", who); return VDJX_ELIMIT; }
+					for (u32 p = 0; p < g.m; p++) ri[first + p] = {at[g.first + p], (u32) total + p * words, kw};
+					bc.push_back({first, g.m, words, (u32) total, first, kw});
+					total += (u64) g.m * words;
+					cells += (u64) g.m * g.m;
+				}
+			}
+			ri[brows] = {0, (u32) total, 0};
+			tree_items(bc, cells, items);
+			work_items += items.size();
+			uint16_t* d_sel;
+			TreeRow* d_ri;
+			TreeItem* d_items;
+			ulonglong2* d_words;
+			u32 *d_comp, *d_parent, *d_count;
+			unsigned long long *d_best, *d_edges;
+			HIP_TRY(wk.alloc(&d_sel, sel.size()));
+			HIP_TRY(wk.alloc(&d_ri, (size_t) brows + 1));
+			HIP_TRY(wk.alloc(&d_items, items.size()));
+			HIP_TRY(wk.alloc(&d_words, (size_t) total));
+			HIP_TRY(wk.alloc(&d_comp, brows));
+			HIP_TRY(wk.alloc(&d_parent, brows));
+			HIP_TRY(wk.alloc(&d_best, brows));
+			HIP_TRY(wk.alloc(&d_edges, cap));
+			HIP_TRY(wk.alloc(&d_count, 1));
+			HIP_TRY(hipMemcpyAsync(d_sel, sel.data(), sel.size() * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+			HIP_TRY(hipMemcpyAsync(d_ri, ri.data(), ((size_t) brows + 1) * sizeof(TreeRow), hipMemcpyHostToDevice, st));
+			HIP_TRY(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(TreeItem), hipMemcpyHostToDevice, st));
+			HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(u32), st));
+			{
+				vdjx_prof_scope ps(c, "k_tree_pack_sel");
+				hipLaunchKernelGGL(k_tree_pack_sel, dim3((u32) ((total + 255) / 256)), dim3(256), 0, st, (const char*) d_contigs, (const TreeRow*) d_ri, brows, (u32) total,
+				                   (const uint16_t*) d_sel, maxw, M, d_words, d_comp, d_parent, d_best);
+			}
+			tree_rounds(c, st, inf.rounds, d_items, (u32) items.size(), d_words, brows, d_comp, d_parent, d_best, d_edges, cap, d_count);
+			{
+				vdjx_prof_scope ps(c, "k_tree_support");
+				hipLaunchKernelGGL(k_tree_support, dim3((cap + 255u) / 256u), dim3(256), 0, st, (const unsigned long long*) d_edges, (const u32*) d_count, cap, brows, M,
+				                   (const u32*) d_item, (const int32_t*) d_scored, d_support);
+			}
+			u32 n_edges = 0;
+			HIP_TRY(hipMemcpyAsync(&n_edges, d_count, sizeof n_edges, hipMemcpyDeviceToHost, st));
+			HIP_TRY(hipStreamSynchronize(st));
+			HIP_TRY(hipGetLastError());
+			vdjx_prof_collect(c, false);
+			if (n_edges != cap) {
+				vdjx_set_error("%s: %u edges for %u members in %zu clones of %u replicates", who, n_edges, M, big.size(), reps);
+				return VDJX_ESTATE;
+			}
+			wk.release_to(mk);
+			inf.batches++;
+		}
+		std::vector<u32> support(n);
+		HIP_TRY(hipMemcpyAsync(support.data(), d_support, n * sizeof(u32), hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipStreamSynchronize(st));
+		for (size_t i = 0; i < n; i++) {
+			if (parent[i] < 0) continue;
+			if (support[i] > B) { vdjx_set_error("%s: item %zu counted in %u of %u replicates", who, i, support[i], B); return VDJX_ESTATE; }
+			out_support[i] = (int32_t) support[i];
+			inf.matched += support[i];
+			inf.full += support[i] == B;
+		}
+	}
+	if (info) *info = inf;
+	c->stats["tree_support_batches"] = inf.batches;
+	c->stats["tree_support_work_items"] = work_items;
+	c->stats["tree_support_us"] = (u64) std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
 	return VDJX_OK;
 }

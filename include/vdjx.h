@@ -336,7 +336,8 @@ int vdjx_quant(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const vdjx
  *               the M/I/D runs 5' to 3' as len << 4 | op (op 0 M, 1 I, 2 D: BAM's codes); n_runs counts them all, runs[] holds them only
  *               when n_runs <= 64 (otherwise zeros: the CIGAR is written empty, stat "annot_cigar_truncated").  S = 0: no traceback
  *               (coordinates and counts 0).  identity = matches / (matches + mismatches + ins + del).
- * NOT modelled: IMGT-gapped sequence_alignment / germline_alignment; reverse-complement contigs (a contig is always V to J);
+ * NOT modelled: IMGT gaps and numbering (the ungapped sequence_alignment / germline_alignment rows are vdjx_mutations' below: `vdjer
+ * --mutations` fills the two AIRR cells); reverse-complement contigs (a contig is always V to J);
  * IgBLAST's or V-QUEST's own identity definitions.  The isotype is a call of its own against a constant-region set (vdjx_isotype below),
  * the D gene a call of its own against the D records, between the V and the J hit (vdjx_dcall below).
  * VDJX_EINVAL: contigs of unequal length (a NUL inside the n*len characters), len >= 4096, a V/J germline of 0 or >= 2048 bases, 2^20
@@ -532,6 +533,67 @@ typedef struct { uint32_t members, clones, largest_clone, replicates, batches, r
 int vdjx_tree_support(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const int32_t* clone, const int32_t* anchor,
                       const int32_t* parent, const vdjx_tree_support_params* params, int32_t* out_support, vdjx_tree_support_info* info);
 
+/* ---- germline rows and R/S mutation counts: the contig and its V(D)J germline side by side, classified codon by codon ----------------
+ * gives `vdjer --mutations` what Change-O's CreateGermlines and shazam's observedMutations make of V'DJer's output in a second tool: the
+ * sequence_alignment / germline_alignment / germline_alignment_d_mask rows and the replacement / silent mutation counts of the V segment.
+ * All arithmetic is integer: the device's results are bitwise the model's (tests/mutation_model.py).
+ *   inputs      contigs, n, len as vdjx_annotate takes them; v[n], j[n] and d[n] (d may be NULL) are hits as vdjx_annotate / vdjx_dcall
+ *               return them, but any CONSISTENT hit is accepted (the VDJX_EINVAL list below is what consistent means); limit[n] (NULL:
+ *               len for every contig) bounds the contig positions whose V mutations are counted.  A hit is USABLE when gene >= 0, score >
+ *               0 and n_runs <= VDJX_ANNOT_RUNS; a hit with gene >= 0, score > 0 and more than 64 runs has no runs to read: it is treated
+ *               as absent, sets flag 16 and counts in info->truncated (per hit).  gene indexes the records as they were given to
+ *               vdjx_germline_load (v, j) or vdjx_dsegment_load (d).  A germline base whose stored code is not ACGT prints as N.
+ *   columns     of contig i, V usable; the alignment starts at contig position v.seq_start:
+ *               1. V columns, from V's runs 5' to 3': an M run of k gives k columns (contig base, germline base), an I run (contig
+ *                  base, '-'), a D run ('-', germline base).
+ *               2. J, when usable: j.seq_start > v.seq_end keeps all its columns.  Otherwise J is clipped (flag 8, info->clipped): its
+ *                  columns are dropped from its 5' end up to, not including, the first column that carries a contig base at a position >
+ *                  v.seq_end (D columns directly before it go too); when there is no such column J is not used (flag 8 stays set).
+ *               3. gap columns, when J is used: g0 = v.seq_end, g1 = the contig position of J's first kept contig base - 1; the gap is the
+ *                  contig positions g0 + 1 .. g1 (empty whenever J was clipped).  With d given, d[i] usable, d.seq_start > g0 and d.seq_end
+ *                  <= g1: np1 = d.seq_start - g0 - 1 columns (contig base, 'N'), the D hit's columns by its runs as for V, np2 = g1 -
+ *                  d.seq_end columns (contig base, 'N').  Otherwise every gap column is (contig base, 'N').
+ *               4. J's kept columns, by its runs.
+ *               5. J not used: the alignment ends after the V columns and D is not used.
+ *   rows        sequence_alignment: the columns' first members; germline_alignment: the second; germline_alignment_d_mask: the germline
+ *               row with N in EVERY column between the last V and the first J column, the D hit's own deletion columns included (so the
+ *               three rows are equally long): CreateGermlines' default dmask, the row shazam reads.  No usable V: cols = 0, empty rows,
+ *               every count 0.
+ *   V counts    a V record is taken to begin with the first base of a codon (IMGT V-REGION records do): germline codon c is the record's
+ *               bases 3c .. 3c+2 (0-based).  A codon is CLASSIFIABLE when it lies inside germ_start .. germ_end, each of its three bases
+ *               is in an M column, those three columns are adjacent (no I between them), the three contig positions are all < limit[i]
+ *               (0-based) and all six characters are upper-case ACGT.  v_codons counts them.  Each position of a classifiable codon at
+ *               which contig and germline differ is classified on its own, in the germline's context (shazam's rule for codons with
+ *               several mutations): take the germline codon with that one base replaced by the contig's; the germline codon or the changed
+ *               one is a stop: v_stop; else both translate alike: v_s; else v_r.  The genetic code is the standard one.  v_na counts
+ *               every other V M column at a contig position < limit[i] whose two characters differ or are not both ACGT.  So v_r + v_s +
+ *               v_stop + v_na = the V mismatch columns below the limit by vdjx_annotate's meaning of a mismatch (v.mismatches when limit
+ *               >= v.seq_end).  j_mis: the kept J M columns that mismatch (J has no frame of its own here: no R/S).
+ *   row         cols and the counts; flags: 1 V used, 2 J used, 4 D used, 8 J clipped, 16 a hit of this contig had more than 64 runs.
+ *   info        (may be NULL; zeroed first, summed from the rows on the host) contigs = n; aligned: rows with flag 1; cols .. v_codons:
+ *               the sums; truncated: hits over 64 runs; clipped: rows with flag 8.
+ *   layout      vdjx_mutations_layout (host only; no context) computes every contig's columns from the hits alone: out_off[i] is where
+ *               contig i's rows start in each of the three row buffers, out_off[n] the size of each.  Deletions make cols exceed len.
+ *   output      contig i's rows go to out_seq / out_germ / out_mask + out_off[i], cols bytes, no terminator; each of the three may be
+ *               NULL.  out_rows is required.
+ * NOT modelled: IMGT gaps and numbering, and so no CDR1 / CDR2 / FWR split of the counts; V records that begin inside a codon (IMGT's
+ * 5'-partial sequences: their codons are shifted); R/S for the J segment; expected mutation counts, targeting models (HH_S5F) and
+ * selection (BASELINe); a clonal consensus germline (CreateGermlines --cloned); a germline node as the root of `--trees`.
+ * VDJX_EINVAL (the message names the contig): a usable hit whose gene is out of range or names a record of the wrong class (v: 'V', j:
+ * 'J'); germ_end past the record's end; seq_start or germ_start < 1, seq_end > len; a run with an op outside 0..2 or a length of 0; M + I
+ * run lengths that do not sum to seq_end - seq_start + 1, M + D run lengths that do not sum to germ_end - germ_start + 1; a limit outside
+ * 0 .. len; contigs of unequal length (a NUL inside the n*len characters), len >= 4096, n >= 2^20; NULL out_rows.  VDJX_ESTATE: no
+ * germline set is loaded, or d is given and no D set is loaded.  n = 0 returns at once with a zeroed info.  The host checks the hits,
+ * computes the layout and uploads per contig 64 bytes of positions and record offsets and its usable runs (4 bytes each), not 340 bytes
+ * per hit.  A call is ONE kernel dispatch (scope "k_mutations") whatever n is.  Scratch comes from the context's workspace; no floating
+ * point, no atomics: two calls give the same bits.  Stats: "mutations_cols" (out_off[n]), "mutations_us" (host clock). */
+typedef struct { int32_t cols, v_r, v_s, v_stop, v_na, v_codons, j_mis, flags; } vdjx_mut_row;      /* 32 bytes */
+typedef struct { uint64_t contigs, aligned, cols, v_r, v_s, v_stop, v_na, v_codons; uint32_t truncated, clipped; } vdjx_mut_info;   /* 72 bytes */
+int vdjx_mutations_layout(const vdjx_annot_hit* v, const vdjx_annot_hit* d, const vdjx_annot_hit* j, size_t n, uint64_t* out_off /* n + 1 */);
+int vdjx_mutations(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const vdjx_annot_hit* v, const vdjx_annot_hit* d,
+                   const vdjx_annot_hit* j, const int32_t* limit, char* out_seq, char* out_germ, char* out_mask,
+                   vdjx_mut_row* out_rows, vdjx_mut_info* info);
+
 /* rows of `row` bytes on the device: row d_pos[i] of d_dst = row i of d_src.  (The records of a pool sharded by pair on their way to
  * the ranks that hold their slice of the scan order for the k-mer build, A2:1388-1390: every record arrives with its place.) */
 int vdjx_rows_scatter(vdjx_ctx* ctx, void* d_dst, const void* d_src, const uint32_t* d_pos, size_t n, size_t row);
@@ -559,6 +621,7 @@ int vdjx_part_u64(vdjx_ctx* ctx, const void* host_in, size_t n, int elem_bytes, 
  * vdjx_annotate's last call: "annot_cells" (DP cells of the scoring phase), "annot_score_us", "annot_trace_us", "annot_cigar_truncated".
  * vdjx_isotype's last call: "iso_cells" (DP cells of the scoring phase), "iso_score_us", "iso_trace_us" (host clock, each ending in a wait).
  * vdjx_dcall's last call: "dcall_cells" (the sum of win_len times the sum of the records' lengths), "dcall_score_us", "dcall_trace_us".
+ * vdjx_mutations' last call: "mutations_cols" (the bytes of each of the three row buffers), "mutations_us" (host clock).
  * What the context keeps from call to call outside its workspaces (anchor bitmaps, V region, read index, the scorers' result and SAM
  * buffers, upload staging, germline / constant / D sets), counted when asked: "kept_device_bytes", "kept_pinned_bytes" (page-locked host
  * memory) and "kept_allocs" (allocations made for them since vdjx_init: unchanged by a call that fitted what was there).  vdjx_trim

@@ -154,6 +154,18 @@ def tree_inputs(ids, contigs, v, clone):
     return anchor, prio
 
 
+def mutation_limit(ids, contigs):
+    """the limit `vdjer --mutations` hands to vdjx_mutations -> int32[n]: V mutations are counted below the 0-based start of the junction
+    (junction_of) plus 3, through the conserved Cys codon: what follows is the CDR3, where the germline row is not the V gene's to
+    judge by.  The contig's length when the junction is not found."""
+    import numpy as np
+    out = np.zeros(len(ids), np.int32)
+    for c, (cid, s) in enumerate(zip(ids, contigs)):
+        p = junction_of(cid, s)[0]
+        out[c] = min(p + 3, len(s)) if p >= 0 else len(s)
+    return out
+
+
 def _mix64(x):
     """splitmix64's output step, in 64-bit wrap-around arithmetic"""
     m = (1 << 64) - 1

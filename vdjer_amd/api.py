@@ -724,6 +724,51 @@ class Context:
         check(self.L.vdjx_dcall(self.h, raw, n, ln, _p(ws), _p(wl), C.byref(prm), _p(hd), _p(sc) if scores and sc.size else None), "vdjx_dcall")
         return {"d": {f: hd[f].copy() for f in self.ANNOT_HIT.names}, "scores": sc}
 
+    MUT_ROW = np.dtype([(f, "<i4") for f in ("cols", "v_r", "v_s", "v_stop", "v_na", "v_codons", "j_mis", "flags")])
+    MUT_INFO_FIELDS = ("contigs", "aligned", "cols", "v_r", "v_s", "v_stop", "v_na", "v_codons", "truncated", "clipped")
+
+    def _hit_array(self, h, n, what):
+        """the field dict of annotate() / dcall() as an array of vdjx_annot_hit"""
+        out = np.zeros(n, self.ANNOT_HIT)
+        for f in self.ANNOT_HIT.names:
+            a = np.asarray(h[f])
+            if a.shape != out[f].shape:
+                raise VdjxError(f"vdjx_mutations: {n} contigs, {what}[{f!r}] of shape {a.shape}")
+            out[f] = a
+        return out
+
+    def mutations(self, contigs, v, j, d=None, limit=None, rows: bool = True):
+        """vdjx_mutations: every contig and its V(D)J germline side by side, and the V segment's replacement / silent / stop mutation
+        counts.  v, j, d: the field dicts annotate() and dcall() return (d may be None); limit: int32[n] or None (the contig's length)
+        -> {"seq", "germ", "mask": list[str] | None (rows=False: no row is fetched), "counts": {field: int32[n]} (cols, v_r, v_s, v_stop,
+        v_na, v_codons, j_mis, flags), "info": dict}"""
+        if isinstance(contigs, tuple):
+            raw, n, ln = contigs
+        else:
+            if len({len(s_) for s_ in contigs}) > 1:
+                raise VdjxError("vdjx_mutations: contigs of unequal length")
+            raw, n, ln = self.pack_strings(contigs)
+        hv, hj = self._hit_array(v, n, "v"), self._hit_array(j, n, "j")
+        hd = None if d is None else self._hit_array(d, n, "d")
+        lim = None if limit is None else np.ascontiguousarray(limit, np.int32)
+        if lim is not None and lim.shape != (n,):
+            raise VdjxError(f"vdjx_mutations: {n} contigs, limit of shape {lim.shape}")
+        off = np.zeros(n + 1, np.uint64)
+        check(self.L.vdjx_mutations_layout(_p(hv), _p(hd), _p(hj), n, _p(off)), "vdjx_mutations_layout")
+        total = int(off[n])
+        bufs = [np.zeros(max(total, 1), np.uint8) for _ in range(3)] if rows else [None] * 3
+        out = np.zeros(n, self.MUT_ROW)
+        info = _lib.MutInfo()
+        check(self.L.vdjx_mutations(self.h, raw, n, ln, _p(hv), _p(hd), _p(hj), _p(lim), _p(bufs[0]), _p(bufs[1]), _p(bufs[2]), _p(out),
+                                    C.byref(info)), "vdjx_mutations")
+        text = [None] * 3
+        if rows:
+            for k in range(3):
+                b = bufs[k].tobytes()
+                text[k] = [b[int(off[i]):int(off[i + 1])].decode("latin-1") for i in range(n)]
+        return {"seq": text[0], "germ": text[1], "mask": text[2], "counts": {f: out[f].copy() for f in self.MUT_ROW.names},
+                "info": {f: int(getattr(info, f)) for f in self.MUT_INFO_FIELDS}}
+
     LINEAGE_NONE = 0xFFFFFFFF                                # VDJX_LINEAGE_NONE (include/vdjx.h)
 
     def lineage(self, junctions, group, max_dist=(1500, 10000), nearest: bool = True):

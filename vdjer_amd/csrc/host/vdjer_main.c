@@ -5,7 +5,7 @@
  *   vdjer --in <reads> --chain IGH|IGK|IGL --ref-dir <dir> --ins <n> [--t --k --mf --mq --mcs --am --miw --maw
  *         --jc --ws -jext --rf --vk --mrs --rs --ms --e0 --e1 --wo --vf --jf --rms] [--gpus N] [--quant <file>] [--airr <file>]
  *         [--d-calls] [--cfa <fasta>] [--isotypes <file>] [--clones <file>] [--sample <name>] [--total-count <n>]
- *         [--lineages <file>] [--lineage-dist <x>] [--trees <file>] [--tree-support <B>] [--tree-seed <s>]
+ *         [--lineages <file>] [--lineage-dist <x>] [--trees <file>] [--tree-support <B>] [--tree-seed <s>] [--mutations <file>]
  * writes ./vdj_contigs.fa and ./vdjer.dot, SAM on stdout, log on stderr; exit 0 on success.  --quant <file>: the contigs' abundances
  * (vdjx_quant, RSEM's isoforms.results columns) into <file> as well.  --airr <file>: the contigs' V/J annotation (vdjx_annotate against
  * the germlines of ig_vdj.fa / --vdjf) as an AIRR Rearrangement TSV; with --d-calls (a flag: no value) the D gene between the V and the
@@ -17,6 +17,9 @@
  * the tree inside every lineage (vdjx_tree: the minimum spanning tree under the Hamming distance over the members' common window around
  * the junction, rooted at the member closest to its germline V); --tree-support <B> (with --trees): a support column, the share of B
  * delete-half jackknife replicates whose tree has the edge to the parent (vdjx_tree_support), the columns drawn from --tree-seed <s>.
+ * --mutations <file>: every contig and its V(D)J germline side by side and the V segment's replacement / silent / stop mutation counts
+ * (vdjx_mutations: Change-O CreateGermlines and shazam observedMutations); with --airr the table's sequence_alignment and
+ * germline_alignment cells are filled, with --d-calls the D hit's germline is laid into the gap, with --lineages the table gets a clone_id.
  *
  * --in: a BAM with its .bai (extraction as bam_read.c:264-446, restated over zlib in bamx.c), or -- recognised by its
  * content -- the extracted read pool as text, one read per line in extraction order:
@@ -67,6 +70,7 @@ typedef struct {
 	const char* trees;                     /* --trees <file> (not in the reference): the tree inside every lineage of --lineages, on the device */
 	const char *tree_support, *tree_seed;  /* --tree-support <B>, --tree-seed <s>: the jackknife support of the trees' edges; read into ts_b (0: none) and ts_seed */
 	uint32_t ts_b; uint64_t ts_seed;
+	const char* mutations;                 /* --mutations <file> (not in the reference): CreateGermlines / observedMutations, on the device */
 	int have_chain, have_ref;
 } cli;
 
@@ -92,7 +96,8 @@ static void usage(void) {
 	                "\t--lineage-dist <largest linked distance as a fraction of the junction length, in [0,1], at most 4 decimals (default: 0.15)>\n"
 	                "\t--trees <file: with --lineages, the minimum spanning tree inside every lineage: parent, distance and depth of every contig>\n"
 	                "\t--tree-support <B: with --trees, a support column from B delete-half jackknife replicates, a whole number in 1 .. 1024>\n"
-	                "\t--tree-seed <seed of the replicates' columns, a whole number below 2^64 (default: 1)>\n");
+	                "\t--tree-seed <seed of the replicates' columns, a whole number below 2^64 (default: 1)>\n"
+	                "\t--mutations <file: every contig beside its V(D)J germline, and the V segment's replacement / silent / stop mutation counts>\n");
 }
 
 static int file_exists(const char* f) { struct stat b; return stat(f, &b) == 0; }
@@ -168,6 +173,7 @@ static int parse(int argc, char** argv, cli* c) {
 		else if (!strcmp(a, "--trees")) c->trees = v;
 		else if (!strcmp(a, "--tree-support")) c->tree_support = v;
 		else if (!strcmp(a, "--tree-seed")) c->tree_seed = v;
+		else if (!strcmp(a, "--mutations")) c->mutations = v;
 		else if (!strcmp(a, "--vf")) snprintf(c->v_anchors, sizeof c->v_anchors, "%s", v);
 		else if (!strcmp(a, "--jf")) snprintf(c->j_anchors, sizeof c->j_anchors, "%s", v);
 		else if (!strcmp(a, "--am")) c->anchor_mismatches = atoi(v);
@@ -588,6 +594,9 @@ typedef struct {
 	const char* trees; vdjx_tree_info ti;
 	/* --tree-support: the jackknife support of the trees' edges (tree_run) */
 	uint32_t ts_b; uint64_t ts_seed; vdjx_tree_support_info tsi;
+	/* --mutations: the germline rows of every contig (mut_run), kept for the --airr table's two alignment cells */
+	const char* mutations; int mut_done;
+	uint64_t* mu_off; char *mu_seq, *mu_germ; vdjx_mut_info mi;
 } hook_ud;
 
 static int h_root_score(void* ud, const char* kmers, size_t n, int k, int thr, uint8_t* out) {
@@ -770,7 +779,7 @@ static long junction_at(const char* id, const char* s, int len, const char** jn_
 /* the V / J hits of every contig (vdjx_annotate against the germlines of ig_vdj.fa / --vdjf), kept for the tables */
 static int annot_run(hook_ud* u, const char* contigs, size_t n, int len) {
 	u->germ = (germ_set*) calloc(1, sizeof(germ_set));
-	if (germ_read(u->vdjf, u->germ, u->airr ? "--airr: cannot read the germline FASTA" : u->clones ? "--clones: cannot read the germline FASTA" : "--lineages: cannot read the germline FASTA")) return -1;
+	if (germ_read(u->vdjf, u->germ, u->airr ? "--airr: cannot read the germline FASTA" : u->clones ? "--clones: cannot read the germline FASTA" : u->lineages ? "--lineages: cannot read the germline FASTA" : "--mutations: cannot read the germline FASTA")) return -1;
 	const germ_set* g = u->germ;
 	for (size_t r = 0; r < g->n; r++) {
 		if (g->cls[r] == 'V' || g->cls[r] == 'J') continue;
@@ -781,7 +790,7 @@ static int annot_run(hook_ud* u, const char* contigs, size_t n, int len) {
 	const vdjx_annot_params ap = {2, 3, 5, 2, 40, 20};
 	int rc = vdjx_germline_load(u->gx, g->seqs, g->off, g->cls, g->n);
 	if (!rc && n) rc = vdjx_annotate(u->gx, contigs, n, len, &ap, u->hv, u->hj);
-	if (rc) fprintf(stderr, "%s: %s\n", u->airr ? "--airr" : u->clones ? "--clones" : "--lineages", vdjx_last_error());
+	if (rc) fprintf(stderr, "%s: %s\n", u->airr ? "--airr" : u->clones ? "--clones" : u->lineages ? "--lineages" : "--mutations", vdjx_last_error());
 	return rc;
 }
 
@@ -883,7 +892,10 @@ static int airr_table(hook_ud* u, const char* const* ids, const char* contigs, s
 			if (u->d_calls) put_call(fp, u->hd + i, u->dset);
 			fputc('\t', fp);
 			put_call(fp, j, &g);
-			fputs("\t\t\t", fp);
+			if (u->mutations) {               /* mut_run's rows: the contig and its germline, column by column */
+				const int cols = (int) (u->mu_off[i + 1] - u->mu_off[i]);
+				fprintf(fp, "\t%.*s\t%.*s\t", cols, cols ? u->mu_seq + u->mu_off[i] : "", cols, cols ? u->mu_germ + u->mu_off[i] : "");
+			} else fputs("\t\t\t", fp);
 			fprintf(fp, "%.*s\t", (int) JL, p >= 0 ? s + p : "");
 			put_aa(fp, p >= 0 ? s + p : "", JL);
 			const size_t cl = JL >= 6 ? JL - 6 : 0;
@@ -1190,14 +1202,72 @@ static int tree_run(hook_ud* u, const char* const* ids, const char* contigs, siz
 	return rc;
 }
 
+/* --mutations: the germline rows and the V mutation counts of every contig (the model: include/vdjx.h, vdjx_mutations; the limit:
+ * mutation_limit of vdjer_amd/annot.py).  V mutations are counted below the junction's start + 3, through the conserved Cys codon: what
+ * follows is the CDR3.  The D hits of --d-calls are laid into the gap; the rows are kept for the --airr table. */
+static int mut_run(hook_ud* u, const char* const* ids, const char* contigs, size_t n, int len) {
+	FILE* fp = fopen(u->mutations, "w");
+	if (!fp) { fprintf(stderr, "cannot write %s\n", u->mutations); return -1; }
+	const germ_set g = *u->germ;
+	const vdjx_annot_hit* hd = u->d_calls ? u->hd : NULL;
+	u->mu_off = (uint64_t*) calloc(n + 1, sizeof(uint64_t));
+	int32_t* lim = (int32_t*) calloc(n + 1, sizeof(int32_t));
+	vdjx_mut_row* rows = (vdjx_mut_row*) calloc(n + 1, sizeof(vdjx_mut_row));
+	char* mask = NULL;
+	for (size_t i = 0; i < n; i++) {
+		const char* jn;
+		size_t jl;
+		const long p = junction_at(ids[i], contigs + i * (size_t) len, len, &jn, &jl);
+		lim[i] = p >= 0 && p + 3 < len ? (int32_t) p + 3 : len;
+	}
+	int rc = n ? vdjx_mutations_layout(u->hv, hd, u->hj, n, u->mu_off) : 0;
+	if (!rc) {
+		const size_t total = (size_t) u->mu_off[n];
+		u->mu_seq = (char*) malloc(total + 1);
+		u->mu_germ = (char*) malloc(total + 1);
+		mask = (char*) malloc(total + 1);
+		rc = vdjx_mutations(u->gx, contigs, n, len, u->hv, hd, u->hj, lim, u->mu_seq, u->mu_germ, mask, rows, &u->mi);
+	}
+	if (rc) fprintf(stderr, "--mutations: %s\n", vdjx_last_error());
+	if (!rc) {
+		fputs("sequence_id\tv_call\tj_call\tsequence_alignment\tgermline_alignment\tgermline_alignment_d_mask\tv_germline_codons\tmu_count_v_r\t"
+		      "mu_count_v_s\tmu_count_v_stop\tmu_count_v_na\tmu_freq_v\tmu_count_j", fp);
+		fputs(u->lineages ? "\tclone_id\n" : "\n", fp);
+		for (size_t i = 0; i < n; i++) {
+			const vdjx_mut_row* r = rows + i;
+			fprintf(fp, "%s\t", ids[i]);
+			put_call(fp, u->hv + i, &g);
+			fputc('\t', fp);
+			put_call(fp, u->hj + i, &g);
+			if (r->flags & 1) {
+				const int cols = r->cols;
+				const uint64_t at = u->mu_off[i];
+				fprintf(fp, "\t%.*s\t%.*s\t%.*s\t%d\t%d\t%d\t%d\t%d\t", cols, u->mu_seq + at, cols, u->mu_germ + at, cols, mask + at, r->v_codons, r->v_r,
+				        r->v_s, r->v_stop, r->v_na);
+				if (r->v_codons) fprintf(fp, "%.4f", (double) (r->v_r + r->v_s) / (double) (3 * r->v_codons));
+				fprintf(fp, "\t%d", r->j_mis);
+			} else fputs("\t\t\t\t\t\t\t\t\t\t", fp);
+			if (u->lineages) { if (u->lin_clone[i] >= 0) fprintf(fp, "\tlin_%d", u->lin_clone[i] + 1); else fputc('\t', fp); }
+			fputc('\n', fp);
+		}
+	}
+	free(lim);
+	free(rows);
+	free(mask);
+	if (fclose(fp) && !rc) { fprintf(stderr, "cannot write %s\n", u->mutations); return -1; }
+	if (!rc) u->mut_done = 1;
+	return rc;
+}
+
 /* the tables after the SAM body: every device step runs once, whichever tables ask for it */
 static int tables(hook_ud* u, const char* const* ids, const char* contigs, size_t n, int len) {
 	int rc = 0;
 	if (!rc && (u->quant || u->clones)) rc = quant_table(u, ids, contigs, n, len);
-	if (!rc && (u->airr || u->clones || u->lineages)) rc = annot_run(u, contigs, n, len);
+	if (!rc && (u->airr || u->clones || u->lineages || u->mutations)) rc = annot_run(u, contigs, n, len);
 	if (!rc && u->d_calls) rc = dcall_run(u, contigs, n, len);
 	if (!rc && u->lineages) rc = lineage_run(u, ids, contigs, n, len);
 	if (!rc && u->trees) rc = tree_run(u, ids, contigs, n, len);
+	if (!rc && u->mutations) rc = mut_run(u, ids, contigs, n, len);
 	if (!rc && u->airr) rc = airr_table(u, ids, contigs, n, len);
 	if (!rc && u->cfa && (u->isotypes || u->clones)) rc = iso_run(u, contigs, n, len);
 	if (!rc && u->isotypes) rc = isotypes_table(u, ids, n, len);
@@ -1475,7 +1545,7 @@ int main(int argc, char** argv) {
 	ud.gx = gx; ud.p = &c.hp; ud.mg = mg; ud.quant = c.quant; ud.airr = c.airr; ud.vdjf = c.vdj_fasta; ud.d_calls = c.d_calls;
 	ud.cfa = c.cfa; ud.isotypes = c.isotypes; ud.clones = c.clones; ud.total_count = c.total_count;
 	ud.lineages = c.lineages; ud.lin_num = c.lin_num; ud.lin_den = c.lin_den; ud.trees = c.trees;
-	ud.ts_b = c.ts_b; ud.ts_seed = c.ts_seed;
+	ud.ts_b = c.ts_b; ud.ts_seed = c.ts_seed; ud.mutations = c.mutations;
 	char sample_buf[4096];
 	if (c.sample) ud.sample = c.sample;
 	else {                                  /* the input's base name up to its first '.' */
@@ -1491,7 +1561,7 @@ int main(int argc, char** argv) {
 		return 1;
 	}
 	/* (no contig: the headers alone) */
-	if (!ud.quant_done && !ud.airr_done && !ud.iso_done && !ud.clones_done && !ud.lin_done && tables(&ud, NULL, NULL, 0, 0)) return 1;
+	if (!ud.quant_done && !ud.airr_done && !ud.iso_done && !ud.clones_done && !ud.lin_done && !ud.mut_done && tables(&ud, NULL, NULL, 0, 0)) return 1;
 	fprintf(stderr, "num root nodes: %zu\nProcessed roots: %zu\ncontig_candidates: %zu\nwindows scored: %zu valid: %zu\ncontigs: %zu\n",
 	        st.n_roots, st.n_roots_accepted, st.n_contig_candidates, st.n_windows_scored, st.n_windows_valid, st.n_contigs_out);
 	if (mg) {
@@ -1542,6 +1612,11 @@ int main(int argc, char** argv) {
 		        ud.cst ? ud.cst->n : (size_t) 0, c.cfa, c.isotypes);
 	if (c.clones)
 		fprintf(stderr, "clones: %zu rows in %zu clusters, isotypes %s; table in %s\n", ud.c_rows, ud.c_clusters, c.cfa ? "called" : "N/A (no --cfa)", c.clones);
+	if (c.mutations)
+		fprintf(stderr, "mutations: %llu contigs, %llu aligned, %llu columns, %llu V codons, %llu R, %llu S, %llu stop, %llu unclassified, %u J clipped, %u over 64 runs\n",
+		        (unsigned long long) ud.mi.contigs, (unsigned long long) ud.mi.aligned, (unsigned long long) ud.mi.cols, (unsigned long long) ud.mi.v_codons,
+		        (unsigned long long) ud.mi.v_r, (unsigned long long) ud.mi.v_s, (unsigned long long) ud.mi.v_stop, (unsigned long long) ud.mi.v_na,
+		        ud.mi.clipped, ud.mi.truncated);
 	fflush(stdout);
 	fflush(stderr);
 	/* the outputs are written; the orderly teardown of a context that holds gigabytes (unmapping the workspaces piece by piece, the

@@ -594,6 +594,45 @@ int vdjx_mutations(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const 
                    const vdjx_annot_hit* j, const int32_t* limit, char* out_seq, char* out_germ, char* out_mask,
                    vdjx_mut_row* out_rows, vdjx_mut_info* info);
 
+/* ---- bootstrap clonal diversity: the Hill curve D(q) of the clone abundances, resampled to a common depth -----------------------------
+ * gives `vdjer --diversity` what alakazam's estimateAbundance / alphaDiversity make of the clone table in a second tool: richness, Shannon
+ * and Simpson diversity as points of one curve, each with the spread of B bootstrap replicates rarefied to N draws, so that samples of
+ * different depth can be compared.  The draws are integer arithmetic: the device's counts are bitwise the model's
+ * (tests/diversity_model.py); the Hill numbers are float64.
+ *   inputs      weight[C]: the abundance of every clone in any unit (`vdjer`: hundredths of a read pair); a clone of weight 0 is legal
+ *               and is never drawn.  params: replicates B, depth N (the draws of a replicate), seed.  q[Q]: the orders.
+ *   draw rule   cum[0] = 0, cum[k + 1] = cum[k] + weight[k], W = cum[C].  mix64 is vdjx_tree_support's (mix64(0) = 0xE220A8397B1DCDAF).
+ *               Draw i (0 .. N - 1) of replicate r (1 .. B): u = mix64(mix64(seed) + ((uint64_t) r << 32 | i)), the addition wrapping;
+ *               t = floor(u * W / 2^64), the high half of the 128-bit product; the draw falls on the clone k with cum[k] <= t <
+ *               cum[k + 1] (an upper bound: a clone of zero width is never hit).  counts[r][k]: the draws of replicate r that fell on k.
+ *               Check values: seed 1, r 1, W 3: t for i = 0 .. 11 is 0 2 0 2 1 1 1 2 2 2 1 0; seed 0, r 1, i 0, W 2^62: t =
+ *               2241935815489788276; weight (1, 3), N 100000, seed 1, r 1: counts (24932, 75068).
+ *   Hill        for one count vector, p_k = c_k / N over the c_k > 0.  q == 0.0: the number of such k (exact); q == 1.0:
+ *               exp(-sum p ln p); otherwise (sum p^q)^(1 / (1 - q)).  out_d[(r - 1) * Q + j]: replicate r at order q[j].
+ *               out_observed[j]: the same with p_k = weight[k] / W, no resampling.  out_mean[j] and out_sd[j] (with n - 1; 0 when B = 1)
+ *               over the replicates are summed on the host in replicate order.
+ *   counts      out_counts (may be NULL): uint32 [B * C], replicate-major.
+ *   info        (may be NULL; zeroed first, every field filled on success) clones = C; weighted: the clones of weight > 0; weight = W;
+ *               depth; replicates; batches: the groups of whole replicates the device ran side by side; path: VDJX_DIV_PATH_LDS or
+ *               VDJX_DIV_PATH_GLOBAL, where the draws were counted.
+ * NOT modelled: alakazam's unseen-species (Chao1) correction of the abundances; the rank-abundance curve with its intervals; grouping by
+ * a second field; rarefaction curves over several depths; beta diversity.
+ * VDJX_EINVAL: C >= 2^20; W = 0, or W >= 2^63; replicates outside 1 .. 4096; depth outside 1 .. 2^31 - 1; Q outside 1 .. 64; an order
+ * that is NaN, below 0 or above 16; an order with 0 < |q - 1| < 1/64 (the exponent 1 / (1 - q) would magnify the sum's rounding without
+ * bound there); NULL weight, q, params, out_observed, out_d, out_mean or out_sd.  C = 0 returns at once with a zeroed info.
+ * The host sums the weights; a batch is max(1, floor(cells / C)) whole replicates (cells = VDJX_DIV_CELLS, 1 .. 2^30, the default 2^28
+ * counters) and costs one memset and three dispatches (draw, Hill partials, Hill numbers) whatever B, C and N are.  A draw workgroup
+ * counts in LDS when C <= VDJX_DIV_LDS_CLONES (0 .. 16384, the default 16384; 0: never) and flushes its non-zero bins with one atomicAdd
+ * each, otherwise it adds to global memory directly: integer adds either way, the counts do not depend on their order.  The device's
+ * float sums are stored per workgroup and added in a fixed order, no float atomics: two calls give the same bits.  Per batch only its
+ * rows of out_d and, if asked for, of out_counts come back.  Stats: "diversity_batches", "diversity_us" (host clock). */
+#define VDJX_DIV_PATH_LDS    1
+#define VDJX_DIV_PATH_GLOBAL 2
+typedef struct { uint32_t replicates, depth; uint64_t seed; } vdjx_diversity_params;                                /* 16 bytes */
+typedef struct { uint32_t clones, weighted; uint64_t weight; uint32_t depth, replicates, batches, path; } vdjx_diversity_info;   /* 32 bytes */
+int vdjx_diversity(vdjx_ctx* ctx, const uint64_t* weight, size_t C, const double* q, size_t Q, const vdjx_diversity_params* params,
+                   double* out_observed, double* out_d, double* out_mean, double* out_sd, uint32_t* out_counts, vdjx_diversity_info* info);
+
 /* rows of `row` bytes on the device: row d_pos[i] of d_dst = row i of d_src.  (The records of a pool sharded by pair on their way to
  * the ranks that hold their slice of the scan order for the k-mer build, A2:1388-1390: every record arrives with its place.) */
 int vdjx_rows_scatter(vdjx_ctx* ctx, void* d_dst, const void* d_src, const uint32_t* d_pos, size_t n, size_t row);
@@ -622,6 +661,7 @@ int vdjx_part_u64(vdjx_ctx* ctx, const void* host_in, size_t n, int elem_bytes, 
  * vdjx_isotype's last call: "iso_cells" (DP cells of the scoring phase), "iso_score_us", "iso_trace_us" (host clock, each ending in a wait).
  * vdjx_dcall's last call: "dcall_cells" (the sum of win_len times the sum of the records' lengths), "dcall_score_us", "dcall_trace_us".
  * vdjx_mutations' last call: "mutations_cols" (the bytes of each of the three row buffers), "mutations_us" (host clock).
+ * vdjx_diversity's last call: "diversity_batches", "diversity_us" (host clock).
  * What the context keeps from call to call outside its workspaces (anchor bitmaps, V region, read index, the scorers' result and SAM
  * buffers, upload staging, germline / constant / D sets), counted when asked: "kept_device_bytes", "kept_pinned_bytes" (page-locked host
  * memory) and "kept_allocs" (allocations made for them since vdjx_init: unchanged by a call that fitted what was there).  vdjx_trim

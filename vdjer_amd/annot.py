@@ -182,3 +182,39 @@ def jackknife_keep(seed, r, w):
     seed, r = int(seed), int(r)
     assert 0 <= seed < 1 << 64 and 0 <= r < 1 << 32
     return np.array([bool(_mix64(seed ^ (r << 32 | q >> 5)) >> (q & 31) & 1) for q in range(int(w))], bool)
+
+
+def diversity_orders():
+    """the orders of `vdjer --diversity`: k / 10.0 for k = 0 .. 40 (q = 1.0 exactly at k = 10)"""
+    return [k / 10.0 for k in range(41)]
+
+
+def diversity_draw(seed, r, i, W):
+    """the draw rule of vdjx_diversity (include/vdjx.h) in plain Python -> t in 0 .. W - 1: draw i (0 .. N - 1) of replicate r (1 ..
+    replicates) is the high half of the 128-bit product mix64(mix64(seed) + (r << 32 | i)) * W; it falls on the clone k with
+    cum[k] <= t < cum[k + 1]"""
+    seed, r, i, W = int(seed), int(r), int(i), int(W)
+    assert 0 <= seed < 1 << 64 and 0 <= r < 1 << 32 and 0 <= i < 1 << 32 and 0 <= W < 1 << 64
+    return _mix64((_mix64(seed) + (r << 32 | i)) & ((1 << 64) - 1)) * W >> 64
+
+
+def diversity_weights(clone, count_cells):
+    """what `vdjer --diversity` hands to vdjx_diversity, from the lineage of every contig (Context.lineage's "clone"; -1: in none) and the
+    printed expected_count cell of every contig ("12.34": two decimals, as the quant table has them) -> (uint64[C] weights, int list of
+    the lineage numbers they belong to, ascending).  A lineage's weight is the sum of its members' cells read as integer hundredths,
+    digit by digit, with no float; lineages of weight 0 and contigs in no lineage are left out."""
+    import numpy as np
+    sums = {}
+    for k, cell in zip(clone, count_cells):
+        k = int(k)
+        if k < 0:
+            continue
+        whole, point, frac = str(cell).partition(".")
+        if not (point and len(frac) == 2 and whole and all(ch in "0123456789" for ch in whole + frac)):
+            raise ValueError(f"an expected_count cell has digits, a point and two digits: {cell!r}")
+        w = 0
+        for ch in whole + frac:
+            w = w * 10 + (ord(ch) - 48)
+        sums[k] = sums.get(k, 0) + w
+    numbers = sorted(k for k, w in sums.items() if w > 0)
+    return np.array([sums[k] for k in numbers], np.uint64), numbers

@@ -840,6 +840,31 @@ class Context:
         check(self.L.vdjx_tree_support(self.h, raw, n, ln, _p(cl), _p(an), _p(pa), C.byref(params), _p(support), C.byref(info)), "vdjx_tree_support")
         return {"support": support, "info": {f: int(getattr(info, f)) for f in self.TREE_SUPPORT_FIELDS}}
 
+    DIVERSITY_FIELDS = ("clones", "weighted", "weight", "depth", "replicates", "batches", "path")
+
+    def diversity(self, weight, depth, q=None, replicates=200, seed=1, counts=False):
+        """vdjx_diversity: the Hill curve of the clone abundances, bootstrapped.  weight: uint64[C], the abundance of every clone in any unit
+        (0 is legal: never drawn); depth: the draws of a replicate, 1 .. 2^31 - 1; q: the orders, float64[Q] (None: annot.diversity_orders(),
+        0.0 .. 4.0 in tenths); replicates: 1 .. 4096; seed: any uint64 -> {"observed", "mean", "sd": float64[Q], "d": float64[B, Q],
+        "counts": uint32[B, C] (None unless counts=True), "info": dict(clones, weighted, weight, depth, replicates, batches, path)}"""
+        from . import annot
+        w = np.ascontiguousarray(weight, np.uint64)
+        qs = np.ascontiguousarray(annot.diversity_orders() if q is None else q, np.float64)
+        if w.ndim != 1 or qs.ndim != 1:
+            raise VdjxError(f"vdjx_diversity: weight of shape {w.shape}, q of shape {qs.shape}")
+        if not 0 <= int(replicates) < 1 << 32 or not 0 <= int(depth) < 1 << 32 or not 0 <= int(seed) < 1 << 64:
+            raise VdjxError(f"vdjx_diversity: replicates {replicates}, depth {depth}, seed {seed}")
+        n, nq, b = w.shape[0], qs.shape[0], int(replicates)
+        rows = b if 1 <= b <= 4096 else 1                                 # (a count the library refuses: nothing is written)
+        params = _lib.DiversityParams(b, int(depth), int(seed))
+        observed, mean, sd = np.zeros(nq), np.zeros(nq), np.zeros(nq)
+        d = np.zeros((rows, nq))
+        cnt = np.zeros((rows, n), np.uint32) if counts else None
+        info = _lib.DiversityInfo()
+        check(self.L.vdjx_diversity(self.h, _p(w), n, _p(qs), nq, C.byref(params), _p(observed), _p(d), _p(mean), _p(sd), _p(cnt), C.byref(info)),
+              "vdjx_diversity")
+        return {"observed": observed, "mean": mean, "sd": sd, "d": d, "counts": cnt, "info": {f: int(getattr(info, f)) for f in self.DIVERSITY_FIELDS}}
+
     def stat(self, name: str) -> int:
         return int(self.L.vdjx_stat(self.h, name.encode()))
 

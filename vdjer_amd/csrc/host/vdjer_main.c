@@ -6,6 +6,7 @@
  *         --jc --ws -jext --rf --vk --mrs --rs --ms --e0 --e1 --wo --vf --jf --rms] [--gpus N] [--quant <file>] [--airr <file>]
  *         [--d-calls] [--cfa <fasta>] [--isotypes <file>] [--clones <file>] [--sample <name>] [--total-count <n>]
  *         [--lineages <file>] [--lineage-dist <x>] [--trees <file>] [--tree-support <B>] [--tree-seed <s>] [--mutations <file>]
+ *         [--diversity <file>] [--diversity-depth <n>] [--diversity-boot <B>] [--diversity-seed <s>]
  * writes ./vdj_contigs.fa and ./vdjer.dot, SAM on stdout, log on stderr; exit 0 on success.  --quant <file>: the contigs' abundances
  * (vdjx_quant, RSEM's isoforms.results columns) into <file> as well.  --airr <file>: the contigs' V/J annotation (vdjx_annotate against
  * the germlines of ig_vdj.fa / --vdjf) as an AIRR Rearrangement TSV; with --d-calls (a flag: no value) the D gene between the V and the
@@ -20,6 +21,9 @@
  * --mutations <file>: every contig and its V(D)J germline side by side and the V segment's replacement / silent / stop mutation counts
  * (vdjx_mutations: Change-O CreateGermlines and shazam observedMutations); with --airr the table's sequence_alignment and
  * germline_alignment cells are filled, with --d-calls the D hit's germline is laid into the gap, with --lineages the table gets a clone_id.
+ * --diversity <file> (with --lineages and the quant step): the Hill diversity curve of the lineages weighed by their expected counts,
+ * orders 0.0 .. 4.0, with the mean and spread of --diversity-boot <B> bootstrap replicates of --diversity-depth <n> draws each
+ * (vdjx_diversity: alakazam's alphaDiversity), drawn from --diversity-seed <s>.
  *
  * --in: a BAM with its .bai (extraction as bam_read.c:264-446, restated over zlib in bamx.c), or -- recognised by its
  * content -- the extracted read pool as text, one read per line in extraction order:
@@ -71,6 +75,9 @@ typedef struct {
 	const char *tree_support, *tree_seed;  /* --tree-support <B>, --tree-seed <s>: the jackknife support of the trees' edges; read into ts_b (0: none) and ts_seed */
 	uint32_t ts_b; uint64_t ts_seed;
 	const char* mutations;                 /* --mutations <file> (not in the reference): CreateGermlines / observedMutations, on the device */
+	const char* diversity;                 /* --diversity <file> (not in the reference): alakazam's alphaDiversity over the lineages, on the device */
+	const char *div_depth_s, *div_boot_s, *div_seed_s;      /* --diversity-depth <n> (read into div_depth; 0: the total expected pairs), --diversity-boot <B>, --diversity-seed <s> */
+	uint32_t div_depth, div_boot; uint64_t div_seed;
 	int have_chain, have_ref;
 } cli;
 
@@ -97,7 +104,11 @@ static void usage(void) {
 	                "\t--trees <file: with --lineages, the minimum spanning tree inside every lineage: parent, distance and depth of every contig>\n"
 	                "\t--tree-support <B: with --trees, a support column from B delete-half jackknife replicates, a whole number in 1 .. 1024>\n"
 	                "\t--tree-seed <seed of the replicates' columns, a whole number below 2^64 (default: 1)>\n"
-	                "\t--mutations <file: every contig beside its V(D)J germline, and the V segment's replacement / silent / stop mutation counts>\n");
+	                "\t--mutations <file: every contig beside its V(D)J germline, and the V segment's replacement / silent / stop mutation counts>\n"
+	                "\t--diversity <file: with --lineages and --quant or --clones, the Hill diversity curve of the lineages, orders 0.0 .. 4.0, bootstrapped>\n"
+	                "\t--diversity-depth <n: draws per bootstrap replicate, a whole number in 1 .. 2147483647 (default: the lineages' total expected pairs)>\n"
+	                "\t--diversity-boot <B: bootstrap replicates, a whole number in 1 .. 4096 (default: 200)>\n"
+	                "\t--diversity-seed <seed of the draws, a whole number below 2^64 (default: 1)>\n");
 }
 
 static int file_exists(const char* f) { struct stat b; return stat(f, &b) == 0; }
@@ -174,6 +185,10 @@ static int parse(int argc, char** argv, cli* c) {
 		else if (!strcmp(a, "--tree-support")) c->tree_support = v;
 		else if (!strcmp(a, "--tree-seed")) c->tree_seed = v;
 		else if (!strcmp(a, "--mutations")) c->mutations = v;
+		else if (!strcmp(a, "--diversity")) c->diversity = v;
+		else if (!strcmp(a, "--diversity-depth")) c->div_depth_s = v;
+		else if (!strcmp(a, "--diversity-boot")) c->div_boot_s = v;
+		else if (!strcmp(a, "--diversity-seed")) c->div_seed_s = v;
 		else if (!strcmp(a, "--vf")) snprintf(c->v_anchors, sizeof c->v_anchors, "%s", v);
 		else if (!strcmp(a, "--jf")) snprintf(c->j_anchors, sizeof c->j_anchors, "%s", v);
 		else if (!strcmp(a, "--am")) c->anchor_mismatches = atoi(v);
@@ -240,6 +255,31 @@ static int parse(int argc, char** argv, cli* c) {
 	}
 	if (c->tree_seed && whole_u64(c->tree_seed, &c->ts_seed)) {
 		fprintf(stderr, "--tree-seed must be a whole decimal number below 2^64: %s\n", c->tree_seed);
+		ok = 0;
+	}
+	c->div_depth = 0;
+	c->div_boot = 200;
+	c->div_seed = 1;
+	if (c->diversity && !c->lineages) { fprintf(stderr, "--diversity is the diversity of the lineages of the --lineages table: it needs --lineages <file>\n"); ok = 0; }
+	if (c->diversity && !c->quant && !c->clones) {
+		fprintf(stderr, "--diversity weighs the lineages by the quant step's expected counts: it needs --quant <file> or --clones <file>\n");
+		ok = 0;
+	}
+	if (c->div_depth_s && !c->diversity) { fprintf(stderr, "--diversity-depth is the draws of a --diversity replicate: it needs --diversity <file>\n"); ok = 0; }
+	if (c->div_boot_s && !c->diversity) { fprintf(stderr, "--diversity-boot is the number of --diversity replicates: it needs --diversity <file>\n"); ok = 0; }
+	if (c->div_seed_s && !c->diversity) { fprintf(stderr, "--diversity-seed is the seed of the --diversity replicates: it needs --diversity <file>\n"); ok = 0; }
+	if (c->div_depth_s) {
+		uint64_t x = 0;
+		if (whole_u64(c->div_depth_s, &x) || x < 1 || x > 2147483647u) { fprintf(stderr, "--diversity-depth must be a whole decimal number in 1 .. 2147483647: %s\n", c->div_depth_s); ok = 0; }
+		else c->div_depth = (uint32_t) x;
+	}
+	if (c->div_boot_s) {
+		uint64_t x = 0;
+		if (whole_u64(c->div_boot_s, &x) || x < 1 || x > 4096) { fprintf(stderr, "--diversity-boot must be a whole decimal number in 1 .. 4096: %s\n", c->div_boot_s); ok = 0; }
+		else c->div_boot = (uint32_t) x;
+	}
+	if (c->div_seed_s && whole_u64(c->div_seed_s, &c->div_seed)) {
+		fprintf(stderr, "--diversity-seed must be a whole decimal number below 2^64: %s\n", c->div_seed_s);
 		ok = 0;
 	}
 	if (!ok) { usage(); return -1; }
@@ -597,6 +637,9 @@ typedef struct {
 	/* --mutations: the germline rows of every contig (mut_run), kept for the --airr table's two alignment cells */
 	const char* mutations; int mut_done;
 	uint64_t* mu_off; char *mu_seq, *mu_germ; vdjx_mut_info mi;
+	/* --diversity: the Hill curve of the lineages (diversity_run, after lineage_run) */
+	const char* diversity; uint32_t dv_depth, dv_boot; uint64_t dv_seed;
+	vdjx_diversity_info dvi; uint64_t dv_weight; double dv_d0, dv_d1, dv_d2;
 } hook_ud;
 
 static int h_root_score(void* ud, const char* kmers, size_t n, int k, int thr, uint8_t* out) {
@@ -1259,6 +1302,60 @@ static int mut_run(hook_ud* u, const char* const* ids, const char* contigs, size
 	return rc;
 }
 
+/* --diversity: the Hill diversity curve of the lineages (the model: include/vdjx.h, vdjx_diversity; the weights: diversity_weights of
+ * vdjer_amd/annot.py).  A lineage's weight is the sum of its members' expected_count as printed, in hundredths, read from the digits;
+ * lineages of weight 0 take no part.  A row per order 0.0 .. 4.0: the unresampled value, the replicates' mean and sd, the 95 % normal
+ * interval (alakazam's alphaDiversity) and the three over d at q = 0 (evenness).  No lineage of weight: the header alone, no device call. */
+#define DIV_ORDERS 41
+static int diversity_run(hook_ud* u, size_t n) {
+	FILE* fp = fopen(u->diversity, "w");
+	if (!fp) { fprintf(stderr, "cannot write %s\n", u->diversity); return -1; }
+	fputs("q\td_observed\td\td_sd\td_lower\td_upper\te\te_lower\te_upper\n", fp);
+	const size_t nk = u->li.clones;
+	uint64_t* w = (uint64_t*) calloc(nk + 1, sizeof(uint64_t));
+	for (size_t i = 0; i < n; i++) {
+		if (u->lin_clone[i] < 0) continue;
+		char cnt[64];
+		snprintf(cnt, sizeof cnt, "%.2f", u->qcnt ? u->qcnt[i] : 0.0);
+		uint64_t h = 0;
+		for (const char* p = cnt; *p; p++)
+			if (*p >= '0' && *p <= '9') h = h * 10 + (uint64_t) (*p - '0');
+		w[u->lin_clone[i]] += h;
+	}
+	size_t C = 0;
+	uint64_t W = 0;
+	for (size_t k = 0; k < nk; k++)
+		if (w[k]) { W += w[k]; w[C++] = w[k]; }
+	u->dv_weight = W;
+	int rc = 0;
+	if (!u->dv_depth) {                    /* the default depth: the total expected pairs rounded half up, at least 1 */
+		const uint64_t pairs = (W + 50) / 100;
+		if (pairs > 2147483647u) { fprintf(stderr, "--diversity: %llu expected pairs are more than a replicate's 2147483647 draws: give --diversity-depth <n>\n", (unsigned long long) pairs); rc = -1; }
+		else u->dv_depth = pairs ? (uint32_t) pairs : 1;
+	}
+	if (!rc && C) {
+		double q[DIV_ORDERS], obs[DIV_ORDERS], mean[DIV_ORDERS], sd[DIV_ORDERS];
+		double* d = (double*) calloc((size_t) u->dv_boot * DIV_ORDERS, sizeof(double));
+		for (int k = 0; k < DIV_ORDERS; k++) q[k] = (double) k / 10.0;
+		const vdjx_diversity_params dp = {u->dv_boot, u->dv_depth, u->dv_seed};
+		rc = vdjx_diversity(u->gx, w, C, q, DIV_ORDERS, &dp, obs, d, mean, sd, NULL, &u->dvi);
+		if (rc) fprintf(stderr, "--diversity: %s\n", vdjx_last_error());
+		if (!rc) {
+			const double z = 1.959963984540054, d0 = mean[0];
+			for (int k = 0; k < DIV_ORDERS; k++) {
+				const double lo = mean[k] - z * sd[k] > 0.0 ? mean[k] - z * sd[k] : 0.0, hi = mean[k] + z * sd[k];
+				fprintf(fp, "%.1f\t%.4f\t%.4f\t%.4f\t%.4f\t%.4f\t%.4f\t%.4f\t%.4f\n", q[k], obs[k], mean[k], sd[k], lo, hi, mean[k] / d0, lo / d0, hi / d0);
+			}
+			u->dv_d0 = mean[0]; u->dv_d1 = mean[10]; u->dv_d2 = mean[20];
+		}
+		free(d);
+	}
+	u->dvi.clones = (uint32_t) C;          /* (no lineage of weight: the device was not called) */
+	free(w);
+	if (fclose(fp) && !rc) { fprintf(stderr, "cannot write %s\n", u->diversity); return -1; }
+	return rc;
+}
+
 /* the tables after the SAM body: every device step runs once, whichever tables ask for it */
 static int tables(hook_ud* u, const char* const* ids, const char* contigs, size_t n, int len) {
 	int rc = 0;
@@ -1267,6 +1364,7 @@ static int tables(hook_ud* u, const char* const* ids, const char* contigs, size_
 	if (!rc && u->d_calls) rc = dcall_run(u, contigs, n, len);
 	if (!rc && u->lineages) rc = lineage_run(u, ids, contigs, n, len);
 	if (!rc && u->trees) rc = tree_run(u, ids, contigs, n, len);
+	if (!rc && u->diversity) rc = diversity_run(u, n);
 	if (!rc && u->mutations) rc = mut_run(u, ids, contigs, n, len);
 	if (!rc && u->airr) rc = airr_table(u, ids, contigs, n, len);
 	if (!rc && u->cfa && (u->isotypes || u->clones)) rc = iso_run(u, contigs, n, len);
@@ -1546,6 +1644,7 @@ int main(int argc, char** argv) {
 	ud.cfa = c.cfa; ud.isotypes = c.isotypes; ud.clones = c.clones; ud.total_count = c.total_count;
 	ud.lineages = c.lineages; ud.lin_num = c.lin_num; ud.lin_den = c.lin_den; ud.trees = c.trees;
 	ud.ts_b = c.ts_b; ud.ts_seed = c.ts_seed; ud.mutations = c.mutations;
+	ud.diversity = c.diversity; ud.dv_depth = c.div_depth; ud.dv_boot = c.div_boot; ud.dv_seed = c.div_seed;
 	char sample_buf[4096];
 	if (c.sample) ud.sample = c.sample;
 	else {                                  /* the input's base name up to its first '.' */
@@ -1617,6 +1716,10 @@ int main(int argc, char** argv) {
 		        (unsigned long long) ud.mi.contigs, (unsigned long long) ud.mi.aligned, (unsigned long long) ud.mi.cols, (unsigned long long) ud.mi.v_codons,
 		        (unsigned long long) ud.mi.v_r, (unsigned long long) ud.mi.v_s, (unsigned long long) ud.mi.v_stop, (unsigned long long) ud.mi.v_na,
 		        ud.mi.clipped, ud.mi.truncated);
+	if (c.diversity)
+		fprintf(stderr, "diversity: %u lineages with weight of %u, %llu.%02llu expected pairs, depth %u, %u replicates (seed %llu), richness %.2f, shannon %.4f, simpson %.4f, %u batches\n",
+		        ud.dvi.clones, ud.li.clones, (unsigned long long) (ud.dv_weight / 100), (unsigned long long) (ud.dv_weight % 100), ud.dv_depth, c.div_boot,
+		        (unsigned long long) c.div_seed, ud.dv_d0, ud.dv_d1, ud.dv_d2, ud.dvi.batches);
 	fflush(stdout);
 	fflush(stderr);
 	/* the outputs are written; the orderly teardown of a context that holds gigabytes (unmapping the workspaces piece by piece, the

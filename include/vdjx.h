@@ -309,6 +309,16 @@ int vdjx_sam_merge(vdjx_ctx* ctx, uint64_t n_blocks, uint64_t n_bytes, const voi
 typedef struct { int max_iter; double tol; } vdjx_quant_params;
 typedef struct { uint64_t pairs, alignments, unique_pairs; uint32_t iterations, converged; double eff_len; } vdjx_quant_info;
 int vdjx_quant(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const vdjx_quant_params* params, double* out_counts, vdjx_quant_info* info);
+/* The same model over placements the caller brings, in the shape vdjx_map_emit returns them: contig-major, offsets[n + 1] with
+ * offsets[0] = 0 and no decrease, pairs[offsets[n]]; contig c holds pairs[offsets[c] .. offsets[c + 1]).  Of a vdjx_pair only pair_id and
+ * insert are read.  Every pair_id < n_pairs (ids without a placement are skipped); an insert may be any int16, and those outside
+ * [50, min(400, len)] weigh 0 (a pair all of whose alignments weigh 0 adds nothing to any contig).  No pool and no read index are needed;
+ * the placements are copied into the context's workspace and nothing is kept.  Output, info and bits are vdjx_quant's for the same
+ * placements; the stat "quant_map_us" is 0.  VDJX_EINVAL: a NULL argument, offsets[0] != 0, offsets that decrease, a pair_id >= n_pairs,
+ * max_iter < 1, tol negative or NaN, len < 1.  VDJX_ELIMIT: n >= 2^20, len >= 4096, offsets[n] >= 2^32.  n = 0 and offsets[n] = 0 give
+ * zeros, converged = 1 and the eff_len of a histogram without counts. */
+int vdjx_quant_pairs(vdjx_ctx* ctx, const uint64_t* offsets, const vdjx_pair* pairs, size_t n, int len, uint32_t n_pairs,
+                     const vdjx_quant_params* params, double* out_counts, vdjx_quant_info* info);
 
 /* ---- contig annotation: V/J calls, identity and CIGARs against the germline segments (the ref-dir's ig_vdj.fa) -----------------------
  * replaces the IMGT HighV-QUEST round trip of the reference's post_process/ (collect_vdjer_stats.py reads the V gene, the J gene, the

@@ -1,5 +1,5 @@
 """vdjx_quant's model (include/vdjx.h) restated in float64 numpy: RSEM's core paired-end EM over (pair, contig, insert) triples, one
-triple per placement.  Also the readers the quant tests share: SAM placements and the isoforms.results table of `vdjer --quant`."""
+triple per placement; quant_trace keeps every iteration, quant_one_exact is its first iteration in exact rationals.  Also the readers the quant tests share: SAM placements and the isoforms.results table of `vdjer --quant`."""
 import numpy as np
 
 MIN_INSERT, MAX_INSERT = 50, 400             # quick_map3.c:23-24
@@ -28,33 +28,91 @@ def frag_weights(pair, insert, L):
     return g, eff_len, int(h.sum())
 
 
-def quant(pair, contig, insert, n_contigs, L, max_iter=10000, tol=1e-5):
-    """-> (N float64[n_contigs], info) with info as vdjx_quant fills it"""
+def _iterate(pair, contig, insert, n_contigs, L):
+    """the model's state before the first iteration (g, eff_len, pairs placed once, placed pairs, N), then (N, delta) after every
+    iteration, for as long as the caller goes on asking"""
     pair = np.asarray(pair, np.int64)
     contig = np.asarray(contig, np.int64)
     insert = np.asarray(insert, np.int64)
     g, eff_len, unique = frag_weights(pair, insert, L)
-    info = dict(pairs=0, alignments=int(pair.size), unique_pairs=unique, iterations=0, converged=True, eff_len=eff_len)
     N = np.zeros(n_contigs)
     if pair.size == 0:
-        return N, info
+        yield eff_len, unique, 0, N
+        return
     upair, inv = np.unique(pair, return_inverse=True)
     placed = np.bincount(contig, minlength=n_contigs) > 0
     N[placed] = upair.size / float(placed.sum())
-    info["pairs"] = int(upair.size)
-    for t in range(1, max_iter + 1):
+    yield eff_len, unique, int(upair.size), N
+    while True:
         w = N[contig] * g
         s = np.bincount(inv, weights=w, minlength=upair.size)[inv]
         r = np.where(s > 0, w / np.where(s > 0, s, 1.0), 0.0)
         Nn = np.bincount(contig, weights=r, minlength=n_contigs)
         delta = float(np.max(np.abs(Nn - N) / np.maximum(Nn, 1.0)))
         N = Nn
+        yield N, delta
+
+
+def quant(pair, contig, insert, n_contigs, L, max_iter=10000, tol=1e-5):
+    """-> (N float64[n_contigs], info) with info as vdjx_quant fills it"""
+    steps = _iterate(pair, contig, insert, n_contigs, L)
+    eff_len, unique, pairs, N = next(steps)
+    info = dict(pairs=pairs, alignments=int(np.asarray(pair).size), unique_pairs=unique, iterations=0, converged=True, eff_len=eff_len)
+    if pairs == 0:
+        return N, info
+    for t in range(1, max_iter + 1):
+        N, delta = next(steps)
         info["iterations"] = t
         if delta < tol:
             info["converged"] = True
             return N, info
     info["converged"] = False
     return N, info
+
+
+def quant_trace(pair, contig, insert, n_contigs, L, iters):
+    """-> (N float64[iters, n_contigs], delta float64[iters]): row t - 1 is quant's N after iteration t, delta[t - 1] what its stop rule
+    compares with tol then (no stop: all `iters` iterations run)"""
+    steps = _iterate(pair, contig, insert, n_contigs, L)
+    next(steps)
+    out = [next(steps) for _ in range(iters)] if np.asarray(pair).size else []
+    return np.array([x[0] for x in out]).reshape(len(out), n_contigs), np.array([x[1] for x in out])
+
+
+def quant_one_exact(pair, contig, insert, n_contigs, L):
+    """iteration 1 of the model in exact rational arithmetic (fractions.Fraction): the histogram of the pairs placed once, P, g, the
+    start value, the E and the M step.  -> (N: list of n_contigs Fractions, degree: dict pair id -> its number of placements)"""
+    from fractions import Fraction
+    pair = [int(x) for x in pair]
+    contig = [int(x) for x in contig]
+    insert = [int(x) for x in insert]
+    degree = {}
+    for p in pair:
+        degree[p] = degree.get(p, 0) + 1
+    h = [0] * (MAX_INSERT - MIN_INSERT + 1)
+    for p, f in zip(pair, insert):
+        if degree[p] == 1 and MIN_INSERT <= f <= MAX_INSERT:
+            h[f - MIN_INSERT] += 1
+    tot = sum(x + 1 for x in h)
+
+    def g(f):
+        if not (MIN_INSERT <= f <= MAX_INSERT and f <= L):
+            return Fraction(0)
+        return Fraction(h[f - MIN_INSERT] + 1, tot) / (L - f + 1)
+
+    N = [Fraction(0)] * n_contigs
+    if not pair:
+        return N, degree
+    placed = set(contig)
+    start = Fraction(len(degree), len(placed))
+    w = [start * g(f) for f in insert]                                   # (every placed contig starts at `start`)
+    total = {}
+    for p, x in zip(pair, w):
+        total[p] = total.get(p, Fraction(0)) + x
+    for p, c, x in zip(pair, contig, w):
+        if total[p] > 0:
+            N[c] += x / total[p]
+    return N, degree
 
 
 def sam_placements(text):

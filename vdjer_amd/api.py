@@ -614,6 +614,33 @@ class Context:
         return counts, dict(pairs=int(info.pairs), alignments=int(info.alignments), unique_pairs=int(info.unique_pairs),
                             iterations=int(info.iterations), converged=bool(info.converged), eff_len=float(info.eff_len))
 
+    def quant_pairs(self, offsets, pairs, length: int, n_pairs: int, max_iter: int = 10000, tol: float = 1e-5):
+        """vdjx_quant_pairs: the same model over placements the caller brings, in map_emit's shape (contig-major): offsets[n + 1],
+        `pairs` a PAIR_DTYPE array of offsets[n] placements or a (pair_id, insert) tuple of arrays, packed here.  Only pair_id and
+        insert are read; no pool and no read index are needed.  -> what quant returns"""
+        offs = _c(offsets, np.uint64)
+        if offs.ndim != 1 or offs.shape[0] < 1:
+            raise VdjxError("vdjx_quant_pairs: offsets must hold n + 1 entries")
+        n = offs.shape[0] - 1
+        if isinstance(pairs, tuple):
+            pid, ins = (np.asarray(x) for x in pairs)
+            if pid.shape != ins.shape or pid.ndim != 1:
+                raise VdjxError("vdjx_quant_pairs: pair_id and insert of unequal shape")
+            packed = np.zeros(pid.shape[0], PAIR_DTYPE)
+            packed["pair_id"] = pid
+            packed["insert"] = ins
+        else:
+            packed = _c(pairs, PAIR_DTYPE)
+        if n and packed.shape[0] != int(offs[n]):
+            raise VdjxError(f"vdjx_quant_pairs: {packed.shape[0]} placements, offsets[n]={int(offs[n])}")
+        counts = np.zeros(n, np.float64)
+        info = _lib.QuantInfo()
+        prm = _lib.QuantParams(int(max_iter), float(tol))
+        check(self.L.vdjx_quant_pairs(self.h, _p(offs), _p(packed), n, int(length), int(n_pairs), C.byref(prm), _p(counts), C.byref(info)),
+              "vdjx_quant_pairs")
+        return counts, dict(pairs=int(info.pairs), alignments=int(info.alignments), unique_pairs=int(info.unique_pairs),
+                            iterations=int(info.iterations), converged=bool(info.converged), eff_len=float(info.eff_len))
+
     def germline_load(self, names_or_records):
         """vdjx_germline_load: a germline FASTA (path) or a list of (FASTA header, sequence) records -> dict(names, classes, skipped).
         Names, classes and sequences as include/vdjx.h states (vdjer_amd/annot.py); the set stays on the device."""

@@ -223,25 +223,14 @@ static double q_us_since(std::chrono::steady_clock::time_point t) {
 	return (double) std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t).count();
 }
 
-extern "C" int vdjx_quant(vdjx_ctx* c, const char* contigs, size_t n, int len, const vdjx_quant_params* prm, double* out_counts, vdjx_quant_info* info) {
-	if (!c || !prm || !info || (n && (!contigs || !out_counts))) { vdjx_set_error("vdjx_quant: NULL argument"); return VDJX_EINVAL; }
-	memset(info, 0, sizeof *info);
-	if (prm->max_iter < 1) { vdjx_set_error("vdjx_quant: max_iter=%d must be at least 1", prm->max_iter); return VDJX_EINVAL; }
-	if (!(prm->tol >= 0.0)) { vdjx_set_error("vdjx_quant: tol must be >= 0"); return VDJX_EINVAL; }
-	info->converged = 1;
-	if (n == 0) return VDJX_OK;
-	if (len < 1) { vdjx_set_error("vdjx_quant: len=%d", len); return VDJX_EINVAL; }
-	if (n >= (1ull << 20) || len >= 4096) { vdjx_set_error("vdjx_quant: at most 2^20 - 1 contigs of fewer than 4096 bases per call"); return VDJX_ELIMIT; }
-	if (memchr(contigs, 0, n * (size_t) len)) { vdjx_set_error("vdjx_quant: contigs of unequal length (a NUL inside the %zu x %d characters)", n, len); return VDJX_EINVAL; }
-	const auto t0 = std::chrono::steady_clock::now();
-	std::vector<uint64_t> offs(n + 1);
-	const vdjx_pair* d_pairs = nullptr;
-	int rc = vdjx_map_emit_device(c, contigs, n, len, offs.data(), &d_pairs);
-	if (rc) return rc;
+// the model over placements that are on the device already (contig-major, offs[n + 1] on the host): what both entries run.  t_map: when
+// the caller began to map (nullptr: it did not, quant_map_us is 0)
+static int q_run(vdjx_ctx* c, vdjx_work& db, const vdjx_pair* d_pairs, const std::vector<uint64_t>& offs, size_t n, int len, u32 P,
+                 const std::chrono::steady_clock::time_point* t_map, const vdjx_quant_params* prm, double* out_counts, vdjx_quant_info* info) {
 	HIP_TRY(hipSetDevice(c->device));
 	hipStream_t st = c->stream;
 	HIP_TRY(hipStreamSynchronize(st));
-	const double us_map = q_us_since(t0);
+	const double us_map = t_map ? q_us_since(*t_map) : 0.0;
 	const u64 A64 = offs[n];
 	u32 placed_contigs = 0;
 	for (size_t i = 0; i < n; i++) placed_contigs += offs[i + 1] > offs[i] ? 1u : 0u;
@@ -255,7 +244,7 @@ extern "C" int vdjx_quant(vdjx_ctx* c, const char* contigs, size_t n, int len, c
 		return VDJX_OK;
 	}
 	if (A64 >= (1ull << 32)) { vdjx_set_error("vdjx_quant: 2^32 placements or more"); return VDJX_ELIMIT; }
-	const u32 A = (u32) A64, P = c->n_pairs;
+	const u32 A = (u32) A64;
 	const auto t1 = std::chrono::steady_clock::now();
 
 	// the M step's chunks: contig after contig, Q_CHUNK alignments at most
@@ -268,7 +257,6 @@ extern "C" int vdjx_quant(vdjx_ctx* c, const char* contigs, size_t n, int len, c
 	cstart[n] = (u32) chunks.size();
 	const u32 nch = (u32) chunks.size();
 
-	vdjx_work db(c);
 	u32 *d_deg, *d_seg, *d_tmp, *d_perm, *d_hist, *d_ct, *d_cstart;
 	u64 *d_excl, *d_off;
 	double *d_gtab, *d_g, *d_r, *d_N, *d_part;
@@ -296,7 +284,7 @@ extern "C" int vdjx_quant(vdjx_ctx* c, const char* contigs, size_t n, int len, c
 	HIP_TRY(hipMemsetAsync(d_deg, 0, (size_t) P * 4, st));
 	HIP_TRY(hipMemsetAsync(d_hist, 0, Q_NBINS * 4, st));
 	HIP_TRY(hipMemsetAsync(d_st, 0, sizeof(QState), st));
-	const u32 gA = (A + 255) / 256, gP = (P + 255) / 256;
+	const u32 gA = (A + 255) / 256, gP = (u32) (((u64) P + 255) / 256);
 	{
 		vdjx_prof_scope ps(c, "k_quant_setup");
 		hipLaunchKernelGGL(k_q_degree, dim3(gA), dim3(256), 0, st, d_pairs, A, P, d_deg);
@@ -362,4 +350,55 @@ extern "C" int vdjx_quant(vdjx_ctx* c, const char* contigs, size_t n, int len, c
 	info->converged = hs.delta < prm->tol ? 1u : 0u;
 	info->eff_len = hs.eff_len;
 	return VDJX_OK;
+}
+
+extern "C" int vdjx_quant(vdjx_ctx* c, const char* contigs, size_t n, int len, const vdjx_quant_params* prm, double* out_counts, vdjx_quant_info* info) {
+	if (!c || !prm || !info || (n && (!contigs || !out_counts))) { vdjx_set_error("vdjx_quant: NULL argument"); return VDJX_EINVAL; }
+	memset(info, 0, sizeof *info);
+	if (prm->max_iter < 1) { vdjx_set_error("vdjx_quant: max_iter=%d must be at least 1", prm->max_iter); return VDJX_EINVAL; }
+	if (!(prm->tol >= 0.0)) { vdjx_set_error("vdjx_quant: tol must be >= 0"); return VDJX_EINVAL; }
+	info->converged = 1;
+	if (n == 0) return VDJX_OK;
+	if (len < 1) { vdjx_set_error("vdjx_quant: len=%d", len); return VDJX_EINVAL; }
+	if (n >= (1ull << 20) || len >= 4096) { vdjx_set_error("vdjx_quant: at most 2^20 - 1 contigs of fewer than 4096 bases per call"); return VDJX_ELIMIT; }
+	if (memchr(contigs, 0, n * (size_t) len)) { vdjx_set_error("vdjx_quant: contigs of unequal length (a NUL inside the %zu x %d characters)", n, len); return VDJX_EINVAL; }
+	const auto t0 = std::chrono::steady_clock::now();
+	std::vector<uint64_t> offs(n + 1);
+	const vdjx_pair* d_pairs = nullptr;
+	int rc = vdjx_map_emit_device(c, contigs, n, len, offs.data(), &d_pairs);
+	if (rc) return rc;
+	vdjx_work db(c);
+	return q_run(c, db, d_pairs, offs, n, len, c->n_pairs, &t0, prm, out_counts, info);
+}
+
+extern "C" int vdjx_quant_pairs(vdjx_ctx* c, const uint64_t* offsets, const vdjx_pair* pairs, size_t n, int len, uint32_t n_pairs,
+                                const vdjx_quant_params* prm, double* out_counts, vdjx_quant_info* info) {
+	if (!c || !prm || !info || (n && (!offsets || !out_counts))) { vdjx_set_error("vdjx_quant_pairs: NULL argument"); return VDJX_EINVAL; }
+	memset(info, 0, sizeof *info);
+	if (prm->max_iter < 1) { vdjx_set_error("vdjx_quant_pairs: max_iter=%d must be at least 1", prm->max_iter); return VDJX_EINVAL; }
+	if (!(prm->tol >= 0.0)) { vdjx_set_error("vdjx_quant_pairs: tol must be >= 0"); return VDJX_EINVAL; }
+	info->converged = 1;
+	if (n == 0) return VDJX_OK;
+	if (len < 1) { vdjx_set_error("vdjx_quant_pairs: len=%d", len); return VDJX_EINVAL; }
+	if (n >= (1ull << 20) || len >= 4096) { vdjx_set_error("vdjx_quant_pairs: at most 2^20 - 1 contigs of fewer than 4096 bases per call"); return VDJX_ELIMIT; }
+	if (offsets[0] != 0) { vdjx_set_error("vdjx_quant_pairs: offsets[0]=%llu must be 0", (unsigned long long) offsets[0]); return VDJX_EINVAL; }
+	for (size_t i = 0; i < n; i++)
+		if (offsets[i + 1] < offsets[i]) { vdjx_set_error("vdjx_quant_pairs: the offsets decrease at contig %zu", i); return VDJX_EINVAL; }
+	const u64 A64 = offsets[n];
+	if (A64 >= (1ull << 32)) { vdjx_set_error("vdjx_quant_pairs: 2^32 placements or more"); return VDJX_ELIMIT; }
+	if (A64 && !pairs) { vdjx_set_error("vdjx_quant_pairs: NULL argument (pairs)"); return VDJX_EINVAL; }
+	for (u64 a = 0; a < A64; a++)
+		if (pairs[a].pair_id >= n_pairs) {
+			vdjx_set_error("vdjx_quant_pairs: placement %llu names pair %u of %u", (unsigned long long) a, pairs[a].pair_id, n_pairs);
+			return VDJX_EINVAL;
+		}
+	const std::vector<uint64_t> offs(offsets, offsets + n + 1);
+	HIP_TRY(hipSetDevice(c->device));
+	vdjx_work db(c);
+	vdjx_pair* d_pairs = nullptr;
+	if (A64) {
+		HIP_TRY(db.alloc(&d_pairs, (size_t) A64));
+		HIP_TRY(hipMemcpyAsync(d_pairs, pairs, (size_t) A64 * sizeof(vdjx_pair), hipMemcpyHostToDevice, c->stream));
+	}
+	return q_run(c, db, d_pairs, offs, n, len, n_pairs, nullptr, prm, out_counts, info);
 }

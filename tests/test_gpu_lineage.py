@@ -1,5 +1,5 @@
 """vdjx_lineage on the GPU: clone, nearest and every info field against the plain model of tests/lineage_model.py, exactly -- bucket sizes
-around the pair pass's row block and column tile (64), junction lengths around its 32-base words, interleaved buckets, a chain that only
+around the pair pass's row block and column tile (64), junction lengths around its 32-base words and at every word count, interleaved buckets, a chain that only
 holds together link by link, two families one substitution past the threshold, characters that are not ACGT, seeded random repertoires,
 permutations, the refusals; buckets of 4,096 and 4,097 and eleven buckets whose column slices hold two tiles, a bucket of 1,000 equal junctions,
 2^20 - 1 items, offsets that start past zero -- and `vdjer --lineages` on a heavy-chain and a light-chain golden against the model's table.  The API cases
@@ -127,11 +127,30 @@ def cases():
         order = r.permutation(len(js))
         out[f"random_{seed}"] = ([js[i] for i in order], [grp[i] for i in order], (int(r.choice(THRESHOLDS)), 10000))
     out.update(_past_one_tile(np.random.default_rng(20241)))
+    # every word count from 4 to 8 (1, 2, 3 and 8 are above): in one group a bucket of 65 (two row blocks, two column tiles) and a bucket
+    # of 3 of the same word count; two families and a few strangers, the last member of the 65 with an N for its last base
+    rng = np.random.default_rng(20242)
+    for L in WORD_LENGTHS:
+        big = (_family(rng, _rand(rng, L), 33) + _family(rng, _rand(rng, L), 32))
+        for k in range(0, 65, 17):
+            big[k] = _rand(rng, L)
+        big[64] = big[64][:L - 1] + "N"
+        small = _family(rng, _rand(rng, small_length(L)), 3)
+        order = rng.permutation(68).tolist()
+        out[f"words_{L}"] = ([(big + small)[i] for i in order], [2] * 68, M.DEFAULT)
     return out
 
 
+WORD_LENGTHS = [97, 128, 129, 160, 161, 192, 193, 224, 225]            # 4 .. 8 words, a full last word and one base in it
+
+
+def small_length(L):
+    """another length of the same word count"""
+    return L + 1 if L % 32 == 1 else L - 1
+
+
 def work_items(sizes):
-    """the work items vdjx_lineage makes of buckets of these sizes (vdjx_lineage.hip): row blocks of 64 times column slices of
+    """the work items vdjx_lineage makes of buckets of these sizes (ham_slice_items, vdjx_hamming.h): row blocks of 64 times column slices of
     max(64, ceil(cells / (64 * 4096) / 64) * 64) columns, cells the sum of the squared sizes -> (items, slice)"""
     cells = sum(m * m for m in sizes)
     per = -(-cells // (64 * 4096))
@@ -323,6 +342,22 @@ def test_lineage_api_vs_model_word_edges(L):
     assert clone[0] == clone[-1] and (L == 1 or near[-2] == 1) and clone[-2] != clone[0]      # the copy is linked, the one that differs in the last base is not
     if L > 1:
         assert models()[f"len_{L}"][1].max() <= L
+
+
+@pytest.mark.parametrize("L", WORD_LENGTHS)
+def test_lineage_every_word_count(L):
+    """every unrolled body of k_lin_pairs that LENGTHS leaves out, at a full last word and at one base in it, past one row block and
+    one column tile"""
+    name = f"words_{L}"
+    _same(device()["cases"][name], models()[name], name)
+    js, grp, md = cases()[name]
+    clone, near, info = models()[name]
+    lengths = [len(s) for s in js]
+    assert sorted((lengths.count(ln), ln) for ln in set(lengths)) == [(3, small_length(L)), (65, L)]
+    assert -(-small_length(L) // 32) == -(-L // 32) in range(4, 9) and max(lengths) <= 255
+    assert info["buckets"] == 2 and info["largest_bucket"] == 65 and info["pairs"] == 65 * 32 + 3 and md == (1500, 10000)
+    assert 2 < info["clones"] < 68 and info["links"] > 0 and sum(s.count("N") for s in js) == 1 and [s for s in js if "N" in s][0][-1] == "N"
+    assert device()["work_items"][name] == 2 * 2 + 1
 
 
 def test_lineage_chain_is_one_clone():

@@ -1,6 +1,6 @@
 """vdjx_tree on the GPU: parent, dist, depth and every info field against the plain model of tests/tree_model.py, exactly -- clone sizes
 around k_tree_min's row block and column tiles, window lengths around its 32-base words, the default span, both sides of the register
-path's 512 bases and the chunked path up to 4,095, windows cut at shifts of 1, 31, 32 and 33, a chain of 200, 100 equal sequences, two
+path's 512 bases and the chunked path up to 4,095, every word count from 1 to 16 and 17 and 33, windows cut at shifts of 1, 31, 32 and 33, a chain of 200, 100 equal sequences, two
 families one substitution apart, characters that are not ACGT, 1,000 small clones interleaved, seeded random repertoires, a permutation, a
 clone of 4,097 (13 rounds, column slices of two tiles), 2^20 - 1 items in pairs, the dispatch counts, the refusals -- and `vdjer --trees`
 on the e2e_families golden against the model's table.  The API cases run in one child process (as tests/test_gpu_lineage.py runs its own);
@@ -164,7 +164,25 @@ def cases():
                                  [pr[k] for k in order] if seed % 2 else None)
     # one clone of 4,097 at 40 bases: 13 rounds, and 4097^2 cells make column slices of 128, two tiles of 64
     out["clone_4097"] = (_descent(np.random.default_rng(20251), 4097, 40, 2), [0] * 4097, [11] * 4097, None)
+    # every word count k_tree_min has a body for: a clone of 65 (two row blocks; two column tiles of 64, three of 32 from 9 words on) and,
+    # laid out after it, a clone of 3; the windows lie at offset 0 or 1 of contigs of w + 1 bases; member 64 has an N in its last word
+    rng = np.random.default_rng(20253)
+    for words in WORDS:
+        w = words_window(words)
+        a0 = w // 3
+        longs = _descent(rng, 65, w, 3) + _descent(rng, 3, w, 3)
+        longs[64] = longs[64][:w - 1] + "N"
+        cs = [_rand(rng, 1) + s if k % 3 == 1 else s + _rand(rng, 1) for k, s in enumerate(longs)]
+        out[f"words_{words}"] = (cs, [4] * 65 + [9] * 3, [a0 + 1 if k % 3 == 1 else a0 for k in range(68)], None)
     return out
+
+
+WORDS = list(range(1, 17)) + [17, 33]                                   # the sixteen register bodies; the chunked path with a partial second chunk, with three chunks
+
+
+def words_window(words):
+    """a window of `words` words: one base in the last for an odd count, a full last word for an even one"""
+    return 32 * (words - 1) + 1 if words % 2 else 32 * words
 
 
 def pairs_case():
@@ -317,6 +335,26 @@ def test_tree_window_lengths(w):
     ws, _ = T.windows(cs, members, an)
     D = T.distance_matrix(ws)
     assert D[0, 20] == 0 and D[0, 17] == 1 and (w == 1 or (D[0, 18] == 1 and D[17, 18] == 2 and D[0, 19] == 2))      # the two ends of the window count
+
+
+@pytest.mark.parametrize("words", WORDS)
+def test_tree_every_word_count(words):
+    """every unrolled body of k_tree_min and two shapes of the chunked path, at one base in the last word and at a full one: two row blocks,
+    more than one column tile, a second clone whose first row and first word are not 0"""
+    name = f"words_{words}"
+    _same(device()["cases"][name], models()[name], name)
+    cs, cl, an, _ = cases()[name]
+    w = words_window(words)
+    big, small = list(range(65)), list(range(65, 68))
+    assert sum(T.window_of(big, an, len(cs[0]))) == sum(T.window_of(small, an, len(cs[0]))) == w and -(-w // 32) == words and w % 32 == words % 2
+    assert all({an[i] - min(an) for i in members} == {0, 1} for members in (big, small))      # windows at offset 0 and at offset 1
+    ws, _ = T.windows(cs, big, an)
+    assert [i for i, s in enumerate(ws) if "N" in s] == [64] and ws[64].index("N") == w - 1
+    D = T.distance_matrix(ws)
+    assert D[64, 64] == 1 and D[:64, :64].max() < 32 and (np.bincount(D[np.triu_indices(65, 1)]).max() > 65)      # small distances, many ties
+    info = models()[name][3]
+    assert info["clones"] == 2 and info["largest_clone"] == 65 and info["rounds"] == 7 == device()["rounds"][name]
+    assert device()["work_items"][name] == 2 * 2 + 1
 
 
 @pytest.mark.parametrize("s", SHIFTS)

@@ -5,39 +5,30 @@
 //
 // The host sorts the (group, length, index) keys -- per item -- and lays the participating items out in bucket order ("rows").  Per
 // pair everything happens on the device, in five dispatches whatever n and the number of buckets are:
-//   k_lin_pack     a row = 8 pairs of 64-bit words {bases, mask}: 32 bases per word, 2 bits each (A0 T1 C2 G3, base k of a word in bits
-//                  2k+1, 2k), the mask with bit 2k+1 set where base k is not ACGT.  Words past the junction's end, and bits past it, are 0.
-//                  A row is 128 bytes (two 64-byte lines); a junction of up to 128 bases lives in the first.
+//   k_lin_pack     a row = 8 {bases, mask} pairs in vdjx_hamming.h's format, 128 bytes (two 64-byte lines); a junction of up to 128
+//                  bases lives in the first
 //   k_lin_pairs    one wave per work item (row block of 64 rows, column slice of the same bucket): a lane keeps its row's live words in
-//                  registers, the columns go through LDS in tiles of 64 and are read back as one 16-byte {bases, mask} broadcast per word:
-//                    d = popcount((((x ^ y) | ((x ^ y) << 1)) & 0xAAAA...) | mx | my), summed over the words
-//                  (the upper bit of a base's two collects the difference: the shift never has to cross the halves of a 64-bit word,
-//                  so it is one v_lshl_or_b32 per half -- ten integer instructions per word and lane)
-//                  the lane keeps the smallest d > 0 (atomicMin per row at the end: the column slices of a row meet there) and, for the
-//                  pairs with column > row and d <= floor(num L / den), counts the link and unites the two items
-//   union-find     (vdjx_unionfind.h) parent[] over the caller's item indices, lock-free: find with path halving (atomicMin: a parent only ever gets
-//                  smaller), union by atomicCAS on the LARGER root, which is hooked under the smaller.  parent[x] <= x always holds, so
-//                  the trees stay trees and the root of a finished component is its smallest member whatever the interleaving was.
+//                  registers, the columns go through LDS in tiles of 64 and are read back as one 16-byte {bases, mask} broadcast per
+//                  word (ham_word).  The lane keeps the smallest d > 0 (atomicMin per row at the end: the column slices of a row meet there) and,
+//                  for the pairs with column > row and d <= floor(num L / den), counts the link and unites the two items
+//                  (vdjx_unionfind.h, parent[] over the caller's item indices)
 //   k_lin_flatten  every item's root; a flag per root, in item order
 //   k_scan_one     (vdjx_scan.h) numbers the flags: the clone id of a root
 //   k_lin_out      clone and nearest of every item, in the caller's order
 // No floating point.  Scratch comes from the context's workspace.
 #include "vdjx_common.h"
+#include "vdjx_hamming.h"
 #include "vdjx_scan.h"
 #include "vdjx_unionfind.h"
 
-#include <algorithm>
 #include <string.h>
 
 #define LIN_NONE 0xFFFFFFFFu
 #define LIN_ROW_WORDS 8u                 // {bases, mask} pairs per row: 8 x 32 = 256 >= VDJX_LINEAGE_MAXLEN bases
-#define LIN_TILE 64u                     // columns per LDS tile (and rows per work item: one per lane)
-#define LIN_TARGET_ITEMS 4096u           // work items aimed at: 4 waves on each of the 1,024 SIMDs
-#define LIN_MA 0xAAAAAAAAu                // the upper bit of every base's two
+#define LIN_TILE 64u                     // columns per LDS tile (the rows of a work item, HAM_ROWS, happen to be as many)
 
 struct LinRow { u64 at; u32 item, len; };                                     // where the junction's characters start, whose they are
-struct LinItem { u32 row0, row_end, col0, col_end, words, dmax, pad0, pad1; };   // rows [row0, row_end) (at most 64) against columns [col0, col_end)
-static_assert(sizeof(LinRow) == 16 && sizeof(LinItem) == 32, "uploaded as they are");
+static_assert(sizeof(LinRow) == 16, "uploaded as it is");
 
 // one thread per {bases, mask} pair of a row
 __global__ __launch_bounds__(256) void k_lin_pack(const char* __restrict__ junc, const LinRow* __restrict__ ri, u32 rows, ulonglong2* __restrict__ out,
@@ -45,21 +36,13 @@ __global__ __launch_bounds__(256) void k_lin_pack(const char* __restrict__ junc,
 	const u32 t = blockIdx.x * 256u + threadIdx.x, r = t / LIN_ROW_WORDS, w = t % LIN_ROW_WORDS;
 	if (r >= rows) return;
 	const LinRow q = ri[r];
-	u64 x = 0, m = 0;
-	for (u32 k = 0; k < 32u; k++) {
-		const u32 pos = w * 32u + k;
-		if (pos >= q.len) break;
-		const char ch = junc[q.at + pos];
-		const u32 code = ch == 'A' ? 0u : ch == 'T' ? 1u : ch == 'C' ? 2u : ch == 'G' ? 3u : 4u;
-		if (code < 4u) x |= (u64) code << (2u * k);
-		else m |= 2ull << (2u * k);
-	}
-	out[(size_t) r * LIN_ROW_WORDS + w] = make_ulonglong2(x, m);
+	out[(size_t) r * LIN_ROW_WORDS + w] = ham_pack_word([&](u32 pos) { return junc[q.at + pos]; }, w, q.len);
 	if (w == 0) { row_item[r] = q.item; parent[q.item] = q.item; }
 }
 
+// the register path: rows [row0, row_end) of a work item against its columns, W live words a row; u[0] of the item is the bucket's dmax
 template <int W>
-__device__ inline void lin_item(const LinItem it, const ulonglong2* __restrict__ rows, const u32* __restrict__ row_item, u32* parent, u32* near_,
+__device__ inline void lin_item(const HamItem it, const ulonglong2* __restrict__ rows, const u32* __restrict__ row_item, u32* parent, u32* near_,
                                 unsigned long long* links, ulonglong2* tile, u32* tile_item) {
 	const u32 lane = threadIdx.x, myrow = it.row0 + lane;
 	const bool live = myrow < it.row_end;
@@ -81,18 +64,13 @@ __device__ inline void lin_item(const LinItem it, const ulonglong2* __restrict__
 		for (u32 c = 0; c < nc; c++) {
 			u32 d = 0;
 #pragma unroll
-			for (int w = 0; w < W; w++) {
-				const ulonglong2 q = tile[c * (u32) W + w];       // (every lane the same address: one broadcast read of 16 bytes)
-				const u64 t = x[w] ^ q.x, mm = m[w] | q.y;
-				const u32 lo = (u32) t, hi = (u32) (t >> 32);
-				d += (u32) __popc(((lo | (lo << 1)) & LIN_MA) | (u32) mm) + (u32) __popc(((hi | (hi << 1)) & LIN_MA) | (u32) (mm >> 32));
-			}
+			for (int w = 0; w < W; w++) d += ham_word(x[w], m[w], tile[c * (u32) W + w]);      // (every lane the same address: one broadcast read of 16 bytes)
 			const u32 p = base + c;
 			if (live && p != myrow) {
 				if (d != 0 && d < best) best = d;
-				if (p > myrow && d <= it.dmax) {
+				if (p > myrow && d <= it.u[0]) {
 					cnt++;
-					lin_unite(parent, me, tile_item[c]);
+					uf_unite(parent, me, tile_item[c]);
 				}
 			}
 		}
@@ -106,20 +84,13 @@ __device__ inline void lin_item(const LinItem it, const ulonglong2* __restrict__
 
 // one wave per work item; the live words of a bucket are the same for all its rows, so the word count is uniform and every loop over
 // words is unrolled (the row stays in registers)
-__global__ __launch_bounds__(64) void k_lin_pairs(const LinItem* __restrict__ items, const ulonglong2* __restrict__ rows, const u32* __restrict__ row_item,
+__global__ __launch_bounds__(64) void k_lin_pairs(const HamItem* __restrict__ items, const ulonglong2* __restrict__ rows, const u32* __restrict__ row_item,
                                                   u32* parent, u32* near_, unsigned long long* links) {
 	__shared__ ulonglong2 tile[LIN_TILE * LIN_ROW_WORDS];
 	__shared__ u32 tile_item[LIN_TILE];
-	const LinItem it = items[blockIdx.x];
-	switch (it.words) {
-		case 1: lin_item<1>(it, rows, row_item, parent, near_, links, tile, tile_item); break;
-		case 2: lin_item<2>(it, rows, row_item, parent, near_, links, tile, tile_item); break;
-		case 3: lin_item<3>(it, rows, row_item, parent, near_, links, tile, tile_item); break;
-		case 4: lin_item<4>(it, rows, row_item, parent, near_, links, tile, tile_item); break;
-		case 5: lin_item<5>(it, rows, row_item, parent, near_, links, tile, tile_item); break;
-		case 6: lin_item<6>(it, rows, row_item, parent, near_, links, tile, tile_item); break;
-		case 7: lin_item<7>(it, rows, row_item, parent, near_, links, tile, tile_item); break;
-		case 8: lin_item<8>(it, rows, row_item, parent, near_, links, tile, tile_item); break;
+	const HamItem it = items[blockIdx.x];
+	switch (it.words) {                                    // (W below is the case's constant: HAM_CASES_8 declares it)
+		HAM_CASES_8(lin_item<W>(it, rows, row_item, parent, near_, links, tile, tile_item))
 		default: break;
 	}
 }
@@ -193,17 +164,12 @@ extern "C" int vdjx_lineage(vdjx_ctx* c, const char* junctions, const uint64_t* 
 		cells += (u64) b.y * b.y;
 	}
 	inf.buckets = (u32) buckets.size();
-	// the work items: (bucket, row block, column slice).  The slice is a whole number of tiles, as wide as it takes for about
-	// LIN_TARGET_ITEMS items in all: one tile where the input is small (a bucket of 2,000 rows: 32 row blocks x 32 slices).
-	const u64 per = (cells + (u64) LIN_TILE * LIN_TARGET_ITEMS - 1) / ((u64) LIN_TILE * LIN_TARGET_ITEMS);
-	const u32 slice = (u32) std::max<u64>(LIN_TILE, (per + LIN_TILE - 1) / LIN_TILE * LIN_TILE);
-	std::vector<LinItem> items;
+	const u32 slice = ham_slice_width(cells);
+	std::vector<HamItem> items;                            // a bucket is a group; its user word: dmax
 	for (const uint2& b : buckets) {
-		const u32 L = ri[b.x].len, end = b.x + b.y;
+		const u32 L = ri[b.x].len;
 		const u32 dmax = (u32) ((u64) prm->num * L / (u64) prm->den);      // d * den <= num * L  <=>  d <= floor(num * L / den)
-		for (u32 r0 = b.x; r0 < end; r0 += LIN_TILE)
-			for (u32 c0 = b.x; c0 < end; c0 += slice)
-				items.push_back({r0, std::min(end, r0 + LIN_TILE), c0, std::min(end, c0 + slice), (L + 31u) / 32u, dmax, 0u, 0u});
+		ham_slice_items({b.x, b.y, (L + 31u) / 32u, {dmax, 0u, 0u}}, slice, items);
 	}
 
 	HIP_TRY(hipSetDevice(c->device));
@@ -212,7 +178,7 @@ extern "C" int vdjx_lineage(vdjx_ctx* c, const char* junctions, const uint64_t* 
 	const size_t jbytes = (size_t) (off[n] - off[0]);
 	char* d_junc;
 	LinRow* d_ri;
-	LinItem* d_items;
+	HamItem* d_items;
 	ulonglong2* d_rows;
 	u32 *d_row_item, *d_state, *d_root, *d_flag, *d_number;
 	unsigned long long* d_links;
@@ -231,7 +197,7 @@ extern "C" int vdjx_lineage(vdjx_ctx* c, const char* junctions, const uint64_t* 
 	u32 *d_parent = d_state, *d_near = d_state + n;
 	if (jbytes) HIP_TRY(hipMemcpyAsync(d_junc, junctions + off[0], jbytes, hipMemcpyHostToDevice, st));
 	HIP_TRY(hipMemcpyAsync(d_ri, ri.data(), rows * sizeof(LinRow), hipMemcpyHostToDevice, st));
-	HIP_TRY(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(LinItem), hipMemcpyHostToDevice, st));
+	HIP_TRY(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(HamItem), hipMemcpyHostToDevice, st));
 	HIP_TRY(hipMemsetAsync(d_state, 0xFF, 2 * n * sizeof(u32), st));
 	HIP_TRY(hipMemsetAsync(d_links, 0, sizeof(unsigned long long), st));
 	const u32 nb = (u32) ((n + 255) / 256);
@@ -242,7 +208,7 @@ extern "C" int vdjx_lineage(vdjx_ctx* c, const char* junctions, const uint64_t* 
 	}
 	{
 		vdjx_prof_scope ps(c, "k_lin_pairs");
-		hipLaunchKernelGGL(k_lin_pairs, dim3((u32) items.size()), dim3(64), 0, st, (const LinItem*) d_items, (const ulonglong2*) d_rows,
+		hipLaunchKernelGGL(k_lin_pairs, dim3((u32) items.size()), dim3(64), 0, st, (const HamItem*) d_items, (const ulonglong2*) d_rows,
 		                   (const u32*) d_row_item, d_parent, d_near, d_links);
 	}
 	{

@@ -8,14 +8,13 @@
 // Inside a clone the rows are in index order, so the order of two rows is the order of the caller's indices: the edge keys carry ROW
 // numbers and compare as the model's (d, min(i, j), max(i, j)) do.  Per pair everything happens on the device, in 1 + 3 * rounds
 // dispatches, rounds = ceil(log2(largest clone)), whatever n and the number of clones are; nothing is read back between the rounds:
-//   k_tree_pack   a row = `words` pairs of 64-bit words {bases, mask} in k_lin_pack's encoding (vdjx_lineage.hip): 32 bases per word, 2 bits
-//                 each (A0 T1 C2 G3), the mask with the upper bit of a base's two set where it is not ACGT, bits past the window 0.  The
-//                 window is cut out of the contig at the member's own offset, character by character: any shift.  comp[r] = parent[r] = r.
+//   k_tree_pack   a row = `words` {bases, mask} pairs in vdjx_hamming.h's format, bits past the window 0.  The window is cut out of the
+//                 contig at the member's own offset, character by character: any shift.  comp[r] = parent[r] = r.
 //   k_tree_min    one wave per work item (row block of 64 rows, column slice of the same clone).  Up to 16 words (512 bases) a lane keeps
-//                 its row in registers and the columns go through LDS in tiles, read back as one 16-byte broadcast per word, d as in
-//                 k_lin_pairs; wider windows walk the words in chunks of 16 against tiles of 8 columns, a running d per column.  Against
-//                 every column of another component the lane forms d << 40 | lo << 20 | hi and keeps the smallest; one atomicMin per
-//                 lane on best[comp[row]] at the end (a minimum: the order it lands in does not matter).
+//                 its row in registers and the columns go through LDS in tiles, read back as one 16-byte broadcast per word (ham_word);
+//                 wider windows walk the words in chunks of 16 against tiles of 8 columns, a running d per column.  Against every column of another
+//                 component the lane forms d << 40 | lo << 20 | hi and keeps the smallest; one atomicMin per lane on best[comp[row]]
+//                 at the end (a minimum: the order it lands in does not matter).
 //   k_tree_hook   per component with a best edge: the edge is appended (once: where both ends chose it, the smaller root does) and
 //                 its two ends are united in parent[] (vdjx_unionfind.h: the larger root goes under the smaller).  comp[] -- the
 //                 components this round began with -- is only read.
@@ -34,28 +33,27 @@
 //   k_tree_support    per edge of the batch's trees: the two rows back to the caller's items, one atomicAdd on the end whose scored parent
 //                 is the other.  Per batch only the edge count is read back; the supports once, at the end.
 #include "vdjx_common.h"
+#include "vdjx_hamming.h"
 #include "vdjx_unionfind.h"
 
-#include <algorithm>
 #include <string.h>
 
 #define TREE_NONE 0xFFFFFFFFFFFFFFFFull
-#define TREE_TARGET_ITEMS 4096u          // work items aimed at: 4 waves on each of the 1,024 SIMDs
-#define TREE_ROWS 64u                    // rows per work item: one per lane
 #define TREE_REG_WORDS 16                // a row of up to 16 words (512 bases) stays in registers
 #define TREE_LDS 512u                    // {bases, mask} pairs of a tile: 8 KiB, 64 columns of up to 8 words or 32 of up to 16
 #define TREE_CH_COLS 8                   // the chunked path: columns per tile, each with a running distance in a register
-#define TREE_MA 0xAAAAAAAAu               // the upper bit of every base's two
 
 struct TreeRow { u64 at; u32 wbase, w; };                                      // where the window's characters start; the row's first word; bases
-struct TreeItem { u32 row0, row_end, col0, col_end, words, first, wbase, pad; };   // rows [row0, row_end) (at most 64) against columns [col0, col_end)
-                                                                                // of the clone whose first row is `first` and first word `wbase`
-static_assert(sizeof(TreeRow) == 16 && sizeof(TreeItem) == 32, "uploaded as they are");
+static_assert(sizeof(TreeRow) == 16, "uploaded as it is");
+// the user words of a clone's work items: u[0] the clone's first row, u[1] its first word
 
-// one thread per {bases, mask} pair; ri[rows] is a sentinel whose wbase is the number of pairs
+// one thread per {bases, mask} pair; ri[rows] is a sentinel whose wbase is the number of pairs.  SEL is the jackknife's pack: a row's
+// characters are the replicate's kept window positions (sel: `stride` ascending positions per replicate of the batch, of which the row
+// uses its first q.w); the rows of a replicate are `per_rep` in a run
+template <bool SEL>
 __global__ __launch_bounds__(256) void k_tree_pack(const char* __restrict__ contigs, const TreeRow* __restrict__ ri, u32 rows, u32 total,
-                                                   ulonglong2* __restrict__ out, u32* __restrict__ comp, u32* __restrict__ parent,
-                                                   unsigned long long* __restrict__ best) {
+                                                   const uint16_t* __restrict__ sel, u32 stride, u32 per_rep, ulonglong2* __restrict__ out,
+                                                   u32* __restrict__ comp, u32* __restrict__ parent, unsigned long long* __restrict__ best) {
 	const u32 t = blockIdx.x * 256u + threadIdx.x;
 	if (t >= total) return;
 	u32 lo = 0, hi = rows;                              // the row r with ri[r].wbase <= t < ri[r + 1].wbase
@@ -65,40 +63,27 @@ __global__ __launch_bounds__(256) void k_tree_pack(const char* __restrict__ cont
 	}
 	const TreeRow q = ri[lo];
 	const u32 w = t - q.wbase;
-	u64 x = 0, m = 0;
-	for (u32 k = 0; k < 32u; k++) {
-		const u32 pos = w * 32u + k;
-		if (pos >= q.w) break;
-		const char ch = contigs[q.at + pos];
-		const u32 code = ch == 'A' ? 0u : ch == 'T' ? 1u : ch == 'C' ? 2u : ch == 'G' ? 3u : 4u;
-		if (code < 4u) x |= (u64) code << (2u * k);
-		else m |= 2ull << (2u * k);
-	}
-	out[t] = make_ulonglong2(x, m);
+	const uint16_t* mine = SEL ? sel + (size_t) (lo / per_rep) * stride : nullptr;
+	// (a replicate that keeps nothing of this window: one word of zeros)
+	out[t] = ham_pack_word([&](u32 pos) { return contigs[q.at + (SEL ? mine[pos] : pos)]; }, w, q.w);
 	if (w == 0) { comp[lo] = lo; parent[lo] = lo; best[lo] = TREE_NONE; }
-}
-
-__device__ inline u32 tree_word(const u64 x, const u64 m, const ulonglong2 q) {
-	const u64 t = x ^ q.x, mm = m | q.y;
-	const u32 lo = (u32) t, hi = (u32) (t >> 32);
-	return (u32) __popc(((lo | (lo << 1)) & TREE_MA) | (u32) mm) + (u32) __popc(((hi | (hi << 1)) & TREE_MA) | (u32) (mm >> 32));
 }
 
 __device__ inline u64 tree_key(u32 d, u32 a, u32 b) { return (u64) d << 40 | (u64) (a < b ? a : b) << 20 | (u64) (a < b ? b : a); }
 
 // the register path: W words per row, tiles of TREE_LDS / W columns (a power of two of them)
 template <int W>
-__device__ inline void tree_item(const TreeItem it, const ulonglong2* __restrict__ words, const u32* __restrict__ comp, unsigned long long* best,
+__device__ inline void tree_item(const HamItem it, const ulonglong2* __restrict__ words, const u32* __restrict__ comp, unsigned long long* best,
                                  ulonglong2* tile, u32* tile_comp) {
 	constexpr u32 TC = W <= 8 ? 64u : 32u;
 	const u32 lane = threadIdx.x, myrow = it.row0 + lane;
 	const bool live = myrow < it.row_end;
 	const u32 r = live ? myrow : it.row0;
-	const ulonglong2* cw = words + it.wbase;             // the clone's rows, W pairs each
+	const ulonglong2* cw = words + it.u[1];              // the clone's rows, W pairs each
 	u64 x[W], m[W];
 #pragma unroll
 	for (int w = 0; w < W; w++) {
-		const ulonglong2 q = cw[(size_t) (r - it.first) * W + w];
+		const ulonglong2 q = cw[(size_t) (r - it.u[0]) * W + w];
 		x[w] = q.x;
 		m[w] = q.y;
 	}
@@ -106,7 +91,7 @@ __device__ inline void tree_item(const TreeItem it, const ulonglong2* __restrict
 	u64 bk = TREE_NONE;
 	for (u32 base = it.col0; base < it.col_end; base += TC) {
 		const u32 nc = min(TC, it.col_end - base);
-		const ulonglong2* src = cw + (size_t) (base - it.first) * W;      // (the tile's columns are contiguous)
+		const ulonglong2* src = cw + (size_t) (base - it.u[0]) * W;      // (the tile's columns are contiguous)
 		for (u32 i = lane; i < nc * (u32) W; i += 64u) tile[i] = src[i];
 		if (lane < nc) tile_comp[lane] = comp[base + lane];
 		__syncthreads();
@@ -115,7 +100,7 @@ __device__ inline void tree_item(const TreeItem it, const ulonglong2* __restrict
 			if (!__any(other)) continue;                   // (wave-uniform: a column of every lane's own component)
 			u32 d = 0;
 #pragma unroll
-			for (int w = 0; w < W; w++) d += tree_word(x[w], m[w], tile[c * (u32) W + w]);   // (every lane the same address: one broadcast read of 16 bytes)
+			for (int w = 0; w < W; w++) d += ham_word(x[w], m[w], tile[c * (u32) W + w]);   // (every lane the same address: one broadcast read of 16 bytes)
 			if (other) {
 				const u64 k = tree_key(d, myrow, base + c);
 				bk = k < bk ? k : bk;
@@ -128,13 +113,13 @@ __device__ inline void tree_item(const TreeItem it, const ulonglong2* __restrict
 
 // the chunked path: any number of words.  Per tile of 8 columns the words go by in chunks of 16: the lane's chunk in registers, the
 // columns' in LDS, a running distance per column.  Words past the row's end count as 0 on both sides.
-__device__ inline void tree_item_wide(const TreeItem it, const ulonglong2* __restrict__ words, const u32* __restrict__ comp, unsigned long long* best,
+__device__ inline void tree_item_wide(const HamItem it, const ulonglong2* __restrict__ words, const u32* __restrict__ comp, unsigned long long* best,
                                       ulonglong2* tile, u32* tile_comp) {
-	const u32 lane = threadIdx.x, myrow = it.row0 + lane, W = it.words;
+	const u32 lane = threadIdx.x, myrow = it.row0 + lane, W = it.words, first = it.u[0];
 	const bool live = myrow < it.row_end;
 	const u32 r = live ? myrow : it.row0;
-	const ulonglong2* cw = words + it.wbase;
-	const ulonglong2* mw = cw + (size_t) (r - it.first) * W;
+	const ulonglong2* cw = words + it.u[1];
+	const ulonglong2* mw = cw + (size_t) (r - first) * W;
 	const u32 mine = comp[r];
 	u64 bk = TREE_NONE;
 	for (u32 base = it.col0; base < it.col_end; base += TREE_CH_COLS) {
@@ -153,13 +138,13 @@ __device__ inline void tree_item_wide(const TreeItem it, const ulonglong2* __res
 			}
 			for (u32 i = lane; i < TREE_CH_COLS * TREE_REG_WORDS; i += 64u) {
 				const u32 c = i / TREE_REG_WORDS, w = w0 + i % TREE_REG_WORDS;
-				tile[i] = c < nc && w < W ? cw[(size_t) (base + c - it.first) * W + w] : make_ulonglong2(0, 0);
+				tile[i] = c < nc && w < W ? cw[(size_t) (base + c - first) * W + w] : make_ulonglong2(0, 0);
 			}
 			__syncthreads();
 #pragma unroll
 			for (int c = 0; c < TREE_CH_COLS; c++)
 #pragma unroll
-				for (int w = 0; w < TREE_REG_WORDS; w++) d[c] += tree_word(x[w], m[w], tile[c * TREE_REG_WORDS + w]);
+				for (int w = 0; w < TREE_REG_WORDS; w++) d[c] += ham_word(x[w], m[w], tile[c * TREE_REG_WORDS + w]);
 			__syncthreads();
 		}
 #pragma unroll
@@ -174,28 +159,13 @@ __device__ inline void tree_item_wide(const TreeItem it, const ulonglong2* __res
 }
 
 // one wave per work item; the word count is the clone's, so it is uniform and every loop over words is unrolled
-__global__ __launch_bounds__(64) void k_tree_min(const TreeItem* __restrict__ items, const ulonglong2* __restrict__ words, const u32* __restrict__ comp,
+__global__ __launch_bounds__(64) void k_tree_min(const HamItem* __restrict__ items, const ulonglong2* __restrict__ words, const u32* __restrict__ comp,
                                                  unsigned long long* best) {
 	__shared__ ulonglong2 tile[TREE_LDS];
 	__shared__ u32 tile_comp[64];
-	const TreeItem it = items[blockIdx.x];
-	switch (it.words) {
-		case 1: tree_item<1>(it, words, comp, best, tile, tile_comp); break;
-		case 2: tree_item<2>(it, words, comp, best, tile, tile_comp); break;
-		case 3: tree_item<3>(it, words, comp, best, tile, tile_comp); break;
-		case 4: tree_item<4>(it, words, comp, best, tile, tile_comp); break;
-		case 5: tree_item<5>(it, words, comp, best, tile, tile_comp); break;
-		case 6: tree_item<6>(it, words, comp, best, tile, tile_comp); break;
-		case 7: tree_item<7>(it, words, comp, best, tile, tile_comp); break;
-		case 8: tree_item<8>(it, words, comp, best, tile, tile_comp); break;
-		case 9: tree_item<9>(it, words, comp, best, tile, tile_comp); break;
-		case 10: tree_item<10>(it, words, comp, best, tile, tile_comp); break;
-		case 11: tree_item<11>(it, words, comp, best, tile, tile_comp); break;
-		case 12: tree_item<12>(it, words, comp, best, tile, tile_comp); break;
-		case 13: tree_item<13>(it, words, comp, best, tile, tile_comp); break;
-		case 14: tree_item<14>(it, words, comp, best, tile, tile_comp); break;
-		case 15: tree_item<15>(it, words, comp, best, tile, tile_comp); break;
-		case 16: tree_item<16>(it, words, comp, best, tile, tile_comp); break;
+	const HamItem it = items[blockIdx.x];
+	switch (it.words) {                                    // (W below is the case's constant: HAM_CASES_16 declares it)
+		HAM_CASES_16(tree_item<W>(it, words, comp, best, tile, tile_comp))
 		default: tree_item_wide(it, words, comp, best, tile, tile_comp); break;
 	}
 }
@@ -213,7 +183,7 @@ __global__ __launch_bounds__(256) void k_tree_hook(const u32* __restrict__ comp,
 	if (best[other] == k && other < r) return;            // both ends chose this edge: the smaller root appends and unites
 	const u32 slot = atomicAdd(n_edges, 1u);
 	if (slot < cap) edges[slot] = k;
-	lin_unite(parent, lo, hi);
+	uf_unite(parent, lo, hi);
 }
 
 __global__ __launch_bounds__(256) void k_tree_flat(const u32* __restrict__ parent, u32 rows, u32* __restrict__ comp, unsigned long long* __restrict__ best) {
@@ -223,34 +193,6 @@ __global__ __launch_bounds__(256) void k_tree_flat(const u32* __restrict__ paren
 	for (u32 p = parent[x]; p != x; p = parent[x]) x = p;
 	comp[r] = x;
 	best[r] = TREE_NONE;
-}
-
-// the jackknife's pack: as k_tree_pack, but a row's characters are the replicate's kept window positions (sel: `stride` ascending
-// positions per replicate of the batch, of which the row uses its first q.w); the rows of a replicate are `per_rep` in a run
-__global__ __launch_bounds__(256) void k_tree_pack_sel(const char* __restrict__ contigs, const TreeRow* __restrict__ ri, u32 rows, u32 total,
-                                                       const uint16_t* __restrict__ sel, u32 stride, u32 per_rep, ulonglong2* __restrict__ out,
-                                                       u32* __restrict__ comp, u32* __restrict__ parent, unsigned long long* __restrict__ best) {
-	const u32 t = blockIdx.x * 256u + threadIdx.x;
-	if (t >= total) return;
-	u32 lo = 0, hi = rows;                              // the row r with ri[r].wbase <= t < ri[r + 1].wbase
-	while (hi - lo > 1u) {
-		const u32 mid = (lo + hi) / 2u;
-		if (ri[mid].wbase <= t) lo = mid; else hi = mid;
-	}
-	const TreeRow q = ri[lo];
-	const u32 w = t - q.wbase;
-	const uint16_t* mine = sel + (size_t) (lo / per_rep) * stride;
-	u64 x = 0, m = 0;
-	for (u32 k = 0; k < 32u; k++) {
-		const u32 pos = w * 32u + k;
-		if (pos >= q.w) break;                            // (a replicate that keeps nothing of this window: one word of zeros)
-		const char ch = contigs[q.at + mine[pos]];
-		const u32 code = ch == 'A' ? 0u : ch == 'T' ? 1u : ch == 'C' ? 2u : ch == 'G' ? 3u : 4u;
-		if (code < 4u) x |= (u64) code << (2u * k);
-		else m |= 2ull << (2u * k);
-	}
-	out[t] = make_ulonglong2(x, m);
-	if (w == 0) { comp[lo] = lo; parent[lo] = lo; best[lo] = TREE_NONE; }
 }
 
 // one thread per edge of the batch's replicate trees: row r is member r % per_rep of its replicate, item[] the caller's index of a member.
@@ -334,22 +276,8 @@ static int tree_lay(const char* who, const std::vector<u64>& keys, int len, cons
 	return VDJX_OK;
 }
 
-// the work items: (clone, row block, column slice), as vdjx_lineage sizes them: the slice is a whole number of 64 columns, as wide as
-// it takes for about TREE_TARGET_ITEMS items in all.  A clone of one has none.
-static void tree_items(const std::vector<TreeClone>& clones, u64 cells, std::vector<TreeItem>& items) {
-	const u64 per = (cells + (u64) TREE_ROWS * TREE_TARGET_ITEMS - 1) / ((u64) TREE_ROWS * TREE_TARGET_ITEMS);
-	const u32 slice = (u32) std::max<u64>(TREE_ROWS, (per + TREE_ROWS - 1) / TREE_ROWS * TREE_ROWS);
-	for (const TreeClone& q : clones) {
-		if (q.m < 2) continue;
-		const u32 end = q.first + q.m;
-		for (u32 r0 = q.first; r0 < end; r0 += TREE_ROWS)
-			for (u32 c0 = q.first; c0 < end; c0 += slice)
-				items.push_back({r0, std::min(end, r0 + TREE_ROWS), c0, std::min(end, c0 + slice), q.words, q.first, q.wbase, 0u});
-	}
-}
-
 // Boruvka's rounds over laid-out rows (packed, comp = parent = the row, best = none): per round min, hook, flat; nothing is read back
-static void tree_rounds(vdjx_ctx* c, hipStream_t st, u32 rounds, const TreeItem* d_items, u32 n_items, const ulonglong2* d_words, u32 rows, u32* d_comp,
+static void tree_rounds(vdjx_ctx* c, hipStream_t st, u32 rounds, const HamItem* d_items, u32 n_items, const ulonglong2* d_words, u32 rows, u32* d_comp,
                         u32* d_parent, unsigned long long* d_best, unsigned long long* d_edges, u32 cap, u32* d_count) {
 	const u32 nb = (rows + 255u) / 256u;
 	for (u32 round = 0; round < rounds; round++) {
@@ -401,8 +329,10 @@ extern "C" int vdjx_tree(vdjx_ctx* c, const char* contigs, size_t n, int len, co
 	inf.clones = (u32) clones.size();
 	inf.edges = (u64) rows - clones.size();
 	while ((1ull << inf.rounds) < inf.largest_clone) inf.rounds++;
-	std::vector<TreeItem> items;
-	tree_items(clones, L.cells, items);
+	const u32 slice = ham_slice_width(L.cells);
+	std::vector<HamItem> items;                            // a clone of two and more is a group (a clone of one has no item)
+	for (const TreeClone& q : clones)
+		if (q.m >= 2) ham_slice_items({q.first, q.m, q.words, {q.first, q.wbase, 0u}}, slice, items);
 	const u32 cap = (u32) inf.edges;
 	std::vector<u64> edges(cap ? cap : 1);
 	u32 n_edges = 0;
@@ -412,7 +342,7 @@ extern "C" int vdjx_tree(vdjx_ctx* c, const char* contigs, size_t n, int len, co
 		vdjx_work wk(c);
 		char* d_contigs;
 		TreeRow* d_ri;
-		TreeItem* d_items;
+		HamItem* d_items;
 		ulonglong2* d_words;
 		u32 *d_comp, *d_parent, *d_count;
 		unsigned long long *d_best, *d_edges;
@@ -427,12 +357,12 @@ extern "C" int vdjx_tree(vdjx_ctx* c, const char* contigs, size_t n, int len, co
 		HIP_TRY(wk.alloc(&d_count, 1));
 		HIP_TRY(hipMemcpyAsync(d_contigs, contigs, n * (size_t) len, hipMemcpyHostToDevice, st));
 		HIP_TRY(hipMemcpyAsync(d_ri, ri.data(), ((size_t) rows + 1) * sizeof(TreeRow), hipMemcpyHostToDevice, st));
-		HIP_TRY(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(TreeItem), hipMemcpyHostToDevice, st));
+		HIP_TRY(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(HamItem), hipMemcpyHostToDevice, st));
 		HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(u32), st));
 		{
 			vdjx_prof_scope ps(c, "k_tree_pack");
-			hipLaunchKernelGGL(k_tree_pack, dim3((u32) ((total + 255) / 256)), dim3(256), 0, st, (const char*) d_contigs, (const TreeRow*) d_ri, rows, (u32) total,
-			                   d_words, d_comp, d_parent, d_best);
+			hipLaunchKernelGGL(k_tree_pack<false>, dim3((u32) ((total + 255) / 256)), dim3(256), 0, st, (const char*) d_contigs, (const TreeRow*) d_ri, rows, (u32) total,
+			                   (const uint16_t*) nullptr, 0u, 1u, d_words, d_comp, d_parent, d_best);      // (sel, stride, per_rep: not read without SEL)
 		}
 		tree_rounds(c, st, inf.rounds, d_items, (u32) items.size(), d_words, rows, d_comp, d_parent, d_best, d_edges, cap, d_count);
 		HIP_TRY(hipMemcpyAsync(&n_edges, d_count, sizeof n_edges, hipMemcpyDeviceToHost, st));
@@ -569,15 +499,16 @@ extern "C" int vdjx_tree_support(vdjx_ctx* c, const char* contigs, size_t n, int
 		const vdjx_arena::mark_t mk = wk.mark();
 		std::vector<uint16_t> sel;
 		std::vector<TreeRow> ri;
-		std::vector<TreeClone> bc;
-		std::vector<TreeItem> items;
+		std::vector<HamItem> items;
+		u64 rep_cells = 0;                                   // the squared clone sizes of one replicate
+		for (const Big& g : big) rep_cells += (u64) g.m * g.m;
 		for (u32 r0 = 0; r0 < B; r0 += per_batch) {
 			const u32 reps = std::min(per_batch, B - r0), brows = reps * M, cap = reps * per_edges;
 			sel.assign((size_t) reps * maxw, 0);
 			ri.resize((size_t) brows + 1);
-			bc.clear();
 			items.clear();
-			u64 total = 0, cells = 0;
+			const u32 slice = ham_slice_width((u64) reps * rep_cells);
+			u64 total = 0;
 			for (u32 k = 0; k < reps; k++) {
 				const u64 r = (u64) r0 + k + 1;                 // replicates count from 1
 				uint16_t* mine = sel.data() + (size_t) k * maxw;
@@ -592,17 +523,15 @@ extern "C" int vdjx_tree_support(vdjx_ctx* c, const char* contigs, size_t n, int
 					const u32 words = std::max(1u, (kw + 31u) / 32u), first = k * M + g.first;
 					if (total + (u64) g.m * words > 0xFFFFFFFFull) { vdjx_set_error("%s: more than 2^32 packed words", who); return VDJX_ELIMIT; }
 					for (u32 p = 0; p < g.m; p++) ri[first + p] = {at[g.first + p], (u32) total + p * words, kw};
-					bc.push_back({first, g.m, words, (u32) total, first, kw});
+					ham_slice_items({first, g.m, words, {first, (u32) total, 0u}}, slice, items);      // each (replicate, clone) a group of its own
 					total += (u64) g.m * words;
-					cells += (u64) g.m * g.m;
 				}
 			}
 			ri[brows] = {0, (u32) total, 0};
-			tree_items(bc, cells, items);
 			work_items += items.size();
 			uint16_t* d_sel;
 			TreeRow* d_ri;
-			TreeItem* d_items;
+			HamItem* d_items;
 			ulonglong2* d_words;
 			u32 *d_comp, *d_parent, *d_count;
 			unsigned long long *d_best, *d_edges;
@@ -617,11 +546,11 @@ extern "C" int vdjx_tree_support(vdjx_ctx* c, const char* contigs, size_t n, int
 			HIP_TRY(wk.alloc(&d_count, 1));
 			HIP_TRY(hipMemcpyAsync(d_sel, sel.data(), sel.size() * sizeof(uint16_t), hipMemcpyHostToDevice, st));
 			HIP_TRY(hipMemcpyAsync(d_ri, ri.data(), ((size_t) brows + 1) * sizeof(TreeRow), hipMemcpyHostToDevice, st));
-			HIP_TRY(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(TreeItem), hipMemcpyHostToDevice, st));
+			HIP_TRY(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(HamItem), hipMemcpyHostToDevice, st));
 			HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(u32), st));
 			{
 				vdjx_prof_scope ps(c, "k_tree_pack_sel");
-				hipLaunchKernelGGL(k_tree_pack_sel, dim3((u32) ((total + 255) / 256)), dim3(256), 0, st, (const char*) d_contigs, (const TreeRow*) d_ri, brows, (u32) total,
+				hipLaunchKernelGGL(k_tree_pack<true>, dim3((u32) ((total + 255) / 256)), dim3(256), 0, st, (const char*) d_contigs, (const TreeRow*) d_ri, brows, (u32) total,
 				                   (const uint16_t*) d_sel, maxw, M, d_words, d_comp, d_parent, d_best);
 			}
 			tree_rounds(c, st, inf.rounds, d_items, (u32) items.size(), d_words, brows, d_comp, d_parent, d_best, d_edges, cap, d_count);

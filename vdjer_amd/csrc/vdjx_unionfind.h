@@ -7,22 +7,22 @@
 #include "vdjx_common.h"
 
 // a word another wave may be changing: read past this CU's L1
-__device__ inline u32 lin_peek(const u32* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ inline u32 uf_peek(const u32* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-__device__ inline u32 lin_find(u32* parent, u32 x) {
+__device__ inline u32 uf_find(u32* parent, u32 x) {
 	for (;;) {
-		const u32 p = lin_peek(parent + x);
+		const u32 p = uf_peek(parent + x);
 		if (p == x) return x;
-		const u32 g = lin_peek(parent + p);
+		const u32 g = uf_peek(parent + p);
 		if (g != p) atomicMin(parent + x, g);          // (path halving; g is an ancestor of x and smaller than p)
 		x = g;
 	}
 }
 
-__device__ inline void lin_unite(u32* parent, u32 a, u32 b) {
+__device__ inline void uf_unite(u32* parent, u32 a, u32 b) {
 	for (;;) {
-		a = lin_find(parent, a);
-		b = lin_find(parent, b);
+		a = uf_find(parent, a);
+		b = uf_find(parent, b);
 		if (a == b) return;
 		const u32 hi = a > b ? a : b, lo = a > b ? b : a;
 		const u32 old = atomicCAS(parent + hi, hi, lo);

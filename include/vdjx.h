@@ -301,7 +301,8 @@ int vdjx_sam_merge(vdjx_ctx* ctx, uint64_t n_blocks, uint64_t n_bytes, const voi
  *   stop              after iteration t when max_c |N_c(t) - N_c(t-1)| / max(N_c(t), 1) < tol, or at t = max_iter (tol 0: max_iter)
  * out_counts[n] = N (RSEM's expected_count; TPM, FPKM and IsoPct follow from it and info->eff_len = sum_{f <= len} P(f) (len - f + 1)).
  * NOT modelled: RSEM's noise transcript, read qualities and mismatches (a placement here is exact), fragment-length tails outside
- * [50, 400], Gibbs sampling and credibility intervals, gene-level grouping (every contig is its own gene).  Bitwise reproducible
+ * [50, 400], Gibbs sampling and credibility intervals (vdjx_quant_boot below bootstraps the counts instead), gene-level grouping (every
+ * contig is its own gene).  Bitwise reproducible
  * (no floating-point atomics).  n = 0 and pools that place no pair give zeros.  Contigs of unequal length (a NUL inside the n*len
  * characters), max_iter < 1 and tol < 0 are VDJX_EINVAL; fewer than 2^20 contigs of fewer than 4096 bases per call (vdjx_sam_blocks'
  * limit).  Scratch comes from the context's workspace; the text of an earlier vdjx_sam_text stays valid.  One GPU only (a pool sharded
@@ -319,6 +320,42 @@ int vdjx_quant(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const vdjx
  * zeros, converged = 1 and the eff_len of a histogram without counts. */
 int vdjx_quant_pairs(vdjx_ctx* ctx, const uint64_t* offsets, const vdjx_pair* pairs, size_t n, int len, uint32_t n_pairs,
                      const vdjx_quant_params* params, double* out_counts, vdjx_quant_info* info);
+/* ---- the bootstrap of the abundances: what `rsem-calculate-expression --calc-ci` (kallisto's and salmon's bootstrap) adds to the table
+ * The bootstrap is over the placed pairs, everything else held fixed (kallisto's bootstrap):
+ *   slots             the placed pairs in ascending pair id are the slots q = 0 .. Pp - 1 (vdjx_quant's pair-major order)
+ *   multiplicities    replicate r (1 .. B) draws Pp times; draw i (0 .. Pp - 1) falls on slot hi64(mix64(mix64(seed) + (r << 32 | i)) * Pp),
+ *                     vdjx_diversity's draw rule with W = Pp; m_r[q] = the draws on slot q, counted exactly in uint32 (integer atomics)
+ *   fixed inputs      the point estimate's, from the original sample: P(f), g(f), eff_len and the start value N_c = Pp / contigs with
+ *                     a placement
+ *   iteration         E: r_a = N_c(a) g(f_a) / sum over the pair's alignments (unchanged);  M: N_c = sum over the alignments a on c of
+ *                     m_r[pair(a)] * r_a
+ *   stop              vdjx_quant's rule, per replicate, with an iteration count of its own (tol 0: max_iter iterations)
+ * No floating-point atomics: a replicate's N is a fixed function of (placements, seed, r, max_iter, tol); its bits do not depend on the
+ * batch it ran in, on how many replicates shared the batch, or on the call before.  out_counts and info are vdjx_quant's for the same
+ * input, bit for bit; out_boot[B * n] is replicate-major (row r - 1 is replicate r), out_iters[B] the iterations of every replicate.
+ * boot_info: converged = replicates whose last delta was below tol, batches, max_iterations = the most iterations of a replicate,
+ * iterations = their sum.  The replicates run in batches of max(1, floor(VDJX_QBOOT_CELLS / (pairs + n))) whole replicates (a replicate
+ * takes a cell per placed pair and per contig).  VDJX_EINVAL: replicates outside 1 .. 1024, and everything vdjx_quant refuses;
+ * VDJX_ELIMIT: replicates * n >= 2^27, and vdjx_quant's limits.  n = 0 and pools that place no pair give zeros, iterations 0 and
+ * converged = replicates.  Scratch comes from the context's workspace; nothing more is kept on the device.  Stats: "quant_boot_us",
+ * "quant_boot_em_us" (host clock).  NOT modelled: a resampled fragment-length distribution (P(f) is the original sample's), Gibbs
+ * sampling, intervals for TPM / FPKM.
+ * vdjx_quant_pairs_boot: the same over the caller's placements (vdjx_quant_pairs' arguments and refusals).  mult (NULL, or B * n_pairs
+ * by replicate and pair id): the draws are skipped and m_r[q] is read from the caller -- a weighted EM; entries of ids without a
+ * placement are ignored, a replicate whose placed multiplicities sum to 2^32 or more is VDJX_EINVAL.  out_mult (NULL, or B * n_pairs):
+ * the multiplicities used, 0 for ids without a placement.
+ * vdjx_quant_boot_summary (plain C, no GPU): per contig of a B x n replicate-major matrix, mean = the replicates added in the order
+ * r = 1 .. B over B; sd = sqrt(sum (x_r - mean)^2 / (B - 1)) in the same order, 0 at B = 1; with v the B values sorted ascending,
+ * lower = v[floor(25 (B - 1) / 1000)] and upper = v[ceil(975 (B - 1) / 1000)] (integer arithmetic: the 2.5 % and 97.5 % order
+ * statistics).  An output that is NULL is left out. */
+typedef struct { int replicates; uint64_t seed; } vdjx_quant_boot_params;
+typedef struct { uint32_t replicates, converged, batches, max_iterations; uint64_t iterations; } vdjx_quant_boot_info;
+int vdjx_quant_boot(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const vdjx_quant_params* params, const vdjx_quant_boot_params* boot_params,
+                    double* out_counts, vdjx_quant_info* info, double* out_boot, uint32_t* out_iters, vdjx_quant_boot_info* boot_info);
+int vdjx_quant_pairs_boot(vdjx_ctx* ctx, const uint64_t* offsets, const vdjx_pair* pairs, size_t n, int len, uint32_t n_pairs,
+                          const vdjx_quant_params* params, const vdjx_quant_boot_params* boot_params, const uint32_t* mult, uint32_t* out_mult,
+                          double* out_counts, vdjx_quant_info* info, double* out_boot, uint32_t* out_iters, vdjx_quant_boot_info* boot_info);
+void vdjx_quant_boot_summary(const double* boot, uint32_t B, size_t n, double* mean, double* sd, double* lower, double* upper);
 
 /* ---- contig annotation: V/J calls, identity and CIGARs against the germline segments (the ref-dir's ig_vdj.fa) -----------------------
  * replaces the IMGT HighV-QUEST round trip of the reference's post_process/ (collect_vdjer_stats.py reads the V gene, the J gene, the

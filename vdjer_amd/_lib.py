@@ -18,7 +18,7 @@ SYMBOLS = [
     "vdjx_anchor_sets_load", "vdjx_anchor_probe", "vdjx_index_generate", "vdjx_anchor_sets_from_anchors",
     "vdjx_kmer_build", "vdjx_graph_nodes", "vdjx_graph_pre_nodes", "vdjx_graph_export", "vdjx_graph_export_begin", "vdjx_graph_export_end", "vdjx_graph_block_layout", "vdjx_graph_export_block", "vdjx_graph_export_block_begin", "vdjx_graph_free",
     "vdjx_vregion_load", "vdjx_root_score", "vdjx_graph_roots", "vdjx_root_part", "vdjx_root_score_graph", "vdjx_root_score_graph_begin", "vdjx_root_score_graph_end",
-    "vdjx_read_index_build", "vdjx_read_index_build_device", "vdjx_read_index_build_begin", "vdjx_read_index_build_device_begin", "vdjx_read_index_build_end", "vdjx_window_score", "vdjx_window_pairs", "vdjx_window_pairs_fetch", "vdjx_window_cover", "vdjx_map_emit", "vdjx_map_emit_begin", "vdjx_map_emit_end", "vdjx_sam_names_load", "vdjx_sam_text", "vdjx_sam_blocks", "vdjx_sam_merge", "vdjx_rows_scatter", "vdjx_quant", "vdjx_quant_pairs", "vdjx_germline_load", "vdjx_annotate", "vdjx_constant_load", "vdjx_isotype", "vdjx_dsegment_load", "vdjx_dcall", "vdjx_lineage", "vdjx_tree", "vdjx_tree_support", "vdjx_mutations_layout", "vdjx_mutations", "vdjx_diversity", "vdjx_scan_u32", "vdjx_part_u64",
+    "vdjx_read_index_build", "vdjx_read_index_build_device", "vdjx_read_index_build_begin", "vdjx_read_index_build_device_begin", "vdjx_read_index_build_end", "vdjx_window_score", "vdjx_window_pairs", "vdjx_window_pairs_fetch", "vdjx_window_cover", "vdjx_map_emit", "vdjx_map_emit_begin", "vdjx_map_emit_end", "vdjx_sam_names_load", "vdjx_sam_text", "vdjx_sam_blocks", "vdjx_sam_merge", "vdjx_rows_scatter", "vdjx_quant", "vdjx_quant_pairs", "vdjx_quant_boot", "vdjx_quant_pairs_boot", "vdjx_quant_boot_summary", "vdjx_germline_load", "vdjx_annotate", "vdjx_constant_load", "vdjx_isotype", "vdjx_dsegment_load", "vdjx_dcall", "vdjx_lineage", "vdjx_tree", "vdjx_tree_support", "vdjx_mutations_layout", "vdjx_mutations", "vdjx_diversity", "vdjx_scan_u32", "vdjx_part_u64",
     "vdjx_host_alloc", "vdjx_host_free", "vdjx_host_take_rows",
     "vdjx_stat", "vdjx_profile_enable", "vdjx_profile_only", "vdjx_profile_reset", "vdjx_profile_count", "vdjx_profile_get",
     "vdjx_shard_begin", "vdjx_shard_begin_share", "vdjx_shard_free", "vdjx_shard_record_bytes", "vdjx_shard_count", "vdjx_shard_geometry", "vdjx_shard_symmetric", "vdjx_shard_geometry2", "vdjx_shard_local", "vdjx_shard_local_fill",
@@ -49,6 +49,15 @@ class QuantParams(C.Structure):
 class QuantInfo(C.Structure):
     _fields_ = [("pairs", C.c_uint64), ("alignments", C.c_uint64), ("unique_pairs", C.c_uint64), ("iterations", C.c_uint32),
                 ("converged", C.c_uint32), ("eff_len", C.c_double)]
+
+
+class QuantBootParams(C.Structure):
+    _fields_ = [("replicates", C.c_int), ("seed", C.c_uint64)]
+
+
+class QuantBootInfo(C.Structure):
+    _fields_ = [("replicates", C.c_uint32), ("converged", C.c_uint32), ("batches", C.c_uint32), ("max_iterations", C.c_uint32),
+                ("iterations", C.c_uint64)]
 
 
 class AnnotParams(C.Structure):
@@ -189,6 +198,12 @@ def lib():
     L.vdjx_sam_merge.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, vp, C.POINTER(C.c_char_p), C.POINTER(C.c_uint64)]
     L.vdjx_quant.argtypes = [vp, C.c_char_p, sz, i32, C.POINTER(QuantParams), vp, C.POINTER(QuantInfo)]
     L.vdjx_quant_pairs.argtypes = [vp, vp, vp, sz, i32, C.c_uint32, C.POINTER(QuantParams), vp, C.POINTER(QuantInfo)]
+    L.vdjx_quant_boot.argtypes = [vp, C.c_char_p, sz, i32, C.POINTER(QuantParams), C.POINTER(QuantBootParams), vp, C.POINTER(QuantInfo), vp, vp,
+                                  C.POINTER(QuantBootInfo)]
+    L.vdjx_quant_pairs_boot.argtypes = [vp, vp, vp, sz, i32, C.c_uint32, C.POINTER(QuantParams), C.POINTER(QuantBootParams), vp, vp, vp,
+                                        C.POINTER(QuantInfo), vp, vp, C.POINTER(QuantBootInfo)]
+    L.vdjx_quant_boot_summary.argtypes = [vp, C.c_uint32, sz, vp, vp, vp, vp]
+    L.vdjx_quant_boot_summary.restype = None
     L.vdjx_germline_load.argtypes = [vp, C.c_char_p, vp, C.c_char_p, sz]
     L.vdjx_annotate.argtypes = [vp, C.c_char_p, sz, i32, C.POINTER(AnnotParams), vp, vp]
     L.vdjx_constant_load.argtypes = [vp, C.c_char_p, vp, sz]

@@ -198,6 +198,29 @@ def diversity_draw(seed, r, i, W):
     return _mix64((_mix64(seed) + (r << 32 | i)) & ((1 << 64) - 1)) * W >> 64
 
 
+def quant_boot_draw(seed, r, i, Pp):
+    """the draw rule of vdjx_quant_boot (include/vdjx.h) in plain Python -> the slot in 0 .. Pp - 1 that draw i (0 .. Pp - 1) of replicate
+    r (1 .. replicates) falls on: vdjx_diversity's rule with W = Pp, the placed pairs in ascending pair id being the slots"""
+    return diversity_draw(seed, r, i, Pp)
+
+
+def quant_boot_summary(boot):
+    """vdjx_quant_boot_summary (plain C, no GPU) over a float64[B, n] matrix of replicate counts -> dict of float64[n]: mean, sd (n - 1;
+    0 at B = 1), lower and upper (the 2.5 % and 97.5 % order statistics)"""
+    import ctypes as C
+
+    import numpy as np
+
+    from . import _lib
+    boot = np.ascontiguousarray(boot, np.float64)
+    if boot.ndim != 2 or boot.shape[0] < 1:
+        raise ValueError(f"a B x n matrix of replicate counts with B >= 1, not shape {boot.shape}")
+    B, n = boot.shape
+    out = {k: np.zeros(n, np.float64) for k in ("mean", "sd", "lower", "upper")}
+    _lib.lib().vdjx_quant_boot_summary(boot.ctypes.data_as(C.c_void_p), B, n, *(out[k].ctypes.data_as(C.c_void_p) for k in ("mean", "sd", "lower", "upper")))
+    return out
+
+
 def diversity_weights(clone, count_cells):
     """what `vdjer --diversity` hands to vdjx_diversity, from the lineage of every contig (Context.lineage's "clone"; -1: in none) and the
     printed expected_count cell of every contig ("12.34": two decimals, as the quant table has them) -> (uint64[C] weights, int list of

@@ -611,35 +611,98 @@ class Context:
         info = _lib.QuantInfo()
         prm = _lib.QuantParams(int(max_iter), float(tol))
         check(self.L.vdjx_quant(self.h, raw, n, ln, C.byref(prm), _p(counts), C.byref(info)), "vdjx_quant")
-        return counts, dict(pairs=int(info.pairs), alignments=int(info.alignments), unique_pairs=int(info.unique_pairs),
-                            iterations=int(info.iterations), converged=bool(info.converged), eff_len=float(info.eff_len))
+        return counts, self._quant_info(info)
 
-    def quant_pairs(self, offsets, pairs, length: int, n_pairs: int, max_iter: int = 10000, tol: float = 1e-5):
-        """vdjx_quant_pairs: the same model over placements the caller brings, in map_emit's shape (contig-major): offsets[n + 1],
-        `pairs` a PAIR_DTYPE array of offsets[n] placements or a (pair_id, insert) tuple of arrays, packed here.  Only pair_id and
-        insert are read; no pool and no read index are needed.  -> what quant returns"""
+    @staticmethod
+    def _placements(who, offsets, pairs):
+        """the placements of quant_pairs / quant_pairs_boot -> (offsets uint64[n + 1], PAIR_DTYPE array, n)"""
         offs = _c(offsets, np.uint64)
         if offs.ndim != 1 or offs.shape[0] < 1:
-            raise VdjxError("vdjx_quant_pairs: offsets must hold n + 1 entries")
+            raise VdjxError(f"{who}: offsets must hold n + 1 entries")
         n = offs.shape[0] - 1
         if isinstance(pairs, tuple):
             pid, ins = (np.asarray(x) for x in pairs)
             if pid.shape != ins.shape or pid.ndim != 1:
-                raise VdjxError("vdjx_quant_pairs: pair_id and insert of unequal shape")
+                raise VdjxError(f"{who}: pair_id and insert of unequal shape")
             packed = np.zeros(pid.shape[0], PAIR_DTYPE)
             packed["pair_id"] = pid
             packed["insert"] = ins
         else:
             packed = _c(pairs, PAIR_DTYPE)
         if n and packed.shape[0] != int(offs[n]):
-            raise VdjxError(f"vdjx_quant_pairs: {packed.shape[0]} placements, offsets[n]={int(offs[n])}")
+            raise VdjxError(f"{who}: {packed.shape[0]} placements, offsets[n]={int(offs[n])}")
+        return offs, packed, n
+
+    def quant_pairs(self, offsets, pairs, length: int, n_pairs: int, max_iter: int = 10000, tol: float = 1e-5):
+        """vdjx_quant_pairs: the same model over placements the caller brings, in map_emit's shape (contig-major): offsets[n + 1],
+        `pairs` a PAIR_DTYPE array of offsets[n] placements or a (pair_id, insert) tuple of arrays, packed here.  Only pair_id and
+        insert are read; no pool and no read index are needed.  -> what quant returns"""
+        offs, packed, n = self._placements("vdjx_quant_pairs", offsets, pairs)
         counts = np.zeros(n, np.float64)
         info = _lib.QuantInfo()
         prm = _lib.QuantParams(int(max_iter), float(tol))
         check(self.L.vdjx_quant_pairs(self.h, _p(offs), _p(packed), n, int(length), int(n_pairs), C.byref(prm), _p(counts), C.byref(info)),
               "vdjx_quant_pairs")
-        return counts, dict(pairs=int(info.pairs), alignments=int(info.alignments), unique_pairs=int(info.unique_pairs),
-                            iterations=int(info.iterations), converged=bool(info.converged), eff_len=float(info.eff_len))
+        return counts, self._quant_info(info)
+
+    @staticmethod
+    def _quant_info(info):
+        return dict(pairs=int(info.pairs), alignments=int(info.alignments), unique_pairs=int(info.unique_pairs),
+                    iterations=int(info.iterations), converged=bool(info.converged), eff_len=float(info.eff_len))
+
+    @staticmethod
+    def _quant_boot_result(counts, info, boot, iters, binfo):
+        from . import annot
+        out = dict(counts=counts, boot=boot, iterations=iters, info=Context._quant_info(info),
+                   boot_info=dict(replicates=int(binfo.replicates), converged=int(binfo.converged), batches=int(binfo.batches),
+                                  max_iterations=int(binfo.max_iterations), iterations=int(binfo.iterations)))
+        out.update(annot.quant_boot_summary(boot))
+        return out
+
+    def quant_boot(self, contigs, replicates: int = 100, seed: int = 1, max_iter: int = 10000, tol: float = 1e-5):
+        """vdjx_quant_boot: quant's point estimate and `replicates` bootstrap replicates of it over the placed pairs -> dict: counts
+        float64[n] and info (quant's), boot float64[B, n], mean / sd / lower / upper float64[n] (vdjx_quant_boot_summary), iterations
+        uint32[B], boot_info (replicates, converged, batches, max_iterations, iterations)"""
+        if isinstance(contigs, tuple):
+            raw, n, ln = contigs
+        else:
+            if len({len(s_) for s_ in contigs}) > 1:
+                raise VdjxError("vdjx_quant_boot: contigs of unequal length")
+            raw, n, ln = self.pack_strings(contigs)
+        b = int(replicates)
+        rows = b if 1 <= b <= 1024 else 1
+        counts, boot, iters = np.zeros(n, np.float64), np.zeros((rows, n), np.float64), np.zeros(rows, np.uint32)
+        info, binfo = _lib.QuantInfo(), _lib.QuantBootInfo()
+        prm, bprm = _lib.QuantParams(int(max_iter), float(tol)), _lib.QuantBootParams(b, int(seed))
+        check(self.L.vdjx_quant_boot(self.h, raw, n, ln, C.byref(prm), C.byref(bprm), _p(counts), C.byref(info), _p(boot), _p(iters),
+                                     C.byref(binfo)), "vdjx_quant_boot")
+        return self._quant_boot_result(counts, info, boot, iters, binfo)
+
+    def quant_pairs_boot(self, offsets, pairs, length: int, n_pairs: int, replicates: int = 100, seed: int = 1, mult=None,
+                         return_mult: bool = False, max_iter: int = 10000, tol: float = 1e-5):
+        """vdjx_quant_pairs_boot: quant_boot over placements the caller brings (quant_pairs' arguments).  mult: None, or uint32[B, n_pairs]
+        multiplicities by replicate and pair id that replace the draws (a weighted EM); return_mult: also "mult", the multiplicities
+        used (0 for ids without a placement).  -> what quant_boot returns"""
+        offs, packed, n = self._placements("vdjx_quant_pairs_boot", offsets, pairs)
+        b = int(replicates)
+        rows = b if 1 <= b <= 1024 else 1
+        m_in = m_out = None
+        if mult is not None:
+            m_in = _c(mult, np.uint32)
+            if m_in.shape != (rows, int(n_pairs)):
+                raise VdjxError(f"vdjx_quant_pairs_boot: mult of shape {m_in.shape}, not ({rows}, {int(n_pairs)})")
+        if return_mult:
+            m_out = np.zeros((rows, int(n_pairs)), np.uint32)
+        counts, boot, iters = np.zeros(n, np.float64), np.zeros((rows, n), np.float64), np.zeros(rows, np.uint32)
+        info, binfo = _lib.QuantInfo(), _lib.QuantBootInfo()
+        prm, bprm = _lib.QuantParams(int(max_iter), float(tol)), _lib.QuantBootParams(b, int(seed))
+        check(self.L.vdjx_quant_pairs_boot(self.h, _p(offs), _p(packed), n, int(length), int(n_pairs), C.byref(prm), C.byref(bprm),
+                                           _p(m_in) if m_in is not None else None, _p(m_out) if m_out is not None else None, _p(counts),
+                                           C.byref(info), _p(boot), _p(iters), C.byref(binfo)), "vdjx_quant_pairs_boot")
+        out = self._quant_boot_result(counts, info, boot, iters, binfo)
+        if return_mult:
+            out["mult"] = m_out
+        return out
 
     def germline_load(self, names_or_records):
         """vdjx_germline_load: a germline FASTA (path) or a list of (FASTA header, sequence) records -> dict(names, classes, skipped).

@@ -3,12 +3,14 @@
  * vdjh (serial host stage).  Plain C; talks to the GPU only through the C ABI of include/vdjx.h.
  *
  *   vdjer --in <reads> --chain IGH|IGK|IGL --ref-dir <dir> --ins <n> [--t --k --mf --mq --mcs --am --miw --maw
- *         --jc --ws -jext --rf --vk --mrs --rs --ms --e0 --e1 --wo --vf --jf --rms] [--gpus N] [--quant <file>] [--airr <file>]
+ *         --jc --ws -jext --rf --vk --mrs --rs --ms --e0 --e1 --wo --vf --jf --rms] [--gpus N] [--quant <file>] [--quant-boot <B>] [--quant-seed <s>] [--airr <file>]
  *         [--d-calls] [--cfa <fasta>] [--isotypes <file>] [--clones <file>] [--sample <name>] [--total-count <n>]
  *         [--lineages <file>] [--lineage-dist <x>] [--trees <file>] [--tree-support <B>] [--tree-seed <s>] [--mutations <file>]
  *         [--diversity <file>] [--diversity-depth <n>] [--diversity-boot <B>] [--diversity-seed <s>]
  * writes ./vdj_contigs.fa and ./vdjer.dot, SAM on stdout, log on stderr; exit 0 on success.  --quant <file>: the contigs' abundances
- * (vdjx_quant, RSEM's isoforms.results columns) into <file> as well.  --airr <file>: the contigs' V/J annotation (vdjx_annotate against
+ * (vdjx_quant, RSEM's isoforms.results columns) into <file> as well; --quant-boot <B> (with --quant): B bootstrap replicates of them over the placed
+ * pairs (vdjx_quant_boot) drawn from --quant-seed <s>: the columns boot_mean, boot_sd, boot_lower and boot_upper, and in the --lineages table
+ * clone_count_sd, the sd over the replicates of a lineage's summed counts.  --airr <file>: the contigs' V/J annotation (vdjx_annotate against
  * the germlines of ig_vdj.fa / --vdjf) as an AIRR Rearrangement TSV; with --d-calls (a flag: no value) the D gene between the V and the
  * J hit as well (vdjx_dcall against the class-D records of the same FASTA), and the N regions around it.  --cfa <fasta>: constant-region sequences; --isotypes <file>: the
  * isotype call of every contig against them (vdjx_isotype); --clones <file>: the per-sample table of the reference's post_process/
@@ -61,6 +63,8 @@ typedef struct {
 	int anchor_mismatches, threads;
 	int gpus;                              /* --gpus N (not in the reference): the k-mer build sharded over N GPUs of this node */
 	const char* quant;                     /* --quant <file> (not in the reference): the RSEM step of demo/quant_demo.bash, on the device */
+	const char *quant_boot_s, *quant_seed_s;      /* --quant-boot <B>, --quant-seed <s>: the bootstrap of the quant table (vdjx_quant_boot); read into qb_b (0: none) and qb_seed */
+	uint32_t qb_b; uint64_t qb_seed;
 	const char* airr;                      /* --airr <file> (not in the reference): the HighV-QUEST step of post_process/, on the device */
 	int d_calls;                           /* --d-calls (not in the reference; no value): d_call, d_cigar and the N regions in the --airr table */
 	const char* cfa;                       /* --cfa <fasta> (not in the reference): the constant-region sequences of --isotypes / --clones */
@@ -92,6 +96,8 @@ static void usage(void) {
 	                "\t--e0/--e1 <start/stop position for contig filtering (default: 52/411)>\n\t--wo <window overlap check size>\n"
 	                "\t--gpus <GPUs of this node to shard the k-mer table over (default: 1)>\n"
 	                "\t--quant <file: expected read pairs per contig, an RSEM isoforms.results table (one GPU only)>\n"
+	                "\t--quant-boot <B: with --quant, bootstrap the placed pairs B times (a whole number in 1 .. 1024): boot_mean, boot_sd, boot_lower, boot_upper>\n"
+	                "\t--quant-seed <seed of the --quant-boot draws, a whole number below 2^64 (default: 1)>\n"
 	                "\t--airr <file: V/J calls of every contig against ig_vdj.fa, an AIRR Rearrangement table>\n"
 	                "\t--d-calls (no value; with --airr: the D gene between the V and the J hit against the D records of ig_vdj.fa, and np1 / np2)\n"
 	                "\t--cfa <constant-region FASTA for --isotypes / --clones>\n"
@@ -173,6 +179,8 @@ static int parse(int argc, char** argv, cli* c) {
 		else if (!strcmp(a, "--t")) c->threads = atoi(v);
 		else if (!strcmp(a, "--gpus")) c->gpus = atoi(v);
 		else if (!strcmp(a, "--quant")) c->quant = v;
+		else if (!strcmp(a, "--quant-boot")) c->quant_boot_s = v;
+		else if (!strcmp(a, "--quant-seed")) c->quant_seed_s = v;
 		else if (!strcmp(a, "--airr")) c->airr = v;
 		else if (!strcmp(a, "--cfa")) c->cfa = v;
 		else if (!strcmp(a, "--isotypes")) c->isotypes = v;
@@ -225,6 +233,19 @@ static int parse(int argc, char** argv, cli* c) {
 	if (c->hp.insert_len <= 0) { fprintf(stderr, "insert_len must be specified and > 0\n"); ok = 0; }
 	/* (vdjx_vregion_load's limit, said here: before the input is read, let alone a pool loaded) */
 	if (c->hp.vregion_kmer_size < 2 || c->hp.vregion_kmer_size > 16) { fprintf(stderr, "--vk: vregion k-mer size %d outside [2,16]\n", c->hp.vregion_kmer_size); ok = 0; }
+	c->qb_b = 0;
+	c->qb_seed = 1;
+	if (c->quant_boot_s && !c->quant) { fprintf(stderr, "--quant-boot bootstraps the --quant table: it needs --quant <file>\n"); ok = 0; }
+	if (c->quant_seed_s && !c->quant_boot_s) { fprintf(stderr, "--quant-seed is the seed of the --quant-boot replicates: it needs --quant-boot <B>\n"); ok = 0; }
+	if (c->quant_boot_s) {
+		uint64_t b = 0;
+		if (whole_u64(c->quant_boot_s, &b) || b < 1 || b > 1024) { fprintf(stderr, "--quant-boot must be a whole decimal number in 1 .. 1024: %s\n", c->quant_boot_s); ok = 0; }
+		else c->qb_b = (uint32_t) b;
+	}
+	if (c->quant_seed_s && whole_u64(c->quant_seed_s, &c->qb_seed)) {
+		fprintf(stderr, "--quant-seed must be a whole decimal number below 2^64: %s\n", c->quant_seed_s);
+		ok = 0;
+	}
 	if (c->d_calls && !c->airr) { fprintf(stderr, "--d-calls adds the D call to the --airr table: it needs --airr <file>\n"); ok = 0; }
 	if (c->isotypes && !c->cfa) { fprintf(stderr, "--isotypes needs the constant-region sequences: --cfa <fasta>\n"); ok = 0; }
 	if (c->cfa) {
@@ -613,6 +634,9 @@ typedef struct {
 	int quant_done;
 	vdjx_quant_info qi;
 	double* qcnt;                       /* its counts (the --airr table's expected_count) */
+	uint32_t qb_b; uint64_t qb_seed;    /* --quant-boot <B> --quant-seed <s>: the bootstrap (0: none) */
+	double* qboot;                      /* its qb_b x n replicate counts, replicate-major (the --lineages table's clone_count_sd) */
+	vdjx_quant_boot_info qbi;
 	const char* airr;                   /* --airr <file>: written after the SAM body (and the quant table) */
 	const char* vdjf;
 	int airr_done;
@@ -688,20 +712,35 @@ static int sam_records(void* ud, const char* const* ids, const char* contigs, si
 static int quant_table(hook_ud* u, const char* const* ids, const char* contigs, size_t n, int len) {
 	double* cnt = (double*) calloc(n + 1, sizeof(double));
 	const vdjx_quant_params qp = {10000, 1e-5};
-	int rc = vdjx_quant(u->gx, contigs, n, len, &qp, cnt, &u->qi);
-	if (rc) { fprintf(stderr, "vdjx_quant: %s\n", vdjx_last_error()); free(cnt); return rc; }
+	const uint32_t B = u->quant ? u->qb_b : 0;
+	double* st = NULL;                  /* the bootstrap's summary: mean, sd, lower, upper, n each */
+	int rc;
+	if (B) {
+		const vdjx_quant_boot_params bp = {(int) B, u->qb_seed};
+		uint32_t* iters = (uint32_t*) calloc(B, sizeof(uint32_t));
+		free(u->qboot);
+		u->qboot = (double*) calloc((size_t) B * n + 1, sizeof(double));
+		st = (double*) calloc(4 * n + 1, sizeof(double));
+		rc = vdjx_quant_boot(u->gx, contigs, n, len, &qp, &bp, cnt, &u->qi, u->qboot, iters, &u->qbi);
+		free(iters);
+		if (!rc) vdjx_quant_boot_summary(u->qboot, B, n, st, st + n, st + 2 * n, st + 3 * n);
+	} else rc = vdjx_quant(u->gx, contigs, n, len, &qp, cnt, &u->qi);
+	if (rc) { fprintf(stderr, "%s: %s\n", B ? "vdjx_quant_boot" : "vdjx_quant", vdjx_last_error()); free(cnt); free(st); return rc; }
 	if (!u->quant) { free(u->qcnt); u->qcnt = cnt; u->quant_done = 1; return 0; }      /* (--clones alone: the counts, no table) */
 	FILE* fp = fopen(u->quant, "w");
-	if (!fp) { fprintf(stderr, "cannot write %s\n", u->quant); free(cnt); return -1; }
+	if (!fp) { fprintf(stderr, "cannot write %s\n", u->quant); free(cnt); free(st); return -1; }
 	free(u->qcnt);
 	double sum = 0.0;
 	for (size_t i = 0; i < n; i++) sum += cnt[i];
 	const double eff = u->qi.eff_len;
-	fprintf(fp, "transcript_id\tgene_id\tlength\teffective_length\texpected_count\tTPM\tFPKM\tIsoPct\n");
+	fprintf(fp, "transcript_id\tgene_id\tlength\teffective_length\texpected_count\tTPM\tFPKM\tIsoPct%s\n", B ? "\tboot_mean\tboot_sd\tboot_lower\tboot_upper" : "");
 	for (size_t i = 0; i < n; i++) {
 		const double tpm = sum > 0.0 ? 1e6 * cnt[i] / sum : 0.0, fpkm = sum > 0.0 && eff > 0.0 ? cnt[i] * 1e9 / (eff * sum) : 0.0;
-		fprintf(fp, "%s\t%s\t%d\t%.2f\t%.2f\t%.2f\t%.2f\t%.2f\n", ids[i], ids[i], len, eff, cnt[i], tpm, fpkm, cnt[i] > 0.0 ? 100.0 : 0.0);
+		fprintf(fp, "%s\t%s\t%d\t%.2f\t%.2f\t%.2f\t%.2f\t%.2f", ids[i], ids[i], len, eff, cnt[i], tpm, fpkm, cnt[i] > 0.0 ? 100.0 : 0.0);
+		if (B) fprintf(fp, "\t%.2f\t%.2f\t%.2f\t%.2f", st[i], st[n + i], st[2 * n + i], st[3 * n + i]);
+		fputc('\n', fp);
 	}
+	free(st);
 	u->qcnt = cnt;
 	if (fclose(fp)) { fprintf(stderr, "cannot write %s\n", u->quant); return -1; }
 	u->quant_done = 1;
@@ -1116,6 +1155,7 @@ static int lineage_run(hook_ud* u, const char* const* ids, const char* contigs, 
 	FILE* fp = fopen(u->lineages, "w");
 	if (!fp) { fprintf(stderr, "cannot write %s\n", u->lineages); return -1; }
 	const int counted = u->quant || u->clones;
+	const uint32_t B = counted && u->qboot ? u->qb_b : 0;      /* --quant-boot: clone_count_sd */
 	char* cat = (char*) malloc(n * (size_t) VDJX_LINEAGE_MAXLEN + 1);
 	uint64_t* off = (uint64_t*) calloc(n + 1, sizeof(uint64_t));
 	uint32_t* grp = (uint32_t*) calloc(n + 1, sizeof(uint32_t));
@@ -1168,18 +1208,32 @@ static int lineage_run(hook_ud* u, const char* const* ids, const char* contigs, 
 			size[u->lin_clone[i]]++;
 			sum[u->lin_clone[i]] += atof(cnt);
 		}
-		fprintf(fp, "sequence_id\tclone_id\tvgene\tjgene\tjunction_length\tdist_nearest\tclone_size%s\n", counted ? "\tclone_expected_count" : "");
+		/* clone_count_sd: per lineage and replicate the members' unrounded replicate counts added in contig order, then the sd of
+		 * vdjx_quant_boot_summary over the replicates */
+		const size_t nk = (size_t) u->li.clones;
+		double* csd = (double*) calloc(nk + 1, sizeof(double));
+		if (B) {
+			double* cb = (double*) calloc((size_t) B * nk + 1, sizeof(double));
+			for (uint32_t r = 0; r < B; r++)
+				for (size_t i = 0; i < n; i++)
+					if (u->lin_clone[i] >= 0) cb[(size_t) r * nk + (size_t) u->lin_clone[i]] += u->qboot[(size_t) r * n + i];
+			vdjx_quant_boot_summary(cb, B, nk, NULL, csd, NULL, NULL);
+			free(cb);
+		}
+		fprintf(fp, "sequence_id\tclone_id\tvgene\tjgene\tjunction_length\tdist_nearest\tclone_size%s%s\n", counted ? "\tclone_expected_count" : "",
+		        B ? "\tclone_count_sd" : "");
 		for (size_t i = 0; i < n; i++) {
 			const int32_t k = u->lin_clone[i];
 			const uint64_t L = off[i + 1] - off[i];
-			if (k < 0) { fprintf(fp, "%s\t\t%s\t%s\t\t\t%s\n", ids[i], vgs[i], jgs[i], counted ? "\t" : ""); continue; }
+			if (k < 0) { fprintf(fp, "%s\t\t%s\t%s\t\t\t%s%s\n", ids[i], vgs[i], jgs[i], counted ? "\t" : "", B ? "\t" : ""); continue; }
 			fprintf(fp, "%s\tlin_%d\t%s\t%s\t%llu\t", ids[i], k + 1, vgs[i], jgs[i], (unsigned long long) L);
 			if (near[i] >= 0) fprintf(fp, "%.4f", (double) near[i] / (double) L);
 			fprintf(fp, "\t%zu", size[k]);
 			if (counted) fprintf(fp, "\t%.2f", sum[k]);
+			if (B) fprintf(fp, "\t%.2f", csd[k]);
 			fputc('\n', fp);
 		}
-		free(size); free(sum);
+		free(size); free(sum); free(csd);
 	}
 	for (size_t i = 0; i < n; i++) { free(vgs[i]); free(jgs[i]); }
 	for (size_t k = 0; k < nkeys; k++) free(keys[k]);
@@ -1640,6 +1694,7 @@ int main(int argc, char** argv) {
 
 	hook_ud ud;
 	memset(&ud, 0, sizeof ud);
+	ud.qb_b = c.qb_b; ud.qb_seed = c.qb_seed;
 	ud.gx = gx; ud.p = &c.hp; ud.mg = mg; ud.quant = c.quant; ud.airr = c.airr; ud.vdjf = c.vdj_fasta; ud.d_calls = c.d_calls;
 	ud.cfa = c.cfa; ud.isotypes = c.isotypes; ud.clones = c.clones; ud.total_count = c.total_count;
 	ud.lineages = c.lineages; ud.lin_num = c.lin_num; ud.lin_den = c.lin_den; ud.trees = c.trees;
@@ -1690,6 +1745,9 @@ int main(int argc, char** argv) {
 		fprintf(stderr, "quant: %llu pairs placed (%llu once), %llu alignments, %u EM iterations, %s; table in %s\n", (unsigned long long) ud.qi.pairs,
 		        (unsigned long long) ud.qi.unique_pairs, (unsigned long long) ud.qi.alignments, ud.qi.iterations,
 		        ud.qi.converged ? "converged" : "stopped at the iteration limit", c.quant);
+	if (c.quant && c.qb_b)
+		fprintf(stderr, "quant boot: %u replicates (seed %llu), %llu EM iterations in all (most %u), %u stopped at the iteration limit, %u batches\n", ud.qbi.replicates,
+		        (unsigned long long) c.qb_seed, (unsigned long long) ud.qbi.iterations, ud.qbi.max_iterations, ud.qbi.replicates - ud.qbi.converged, ud.qbi.batches);
 	if (c.airr)
 		fprintf(stderr, "airr: %zu contigs, %zu V called, %zu J called, %zu productive, %zu CIGARs truncated; germline records skipped: %zu D, %zu other; table in %s\n",
 		        ud.a_contigs, ud.a_v, ud.a_j, ud.a_prod, ud.a_trunc, ud.a_skip_d, ud.a_skip_other, c.airr);

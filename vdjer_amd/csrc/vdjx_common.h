@@ -379,6 +379,14 @@ struct vdjx_qrows {
 	const uint8_t* a; const uint8_t* b; size_t split; int stride;
 	__host__ __device__ inline const uint8_t* row(size_t rec) const { return rec < split ? a + rec * (size_t) stride : b + (rec - split) * (size_t) stride; }
 };
+// splitmix64's output step: the counter-based generator behind every rule of include/vdjx.h that draws (the keep rule of
+// vdjx_tree_support, the draws of vdjx_diversity and vdjx_quant_boot)
+__host__ __device__ inline u64 vdjx_mix64(u64 x) {
+	u64 z = x + 0x9E3779B97F4A7C15ull;
+	z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+	z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+	return z ^ (z >> 31);
+}
 __host__ __device__ inline u64 vdjx_mix(u64 lo, u64 hi) {
 	u64 x = lo ^ (hi * 0x9E3779B97F4A7C15ull) ^ 0x2545F4914F6CDD1Dull;
 	x ^= x >> 32; x *= 0xD6E8FEB86659FD93ull;

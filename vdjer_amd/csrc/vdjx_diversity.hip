@@ -35,14 +35,6 @@
 #define DIV_HILL_WG 32u                  // at most this many workgroups (partials) per replicate
 #define DIV_TARGET_WG 1024u              // draw workgroups aimed at: two rounds of two per CU
 
-// splitmix64's output step (include/vdjx.h: the keep rule of vdjx_tree_support)
-__host__ __device__ static inline u64 div_mix64(u64 x) {
-	u64 z = x + 0x9E3779B97F4A7C15ull;
-	z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-	z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-	return z ^ (z >> 31);
-}
-
 // cum[0 .. C) is read (cum[C] = W > t never has to be); seedmix = mix64(seed); replicate r = r0 + blockIdx.y + 1
 template <bool LDS_HIST>
 __global__ __launch_bounds__(1024) void k_div_draw(const u64* __restrict__ cum, u32 C, u32 stride, u32 ncoarse, u64 W, u64 seedmix, u32 r0, u32 N,
@@ -58,7 +50,7 @@ __global__ __launch_bounds__(1024) void k_div_draw(const u64* __restrict__ cum, 
 	const u64 r = (u64) r0 + blockIdx.y + 1u;
 	const u64 begin = (u64) blockIdx.x * per_slice, end = min(begin + per_slice, (u64) N);
 	for (u64 i = begin + tid; i < end; i += DIV_DRAW_THREADS) {
-		const u64 u = div_mix64(seedmix + (r << 32 | i));
+		const u64 u = vdjx_mix64(seedmix + (r << 32 | i));
 		const u64 t = __umul64hi(u, W);                     // < W
 		u32 lo = 0, hi = ncoarse;                          // coarse[0] = 0 <= t: the largest j with coarse[j] <= t
 		while (hi - lo > 1u) {
@@ -213,7 +205,7 @@ extern "C" int vdjx_diversity(vdjx_ctx* c, const uint64_t* weight, size_t C, con
 	HIP_TRY(hipMemcpyAsync(out_observed, d_d, Q * sizeof(double), hipMemcpyDeviceToHost, st));
 	HIP_TRY(hipStreamSynchronize(st));
 	HIP_TRY(hipGetLastError());
-	const u64 seedmix = div_mix64(params->seed);
+	const u64 seedmix = vdjx_mix64(params->seed);
 	for (u32 r0 = 0; r0 < B; r0 += per_batch) {
 		const u32 reps = std::min(per_batch, B - r0);
 		// slices of a replicate: enough workgroups to fill the device, but every one with draws to speak of (the LDS path: four per counter it flushes)

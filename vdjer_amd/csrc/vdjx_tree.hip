@@ -414,14 +414,6 @@ extern "C" int vdjx_tree(vdjx_ctx* c, const char* contigs, size_t n, int len, co
 	return VDJX_OK;
 }
 
-// splitmix64's output step (include/vdjx.h: the keep rule)
-static inline u64 tree_mix64(u64 x) {
-	u64 z = x + 0x9E3779B97F4A7C15ull;
-	z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-	z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-	return z ^ (z >> 31);
-}
-
 // vdjx_tree_support -- the delete-half jackknife over the window's columns.  The host lays the clones of two and more out once ("per
 // replicate": member p of M), computes every replicate's kept positions and, per batch of whole replicates, the rows (replicate-major:
 // row = replicate * M + p) with their kept counts and the work items; a batch is 1 + 3 * rounds + 1 dispatches: k_tree_pack_sel, the
@@ -515,7 +507,7 @@ extern "C" int vdjx_tree_support(vdjx_ctx* c, const char* contigs, size_t n, int
 				u32 kept = 0;
 				u64 bits = 0;
 				for (u32 q = 0; q < maxw; q++) {
-					if ((q & 31u) == 0) bits = tree_mix64(params->seed ^ (r << 32 | (u64) (q >> 5)));
+					if ((q & 31u) == 0) bits = vdjx_mix64(params->seed ^ (r << 32 | (u64) (q >> 5)));
 					if (bits >> (q & 31u) & 1u) mine[kept++] = (uint16_t) q;
 				}
 				for (const Big& g : big) {

@@ -623,9 +623,10 @@ int vdjx_tree_support(vdjx_ctx* ctx, const char* contigs, size_t n, int len, con
  *               contig i's rows start in each of the three row buffers, out_off[n] the size of each.  Deletions make cols exceed len.
  *   output      contig i's rows go to out_seq / out_germ / out_mask + out_off[i], cols bytes, no terminator; each of the three may be
  *               NULL.  out_rows is required.
- * NOT modelled: IMGT gaps and numbering, and so no CDR1 / CDR2 / FWR split of the counts; V records that begin inside a codon (IMGT's
- * 5'-partial sequences: their codons are shifted); R/S for the J segment; expected mutation counts, targeting models (HH_S5F) and
- * selection (BASELINe); a clonal consensus germline (CreateGermlines --cloned); a germline node as the root of `--trees`.
+ * NOT modelled: IMGT gaps and numbering (the CDR / FWR split of the counts by the caller's intervals, the expected counts under a
+ * targeting model and the selection strength are vdjx_selection's, below); V records that begin inside a codon (IMGT's 5'-partial
+ * sequences: their codons are shifted); R/S for the J segment; a clonal consensus germline (CreateGermlines --cloned); a germline node as
+ * the root of `--trees`.
  * VDJX_EINVAL (the message names the contig): a usable hit whose gene is out of range or names a record of the wrong class (v: 'V', j:
  * 'J'); germ_end past the record's end; seq_start or germ_start < 1, seq_end > len; a run with an op outside 0..2 or a length of 0; M + I
  * run lengths that do not sum to seq_end - seq_start + 1, M + D run lengths that do not sum to germ_end - germ_start + 1; a limit outside
@@ -640,6 +641,70 @@ int vdjx_mutations_layout(const vdjx_annot_hit* v, const vdjx_annot_hit* d, cons
 int vdjx_mutations(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const vdjx_annot_hit* v, const vdjx_annot_hit* d,
                    const vdjx_annot_hit* j, const int32_t* limit, char* out_seq, char* out_germ, char* out_mask,
                    vdjx_mut_row* out_rows, vdjx_mut_info* info);
+
+/* ---- selection strength: observed against expected R / S of the V segment, and the posterior of sigma (BASELINe) ----------------------
+ * gives `vdjer --selection` what shazam's expectedMutations / calcBaseline / groupBaseline / summarizeBaseline make of the mutation counts
+ * in a second tool: whether the replacement share departs from what the germline's codons and the mutation process alone would give.  The
+ * counts and weights are integer: the device's are bitwise the model's (tests/selection_model.py).  The posterior is float64.
+ *   inputs      contigs, n, len, v[n] and limit[n] as vdjx_mutations takes them (no J, no D).  cdr: the region map (below) or NULL;
+ *               weight: the targeting model, uint32 [1024][4], or NULL (uniform); group[n]: the group 0 .. G - 1 of every contig, negative:
+ *               in no group (may be NULL when G = 0).
+ *   observed    the classifiable codons of the V hit exactly as vdjx_mutations defines them, limit included; each differing base is
+ *               classified as there (R, S or stop) and counted in the REGION of the germline position that carries the base; stops are
+ *               counted in neither obs_r nor obs_s.  A codon is counted (codons) in the region of its first base.  Summed over the regions
+ *               obs_r, obs_s and codons are vdjx_mutations' v_r, v_s and v_codons.
+ *   expected    (integer, exact) for every base position p of a classifiable codon whose germline codon is not a stop, and each of the
+ *               three other bases b: the germline codon with b at p is a stop: nothing; it translates like the germline codon: w goes to
+ *               exp_s; otherwise w goes to exp_r -- of the region of p.  w = weight[idx5(p)][b], idx5 = 256 g[p-2] + 64 g[p-1] + 16 g[p] +
+ *               4 g[p+1] + g[p+2] (A 0, C 1, G 2, T 3) over the RECORD's bases, not the hit's; one of the five outside the record or not
+ *               ACGT: the position adds nothing.  weight == NULL: w = 1 at every position, whatever its neighbours.  Weights are uint32,
+ *               sums uint64.  (The entry weight[..][g[p]] of the centre base itself is never read.)
+ *   region map  cdr: four int32 per record, indexed by the record index given to vdjx_germline_load (n_records rows): cdr1_start,
+ *               cdr1_end, cdr2_start, cdr2_end; 1-based, inclusive, ungapped positions of the record; 0, 0: no such interval.  A position
+ *               inside either interval is CDR (region 1), every other is FWR (region 0).  A record whose first entry is -1 has no regions:
+ *               its contigs take no part (flag 32, all counts 0, info->no_regions).  Rows of records that are not V records are not read.
+ *               cdr == NULL: one region, the whole V (K = 1); otherwise K = 2.
+ *   counts      out_counts[i]: obs_r, obs_s, codons, exp_r, exp_s per region (index 1 is 0 when K = 1); flags: 1 V used, 16 the hit has
+ *               more than 64 runs (treated as absent, as in vdjx_mutations), 32 the V record has no regions.
+ *   statistic   (BASELINe's focused test; its local test when K = 1) contig i in region k: x = obs_r[k], n = obs_r[k] + the sum over the
+ *               regions of obs_s, odds exp_r[k] : the sum over the regions of exp_s.  A contig with n = 0, exp_r[k] = 0 or that sum 0 adds
+ *               nothing to region k and is not counted in `sequences`.
+ *   posterior   on the fixed grid sigma_t = (t - 2000) / 100, t = 0 .. 4000 (VDJX_SEL_GRID points, -20 .. 20).  For a row (a set of
+ *               contigs) and a region, with softplus(z) = max(z, 0) + log1p(exp(-|z|)):
+ *                   l(sigma) = sigma - 2 softplus(sigma) + sum over the members of [ x_i z_i - n_i softplus(z_i) ],
+ *                   z_i = sigma + ln(exp_r_i) - ln(exp_s_i)
+ *               The first term is the prior, a standard logistic on sigma centred on no selection (a uniform prior on the replacement share
+ *               when the expected share is 1/2); the sum is the binomial log-likelihood of a shared sigma with every member's own expected
+ *               odds.  f_t = exp(l_t - max l), S = sum f_t; pdf_t = f_t / (0.01 S); sigma = sum sigma_t f_t / S; cdf_t = sum over u <= t
+ *               of f_u / S; lower (upper): sigma_t of the first t with cdf_t >= 0.025 (0.975); p_positive = (sum over t > 2000 of f_t + f_2000
+ *               / 2) / S.
+ *   rows        one per contig (a set of one), one per group 0 .. G - 1, one last for all contigs: n + G + 1 rows of K regions;
+ *               out_stat[row * K + region].  sequences: the contributing members; x, n, exp_r, exp_s: their sums.  A row without one is
+ *               the prior alone: sigma 0, p_positive 1/2.  out_pdf (may be NULL): the densities of the G + 1 group and sample rows,
+ *               [(G + 1)][K][VDJX_SEL_GRID].
+ *   info        (may be NULL; zeroed first) contigs = n; used: rows with flag 1; no_regions: flag 32; truncated: flag 16; groups = G;
+ *               regions = K; chunks: the partial sums of large rows (below), over both regions; large_rows: the rows that had them.
+ * NOT modelled: shazam's fitted priors (BAYESIAN_FITTED); its convolution of the members' densities -- a group here is a SHARED sigma, not
+ * the distribution of a weighted mean of the members'; IMGT numbering (the regions are the caller's intervals); N-averaged 5-mers; one
+ * representative per clone for the sample row; the J segment; the comparison of two groups' densities.
+ * VDJX_EINVAL (the message names the contig or the record): vdjx_mutations' list for the contigs, the V hits and the limit; n_records is not
+ * the number of records given to vdjx_germline_load; an interval of a V record with start > end, start < 1 or end past the record; group[i]
+ * >= G; G >= 2^20; out_pdf with G + 1 > 65,536; NULL out_counts or out_stat.  VDJX_ESTATE: no germline set is loaded.  n = 0 returns at
+ * once with a zeroed info.  Three kernels: k_sel_counts (one dispatch, a wave per contig; integer only, no atomics), then on the host the
+ * members' x, n and log-odds and ONE sort of the members by group; k_sel_loglik only for rows of more than `chunk` members (VDJX_SEL_CHUNK,
+ * 1 .. 65,536, default 1024, read per call): a row's members are cut into chunks in order and every chunk's sum over its members, in
+ * contig order, is stored per grid point -- at most 2n / chunk + G + 1 chunks per region; k_sel_finish, a workgroup per (row, region), adds a
+ * row's chunks in order (or its members directly) to the prior and reduces.  No float atomics, every sum in a fixed order: two calls with
+ * the same VDJX_SEL_CHUNK give the same bits.  Scratch comes from the context's workspace.  Stats: "selection_us" (host clock),
+ * "selection_chunks". */
+#define VDJX_SEL_GRID 4001
+typedef struct { int32_t obs_r[2], obs_s[2], codons[2]; uint32_t flags, pad; uint64_t exp_r[2], exp_s[2]; } vdjx_sel_counts;   /* 64 bytes */
+typedef struct { uint32_t sequences, pad; uint64_t x, n, exp_r, exp_s; double sigma, lower, upper, p_positive; } vdjx_sel_stat;   /* 72 bytes */
+typedef struct { uint64_t contigs, used, no_regions, truncated; uint32_t groups, regions, chunks, large_rows; } vdjx_sel_info;    /* 48 bytes */
+int vdjx_selection(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const vdjx_annot_hit* v, const int32_t* limit, const int32_t* cdr,
+                   size_t n_records, const uint32_t* weight /* 1024 * 4, or NULL */, const int32_t* group, uint32_t G,
+                   vdjx_sel_counts* out_counts /* n */, vdjx_sel_stat* out_stat /* (n + G + 1) * K, row-major */,
+                   double* out_pdf /* NULL, or (G + 1) * K * 4001: the group rows, then the sample row */, vdjx_sel_info* info);
 
 /* ---- bootstrap clonal diversity: the Hill curve D(q) of the clone abundances, resampled to a common depth -----------------------------
  * gives `vdjer --diversity` what alakazam's estimateAbundance / alphaDiversity make of the clone table in a second tool: richness, Shannon
@@ -708,6 +773,7 @@ int vdjx_part_u64(vdjx_ctx* ctx, const void* host_in, size_t n, int elem_bytes, 
  * vdjx_isotype's last call: "iso_cells" (DP cells of the scoring phase), "iso_score_us", "iso_trace_us" (host clock, each ending in a wait).
  * vdjx_dcall's last call: "dcall_cells" (the sum of win_len times the sum of the records' lengths), "dcall_score_us", "dcall_trace_us".
  * vdjx_mutations' last call: "mutations_cols" (the bytes of each of the three row buffers), "mutations_us" (host clock).
+ * vdjx_selection's last call: "selection_chunks" (the partial sums of its large rows), "selection_us" (host clock).
  * vdjx_diversity's last call: "diversity_batches", "diversity_us" (host clock).
  * What the context keeps from call to call outside its workspaces (anchor bitmaps, V region, read index, the scorers' result and SAM
  * buffers, upload staging, germline / constant / D sets), counted when asked: "kept_device_bytes", "kept_pinned_bytes" (page-locked host

@@ -166,6 +166,86 @@ def mutation_limit(ids, contigs):
     return out
 
 
+SELECTION_GRID = 4001                                       # VDJX_SEL_GRID (include/vdjx.h)
+
+
+def selection_grid():
+    """the grid of vdjx_selection's posterior -> float64[4001]: sigma_t = (t - 2000) / 100, -20 .. 20"""
+    import numpy as np
+    return (np.arange(SELECTION_GRID, dtype=np.float64) - 2000.0) / 100.0
+
+
+def _whole(text: str, below: int):
+    """the whole text as a decimal number below `below` (digits only, at least one), or None"""
+    if not text or any(ch not in "0123456789" for ch in text) or len(text) > 20 or int(text) >= below:
+        return None
+    return int(text)
+
+
+def read_v_regions(path: str, names, unmatched=None):
+    """the region map of `vdjer --selection --v-regions` -> int32[records, 4] for vdjx_selection's cdr.  Lines `name cdr1_start cdr1_end
+    cdr2_start cdr2_end`, separated by tabs or blanks; '#' lines and blank lines are skipped.  Positions are whole decimal numbers, 1-based
+    and inclusive, 0 0 for no interval.  names: the records' names as parse_name gives them, in record order; every record of a line's name
+    gets its intervals, a record without a line is -1 -1 -1 -1 (no regions).  A name that matches no record is appended to `unmatched`
+    (when given).  ValueError, naming the line: not five fields, a position that is no whole number below 2^31, start > end, start 0 with
+    end not 0, a name given twice."""
+    import numpy as np
+    out = np.full((len(names), 4), -1, np.int32)
+    where = {}
+    for r, nm in enumerate(names):
+        where.setdefault(nm, []).append(r)
+    seen = set()
+    with open(path) as f:
+        for no, line in enumerate(f, 1):
+            t = line.split()
+            if not t or t[0].startswith("#"):
+                continue
+            iv = [_whole(x, 1 << 31) for x in t[1:]]
+            if len(t) != 5 or None in iv:
+                raise ValueError(f"{path}: line {no}: expected `name cdr1_start cdr1_end cdr2_start cdr2_end` with whole numbers")
+            for a, b in (iv[:2], iv[2:]):
+                if a > b or (a == 0 and b != 0):
+                    raise ValueError(f"{path}: line {no}: the interval {a} .. {b} (1 <= start <= end, or 0 0)")
+            if t[0] in seen:
+                raise ValueError(f"{path}: line {no}: the name {t[0]} is given twice")
+            seen.add(t[0])
+            if t[0] not in where:
+                if unmatched is not None:
+                    unmatched.append(t[0])
+                continue
+            for r in where[t[0]]:
+                out[r] = iv
+    return out
+
+
+def read_targeting(path: str):
+    """the targeting model of `vdjer --selection --targeting` -> uint32[1024, 4] for vdjx_selection's weight: row 256 a + 64 b + 16 c + 4 d +
+    e of the 5-mer abcde (A 0, C 1, G 2, T 3), column the new base.  Exactly 1,024 lines `<5-mer> <wA> <wC> <wG> <wT>`, separated by tabs or
+    blanks, each 5-mer over ACGT once; '#' lines and blank lines are skipped.  Weights are whole decimal numbers below 2^32 (the user scales
+    the model, e.g. HH_S5F's targeting times 10^6); the column of the centre base is read and never used.  ValueError, naming the line."""
+    import numpy as np
+    out = np.zeros((1024, 4), np.uint32)
+    seen = set()
+    with open(path) as f:
+        for no, line in enumerate(f, 1):
+            t = line.split()
+            if not t or t[0].startswith("#"):
+                continue
+            w = [_whole(x, 1 << 32) for x in t[1:]]
+            if len(t) != 5 or None in w or len(t[0]) != 5 or any(ch not in "ACGT" for ch in t[0]):
+                raise ValueError(f"{path}: line {no}: expected `<5-mer over ACGT> <wA> <wC> <wG> <wT>` with whole numbers below 2^32")
+            idx = 0
+            for ch in t[0]:
+                idx = 4 * idx + "ACGT".index(ch)
+            if idx in seen:
+                raise ValueError(f"{path}: line {no}: the 5-mer {t[0]} is given twice")
+            seen.add(idx)
+            out[idx] = w
+    if len(seen) != 1024:
+        raise ValueError(f"{path}: {len(seen)} 5-mers, expected every one of the 1024 once")
+    return out
+
+
 def _mix64(x):
     """splitmix64's output step, in 64-bit wrap-around arithmetic"""
     m = (1 << 64) - 1

@@ -859,6 +859,53 @@ class Context:
         return {"seq": text[0], "germ": text[1], "mask": text[2], "counts": {f: out[f].copy() for f in self.MUT_ROW.names},
                 "info": {f: int(getattr(info, f)) for f in self.MUT_INFO_FIELDS}}
 
+    SEL_COUNTS = np.dtype([("obs_r", "<i4", 2), ("obs_s", "<i4", 2), ("codons", "<i4", 2), ("flags", "<u4"), ("pad", "<u4"), ("exp_r", "<u8", 2),
+                           ("exp_s", "<u8", 2)])
+    SEL_STAT = np.dtype([("sequences", "<u4"), ("pad", "<u4"), ("x", "<u8"), ("n", "<u8"), ("exp_r", "<u8"), ("exp_s", "<u8"), ("sigma", "<f8"),
+                         ("lower", "<f8"), ("upper", "<f8"), ("p_positive", "<f8")])
+    SEL_INFO_FIELDS = ("contigs", "used", "no_regions", "truncated", "groups", "regions", "chunks", "large_rows")
+
+    def selection(self, contigs, v, limit=None, cdr=None, weight=None, group=None, groups=None, pdf: bool = False):
+        """vdjx_selection: the observed R / S counts of the V segment per region, the expected R / S weights of its germline codons and the
+        posterior of the selection strength per contig, per group and for all contigs.  v: the field dict annotate() returns; limit:
+        int32[n] or None; cdr: int32[records, 4] (annot.read_v_regions) or None (one region); weight: uint32[1024, 4]
+        (annot.read_targeting) or None (uniform); group: int32[n] (negative: in no group) or None; groups: G (None: max(group) + 1)
+        -> {"counts": {field: array[n] or [n, 2]}, "stat": {field: array[n + G + 1, K]}, "pdf": float64[G + 1, K, 4001] | None, "info":
+        dict}"""
+        if isinstance(contigs, tuple):
+            raw, n, ln = contigs
+        else:
+            if len({len(s_) for s_ in contigs}) > 1:
+                raise VdjxError("vdjx_selection: contigs of unequal length")
+            raw, n, ln = self.pack_strings(contigs)
+        hv = self._hit_array(v, n, "v")
+        lim = None if limit is None else np.ascontiguousarray(limit, np.int32)
+        if lim is not None and lim.shape != (n,):
+            raise VdjxError(f"vdjx_selection: {n} contigs, limit of shape {lim.shape}")
+        reg = None if cdr is None else np.ascontiguousarray(cdr, np.int32)
+        if reg is not None and (reg.ndim != 2 or reg.shape[1] != 4):
+            raise VdjxError(f"vdjx_selection: cdr of shape {reg.shape}")
+        w = None if weight is None else np.ascontiguousarray(weight, np.uint32)
+        if w is not None and w.shape != (1024, 4):
+            raise VdjxError(f"vdjx_selection: weight of shape {w.shape}")
+        grp = None if group is None else np.ascontiguousarray(group, np.int32)
+        if grp is not None and grp.shape != (n,):
+            raise VdjxError(f"vdjx_selection: {n} contigs, group of shape {grp.shape}")
+        g = int(groups) if groups is not None else (int(grp.max()) + 1 if grp is not None and n and int(grp.max()) >= 0 else 0)
+        if not 0 <= g < 1 << 32:
+            raise VdjxError(f"vdjx_selection: {g} groups")
+        k = 1 if reg is None else 2
+        big = g >= 1 << 20                                            # (a count the library refuses: nothing is written)
+        counts = np.zeros(n, self.SEL_COUNTS)
+        stat = np.zeros((1 if big else n + g + 1, k), self.SEL_STAT)
+        dens = (np.zeros((g + 1, k, 4001)) if g + 1 <= 65536 else np.zeros(1)) if pdf else None      # (as above: refused, not written)
+        info = _lib.SelInfo()
+        check(self.L.vdjx_selection(self.h, raw, n, ln, _p(hv), _p(lim), _p(reg), 0 if reg is None else reg.shape[0], _p(w), _p(grp), g,
+                                    _p(counts), _p(stat), _p(dens), C.byref(info)), "vdjx_selection")
+        return {"counts": {f: counts[f].copy() for f in self.SEL_COUNTS.names if f != "pad"},
+                "stat": {f: stat[f].copy() for f in self.SEL_STAT.names if f != "pad"}, "pdf": dens,
+                "info": {f: int(getattr(info, f)) for f in self.SEL_INFO_FIELDS}}
+
     LINEAGE_NONE = 0xFFFFFFFF                                # VDJX_LINEAGE_NONE (include/vdjx.h)
 
     def lineage(self, junctions, group, max_dist=(1500, 10000), nearest: bool = True):

@@ -7,6 +7,7 @@
  *         [--d-calls] [--cfa <fasta>] [--isotypes <file>] [--clones <file>] [--sample <name>] [--total-count <n>]
  *         [--lineages <file>] [--lineage-dist <x>] [--trees <file>] [--tree-support <B>] [--tree-seed <s>] [--mutations <file>]
  *         [--diversity <file>] [--diversity-depth <n>] [--diversity-boot <B>] [--diversity-seed <s>]
+ *         [--selection <file>] [--v-regions <file>] [--targeting <file>]
  * writes ./vdj_contigs.fa and ./vdjer.dot, SAM on stdout, log on stderr; exit 0 on success.  --quant <file>: the contigs' abundances
  * (vdjx_quant, RSEM's isoforms.results columns) into <file> as well; --quant-boot <B> (with --quant): B bootstrap replicates of them over the placed
  * pairs (vdjx_quant_boot) drawn from --quant-seed <s>: the columns boot_mean, boot_sd, boot_lower and boot_upper, and in the --lineages table
@@ -26,6 +27,10 @@
  * --diversity <file> (with --lineages and the quant step): the Hill diversity curve of the lineages weighed by their expected counts,
  * orders 0.0 .. 4.0, with the mean and spread of --diversity-boot <B> bootstrap replicates of --diversity-depth <n> draws each
  * (vdjx_diversity: alakazam's alphaDiversity), drawn from --diversity-seed <s>.
+ * --selection <file>: the selection strength of the V segment's mutations (vdjx_selection: shazam's expectedMutations / calcBaseline /
+ * groupBaseline / summarizeBaseline): observed against expected replacement and silent mutations and the posterior of sigma for every
+ * contig, every lineage (with --lineages) and the sample, below --mutations' limit; --v-regions <file>: the CDR1 / CDR2 intervals of the V
+ * records, which split every row into fwr and cdr; --targeting <file>: a 5-mer targeting model (default: uniform).
  *
  * --in: a BAM with its .bai (extraction as bam_read.c:264-446, restated over zlib in bamx.c), or -- recognised by its
  * content -- the extracted read pool as text, one read per line in extraction order:
@@ -82,6 +87,10 @@ typedef struct {
 	const char* diversity;                 /* --diversity <file> (not in the reference): alakazam's alphaDiversity over the lineages, on the device */
 	const char *div_depth_s, *div_boot_s, *div_seed_s;      /* --diversity-depth <n> (read into div_depth; 0: the total expected pairs), --diversity-boot <B>, --diversity-seed <s> */
 	uint32_t div_depth, div_boot; uint64_t div_seed;
+	const char* selection;                 /* --selection <file> (not in the reference): shazam's BASELINe over the V segment, on the device */
+	const char *v_regions, *targeting;     /* --v-regions <file>, --targeting <file>: read by parse() into regs / nregs and weight (NULL: uniform) */
+	struct vreg_line* regs; size_t nregs;
+	uint32_t* weight;
 	int have_chain, have_ref;
 } cli;
 
@@ -114,7 +123,10 @@ static void usage(void) {
 	                "\t--diversity <file: with --lineages and --quant or --clones, the Hill diversity curve of the lineages, orders 0.0 .. 4.0, bootstrapped>\n"
 	                "\t--diversity-depth <n: draws per bootstrap replicate, a whole number in 1 .. 2147483647 (default: the lineages' total expected pairs)>\n"
 	                "\t--diversity-boot <B: bootstrap replicates, a whole number in 1 .. 4096 (default: 200)>\n"
-	                "\t--diversity-seed <seed of the draws, a whole number below 2^64 (default: 1)>\n");
+	                "\t--diversity-seed <seed of the draws, a whole number below 2^64 (default: 1)>\n"
+	                "\t--selection <file: selection strength (BASELINe) of the V mutations: observed and expected R / S and the posterior of sigma per contig, lineage (with --lineages) and sample>\n"
+	                "\t--v-regions <file: with --selection, lines `name cdr1_start cdr1_end cdr2_start cdr2_end` (1-based, inclusive, 0 0: none) of the V records: rows fwr and cdr>\n"
+	                "\t--targeting <file: with --selection, 1024 lines `<5-mer> <wA> <wC> <wG> <wT>`, whole numbers below 2^32 (default: uniform)>\n");
 }
 
 static int file_exists(const char* f) { struct stat b; return stat(f, &b) == 0; }
@@ -142,6 +154,87 @@ static int whole_u64(const char* s, uint64_t* out) {
 	}
 	*out = x;
 	return 0;
+}
+
+/* --v-regions: lines `name cdr1_start cdr1_end cdr2_start cdr2_end`, separated by tabs or blanks; '#' lines and blank lines are skipped
+ * (read_v_regions of vdjer_amd/annot.py).  The names meet the germline records later (sel_run). */
+typedef struct vreg_line { char* name; int32_t iv[4]; } vreg_line;
+
+static int split_fields(char* line, char** f, int max) {
+	int nf = 0;
+	for (char* t = strtok(line, " \t\r\n"); t; t = strtok(NULL, " \t\r\n")) { if (nf < max) f[nf] = t; nf++; }
+	return nf;
+}
+
+static int read_v_regions(const char* path, vreg_line** out, size_t* n_out) {
+	FILE* fp = fopen(path, "r");
+	if (!fp) { fprintf(stderr, "--v-regions: cannot read %s\n", path); return -1; }
+	char* line = NULL;
+	size_t lcap = 0, n = 0, cap = 0, no = 0;
+	vreg_line* v = NULL;
+	int rc = 0;
+	while (!rc && getline(&line, &lcap, fp) >= 0) {
+		no++;
+		char* f[5];
+		const int nf = split_fields(line, f, 5);
+		if (!nf || f[0][0] == '#') continue;
+		uint64_t x[4] = {0, 0, 0, 0};
+		int bad = nf != 5;
+		for (int k = 0; !bad && k < 4; k++) bad = whole_u64(f[1 + k], &x[k]) || x[k] > 2147483647u;
+		if (bad) { fprintf(stderr, "--v-regions: %s line %zu: expected `name cdr1_start cdr1_end cdr2_start cdr2_end` with whole numbers\n", path, no); rc = -1; break; }
+		for (int k = 0; k < 4; k += 2)
+			if (x[k] > x[k + 1] || (x[k] == 0 && x[k + 1] != 0)) {
+				fprintf(stderr, "--v-regions: %s line %zu: the interval %llu .. %llu (1 <= start <= end, or 0 0)\n", path, no, (unsigned long long) x[k], (unsigned long long) x[k + 1]);
+				rc = -1;
+			}
+		for (size_t q = 0; !rc && q < n; q++)
+			if (!strcmp(v[q].name, f[0])) { fprintf(stderr, "--v-regions: %s line %zu: the name %s is given twice\n", path, no, f[0]); rc = -1; }
+		if (rc) break;
+		if (n + 1 > cap) { cap = cap ? 2 * cap : 256; v = (vreg_line*) realloc(v, cap * sizeof *v); }
+		v[n].name = strdup(f[0]);
+		for (int k = 0; k < 4; k++) v[n].iv[k] = (int32_t) x[k];
+		n++;
+	}
+	free(line);
+	fclose(fp);
+	*out = v;
+	*n_out = n;
+	return rc;
+}
+
+/* --targeting: exactly 1,024 lines `<5-mer> <wA> <wC> <wG> <wT>`, each 5-mer over ACGT once, whole decimal numbers below 2^32; '#' lines and
+ * blank lines are skipped (read_targeting of vdjer_amd/annot.py) -> uint32 [1024][4] */
+static int read_targeting(const char* path, uint32_t** out) {
+	FILE* fp = fopen(path, "r");
+	if (!fp) { fprintf(stderr, "--targeting: cannot read %s\n", path); return -1; }
+	uint32_t* w = (uint32_t*) calloc(4096, sizeof(uint32_t));
+	unsigned char* seen = (unsigned char*) calloc(1024, 1);
+	char* line = NULL;
+	size_t lcap = 0, no = 0, got = 0;
+	int rc = 0;
+	while (getline(&line, &lcap, fp) >= 0) {
+		no++;
+		char* f[5];
+		const int nf = split_fields(line, f, 5);
+		if (!nf || f[0][0] == '#') continue;
+		uint64_t x[4] = {0, 0, 0, 0};
+		int bad = nf != 5 || strlen(f[0]) != 5 || strspn(f[0], "ACGT") != 5;
+		for (int k = 0; !bad && k < 4; k++) bad = whole_u64(f[1 + k], &x[k]) || x[k] > 4294967295ull;
+		if (bad) { fprintf(stderr, "--targeting: %s line %zu: expected `<5-mer over ACGT> <wA> <wC> <wG> <wT>` with whole numbers below 2^32\n", path, no); rc = -1; break; }
+		int idx = 0;
+		for (int k = 0; k < 5; k++) idx = 4 * idx + (int) (strchr("ACGT", f[0][k]) - "ACGT");
+		if (seen[idx]) { fprintf(stderr, "--targeting: %s line %zu: the 5-mer %s is given twice\n", path, no, f[0]); rc = -1; break; }
+		seen[idx] = 1;
+		got++;
+		for (int k = 0; k < 4; k++) w[4 * idx + k] = (uint32_t) x[k];
+	}
+	if (!rc && got != 1024) { fprintf(stderr, "--targeting: %s holds %zu 5-mers, expected every one of the 1024 once\n", path, got); rc = -1; }
+	free(line);
+	free(seen);
+	fclose(fp);
+	if (rc) { free(w); w = NULL; }
+	*out = w;
+	return rc;
 }
 
 /* params.c:214-298: positional "--flag value" pairs; unknown flags only warn */
@@ -197,6 +290,9 @@ static int parse(int argc, char** argv, cli* c) {
 		else if (!strcmp(a, "--diversity-depth")) c->div_depth_s = v;
 		else if (!strcmp(a, "--diversity-boot")) c->div_boot_s = v;
 		else if (!strcmp(a, "--diversity-seed")) c->div_seed_s = v;
+		else if (!strcmp(a, "--selection")) c->selection = v;
+		else if (!strcmp(a, "--v-regions")) c->v_regions = v;
+		else if (!strcmp(a, "--targeting")) c->targeting = v;
 		else if (!strcmp(a, "--vf")) snprintf(c->v_anchors, sizeof c->v_anchors, "%s", v);
 		else if (!strcmp(a, "--jf")) snprintf(c->j_anchors, sizeof c->j_anchors, "%s", v);
 		else if (!strcmp(a, "--am")) c->anchor_mismatches = atoi(v);
@@ -303,6 +399,10 @@ static int parse(int argc, char** argv, cli* c) {
 		fprintf(stderr, "--diversity-seed must be a whole decimal number below 2^64: %s\n", c->div_seed_s);
 		ok = 0;
 	}
+	if (c->v_regions && !c->selection) { fprintf(stderr, "--v-regions is the region map of the --selection table: it needs --selection <file>\n"); ok = 0; }
+	if (c->targeting && !c->selection) { fprintf(stderr, "--targeting is the targeting model of the --selection table: it needs --selection <file>\n"); ok = 0; }
+	if (c->v_regions && c->selection && read_v_regions(c->v_regions, &c->regs, &c->nregs)) ok = 0;
+	if (c->targeting && c->selection && read_targeting(c->targeting, &c->weight)) ok = 0;
 	if (!ok) { usage(); return -1; }
 	if (c->hp.min_base_quality >= 255) c->hp.min_base_quality = 254;      /* A2:1514-1516 */
 	return 0;
@@ -664,6 +764,9 @@ typedef struct {
 	/* --diversity: the Hill curve of the lineages (diversity_run, after lineage_run) */
 	const char* diversity; uint32_t dv_depth, dv_boot; uint64_t dv_seed;
 	vdjx_diversity_info dvi; uint64_t dv_weight; double dv_d0, dv_d1, dv_d2;
+	/* --selection: the selection strength of the V mutations (sel_run, after lineage_run) */
+	const char* selection; const struct vreg_line* regs; size_t nregs; const uint32_t* weight; int have_regs, sel_done;
+	vdjx_sel_info si; double sel_sigma[2]; size_t sel_unmatched;
 } hook_ud;
 
 static int h_root_score(void* ud, const char* kmers, size_t n, int k, int thr, uint8_t* out) {
@@ -861,7 +964,7 @@ static long junction_at(const char* id, const char* s, int len, const char** jn_
 /* the V / J hits of every contig (vdjx_annotate against the germlines of ig_vdj.fa / --vdjf), kept for the tables */
 static int annot_run(hook_ud* u, const char* contigs, size_t n, int len) {
 	u->germ = (germ_set*) calloc(1, sizeof(germ_set));
-	if (germ_read(u->vdjf, u->germ, u->airr ? "--airr: cannot read the germline FASTA" : u->clones ? "--clones: cannot read the germline FASTA" : u->lineages ? "--lineages: cannot read the germline FASTA" : "--mutations: cannot read the germline FASTA")) return -1;
+	if (germ_read(u->vdjf, u->germ, u->airr ? "--airr: cannot read the germline FASTA" : u->clones ? "--clones: cannot read the germline FASTA" : u->lineages ? "--lineages: cannot read the germline FASTA" : u->mutations ? "--mutations: cannot read the germline FASTA" : "--selection: cannot read the germline FASTA")) return -1;
 	const germ_set* g = u->germ;
 	for (size_t r = 0; r < g->n; r++) {
 		if (g->cls[r] == 'V' || g->cls[r] == 'J') continue;
@@ -872,7 +975,7 @@ static int annot_run(hook_ud* u, const char* contigs, size_t n, int len) {
 	const vdjx_annot_params ap = {2, 3, 5, 2, 40, 20};
 	int rc = vdjx_germline_load(u->gx, g->seqs, g->off, g->cls, g->n);
 	if (!rc && n) rc = vdjx_annotate(u->gx, contigs, n, len, &ap, u->hv, u->hj);
-	if (rc) fprintf(stderr, "%s: %s\n", u->airr ? "--airr" : u->clones ? "--clones" : u->lineages ? "--lineages" : "--mutations", vdjx_last_error());
+	if (rc) fprintf(stderr, "%s: %s\n", u->airr ? "--airr" : u->clones ? "--clones" : u->lineages ? "--lineages" : u->mutations ? "--mutations" : "--selection", vdjx_last_error());
 	return rc;
 }
 
@@ -1302,21 +1405,26 @@ static int tree_run(hook_ud* u, const char* const* ids, const char* contigs, siz
 /* --mutations: the germline rows and the V mutation counts of every contig (the model: include/vdjx.h, vdjx_mutations; the limit:
  * mutation_limit of vdjer_amd/annot.py).  V mutations are counted below the junction's start + 3, through the conserved Cys codon: what
  * follows is the CDR3.  The D hits of --d-calls are laid into the gap; the rows are kept for the --airr table. */
-static int mut_run(hook_ud* u, const char* const* ids, const char* contigs, size_t n, int len) {
-	FILE* fp = fopen(u->mutations, "w");
-	if (!fp) { fprintf(stderr, "cannot write %s\n", u->mutations); return -1; }
-	const germ_set g = *u->germ;
-	const vdjx_annot_hit* hd = u->d_calls ? u->hd : NULL;
-	u->mu_off = (uint64_t*) calloc(n + 1, sizeof(uint64_t));
+static int32_t* mutation_limits(const char* const* ids, const char* contigs, size_t n, int len) {
 	int32_t* lim = (int32_t*) calloc(n + 1, sizeof(int32_t));
-	vdjx_mut_row* rows = (vdjx_mut_row*) calloc(n + 1, sizeof(vdjx_mut_row));
-	char* mask = NULL;
 	for (size_t i = 0; i < n; i++) {
 		const char* jn;
 		size_t jl;
 		const long p = junction_at(ids[i], contigs + i * (size_t) len, len, &jn, &jl);
 		lim[i] = p >= 0 && p + 3 < len ? (int32_t) p + 3 : len;
 	}
+	return lim;
+}
+
+static int mut_run(hook_ud* u, const char* const* ids, const char* contigs, size_t n, int len) {
+	FILE* fp = fopen(u->mutations, "w");
+	if (!fp) { fprintf(stderr, "cannot write %s\n", u->mutations); return -1; }
+	const germ_set g = *u->germ;
+	const vdjx_annot_hit* hd = u->d_calls ? u->hd : NULL;
+	u->mu_off = (uint64_t*) calloc(n + 1, sizeof(uint64_t));
+	int32_t* lim = mutation_limits(ids, contigs, n, len);
+	vdjx_mut_row* rows = (vdjx_mut_row*) calloc(n + 1, sizeof(vdjx_mut_row));
+	char* mask = NULL;
 	int rc = n ? vdjx_mutations_layout(u->hv, hd, u->hj, n, u->mu_off) : 0;
 	if (!rc) {
 		const size_t total = (size_t) u->mu_off[n];
@@ -1353,6 +1461,70 @@ static int mut_run(hook_ud* u, const char* const* ids, const char* contigs, size
 	free(mask);
 	if (fclose(fp) && !rc) { fprintf(stderr, "cannot write %s\n", u->mutations); return -1; }
 	if (!rc) u->mut_done = 1;
+	return rc;
+}
+
+/* --selection: the selection strength of the V segment's mutations (the model: include/vdjx.h, vdjx_selection), in the long format of
+ * shazam's summarizeBaseline: a row per contig, per lineage of --lineages and for the sample, times the regions (v; fwr and cdr with
+ * --v-regions).  The limit is --mutations'.  A V record without a --v-regions line has no regions: its contigs take no part. */
+static void sel_rows(FILE* fp, const char* level, const char* id, const vdjx_sel_stat* st, uint32_t K) {
+	for (uint32_t k = 0; k < K; k++) {
+		const vdjx_sel_stat* s = st + k;
+		const double sg = s->sigma > -0.00005 && s->sigma < 0.0 ? 0.0 : s->sigma;      /* (no "-0.0000") */
+		fprintf(fp, "%s\t%s\t%s\t%u\t%llu\t%llu\t%llu\t%llu\t%.4f\t%.2f\t%.2f\t%.4f\n", level, id, K == 1 ? "v" : k ? "cdr" : "fwr", s->sequences,
+		        (unsigned long long) s->x, (unsigned long long) (s->n - s->x), (unsigned long long) s->exp_r, (unsigned long long) s->exp_s, sg, s->lower, s->upper,
+		        s->p_positive);
+	}
+}
+
+static int sel_run(hook_ud* u, const char* const* ids, const char* contigs, size_t n, int len) {
+	FILE* fp = fopen(u->selection, "w");
+	if (!fp) { fprintf(stderr, "cannot write %s\n", u->selection); return -1; }
+	fputs("level\tid\tregion\tsequences\tobs_r\tobs_s\texp_r\texp_s\tsigma\tsigma_lower\tsigma_upper\tp_positive\n", fp);
+	const uint32_t K = u->have_regs ? 2 : 1, G = u->lineages && n ? u->li.clones : 0;
+	int rc = 0;
+	if (n) {
+		const germ_set* g = u->germ;
+		int32_t* cdr = NULL;
+		if (u->have_regs) {
+			cdr = (int32_t*) malloc((g->n * 4 + 1) * sizeof(int32_t));
+			for (size_t k = 0; k < g->n * 4; k++) cdr[k] = -1;
+			const char* first = NULL;
+			for (size_t q = 0; q < u->nregs; q++) {
+				int hit = 0;
+				for (size_t r = 0; r < g->n; r++)
+					if (!strcmp(g->names[r], u->regs[q].name)) { memcpy(cdr + 4 * r, u->regs[q].iv, sizeof u->regs[q].iv); hit = 1; }
+				if (!hit && !u->sel_unmatched++) first = u->regs[q].name;
+			}
+			if (u->sel_unmatched) fprintf(stderr, "--v-regions: %zu names match no germline record (the first: %s)\n", u->sel_unmatched, first);
+		}
+		int32_t* lim = mutation_limits(ids, contigs, n, len);
+		vdjx_sel_counts* cnt = (vdjx_sel_counts*) calloc(n + 1, sizeof(vdjx_sel_counts));
+		vdjx_sel_stat* st = (vdjx_sel_stat*) calloc((n + G + 1) * (size_t) K, sizeof(vdjx_sel_stat));
+		rc = vdjx_selection(u->gx, contigs, n, len, u->hv, lim, cdr, g->n, u->weight, G ? u->lin_clone : NULL, G, cnt, st, NULL, &u->si);
+		if (rc) fprintf(stderr, "--selection: %s\n", vdjx_last_error());
+		if (!rc) {
+			for (size_t i = 0; i < n; i++) {
+				if (cnt[i].flags & 1) sel_rows(fp, "sequence", ids[i], st + i * K, K);
+				else fprintf(fp, "sequence\t%s\t\t\t\t\t\t\t\t\t\t\n", ids[i]);
+			}
+			for (uint32_t k = 0; k < G; k++) {
+				char id[32];
+				snprintf(id, sizeof id, "lin_%u", k + 1);
+				sel_rows(fp, "lineage", id, st + (n + k) * (size_t) K, K);
+			}
+			sel_rows(fp, "sample", u->sample, st + (n + G) * (size_t) K, K);
+			for (uint32_t k = 0; k < K; k++) {
+				const double sg = st[(n + G) * (size_t) K + k].sigma;
+				u->sel_sigma[k] = sg > -0.00005 && sg < 0.0 ? 0.0 : sg;
+			}
+		}
+		free(cdr); free(lim); free(cnt); free(st);
+	}
+	u->si.groups = G;
+	u->si.regions = K;
+	if (fclose(fp) && !rc) { fprintf(stderr, "cannot write %s\n", u->selection); return -1; }
+	if (!rc) u->sel_done = 1;
 	return rc;
 }
 
@@ -1414,12 +1586,13 @@ static int diversity_run(hook_ud* u, size_t n) {
 static int tables(hook_ud* u, const char* const* ids, const char* contigs, size_t n, int len) {
 	int rc = 0;
 	if (!rc && (u->quant || u->clones)) rc = quant_table(u, ids, contigs, n, len);
-	if (!rc && (u->airr || u->clones || u->lineages || u->mutations)) rc = annot_run(u, contigs, n, len);
+	if (!rc && (u->airr || u->clones || u->lineages || u->mutations || u->selection)) rc = annot_run(u, contigs, n, len);
 	if (!rc && u->d_calls) rc = dcall_run(u, contigs, n, len);
 	if (!rc && u->lineages) rc = lineage_run(u, ids, contigs, n, len);
 	if (!rc && u->trees) rc = tree_run(u, ids, contigs, n, len);
 	if (!rc && u->diversity) rc = diversity_run(u, n);
 	if (!rc && u->mutations) rc = mut_run(u, ids, contigs, n, len);
+	if (!rc && u->selection) rc = sel_run(u, ids, contigs, n, len);
 	if (!rc && u->airr) rc = airr_table(u, ids, contigs, n, len);
 	if (!rc && u->cfa && (u->isotypes || u->clones)) rc = iso_run(u, contigs, n, len);
 	if (!rc && u->isotypes) rc = isotypes_table(u, ids, n, len);
@@ -1700,6 +1873,7 @@ int main(int argc, char** argv) {
 	ud.lineages = c.lineages; ud.lin_num = c.lin_num; ud.lin_den = c.lin_den; ud.trees = c.trees;
 	ud.ts_b = c.ts_b; ud.ts_seed = c.ts_seed; ud.mutations = c.mutations;
 	ud.diversity = c.diversity; ud.dv_depth = c.div_depth; ud.dv_boot = c.div_boot; ud.dv_seed = c.div_seed;
+	ud.selection = c.selection; ud.regs = c.regs; ud.nregs = c.nregs; ud.weight = c.weight; ud.have_regs = c.v_regions != NULL;
 	char sample_buf[4096];
 	if (c.sample) ud.sample = c.sample;
 	else {                                  /* the input's base name up to its first '.' */
@@ -1715,7 +1889,7 @@ int main(int argc, char** argv) {
 		return 1;
 	}
 	/* (no contig: the headers alone) */
-	if (!ud.quant_done && !ud.airr_done && !ud.iso_done && !ud.clones_done && !ud.lin_done && !ud.mut_done && tables(&ud, NULL, NULL, 0, 0)) return 1;
+	if (!ud.quant_done && !ud.airr_done && !ud.iso_done && !ud.clones_done && !ud.lin_done && !ud.mut_done && !ud.sel_done && tables(&ud, NULL, NULL, 0, 0)) return 1;
 	fprintf(stderr, "num root nodes: %zu\nProcessed roots: %zu\ncontig_candidates: %zu\nwindows scored: %zu valid: %zu\ncontigs: %zu\n",
 	        st.n_roots, st.n_roots_accepted, st.n_contig_candidates, st.n_windows_scored, st.n_windows_valid, st.n_contigs_out);
 	if (mg) {
@@ -1778,6 +1952,12 @@ int main(int argc, char** argv) {
 		fprintf(stderr, "diversity: %u lineages with weight of %u, %llu.%02llu expected pairs, depth %u, %u replicates (seed %llu), richness %.2f, shannon %.4f, simpson %.4f, %u batches\n",
 		        ud.dvi.clones, ud.li.clones, (unsigned long long) (ud.dv_weight / 100), (unsigned long long) (ud.dv_weight % 100), ud.dv_depth, c.div_boot,
 		        (unsigned long long) c.div_seed, ud.dv_d0, ud.dv_d1, ud.dv_d2, ud.dvi.batches);
+	if (c.selection) {
+		fprintf(stderr, "selection: %llu contigs, %llu used, %llu without regions, %u lineages, %u regions, targeting %s, sample sigma %.4f", (unsigned long long) ud.si.contigs,
+		        (unsigned long long) ud.si.used, (unsigned long long) ud.si.no_regions, ud.si.groups, ud.si.regions, c.targeting ? c.targeting : "uniform", ud.sel_sigma[0]);
+		if (ud.si.regions == 2) fprintf(stderr, " %.4f", ud.sel_sigma[1]);
+		fprintf(stderr, ", %u chunks\n", ud.si.chunks);
+	}
 	fflush(stdout);
 	fflush(stderr);
 	/* the outputs are written; the orderly teardown of a context that holds gigabytes (unmapping the workspaces piece by piece, the

@@ -289,6 +289,7 @@ __global__ __launch_bounds__(64) void k_an_trace(const char* __restrict__ contig
 static int an_set_load(vdjx_ctx* c, vdjx_recset& s, int ncls, const char* seqs, const uint64_t* off, const int8_t* cls, size_t n) {
 	s.loaded = false;
 	s.ncls = ncls;
+	s.given = n;
 	std::vector<uint8_t> h;
 	for (int k = 0; k < ncls; k++) {
 		s.rec[k].clear();

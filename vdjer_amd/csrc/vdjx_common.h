@@ -159,6 +159,7 @@ struct vdjx_recset {
 	std::vector<u32> rec[2];          // per class: the record index of every record of the class, ascending
 	std::vector<u64> at[2];           // its reset column in d_cols (its bases follow); one more entry: the class's last reset column
 	std::vector<u32> len[2];
+	size_t given = 0;                 // the records the load was given, those of no class included (vdjx_selection's region map has a row for each)
 };
 
 struct vdjx_ctx {

@@ -1,0 +1,579 @@
+// vdjx_select.hip -- selection strength of the V segment's mutations, BASELINe's focused test (gfx950 only, wave64).
+//
+//   vdjx_selection   observed R / S counts per region, the expected R / S weights of the germline's codons under a 5-mer targeting model,
+//                    and the posterior of the selection strength sigma per contig, per group and for all contigs (the model:
+//                    include/vdjx.h; in Python: tests/selection_model.py)
+//
+// The hits are the caller's, so the host checks every one of them before anything reaches the device, as vdjx_mutations does (sel_check):
+// every index k_sel_counts forms lies inside the contig and the record.
+//   k_sel_counts   one dispatch; a wave per contig, SEL_WAVES waves per workgroup, no barrier between the waves.  The V segment table of
+//                  k_mutations (its V part: 64 slots) in LDS, a lane per germline codon.  Per base of a classifiable codon: the region of
+//                  its germline position, the observed class, and -- the germline codon not being a stop -- the three other bases through
+//                  the amino-acid table, weighted by the 5-mer around the base in the RECORD (germline.d_cols; the record's bounds are
+//                  checked, its neighbours in the set are never read as context).  The 1024 x 4 weights stay in global memory: a position
+//                  reads the 16 bytes of its 5-mer with one load, a contig of 100 codons reads 4.8 KB of a 16 KB table that every wave
+//                  shares, so it lives in L2 and the vector cache; staging it in LDS would cost every workgroup of four contigs the whole
+//                  16 KB and a barrier.  int32 and uint64 wave reductions by shuffles; lane 0 writes the 64-byte row as four 16-byte
+//                  stores.  No floating point, no atomics.
+//   k_sel_loglik   rows with more than `chunk` members: a workgroup per (row, region, chunk of members) and tile of 256 grid points; a
+//                  thread sums its grid point's terms over the chunk's members in order and writes partial[chunk][t].
+//   k_sel_finish   a workgroup per (row, region): l[T] in LDS (32 KB), from its members directly or from the row's partials in chunk
+//                  order, plus the prior; the block maximum, f = exp(l - max), a block scan for the CDF (a thread owns 16 consecutive grid
+//                  points), the two quantile indices, sigma and p_positive; one 72-byte stat and, where asked, the density.
+// No float atomics; every sum runs in a fixed order, so two calls with the same VDJX_SEL_CHUNK give the same bits.
+#include "vdjx_common.h"
+
+#include <algorithm>
+#include <math.h>
+#include <string.h>
+
+#define SEL_WAVES 4
+#define SEL_T VDJX_SEL_GRID
+#define SEL_PER 16                       // grid points a thread of k_sel_finish owns: 256 * 16 >= 4001
+
+struct SelContig {
+	u32 run_off;                         // V's runs in the pool
+	u32 v_at;                            // the column of the hit's base germ_start in the set's columns
+	u32 rec_at;                          // the column of the record's base 1
+	u32 rec_len;
+	u32 nruns;
+	u32 flags;
+	int v_seq0;                          // seq_start - 1
+	int v_germ0;                         // germ_start - 1
+	int limit;
+	int cdr[4];                          // 1-based, inclusive; 0, 0: no such interval (all four 0 without a region map)
+	int pad[3];
+};
+struct SelMember { u32 x, n; double lo; };            // a contig in a region: x of n, ln exp_r - ln sum exp_s; n = 0: adds nothing
+struct SelRow {                          // a row in a region
+	u32 start, count;                    // its members in the region's member array
+	u32 sequences;
+	u32 part;                            // its first chunk of partials; SEL_DIRECT: summed from the members
+	u32 nparts, pdf;                     // pdf: the density's row + 1, 0: none
+	u64 x, n, exp_r, exp_s;
+};
+struct SelItem { u32 start, count, part, region; };    // a chunk of a large row's members
+#define SEL_DIRECT 0xFFFFFFFFu
+static_assert(sizeof(SelContig) == 64 && sizeof(vdjx_sel_counts) == 64 && sizeof(vdjx_sel_stat) == 72 && sizeof(SelMember) == 16 && sizeof(SelRow) == 56,
+              "uploaded / returned as they are");
+
+// the standard genetic code, codon 16 a + 4 b + c with A 0, C 1, G 2, T 3
+__constant__ char sel_aa[65] = "KNKNTTTTRSRSIIMIQHQHPPPPRRRRLLLLEDEDAAAAGGGGVVVV*Y*YSSSS*CWCLFLF";
+
+__device__ __forceinline__ int sel_ccode(char ch) { return ch == 'A' ? 0 : ch == 'C' ? 1 : ch == 'G' ? 2 : ch == 'T' ? 3 : 4; }
+
+__device__ __forceinline__ int sel_excl(int v, u32 lane, int& total) {      // exclusive prefix sum over the wave
+	int s = v;
+#pragma unroll
+	for (int o = 1; o < 64; o <<= 1) {
+		const int t = __shfl_up(s, o, 64);
+		if ((int) lane >= o) s += t;
+	}
+	total = __shfl(s, 63, 64);
+	return s - v;
+}
+
+__device__ __forceinline__ int sel_sum(int v) {
+#pragma unroll
+	for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+	return v;
+}
+
+__device__ __forceinline__ u64 sel_sum64(u64 v) {
+#pragma unroll
+	for (int o = 32; o >= 1; o >>= 1) {
+		const u32 lo = (u32) __shfl_xor((int) (u32) v, o, 64), hi = (u32) __shfl_xor((int) (u32) (v >> 32), o, 64);
+		v += (u64) hi << 32 | lo;
+	}
+	return v;
+}
+
+__global__ __launch_bounds__(64 * SEL_WAVES) void k_sel_counts(const char* __restrict__ contigs, u32 n, u32 len, const SelContig* __restrict__ sc,
+                                                              const u32* __restrict__ runs, const uint8_t* __restrict__ gcols,
+                                                              const uint4* __restrict__ weight, int4* __restrict__ out) {
+	__shared__ int4 seg_all[SEL_WAVES][65];
+	__shared__ char aa_all[SEL_WAVES][64];
+	const u32 w = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+	const u32 c = blockIdx.x * SEL_WAVES + w;
+	if (c >= n) return;                  // (a whole wave; nothing below waits for the others)
+	int4* seg = seg_all[w];
+	char* aa = aa_all[w];
+	aa[lane] = sel_aa[lane];
+	const SelContig q = sc[c];
+	const char* ct = contigs + (size_t) c * len;
+	const int nr = (int) q.nruns;
+	// the V segment table: {first column, first contig index, first germline column, op}; a slot without a run is empty at the end
+	const bool live = (int) lane < nr;
+	const u32 r = live ? runs[q.run_off + lane] : 0u;
+	const int L = (int) (r >> 4), op = (int) (r & 15u);
+	int tc, tb, tg;
+	const int ec = sel_excl(L, lane, tc), eb = sel_excl(op != 2 ? L : 0, lane, tb), eg = sel_excl(op != 1 ? L : 0, lane, tg);
+	seg[lane] = live ? make_int4(ec, q.v_seq0 + eb, (int) q.v_at + eg, op) : make_int4(tc, q.v_seq0 + tb, (int) q.v_at + tg, 0);
+	const int vgerm = tg;
+	vdjx_wave_lds_fence();               // the table and the amino acids are read by other lanes of the wave
+
+	int obs_r[2] = {0, 0}, obs_s[2] = {0, 0}, ncod[2] = {0, 0};
+	u64 exp_r[2] = {0, 0}, exp_s[2] = {0, 0};
+	const int c_lo = (q.v_germ0 + 2) / 3, c_hi = (q.v_germ0 + vgerm) / 3;       // codons c_lo .. c_hi - 1, as k_mutations takes them
+	const int rlen = (int) q.rec_len;
+	for (int cd = c_lo + (int) lane; cd < c_hi; cd += 64) {
+		int colb[3], cb[3], gb[3];
+		bool ok = true;
+#pragma unroll
+		for (int b = 0; b < 3; b++) {
+			const int ga = (int) q.v_at + 3 * cd + b - q.v_germ0;      // the base's column in the germline set
+			int lo = 0, hi = 64;             // the last slot whose first germline column is <= ga (an I run shares the next run's)
+			while (hi - lo > 1) {
+				const int mid = (lo + hi) >> 1;
+				if (seg[mid].z <= ga) lo = mid; else hi = mid;
+			}
+			const int4 s = seg[lo];
+			const int off = ga - s.z;
+			ok = ok && (s.w & 3) == 0;
+			colb[b] = s.x + off;
+			const int pos = s.y + off;
+			ok = ok && pos < q.limit;
+			cb[b] = ok ? sel_ccode(ct[pos]) : 4;      // (pos is inside the contig whenever the slot is an M run)
+			gb[b] = gcols[ga];
+			ok = ok && cb[b] < 4 && gb[b] < 4;
+		}
+		ok = ok && colb[1] == colb[0] + 1 && colb[2] == colb[1] + 1;
+		if (!ok) continue;
+		const int gc = 16 * gb[0] + 4 * gb[1] + gb[2];
+		const char ga_ = aa[gc];
+#pragma unroll
+		for (int b = 0; b < 3; b++) {
+			const int p = 3 * cd + b;            // the base's 0-based position in the record
+			const int p1 = p + 1;
+			const int reg = (p1 >= q.cdr[0] && p1 <= q.cdr[1]) || (p1 >= q.cdr[2] && p1 <= q.cdr[3]) ? 1 : 0;
+			if (b == 0) ncod[reg]++;             // a codon belongs to the region of its first base
+			const int sh = 4 - 2 * b;
+			if (cb[b] != gb[b]) {
+				const char ma = aa[(gc & ~(3 << sh)) | (cb[b] << sh)];
+				if (ga_ != '*' && ma != '*') {
+					if (ga_ == ma) obs_s[reg]++; else obs_r[reg]++;
+				}
+			}
+			if (ga_ == '*') continue;
+			u32 wt[4] = {1u, 1u, 1u, 1u};
+			if (weight) {
+				if (p < 2 || p + 2 >= rlen) continue;
+				const uint8_t* g5 = gcols + q.rec_at + (u32) (p - 2);
+				const int g0 = g5[0], g1 = g5[1], g3 = g5[3], g4 = g5[4];
+				if (g0 > 3 || g1 > 3 || g3 > 3 || g4 > 3) continue;      // (the centre is the codon's base: ACGT)
+				const uint4 wv = weight[256 * g0 + 64 * g1 + 16 * gb[b] + 4 * g3 + g4];
+				wt[0] = wv.x; wt[1] = wv.y; wt[2] = wv.z; wt[3] = wv.w;
+			}
+#pragma unroll
+			for (int alt = 0; alt < 4; alt++) {
+				if (alt == gb[b]) continue;
+				const char ma = aa[(gc & ~(3 << sh)) | (alt << sh)];
+				if (ma == '*') continue;
+				if (ma == ga_) exp_s[reg] += wt[alt]; else exp_r[reg] += wt[alt];
+			}
+		}
+	}
+#pragma unroll
+	for (int k = 0; k < 2; k++) {
+		obs_r[k] = sel_sum(obs_r[k]);
+		obs_s[k] = sel_sum(obs_s[k]);
+		ncod[k] = sel_sum(ncod[k]);
+		exp_r[k] = sel_sum64(exp_r[k]);
+		exp_s[k] = sel_sum64(exp_s[k]);
+	}
+	if (lane == 0) {
+		int4* o = out + 4 * (size_t) c;
+		o[0] = make_int4(obs_r[0], obs_r[1], obs_s[0], obs_s[1]);
+		o[1] = make_int4(ncod[0], ncod[1], (int) q.flags, 0);
+		o[2] = make_int4((int) (u32) exp_r[0], (int) (u32) (exp_r[0] >> 32), (int) (u32) exp_r[1], (int) (u32) (exp_r[1] >> 32));
+		o[3] = make_int4((int) (u32) exp_s[0], (int) (u32) (exp_s[0] >> 32), (int) (u32) exp_s[1], (int) (u32) (exp_s[1] >> 32));
+	}
+}
+
+// ---- the posterior -------------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double sel_softplus(double z) { return fmax(z, 0.0) + log1p(exp(-fabs(z))); }
+__device__ __forceinline__ double sel_sigma(int t) { return (double) (t - 2000) / 100.0; }
+
+// the members' terms at one grid point, in member order, from 0
+__device__ __forceinline__ double sel_terms(const SelMember* __restrict__ m, u32 count, double sg) {
+	double acc = 0.0;
+	for (u32 k = 0; k < count; k++) {
+		const SelMember e = m[k];            // (uniform across the workgroup)
+		if (e.n == 0) continue;
+		const double z = sg + e.lo;
+		acc += (double) e.x * z - (double) e.n * sel_softplus(z);
+	}
+	return acc;
+}
+
+__global__ __launch_bounds__(256) void k_sel_loglik(const SelMember* __restrict__ members, size_t region_stride, const SelItem* __restrict__ items,
+                                                    double* __restrict__ partial) {
+	const SelItem it = items[blockIdx.y];
+	const int t = (int) (blockIdx.x * 256 + threadIdx.x);
+	if (t >= SEL_T) return;              // (the last tile: 161 of 256)
+	partial[(size_t) it.part * SEL_T + (size_t) t] = sel_terms(members + (size_t) it.region * region_stride + it.start, it.count, sel_sigma(t));
+}
+
+__device__ __forceinline__ double sel_shfl_xor(double v, int o) {
+	const long long b = __double_as_longlong(v);
+	const u32 lo = (u32) __shfl_xor((int) (u32) b, o, 64), hi = (u32) __shfl_xor((int) (u32) ((u64) b >> 32), o, 64);
+	return __longlong_as_double((long long) ((u64) hi << 32 | lo));
+}
+
+// the block's sum / maximum of one value per thread, in a fixed order: inside a wave by a butterfly, the four waves in order
+__device__ __forceinline__ double sel_block_sum(double v, double* red) {
+#pragma unroll
+	for (int o = 32; o >= 1; o >>= 1) v += sel_shfl_xor(v, o);
+	__syncthreads();
+	if ((threadIdx.x & 63u) == 0) red[threadIdx.x >> 6] = v;
+	__syncthreads();
+	return ((red[0] + red[1]) + red[2]) + red[3];
+}
+__device__ __forceinline__ double sel_block_max(double v, double* red) {
+#pragma unroll
+	for (int o = 32; o >= 1; o >>= 1) v = fmax(v, sel_shfl_xor(v, o));
+	__syncthreads();
+	if ((threadIdx.x & 63u) == 0) red[threadIdx.x >> 6] = v;
+	__syncthreads();
+	return fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+}
+
+__global__ __launch_bounds__(256) void k_sel_finish(const SelMember* __restrict__ members, size_t region_stride, const SelRow* __restrict__ rows,
+                                                    u32 nrows, const double* __restrict__ partial, vdjx_sel_stat* __restrict__ out_stat,
+                                                    double* __restrict__ out_pdf, u32 K) {
+	__shared__ double ell[SEL_T];
+	__shared__ double tot[256];
+	__shared__ double red[4];
+	__shared__ int qidx[2][4];
+	const u32 row = blockIdx.x / K, region = blockIdx.x % K;
+	const u32 tid = threadIdx.x;
+	const SelRow rw = rows[(size_t) region * nrows + row];
+	const SelMember* m = members + (size_t) region * region_stride + rw.start;
+	// l[t], striped over the threads (t = tid + 256 j): uniform member reads, neighbouring partials
+	double mx = -INFINITY;
+	for (int t = (int) tid; t < SEL_T; t += 256) {
+		const double sg = sel_sigma(t);
+		double l = sg - 2.0 * sel_softplus(sg);
+		if (rw.part == SEL_DIRECT) l += sel_terms(m, rw.count, sg);
+		else {
+			double acc = 0.0;
+			for (u32 p = 0; p < rw.nparts; p++) acc += partial[(size_t) (rw.part + p) * SEL_T + (size_t) t];
+			l += acc;
+		}
+		ell[t] = l;
+		mx = fmax(mx, l);
+	}
+	mx = sel_block_max(mx, red);         // (its barriers publish ell)
+	// f over 16 consecutive grid points per thread
+	const int t0 = (int) tid * SEL_PER;
+	double f[SEL_PER];
+	double loc = 0.0, sw = 0.0, pos = 0.0;
+#pragma unroll
+	for (int j = 0; j < SEL_PER; j++) {
+		const int t = t0 + j;
+		f[j] = t < SEL_T ? exp(ell[t] - mx) : 0.0;
+		loc += f[j];
+		sw += sel_sigma(t) * f[j];
+		pos += t > 2000 ? f[j] : t == 2000 ? 0.5 * f[j] : 0.0;
+	}
+	// the exclusive scan of the threads' totals: the wave's by shuffles, the waves' in order
+	double inc = loc;
+#pragma unroll
+	for (int o = 1; o < 64; o <<= 1) {
+		const long long b = __double_as_longlong(inc);
+		const u32 lo = (u32) __shfl_up((int) (u32) b, o, 64), hi = (u32) __shfl_up((int) (u32) ((u64) b >> 32), o, 64);
+		const double up = __longlong_as_double((long long) ((u64) hi << 32 | lo));
+		if ((int) (tid & 63u) >= o) inc += up;
+	}
+	tot[tid] = inc;
+	__syncthreads();
+	const u32 wv = tid >> 6;
+	double base = 0.0;
+	for (u32 k = 0; k < wv; k++) base += tot[64 * k + 63];
+	const double S = ((tot[63] + tot[127]) + tot[191]) + tot[255];
+	double run = base + (inc - loc);
+	int first[2] = {SEL_T, SEL_T};
+#pragma unroll
+	for (int j = 0; j < SEL_PER; j++) {
+		run += f[j];
+		const double cdf = run / S;
+		const int t = t0 + j;
+		if (t < SEL_T) {
+			if (cdf >= 0.025 && first[0] == SEL_T) first[0] = t;
+			if (cdf >= 0.975 && first[1] == SEL_T) first[1] = t;
+		}
+	}
+#pragma unroll
+	for (int k = 0; k < 2; k++) {
+		int v = first[k];
+#pragma unroll
+		for (int o = 32; o >= 1; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+		if ((tid & 63u) == 0) qidx[k][wv] = v;
+	}
+	const double ssum = sel_block_sum(sw, red);      // (its barriers publish qidx)
+	const double psum = sel_block_sum(pos, red);
+	if (tid == 0) {
+		int qi[2];
+		for (int k = 0; k < 2; k++) qi[k] = min(min(min(qidx[k][0], qidx[k][1]), min(qidx[k][2], qidx[k][3])), SEL_T - 1);
+		vdjx_sel_stat s;
+		s.sequences = rw.sequences;
+		s.pad = 0;
+		s.x = rw.x; s.n = rw.n; s.exp_r = rw.exp_r; s.exp_s = rw.exp_s;
+		s.sigma = ssum / S;
+		s.lower = sel_sigma(qi[0]);
+		s.upper = sel_sigma(qi[1]);
+		s.p_positive = psum / S;
+		out_stat[(size_t) row * K + region] = s;
+	}
+	if (out_pdf && rw.pdf) {
+		double* o = out_pdf + ((size_t) (rw.pdf - 1) * K + region) * SEL_T;
+		const double den = 0.01 * S;
+		__syncthreads();                     // (rw is the workgroup's: all of it comes here)
+#pragma unroll
+		for (int j = 0; j < SEL_PER; j++)
+			if (t0 + j < SEL_T) ell[t0 + j] = f[j] / den;
+		__syncthreads();
+		for (int t = (int) tid; t < SEL_T; t += 256) o[t] = ell[t];      // (through LDS: neighbouring threads store neighbouring doubles)
+	}
+}
+
+// ---- the host's side -------------------------------------------------------------------------------------------------------------------------
+static inline bool sel_called(const vdjx_annot_hit& h) { return h.gene >= 0 && h.score > 0; }
+static inline bool sel_usable(const vdjx_annot_hit& h) { return sel_called(h) && h.n_runs <= VDJX_ANNOT_RUNS; }
+
+// a usable V hit of contig i against the loaded set, by vdjx_mutations' rules: *slot = its record's place among the V records
+static int sel_check(size_t i, const vdjx_annot_hit& h, const vdjx_recset& s, int len, size_t* slot_out) {
+	const std::vector<u32>& rec = s.rec[0];
+	const size_t slot = std::lower_bound(rec.begin(), rec.end(), (u32) h.gene) - rec.begin();
+	if (slot >= rec.size() || rec[slot] != (u32) h.gene) {
+		vdjx_set_error("vdjx_selection: contig %zu: the V hit's gene %d is not a V record of the loaded set", i, h.gene);
+		return VDJX_EINVAL;
+	}
+	int64_t ns = 0, ng = 0;
+	bool ok = h.n_runs >= 0;
+	for (int r = 0; ok && r < h.n_runs; r++) {
+		const u32 L = h.runs[r] >> 4, op = h.runs[r] & 15u;
+		if (op > 2 || L == 0) ok = false;
+		if (op != 2) ns += L;
+		if (op != 1) ng += L;
+	}
+	if (!ok) {
+		vdjx_set_error("vdjx_selection: contig %zu: the V hit has a run with an op outside 0..2 or a length of 0 (n_runs %d)", i, h.n_runs);
+		return VDJX_EINVAL;
+	}
+	if (h.seq_start < 1 || h.germ_start < 1 || h.seq_end > len || (int64_t) h.germ_end > (int64_t) s.len[0][slot]) {
+		vdjx_set_error("vdjx_selection: contig %zu: the V hit's contig positions %d .. %d (1 .. %d) or germline positions %d .. %d (1 .. %u)", i,
+		               h.seq_start, h.seq_end, len, h.germ_start, h.germ_end, s.len[0][slot]);
+		return VDJX_EINVAL;
+	}
+	if (ns != (int64_t) h.seq_end - h.seq_start + 1 || ng != (int64_t) h.germ_end - h.germ_start + 1) {
+		vdjx_set_error("vdjx_selection: contig %zu: the V hit's runs hold %lld contig and %lld germline bases, its positions %d .. %d and %d .. %d", i,
+		               (long long) ns, (long long) ng, h.seq_start, h.seq_end, h.germ_start, h.germ_end);
+		return VDJX_EINVAL;
+	}
+	if (s.at[0][slot] + (u64) s.len[0][slot] >= (1ull << 31)) {
+		vdjx_set_error("vdjx_selection: contig %zu: the V record lies past 2^31 columns of its set", i);
+		return VDJX_EINVAL;
+	}
+	*slot_out = slot;
+	return VDJX_OK;
+}
+
+extern "C" int vdjx_selection(vdjx_ctx* c, const char* contigs, size_t n, int len, const vdjx_annot_hit* v, const int32_t* limit, const int32_t* cdr,
+                              size_t n_records, const uint32_t* weight, const int32_t* group, uint32_t G, vdjx_sel_counts* out_counts,
+                              vdjx_sel_stat* out_stat, double* out_pdf, vdjx_sel_info* info) {
+	if (info) memset(info, 0, sizeof *info);
+	if (!c) { vdjx_set_error("vdjx_selection: NULL argument"); return VDJX_EINVAL; }
+	if (n == 0) return VDJX_OK;
+	if (!contigs || !v || !out_counts || !out_stat) { vdjx_set_error("vdjx_selection: NULL argument"); return VDJX_EINVAL; }
+	if (len < 1 || len >= 4096) { vdjx_set_error("vdjx_selection: len=%d (1 .. 4095)", len); return VDJX_EINVAL; }
+	if (n >= (1ull << 20)) { vdjx_set_error("vdjx_selection: %zu contigs (at most 2^20 - 1 per call)", n); return VDJX_EINVAL; }
+	if (G >= (1u << 20)) { vdjx_set_error("vdjx_selection: %u groups (at most 2^20 - 1)", G); return VDJX_EINVAL; }
+	if (G && !group) { vdjx_set_error("vdjx_selection: %u groups and no group array", G); return VDJX_EINVAL; }
+	if (out_pdf && (u64) G + 1 > 65536) { vdjx_set_error("vdjx_selection: densities of %u groups and the sample (at most 65536 rows)", G); return VDJX_EINVAL; }
+	if (memchr(contigs, 0, n * (size_t) len)) {
+		vdjx_set_error("vdjx_selection: contigs of unequal length (a NUL inside the %zu x %d characters)", n, len);
+		return VDJX_EINVAL;
+	}
+	if (!c->germline.loaded) { vdjx_set_error("vdjx_selection: no germline set is loaded (call vdjx_germline_load first)"); return VDJX_ESTATE; }
+	const vdjx_recset& gs = c->germline;
+	if (cdr) {
+		if (n_records != gs.given) {
+			vdjx_set_error("vdjx_selection: a region map of %zu records, %zu records were loaded", n_records, gs.given);
+			return VDJX_EINVAL;
+		}
+		for (size_t s = 0; s < gs.rec[0].size(); s++) {
+			const int32_t* iv = cdr + 4 * (size_t) gs.rec[0][s];
+			if (iv[0] == -1) continue;
+			for (int k = 0; k < 4; k += 2) {
+				if (iv[k] == 0 && iv[k + 1] == 0) continue;
+				if (iv[k] < 1 || iv[k] > iv[k + 1] || (int64_t) iv[k + 1] > (int64_t) gs.len[0][s]) {
+					vdjx_set_error("vdjx_selection: record %u: the interval %d .. %d (1 <= start <= end <= %u, or 0 0)", gs.rec[0][s], iv[k], iv[k + 1], gs.len[0][s]);
+					return VDJX_EINVAL;
+				}
+			}
+		}
+	}
+	const u32 K = cdr ? 2 : 1;
+	const long long chunk_ll = vdjx_env_num("VDJX_SEL_CHUNK", 1024, 1, 65536);
+	const u32 chunk = (u32) chunk_ll;
+	const auto t0 = std::chrono::steady_clock::now();
+	std::vector<SelContig> sc(n);
+	std::vector<u32> runs;
+	u64 truncated = 0, no_regions = 0;
+	for (size_t i = 0; i < n; i++) {
+		const int lim = limit ? limit[i] : len;
+		if (lim < 0 || lim > len) { vdjx_set_error("vdjx_selection: contig %zu: limit %d (0 .. %d)", i, lim, len); return VDJX_EINVAL; }
+		if (group && G && group[i] >= 0 && (u32) group[i] >= G) { vdjx_set_error("vdjx_selection: contig %zu: group %d of %u", i, group[i], G); return VDJX_EINVAL; }
+		SelContig& q = sc[i];
+		memset(&q, 0, sizeof q);
+		q.limit = lim;
+		q.run_off = (u32) runs.size();
+		if (sel_called(v[i]) && !sel_usable(v[i])) { q.flags = 16; truncated++; continue; }
+		if (!sel_usable(v[i])) continue;
+		size_t slot = 0;
+		const int rc = sel_check(i, v[i], gs, len, &slot);
+		if (rc != VDJX_OK) return rc;
+		if (cdr) {
+			const int32_t* iv = cdr + 4 * (size_t) v[i].gene;
+			if (iv[0] == -1) { q.flags = 32; no_regions++; continue; }
+			for (int k = 0; k < 4; k++) q.cdr[k] = iv[k];
+		}
+		q.flags = 1;
+		q.nruns = (u32) v[i].n_runs;
+		runs.insert(runs.end(), v[i].runs, v[i].runs + q.nruns);
+		q.rec_at = (u32) (gs.at[0][slot] + 1);
+		q.rec_len = gs.len[0][slot];
+		q.v_at = (u32) (gs.at[0][slot] + (u64) v[i].germ_start);
+		q.v_seq0 = v[i].seq_start - 1;
+		q.v_germ0 = v[i].germ_start - 1;
+	}
+
+	HIP_TRY(hipSetDevice(c->device));
+	hipStream_t st = c->stream;
+	vdjx_work wk(c);
+	char* d_ct;
+	SelContig* d_sc;
+	u32 *d_runs, *d_w = nullptr;
+	int4* d_out;
+	HIP_TRY(wk.alloc(&d_ct, n * (size_t) len));
+	HIP_TRY(wk.alloc(&d_sc, n));
+	HIP_TRY(wk.alloc(&d_runs, runs.size()));
+	HIP_TRY(wk.alloc(&d_out, 4 * n));
+	HIP_TRY(hipMemcpyAsync(d_ct, contigs, n * (size_t) len, hipMemcpyHostToDevice, st));
+	HIP_TRY(hipMemcpyAsync(d_sc, sc.data(), n * sizeof(SelContig), hipMemcpyHostToDevice, st));
+	if (!runs.empty()) HIP_TRY(hipMemcpyAsync(d_runs, runs.data(), runs.size() * sizeof(u32), hipMemcpyHostToDevice, st));
+	if (weight) {
+		HIP_TRY(wk.alloc(&d_w, 4096));
+		HIP_TRY(hipMemcpyAsync(d_w, weight, 4096 * sizeof(u32), hipMemcpyHostToDevice, st));
+	}
+	{
+		vdjx_prof_scope ps(c, "k_sel_counts");
+		hipLaunchKernelGGL(k_sel_counts, dim3((u32) ((n + SEL_WAVES - 1) / SEL_WAVES)), dim3(64 * SEL_WAVES), 0, st, (const char*) d_ct, (u32) n, (u32) len,
+		                   (const SelContig*) d_sc, (const u32*) d_runs, (const uint8_t*) c->germline.d_cols, (const uint4*) d_w, d_out);
+	}
+	HIP_TRY(hipMemcpyAsync(out_counts, d_out, n * sizeof(vdjx_sel_counts), hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipStreamSynchronize(st));
+	HIP_TRY(hipGetLastError());
+
+	// the members: per region the contigs in order, then the grouped contigs by group (contig order inside a group)
+	std::vector<u32> gstart(G + 1, 0), gorder;
+	if (G) {
+		for (size_t i = 0; i < n; i++)
+			if (group[i] >= 0) gstart[(u32) group[i] + 1]++;
+		for (u32 g = 0; g < G; g++) gstart[g + 1] += gstart[g];
+		gorder.resize(gstart[G]);
+		std::vector<u32> at(gstart.begin(), gstart.end() - 1);
+		for (size_t i = 0; i < n; i++)
+			if (group[i] >= 0) gorder[at[(u32) group[i]]++] = (u32) i;
+	}
+	const size_t ng = gorder.size(), stride = n + ng, nrows = n + G + 1;
+	std::vector<SelMember> mem(K * stride);
+	std::vector<SelRow> rows(K * nrows);
+	std::vector<SelItem> items;
+	u32 nparts = 0, large_rows = 0;
+	u64 used = 0;
+	for (size_t i = 0; i < n; i++) used += (out_counts[i].flags & 1u) != 0;
+	for (u32 k = 0; k < K; k++) {
+		SelMember* m = mem.data() + k * stride;
+		for (size_t i = 0; i < n; i++) {
+			const vdjx_sel_counts& r = out_counts[i];
+			u64 ss = 0, es = 0;
+			for (u32 j = 0; j < K; j++) { ss += (u64) r.obs_s[j]; es += r.exp_s[j]; }
+			const u64 x = (u64) r.obs_r[k], nn = x + ss;
+			SelMember e = {0u, 0u, 0.0};
+			if (nn > 0 && r.exp_r[k] > 0 && es > 0) { e.x = (u32) x; e.n = (u32) nn; e.lo = log((double) r.exp_r[k]) - log((double) es); }
+			m[i] = e;
+		}
+		for (size_t a = 0; a < ng; a++) m[n + a] = m[gorder[a]];
+		SelRow* rw = rows.data() + k * nrows;
+		for (size_t r = 0; r < nrows; r++) {
+			SelRow& R = rw[r];
+			memset(&R, 0, sizeof R);
+			if (r < n) { R.start = (u32) r; R.count = 1; }
+			else if (r < n + G) { R.start = (u32) (n + gstart[r - n]); R.count = gstart[r - n + 1] - gstart[r - n]; R.pdf = out_pdf ? (u32) (r - n) + 1 : 0; }
+			else { R.start = 0; R.count = (u32) n; R.pdf = out_pdf ? G + 1 : 0; }
+			for (u32 a = 0; a < R.count; a++) {
+				const SelMember& e = m[R.start + a];
+				if (!e.n) continue;
+				const size_t i = R.start + a < n ? R.start + a : gorder[R.start + a - n];
+				u64 es = 0;
+				for (u32 j = 0; j < K; j++) es += out_counts[i].exp_s[j];
+				R.sequences++;
+				R.x += e.x; R.n += e.n; R.exp_r += out_counts[i].exp_r[k]; R.exp_s += es;
+			}
+			R.part = SEL_DIRECT;
+			if (R.count > chunk) {
+				R.part = nparts;
+				R.nparts = (R.count + chunk - 1) / chunk;
+				for (u32 p = 0; p < R.nparts; p++) items.push_back({R.start + p * chunk, std::min(chunk, R.count - p * chunk), nparts + p, k});
+				nparts += R.nparts;
+				large_rows += k == 0;
+			}
+		}
+	}
+	SelMember* d_mem;
+	SelRow* d_rows;
+	SelItem* d_items;
+	double *d_partial, *d_pdf = nullptr;
+	vdjx_sel_stat* d_stat;
+	HIP_TRY(wk.alloc(&d_mem, mem.size()));
+	HIP_TRY(wk.alloc(&d_rows, rows.size()));
+	HIP_TRY(wk.alloc(&d_items, items.size()));
+	HIP_TRY(wk.alloc(&d_partial, (size_t) nparts * SEL_T));
+	HIP_TRY(wk.alloc(&d_stat, nrows * K));
+	if (out_pdf) HIP_TRY(wk.alloc(&d_pdf, (size_t) (G + 1) * K * SEL_T));
+	HIP_TRY(hipMemcpyAsync(d_mem, mem.data(), mem.size() * sizeof(SelMember), hipMemcpyHostToDevice, st));
+	HIP_TRY(hipMemcpyAsync(d_rows, rows.data(), rows.size() * sizeof(SelRow), hipMemcpyHostToDevice, st));
+	if (!items.empty()) {
+		HIP_TRY(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(SelItem), hipMemcpyHostToDevice, st));
+		for (size_t a = 0; a < items.size(); a += 65535) {       // (a launch's second grid dimension holds 65,535)
+			vdjx_prof_scope ps(c, "k_sel_loglik");
+			hipLaunchKernelGGL(k_sel_loglik, dim3((SEL_T + 255) / 256, (u32) std::min<size_t>(65535, items.size() - a)), dim3(256), 0, st,
+			                   (const SelMember*) d_mem, stride, (const SelItem*) d_items + a, d_partial);
+		}
+	}
+	{
+		vdjx_prof_scope ps(c, "k_sel_finish");
+		hipLaunchKernelGGL(k_sel_finish, dim3((u32) (nrows * K)), dim3(256), 0, st, (const SelMember*) d_mem, stride, (const SelRow*) d_rows, (u32) nrows,
+		                   (const double*) d_partial, d_stat, d_pdf, K);
+	}
+	HIP_TRY(hipMemcpyAsync(out_stat, d_stat, nrows * K * sizeof(vdjx_sel_stat), hipMemcpyDeviceToHost, st));
+	if (out_pdf) HIP_TRY(hipMemcpyAsync(out_pdf, d_pdf, (size_t) (G + 1) * K * SEL_T * sizeof(double), hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipStreamSynchronize(st));
+	HIP_TRY(hipGetLastError());
+	vdjx_prof_collect(c, false);
+	if (info) {
+		info->contigs = n;
+		info->used = used;
+		info->no_regions = no_regions;
+		info->truncated = truncated;
+		info->groups = G;
+		info->regions = K;
+		info->chunks = nparts;
+		info->large_rows = large_rows;
+	}
+	c->stats["selection_chunks"] = nparts;
+	c->stats["selection_us"] = (u64) std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
+	return VDJX_OK;
+}

@@ -772,6 +772,10 @@ int vdjx_part_u64(vdjx_ctx* ctx, const void* host_in, size_t n, int elem_bytes, 
  * vdjx_annotate's last call: "annot_cells" (DP cells of the scoring phase), "annot_score_us", "annot_trace_us", "annot_cigar_truncated".
  * vdjx_isotype's last call: "iso_cells" (DP cells of the scoring phase), "iso_score_us", "iso_trace_us" (host clock, each ending in a wait).
  * vdjx_dcall's last call: "dcall_cells" (the sum of win_len times the sum of the records' lengths), "dcall_score_us", "dcall_trace_us".
+ * How the last call of each of the three was cut up (0 after a call that failed or had no contig): "annot_chunks", "iso_chunks",
+ * "dcall_chunks" (the chunks of the record set, all classes), "annot_score_launches", "iso_score_launches", "dcall_score_launches" (the
+ * scoring launches that held work) and "annot_trace_launches", "iso_trace_launches", "dcall_trace_launches" (the traceback launches: 0
+ * where no hit was traced, more than 1 where the direction bytes of the hits exceed one launch's).
  * vdjx_mutations' last call: "mutations_cols" (the bytes of each of the three row buffers), "mutations_us" (host clock).
  * vdjx_selection's last call: "selection_chunks" (the partial sums of its large rows), "selection_us" (host clock).
  * vdjx_diversity's last call: "diversity_batches", "diversity_us" (host clock).

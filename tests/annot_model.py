@@ -152,19 +152,115 @@ def traceback(contig, germ, p=DEFAULT):
     return out
 
 
+def trace_fast(contig, germ, p=DEFAULT):
+    """traceback()'s dict, computed by anti-diagonals in numpy (int64, E and F unclamped) with a direction byte per cell instead of the
+    three matrices: bits 0-1 where H came from (0 stop, 1 diagonal, 2 E, 3 F, in that order of preference), bit 2 E opened here, bit 3
+    F opened here.  For pairs whose matrices plain Python cannot hold (4,095 x 2,047: about 1.5 s)."""
+    m, g = len(contig), len(germ)
+    ma, mi, oe, ext = p["match"], p["mismatch"], p["gap_open"] + p["gap_extend"], p["gap_extend"]
+    out = dict(score=0, seq_start=0, seq_end=0, germ_start=0, germ_end=0, matches=0, mismatches=0, ins=0, dele=0, opens=0, n_runs=0, ops=[])
+    if m == 0 or g == 0:
+        return out
+    cc, gc = _codes(contig, 4), _codes(germ, 5)
+    dirs = np.zeros(m * g, np.uint8)                                          # cell (i, j) at (i - 1) * g + (j - 1)
+    # diagonals indexed by i (0 .. m): H of d-1 and d-2, E and F of d-1; an entry a diagonal does not write is a border cell (0, -inf)
+    H1, H2 = np.zeros(m + 1, np.int64), np.zeros(m + 1, np.int64)
+    E1, F1 = np.full(m + 1, NEG, np.int64), np.full(m + 1, NEG, np.int64)
+    S, end = 0, -1
+    for d in range(2, m + g + 1):
+        lo, hi = max(1, d - g), min(m, d - 1)
+        i = np.arange(lo, hi + 1)
+        j = d - i
+        s = np.where(cc[i - 1] == gc[j - 1], ma, -mi)
+        eo, fo = H1[lo:hi + 1] - oe, H1[lo - 1:hi] - oe
+        e = np.maximum(E1[lo:hi + 1] - ext, eo)
+        f = np.maximum(F1[lo - 1:hi] - ext, fo)
+        dg = H2[lo - 1:hi] + s
+        h = np.maximum(np.maximum(dg, 0), np.maximum(e, f))
+        src = np.where(h == 0, 0, np.where(h == dg, 1, np.where(h == e, 2, 3)))
+        at = (i - 1) * g + (j - 1)
+        dirs[at] = src | np.where(e == eo, 4, 0) | np.where(f == fo, 8, 0)
+        top = int(h.max())
+        if top > S:
+            S, end = top, -1
+        if top == S and S > 0:
+            first = int(at[h == S].min())
+            end = first if end < 0 else min(end, first)
+        H0, E0, F0 = np.zeros(m + 1, np.int64), np.full(m + 1, NEG, np.int64), np.full(m + 1, NEG, np.int64)
+        H0[lo:hi + 1], E0[lo:hi + 1], F0[lo:hi + 1] = h, e, f
+        H2, H1, E1, F1 = H1, H0, E0, F0
+    if S == 0:
+        return out
+    ie, je = end // g + 1, end % g + 1
+    i, j, st, ops = ie, je, "H", []
+    while True:
+        dv = int(dirs[(i - 1) * g + (j - 1)]) if i > 0 and j > 0 else 0
+        if st == "H":
+            if dv & 3 == 0:
+                break
+            if dv & 3 == 1:
+                ops.append("M")
+                out["matches" if cc[i - 1] == gc[j - 1] else "mismatches"] += 1
+                i, j = i - 1, j - 1
+            else:
+                st = "E" if dv & 3 == 2 else "F"
+        elif st == "E":
+            ops.append("D")
+            out["dele"] += 1
+            if dv & 4:
+                out["opens"] += 1
+                st = "H"
+            j -= 1
+        else:
+            ops.append("I")
+            out["ins"] += 1
+            if dv & 8:
+                out["opens"] += 1
+                st = "H"
+            i -= 1
+    ops.reverse()
+    runs = []
+    for o in ops:
+        if runs and runs[-1][1] == o:
+            runs[-1][0] += 1
+        else:
+            runs.append([1, o])
+    out.update(seq_start=i + 1, seq_end=ie, germ_start=j + 1, germ_end=je, n_runs=len(runs), ops=runs, score=S)
+    return out
+
+
 def encode_runs(runs):
     code = {"M": 0, "I": 1, "D": 2}
     r = [(l << 4) | code[o] for l, o in runs] if len(runs) <= RUNS else []
     return r + [0] * (RUNS - len(r))
 
 
-def annotate(contigs, germs, classes, p=DEFAULT):
-    """the model of vdjx_annotate: {"v": {field: array}, "j": {...}} as api.Context.annotate returns them"""
+def _scores_by_length(contigs, germs, p):
+    """scores(), the records taken in groups of similar length (each longer than half the group's longest), so that a short record is
+    not padded to the longest one's columns"""
+    S = np.zeros((len(contigs), len(germs)), np.int64)
+    left = sorted(range(len(germs)), key=lambda k: -len(germs[k]))
+    while left:
+        grp = [k for k in left if 2 * len(germs[k]) > len(germs[left[0]])]
+        S[:, grp] = scores(contigs, [germs[k] for k in grp], p)
+        left = left[len(grp):]
+    return S
+
+
+def annotate(contigs, germs, classes, p=DEFAULT, fast=False):
+    """the model of vdjx_annotate: {"v": {field: array}, "j": {...}} as api.Context.annotate returns them.  fast: the primary hits by
+    trace_fast, and every distinct contig computed once (for long contigs against long records)"""
+    if fast:
+        first = {}
+        order = [first.setdefault(c, len(first)) for c in contigs]
+        if len(first) < len(contigs):
+            h = annotate(list(first), germs, classes, p, fast=True)
+            return {key: {f: v[order] for f, v in h[key].items()} for key in h}
     n = len(contigs)
     out = {}
     for cls, key, mn in (("V", "v", p["min_v_score"]), ("J", "j", p["min_j_score"])):
         idx = [r for r, c in enumerate(classes) if c == cls]
-        S = scores(contigs, [germs[r] for r in idx], p) if idx else np.zeros((n, 0), np.int64)
+        S = (_scores_by_length if fast else scores)(contigs, [germs[r] for r in idx], p) if idx else np.zeros((n, 0), np.int64)
         f = {k: np.zeros(n, np.int64) for k in FIELDS if k not in ("tied", "runs")}
         f["tied"] = np.full((n, TIED), -1, np.int64)
         f["runs"] = np.zeros((n, RUNS), np.int64)
@@ -178,7 +274,7 @@ def annotate(contigs, germs, classes, p=DEFAULT):
             f["gene"][c], f["n_tied"][c] = tied[0], len(tied)
             f["tied"][c, :min(TIED, len(tied))] = tied[:TIED]
             if best > 0:
-                tb = traceback(contigs[c], germs[tied[0]], p)
+                tb = (trace_fast if fast else traceback)(contigs[c], germs[tied[0]], p)
                 assert tb["score"] == best
                 for k in ("seq_start", "seq_end", "germ_start", "germ_end", "matches", "mismatches", "ins", "opens", "n_runs"):
                     f[k][c] = tb[k]

@@ -7,6 +7,7 @@ import re
 import numpy as np
 import pytest
 
+from tests import annot_limit_cases as L
 from tests import annot_model as A
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -166,3 +167,190 @@ def test_annot_struct_sizes_match_header():
     assert "/* 340 bytes */" in header
     for s in ("vdjx_germline_load", "vdjx_annotate"):
         assert s in _lib.SYMBOLS and hasattr(_lib.lib(), s)
+
+
+# ---- trace_fast: the single-pair model by anti-diagonals, equal to traceback() on every field -----------------------------------------
+PARAM_SETS = [A.DEFAULT, dict(match=1, mismatch=1, gap_open=0, gap_extend=1, min_v_score=10, min_j_score=5),
+              dict(match=15, mismatch=31, gap_open=31, gap_extend=31, min_v_score=0, min_j_score=0),
+              dict(match=3, mismatch=2, gap_open=2, gap_extend=1, min_v_score=40, min_j_score=20), dict(A.DEFAULT, gap_open=0)]
+
+
+def _fast_equals_plain(a, b, p, what=None):
+    x, y = A.traceback(a, b, p), A.trace_fast(a, b, p)
+    assert x == y, (what, a, b, p, x, y)
+    return x
+
+
+@pytest.mark.parametrize("k", range(len(PARAM_SETS)))
+def test_trace_fast_equals_traceback_random_pairs(k):
+    """240 seeded pairs of 1 .. 120 bases per parameter set (the five of test_gpu_annot._api_checks; DEFAULT is two of them, so
+    gap_open = 0 with DEFAULT's other costs stands in): unrelated pairs, a mutated copy of the other, N and lower-case bases"""
+    p = PARAM_SETS[k]
+    rng = np.random.default_rng(100 + k)
+    zero = hit = 0
+    for q in range(240):
+        a = _rand(rng, int(rng.integers(1, 121)), "ACGTN" if q % 5 == 0 else "ACGT")
+        if q % 3 == 0:
+            b = _rand(rng, int(rng.integers(1, 121)))
+        else:                                                                   # (a piece of a with substitutions and indels)
+            lo = int(rng.integers(0, len(a)))
+            b = list(a[lo:lo + int(rng.integers(1, 121))])
+            for _ in range(int(rng.integers(0, 6))):
+                at, op = int(rng.integers(0, len(b))), int(rng.integers(0, 3))
+                if op == 0:
+                    b[at] = "ACGT"[int(rng.integers(0, 4))]
+                elif op == 1 and len(b) > 1:
+                    del b[at]
+                else:
+                    b.insert(at, "ACGT"[int(rng.integers(0, 4))])
+            b = "".join(b)[:120]
+        if q % 7 == 0:
+            a = a[:len(a) // 2] + a[len(a) // 2:].lower()                       # (a lower-case base matches nothing)
+        if q % 11 == 0:
+            b = b[:len(b) // 2] + "N" + b[len(b) // 2 + 1:]
+        t = _fast_equals_plain(a, b, p, q)
+        zero += t["score"] == 0
+        hit += t["n_runs"] > 1
+    assert hit > 20, hit
+
+
+def test_trace_fast_equals_traceback_ties_and_zero():
+    """S = 0; cells that two or three sources reach with the same value; several cells that hold S"""
+    for p in PARAM_SETS:
+        for a, b in (("AAAA", "CCCC"), ("NNNN", "NNNN"), ("acgt", "ACGT"), ("A", "C"), ("N", "A")):
+            assert _fast_equals_plain(a, b, p)["score"] == 0
+    # match = mismatch = extend = 1, open = 0: a gap of one costs what a mismatch costs, so diagonal, E and F tie all over
+    flat = PARAM_SETS[1]
+    rng = np.random.default_rng(77)
+    for _ in range(60):
+        a, b = _rand(rng, int(rng.integers(2, 40)), "AC"), _rand(rng, int(rng.integers(2, 40)), "AC")
+        _fast_equals_plain(a, b, flat)
+    # handmade: a cell whose diagonal, E and F all give H (1 - 1 = 2 - 2 ... ) -- count them in the plain matrices
+    three = two = 0
+    for _ in range(60):
+        a, b = _rand(rng, 12, "AC"), _rand(rng, 12, "AC")
+        H, E, F = A.matrices(a, b, flat)
+        for i in range(1, 13):
+            for j in range(1, 13):
+                s = 1 if a[i - 1] == b[j - 1] else -1
+                srcs = [H[i - 1][j - 1] + s, E[i][j], F[i][j]]
+                if H[i][j] > 0:
+                    n = sum(x == H[i][j] for x in srcs)
+                    three += n == 3
+                    two += n == 2
+    assert three > 0 and two > 0, (three, two)
+    # several cells hold S: a repeat in the contig, in the record, in both; the first in row-major order is the end
+    g = "ACGTTGCAAGGC"
+    for a, b in ((g + "TTTTT" + g, g), (g, g + "AAAAA" + g), (g + "T" * 20 + g, g + "A" * 20 + g), ("ACACACACAC", "ACACAC"), ("AAAAAAAA", "AAA")):
+        for p in PARAM_SETS:
+            t = _fast_equals_plain(a, b, p)
+            H = A.matrices(a, b, p)[0]
+            assert sum(x == t["score"] for r in H for x in r) > 1, (a, b)
+    t = A.trace_fast(g + "TTTTT" + g, g)
+    assert (t["seq_start"], t["seq_end"]) == (1, 12)
+
+
+def test_trace_fast_more_than_64_runs():
+    """the case of test_gpu_annot._api_checks: n_runs exact, the run list dropped by encode_runs, the same through annotate(fast=True)"""
+    rng = np.random.default_rng(9)
+    g = _rand(rng, 900)
+    cont = "".join(g[q:q + 6] + ("" if (q // 6) % 2 else "T") for q in range(0, 900, 6))[:700]
+    p = dict(A.DEFAULT, gap_open=0, gap_extend=1)
+    t = _fast_equals_plain(cont, g, p)
+    assert t["n_runs"] > 64 and not any(A.encode_runs(t["ops"]))
+    slow, fast = A.annotate([cont, cont], [g, g[:50]], ["V", "J"], p), A.annotate([cont, cont], [g, g[:50]], ["V", "J"], p, fast=True)
+    for cls in ("v", "j"):
+        for f in A.FIELDS:
+            assert np.array_equal(slow[cls][f], fast[cls][f]), (cls, f)
+    assert fast["v"]["n_runs"][0] == t["n_runs"] and not fast["v"]["runs"].any()
+
+
+def test_annotate_fast_equals_plain_on_a_random_case():
+    from tests.test_gpu_annot import _random_case
+    contigs, recs, germs, classes = _random_case(3, 64, n=5)
+    slow, fast = A.annotate(contigs, germs, classes), A.annotate(contigs + contigs[:2], germs, classes, fast=True)
+    for cls in ("v", "j"):
+        for f in A.FIELDS:
+            assert np.array_equal(slow[cls][f], fast[cls][f][:5]) and np.array_equal(fast[cls][f][5:], fast[cls][f][:2]), (cls, f)
+
+
+# ---- the limit cases (tests/annot_limit_cases.py): each one's condition, from the inputs and the model alone ---------------------------
+def _vlens(c):
+    return [len(g) for g, cl in zip(c["germs"], c["classes"]) if cl == "V"]
+
+
+def test_packing_rules_restated():
+    assert L.chunk_sizes([2047] * 32) == [31, 1] and L.chunk_sizes([2047] * 5 + [2046] + [2047] * 26) == [32]
+    assert L.chunk_sizes([65534]) == [1] and L.chunk_sizes([10, 20, 30], recs=2) == [2, 1] and L.chunk_sizes([]) == []
+    assert L.chunk_sizes([2047] * 32, cols=65537) == [32]
+    h = dict(v=dict(gene=[0] * 33, score=[5] * 33), j=dict(gene=[-1, 1], score=[9, 0]))
+    assert L.trace_launch_sizes(h, 4095, ["A" * 2047, "A"]) == [32, 1]
+    assert 32 * 4095 * 2047 == 268238880 <= L.DIR_BYTES == 268435456 < 33 * 4095 * 2047
+    assert L.trace_launch_sizes(dict(v=dict(gene=[-1], score=[0]), j=dict(gene=[], score=[])), 10, ["A"]) == []
+
+
+def test_limit_case_long_pair():
+    c = L.long_pair()
+    assert c["m"] == 4095 and len(c["contigs"]) == 6 and [len(c["germs"][k]) for k in (L.VA, L.VB)] == [2047, 2047]
+    assert c["germs"][L.VA] != c["germs"][L.VB] and c["germs"][5] == c["germs"][2] and c["params"] == [A.DEFAULT, dict(A.DEFAULT, gap_open=0)]
+    assert all(30 <= len(g) <= 60 for g, cl in zip(c["germs"], c["classes"]) if cl == "J")
+    for k in range(2):
+        h = L.model("long_pair", k)
+        v, j = h["v"], h["j"]
+        assert v["gene"].tolist() == [L.VA, L.VA, L.VB, L.VB, L.VA, L.VB], (k, v["gene"])
+        assert (v["germ_end"] - v["germ_start"] >= 1400).all() and (v["n_runs"] <= 64).all() and (v["n_runs"] > 1).all(), (k, v["n_runs"])
+        assert (v["ins"] > 0).any() and (v["del"] > 0).any()
+        assert v["seq_end"][5] == 4095 and v["seq_start"][4] == 1 and (j["gene"] >= 0).all()
+        assert (j["seq_start"][:5] > v["seq_end"][:5]).all() and j["seq_end"][5] < v["seq_start"][5]
+
+
+def test_limit_case_ceiling():
+    c = L.ceiling()
+    assert c["params"][0] == dict(match=15, mismatch=31, gap_open=31, gap_extend=31, min_v_score=0, min_j_score=0)
+    v = L.model("ceiling")["v"]
+    s = v["score"].tolist()
+    assert s[0] == 30705 == 15 * 2047 and v["matches"][0] == 2047 and v["n_runs"][0] == 1 and v["runs"][0][0] == 2047 << 4
+    assert all(0 < 30705 - x <= 200 for x in s[1:]) and len(set(s)) == 4, s
+    assert v["mismatches"][1] == 1 and v["del"][2] == 1 and v["germ_end"][3] == 2046 and (v["gene"] == 1).all()
+
+
+def test_limit_case_column_chunks():
+    a, b = L.column_chunks("A"), L.column_chunks("B")
+    la, lb = _vlens(a), _vlens(b)
+    assert la[:32] == [2047] * 32 and len(la) == 35 and lb[5] == 2046 and [x for k, x in enumerate(lb) if k != 5] == [x for k, x in enumerate(la) if k != 5]
+    assert sum(x + 1 for x in la[:32]) + 1 == 65537 and sum(x + 1 for x in lb[:32]) + 1 == 65536
+    assert L.chunk_sizes(la) == [31, 4] and L.n_chunks(a["germs"], a["classes"]) == 3
+    assert L.chunk_sizes(lb) == [32, 3] and L.n_chunks(b["germs"], b["classes"]) == 3
+    # the long records alone: the class is 65,537 and 65,536 columns, two chunks and one
+    al, bl = L.column_chunks("A", False), L.column_chunks("B", False)
+    assert L.chunk_sizes(_vlens(al)) == [31, 1] and L.n_chunks(al["germs"], al["classes"]) == 3
+    assert L.chunk_sizes(_vlens(bl)) == [32] and L.n_chunks(bl["germs"], bl["classes"]) == 2
+    # VDJX_ANNOT_PAIRS = 100: at most 25 records per chunk, and a launch that ends between two contig groups of a chunk
+    assert L.chunk_sizes(la, recs=25) == [25, 10] and L.n_chunks(a["germs"], a["classes"], recs=25) == 3
+    assert L.score_launches(9, a["germs"], a["classes"], 100) == 4
+    assert len(a["contigs"]) == 9 and all(len(x) == 70 for x in a["contigs"])
+    for which, cut in (("A", 31), ("B", 32)):
+        v = L.model("column_chunks_" + which)["v"]
+        assert v["n_tied"][0] == 11 and v["tied"][0].tolist() == L.TIED_IN[:8] and v["score"][0] == 140
+        assert sum(r < cut for r in L.TIED_IN) in (7, 8) and sum(r >= cut for r in L.TIED_IN) >= 3
+        assert v["n_tied"][1] == 2 and v["tied"][1].tolist()[:2] == L.TWICE_IN and L.TWICE_IN[0] < 25 and L.TWICE_IN[1] >= cut
+        assert v["gene"][2] == L.AFTER_IN >= cut and v["gene"][3] == L.BEFORE_IN < 25 and v["n_tied"][2] == v["n_tied"][3] == 1
+        assert v["n_tied"][4] == 11 and 0 < v["score"][4] < 140 and v["del"][5] == 1
+    assert L.model("column_chunks_A_long")["v"]["n_tied"][0] == 8 and L.model("column_chunks_B_long")["v"]["n_tied"][1] == 1
+
+
+def test_limit_case_trace_launches():
+    c = L.trace_launches()
+    assert len(c["contigs"]) == 34 and c["m"] == 4095 and len(set(c["contigs"])) == 7
+    assert all(c["contigs"][q] == c["contigs"][q % 4] for q in range(31)) and len(set(c["contigs"][:4] + c["contigs"][31:])) == 7
+    assert all(c["contigs"][q] != c["contigs"][q + 1] for q in range(33))
+    h = L.model("trace_launches")
+    v, j = h["v"], h["j"]
+    assert set(v["gene"].tolist()) == {L.VA, L.VB} and (v["gene"][:-1] != v["gene"][1:]).all() and (j["gene"] >= 0).all() and (j["score"] > 0).all()
+    sizes = L.trace_launch_sizes(h, 4095, c["germs"])
+    assert len(sizes) >= 2 and sizes[0] == 32 and sum(sizes) == 68, sizes       # (V alignments 0 .. 31 | 32, 33 and the J's)
+    # the parts taken from long_pair's model are what annotate gives for this case's own contigs
+    own = A.annotate(c["contigs"][2:3], c["germs"], c["classes"], c["params"][0], fast=True)
+    for cls in ("v", "j"):
+        for f in A.FIELDS:
+            assert np.array_equal(own[cls][f][0], h[cls][f][2]) and np.array_equal(h[cls][f][2], h[cls][f][30]), (cls, f)

@@ -376,11 +376,13 @@ struct AnCall {
 	const char *scope_score, *scope_trace;
 	vdjx_annot_hit* out[2];              // per class: [n]
 	u64 cells, us_score, us_trace;
+	u64 chunks, score_launches, trace_launches;   // the call's chunks, its scoring launches that held work, its traceback launches
 };
 
 // The two phases for n contigs of `len` characters (the header comment).  Nothing is done for n == 0.
 static int an_run(vdjx_ctx* c, const char* contigs, size_t n, int len, AnParams p, AnCall& a) {
 	a.cells = a.us_score = a.us_trace = 0;              // (they stay 0 unless the call succeeds)
+	a.chunks = a.score_launches = a.trace_launches = 0;
 	if (n == 0) return VDJX_OK;
 	if (len < 1 || len >= 4096) { vdjx_set_error("%s: len=%d (1 .. 4095)", a.who, len); return VDJX_EINVAL; }
 	if (n >= (1ull << 20)) { vdjx_set_error("%s: %zu contigs (at most 2^20 - 1 per call)", a.who, n); return VDJX_EINVAL; }
@@ -458,6 +460,7 @@ static int an_run(vdjx_ctx* c, const char* contigs, size_t n, int len, AnParams 
 	const AnChunk* d_ck = (const AnChunk*) d_tab;
 	const uint2* d_items = (const uint2*) (d_tab + b_ck);
 	const u32* d_genes = (const u32*) (d_tab + b_ck + b_it);
+	u64 score_launches = 0;
 #define AN_LAUNCH(RR, MX, WN) hipLaunchKernelGGL((k_an_score<RR, MX, WN>), dim3(nb), dim3(64 * AN_WAVES), 0, st, (const char*) d_ct + q0, (u32) n, (u32) len, m, \
 	(const uint8_t*) s.d_cols, d_ck, d_genes, d_items + b0, p, (u32) C, d_scores, d_res, (const int2*) d_win)
 #define AN_CASE(RR) case RR: AN_LAUNCH(RR, false, false); break;
@@ -467,6 +470,7 @@ static int an_run(vdjx_ctx* c, const char* contigs, size_t n, int len, AnParams 
 		for (size_t L = 0; L + 1 < launch_at.size(); L++) {
 			const u32 b0 = launch_at[L], nb = launch_at[L + 1] - b0;
 			if (!nb) continue;
+			score_launches++;
 			if (win) switch (an_rows(m)) {                  // (m <= 256: 1 .. 4 rows per lane)
 				AN_CASE_WIN(1) AN_CASE_WIN(2) AN_CASE_WIN(3) AN_CASE_WIN(4)
 			}
@@ -526,6 +530,9 @@ static int an_run(vdjx_ctx* c, const char* contigs, size_t n, int len, AnParams 
 	a.cells = cells;
 	a.us_score = us_score;
 	a.us_trace = (u64) an_us_since(t1);
+	a.chunks = nck;
+	a.score_launches = score_launches;
+	a.trace_launches = al.empty() ? 0 : at.size() - 1;
 	return VDJX_OK;
 }
 
@@ -549,6 +556,9 @@ extern "C" int vdjx_annotate(vdjx_ctx* c, const char* contigs, size_t n, int len
 	c->stats["annot_cells"] = a.cells;
 	c->stats["annot_score_us"] = a.us_score;
 	c->stats["annot_trace_us"] = a.us_trace;
+	c->stats["annot_chunks"] = a.chunks;
+	c->stats["annot_score_launches"] = a.score_launches;
+	c->stats["annot_trace_launches"] = a.trace_launches;
 	c->stats["annot_cigar_truncated"] = trunc;
 	return rc;
 }
@@ -569,6 +579,9 @@ extern "C" int vdjx_isotype(vdjx_ctx* c, const char* contigs, size_t n, int len,
 	c->stats["iso_cells"] = a.cells;
 	c->stats["iso_score_us"] = a.us_score;
 	c->stats["iso_trace_us"] = a.us_trace;
+	c->stats["iso_chunks"] = a.chunks;
+	c->stats["iso_score_launches"] = a.score_launches;
+	c->stats["iso_trace_launches"] = a.trace_launches;
 	return rc;
 }
 
@@ -593,5 +606,8 @@ extern "C" int vdjx_dcall(vdjx_ctx* c, const char* contigs, size_t n, int len, c
 	c->stats["dcall_cells"] = a.cells;
 	c->stats["dcall_score_us"] = a.us_score;
 	c->stats["dcall_trace_us"] = a.us_trace;
+	c->stats["dcall_chunks"] = a.chunks;
+	c->stats["dcall_score_launches"] = a.score_launches;
+	c->stats["dcall_trace_launches"] = a.trace_launches;
 	return rc;
 }

@@ -281,6 +281,15 @@ def _device(_):
         ctx.mutations((two[0]["contig"].encode() + b"ACG\0" + two[1]["contig"].encode()[4:], 2, LEN), _hits(two, "v"), _hits(two, "j"))
     with pytest.raises(VdjxError, match="len=4096"):
         ctx.mutations(["A" * 4096], _hits([dict(v=NONE, j=NONE)], "v"), _hits([dict(v=NONE, j=NONE)], "j"))
+    # strings of unequal length: one preamble behind every call, under each caller's name
+    short = [two[0]["contig"], two[1]["contig"][:-1]]
+    for who, call in (("vdjx_mutations", lambda: ctx.mutations(short, _hits(two, "v"), _hits(two, "j"))),
+                      ("vdjx_selection", lambda: ctx.selection(short, _hits(two, "v"))),
+                      ("vdjx_tree", lambda: ctx.tree(short, [0, 0], [0, 0]))):
+        with pytest.raises(VdjxError) as err:
+            call()
+        assert str(err.value) == f"{who}: contigs of unequal length"
+    out["unequal"] = 3
     big = 1 << 20                                                    # (the arrays are zero pages until someone reads them: nobody does)
     zero = np.zeros(big, api.Context.ANNOT_HIT)
     rows = np.zeros(big, api.Context.MUT_ROW)
@@ -312,7 +321,7 @@ def _info_of(counts, cs, sl, with_d):
 def test_mutations_api_vs_model(knobs):
     res = _run_child("_device", "x", _child_env(knobs))
     cs = cases()
-    assert res["n"] == len(cs) and len(cs) % CALL == 0 and res["refused"] == 15
+    assert res["n"] == len(cs) and len(cs) % CALL == 0 and res["refused"] == 15 and res["unequal"] == 3
     for with_d, key in ((True, "calls"), (False, "calls_no_d")):
         rows, counts, info = model(with_d)
         for k, dev in enumerate(res[key]):

@@ -188,11 +188,27 @@ def _device_refusals(_):
     ctx.germline_load(TM.records())
     vh = good["v"]
     hit = lambda h, **kw: dict(h, **kw)
+    by_layout = 0
     for cs2 in (pair(v=hit(vh, gene=11)), pair(v=hit(vh, gene=TM.J0)), pair(v=hit(vh, gene=TM.C1)), pair(v=H(TM.V2, 5, 1, [("M", 2)])),
                 pair(v=hit(H(TM.V0, 1, 1, [("M", 9)]), seq_start=0, seq_end=8)), pair(v=hit(H(TM.V0, 5, 1, [("M", 9)]), germ_start=0, germ_end=8)),
                 pair(v=H(TM.V0, 290, 1, [("M", 20)])), pair(v=hit(vh, runs=[(100 << 4) | 3] + [0] * 63)), pair(v=hit(vh, runs=[0] + [0] * 63)),
                 pair(v=hit(vh, seq_end=vh["seq_end"] + 1)), pair(v=hit(vh, germ_end=vh["germ_end"] + 1))):
-        done += call(ctx, cs2, "vdjx_selection: contig 1")
+        with pytest.raises(VdjxError, match="vdjx_selection: contig 1") as sel:
+            ctx.selection([c["contig"] for c in cs2], SC.hits(cs2))
+        done += 1
+        # one hit check behind both calls: where vdjx_mutations refuses the same V hit (J: none), it says the same under its own name.
+        # A run with a bad op or a length of 0 never reaches it: vdjx_mutations_layout meets it first.
+        with pytest.raises(VdjxError) as mut:
+            ctx.mutations([c["contig"] for c in cs2], SC.hits(cs2), SC.hits([dict(j=TM.NONE)] * 2, "j"))
+        if str(mut.value).startswith("vdjx_mutations_layout"):
+            by_layout += 1
+        else:
+            assert str(mut.value) == str(sel.value).replace("vdjx_selection", "vdjx_mutations")
+            done += 1
+    assert by_layout == 2
+    with pytest.raises(VdjxError, match="^vdjx_selection: 2 contigs, v\\['runs'\\] of shape"):        # the caller's name in _hit_array's message
+        ctx.selection([c["contig"] for c in pair()], dict(SC.hits(pair()), runs=np.zeros((2, 63), np.int64)))
+    done += 1
     for bad in (-1, TM.LEN + 1):
         done += call(ctx, pair(), "contig 1: limit", limit=[TM.LEN, bad])
     two = pair()
@@ -218,7 +234,7 @@ def _device_refusals(_):
     done += call(ctx, pair(), "1048576 groups", group=[0, 1], groups=1 << 20)
     done += call(ctx, pair(), "densities of 65536 groups", group=[0, 1], groups=65536, pdf=True)
     raw, n, ln = ctx.pack_strings([c["contig"] for c in pair()])
-    hv = ctx._hit_array(SC.hits(pair()), 2, "v")
+    hv = ctx._hit_array(SC.hits(pair()), 2, "v", "vdjx_selection")
     cnt, st = np.zeros(2, api.Context.SEL_COUNTS), np.zeros((3, 1), api.Context.SEL_STAT)
     for a, b in ((None, st.ctypes.data), (cnt.ctypes.data, None)):
         rc = ctx.L.vdjx_selection(ctx.h, raw, 2, ln, hv.ctypes.data, None, None, 0, None, None, 0, a, b, None, None)
@@ -233,4 +249,4 @@ def _device_refusals(_):
 
 
 def test_refusals_by_message():
-    assert _run_child("_device_refusals", "x", _child_env("shipped")) == 26
+    assert _run_child("_device_refusals", "x", _child_env("shipped")) == 36

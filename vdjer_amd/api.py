@@ -598,15 +598,18 @@ class Context:
         addr = C.cast(txt, C.c_void_p).value
         return bytes((C.c_char * nb.value).from_address(addr)) if nb.value else b""
 
+    def _contig_block(self, contigs, who):
+        """pack_strings' tuple as it is, or equally long strings packed -> (raw, n, ln)"""
+        if isinstance(contigs, tuple):
+            return contigs
+        if len({len(s_) for s_ in contigs}) > 1:
+            raise VdjxError(f"{who}: contigs of unequal length")
+        return self.pack_strings(contigs)
+
     def quant(self, contigs, max_iter: int = 10000, tol: float = 1e-5):
         """vdjx_quant: expected read pairs per contig (RSEM's paired-end EM over map_emit's placements, on the device)
         -> (counts float64[n], info dict: pairs, alignments, unique_pairs, iterations, converged, eff_len)"""
-        if isinstance(contigs, tuple):
-            raw, n, ln = contigs
-        else:
-            if len({len(s_) for s_ in contigs}) > 1:
-                raise VdjxError("vdjx_quant: contigs of unequal length")
-            raw, n, ln = self.pack_strings(contigs)
+        raw, n, ln = self._contig_block(contigs, "vdjx_quant")
         counts = np.zeros(n, np.float64)
         info = _lib.QuantInfo()
         prm = _lib.QuantParams(int(max_iter), float(tol))
@@ -663,12 +666,7 @@ class Context:
         """vdjx_quant_boot: quant's point estimate and `replicates` bootstrap replicates of it over the placed pairs -> dict: counts
         float64[n] and info (quant's), boot float64[B, n], mean / sd / lower / upper float64[n] (vdjx_quant_boot_summary), iterations
         uint32[B], boot_info (replicates, converged, batches, max_iterations, iterations)"""
-        if isinstance(contigs, tuple):
-            raw, n, ln = contigs
-        else:
-            if len({len(s_) for s_ in contigs}) > 1:
-                raise VdjxError("vdjx_quant_boot: contigs of unequal length")
-            raw, n, ln = self.pack_strings(contigs)
+        raw, n, ln = self._contig_block(contigs, "vdjx_quant_boot")
         b = int(replicates)
         rows = b if 1 <= b <= 1024 else 1
         counts, boot, iters = np.zeros(n, np.float64), np.zeros((rows, n), np.float64), np.zeros(rows, np.uint32)
@@ -731,12 +729,7 @@ class Context:
                  min_j_score: int = 20):
         """vdjx_annotate: V and J hits of every contig against the loaded germlines -> {"v": {field: array}, "j": {...}}, the fields of
         vdjx_annot_hit (tied: [n, 8], runs: [n, 64])"""
-        if isinstance(contigs, tuple):
-            raw, n, ln = contigs
-        else:
-            if len({len(s_) for s_ in contigs}) > 1:
-                raise VdjxError("vdjx_annotate: contigs of unequal length")
-            raw, n, ln = self.pack_strings(contigs)
+        raw, n, ln = self._contig_block(contigs, "vdjx_annotate")
         hv = np.zeros(n, self.ANNOT_HIT)
         hj = np.zeros(n, self.ANNOT_HIT)
         prm = _lib.AnnotParams(int(match), int(mismatch), int(gap_open), int(gap_extend), int(min_v_score), int(min_j_score))
@@ -761,12 +754,7 @@ class Context:
                 min_score: int = 48, scores: bool = True):
         """vdjx_isotype: the last `tail` bases of every contig against the loaded constant set -> {"c": {field: array}, "scores":
         int32[n, C] | None}, the fields of vdjx_annot_hit (seq_start / seq_end in contig coordinates)"""
-        if isinstance(contigs, tuple):
-            raw, n, ln = contigs
-        else:
-            if len({len(s_) for s_ in contigs}) > 1:
-                raise VdjxError("vdjx_isotype: contigs of unequal length")
-            raw, n, ln = self.pack_strings(contigs)
+        raw, n, ln = self._contig_block(contigs, "vdjx_isotype")
         hc = np.zeros(n, self.ANNOT_HIT)
         nc = getattr(self, "_const_n", 0)
         sc = np.zeros((n, nc), np.int32) if scores else None
@@ -797,12 +785,7 @@ class Context:
               min_score: int = 22, scores: bool = True):
         """vdjx_dcall: contig c's window [win_start[c], win_start[c] + win_len[c]) (0-based, at most 256 bases) against the loaded D set
         -> {"d": {field: array}, "scores": int32[n, C] | None}, the fields of vdjx_annot_hit (seq_start / seq_end in contig coordinates)"""
-        if isinstance(contigs, tuple):
-            raw, n, ln = contigs
-        else:
-            if len({len(s_) for s_ in contigs}) > 1:
-                raise VdjxError("vdjx_dcall: contigs of unequal length")
-            raw, n, ln = self.pack_strings(contigs)
+        raw, n, ln = self._contig_block(contigs, "vdjx_dcall")
         ws = np.ascontiguousarray(win_start, np.int32)
         wl = np.ascontiguousarray(win_len, np.int32)
         if ws.shape != (n,) or wl.shape != (n,):
@@ -817,13 +800,13 @@ class Context:
     MUT_ROW = np.dtype([(f, "<i4") for f in ("cols", "v_r", "v_s", "v_stop", "v_na", "v_codons", "j_mis", "flags")])
     MUT_INFO_FIELDS = ("contigs", "aligned", "cols", "v_r", "v_s", "v_stop", "v_na", "v_codons", "truncated", "clipped")
 
-    def _hit_array(self, h, n, what):
-        """the field dict of annotate() / dcall() as an array of vdjx_annot_hit"""
+    def _hit_array(self, h, n, what, who):
+        """the field dict of annotate() / dcall() as an array of vdjx_annot_hit; who: the call's name in the message"""
         out = np.zeros(n, self.ANNOT_HIT)
         for f in self.ANNOT_HIT.names:
             a = np.asarray(h[f])
             if a.shape != out[f].shape:
-                raise VdjxError(f"vdjx_mutations: {n} contigs, {what}[{f!r}] of shape {a.shape}")
+                raise VdjxError(f"{who}: {n} contigs, {what}[{f!r}] of shape {a.shape}")
             out[f] = a
         return out
 
@@ -832,14 +815,9 @@ class Context:
         counts.  v, j, d: the field dicts annotate() and dcall() return (d may be None); limit: int32[n] or None (the contig's length)
         -> {"seq", "germ", "mask": list[str] | None (rows=False: no row is fetched), "counts": {field: int32[n]} (cols, v_r, v_s, v_stop,
         v_na, v_codons, j_mis, flags), "info": dict}"""
-        if isinstance(contigs, tuple):
-            raw, n, ln = contigs
-        else:
-            if len({len(s_) for s_ in contigs}) > 1:
-                raise VdjxError("vdjx_mutations: contigs of unequal length")
-            raw, n, ln = self.pack_strings(contigs)
-        hv, hj = self._hit_array(v, n, "v"), self._hit_array(j, n, "j")
-        hd = None if d is None else self._hit_array(d, n, "d")
+        raw, n, ln = self._contig_block(contigs, "vdjx_mutations")
+        hv, hj = self._hit_array(v, n, "v", "vdjx_mutations"), self._hit_array(j, n, "j", "vdjx_mutations")
+        hd = None if d is None else self._hit_array(d, n, "d", "vdjx_mutations")
         lim = None if limit is None else np.ascontiguousarray(limit, np.int32)
         if lim is not None and lim.shape != (n,):
             raise VdjxError(f"vdjx_mutations: {n} contigs, limit of shape {lim.shape}")
@@ -872,13 +850,8 @@ class Context:
         (annot.read_targeting) or None (uniform); group: int32[n] (negative: in no group) or None; groups: G (None: max(group) + 1)
         -> {"counts": {field: array[n] or [n, 2]}, "stat": {field: array[n + G + 1, K]}, "pdf": float64[G + 1, K, 4001] | None, "info":
         dict}"""
-        if isinstance(contigs, tuple):
-            raw, n, ln = contigs
-        else:
-            if len({len(s_) for s_ in contigs}) > 1:
-                raise VdjxError("vdjx_selection: contigs of unequal length")
-            raw, n, ln = self.pack_strings(contigs)
-        hv = self._hit_array(v, n, "v")
+        raw, n, ln = self._contig_block(contigs, "vdjx_selection")
+        hv = self._hit_array(v, n, "v", "vdjx_selection")
         lim = None if limit is None else np.ascontiguousarray(limit, np.int32)
         if lim is not None and lim.shape != (n,):
             raise VdjxError(f"vdjx_selection: {n} contigs, limit of shape {lim.shape}")
@@ -935,12 +908,7 @@ class Context:
         anchors, rooted at the member of smallest (prio, index).  contigs: equally long strings (or pack_strings' tuple); clone: int32[n],
         -1 for an item that takes no part; anchor: int32[n], 0 .. len; prio: uint32[n] or None -> {"parent", "dist", "depth": int32[n]
         (-1: no part; parent and dist -1 for a root), "info": dict(members, clones, largest_clone, rounds, edges, weight)}"""
-        if isinstance(contigs, tuple):
-            raw, n, ln = contigs
-        else:
-            if len({len(s_) for s_ in contigs}) > 1:
-                raise VdjxError("vdjx_tree: contigs of unequal length")
-            raw, n, ln = self.pack_strings(contigs)
+        raw, n, ln = self._contig_block(contigs, "vdjx_tree")
         cl = np.ascontiguousarray(clone, np.int32)
         an = np.ascontiguousarray(anchor, np.int32)
         pr = None if prio is None else np.ascontiguousarray(prio, np.uint32)
@@ -958,12 +926,7 @@ class Context:
         int32[n], for every member the item whose edge to it is scored, or -1 (typically tree()'s "parent"); replicates: 1 .. 1024; seed:
         any uint64 -> {"support": int32[n] (the replicates whose tree has the edge {i, parent[i]}; -1 where parent is), "info":
         dict(members, clones, largest_clone, replicates, batches, rounds, edges, matched, full)}"""
-        if isinstance(contigs, tuple):
-            raw, n, ln = contigs
-        else:
-            if len({len(s_) for s_ in contigs}) > 1:
-                raise VdjxError("vdjx_tree_support: contigs of unequal length")
-            raw, n, ln = self.pack_strings(contigs)
+        raw, n, ln = self._contig_block(contigs, "vdjx_tree_support")
         cl = np.ascontiguousarray(clone, np.int32)
         an = np.ascontiguousarray(anchor, np.int32)
         pa = np.ascontiguousarray(parent, np.int32)

@@ -600,6 +600,34 @@ __device__ inline u64 vdjx_wave_max64(u64 v) {
 	return v;
 }
 
+// an 8-byte value from lane ^ o: its two halves through two 4-byte shuffles
+__device__ __forceinline__ u64 vdjx_shfl_xor64(u64 v, int o) {
+	const u32 lo = (u32) __shfl_xor((int) (u32) v, o, 64), hi = (u32) __shfl_xor((int) (u32) (v >> 32), o, 64);
+	return (u64) hi << 32 | lo;
+}
+// wave-wide sums by a butterfly of shuffles, in every lane
+__device__ __forceinline__ int vdjx_wave_sum(int v) {
+#pragma unroll
+	for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+	return v;
+}
+__device__ __forceinline__ u64 vdjx_wave_sum64(u64 v) {
+#pragma unroll
+	for (int o = 32; o >= 1; o >>= 1) v += vdjx_shfl_xor64(v, o);
+	return v;
+}
+// exclusive prefix sum over the wave by shuffles; total: the wave's sum, in every lane
+__device__ __forceinline__ int vdjx_wave_excl(int v, u32 lane, int& total) {
+	int s = v;
+#pragma unroll
+	for (int o = 1; o < 64; o <<= 1) {
+		const int t = __shfl_up(s, o, 64);
+		if ((int) lane >= o) s += t;
+	}
+	total = __shfl(s, 63, 64);
+	return s - v;
+}
+
 // wave-wide inclusive prefix sum through DPP (row shifts inside the rows of 16 lanes, then the two row broadcasts): all 64 lanes
 // must be active
 __device__ inline int vdjx_wave_scan_add(int v) {

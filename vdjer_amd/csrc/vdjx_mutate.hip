@@ -4,28 +4,26 @@
 //   vdjx_mutations          lays each contig and its V(D)J germline side by side, column by column, and classifies the V differences codon
 //                           by codon (the model: include/vdjx.h; in Python: tests/mutation_model.py)
 //
-// The hits are the caller's, so the host checks every one of them before anything reaches the device (mu_plan): every index the kernel forms
-// lies inside the contig, the record and the row buffers because the run lengths were summed here.  Per contig the host uploads 64 bytes of
-// positions and record offsets (MuContig) and the usable hits' runs, 4 bytes each.
+// The hits are the caller's, so the host checks every one of them before anything reaches the device (vh_check of vdjx_vhit.h, then mu_plan):
+// every index the kernel forms lies inside the contig, the record and the row buffers because the run lengths were summed there.  Per contig
+// the host uploads 64 bytes of positions and record offsets (MuContig) and the usable hits' runs, 4 bytes each.  The hit check, a hit's rows
+// of the segment table and the codon resolver are vdjx_vhit.h's, shared with vdjx_select.hip; what is here is the layout, the rows pass and
+// what a resolved codon counts as.
 //   k_mutations   one dispatch; a wave per contig, MU_WAVES waves per workgroup, no barrier between the waves.
-//     table       one lane per run of V, then of D, then of J; three wave-wide exclusive scans per hit (columns, contig bases, germline
-//                 bases) give the segment table in LDS: MU_SLOTS segments {first column, first contig index, first germline column, op |
-//                 region << 2} in a fixed order -- V's runs 0 .. 63, np1 64, D's runs 65 .. 128, np2 129, J's runs 130 .. 193.  A slot
-//                 without a run is empty at its section's end, so the first columns (and, inside V, the germline columns) ascend over the
-//                 whole table and the segment of a column is the LAST slot that starts at or before it.  A clipped J loses its first jdrop
-//                 columns: a run wholly inside them becomes empty, the run they end in is trimmed.
+//     table       one lane per run of V, then of D, then of J (vh_hit_segments per hit) gives the segment table in LDS: MU_SLOTS segments
+//                 {first column, first contig index, first germline column, op | region << 2} in a fixed order -- V's runs 0 .. 63, np1 64,
+//                 D's runs 65 .. 128, np2 129, J's runs 130 .. 193.  A slot without a run is empty at its section's end, so the first
+//                 columns (and, inside V, the germline columns) ascend over the whole table and the segment of a column is the LAST slot
+//                 that starts at or before it.  A clipped J loses its first jdrop columns.
 //     rows        the columns are striped over the lanes (column = lane + 64 k); a lane finds its segment by a binary search of the table,
 //                 reads its contig character and germline code and writes one byte of each row: 64 consecutive bytes per store.  It counts
 //                 the V M columns below the limit that mismatch, and J's mismatches.
-//     codons      a lane per V germline codon; its three bases go to columns through the same table (searched by germline column); a
-//                 classifiable codon's differences are classified through a 64-entry amino-acid table in LDS.
+//     codons      a lane per V germline codon; its three bases go to columns through the same table (vh_codon: searched by germline
+//                 column); a classifiable codon's differences are classified through a 64-entry amino-acid table in LDS.
 //     row         the counts are reduced across the wave by shuffles (v_na = the mismatches below the limit - the classified ones); lane 0
 //                 writes the 32-byte row as two 16-byte stores.
 // No floating point, no atomics, no scratch.
-#include "vdjx_common.h"
-
-#include <algorithm>
-#include <string.h>
+#include "vdjx_vhit.h"
 
 #define MU_WAVES 4
 #define MU_V0 0
@@ -50,28 +48,6 @@ struct MuContig {
 };
 static_assert(sizeof(MuContig) == 64 && sizeof(vdjx_mut_row) == 32 && sizeof(vdjx_mut_info) == 72, "uploaded / returned as they are");
 
-// the standard genetic code, codon 16 a + 4 b + c with A 0, C 1, G 2, T 3
-__constant__ char mu_aa[65] = "KNKNTTTTRSRSIIMIQHQHPPPPRRRRLLLLEDEDAAAAGGGGVVVV*Y*YSSSS*CWCLFLF";
-
-__device__ __forceinline__ int mu_ccode(char ch) { return ch == 'A' ? 0 : ch == 'C' ? 1 : ch == 'G' ? 2 : ch == 'T' ? 3 : 4; }
-
-__device__ __forceinline__ int mu_excl(int v, u32 lane, int& total) {      // exclusive prefix sum over the wave
-	int s = v;
-#pragma unroll
-	for (int o = 1; o < 64; o <<= 1) {
-		const int t = __shfl_up(s, o, 64);
-		if ((int) lane >= o) s += t;
-	}
-	total = __shfl(s, 63, 64);
-	return s - v;
-}
-
-__device__ __forceinline__ int mu_sum(int v) {
-#pragma unroll
-	for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-	return v;
-}
-
 __global__ __launch_bounds__(64 * MU_WAVES) void k_mutations(const char* __restrict__ contigs, u32 n, u32 len, const MuContig* __restrict__ mc,
                                                             const u32* __restrict__ runs, const uint8_t* __restrict__ gcols,
                                                             const uint8_t* __restrict__ dcols, char* __restrict__ out_seq,
@@ -83,7 +59,7 @@ __global__ __launch_bounds__(64 * MU_WAVES) void k_mutations(const char* __restr
 	if (c >= n) return;                  // (a whole wave; nothing below waits for the others)
 	int4* seg = seg_all[w];
 	char* aa = aa_all[w];
-	aa[lane] = mu_aa[lane];
+	aa[lane] = vh_aa[lane];
 	const MuContig q = mc[c];
 	const char* ct = contigs + (size_t) c * len;
 	const int nr[3] = {(int) (q.nruns & 255u), (int) (q.nruns >> 8 & 255u), (int) (q.nruns >> 16 & 255u)};
@@ -93,20 +69,9 @@ __global__ __launch_bounds__(64 * MU_WAVES) void k_mutations(const char* __restr
 	int colbase = 0, vgerm = 0, roff = 0;
 #pragma unroll
 	for (int h = 0; h < 3; h++) {
-		const bool live = (int) lane < nr[h];
-		const u32 r = live ? runs[q.run_off + (u32) roff + lane] : 0u;
-		const int L = (int) (r >> 4), op = (int) (r & 15u);
-		int tc, tb, tg;
-		const int ec = mu_excl(L, lane, tc), eb = mu_excl(op != 2 ? L : 0, lane, tb), eg = mu_excl(op != 1 ? L : 0, lane, tg);
 		const int drop = h == 2 ? q.jdrop : 0;
-		const int keep = max(0, min(L, ec + L - drop)), trim = L - keep;      // (a run wholly inside the dropped columns keeps nothing)
-		int4 s;
-		s.x = colbase + max(ec - drop, 0);
-		s.y = seq0[h] + eb + (op != 2 ? trim : 0);
-		s.z = (int) at0[h] + eg + (op != 1 ? trim : 0);
-		s.w = op | (h == 0 ? 0 : h == 1 ? 4 : 8);
-		if (!live) s = make_int4(colbase + tc - drop, seq0[h] + tb, (int) at0[h] + tg, s.w);
-		seg[slot0[h] + (int) lane] = s;
+		int tc, tb, tg;
+		seg[slot0[h] + (int) lane] = vh_hit_segments(runs, q.run_off + (u32) roff, nr[h], lane, colbase, seq0[h], (int) at0[h], drop, h, tc, tb, tg);
 		colbase += tc - drop;
 		roff += nr[h];
 		if (h == 0) {
@@ -142,7 +107,7 @@ __global__ __launch_bounds__(64 * MU_WAVES) void k_mutations(const char* __restr
 			code = (region == 1 ? dcols : gcols)[(u32) s.z + (u32) off];
 			g = code == 0 ? 'A' : code == 1 ? 'C' : code == 2 ? 'G' : code == 3 ? 'T' : 'N';
 		}
-		if (op == 0 && mu_ccode(a) != code) {
+		if (op == 0 && vh_ccode(a) != code) {
 			if (region == 0 && s.y + off < q.limit) vmis++;
 			if (region == 2) jmis++;
 		}
@@ -156,49 +121,29 @@ __global__ __launch_bounds__(64 * MU_WAVES) void k_mutations(const char* __restr
 
 	// the codons of the record that lie inside germ_start .. germ_end
 	int vr = 0, vs = 0, vstop = 0, ncod = 0;
-	const int c_lo = (q.v_germ0 + 2) / 3, c_hi = (q.v_germ0 + vgerm) / 3;       // codons c_lo .. c_hi - 1
+	int c_lo, c_hi;
+	vh_codon_range(q.v_germ0, vgerm, c_lo, c_hi);
 	for (int cd = c_lo + (int) lane; cd < c_hi; cd += 64) {
-		int colb[3], cb[3], gb[3];
-		bool ok = true;
-#pragma unroll
-		for (int b = 0; b < 3; b++) {
-			const int ga = (int) q.v_at + 3 * cd + b - q.v_germ0;      // the base's column in the germline set
-			int lo = 0, hi = 64;             // the last V slot whose first germline column is <= ga (an I run shares the next run's)
-			while (hi - lo > 1) {
-				const int mid = (lo + hi) >> 1;
-				if (seg[mid].z <= ga) lo = mid; else hi = mid;
-			}
-			const int4 s = seg[lo];
-			const int off = ga - s.z;
-			ok = ok && (s.w & 3) == 0;
-			colb[b] = s.x + off;
-			const int pos = s.y + off;
-			ok = ok && pos < q.limit;
-			cb[b] = ok ? mu_ccode(ct[pos]) : 4;      // (pos is inside the contig whenever the slot is an M run)
-			gb[b] = gcols[ga];
-			ok = ok && cb[b] < 4 && gb[b] < 4;
-		}
-		ok = ok && colb[1] == colb[0] + 1 && colb[2] == colb[1] + 1;
-		if (!ok) continue;
+		int cb[3], gb[3];
+		if (!vh_codon(seg, ct, gcols, q.v_at, q.v_germ0, q.limit, cd, cb, gb)) continue;
 		ncod++;
 		const int gc = 16 * gb[0] + 4 * gb[1] + gb[2];
 		const char ga_ = aa[gc];
 #pragma unroll
 		for (int b = 0; b < 3; b++) {
 			if (cb[b] == gb[b]) continue;
-			const int sh = 4 - 2 * b;
-			const char ma = aa[(gc & ~(3 << sh)) | (cb[b] << sh)];
+			const char ma = vh_subst_aa(aa, gc, b, cb[b]);
 			if (ga_ == '*' || ma == '*') vstop++;
 			else if (ga_ == ma) vs++;
 			else vr++;
 		}
 	}
-	vmis = mu_sum(vmis);
-	jmis = mu_sum(jmis);
-	vr = mu_sum(vr);
-	vs = mu_sum(vs);
-	vstop = mu_sum(vstop);
-	ncod = mu_sum(ncod);
+	vmis = vdjx_wave_sum(vmis);
+	jmis = vdjx_wave_sum(jmis);
+	vr = vdjx_wave_sum(vr);
+	vs = vdjx_wave_sum(vs);
+	vstop = vdjx_wave_sum(vstop);
+	ncod = vdjx_wave_sum(ncod);
 	if (lane == 0) {
 		out_rows[2 * (size_t) c] = make_int4(cols, vr, vs, vstop);
 		out_rows[2 * (size_t) c + 1] = make_int4(vmis - vr - vs - vstop, ncod, jmis, (int) q.flags);
@@ -206,37 +151,21 @@ __global__ __launch_bounds__(64 * MU_WAVES) void k_mutations(const char* __restr
 }
 
 // ---- the host's side: the checks and the layout ----------------------------------------------------------------------------------------
-static inline bool mu_called(const vdjx_annot_hit& h) { return h.gene >= 0 && h.score > 0; }
-static inline bool mu_usable(const vdjx_annot_hit& h) { return mu_called(h) && h.n_runs <= VDJX_ANNOT_RUNS; }
-
-// the runs of a usable hit: columns, contig bases (M + I), germline bases (M + D); false: an op outside 0..2 or a length of 0
-static bool mu_sums(const vdjx_annot_hit& h, int64_t& ncol, int64_t& nseq, int64_t& ngerm) {
-	ncol = nseq = ngerm = 0;
-	for (int r = 0; r < h.n_runs; r++) {
-		const u32 L = h.runs[r] >> 4, op = h.runs[r] & 15u;
-		if (op > 2 || L == 0) return false;
-		ncol += L;
-		if (op != 2) nseq += L;
-		if (op != 1) ngerm += L;
-	}
-	return true;
-}
-
 struct MuPlan { u32 flags; u32 truncated; int64_t cols; int jdrop, gap, np1; bool use_d; };
 
 // contig i's plan from its hits alone (d may be NULL); false: a run with an op outside 0..2 or a length of 0
 static bool mu_plan(const vdjx_annot_hit& v, const vdjx_annot_hit* d, const vdjx_annot_hit& j, MuPlan& p) {
 	memset(&p, 0, sizeof p);
-	p.truncated = (u32) (mu_called(v) && !mu_usable(v)) + (u32) (mu_called(j) && !mu_usable(j)) + (u32) (d && mu_called(*d) && !mu_usable(*d));
+	p.truncated = (u32) (vh_called(v) && !vh_usable(v)) + (u32) (vh_called(j) && !vh_usable(j)) + (u32) (d && vh_called(*d) && !vh_usable(*d));
 	if (p.truncated) p.flags |= 16;
 	int64_t vc, vs, vg, jc = 0, js = 0, jg = 0, dc = 0, ds = 0, dg = 0;
-	if (mu_usable(v) && !mu_sums(v, vc, vs, vg)) return false;
-	if (mu_usable(j) && !mu_sums(j, jc, js, jg)) return false;
-	if (d && mu_usable(*d) && !mu_sums(*d, dc, ds, dg)) return false;
-	if (!mu_usable(v)) return true;
+	if (vh_usable(v) && !vh_run_sums(v, vc, vs, vg)) return false;
+	if (vh_usable(j) && !vh_run_sums(j, jc, js, jg)) return false;
+	if (d && vh_usable(*d) && !vh_run_sums(*d, dc, ds, dg)) return false;
+	if (!vh_usable(v)) return true;
 	p.flags |= 1;
 	p.cols = vc;
-	if (!mu_usable(j)) return true;
+	if (!vh_usable(j)) return true;
 	int64_t kept = jc;
 	if (j.seq_start <= v.seq_end) {          // clipped: up to the column of contig position v.seq_end + 1
 		p.flags |= 8;
@@ -257,7 +186,7 @@ static bool mu_plan(const vdjx_annot_hit& v, const vdjx_annot_hit* d, const vdjx
 	} else p.gap = j.seq_start - 1 - v.seq_end;
 	p.flags |= 2;
 	p.np1 = p.gap;
-	if (d && mu_usable(*d) && d->seq_start > v.seq_end && d->seq_end <= v.seq_end + p.gap) {
+	if (d && vh_usable(*d) && d->seq_start > v.seq_end && d->seq_end <= v.seq_end + p.gap) {
 		p.flags |= 4;
 		p.use_d = true;
 		p.np1 = d->seq_start - v.seq_end - 1;
@@ -283,33 +212,10 @@ extern "C" int vdjx_mutations_layout(const vdjx_annot_hit* v, const vdjx_annot_h
 
 // a usable hit of contig i against its record set: *at = the column of its base germ_start.  what: "V", "D", "J"
 static int mu_check(const char* what, size_t i, const vdjx_annot_hit& h, const vdjx_recset& s, int cls, int len, u32* at) {
-	const std::vector<u32>& rec = s.rec[cls];
-	const size_t slot = std::lower_bound(rec.begin(), rec.end(), (u32) h.gene) - rec.begin();
-	if (slot >= rec.size() || rec[slot] != (u32) h.gene) {
-		vdjx_set_error("vdjx_mutations: contig %zu: the %s hit's gene %d is not a %s record of the loaded set", i, what, h.gene, what);
-		return VDJX_EINVAL;
-	}
-	int64_t nc, ns, ng;
-	if (h.n_runs < 0 || !mu_sums(h, nc, ns, ng)) {
-		vdjx_set_error("vdjx_mutations: contig %zu: the %s hit has a run with an op outside 0..2 or a length of 0 (n_runs %d)", i, what, h.n_runs);
-		return VDJX_EINVAL;
-	}
-	if (h.seq_start < 1 || h.germ_start < 1 || h.seq_end > len || (int64_t) h.germ_end > (int64_t) s.len[cls][slot]) {
-		vdjx_set_error("vdjx_mutations: contig %zu: the %s hit's contig positions %d .. %d (1 .. %d) or germline positions %d .. %d (1 .. %u)",
-		               i, what, h.seq_start, h.seq_end, len, h.germ_start, h.germ_end, s.len[cls][slot]);
-		return VDJX_EINVAL;
-	}
-	if (ns != (int64_t) h.seq_end - h.seq_start + 1 || ng != (int64_t) h.germ_end - h.germ_start + 1) {
-		vdjx_set_error("vdjx_mutations: contig %zu: the %s hit's runs hold %lld contig and %lld germline bases, its positions %d .. %d and %d .. %d",
-		               i, what, (long long) ns, (long long) ng, h.seq_start, h.seq_end, h.germ_start, h.germ_end);
-		return VDJX_EINVAL;
-	}
-	if (s.at[cls][slot] + (u64) s.len[cls][slot] >= (1ull << 31)) {
-		vdjx_set_error("vdjx_mutations: contig %zu: the %s record lies past 2^31 columns of its set", i, what);
-		return VDJX_EINVAL;
-	}
-	*at = (u32) (s.at[cls][slot] + (u64) h.germ_start);      // (at: the record's reset column; its base 1 follows)
-	return VDJX_OK;
+	size_t slot = 0;
+	const int rc = vh_check("vdjx_mutations", what, i, h, s, cls, len, &slot);
+	if (rc == VDJX_OK) *at = (u32) (s.at[cls][slot] + (u64) h.germ_start);      // (at: the record's reset column; its base 1 follows)
+	return rc;
 }
 
 extern "C" int vdjx_mutations(vdjx_ctx* c, const char* contigs, size_t n, int len, const vdjx_annot_hit* v, const vdjx_annot_hit* d,
@@ -319,13 +225,9 @@ extern "C" int vdjx_mutations(vdjx_ctx* c, const char* contigs, size_t n, int le
 	if (!c) { vdjx_set_error("vdjx_mutations: NULL argument"); return VDJX_EINVAL; }
 	if (n == 0) return VDJX_OK;
 	if (!contigs || !v || !j || !out_rows) { vdjx_set_error("vdjx_mutations: NULL argument"); return VDJX_EINVAL; }
-	if (len < 1 || len >= 4096) { vdjx_set_error("vdjx_mutations: len=%d (1 .. 4095)", len); return VDJX_EINVAL; }
-	if (n >= (1ull << 20)) { vdjx_set_error("vdjx_mutations: %zu contigs (at most 2^20 - 1 per call)", n); return VDJX_EINVAL; }
-	if (memchr(contigs, 0, n * (size_t) len)) {
-		vdjx_set_error("vdjx_mutations: contigs of unequal length (a NUL inside the %zu x %d characters)", n, len);
-		return VDJX_EINVAL;
-	}
-	if (!c->germline.loaded) { vdjx_set_error("vdjx_mutations: no germline set is loaded (call vdjx_germline_load first)"); return VDJX_ESTATE; }
+	int rc = vh_check_sizes("vdjx_mutations", n, len);
+	if (rc == VDJX_OK) rc = vh_check_contigs("vdjx_mutations", c, contigs, n, len);
+	if (rc != VDJX_OK) return rc;
 	if (d && !c->dsegment.loaded) { vdjx_set_error("vdjx_mutations: D hits are given and no D set is loaded (call vdjx_dsegment_load first)"); return VDJX_ESTATE; }
 	const auto t0 = std::chrono::steady_clock::now();
 	std::vector<MuContig> mc(n);
@@ -338,10 +240,10 @@ extern "C" int vdjx_mutations(vdjx_ctx* c, const char* contigs, size_t n, int le
 		MuContig& q = mc[i];
 		memset(&q, 0, sizeof q);
 		u32 at[3] = {0, 0, 0};
-		int rc = VDJX_OK;
-		if (mu_usable(v[i])) rc = mu_check("V", i, v[i], c->germline, 0, len, &at[0]);
-		if (rc == VDJX_OK && d && mu_usable(d[i])) rc = mu_check("D", i, d[i], c->dsegment, 0, len, &at[1]);
-		if (rc == VDJX_OK && mu_usable(j[i])) rc = mu_check("J", i, j[i], c->germline, 1, len, &at[2]);
+		rc = VDJX_OK;
+		if (vh_usable(v[i])) rc = mu_check("V", i, v[i], c->germline, 0, len, &at[0]);
+		if (rc == VDJX_OK && d && vh_usable(d[i])) rc = mu_check("D", i, d[i], c->dsegment, 0, len, &at[1]);
+		if (rc == VDJX_OK && vh_usable(j[i])) rc = mu_check("J", i, j[i], c->germline, 1, len, &at[2]);
 		if (rc != VDJX_OK) return rc;
 		MuPlan p;
 		mu_plan(v[i], d ? d + i : nullptr, j[i], p);          // (the runs passed mu_check)

@@ -4,12 +4,13 @@
 //                    and the posterior of the selection strength sigma per contig, per group and for all contigs (the model:
 //                    include/vdjx.h; in Python: tests/selection_model.py)
 //
-// The hits are the caller's, so the host checks every one of them before anything reaches the device, as vdjx_mutations does (sel_check):
-// every index k_sel_counts forms lies inside the contig and the record.
-//   k_sel_counts   one dispatch; a wave per contig, SEL_WAVES waves per workgroup, no barrier between the waves.  The V segment table of
-//                  k_mutations (its V part: 64 slots) in LDS, a lane per germline codon.  Per base of a classifiable codon: the region of
-//                  its germline position, the observed class, and -- the germline codon not being a stop -- the three other bases through
-//                  the amino-acid table, weighted by the 5-mer around the base in the RECORD (germline.d_cols; the record's bounds are
+// The hits are the caller's, so the host checks every one of them before anything reaches the device with the check vdjx_mutations uses
+// (vh_check of vdjx_vhit.h): every index k_sel_counts forms lies inside the contig and the record.  The V segment table and the codon
+// resolver are that header's too, so the two calls classify the same codons; what is here is what a resolved codon counts as.
+//   k_sel_counts   one dispatch; a wave per contig, SEL_WAVES waves per workgroup, no barrier between the waves.  The V section of
+//                  k_mutations' segment table (vh_hit_segments: 64 slots) in LDS, a lane per germline codon (vh_codon).  Per base of a
+//                  classifiable codon: the region of its germline position, the observed class, and -- the germline codon not being a
+//                  stop -- the three other bases through the amino-acid table, weighted by the 5-mer around the base in the RECORD (germline.d_cols; the record's bounds are
 //                  checked, its neighbours in the set are never read as context).  The 1024 x 4 weights stay in global memory: a position
 //                  reads the 16 bytes of its 5-mer with one load, a contig of 100 codons reads 4.8 KB of a 16 KB table that every wave
 //                  shares, so it lives in L2 and the vector cache; staging it in LDS would cost every workgroup of four contigs the whole
@@ -21,11 +22,9 @@
 //                  order, plus the prior; the block maximum, f = exp(l - max), a block scan for the CDF (a thread owns 16 consecutive grid
 //                  points), the two quantile indices, sigma and p_positive; one 72-byte stat and, where asked, the density.
 // No float atomics; every sum runs in a fixed order, so two calls with the same VDJX_SEL_CHUNK give the same bits.
-#include "vdjx_common.h"
+#include "vdjx_vhit.h"
 
-#include <algorithm>
 #include <math.h>
-#include <string.h>
 
 #define SEL_WAVES 4
 #define SEL_T VDJX_SEL_GRID
@@ -57,37 +56,6 @@ struct SelItem { u32 start, count, part, region; };    // a chunk of a large row
 static_assert(sizeof(SelContig) == 64 && sizeof(vdjx_sel_counts) == 64 && sizeof(vdjx_sel_stat) == 72 && sizeof(SelMember) == 16 && sizeof(SelRow) == 56,
               "uploaded / returned as they are");
 
-// the standard genetic code, codon 16 a + 4 b + c with A 0, C 1, G 2, T 3
-__constant__ char sel_aa[65] = "KNKNTTTTRSRSIIMIQHQHPPPPRRRRLLLLEDEDAAAAGGGGVVVV*Y*YSSSS*CWCLFLF";
-
-__device__ __forceinline__ int sel_ccode(char ch) { return ch == 'A' ? 0 : ch == 'C' ? 1 : ch == 'G' ? 2 : ch == 'T' ? 3 : 4; }
-
-__device__ __forceinline__ int sel_excl(int v, u32 lane, int& total) {      // exclusive prefix sum over the wave
-	int s = v;
-#pragma unroll
-	for (int o = 1; o < 64; o <<= 1) {
-		const int t = __shfl_up(s, o, 64);
-		if ((int) lane >= o) s += t;
-	}
-	total = __shfl(s, 63, 64);
-	return s - v;
-}
-
-__device__ __forceinline__ int sel_sum(int v) {
-#pragma unroll
-	for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-	return v;
-}
-
-__device__ __forceinline__ u64 sel_sum64(u64 v) {
-#pragma unroll
-	for (int o = 32; o >= 1; o >>= 1) {
-		const u32 lo = (u32) __shfl_xor((int) (u32) v, o, 64), hi = (u32) __shfl_xor((int) (u32) (v >> 32), o, 64);
-		v += (u64) hi << 32 | lo;
-	}
-	return v;
-}
-
 __global__ __launch_bounds__(64 * SEL_WAVES) void k_sel_counts(const char* __restrict__ contigs, u32 n, u32 len, const SelContig* __restrict__ sc,
                                                               const u32* __restrict__ runs, const uint8_t* __restrict__ gcols,
                                                               const uint4* __restrict__ weight, int4* __restrict__ out) {
@@ -98,47 +66,22 @@ __global__ __launch_bounds__(64 * SEL_WAVES) void k_sel_counts(const char* __res
 	if (c >= n) return;                  // (a whole wave; nothing below waits for the others)
 	int4* seg = seg_all[w];
 	char* aa = aa_all[w];
-	aa[lane] = sel_aa[lane];
+	aa[lane] = vh_aa[lane];
 	const SelContig q = sc[c];
 	const char* ct = contigs + (size_t) c * len;
-	const int nr = (int) q.nruns;
-	// the V segment table: {first column, first contig index, first germline column, op}; a slot without a run is empty at the end
-	const bool live = (int) lane < nr;
-	const u32 r = live ? runs[q.run_off + lane] : 0u;
-	const int L = (int) (r >> 4), op = (int) (r & 15u);
-	int tc, tb, tg;
-	const int ec = sel_excl(L, lane, tc), eb = sel_excl(op != 2 ? L : 0, lane, tb), eg = sel_excl(op != 1 ? L : 0, lane, tg);
-	seg[lane] = live ? make_int4(ec, q.v_seq0 + eb, (int) q.v_at + eg, op) : make_int4(tc, q.v_seq0 + tb, (int) q.v_at + tg, 0);
-	const int vgerm = tg;
+	// the V segment table, as k_mutations lays its V section: the hit starts at column 0, nothing is dropped
+	int tc, tb, vgerm;
+	seg[lane] = vh_hit_segments(runs, q.run_off, (int) q.nruns, lane, 0, q.v_seq0, (int) q.v_at, 0, 0, tc, tb, vgerm);
 	vdjx_wave_lds_fence();               // the table and the amino acids are read by other lanes of the wave
 
 	int obs_r[2] = {0, 0}, obs_s[2] = {0, 0}, ncod[2] = {0, 0};
 	u64 exp_r[2] = {0, 0}, exp_s[2] = {0, 0};
-	const int c_lo = (q.v_germ0 + 2) / 3, c_hi = (q.v_germ0 + vgerm) / 3;       // codons c_lo .. c_hi - 1, as k_mutations takes them
+	int c_lo, c_hi;
+	vh_codon_range(q.v_germ0, vgerm, c_lo, c_hi);
 	const int rlen = (int) q.rec_len;
 	for (int cd = c_lo + (int) lane; cd < c_hi; cd += 64) {
-		int colb[3], cb[3], gb[3];
-		bool ok = true;
-#pragma unroll
-		for (int b = 0; b < 3; b++) {
-			const int ga = (int) q.v_at + 3 * cd + b - q.v_germ0;      // the base's column in the germline set
-			int lo = 0, hi = 64;             // the last slot whose first germline column is <= ga (an I run shares the next run's)
-			while (hi - lo > 1) {
-				const int mid = (lo + hi) >> 1;
-				if (seg[mid].z <= ga) lo = mid; else hi = mid;
-			}
-			const int4 s = seg[lo];
-			const int off = ga - s.z;
-			ok = ok && (s.w & 3) == 0;
-			colb[b] = s.x + off;
-			const int pos = s.y + off;
-			ok = ok && pos < q.limit;
-			cb[b] = ok ? sel_ccode(ct[pos]) : 4;      // (pos is inside the contig whenever the slot is an M run)
-			gb[b] = gcols[ga];
-			ok = ok && cb[b] < 4 && gb[b] < 4;
-		}
-		ok = ok && colb[1] == colb[0] + 1 && colb[2] == colb[1] + 1;
-		if (!ok) continue;
+		int cb[3], gb[3];
+		if (!vh_codon(seg, ct, gcols, q.v_at, q.v_germ0, q.limit, cd, cb, gb)) continue;
 		const int gc = 16 * gb[0] + 4 * gb[1] + gb[2];
 		const char ga_ = aa[gc];
 #pragma unroll
@@ -147,9 +90,8 @@ __global__ __launch_bounds__(64 * SEL_WAVES) void k_sel_counts(const char* __res
 			const int p1 = p + 1;
 			const int reg = (p1 >= q.cdr[0] && p1 <= q.cdr[1]) || (p1 >= q.cdr[2] && p1 <= q.cdr[3]) ? 1 : 0;
 			if (b == 0) ncod[reg]++;             // a codon belongs to the region of its first base
-			const int sh = 4 - 2 * b;
 			if (cb[b] != gb[b]) {
-				const char ma = aa[(gc & ~(3 << sh)) | (cb[b] << sh)];
+				const char ma = vh_subst_aa(aa, gc, b, cb[b]);
 				if (ga_ != '*' && ma != '*') {
 					if (ga_ == ma) obs_s[reg]++; else obs_r[reg]++;
 				}
@@ -167,7 +109,7 @@ __global__ __launch_bounds__(64 * SEL_WAVES) void k_sel_counts(const char* __res
 #pragma unroll
 			for (int alt = 0; alt < 4; alt++) {
 				if (alt == gb[b]) continue;
-				const char ma = aa[(gc & ~(3 << sh)) | (alt << sh)];
+				const char ma = vh_subst_aa(aa, gc, b, alt);
 				if (ma == '*') continue;
 				if (ma == ga_) exp_s[reg] += wt[alt]; else exp_r[reg] += wt[alt];
 			}
@@ -175,11 +117,11 @@ __global__ __launch_bounds__(64 * SEL_WAVES) void k_sel_counts(const char* __res
 	}
 #pragma unroll
 	for (int k = 0; k < 2; k++) {
-		obs_r[k] = sel_sum(obs_r[k]);
-		obs_s[k] = sel_sum(obs_s[k]);
-		ncod[k] = sel_sum(ncod[k]);
-		exp_r[k] = sel_sum64(exp_r[k]);
-		exp_s[k] = sel_sum64(exp_s[k]);
+		obs_r[k] = vdjx_wave_sum(obs_r[k]);
+		obs_s[k] = vdjx_wave_sum(obs_s[k]);
+		ncod[k] = vdjx_wave_sum(ncod[k]);
+		exp_r[k] = vdjx_wave_sum64(exp_r[k]);
+		exp_s[k] = vdjx_wave_sum64(exp_s[k]);
 	}
 	if (lane == 0) {
 		int4* o = out + 4 * (size_t) c;
@@ -215,9 +157,7 @@ __global__ __launch_bounds__(256) void k_sel_loglik(const SelMember* __restrict_
 }
 
 __device__ __forceinline__ double sel_shfl_xor(double v, int o) {
-	const long long b = __double_as_longlong(v);
-	const u32 lo = (u32) __shfl_xor((int) (u32) b, o, 64), hi = (u32) __shfl_xor((int) (u32) ((u64) b >> 32), o, 64);
-	return __longlong_as_double((long long) ((u64) hi << 32 | lo));
+	return __longlong_as_double((long long) vdjx_shfl_xor64((u64) __double_as_longlong(v), o));
 }
 
 // the block's sum / maximum of one value per thread, in a fixed order: inside a wave by a butterfly, the four waves in order
@@ -338,47 +278,6 @@ __global__ __launch_bounds__(256) void k_sel_finish(const SelMember* __restrict_
 }
 
 // ---- the host's side -------------------------------------------------------------------------------------------------------------------------
-static inline bool sel_called(const vdjx_annot_hit& h) { return h.gene >= 0 && h.score > 0; }
-static inline bool sel_usable(const vdjx_annot_hit& h) { return sel_called(h) && h.n_runs <= VDJX_ANNOT_RUNS; }
-
-// a usable V hit of contig i against the loaded set, by vdjx_mutations' rules: *slot = its record's place among the V records
-static int sel_check(size_t i, const vdjx_annot_hit& h, const vdjx_recset& s, int len, size_t* slot_out) {
-	const std::vector<u32>& rec = s.rec[0];
-	const size_t slot = std::lower_bound(rec.begin(), rec.end(), (u32) h.gene) - rec.begin();
-	if (slot >= rec.size() || rec[slot] != (u32) h.gene) {
-		vdjx_set_error("vdjx_selection: contig %zu: the V hit's gene %d is not a V record of the loaded set", i, h.gene);
-		return VDJX_EINVAL;
-	}
-	int64_t ns = 0, ng = 0;
-	bool ok = h.n_runs >= 0;
-	for (int r = 0; ok && r < h.n_runs; r++) {
-		const u32 L = h.runs[r] >> 4, op = h.runs[r] & 15u;
-		if (op > 2 || L == 0) ok = false;
-		if (op != 2) ns += L;
-		if (op != 1) ng += L;
-	}
-	if (!ok) {
-		vdjx_set_error("vdjx_selection: contig %zu: the V hit has a run with an op outside 0..2 or a length of 0 (n_runs %d)", i, h.n_runs);
-		return VDJX_EINVAL;
-	}
-	if (h.seq_start < 1 || h.germ_start < 1 || h.seq_end > len || (int64_t) h.germ_end > (int64_t) s.len[0][slot]) {
-		vdjx_set_error("vdjx_selection: contig %zu: the V hit's contig positions %d .. %d (1 .. %d) or germline positions %d .. %d (1 .. %u)", i,
-		               h.seq_start, h.seq_end, len, h.germ_start, h.germ_end, s.len[0][slot]);
-		return VDJX_EINVAL;
-	}
-	if (ns != (int64_t) h.seq_end - h.seq_start + 1 || ng != (int64_t) h.germ_end - h.germ_start + 1) {
-		vdjx_set_error("vdjx_selection: contig %zu: the V hit's runs hold %lld contig and %lld germline bases, its positions %d .. %d and %d .. %d", i,
-		               (long long) ns, (long long) ng, h.seq_start, h.seq_end, h.germ_start, h.germ_end);
-		return VDJX_EINVAL;
-	}
-	if (s.at[0][slot] + (u64) s.len[0][slot] >= (1ull << 31)) {
-		vdjx_set_error("vdjx_selection: contig %zu: the V record lies past 2^31 columns of its set", i);
-		return VDJX_EINVAL;
-	}
-	*slot_out = slot;
-	return VDJX_OK;
-}
-
 extern "C" int vdjx_selection(vdjx_ctx* c, const char* contigs, size_t n, int len, const vdjx_annot_hit* v, const int32_t* limit, const int32_t* cdr,
                               size_t n_records, const uint32_t* weight, const int32_t* group, uint32_t G, vdjx_sel_counts* out_counts,
                               vdjx_sel_stat* out_stat, double* out_pdf, vdjx_sel_info* info) {
@@ -386,16 +285,13 @@ extern "C" int vdjx_selection(vdjx_ctx* c, const char* contigs, size_t n, int le
 	if (!c) { vdjx_set_error("vdjx_selection: NULL argument"); return VDJX_EINVAL; }
 	if (n == 0) return VDJX_OK;
 	if (!contigs || !v || !out_counts || !out_stat) { vdjx_set_error("vdjx_selection: NULL argument"); return VDJX_EINVAL; }
-	if (len < 1 || len >= 4096) { vdjx_set_error("vdjx_selection: len=%d (1 .. 4095)", len); return VDJX_EINVAL; }
-	if (n >= (1ull << 20)) { vdjx_set_error("vdjx_selection: %zu contigs (at most 2^20 - 1 per call)", n); return VDJX_EINVAL; }
+	int rc = vh_check_sizes("vdjx_selection", n, len);
+	if (rc != VDJX_OK) return rc;
 	if (G >= (1u << 20)) { vdjx_set_error("vdjx_selection: %u groups (at most 2^20 - 1)", G); return VDJX_EINVAL; }
 	if (G && !group) { vdjx_set_error("vdjx_selection: %u groups and no group array", G); return VDJX_EINVAL; }
 	if (out_pdf && (u64) G + 1 > 65536) { vdjx_set_error("vdjx_selection: densities of %u groups and the sample (at most 65536 rows)", G); return VDJX_EINVAL; }
-	if (memchr(contigs, 0, n * (size_t) len)) {
-		vdjx_set_error("vdjx_selection: contigs of unequal length (a NUL inside the %zu x %d characters)", n, len);
-		return VDJX_EINVAL;
-	}
-	if (!c->germline.loaded) { vdjx_set_error("vdjx_selection: no germline set is loaded (call vdjx_germline_load first)"); return VDJX_ESTATE; }
+	rc = vh_check_contigs("vdjx_selection", c, contigs, n, len);
+	if (rc != VDJX_OK) return rc;
 	const vdjx_recset& gs = c->germline;
 	if (cdr) {
 		if (n_records != gs.given) {
@@ -429,10 +325,10 @@ extern "C" int vdjx_selection(vdjx_ctx* c, const char* contigs, size_t n, int le
 		memset(&q, 0, sizeof q);
 		q.limit = lim;
 		q.run_off = (u32) runs.size();
-		if (sel_called(v[i]) && !sel_usable(v[i])) { q.flags = 16; truncated++; continue; }
-		if (!sel_usable(v[i])) continue;
+		if (vh_called(v[i]) && !vh_usable(v[i])) { q.flags = 16; truncated++; continue; }
+		if (!vh_usable(v[i])) continue;
 		size_t slot = 0;
-		const int rc = sel_check(i, v[i], gs, len, &slot);
+		rc = vh_check("vdjx_selection", "V", i, v[i], gs, 0, len, &slot);
 		if (rc != VDJX_OK) return rc;
 		if (cdr) {
 			const int32_t* iv = cdr + 4 * (size_t) v[i].gene;

@@ -706,6 +706,54 @@ int vdjx_selection(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const 
                    vdjx_sel_counts* out_counts /* n */, vdjx_sel_stat* out_stat /* (n + G + 1) * K, row-major */,
                    double* out_pdf /* NULL, or (G + 1) * K * 4001: the group rows, then the sample row */, vdjx_sel_info* info);
 
+/* ---- the sample's own 5-mer targeting model: which 5-mers mutate, and to which base (S5F) ---------------------------------------------
+ * gives `vdjer --targeting-model` what shazam's createTargetingModel (createSubstitutionMatrix, createMutabilityMatrix,
+ * createTargetingMatrix) makes of the sample in a second tool: the weights vdjx_selection takes, learnt from the V segments at hand.
+ * Everything on the device is integer: its counts are bitwise the model's (tests/targeting_model.py).
+ *   inputs      contigs, n, len, v[n], limit[n] and group[n] as vdjx_selection takes them; no region map, no weights, no G: any group[i]
+ *               >= 0 is a group, a negative one (or group == NULL) leaves the contig on its own.  A hit with more than 64 runs is treated
+ *               as absent (info->truncated).
+ *   units       a unit is a pair (group, V record); a contig in no group is a unit of its own.  A unit owns 4 bits per 0-based record
+ *               position p.
+ *   marking     for every contig, every codon vdjx_mutations classifies (limit included) whose germline codon is not a stop, and every base
+ *               p of it that has a 5-mer -- vdjx_selection's rule: p >= 2, p + 2 < the record's length, the four neighbours in the RECORD
+ *               are ACGT -- with gb the germline's and cb the contig's base code (A 0, C 1, G 2, T 3): bit gb of p is set ("seen"); if cb !=
+ *               gb and the germline codon with this ONE base replaced is not a stop, bit cb of p is set.  Each base is judged on its own.
+ *   counting    out[kind][class][m][x], kind 0 observed, 1 opportunity; class 0 silent, 1 replacement; m = idx5(p) as vdjx_selection forms
+ *               it; x the new base.  For every seen p of every unit and every x != gb whose substituted codon is no stop: the opportunity of
+ *               x's class + 1, and if bit x of p is set the observed count + 1.  The entries x == gb stay 0.
+ *               The result is a function of the SET of bits: it does not depend on the order of the contigs, on which member set a bit or
+ *               on the batches.  A mutation the members of a lineage share over one record is one event; the same change over two records
+ *               of one lineage is two.
+ *   info        (may be NULL; zeroed first) contigs = n; used: the contigs with a usable V hit; truncated; units; positions: the seen
+ *               bits; obs_s, obs_r, opp_s, opp_r: the four tables' sums; batches.
+ * VDJX_EINVAL (the message names the contig): vdjx_selection's list for the contigs, the V hits and the limit; NULL out.  VDJX_ESTATE: no
+ * germline set is loaded.  n = 0 returns at once with a zeroed info and zeroed counts.  The host orders the contigs by unit and cuts the units
+ * into batches of VDJX_TGT_UNITS (1 .. 2^20 - 1, default 2^18, read per call; 1 KB of bitmap each, from the context's workspace); any value
+ * gives the same counts.  Per batch one memset and two kernels: k_tgt_mark (a wave per contig, 32-bit atomicOr into the unit's words) and
+ * k_tgt_count (a wave per unit, a 48 KB histogram in LDS per workgroup, integer LDS atomics, non-zero counters added with 64-bit global atomics).  No
+ * floating point, no float atomics: two calls give the same bytes.  Stats: "targeting_units", "targeting_batches", "targeting_us" (host
+ * clock).
+ *
+ * vdjx_targeting_model (plain C, no GPU, no context): the counts -> weights.  obs and opp are the counts of class 0 (cls 0: silent only,
+ * shazam's default, so that the model is free of the selection it is used to measure) or of classes 0 + 1 (cls 1).  c: m's centre base.
+ *   substitution  a[x] = obs[m][x] (level 5), summed over the 16 5-mers with m's inner three bases (level 3), over the 256 with m's centre
+ *                 (level 1): the first level with sum a >= min_sub; otherwise level 0, a[x] = 1 for x != c.  S[x] = a[x] / sum a.
+ *   mutability    (o, p) = (sum over x of obs, of opp) at level 5, 3 or 1: the first level with o >= min_mut and p > 0; otherwise level 0,
+ *                 all 1,024 5-mers together.  M = o / p; if the level-0 o or p is 0, M = 1 for every 5-mer.
+ *   weights       Z = sum M[m], m = 0 .. 1023 in that order; T = (M[m] / Z) * S[x]; weight[m][x] = max(1, rint(T * 1e9)) for x != c and 0
+ *                 for x = c: no 5-mer has a zero row.  float64, one operation per statement.  out_level[m] = {substitution level,
+ *                 mutability level}.
+ * min_sub and min_mut are shazam's minNumMutations (50) and minNumSeqMutations (500).  VDJX_EINVAL: cls outside 0, 1; a minimum of 0; a
+ * NULL argument.
+ * NOT modelled: shazam's per-sequence normalisation of the background; its N-extended 5-mers; the multipleMutation choice (each differing
+ * base is independent here); the clonal consensus sequence -- a clone contributes the UNION of its members' events. */
+typedef struct { uint64_t contigs, used, truncated, units, positions, obs_s, obs_r, opp_s, opp_r; uint32_t batches, pad; } vdjx_tgt_info;   /* 80 bytes */
+int vdjx_targeting_counts(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const vdjx_annot_hit* v, const int32_t* limit,
+                          const int32_t* group /* NULL, or n; < 0: no group */, uint64_t* out /* [2][2][1024][4] */, vdjx_tgt_info* info);
+int vdjx_targeting_model(const uint64_t* counts /* [2][2][1024][4] */, int cls /* 0: silent only, 1: silent + replacement */,
+                         uint64_t min_sub, uint64_t min_mut /* both >= 1 */, uint32_t* out_weight /* [1024][4] */, uint8_t* out_level /* [1024][2] */);
+
 /* ---- bootstrap clonal diversity: the Hill curve D(q) of the clone abundances, resampled to a common depth -----------------------------
  * gives `vdjer --diversity` what alakazam's estimateAbundance / alphaDiversity make of the clone table in a second tool: richness, Shannon
  * and Simpson diversity as points of one curve, each with the spread of B bootstrap replicates rarefied to N draws, so that samples of
@@ -779,6 +827,7 @@ int vdjx_part_u64(vdjx_ctx* ctx, const void* host_in, size_t n, int elem_bytes, 
  * vdjx_mutations' last call: "mutations_cols" (the bytes of each of the three row buffers), "mutations_us" (host clock).
  * vdjx_selection's last call: "selection_chunks" (the partial sums of its large rows), "selection_us" (host clock).
  * vdjx_diversity's last call: "diversity_batches", "diversity_us" (host clock).
+ * vdjx_targeting_counts' last call: "targeting_units", "targeting_batches", "targeting_us" (host clock).
  * What the context keeps from call to call outside its workspaces (anchor bitmaps, V region, read index, the scorers' result and SAM
  * buffers, upload staging, germline / constant / D sets), counted when asked: "kept_device_bytes", "kept_pinned_bytes" (page-locked host
  * memory) and "kept_allocs" (allocations made for them since vdjx_init: unchanged by a call that fitted what was there).  vdjx_trim

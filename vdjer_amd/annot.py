@@ -246,6 +246,48 @@ def read_targeting(path: str):
     return out
 
 
+def kmer5(m: int) -> str:
+    """the 5-mer of row m of a targeting model: m = 256 a + 64 b + 16 c + 4 d + e"""
+    return "".join("ACGT"[m >> s & 3] for s in (8, 6, 4, 2, 0))
+
+
+def targeting_model(counts, cls="s", min_sub=50, min_mut=500):
+    """vdjx_targeting_model (plain C, no GPU) over the uint64[2, 2, 1024, 4] counts of Context.targeting_counts -> (weight uint32[1024, 4]
+    for vdjx_selection, level uint8[1024, 2]: the substitution and the mutability level 5, 3, 1 or 0 of every 5-mer).  cls: "s" (silent
+    changes only) or "rs" (silent and replacement); min_sub, min_mut: whole numbers in 1 .. 2^32 - 1."""
+    import ctypes as C
+
+    import numpy as np
+
+    from . import _lib
+    counts = np.ascontiguousarray(counts, np.uint64)
+    if counts.shape != (2, 2, 1024, 4):
+        raise ValueError(f"counts of shape {counts.shape}, not (2, 2, 1024, 4)")
+    if cls not in ("s", "rs"):
+        raise ValueError(f"class {cls!r}: s or rs")
+    for name, x in (("min_sub", min_sub), ("min_mut", min_mut)):
+        if int(x) != x or not 1 <= int(x) < 1 << 32:
+            raise ValueError(f"{name} = {x!r}: a whole number in 1 .. 2^32 - 1")
+    weight, level = np.zeros((1024, 4), np.uint32), np.zeros((1024, 2), np.uint8)
+    _lib.check(_lib.lib().vdjx_targeting_model(counts.ctypes.data_as(C.c_void_p), int(cls == "rs"), int(min_sub), int(min_mut),
+                                               weight.ctypes.data_as(C.c_void_p), level.ctypes.data_as(C.c_void_p)), "vdjx_targeting_model")
+    return weight, level
+
+
+def write_targeting(path: str, weight, comments=()):
+    """a targeting model as `vdjer --targeting-model` writes it and read_targeting / `vdjer --targeting` read it: the comments as '# '
+    lines, then 1,024 lines `<5-mer>\\t<wA>\\t<wC>\\t<wG>\\t<wT>` in index order"""
+    import numpy as np
+    w = np.asarray(weight)
+    if w.shape != (1024, 4) or (w < 0).any() or (w >= 1 << 32).any():
+        raise ValueError(f"weights of shape {w.shape}: whole numbers below 2^32, [1024, 4]")
+    with open(path, "w") as f:
+        for line in comments:
+            f.write(f"# {line}\n")
+        for m in range(1024):
+            f.write(kmer5(m) + "".join(f"\t{int(x)}" for x in w[m]) + "\n")
+
+
 def _mix64(x):
     """splitmix64's output step, in 64-bit wrap-around arithmetic"""
     m = (1 << 64) - 1

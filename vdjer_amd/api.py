@@ -879,6 +879,26 @@ class Context:
                 "stat": {f: stat[f].copy() for f in self.SEL_STAT.names if f != "pad"}, "pdf": dens,
                 "info": {f: int(getattr(info, f)) for f in self.SEL_INFO_FIELDS}}
 
+    TGT_INFO_FIELDS = ("contigs", "used", "truncated", "units", "positions", "obs_s", "obs_r", "opp_s", "opp_r", "batches")
+
+    def targeting_counts(self, contigs, v, limit=None, group=None):
+        """vdjx_targeting_counts: per 5-mer and new base the observed changes and the opportunities of the V segments, silent and
+        replacement apart, a (group, V record) pair counted once.  v: the field dict annotate() returns; limit: int32[n] or None; group:
+        int32[n] (negative: in no group) or None -> {"counts": uint64[2, 2, 1024, 4] (kind: observed, opportunity; class: silent,
+        replacement; 5-mer; new base), "info": dict}.  annot.targeting_model makes the weights of them."""
+        raw, n, ln = self._contig_block(contigs, "vdjx_targeting_counts")
+        hv = self._hit_array(v, n, "v", "vdjx_targeting_counts")
+        lim = None if limit is None else np.ascontiguousarray(limit, np.int32)
+        if lim is not None and lim.shape != (n,):
+            raise VdjxError(f"vdjx_targeting_counts: {n} contigs, limit of shape {lim.shape}")
+        grp = None if group is None else np.ascontiguousarray(group, np.int32)
+        if grp is not None and grp.shape != (n,):
+            raise VdjxError(f"vdjx_targeting_counts: {n} contigs, group of shape {grp.shape}")
+        counts = np.zeros((2, 2, 1024, 4), np.uint64)
+        info = _lib.TgtInfo()
+        check(self.L.vdjx_targeting_counts(self.h, raw, n, ln, _p(hv), _p(lim), _p(grp), _p(counts), C.byref(info)), "vdjx_targeting_counts")
+        return {"counts": counts, "info": {f: int(getattr(info, f)) for f in self.TGT_INFO_FIELDS}}
+
     LINEAGE_NONE = 0xFFFFFFFF                                # VDJX_LINEAGE_NONE (include/vdjx.h)
 
     def lineage(self, junctions, group, max_dist=(1500, 10000), nearest: bool = True):

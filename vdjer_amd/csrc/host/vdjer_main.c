@@ -8,6 +8,7 @@
  *         [--lineages <file>] [--lineage-dist <x>] [--trees <file>] [--tree-support <B>] [--tree-seed <s>] [--mutations <file>]
  *         [--diversity <file>] [--diversity-depth <n>] [--diversity-boot <B>] [--diversity-seed <s>]
  *         [--selection <file>] [--v-regions <file>] [--targeting <file>]
+ *         [--targeting-model <file>] [--targeting-class s|rs] [--targeting-min-sub <n>] [--targeting-min-mut <n>] [--targeting-counts <file>]
  * writes ./vdj_contigs.fa and ./vdjer.dot, SAM on stdout, log on stderr; exit 0 on success.  --quant <file>: the contigs' abundances
  * (vdjx_quant, RSEM's isoforms.results columns) into <file> as well; --quant-boot <B> (with --quant): B bootstrap replicates of them over the placed
  * pairs (vdjx_quant_boot) drawn from --quant-seed <s>: the columns boot_mean, boot_sd, boot_lower and boot_upper, and in the --lineages table
@@ -31,6 +32,11 @@
  * groupBaseline / summarizeBaseline): observed against expected replacement and silent mutations and the posterior of sigma for every
  * contig, every lineage (with --lineages) and the sample, below --mutations' limit; --v-regions <file>: the CDR1 / CDR2 intervals of the V
  * records, which split every row into fwr and cdr; --targeting <file>: a 5-mer targeting model (default: uniform).
+ * --targeting-model <file>: the sample's own 5-mer targeting model in the format --targeting reads (vdjx_targeting_counts and
+ * vdjx_targeting_model: shazam's createTargetingModel), learnt from the V segments below --mutations' limit, a lineage of --lineages over
+ * one V record counted once; --targeting-class s|rs: from silent changes only (default) or silent and replacement; --targeting-min-sub
+ * <n>, --targeting-min-mut <n>: the observed changes a 5-mer needs for a substitution (50) and a mutability (500) estimate of its own;
+ * --targeting-counts <file>: the counts behind the model.  A --selection table of the same run does not read the model being written.
  *
  * --in: a BAM with its .bai (extraction as bam_read.c:264-446, restated over zlib in bamx.c), or -- recognised by its
  * content -- the extracted read pool as text, one read per line in extraction order:
@@ -91,6 +97,9 @@ typedef struct {
 	const char *v_regions, *targeting;     /* --v-regions <file>, --targeting <file>: read by parse() into regs / nregs and weight (NULL: uniform) */
 	struct vreg_line* regs; size_t nregs;
 	uint32_t* weight;
+	const char* tgt_model;                 /* --targeting-model <file> (not in the reference): shazam's createTargetingModel, on the device */
+	const char *tgt_class, *tgt_min_sub_s, *tgt_min_mut_s, *tgt_counts;      /* --targeting-class s|rs (read into tgt_cls), --targeting-min-sub <n>, --targeting-min-mut <n>, --targeting-counts <file> */
+	int tgt_cls; uint64_t tgt_min_sub, tgt_min_mut;
 	int have_chain, have_ref;
 } cli;
 
@@ -126,7 +135,12 @@ static void usage(void) {
 	                "\t--diversity-seed <seed of the draws, a whole number below 2^64 (default: 1)>\n"
 	                "\t--selection <file: selection strength (BASELINe) of the V mutations: observed and expected R / S and the posterior of sigma per contig, lineage (with --lineages) and sample>\n"
 	                "\t--v-regions <file: with --selection, lines `name cdr1_start cdr1_end cdr2_start cdr2_end` (1-based, inclusive, 0 0: none) of the V records: rows fwr and cdr>\n"
-	                "\t--targeting <file: with --selection, 1024 lines `<5-mer> <wA> <wC> <wG> <wT>`, whole numbers below 2^32 (default: uniform)>\n");
+	                "\t--targeting <file: with --selection, 1024 lines `<5-mer> <wA> <wC> <wG> <wT>`, whole numbers below 2^32 (default: uniform)>\n"
+	                "\t--targeting-model <file: the sample's own 5-mer targeting model, in the format --targeting reads, learnt from the V mutations (a lineage of --lineages counted once)>\n"
+	                "\t--targeting-class <s|rs: with --targeting-model, learn from silent changes only (default: s) or from silent and replacement>\n"
+	                "\t--targeting-min-sub <n: with --targeting-model, changes a 5-mer needs for its own substitution row, a whole number in 1 .. 4294967295 (default: 50)>\n"
+	                "\t--targeting-min-mut <n: with --targeting-model, changes a 5-mer needs for its own mutability, a whole number in 1 .. 4294967295 (default: 500)>\n"
+	                "\t--targeting-counts <file: with --targeting-model, the observed and opportunity counts per 5-mer and the levels used>\n");
 }
 
 static int file_exists(const char* f) { struct stat b; return stat(f, &b) == 0; }
@@ -293,6 +307,11 @@ static int parse(int argc, char** argv, cli* c) {
 		else if (!strcmp(a, "--selection")) c->selection = v;
 		else if (!strcmp(a, "--v-regions")) c->v_regions = v;
 		else if (!strcmp(a, "--targeting")) c->targeting = v;
+		else if (!strcmp(a, "--targeting-model")) c->tgt_model = v;
+		else if (!strcmp(a, "--targeting-class")) c->tgt_class = v;
+		else if (!strcmp(a, "--targeting-min-sub")) c->tgt_min_sub_s = v;
+		else if (!strcmp(a, "--targeting-min-mut")) c->tgt_min_mut_s = v;
+		else if (!strcmp(a, "--targeting-counts")) c->tgt_counts = v;
 		else if (!strcmp(a, "--vf")) snprintf(c->v_anchors, sizeof c->v_anchors, "%s", v);
 		else if (!strcmp(a, "--jf")) snprintf(c->j_anchors, sizeof c->j_anchors, "%s", v);
 		else if (!strcmp(a, "--am")) c->anchor_mismatches = atoi(v);
@@ -403,6 +422,26 @@ static int parse(int argc, char** argv, cli* c) {
 	if (c->targeting && !c->selection) { fprintf(stderr, "--targeting is the targeting model of the --selection table: it needs --selection <file>\n"); ok = 0; }
 	if (c->v_regions && c->selection && read_v_regions(c->v_regions, &c->regs, &c->nregs)) ok = 0;
 	if (c->targeting && c->selection && read_targeting(c->targeting, &c->weight)) ok = 0;
+	c->tgt_cls = 0;
+	c->tgt_min_sub = 50;
+	c->tgt_min_mut = 500;
+	if (c->tgt_class && !c->tgt_model) { fprintf(stderr, "--targeting-class is the mutation class of the --targeting-model file: it needs --targeting-model <file>\n"); ok = 0; }
+	if (c->tgt_min_sub_s && !c->tgt_model) { fprintf(stderr, "--targeting-min-sub is a threshold of the --targeting-model file: it needs --targeting-model <file>\n"); ok = 0; }
+	if (c->tgt_min_mut_s && !c->tgt_model) { fprintf(stderr, "--targeting-min-mut is a threshold of the --targeting-model file: it needs --targeting-model <file>\n"); ok = 0; }
+	if (c->tgt_counts && !c->tgt_model) { fprintf(stderr, "--targeting-counts is the counts behind the --targeting-model file: it needs --targeting-model <file>\n"); ok = 0; }
+	if (c->tgt_class) {
+		if (!strcmp(c->tgt_class, "s")) c->tgt_cls = 0;
+		else if (!strcmp(c->tgt_class, "rs")) c->tgt_cls = 1;
+		else { fprintf(stderr, "--targeting-class must be s (silent changes only) or rs (silent and replacement): %s\n", c->tgt_class); ok = 0; }
+	}
+	if (c->tgt_min_sub_s && (whole_u64(c->tgt_min_sub_s, &c->tgt_min_sub) || c->tgt_min_sub < 1 || c->tgt_min_sub > 4294967295ull)) {
+		fprintf(stderr, "--targeting-min-sub must be a whole decimal number in 1 .. 4294967295: %s\n", c->tgt_min_sub_s);
+		ok = 0;
+	}
+	if (c->tgt_min_mut_s && (whole_u64(c->tgt_min_mut_s, &c->tgt_min_mut) || c->tgt_min_mut < 1 || c->tgt_min_mut > 4294967295ull)) {
+		fprintf(stderr, "--targeting-min-mut must be a whole decimal number in 1 .. 4294967295: %s\n", c->tgt_min_mut_s);
+		ok = 0;
+	}
 	if (!ok) { usage(); return -1; }
 	if (c->hp.min_base_quality >= 255) c->hp.min_base_quality = 254;      /* A2:1514-1516 */
 	return 0;
@@ -767,6 +806,9 @@ typedef struct {
 	/* --selection: the selection strength of the V mutations (sel_run, after lineage_run) */
 	const char* selection; const struct vreg_line* regs; size_t nregs; const uint32_t* weight; int have_regs, sel_done;
 	vdjx_sel_info si; double sel_sigma[2]; size_t sel_unmatched;
+	/* --targeting-model: the sample's own targeting model (tgt_run, after lineage_run) */
+	const char *tgt_model, *tgt_counts; int tgt_cls, tgt_done; uint64_t tgt_min_sub, tgt_min_mut;
+	vdjx_tgt_info tgi; unsigned tgt_levels[2][4];      /* [substitution, mutability][level 5, 3, 1, 0]: the 5-mers on it */
 } hook_ud;
 
 static int h_root_score(void* ud, const char* kmers, size_t n, int k, int thr, uint8_t* out) {
@@ -964,7 +1006,7 @@ static long junction_at(const char* id, const char* s, int len, const char** jn_
 /* the V / J hits of every contig (vdjx_annotate against the germlines of ig_vdj.fa / --vdjf), kept for the tables */
 static int annot_run(hook_ud* u, const char* contigs, size_t n, int len) {
 	u->germ = (germ_set*) calloc(1, sizeof(germ_set));
-	if (germ_read(u->vdjf, u->germ, u->airr ? "--airr: cannot read the germline FASTA" : u->clones ? "--clones: cannot read the germline FASTA" : u->lineages ? "--lineages: cannot read the germline FASTA" : u->mutations ? "--mutations: cannot read the germline FASTA" : "--selection: cannot read the germline FASTA")) return -1;
+	if (germ_read(u->vdjf, u->germ, u->airr ? "--airr: cannot read the germline FASTA" : u->clones ? "--clones: cannot read the germline FASTA" : u->lineages ? "--lineages: cannot read the germline FASTA" : u->mutations ? "--mutations: cannot read the germline FASTA" : u->selection ? "--selection: cannot read the germline FASTA" : "--targeting-model: cannot read the germline FASTA")) return -1;
 	const germ_set* g = u->germ;
 	for (size_t r = 0; r < g->n; r++) {
 		if (g->cls[r] == 'V' || g->cls[r] == 'J') continue;
@@ -975,7 +1017,7 @@ static int annot_run(hook_ud* u, const char* contigs, size_t n, int len) {
 	const vdjx_annot_params ap = {2, 3, 5, 2, 40, 20};
 	int rc = vdjx_germline_load(u->gx, g->seqs, g->off, g->cls, g->n);
 	if (!rc && n) rc = vdjx_annotate(u->gx, contigs, n, len, &ap, u->hv, u->hj);
-	if (rc) fprintf(stderr, "%s: %s\n", u->airr ? "--airr" : u->clones ? "--clones" : u->lineages ? "--lineages" : u->mutations ? "--mutations" : "--selection", vdjx_last_error());
+	if (rc) fprintf(stderr, "%s: %s\n", u->airr ? "--airr" : u->clones ? "--clones" : u->lineages ? "--lineages" : u->mutations ? "--mutations" : u->selection ? "--selection" : "--targeting-model", vdjx_last_error());
 	return rc;
 }
 
@@ -1528,6 +1570,63 @@ static int sel_run(hook_ud* u, const char* const* ids, const char* contigs, size
 	return rc;
 }
 
+/* --targeting-model: the sample's own 5-mer targeting model (the model: include/vdjx.h, vdjx_targeting_counts and vdjx_targeting_model),
+ * in the format --targeting reads: '#' lines with what it was made of, then the 1,024 5-mers in index order.  The limit is --mutations';
+ * the lineages of --lineages are the groups, a contig in no lineage is a unit of its own.  --targeting-counts: the counts, a row per 5-mer. */
+static int tgt_run(hook_ud* u, const char* const* ids, const char* contigs, size_t n, int len) {
+	static const char B[5] = "ACGT";
+	uint64_t* cnt = (uint64_t*) calloc(2 * 2 * 1024 * 4, sizeof(uint64_t));
+	uint32_t* w = (uint32_t*) calloc(1024 * 4, sizeof(uint32_t));
+	uint8_t* lv = (uint8_t*) calloc(1024 * 2, 1);
+	int rc = 0;
+	if (n) {
+		int32_t* lim = mutation_limits(ids, contigs, n, len);
+		rc = vdjx_targeting_counts(u->gx, contigs, n, len, u->hv, lim, u->lineages ? u->lin_clone : NULL, cnt, &u->tgi);
+		free(lim);
+	}
+	if (!rc) rc = vdjx_targeting_model(cnt, u->tgt_cls, u->tgt_min_sub, u->tgt_min_mut, w, lv);
+	if (rc) fprintf(stderr, "--targeting-model: %s\n", vdjx_last_error());
+	if (!rc) {
+		for (int m = 0; m < 1024; m++)
+			for (int t = 0; t < 2; t++) u->tgt_levels[t][lv[2 * m + t] == 5 ? 0 : lv[2 * m + t] == 3 ? 1 : lv[2 * m + t] == 1 ? 2 : 3]++;
+		FILE* fp = fopen(u->tgt_model, "w");
+		if (!fp) { fprintf(stderr, "cannot write %s\n", u->tgt_model); rc = -1; }
+		else {
+			fprintf(fp, "# targeting model of %s: class %s, min_sub %llu, min_mut %llu\n", u->sample, u->tgt_cls ? "rs" : "s", (unsigned long long) u->tgt_min_sub,
+			        (unsigned long long) u->tgt_min_mut);
+			fprintf(fp, "# %llu units, %llu positions, observed %llu S %llu R, opportunities %llu S %llu R\n", (unsigned long long) u->tgi.units,
+			        (unsigned long long) u->tgi.positions, (unsigned long long) u->tgi.obs_s, (unsigned long long) u->tgi.obs_r, (unsigned long long) u->tgi.opp_s,
+			        (unsigned long long) u->tgi.opp_r);
+			fprintf(fp, "# substitution levels 5/3/1/0: %u/%u/%u/%u 5-mers\n", u->tgt_levels[0][0], u->tgt_levels[0][1], u->tgt_levels[0][2], u->tgt_levels[0][3]);
+			fprintf(fp, "# mutability levels 5/3/1/0: %u/%u/%u/%u 5-mers\n", u->tgt_levels[1][0], u->tgt_levels[1][1], u->tgt_levels[1][2], u->tgt_levels[1][3]);
+			for (int m = 0; m < 1024; m++)
+				fprintf(fp, "%c%c%c%c%c\t%u\t%u\t%u\t%u\n", B[m >> 8 & 3], B[m >> 6 & 3], B[m >> 4 & 3], B[m >> 2 & 3], B[m & 3], w[4 * m], w[4 * m + 1], w[4 * m + 2],
+				        w[4 * m + 3]);
+			if (fclose(fp)) { fprintf(stderr, "cannot write %s\n", u->tgt_model); rc = -1; }
+		}
+	}
+	if (!rc && u->tgt_counts) {
+		FILE* fp = fopen(u->tgt_counts, "w");
+		if (!fp) { fprintf(stderr, "cannot write %s\n", u->tgt_counts); rc = -1; }
+		else {
+			fputs("kmer", fp);
+			for (int t = 0; t < 4; t++)
+				for (int x = 0; x < 4; x++) fprintf(fp, "\t%s_%c_%c", t < 2 ? "obs" : "opp", t & 1 ? 'r' : 's', "acgt"[x]);
+			fputs("\tsub_level\tmut_level\n", fp);
+			for (int m = 0; m < 1024; m++) {
+				fprintf(fp, "%c%c%c%c%c", B[m >> 8 & 3], B[m >> 6 & 3], B[m >> 4 & 3], B[m >> 2 & 3], B[m & 3]);
+				for (int t = 0; t < 4; t++)
+					for (int x = 0; x < 4; x++) fprintf(fp, "\t%llu", (unsigned long long) cnt[(size_t) t * 4096 + 4 * (size_t) m + (size_t) x]);
+				fprintf(fp, "\t%u\t%u\n", lv[2 * m], lv[2 * m + 1]);
+			}
+			if (fclose(fp)) { fprintf(stderr, "cannot write %s\n", u->tgt_counts); rc = -1; }
+		}
+	}
+	free(cnt); free(w); free(lv);
+	if (!rc) u->tgt_done = 1;
+	return rc;
+}
+
 /* --diversity: the Hill diversity curve of the lineages (the model: include/vdjx.h, vdjx_diversity; the weights: diversity_weights of
  * vdjer_amd/annot.py).  A lineage's weight is the sum of its members' expected_count as printed, in hundredths, read from the digits;
  * lineages of weight 0 take no part.  A row per order 0.0 .. 4.0: the unresampled value, the replicates' mean and sd, the 95 % normal
@@ -1586,13 +1685,14 @@ static int diversity_run(hook_ud* u, size_t n) {
 static int tables(hook_ud* u, const char* const* ids, const char* contigs, size_t n, int len) {
 	int rc = 0;
 	if (!rc && (u->quant || u->clones)) rc = quant_table(u, ids, contigs, n, len);
-	if (!rc && (u->airr || u->clones || u->lineages || u->mutations || u->selection)) rc = annot_run(u, contigs, n, len);
+	if (!rc && (u->airr || u->clones || u->lineages || u->mutations || u->selection || u->tgt_model)) rc = annot_run(u, contigs, n, len);
 	if (!rc && u->d_calls) rc = dcall_run(u, contigs, n, len);
 	if (!rc && u->lineages) rc = lineage_run(u, ids, contigs, n, len);
 	if (!rc && u->trees) rc = tree_run(u, ids, contigs, n, len);
 	if (!rc && u->diversity) rc = diversity_run(u, n);
 	if (!rc && u->mutations) rc = mut_run(u, ids, contigs, n, len);
 	if (!rc && u->selection) rc = sel_run(u, ids, contigs, n, len);
+	if (!rc && u->tgt_model) rc = tgt_run(u, ids, contigs, n, len);
 	if (!rc && u->airr) rc = airr_table(u, ids, contigs, n, len);
 	if (!rc && u->cfa && (u->isotypes || u->clones)) rc = iso_run(u, contigs, n, len);
 	if (!rc && u->isotypes) rc = isotypes_table(u, ids, n, len);
@@ -1874,6 +1974,7 @@ int main(int argc, char** argv) {
 	ud.ts_b = c.ts_b; ud.ts_seed = c.ts_seed; ud.mutations = c.mutations;
 	ud.diversity = c.diversity; ud.dv_depth = c.div_depth; ud.dv_boot = c.div_boot; ud.dv_seed = c.div_seed;
 	ud.selection = c.selection; ud.regs = c.regs; ud.nregs = c.nregs; ud.weight = c.weight; ud.have_regs = c.v_regions != NULL;
+	ud.tgt_model = c.tgt_model; ud.tgt_counts = c.tgt_counts; ud.tgt_cls = c.tgt_cls; ud.tgt_min_sub = c.tgt_min_sub; ud.tgt_min_mut = c.tgt_min_mut;
 	char sample_buf[4096];
 	if (c.sample) ud.sample = c.sample;
 	else {                                  /* the input's base name up to its first '.' */
@@ -1889,7 +1990,7 @@ int main(int argc, char** argv) {
 		return 1;
 	}
 	/* (no contig: the headers alone) */
-	if (!ud.quant_done && !ud.airr_done && !ud.iso_done && !ud.clones_done && !ud.lin_done && !ud.mut_done && !ud.sel_done && tables(&ud, NULL, NULL, 0, 0)) return 1;
+	if (!ud.quant_done && !ud.airr_done && !ud.iso_done && !ud.clones_done && !ud.lin_done && !ud.mut_done && !ud.sel_done && !ud.tgt_done && tables(&ud, NULL, NULL, 0, 0)) return 1;
 	fprintf(stderr, "num root nodes: %zu\nProcessed roots: %zu\ncontig_candidates: %zu\nwindows scored: %zu valid: %zu\ncontigs: %zu\n",
 	        st.n_roots, st.n_roots_accepted, st.n_contig_candidates, st.n_windows_scored, st.n_windows_valid, st.n_contigs_out);
 	if (mg) {
@@ -1958,6 +2059,11 @@ int main(int argc, char** argv) {
 		if (ud.si.regions == 2) fprintf(stderr, " %.4f", ud.sel_sigma[1]);
 		fprintf(stderr, ", %u chunks\n", ud.si.chunks);
 	}
+	if (c.tgt_model)
+		fprintf(stderr, "targeting model: %llu contigs, %llu used, %llu units, %llu positions, %llu S, %llu R, class %s, substitution levels %u/%u/%u/%u, mutability levels %u/%u/%u/%u, %u batches\n",
+		        (unsigned long long) ud.tgi.contigs, (unsigned long long) ud.tgi.used, (unsigned long long) ud.tgi.units, (unsigned long long) ud.tgi.positions,
+		        (unsigned long long) ud.tgi.obs_s, (unsigned long long) ud.tgi.obs_r, c.tgt_cls ? "rs" : "s", ud.tgt_levels[0][0], ud.tgt_levels[0][1], ud.tgt_levels[0][2],
+		        ud.tgt_levels[0][3], ud.tgt_levels[1][0], ud.tgt_levels[1][1], ud.tgt_levels[1][2], ud.tgt_levels[1][3], ud.tgi.batches);
 	fflush(stdout);
 	fflush(stderr);
 	/* the outputs are written; the orderly teardown of a context that holds gigabytes (unmapping the workspaces piece by piece, the

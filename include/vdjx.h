@@ -491,8 +491,9 @@ int vdjx_dcall(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const int3
  *               items of the largest; clones; pairs: the sum of m (m - 1) / 2 over the buckets of m items; links: unordered linked pairs.
  * Defaults (what `vdjer --lineages` uses): num / den = 1500 / 10000, the 0.15 SCOPer documents as a starting point.  It is a parameter of
  * the model, not a tolerance: out_nearest (the table's dist_nearest) is there so that a user can choose their own from its histogram.
- * NOT modelled: amino-acid or substitution-model (HH_S5F) distances; N as a wildcard; average or complete linkage; clustering across
- * samples; "first gene only" handling of tied V calls (the group is the caller's: `vdjer` keys on the whole normalised tie list).
+ * NOT modelled: amino-acid distances (a 5-mer substitution distance: vdjx_lineage_model, below); N as a wildcard; average or complete
+ * linkage; clustering across samples; "first gene only" handling of tied V calls (the group is the caller's: `vdjer` keys on the whole
+ * normalised tie list).
  * VDJX_EINVAL: n >= 2^20, a participating item of 0 or more than VDJX_LINEAGE_MAXLEN bases, offsets that decrease, den < 1, den > 10^6,
  * num < 0, num > den, NULL out_clone.  n = 0 returns at once with a zeroed info.  The (group, L, index) keys are sorted on the host (per
  * item); everything per pair runs on the device.  A call is five kernel dispatches (pack, pairs, flatten, number, out) whatever n and the
@@ -505,6 +506,47 @@ typedef struct { int num, den; } vdjx_lineage_params;                 /* 8 bytes
 typedef struct { uint32_t items, buckets, largest_bucket, clones; uint64_t pairs, links; } vdjx_lineage_info;  /* 32 bytes */
 int vdjx_lineage(vdjx_ctx* ctx, const char* junctions, const uint64_t* off, const uint32_t* group, size_t n,
                  const vdjx_lineage_params* params, int32_t* out_clone, int32_t* out_nearest, vdjx_lineage_info* info);
+
+/* ---- clonal lineages under a 5-mer substitution distance (HH_S5F and its kin) ----------------------------------------------------------
+ * gives `vdjer --lineages --lineage-model` what Change-O's DefineClones --model hh_s5f, shazam's distToNearest(model = "hh_s5f") and SCOPer
+ * do with a targeting model: a mismatch is weighed by the 5-mer it happens in, so that a transition at a hot spot costs less than a rare
+ * change in a cold context.  Every quantity is an integer except the table's construction on the host; the device's results are bitwise the
+ * model's (tests/lineage_dist_model.py).
+ *
+ * vdjx_lineage_distance_table (plain C, no GPU, no context): the targeting weights -> the distance table.
+ *   weight      uint32 [1024][4] as vdjx_selection takes it: row 256 a + 64 b + 16 c + 4 d + e of the 5-mer abcde (A 0, C 1, G 2, T 3), column
+ *               the new base; the column of the centre base c is ignored.
+ *   table       w' = max(w, 1) for the 3,072 off-centre cells; S = their sum (64 bits); d = -log10((double) w' / (double) S) (libm); mean =
+ *               the sum of all d in index order (row by row, columns A C G T, centre skipped), added left to right in double, / 3072.0;
+ *               t = floor(1000 * d / mean + 0.5), clamped to 1 .. 65535; a centre cell is 0.  shazam's calcTargetingDistance in thousandths:
+ *               a mismatch under the uniform model costs exactly 1000.
+ *   info        (may be NULL) mean, and the smallest and largest off-centre t.
+ * VDJX_EINVAL: a NULL weight or table.
+ *
+ * vdjx_lineage_model: arguments, buckets, limits, refusals, clone numbering and info are vdjx_lineage's.
+ *   distance    a, b of one bucket of length L.  At every position p where they differ or either character is not one of ACGT:
+ *               side(a->b, p) = table[5-mer a[p-2 .. p+2]][b[p]] when 2 <= p <= L - 3, all five characters of a are ACGT and b[p] is ACGT,
+ *               and 1000 otherwise; side(b->a, p) alike.  symmetry 0 ("avg", shazam's): the position costs side(a->b) + side(b->a);
+ *               symmetry 1 ("min"): 2 * the smaller.  D(a, b) = the sum over these positions (at most 255 * 2 * 65535, fits 32 bits).  With
+ *               a table of all 1000, D = 2000 * the Hamming distance of vdjx_lineage on every input; a junction of fewer than 5 bases has no
+ *               5-mer and behaves so under any table.
+ *   link        iff D * den <= 2000 * num * L: num / den is still a fraction of the length, now in units of a mean mismatch.
+ *   nearest     the smallest D > 0 in the bucket, -1 when there is none (D = 0 iff the junctions are equal and all ACGT).
+ * NOT modelled: shazam's NN padding with N-averaged 5-mers at the junction's ends (a position without a full ACGT 5-mer costs the mean);
+ * amino-acid distances; any linkage other than single; a threshold chosen automatically.
+ * VDJX_EINVAL, beyond vdjx_lineage's: symmetry not 0 or 1, a NULL table, an off-centre cell of 0.  The host re-indexes the table to the packed
+ * rows' code order; a call is five dispatches whatever n is (pack, k_lin_pairs_model, flatten, number, out).  The pair pass first takes the
+ * Hamming count h of a pair: every counted position costs at least cmin = 2 * min(1000, smallest cell), so a pair with h * cmin past both the
+ * bucket's dmax and the lane's smallest D so far gives neither a link nor a nearest and is not walked; no result depends on it.  No floating
+ * point on the device, integer atomics only: two calls give the same bits.  Stats: vdjx_lineage's, "lineage_model_walked": the ordered
+ * pairs (row, column) whose positions were walked, of 2 * info->pairs, and "lineage_model_positions": the positions those walks looked at
+ * (two look-ups each where both sides have a 5-mer; a walk stops once its sum is past both dmax and the lane's smallest D). */
+typedef struct { int num, den, symmetry; } vdjx_lineage_model_params;            /* 12 bytes */
+typedef struct { double mean; uint32_t min_cost, max_cost; } vdjx_lineage_table_info;   /* 16 bytes */
+int vdjx_lineage_distance_table(const uint32_t* weight /* [1024][4] */, uint16_t* table /* [1024][4] */, vdjx_lineage_table_info* info);
+int vdjx_lineage_model(vdjx_ctx* ctx, const char* junctions, const uint64_t* off, const uint32_t* group, size_t n,
+                       const vdjx_lineage_model_params* params, const uint16_t* table /* [1024][4] */, int32_t* out_clone,
+                       int32_t* out_nearest, vdjx_lineage_info* info);
 
 /* ---- lineage trees: the minimum spanning tree of every clone under the Hamming distance of its members' common window -------------------
  * gives `vdjer --trees` what a repertoire user looks at inside a lineage (alakazam / dowser / Change-O BuildTrees): which member is

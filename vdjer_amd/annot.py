@@ -288,6 +288,28 @@ def write_targeting(path: str, weight, comments=()):
             f.write(kmer5(m) + "".join(f"\t{int(x)}" for x in w[m]) + "\n")
 
 
+def lineage_distance_table(weight):
+    """vdjx_lineage_distance_table (plain C, no GPU) over targeting weights -- uint32[1024, 4] as read_targeting returns them, or the path of
+    such a file, read by read_targeting with its refusals -> (table uint16[1024, 4] for Context.lineage(table=...), info dict(mean,
+    min_cost, max_cost)): -log10 of the targeting probability, normalised to a mean of 1, in thousandths; a centre cell is 0"""
+    import ctypes as C
+
+    import numpy as np
+
+    from . import _lib
+    if isinstance(weight, (str, bytes)) or hasattr(weight, "__fspath__"):
+        weight = read_targeting(weight if isinstance(weight, str) else __import__("os").fsdecode(weight))
+    given = np.asarray(weight)
+    if given.shape != (1024, 4) or given.dtype.kind not in "ui" or (given < 0).any() or (given >= 1 << 32).any():
+        raise ValueError(f"weights of shape {given.shape} and type {given.dtype}: whole numbers below 2^32, [1024, 4]")
+    w = np.ascontiguousarray(given, np.uint32)
+    table = np.zeros((1024, 4), np.uint16)
+    info = _lib.LineageTableInfo()
+    _lib.check(_lib.lib().vdjx_lineage_distance_table(w.ctypes.data_as(C.c_void_p), table.ctypes.data_as(C.c_void_p), C.byref(info)),
+               "vdjx_lineage_distance_table")
+    return table, dict(mean=float(info.mean), min_cost=int(info.min_cost), max_cost=int(info.max_cost))
+
+
 def _mix64(x):
     """splitmix64's output step, in 64-bit wrap-around arithmetic"""
     m = (1 << 64) - 1

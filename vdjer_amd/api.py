@@ -901,11 +901,16 @@ class Context:
 
     LINEAGE_NONE = 0xFFFFFFFF                                # VDJX_LINEAGE_NONE (include/vdjx.h)
 
-    def lineage(self, junctions, group, max_dist=(1500, 10000), nearest: bool = True):
+    LINEAGE_SYMMETRY = {"avg": 0, "min": 1}                  # vdjx_lineage_model_params.symmetry
+
+    def lineage(self, junctions, group, max_dist=(1500, 10000), nearest: bool = True, table=None, symmetry="avg"):
         """vdjx_lineage: single linkage inside the buckets of equal group and junction length; two junctions are linked when
         d * max_dist[1] <= max_dist[0] * L (d: positions that differ or are not ACGT).  junctions: str or bytes per item; group: uint32[n],
         LINEAGE_NONE for an item that takes no part -> {"clone": int32[n] (0-based, -1: no part), "nearest": int32[n] | None (smallest
-        non-zero distance inside the bucket, -1: none), "info": dict(items, buckets, largest_bucket, clones, pairs, links)}"""
+        non-zero distance inside the bucket, -1: none), "info": dict(items, buckets, largest_bucket, clones, pairs, links)}.
+        table: uint16[1024, 4] (annot.lineage_distance_table) -> vdjx_lineage_model instead: the 5-mer substitution distance D, linked when
+        D * max_dist[1] <= 2000 * max_dist[0] * L, nearest in the same units; symmetry: "avg" (both directions added) or "min" (twice the
+        smaller).  Without a table the call is vdjx_lineage's and symmetry is not looked at."""
         enc = [s_ if isinstance(s_, (bytes, bytearray)) else s_.encode() for s_ in junctions]
         n = len(enc)
         grp = np.ascontiguousarray(group, np.uint32)
@@ -916,8 +921,19 @@ class Context:
         clone = np.zeros(n, np.int32)
         near = np.zeros(n, np.int32) if nearest else None
         info = _lib.LineageInfo()
-        prm = _lib.LineageParams(int(max_dist[0]), int(max_dist[1]))
-        check(self.L.vdjx_lineage(self.h, b"".join(enc), _p(off), _p(grp), n, C.byref(prm), _p(clone), _p(near), C.byref(info)), "vdjx_lineage")
+        if table is None:
+            prm = _lib.LineageParams(int(max_dist[0]), int(max_dist[1]))
+            check(self.L.vdjx_lineage(self.h, b"".join(enc), _p(off), _p(grp), n, C.byref(prm), _p(clone), _p(near), C.byref(info)), "vdjx_lineage")
+        else:
+            tab = np.ascontiguousarray(table, np.uint16)
+            if tab.shape != (1024, 4) or not np.array_equal(tab, np.asarray(table)):
+                raise VdjxError(f"vdjx_lineage_model: a table of shape {np.shape(table)}, not uint16[1024, 4]")
+            sym = self.LINEAGE_SYMMETRY.get(symmetry, symmetry)
+            if not isinstance(sym, (int, np.integer)):
+                raise VdjxError(f"vdjx_lineage_model: symmetry {symmetry!r} (avg or min)")
+            prm = _lib.LineageModelParams(int(max_dist[0]), int(max_dist[1]), int(sym))
+            check(self.L.vdjx_lineage_model(self.h, b"".join(enc), _p(off), _p(grp), n, C.byref(prm), _p(tab), _p(clone), _p(near), C.byref(info)),
+                  "vdjx_lineage_model")
         return {"clone": clone, "nearest": near,
                 "info": {f: int(getattr(info, f)) for f in ("items", "buckets", "largest_bucket", "clones", "pairs", "links")}}
 

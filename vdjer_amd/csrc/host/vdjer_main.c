@@ -5,7 +5,7 @@
  *   vdjer --in <reads> --chain IGH|IGK|IGL --ref-dir <dir> --ins <n> [--t --k --mf --mq --mcs --am --miw --maw
  *         --jc --ws -jext --rf --vk --mrs --rs --ms --e0 --e1 --wo --vf --jf --rms] [--gpus N] [--quant <file>] [--quant-boot <B>] [--quant-seed <s>] [--airr <file>]
  *         [--d-calls] [--cfa <fasta>] [--isotypes <file>] [--clones <file>] [--sample <name>] [--total-count <n>]
- *         [--lineages <file>] [--lineage-dist <x>] [--trees <file>] [--tree-support <B>] [--tree-seed <s>] [--mutations <file>]
+ *         [--lineages <file>] [--lineage-dist <x>] [--lineage-model <file>] [--lineage-symmetry avg|min] [--trees <file>] [--tree-support <B>] [--tree-seed <s>] [--mutations <file>]
  *         [--diversity <file>] [--diversity-depth <n>] [--diversity-boot <B>] [--diversity-seed <s>]
  *         [--selection <file>] [--v-regions <file>] [--targeting <file>]
  *         [--targeting-model <file>] [--targeting-class s|rs] [--targeting-min-sub <n>] [--targeting-min-mut <n>] [--targeting-counts <file>]
@@ -18,7 +18,11 @@
  * isotype call of every contig against them (vdjx_isotype); --clones <file>: the per-sample table of the reference's post_process/
  * (collect_vdjer_stats.py | cluster_results.py) from the three device steps (one GPU only).  --lineages <file>: the contigs grouped into
  * clonal lineages (vdjx_lineage: single linkage on the junctions' Hamming distance inside a V gene / J gene / junction length bucket,
- * linked up to --lineage-dist, default 0.15 of the length); with --airr the table gets a clone_id column.  --trees <file> (with --lineages):
+ * linked up to --lineage-dist, default 0.15 of the length); with --airr the table gets a clone_id column.  --lineage-model <file> (with
+ * --lineages): a 5-mer targeting model in the format --targeting reads; the junctions are then compared under its substitution distance
+ * (vdjx_lineage_distance_table, vdjx_lineage_model: Change-O DefineClones --model hh_s5f), --lineage-dist in units of a mean mismatch;
+ * --lineage-symmetry avg|min: both directions of a mismatch added (default) or twice the cheaper.  The file must exist beforehand: a run does
+ * not read the --targeting-model file it is writing itself.  --trees <file> (with --lineages):
  * the tree inside every lineage (vdjx_tree: the minimum spanning tree under the Hamming distance over the members' common window around
  * the junction, rooted at the member closest to its germline V); --tree-support <B> (with --trees): a support column, the share of B
  * delete-half jackknife replicates whose tree has the edge to the parent (vdjx_tree_support), the columns drawn from --tree-seed <s>.
@@ -86,6 +90,8 @@ typedef struct {
 	const char* lineages;                  /* --lineages <file> (not in the reference): Change-O DefineClones' grouping of the contigs, on the device */
 	const char* lineage_dist;              /* --lineage-dist <x>: its threshold, a decimal read exactly into lin_num / lin_den (default 1500 / 10000) */
 	int lin_num, lin_den;
+	const char *lin_model, *lin_symmetry;  /* --lineage-model <file>: a --targeting file, read by parse() into lin_table (NULL: Hamming); --lineage-symmetry avg|min -> lin_sym */
+	int lin_sym; uint16_t* lin_table; vdjx_lineage_table_info lin_ti;
 	const char* trees;                     /* --trees <file> (not in the reference): the tree inside every lineage of --lineages, on the device */
 	const char *tree_support, *tree_seed;  /* --tree-support <B>, --tree-seed <s>: the jackknife support of the trees' edges; read into ts_b (0: none) and ts_seed */
 	uint32_t ts_b; uint64_t ts_seed;
@@ -125,6 +131,8 @@ static void usage(void) {
 	                "\t--total-count <whole number for the clone table's total_count column (default: N/A)>\n"
 	                "\t--lineages <file: clonal lineages of the contigs, single linkage on the junctions inside a V gene / J gene / length bucket>\n"
 	                "\t--lineage-dist <largest linked distance as a fraction of the junction length, in [0,1], at most 4 decimals (default: 0.15)>\n"
+	                "\t--lineage-model <file: with --lineages, a 5-mer targeting model as --targeting reads it: link under its substitution distance, --lineage-dist in mean mismatches>\n"
+	                "\t--lineage-symmetry <avg|min: with --lineage-model, add both directions of a mismatch (default: avg) or take twice the cheaper>\n"
 	                "\t--trees <file: with --lineages, the minimum spanning tree inside every lineage: parent, distance and depth of every contig>\n"
 	                "\t--tree-support <B: with --trees, a support column from B delete-half jackknife replicates, a whole number in 1 .. 1024>\n"
 	                "\t--tree-seed <seed of the replicates' columns, a whole number below 2^64 (default: 1)>\n"
@@ -218,9 +226,9 @@ static int read_v_regions(const char* path, vreg_line** out, size_t* n_out) {
 
 /* --targeting: exactly 1,024 lines `<5-mer> <wA> <wC> <wG> <wT>`, each 5-mer over ACGT once, whole decimal numbers below 2^32; '#' lines and
  * blank lines are skipped (read_targeting of vdjer_amd/annot.py) -> uint32 [1024][4] */
-static int read_targeting(const char* path, uint32_t** out) {
+static int read_targeting(const char* flag, const char* path, uint32_t** out) {
 	FILE* fp = fopen(path, "r");
-	if (!fp) { fprintf(stderr, "--targeting: cannot read %s\n", path); return -1; }
+	if (!fp) { fprintf(stderr, "%s: cannot read %s\n", flag, path); return -1; }
 	uint32_t* w = (uint32_t*) calloc(4096, sizeof(uint32_t));
 	unsigned char* seen = (unsigned char*) calloc(1024, 1);
 	char* line = NULL;
@@ -234,15 +242,15 @@ static int read_targeting(const char* path, uint32_t** out) {
 		uint64_t x[4] = {0, 0, 0, 0};
 		int bad = nf != 5 || strlen(f[0]) != 5 || strspn(f[0], "ACGT") != 5;
 		for (int k = 0; !bad && k < 4; k++) bad = whole_u64(f[1 + k], &x[k]) || x[k] > 4294967295ull;
-		if (bad) { fprintf(stderr, "--targeting: %s line %zu: expected `<5-mer over ACGT> <wA> <wC> <wG> <wT>` with whole numbers below 2^32\n", path, no); rc = -1; break; }
+		if (bad) { fprintf(stderr, "%s: %s line %zu: expected `<5-mer over ACGT> <wA> <wC> <wG> <wT>` with whole numbers below 2^32\n", flag, path, no); rc = -1; break; }
 		int idx = 0;
 		for (int k = 0; k < 5; k++) idx = 4 * idx + (int) (strchr("ACGT", f[0][k]) - "ACGT");
-		if (seen[idx]) { fprintf(stderr, "--targeting: %s line %zu: the 5-mer %s is given twice\n", path, no, f[0]); rc = -1; break; }
+		if (seen[idx]) { fprintf(stderr, "%s: %s line %zu: the 5-mer %s is given twice\n", flag, path, no, f[0]); rc = -1; break; }
 		seen[idx] = 1;
 		got++;
 		for (int k = 0; k < 4; k++) w[4 * idx + k] = (uint32_t) x[k];
 	}
-	if (!rc && got != 1024) { fprintf(stderr, "--targeting: %s holds %zu 5-mers, expected every one of the 1024 once\n", path, got); rc = -1; }
+	if (!rc && got != 1024) { fprintf(stderr, "%s: %s holds %zu 5-mers, expected every one of the 1024 once\n", flag, path, got); rc = -1; }
 	free(line);
 	free(seen);
 	fclose(fp);
@@ -296,6 +304,8 @@ static int parse(int argc, char** argv, cli* c) {
 		else if (!strcmp(a, "--total-count")) c->total_count = v;
 		else if (!strcmp(a, "--lineages")) c->lineages = v;
 		else if (!strcmp(a, "--lineage-dist")) c->lineage_dist = v;
+		else if (!strcmp(a, "--lineage-model")) c->lin_model = v;
+		else if (!strcmp(a, "--lineage-symmetry")) c->lin_symmetry = v;
 		else if (!strcmp(a, "--trees")) c->trees = v;
 		else if (!strcmp(a, "--tree-support")) c->tree_support = v;
 		else if (!strcmp(a, "--tree-seed")) c->tree_seed = v;
@@ -379,6 +389,23 @@ static int parse(int argc, char** argv, cli* c) {
 		fprintf(stderr, "--lineage-dist must be a decimal in [0, 1] with at most four digits after the point: %s\n", c->lineage_dist);
 		ok = 0;
 	}
+	c->lin_sym = 0;
+	if (c->lin_model && !c->lineages) { fprintf(stderr, "--lineage-model is the distance model of the --lineages table: it needs --lineages <file>\n"); ok = 0; }
+	if (c->lin_symmetry && !c->lin_model) { fprintf(stderr, "--lineage-symmetry is the symmetry of the --lineage-model distance: it needs --lineage-model <file>\n"); ok = 0; }
+	if (c->lin_symmetry) {
+		if (!strcmp(c->lin_symmetry, "avg")) c->lin_sym = 0;
+		else if (!strcmp(c->lin_symmetry, "min")) c->lin_sym = 1;
+		else { fprintf(stderr, "--lineage-symmetry must be avg (both directions added) or min (twice the cheaper): %s\n", c->lin_symmetry); ok = 0; }
+	}
+	if (c->lin_model && c->lineages) {
+		uint32_t* w = NULL;
+		if (read_targeting("--lineage-model", c->lin_model, &w)) ok = 0;
+		else {
+			c->lin_table = (uint16_t*) calloc(4096, sizeof(uint16_t));
+			if (vdjx_lineage_distance_table(w, c->lin_table, &c->lin_ti)) { fprintf(stderr, "--lineage-model: %s\n", vdjx_last_error()); ok = 0; }
+			free(w);
+		}
+	}
 	if (c->trees && !c->lineages) { fprintf(stderr, "--trees writes the tree inside every lineage of the --lineages table: it needs --lineages <file>\n"); ok = 0; }
 	c->ts_b = 0;
 	c->ts_seed = 1;
@@ -421,7 +448,7 @@ static int parse(int argc, char** argv, cli* c) {
 	if (c->v_regions && !c->selection) { fprintf(stderr, "--v-regions is the region map of the --selection table: it needs --selection <file>\n"); ok = 0; }
 	if (c->targeting && !c->selection) { fprintf(stderr, "--targeting is the targeting model of the --selection table: it needs --selection <file>\n"); ok = 0; }
 	if (c->v_regions && c->selection && read_v_regions(c->v_regions, &c->regs, &c->nregs)) ok = 0;
-	if (c->targeting && c->selection && read_targeting(c->targeting, &c->weight)) ok = 0;
+	if (c->targeting && c->selection && read_targeting("--targeting", c->targeting, &c->weight)) ok = 0;
 	c->tgt_cls = 0;
 	c->tgt_min_sub = 50;
 	c->tgt_min_mut = 500;
@@ -791,6 +818,7 @@ typedef struct {
 	size_t i_contigs, i_called, c_rows, c_clusters;
 	/* --lineages: the clone of every contig (lineage_run; -1: not eligible), kept for the --airr table's clone_id */
 	const char* lineages; int lin_num, lin_den, lin_done;
+	const uint16_t* lin_table; int lin_sym; unsigned long long lin_walked;      /* --lineage-model: the distance table (NULL: Hamming), its symmetry, the pairs walked */
 	int32_t* lin_clone; vdjx_lineage_info li;
 	size_t l_contigs, l_eligible;
 	/* --trees: the tree inside every lineage (tree_run, after lineage_run) */
@@ -1341,8 +1369,12 @@ static int lineage_run(hook_ud* u, const char* const* ids, const char* contigs, 
 		u->l_contigs++;
 	}
 	const vdjx_lineage_params lp = {u->lin_num, u->lin_den};
-	int rc = vdjx_lineage(u->gx, cat, off, grp, n, &lp, u->lin_clone, near, &u->li);
+	const vdjx_lineage_model_params lmp = {u->lin_num, u->lin_den, u->lin_sym};
+	int rc = u->lin_table ? vdjx_lineage_model(u->gx, cat, off, grp, n, &lmp, u->lin_table, u->lin_clone, near, &u->li)
+	                      : vdjx_lineage(u->gx, cat, off, grp, n, &lp, u->lin_clone, near, &u->li);
 	if (rc) fprintf(stderr, "--lineages: %s\n", vdjx_last_error());
+	if (!rc && u->lin_table) u->lin_walked = vdjx_stat(u->gx, "lineage_model_walked");
+	const double unit = u->lin_table ? 2000.0 : 1.0;      /* dist_nearest: in mean mismatches per base under a model */
 	if (!rc) {
 		size_t* size = (size_t*) calloc((size_t) u->li.clones + 1, sizeof(size_t));
 		double* sum = (double*) calloc((size_t) u->li.clones + 1, sizeof(double));
@@ -1372,7 +1404,7 @@ static int lineage_run(hook_ud* u, const char* const* ids, const char* contigs, 
 			const uint64_t L = off[i + 1] - off[i];
 			if (k < 0) { fprintf(fp, "%s\t\t%s\t%s\t\t\t%s%s\n", ids[i], vgs[i], jgs[i], counted ? "\t" : "", B ? "\t" : ""); continue; }
 			fprintf(fp, "%s\tlin_%d\t%s\t%s\t%llu\t", ids[i], k + 1, vgs[i], jgs[i], (unsigned long long) L);
-			if (near[i] >= 0) fprintf(fp, "%.4f", (double) near[i] / (double) L);
+			if (near[i] >= 0) fprintf(fp, "%.4f", (double) near[i] / (unit * (double) L));
 			fprintf(fp, "\t%zu", size[k]);
 			if (counted) fprintf(fp, "\t%.2f", sum[k]);
 			if (B) fprintf(fp, "\t%.2f", csd[k]);
@@ -1970,7 +2002,7 @@ int main(int argc, char** argv) {
 	ud.qb_b = c.qb_b; ud.qb_seed = c.qb_seed;
 	ud.gx = gx; ud.p = &c.hp; ud.mg = mg; ud.quant = c.quant; ud.airr = c.airr; ud.vdjf = c.vdj_fasta; ud.d_calls = c.d_calls;
 	ud.cfa = c.cfa; ud.isotypes = c.isotypes; ud.clones = c.clones; ud.total_count = c.total_count;
-	ud.lineages = c.lineages; ud.lin_num = c.lin_num; ud.lin_den = c.lin_den; ud.trees = c.trees;
+	ud.lineages = c.lineages; ud.lin_num = c.lin_num; ud.lin_den = c.lin_den; ud.lin_table = c.lin_table; ud.lin_sym = c.lin_sym; ud.trees = c.trees;
 	ud.ts_b = c.ts_b; ud.ts_seed = c.ts_seed; ud.mutations = c.mutations;
 	ud.diversity = c.diversity; ud.dv_depth = c.div_depth; ud.dv_boot = c.div_boot; ud.dv_seed = c.div_seed;
 	ud.selection = c.selection; ud.regs = c.regs; ud.nregs = c.nregs; ud.weight = c.weight; ud.have_regs = c.v_regions != NULL;
@@ -2032,6 +2064,9 @@ int main(int argc, char** argv) {
 	if (c.lineages)
 		fprintf(stderr, "lineages: %zu contigs, %zu eligible, %u buckets (largest %u), %llu pairs, %llu links, %u lineages at %d/%d\n", ud.l_contigs, ud.l_eligible,
 		        ud.li.buckets, ud.li.largest_bucket, (unsigned long long) ud.li.pairs, (unsigned long long) ud.li.links, ud.li.clones, c.lin_num, c.lin_den);
+	if (c.lin_model)
+		fprintf(stderr, "lineage model: %s, symmetry %s, mean %.4f, costs %u .. %u, %llu of %llu ordered pairs walked\n", c.lin_model, c.lin_sym ? "min" : "avg",
+		        c.lin_ti.mean, c.lin_ti.min_cost, c.lin_ti.max_cost, ud.lin_walked, 2ull * (unsigned long long) ud.li.pairs);
 	if (c.trees)
 		fprintf(stderr, "trees: %u contigs in %u lineages (largest %u), %llu edges, total distance %llu, %u rounds\n", ud.ti.members, ud.ti.clones, ud.ti.largest_clone,
 		        (unsigned long long) ud.ti.edges, (unsigned long long) ud.ti.weight, ud.ti.rounds);

@@ -667,7 +667,8 @@ int vdjx_tree_support(vdjx_ctx* ctx, const char* contigs, size_t n, int len, con
  *               NULL.  out_rows is required.
  * NOT modelled: IMGT gaps and numbering (the CDR / FWR split of the counts by the caller's intervals, the expected counts under a
  * targeting model and the selection strength are vdjx_selection's, below); V records that begin inside a codon (IMGT's 5'-partial
- * sequences: their codons are shifted); R/S for the J segment; a clonal consensus germline (CreateGermlines --cloned); a germline node as
+ * sequences: their codons are shifted); R/S for the J segment; a clonal consensus germline (CreateGermlines --cloned; the clone's own
+ * consensus is vdjx_consensus, below); a germline node as
  * the root of `--trees`.
  * VDJX_EINVAL (the message names the contig): a usable hit whose gene is out of range or names a record of the wrong class (v: 'V', j:
  * 'J'); germ_end past the record's end; seq_start or germ_start < 1, seq_end > len; a run with an op outside 0..2 or a length of 0; M + I
@@ -728,7 +729,7 @@ int vdjx_mutations(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const 
  *               regions = K; chunks: the partial sums of large rows (below), over both regions; large_rows: the rows that had them.
  * NOT modelled: shazam's fitted priors (BAYESIAN_FITTED); its convolution of the members' densities -- a group here is a SHARED sigma, not
  * the distribution of a weighted mean of the members'; IMGT numbering (the regions are the caller's intervals); N-averaged 5-mers; one
- * representative per clone for the sample row; the J segment; the comparison of two groups' densities.
+ * representative per clone for the sample row (run it on vdjx_consensus_hits' pseudo-contigs for that); the J segment; the comparison of two groups' densities.
  * VDJX_EINVAL (the message names the contig or the record): vdjx_mutations' list for the contigs, the V hits and the limit; n_records is not
  * the number of records given to vdjx_germline_load; an interval of a V record with start > end, start < 1 or end past the record; group[i]
  * >= G; G >= 2^20; out_pdf with G + 1 > 65,536; NULL out_counts or out_stat.  VDJX_ESTATE: no germline set is loaded.  n = 0 returns at
@@ -789,12 +790,72 @@ int vdjx_selection(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const 
  * min_sub and min_mut are shazam's minNumMutations (50) and minNumSeqMutations (500).  VDJX_EINVAL: cls outside 0, 1; a minimum of 0; a
  * NULL argument.
  * NOT modelled: shazam's per-sequence normalisation of the background; its N-extended 5-mers; the multipleMutation choice (each differing
- * base is independent here); the clonal consensus sequence -- a clone contributes the UNION of its members' events. */
+ * base is independent here); the clonal consensus sequence (vdjx_consensus, below, is not read here) -- a clone contributes the
+ * UNION of its members' events, which is clone-aware already. */
 typedef struct { uint64_t contigs, used, truncated, units, positions, obs_s, obs_r, opp_s, opp_r; uint32_t batches, pad; } vdjx_tgt_info;   /* 80 bytes */
 int vdjx_targeting_counts(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const vdjx_annot_hit* v, const int32_t* limit,
                           const int32_t* group /* NULL, or n; < 0: no group */, uint64_t* out /* [2][2][1024][4] */, vdjx_tgt_info* info);
 int vdjx_targeting_model(const uint64_t* counts /* [2][2][1024][4] */, int cls /* 0: silent only, 1: silent + replacement */,
                          uint64_t min_sub, uint64_t min_mut /* both >= 1 */, uint32_t* out_weight /* [1024][4] */, uint8_t* out_level /* [1024][2] */);
+
+/* ---- clonal consensus sequences: one sequence per lineage, decided column by column ----------------------------------------------------
+ * gives `vdjer --consensus` what shazam's collapseClones makes of the clones in a second tool: the sequence a lineage's members agree
+ * on, laid against the lineage's V record, so that a lineage counts once and one member's error is outvoted.  Everything is integer: the
+ * device's results are bitwise the model's (tests/consensus_model.py).
+ *   inputs      contigs, n, len, v[n], limit[n] and group[n] exactly as vdjx_targeting_counts takes them (limit == NULL: len; group ==
+ *               NULL or a negative entry: a contig on its own; a hit with more than 64 runs is treated as absent, info->truncated).
+ *   units       a unit is a group, or a lone contig.  Its RECORD is the V record most of its contigs with a usable hit name, the lowest
+ *               record index on a tie; its VOTERS are the contigs whose usable hit names that record; the group's other usable contigs are
+ *               off_record and take no part.  A group without a usable hit is no unit.  Units are numbered from 0 in the order of their
+ *               first usable contig; out_unit[i] is the voter's unit, -1 for every other contig.
+ *   votes       a voter's runs are walked with q = seq_start - 1, p = germ_start - 1 (0-based contig index and record position).  An M
+ *               run of L: for t < L with q + t < limit one vote at p + t for the symbol of contig[q + t] (A, C, G, T; anything else: N);
+ *               q and p advance by L.  A D run of L: if q < limit, one vote for GAP at each of p .. p + L - 1; p advances by L.  An I run:
+ *               its bases below the limit are counted in info->inserted, q advances, there is no column for them.
+ *               lo .. hi: the unit's smallest voted position through its largest + 1; a unit nobody voted in has lo = hi = 0.
+ *   decision    at every p in lo .. hi - 1, with the counts c[A, C, G, T, N, gap] and cover = their sum: the candidates are A, C, G, T and
+ *               gap (N never wins); best = the largest count of a candidate.  cover = 0 (a hole between two voters' ranges) or best = 0:
+ *               N.  One candidate at best: that one.  Several: the germline base of p if it is among them, else N.  Then the threshold:
+ *               best * den < num * cover gives N.  num / den = 0 / 1 is shazam's mostCommon, 6000 / 10000 (params == NULL) its
+ *               thresholdedFreq at minimumFrequency 0.6.
+ *   rows        unit u's rows are hi - lo bytes at out_cons / out_germ + off (out_cover, out_best: entries), no terminator: the consensus
+ *               row over ACGTN-, the germline row = the record's characters lo .. hi - 1, not ACGT as N; cover and best as above (each may
+ *               be NULL).  off ascends in unit order; the sizes come from vdjx_consensus_layout.
+ *   units out   group (-1: a lone contig), gene (the record, as given to vdjx_germline_load), members (the voters), off_record, lo, hi, off.
+ *   info        (may be NULL; zeroed first) contigs = n; used: the contigs with a usable hit; truncated; off_record; units; columns: the
+ *               sum of hi - lo; votes: the sum of cover; inserted; undecided: the N columns with cover > 0; batches; large_units: the units
+ *               of more voters than one workgroup takes (255).
+ * The result is a function of the MULTISET of votes: the order of the contigs inside a group, the batches and the launch geometry change
+ * no byte.
+ * vdjx_consensus_layout (plain C, no GPU, no context): out_unit, the units and the two sizes from the hits alone (it cannot know the record
+ * set: a gene is taken as given, germ_end up to 2,047).  out_units has room for n units.
+ * vdjx_consensus_hits (plain C, no GPU, no context): pseudo-contig u = the consensus row without its '-', padded with N to plen; *out_plen =
+ * the longest, at least 1 (out_contigs == NULL: only that).  Its hit: the unit's gene, seq_start 1, seq_end its bases, germ_start /
+ * germ_end after the gap columns at either end are trimmed; runs alternating M (maximal stretches of ACGTN) and D (stretches of '-');
+ * matches: the M columns equal and ACGT on both sides, mismatches the other M columns, del the gap columns, ins 0, opens the D runs; score =
+ * max(1, matches), n_tied 1.  More than 64 runs: n_runs is kept and runs zeroed, as vdjx_annotate does.  A row without a base: gene -1,
+ * score 0.  Such hits are consistent by construction: vdjx_mutations, vdjx_selection and vdjx_targeting_counts take them unchanged.
+ * NOT modelled: shazam's mostMutated / leastMutated / catchAll methods; ambiguity codes and stochastic tie-breaking; inserted bases; a
+ * consensus of the J segment or the junction; CreateGermlines --cloned's choice among tied V calls (the tie goes to the lowest record).
+ * VDJX_EINVAL (the message names the contig): vdjx_targeting_counts' list for the contigs, the V hits and the limit; den outside 1 .. 10^6
+ * or num outside 0 .. den; NULL out_cons, out_germ, out_units or out_unit; vdjx_consensus_hits: a plen below the longest row or above
+ * 4095.  VDJX_ESTATE: no germline set is loaded.  n = 0 returns at once with a zeroed info.  The host checks every hit, orders the voters
+ * by unit with one counting sort and cuts the units into batches of whole units of at most VDJX_CONS_CELLS columns (1 .. 2^28, default 2^24,
+ * read per call; 24 bytes of counters each, from the context's workspace; a unit of more columns is a batch of its own); any value gives the
+ * same bytes.  Per batch one memset and two kernels: k_cons_vote (a wave per voter; a workgroup takes up to 255 consecutive voters of one
+ * unit and counts them in LDS in bytes, 16 KB, with 32-bit LDS atomics; plain stores when it holds the whole unit, 32-bit global atomics
+ * otherwise; lone voters store their votes directly) and k_cons_decide (a thread per column).  No floating point, no float atomics: two calls
+ * give the same bytes.  Stats: "consensus_units", "consensus_batches", "consensus_us" (host clock). */
+typedef struct { int num, den; } vdjx_cons_params;                                                              /* 8 bytes */
+typedef struct { int32_t group, gene; uint32_t members, off_record; int32_t lo, hi; uint64_t off; } vdjx_cons_unit;   /* 32 bytes */
+typedef struct { uint64_t contigs, used, truncated, off_record, units, columns, votes, inserted, undecided; uint32_t batches, large_units; } vdjx_cons_info;   /* 80 bytes */
+int vdjx_consensus_layout(const vdjx_annot_hit* v, const int32_t* limit, const int32_t* group, size_t n, int len, int32_t* out_unit,
+                          vdjx_cons_unit* out_units /* up to n */, uint64_t* n_units, uint64_t* n_cols);
+int vdjx_consensus(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const vdjx_annot_hit* v, const int32_t* limit, const int32_t* group,
+                   const vdjx_cons_params* params /* NULL: 6000 / 10000 */, char* out_cons, char* out_germ, uint32_t* out_cover /* NULL ok */,
+                   uint32_t* out_best /* NULL ok */, vdjx_cons_unit* out_units, int32_t* out_unit, vdjx_cons_info* info);
+int vdjx_consensus_hits(const vdjx_cons_unit* units, size_t U, const char* cons, const char* germ, int plen,
+                        char* out_contigs /* U * plen, or NULL: only *out_plen */, vdjx_annot_hit* out_hits, int* out_plen);
 
 /* ---- bootstrap clonal diversity: the Hill curve D(q) of the clone abundances, resampled to a common depth -----------------------------
  * gives `vdjer --diversity` what alakazam's estimateAbundance / alphaDiversity make of the clone table in a second tool: richness, Shannon
@@ -870,6 +931,7 @@ int vdjx_part_u64(vdjx_ctx* ctx, const void* host_in, size_t n, int elem_bytes, 
  * vdjx_selection's last call: "selection_chunks" (the partial sums of its large rows), "selection_us" (host clock).
  * vdjx_diversity's last call: "diversity_batches", "diversity_us" (host clock).
  * vdjx_targeting_counts' last call: "targeting_units", "targeting_batches", "targeting_us" (host clock).
+ * vdjx_consensus' last call: "consensus_units", "consensus_batches", "consensus_us" (host clock).
  * What the context keeps from call to call outside its workspaces (anchor bitmaps, V region, read index, the scorers' result and SAM
  * buffers, upload staging, germline / constant / D sets), counted when asked: "kept_device_bytes", "kept_pinned_bytes" (page-locked host
  * memory) and "kept_allocs" (allocations made for them since vdjx_init: unchanged by a call that fitted what was there).  vdjx_trim

@@ -385,3 +385,79 @@ def diversity_weights(clone, count_cells):
         sums[k] = sums.get(k, 0) + w
     numbers = sorted(k for k, w in sums.items() if w > 0)
     return np.array([sums[k] for k in numbers], np.uint64), numbers
+
+
+HIT_FIELDS = ("gene", "score", "n_tied", "tied", "seq_start", "seq_end", "germ_start", "germ_end", "matches", "mismatches", "ins", "del", "opens",
+              "n_runs", "runs")
+CONS_UNIT_FIELDS = ("group", "gene", "members", "off_record", "lo", "hi", "off")
+
+
+def _hit_dtype():
+    import numpy as np
+    return np.dtype([(f, "<u4" if f == "runs" else "<i4", {"tied": (8,), "runs": (64,)}.get(f, ())) for f in HIT_FIELDS])      # vdjx_annot_hit
+
+
+def _cons_unit_dtype():
+    import numpy as np
+    return np.dtype([(f, {"members": "<u4", "off_record": "<u4", "off": "<u8"}.get(f, "<i4")) for f in CONS_UNIT_FIELDS])       # vdjx_cons_unit
+
+
+def consensus_layout(v, length, limit=None, group=None):
+    """vdjx_consensus_layout (plain C, no GPU): the units of vdjx_consensus from the hits alone.  v: the field dict Context.annotate returns;
+    length: the contigs' length; limit: int32[n] or None; group: int32[n] (negative: in no group) or None -> (unit int32[n]: the voter's
+    unit or -1, {field: array[U]}: group, gene, members, off_record, lo, hi, off, the columns of all units together)"""
+    import ctypes as C
+
+    import numpy as np
+
+    from . import _lib
+    n = len(np.asarray(v["gene"]))
+    hv = np.zeros(n, _hit_dtype())
+    for f in HIT_FIELDS:
+        hv[f] = np.asarray(v[f])
+    lim = None if limit is None else np.ascontiguousarray(limit, np.int32)
+    grp = None if group is None else np.ascontiguousarray(group, np.int32)
+    if (lim is not None and lim.shape != (n,)) or (grp is not None and grp.shape != (n,)):
+        raise ValueError(f"{n} hits, limit and group of as many entries")
+    unit = np.full(n, -1, np.int32)
+    units = np.zeros(max(n, 1), _cons_unit_dtype())
+    nu, ncol = C.c_uint64(0), C.c_uint64(0)
+    ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    _lib.check(_lib.lib().vdjx_consensus_layout(ptr(hv), ptr(lim), ptr(grp), n, int(length), ptr(unit), ptr(units), C.byref(nu), C.byref(ncol)),
+               "vdjx_consensus_layout")
+    units = units[:int(nu.value)]
+    return unit, {f: units[f].copy() for f in CONS_UNIT_FIELDS}, int(ncol.value)
+
+
+def consensus_hits(units, cons, germ):
+    """vdjx_consensus_hits (plain C, no GPU): the rows of Context.consensus as contigs and V hits that mutations(), selection() and
+    targeting_counts() take.  units: {field: array[U]}; cons, germ: one str per unit -> (contigs: list[str] of one length -- a row without its
+    '-', padded with N --, v: {field: array} of vdjx_annot_hit; a row without a base has gene -1 and score 0)"""
+    import ctypes as C
+
+    import numpy as np
+
+    from . import _lib
+    U = len(cons)
+    if len(germ) != U or any(len(np.asarray(units[f])) != U for f in CONS_UNIT_FIELDS) or any(len(a) != len(b) for a, b in zip(cons, germ)):
+        raise ValueError(f"{U} consensus rows, as many germline rows of the same lengths and as many units")
+    un = np.zeros(max(U, 1), _cons_unit_dtype())
+    for f in CONS_UNIT_FIELDS:
+        un[f][:U] = np.asarray(units[f])
+    off = 0
+    for u in range(U):                                                # the rows as this call lays them out, whatever the units' own offsets were
+        if len(cons[u]) != int(un["hi"][u]) - int(un["lo"][u]):
+            raise ValueError(f"unit {u}: a row of {len(cons[u])} columns, positions {int(un['lo'][u])} .. {int(un['hi'][u])}")
+        un["off"][u] = off
+        off += len(cons[u])
+    rc, rg = ("".join(cons).encode("latin-1") + b"\0"), ("".join(germ).encode("latin-1") + b"\0")
+    ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    plen = C.c_int(0)
+    L = _lib.lib()
+    _lib.check(L.vdjx_consensus_hits(ptr(un), U, rc, rg, 0, None, None, C.byref(plen)), "vdjx_consensus_hits")
+    pl = int(plen.value)
+    text = np.zeros(max(U, 1) * pl, np.uint8)
+    hv = np.zeros(max(U, 1), _hit_dtype())
+    _lib.check(L.vdjx_consensus_hits(ptr(un), U, rc, rg, pl, ptr(text), ptr(hv), C.byref(plen)), "vdjx_consensus_hits")
+    raw = text.tobytes()
+    return [raw[u * pl:(u + 1) * pl].decode("latin-1") for u in range(U)], {f: hv[f][:U].copy() for f in HIT_FIELDS}

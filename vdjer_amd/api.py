@@ -899,6 +899,48 @@ class Context:
         check(self.L.vdjx_targeting_counts(self.h, raw, n, ln, _p(hv), _p(lim), _p(grp), _p(counts), C.byref(info)), "vdjx_targeting_counts")
         return {"counts": counts, "info": {f: int(getattr(info, f)) for f in self.TGT_INFO_FIELDS}}
 
+    CONS_UNIT = np.dtype([("group", "<i4"), ("gene", "<i4"), ("members", "<u4"), ("off_record", "<u4"), ("lo", "<i4"), ("hi", "<i4"), ("off", "<u8")])
+    CONS_INFO_FIELDS = ("contigs", "used", "truncated", "off_record", "units", "columns", "votes", "inserted", "undecided", "batches",
+                        "large_units")
+
+    def consensus(self, contigs, v, limit=None, group=None, min_freq=(6000, 10000), counts: bool = False):
+        """vdjx_consensus: per unit (a group, or a contig on its own) the sequence its voters agree on, column by column over the unit's V
+        record, and the record's own bases beside it.  v: the field dict annotate() returns; limit: int32[n] or None; group: int32[n]
+        (negative: in no group) or None; min_freq: (num, den), a column's winner needs best * den >= num * cover ((0, 1): the most
+        common symbol) -> {"unit": int32[n] (the voter's unit, -1: none), "units": {field: array[U]} (group, gene, members, off_record, lo,
+        hi, off), "cons", "germ": list[str] per unit (cons over ACGTN-), "cover", "best": list of uint32 arrays per unit | None
+        (counts=False), "info": dict}.  annot.consensus_hits makes contigs and V hits of the rows."""
+        raw, n, ln = self._contig_block(contigs, "vdjx_consensus")
+        hv = self._hit_array(v, n, "v", "vdjx_consensus")
+        lim = None if limit is None else np.ascontiguousarray(limit, np.int32)
+        if lim is not None and lim.shape != (n,):
+            raise VdjxError(f"vdjx_consensus: {n} contigs, limit of shape {lim.shape}")
+        grp = None if group is None else np.ascontiguousarray(group, np.int32)
+        if grp is not None and grp.shape != (n,):
+            raise VdjxError(f"vdjx_consensus: {n} contigs, group of shape {grp.shape}")
+        unit = np.full(n, -1, np.int32)
+        units = np.zeros(max(n, 1), self.CONS_UNIT)
+        nu, ncol = C.c_uint64(0), C.c_uint64(0)
+        info = _lib.ConsInfo()
+        prm = _lib.ConsParams(int(min_freq[0]), int(min_freq[1]))
+        # the sizes first; whatever the layout refuses the call refuses under its own name (with nothing to write into)
+        total = 0
+        if self.L.vdjx_consensus_layout(_p(hv), _p(lim), _p(grp), n, ln, _p(unit), _p(units), C.byref(nu), C.byref(ncol)) == 0:
+            total = int(ncol.value)
+        rows = [np.zeros(max(total, 1), np.uint8) for _ in range(2)]
+        cnt = [np.zeros(max(total, 1), np.uint32) for _ in range(2)] if counts else [None, None]
+        check(self.L.vdjx_consensus(self.h, raw, n, ln, _p(hv), _p(lim), _p(grp), C.byref(prm), _p(rows[0]), _p(rows[1]), _p(cnt[0]), _p(cnt[1]),
+                                    _p(units), _p(unit), C.byref(info)), "vdjx_consensus")
+        U = int(info.units)
+        units = units[:U]
+        cut = [(int(o), int(o) + int(h) - int(l)) for o, l, h in zip(units["off"], units["lo"], units["hi"])]
+        text = [r.tobytes() for r in rows]
+        return {"unit": unit, "units": {f: units[f].copy() for f in self.CONS_UNIT.names},
+                "cons": [text[0][a:b].decode("latin-1") for a, b in cut], "germ": [text[1][a:b].decode("latin-1") for a, b in cut],
+                "cover": [cnt[0][a:b].copy() for a, b in cut] if counts else None,
+                "best": [cnt[1][a:b].copy() for a, b in cut] if counts else None,
+                "info": {f: int(getattr(info, f)) for f in self.CONS_INFO_FIELDS}}
+
     LINEAGE_NONE = 0xFFFFFFFF                                # VDJX_LINEAGE_NONE (include/vdjx.h)
 
     LINEAGE_SYMMETRY = {"avg": 0, "min": 1}                  # vdjx_lineage_model_params.symmetry

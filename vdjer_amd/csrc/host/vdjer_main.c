@@ -9,6 +9,7 @@
  *         [--diversity <file>] [--diversity-depth <n>] [--diversity-boot <B>] [--diversity-seed <s>]
  *         [--selection <file>] [--v-regions <file>] [--targeting <file>]
  *         [--targeting-model <file>] [--targeting-class s|rs] [--targeting-min-sub <n>] [--targeting-min-mut <n>] [--targeting-counts <file>]
+ *         [--consensus <file>] [--consensus-min-freq <x>]
  * writes ./vdj_contigs.fa and ./vdjer.dot, SAM on stdout, log on stderr; exit 0 on success.  --quant <file>: the contigs' abundances
  * (vdjx_quant, RSEM's isoforms.results columns) into <file> as well; --quant-boot <B> (with --quant): B bootstrap replicates of them over the placed
  * pairs (vdjx_quant_boot) drawn from --quant-seed <s>: the columns boot_mean, boot_sd, boot_lower and boot_upper, and in the --lineages table
@@ -41,6 +42,10 @@
  * one V record counted once; --targeting-class s|rs: from silent changes only (default) or silent and replacement; --targeting-min-sub
  * <n>, --targeting-min-mut <n>: the observed changes a 5-mer needs for a substitution (50) and a mutability (500) estimate of its own;
  * --targeting-counts <file>: the counts behind the model.  A --selection table of the same run does not read the model being written.
+ * --consensus <file> (with --lineages): the consensus V sequence of every lineage, and of every contig in none, beside its germline
+ * (vdjx_consensus: shazam's collapseClones, thresholdedFreq), decided column by column below --mutations' limit; --consensus-min-freq <x>:
+ * the share of a column's votes its winner needs (default 0.6; 0: the most common symbol); the row's mutation counts are vdjx_mutations' of
+ * the consensus; with --selection that table gets a consensus row per unit and one consensus_sample row, one representative per clone.
  *
  * --in: a BAM with its .bai (extraction as bam_read.c:264-446, restated over zlib in bamx.c), or -- recognised by its
  * content -- the extracted read pool as text, one read per line in extraction order:
@@ -106,6 +111,8 @@ typedef struct {
 	const char* tgt_model;                 /* --targeting-model <file> (not in the reference): shazam's createTargetingModel, on the device */
 	const char *tgt_class, *tgt_min_sub_s, *tgt_min_mut_s, *tgt_counts;      /* --targeting-class s|rs (read into tgt_cls), --targeting-min-sub <n>, --targeting-min-mut <n>, --targeting-counts <file> */
 	int tgt_cls; uint64_t tgt_min_sub, tgt_min_mut;
+	const char *consensus, *cons_min_freq; /* --consensus <file> (not in the reference): shazam's collapseClones over the lineages, on the device; --consensus-min-freq <x>: read as --lineage-dist is, into cons_num over 10000 (default 6000) */
+	int cons_num;
 	int have_chain, have_ref;
 } cli;
 
@@ -148,7 +155,9 @@ static void usage(void) {
 	                "\t--targeting-class <s|rs: with --targeting-model, learn from silent changes only (default: s) or from silent and replacement>\n"
 	                "\t--targeting-min-sub <n: with --targeting-model, changes a 5-mer needs for its own substitution row, a whole number in 1 .. 4294967295 (default: 50)>\n"
 	                "\t--targeting-min-mut <n: with --targeting-model, changes a 5-mer needs for its own mutability, a whole number in 1 .. 4294967295 (default: 500)>\n"
-	                "\t--targeting-counts <file: with --targeting-model, the observed and opportunity counts per 5-mer and the levels used>\n");
+	                "\t--targeting-counts <file: with --targeting-model, the observed and opportunity counts per 5-mer and the levels used>\n"
+	                "\t--consensus <file: with --lineages, the consensus V sequence of every lineage (and of every contig in none) beside its germline, and its mutation counts>\n"
+	                "\t--consensus-min-freq <share of a column's votes its winner needs, in [0,1], at most 4 decimals (default: 0.6; 0: the most common)>\n");
 }
 
 static int file_exists(const char* f) { struct stat b; return stat(f, &b) == 0; }
@@ -322,6 +331,8 @@ static int parse(int argc, char** argv, cli* c) {
 		else if (!strcmp(a, "--targeting-min-sub")) c->tgt_min_sub_s = v;
 		else if (!strcmp(a, "--targeting-min-mut")) c->tgt_min_mut_s = v;
 		else if (!strcmp(a, "--targeting-counts")) c->tgt_counts = v;
+		else if (!strcmp(a, "--consensus")) c->consensus = v;
+		else if (!strcmp(a, "--consensus-min-freq")) c->cons_min_freq = v;
 		else if (!strcmp(a, "--vf")) snprintf(c->v_anchors, sizeof c->v_anchors, "%s", v);
 		else if (!strcmp(a, "--jf")) snprintf(c->j_anchors, sizeof c->j_anchors, "%s", v);
 		else if (!strcmp(a, "--am")) c->anchor_mismatches = atoi(v);
@@ -449,6 +460,13 @@ static int parse(int argc, char** argv, cli* c) {
 	if (c->targeting && !c->selection) { fprintf(stderr, "--targeting is the targeting model of the --selection table: it needs --selection <file>\n"); ok = 0; }
 	if (c->v_regions && c->selection && read_v_regions(c->v_regions, &c->regs, &c->nregs)) ok = 0;
 	if (c->targeting && c->selection && read_targeting("--targeting", c->targeting, &c->weight)) ok = 0;
+	c->cons_num = 6000;
+	if (c->consensus && !c->lineages) { fprintf(stderr, "--consensus is the consensus of every lineage of the --lineages table: it needs --lineages <file>\n"); ok = 0; }
+	if (c->cons_min_freq && !c->consensus) { fprintf(stderr, "--consensus-min-freq is the threshold of the --consensus table: it needs --consensus <file>\n"); ok = 0; }
+	if (c->cons_min_freq && (c->cons_num = lineage_dist_num(c->cons_min_freq)) < 0) {
+		fprintf(stderr, "--consensus-min-freq must be a decimal in [0, 1] with at most four digits after the point: %s\n", c->cons_min_freq);
+		ok = 0;
+	}
 	c->tgt_cls = 0;
 	c->tgt_min_sub = 50;
 	c->tgt_min_mut = 500;
@@ -837,6 +855,10 @@ typedef struct {
 	/* --targeting-model: the sample's own targeting model (tgt_run, after lineage_run) */
 	const char *tgt_model, *tgt_counts; int tgt_cls, tgt_done; uint64_t tgt_min_sub, tgt_min_mut;
 	vdjx_tgt_info tgi; unsigned tgt_levels[2][4];      /* [substitution, mutability][level 5, 3, 1, 0]: the 5-mers on it */
+	/* --consensus: the consensus of every lineage (cons_run, after lineage_run); the pseudo-contigs, their hits and first voters are kept for sel_run */
+	const char* consensus; int cons_num, cons_done;
+	vdjx_cons_info ci; uint32_t cs_largest;
+	size_t cs_units; int cs_plen; char* cs_pc; vdjx_annot_hit* cs_hv; vdjx_cons_unit* cs_un; size_t* cs_first;
 } hook_ud;
 
 static int h_root_score(void* ud, const char* kmers, size_t n, int k, int thr, uint8_t* out) {
@@ -1588,6 +1610,23 @@ static int sel_run(hook_ud* u, const char* const* ids, const char* contigs, size
 				sel_rows(fp, "lineage", id, st + (n + k) * (size_t) K, K);
 			}
 			sel_rows(fp, "sample", u->sample, st + (n + G) * (size_t) K, K);
+			/* --consensus: the units' pseudo-contigs, each on its own and all under a shared sigma -- one representative per clone */
+			if (u->consensus && u->cs_units) {
+				const size_t U = u->cs_units;
+				vdjx_sel_counts* cnt2 = (vdjx_sel_counts*) calloc(U + 1, sizeof(vdjx_sel_counts));
+				vdjx_sel_stat* st2 = (vdjx_sel_stat*) calloc((U + 1) * (size_t) K, sizeof(vdjx_sel_stat));
+				rc = vdjx_selection(u->gx, u->cs_pc, U, u->cs_plen, u->cs_hv, NULL, cdr, g->n, u->weight, NULL, 0, cnt2, st2, NULL, NULL);
+				if (rc) fprintf(stderr, "--selection: %s\n", vdjx_last_error());
+				for (size_t k = 0; k < U && !rc; k++) {
+					char id[32];
+					snprintf(id, sizeof id, "lin_%d", u->cs_un[k].group + 1);
+					const char* name = u->cs_un[k].group >= 0 ? id : ids[u->cs_first[k]];
+					if (cnt2[k].flags & 1) sel_rows(fp, "consensus", name, st2 + k * K, K);
+					else fprintf(fp, "consensus\t%s\t\t\t\t\t\t\t\t\t\t\n", name);
+				}
+				if (!rc) sel_rows(fp, "consensus_sample", u->sample, st2 + U * (size_t) K, K);
+				free(cnt2); free(st2);
+			}
 			for (uint32_t k = 0; k < K; k++) {
 				const double sg = st[(n + G) * (size_t) K + k].sigma;
 				u->sel_sigma[k] = sg > -0.00005 && sg < 0.0 ? 0.0 : sg;
@@ -1659,6 +1698,83 @@ static int tgt_run(hook_ud* u, const char* const* ids, const char* contigs, size
 	return rc;
 }
 
+/* --consensus: the consensus V sequence of every unit (the model: include/vdjx.h, vdjx_consensus): the lineages of --lineages are the
+ * groups, a contig in no lineage is a unit of its own, the limit is --mutations'.  A row per unit, in unit order; the six mutation cells are
+ * vdjx_mutations' counts of the unit's pseudo-contig under its synthetic hit (vdjx_consensus_hits), J absent, no limit.  The pseudo-contigs
+ * are kept for the --selection table's consensus rows. */
+static int cons_run(hook_ud* u, const char* const* ids, const char* contigs, size_t n, int len) {
+	FILE* fp = fopen(u->consensus, "w");
+	if (!fp) { fprintf(stderr, "cannot write %s\n", u->consensus); return -1; }
+	fputs("clone_id\tsequence_id\tv_call\tmembers\toff_record\tgermline_start\tgermline_end\tconsensus_alignment\tgermline_alignment\tmin_cover\tundecided\t"
+	      "v_germline_codons\tmu_count_v_r\tmu_count_v_s\tmu_count_v_stop\tmu_count_v_na\tmu_freq_v\n", fp);
+	int rc = 0;
+	if (n) {
+		const germ_set* g = u->germ;
+		int32_t* lim = mutation_limits(ids, contigs, n, len);
+		int32_t* unit = (int32_t*) calloc(n + 1, sizeof(int32_t));
+		vdjx_cons_unit* un = (vdjx_cons_unit*) calloc(n + 1, sizeof(vdjx_cons_unit));
+		uint64_t U = 0, cols = 0;
+		char *cons = NULL, *germ = NULL;
+		uint32_t* cover = NULL;
+		vdjx_mut_row* rows = NULL;
+		vdjx_annot_hit* nohit = NULL;
+		rc = vdjx_consensus_layout(u->hv, lim, u->lin_clone, n, len, unit, un, &U, &cols);
+		if (!rc) {
+			cons = (char*) malloc((size_t) cols + 1);
+			germ = (char*) malloc((size_t) cols + 1);
+			cover = (uint32_t*) calloc((size_t) cols + 1, sizeof(uint32_t));
+			const vdjx_cons_params cp = {u->cons_num, 10000};
+			rc = vdjx_consensus(u->gx, contigs, n, len, u->hv, lim, u->lin_clone, &cp, cons, germ, cover, NULL, un, unit, &u->ci);
+		}
+		int plen = 1;
+		if (!rc) rc = vdjx_consensus_hits(un, (size_t) U, cons, germ, 0, NULL, NULL, &plen);
+		if (!rc) {
+			u->cs_pc = (char*) malloc((size_t) U * (size_t) plen + 1);
+			u->cs_hv = (vdjx_annot_hit*) calloc((size_t) U + 1, sizeof(vdjx_annot_hit));
+			rc = vdjx_consensus_hits(un, (size_t) U, cons, germ, plen, u->cs_pc, u->cs_hv, &plen);
+		}
+		rows = (vdjx_mut_row*) calloc((size_t) U + 1, sizeof(vdjx_mut_row));
+		if (!rc && U) {
+			nohit = (vdjx_annot_hit*) calloc((size_t) U + 1, sizeof(vdjx_annot_hit));
+			for (size_t k = 0; k < U; k++) nohit[k].gene = -1;
+			rc = vdjx_mutations(u->gx, u->cs_pc, (size_t) U, plen, u->cs_hv, NULL, nohit, NULL, NULL, NULL, NULL, rows, NULL);
+		}
+		if (rc) fprintf(stderr, "--consensus: %s\n", vdjx_last_error());
+		if (!rc) {
+			u->cs_units = (size_t) U;
+			u->cs_plen = plen;
+			u->cs_un = un;
+			u->cs_first = (size_t*) calloc((size_t) U + 1, sizeof(size_t));
+			for (size_t i = n; i-- > 0;)
+				if (unit[i] >= 0) u->cs_first[unit[i]] = i;
+			for (size_t k = 0; k < U; k++) {
+				const vdjx_cons_unit* q = un + k;
+				const int w = q->hi - q->lo;
+				uint32_t minc = w ? UINT32_MAX : 0, und = 0;
+				for (int x = 0; x < w; x++) {
+					const uint32_t cv = cover[q->off + (uint64_t) x];
+					if (cv < minc) minc = cv;
+					und += cons[q->off + (uint64_t) x] == 'N' && cv > 0;
+				}
+				if (q->members > u->cs_largest) u->cs_largest = q->members;
+				if (q->group >= 0) fprintf(fp, "lin_%d", q->group + 1);
+				fprintf(fp, "\t%s\t%s\t%u\t%u\t%d\t%d\t%.*s\t%.*s\t%u\t%u\t", ids[u->cs_first[k]], g->names[q->gene], q->members, q->off_record, q->lo + 1, q->hi, w,
+				        cons + q->off, w, germ + q->off, minc, und);
+				const vdjx_mut_row* r = rows + k;
+				if (r->flags & 1) {
+					fprintf(fp, "%d\t%d\t%d\t%d\t%d\t", r->v_codons, r->v_r, r->v_s, r->v_stop, r->v_na);
+					if (r->v_codons) fprintf(fp, "%.4f", (double) (r->v_r + r->v_s) / (double) (3 * r->v_codons));
+				} else fputs("\t\t\t\t\t", fp);
+				fputc('\n', fp);
+			}
+		} else free(un);
+		free(lim); free(unit); free(cons); free(germ); free(cover); free(rows); free(nohit);
+	}
+	if (fclose(fp) && !rc) { fprintf(stderr, "cannot write %s\n", u->consensus); return -1; }
+	if (!rc) u->cons_done = 1;
+	return rc;
+}
+
 /* --diversity: the Hill diversity curve of the lineages (the model: include/vdjx.h, vdjx_diversity; the weights: diversity_weights of
  * vdjer_amd/annot.py).  A lineage's weight is the sum of its members' expected_count as printed, in hundredths, read from the digits;
  * lineages of weight 0 take no part.  A row per order 0.0 .. 4.0: the unresampled value, the replicates' mean and sd, the 95 % normal
@@ -1723,6 +1839,7 @@ static int tables(hook_ud* u, const char* const* ids, const char* contigs, size_
 	if (!rc && u->trees) rc = tree_run(u, ids, contigs, n, len);
 	if (!rc && u->diversity) rc = diversity_run(u, n);
 	if (!rc && u->mutations) rc = mut_run(u, ids, contigs, n, len);
+	if (!rc && u->consensus) rc = cons_run(u, ids, contigs, n, len);
 	if (!rc && u->selection) rc = sel_run(u, ids, contigs, n, len);
 	if (!rc && u->tgt_model) rc = tgt_run(u, ids, contigs, n, len);
 	if (!rc && u->airr) rc = airr_table(u, ids, contigs, n, len);
@@ -2007,6 +2124,7 @@ int main(int argc, char** argv) {
 	ud.diversity = c.diversity; ud.dv_depth = c.div_depth; ud.dv_boot = c.div_boot; ud.dv_seed = c.div_seed;
 	ud.selection = c.selection; ud.regs = c.regs; ud.nregs = c.nregs; ud.weight = c.weight; ud.have_regs = c.v_regions != NULL;
 	ud.tgt_model = c.tgt_model; ud.tgt_counts = c.tgt_counts; ud.tgt_cls = c.tgt_cls; ud.tgt_min_sub = c.tgt_min_sub; ud.tgt_min_mut = c.tgt_min_mut;
+	ud.consensus = c.consensus; ud.cons_num = c.cons_num;
 	char sample_buf[4096];
 	if (c.sample) ud.sample = c.sample;
 	else {                                  /* the input's base name up to its first '.' */
@@ -2022,7 +2140,7 @@ int main(int argc, char** argv) {
 		return 1;
 	}
 	/* (no contig: the headers alone) */
-	if (!ud.quant_done && !ud.airr_done && !ud.iso_done && !ud.clones_done && !ud.lin_done && !ud.mut_done && !ud.sel_done && !ud.tgt_done && tables(&ud, NULL, NULL, 0, 0)) return 1;
+	if (!ud.quant_done && !ud.airr_done && !ud.iso_done && !ud.clones_done && !ud.lin_done && !ud.mut_done && !ud.sel_done && !ud.tgt_done && !ud.cons_done && tables(&ud, NULL, NULL, 0, 0)) return 1;
 	fprintf(stderr, "num root nodes: %zu\nProcessed roots: %zu\ncontig_candidates: %zu\nwindows scored: %zu valid: %zu\ncontigs: %zu\n",
 	        st.n_roots, st.n_roots_accepted, st.n_contig_candidates, st.n_windows_scored, st.n_windows_valid, st.n_contigs_out);
 	if (mg) {
@@ -2099,6 +2217,10 @@ int main(int argc, char** argv) {
 		        (unsigned long long) ud.tgi.contigs, (unsigned long long) ud.tgi.used, (unsigned long long) ud.tgi.units, (unsigned long long) ud.tgi.positions,
 		        (unsigned long long) ud.tgi.obs_s, (unsigned long long) ud.tgi.obs_r, c.tgt_cls ? "rs" : "s", ud.tgt_levels[0][0], ud.tgt_levels[0][1], ud.tgt_levels[0][2],
 		        ud.tgt_levels[0][3], ud.tgt_levels[1][0], ud.tgt_levels[1][1], ud.tgt_levels[1][2], ud.tgt_levels[1][3], ud.tgi.batches);
+	if (c.consensus)
+		fprintf(stderr, "consensus: %llu contigs, %llu used, %llu units (largest %u), %llu off the unit's record, %llu columns, %llu undecided, min share %d.%04d, %u batches\n",
+		        (unsigned long long) ud.ci.contigs, (unsigned long long) ud.ci.used, (unsigned long long) ud.ci.units, ud.cs_largest, (unsigned long long) ud.ci.off_record,
+		        (unsigned long long) ud.ci.columns, (unsigned long long) ud.ci.undecided, c.cons_num / 10000, c.cons_num % 10000, ud.ci.batches);
 	fflush(stdout);
 	fflush(stderr);
 	/* the outputs are written; the orderly teardown of a context that holds gigabytes (unmapping the workspaces piece by piece, the

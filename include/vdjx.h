@@ -490,7 +490,8 @@ int vdjx_dcall(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const int3
  *   info        (may be NULL; zeroed first, every field filled on success) items: participating items; buckets; largest_bucket: the
  *               items of the largest; clones; pairs: the sum of m (m - 1) / 2 over the buckets of m items; links: unordered linked pairs.
  * Defaults (what `vdjer --lineages` uses): num / den = 1500 / 10000, the 0.15 SCOPer documents as a starting point.  It is a parameter of
- * the model, not a tolerance: out_nearest (the table's dist_nearest) is there so that a user can choose their own from its histogram.
+ * the model, not a tolerance: out_nearest (the table's dist_nearest) is there so that a user can choose their own from its histogram, and
+ * vdjx_lineage_threshold, below, chooses it from that histogram on the device.
  * NOT modelled: amino-acid distances (a 5-mer substitution distance: vdjx_lineage_model, below); N as a wildcard; average or complete
  * linkage; clustering across samples; "first gene only" handling of tied V calls (the group is the caller's: `vdjer` keys on the whole
  * normalised tie list).
@@ -533,7 +534,7 @@ int vdjx_lineage(vdjx_ctx* ctx, const char* junctions, const uint64_t* off, cons
  *   link        iff D * den <= 2000 * num * L: num / den is still a fraction of the length, now in units of a mean mismatch.
  *   nearest     the smallest D > 0 in the bucket, -1 when there is none (D = 0 iff the junctions are equal and all ACGT).
  * NOT modelled: shazam's NN padding with N-averaged 5-mers at the junction's ends (a position without a full ACGT 5-mer costs the mean);
- * amino-acid distances; any linkage other than single; a threshold chosen automatically.
+ * amino-acid distances; any linkage other than single.  (A threshold chosen automatically: vdjx_lineage_threshold, below, unit 2000.)
  * VDJX_EINVAL, beyond vdjx_lineage's: symmetry not 0 or 1, a NULL table, an off-centre cell of 0.  The host re-indexes the table to the packed
  * rows' code order; a call is five dispatches whatever n is (pack, k_lin_pairs_model, flatten, number, out).  The pair pass first takes the
  * Hamming count h of a pair: every counted position costs at least cmin = 2 * min(1000, smallest cell), so a pair with h * cmin past both the
@@ -547,6 +548,68 @@ int vdjx_lineage_distance_table(const uint32_t* weight /* [1024][4] */, uint16_t
 int vdjx_lineage_model(vdjx_ctx* ctx, const char* junctions, const uint64_t* off, const uint32_t* group, size_t n,
                        const vdjx_lineage_model_params* params, const uint16_t* table /* [1024][4] */, int32_t* out_clone,
                        int32_t* out_nearest, vdjx_lineage_info* info);
+
+/* ---- the lineage threshold: the valley between the two modes of the nearest-neighbour distances ----------------------------------------
+ * gives `vdjer --lineages --lineage-threshold` what shazam's findThreshold(method = "density") makes of distToNearest before DefineClones
+ * runs: the distances to the nearest neighbour have a mode of clonal relatives and a mode of unrelated sequences, and the threshold is the
+ * valley between them.  Everything is integer except the construction of the kernel tables on the host: the device's results are bitwise
+ * the model's (tests/threshold_model.py).
+ *   constants   G = 10,000: the grid is g = 0 .. G, G + 1 points of 0.0001, the unit of --lineage-dist.  FIX = 2^30.
+ *   inputs      nearest[n]: out_nearest of the two lineage calls, -1: none; length[n]: the junctions' lengths; unit: 1 for vdjx_lineage's
+ *               distances, 2000 for vdjx_lineage_model's.
+ *   bins        an item with nearest < 0 takes no part and its length is not read.  Any other falls into bin v = min(G, (2 G nearest +
+ *               unit L) / (2 unit L)) by 64-bit integer division: nearest / (unit L) rounded half up to the grid, clamped at 1.0.  c[v]
+ *               counts the items of bin v; values = the sum of c, distinct = the bins that are not 0.
+ *   tables      vdjx_threshold_kernel (plain C, no GPU, no context), k = 1 .. VDJX_THRESHOLD_MAX_K: w[d] = floor(FIX * exp(-(double)(d * d) /
+ *               (double)(200 * k * k)) + 0.5) with libm's exp, for d = 0, 1, .. up to the first d that gives 0; every entry from there on is 0
+ *               (the table does not increase).  *len (may be NULL) = the entries before it.  A Gaussian with a standard deviation of 10 k grid
+ *               steps, the bandwidth h = k / 1000; w[0] = FIX; len is about 65.6 k, so from k = 153 on the table covers the whole grid.
+ *   density     Y_k[g] = the sum over v of c[v] * w_k[|g - v|], in uint64 (values < 2^20: Y < 2^50).
+ *   peaks       of row k: cut 0 .. G into maximal runs of equal Y.  A run is a peak when its Y > 0, is greater than the run before it (or
+ *               there is none) and greater than the run after it (or there is none).  A peak is counted when Y << peak_shift >= the row's
+ *               largest Y: a bump below 1 / 2^peak_shift of the highest peak, an outlier in the far tail, is ignored.  peaks_all[k] and
+ *               peaks[k] are the two counts.
+ *   bandwidth   k* = the smallest k in 1 .. max_k with peaks[k] <= 2: Silverman's critical bandwidth for two modes, over a fixed list.
+ *   valley      with two counted peaks: a = the last point of the first peak's run, b = the first point of the second's; m = the smallest Y
+ *               over a < g < b; t_first, t_last = the first and last g there with Y = m; threshold = (t_first + t_last) / 2 rounded down,
+ *               the middle of the valley's floor (which matters when the floor is a run of zeros).  The valley is accepted when valley_den *
+ *               m <= valley_num * min(Y_a, Y_b).
+ *   status      VDJX_THRESHOLD_FOUND; _FEW: fewer than min_values values, no density is computed; _NO_SCALE: no k up to max_k with at most two
+ *               counted peaks; _ONE_MODE: one counted peak at k*; _SHALLOW: two peaks and a valley the guard refuses.  With any status but
+ *               FOUND the threshold is 0 and the caller keeps its own.
+ *   outputs     (each of the three may be NULL) out_hist[G + 1]: c; out_density[G + 1]: row k*, row max_k under _NO_SCALE, zeros under _FEW;
+ *               out_peaks[max_k][2]: peaks_all and peaks of every row (zeros under _FEW).
+ *   info        (zeroed first) values, distinct, status; k: k*, max_k under _NO_SCALE, 0 under _FEW; of that row peaks_all, peaks, ymax, the
+ *               first counted peak's first and last point and Y (p1_first, p1_last, y1) and, with two or more, the second's; with exactly two
+ *               (FOUND, _SHALLOW) t_first, t_last, m; threshold.
+ * Defaults (what `vdjer --lineage-threshold` uses): max_k 200, peak_shift 5, valley 1 / 2, min_values 10.
+ * NOT modelled: shazam's "gmm" method; its bandwidth selector (this is the critical bandwidth over thousandths); subsampling (the
+ * distances are exact and all there); a threshold per V/J bucket; a confidence interval of the threshold.
+ * VDJX_EINVAL: n >= 2^20, nearest < -1, a participating length of 0 or above 255, unit 0 or above 2^20, max_k outside 1 .. 200, peak_shift
+ * outside 0 .. 13, valley_den < 1 or > 10^6, valley_num outside 0 .. valley_den, min_values < 1, a NULL info; vdjx_threshold_kernel: k
+ * outside 1 .. 200, a NULL w.  n = 0 is status _FEW.
+ * A call is five kernel dispatches whatever n is (histogram, number, compact, density, peaks; the histogram alone under _FEW, none without a
+ * value).  The items are counted in LDS histograms with integer atomics; the non-zero bins are compacted to an ascending list; the density
+ * pass is a grid of (tiles of VDJX_THRESHOLD_TILE grid points, k) with w_k in LDS; a workgroup per k finds the row's peaks.  The host picks
+ * k* from the max_k records and reads that one row back for the valley: the max_k x (G + 1) matrix stays on the device.  The tables are
+ * built once per process on the host (about 1.2 M exp, 5 MB) and their leading non-zero entries uploaded per call.  Scratch comes from the
+ * context's workspace; no floating point on the device, integer atomics only: two calls give the same bits.  Stats: "threshold_us" (host
+ * clock), "threshold_macs" (the terms c[v] * w_k[|g - v|] with |g - v| < len_k, all k), "threshold_table_us" (the tables' one build). */
+#define VDJX_THRESHOLD_GRID  10000u
+#define VDJX_THRESHOLD_MAX_K 200
+#define VDJX_THRESHOLD_TILE  256u       /* grid points per workgroup of the density pass (the tests place modes on a tile's ends) */
+#define VDJX_THRESHOLD_FOUND    0u
+#define VDJX_THRESHOLD_FEW      1u
+#define VDJX_THRESHOLD_NO_SCALE 2u
+#define VDJX_THRESHOLD_ONE_MODE 3u
+#define VDJX_THRESHOLD_SHALLOW  4u
+typedef struct { int max_k, peak_shift, valley_num, valley_den, min_values; } vdjx_threshold_params;     /* 20 bytes */
+typedef struct { uint32_t values, distinct, status, k, peaks_all, peaks, p1_first, p1_last, p2_first, p2_last, t_first, t_last, threshold, reserved;
+                 uint64_t y1, y2, m, ymax; } vdjx_threshold_info;                                          /* 88 bytes */
+int vdjx_threshold_kernel(int k, uint32_t* w /* [G + 1] */, uint32_t* len);
+int vdjx_lineage_threshold(vdjx_ctx* ctx, const int32_t* nearest, const uint32_t* length, size_t n, uint32_t unit,
+                           const vdjx_threshold_params* params, uint32_t* out_hist /* [G + 1] */, uint64_t* out_density /* [G + 1] */,
+                           uint32_t* out_peaks /* [max_k][2] */, vdjx_threshold_info* info);
 
 /* ---- lineage trees: the minimum spanning tree of every clone under the Hamming distance of its members' common window -------------------
  * gives `vdjer --trees` what a repertoire user looks at inside a lineage (alakazam / dowser / Change-O BuildTrees): which member is

@@ -310,6 +310,48 @@ def lineage_distance_table(weight):
     return table, dict(mean=float(info.mean), min_cost=int(info.min_cost), max_cost=int(info.max_cost))
 
 
+THRESHOLD_GRID = 10000                                   # VDJX_THRESHOLD_GRID (include/vdjx.h): the grid is 0 .. 10000 ten-thousandths
+
+
+def threshold_kernel(k):
+    """vdjx_threshold_kernel (plain C, no GPU): the fixed-point Gaussian of bandwidth k / 1000, k = 1 .. 200 -> (uint32[10001]: w[d] =
+    floor(2^30 exp(-d d / (200 k k)) + 0.5) up to its first 0 and zeros from there, len: the entries before that 0)"""
+    import ctypes as C
+
+    import numpy as np
+
+    from . import _lib
+    if not isinstance(k, (int, np.integer)) or not -(1 << 31) <= int(k) < 1 << 31:
+        raise ValueError(f"a bandwidth k in 1 .. 200 thousandths, not {k!r}")
+    w = np.zeros(THRESHOLD_GRID + 1, np.uint32)
+    ln = C.c_uint32(0)
+    _lib.check(_lib.lib().vdjx_threshold_kernel(int(k), w.ctypes.data_as(C.c_void_p), C.byref(ln)), "vdjx_threshold_kernel")
+    return w, int(ln.value)
+
+
+def threshold_bins(nearest, length, unit=1):
+    """the bin rule of vdjx_lineage_threshold (include/vdjx.h) in plain Python integers -> int32[n]: the bin 0 .. 10000 of every item, -1
+    for an item that takes no part (nearest -1; its length is not read): min(10000, (20000 nearest + unit L) // (2 unit L)).  ValueError
+    where the library refuses: nearest below -1, a participating length of 0 or above 255, unit outside 1 .. 2^20, 2^20 items or more"""
+    import numpy as np
+    near, ln = [int(x) for x in nearest], [int(x) for x in length]
+    if len(near) != len(ln) or len(near) >= 1 << 20:
+        raise ValueError(f"{len(near)} nearest distances and {len(ln)} lengths: as many of each, fewer than 2^20")
+    if not isinstance(unit, (int, np.integer)) or not 1 <= int(unit) <= 1 << 20:
+        raise ValueError(f"unit {unit!r} (1 .. 2^20)")
+    unit = int(unit)
+    out = np.full(len(near), -1, np.int32)
+    for i, (d, L) in enumerate(zip(near, ln)):
+        if d < -1 or d >= 1 << 31:
+            raise ValueError(f"item {i} has nearest {d} (-1: none)")
+        if d < 0:
+            continue
+        if not 1 <= L <= 255:
+            raise ValueError(f"item {i} has length {L} (1 .. 255)")
+        out[i] = min(THRESHOLD_GRID, (2 * THRESHOLD_GRID * d + unit * L) // (2 * unit * L))
+    return out
+
+
 def _mix64(x):
     """splitmix64's output step, in 64-bit wrap-around arithmetic"""
     m = (1 << 64) - 1

@@ -979,6 +979,34 @@ class Context:
         return {"clone": clone, "nearest": near,
                 "info": {f: int(getattr(info, f)) for f in ("items", "buckets", "largest_bucket", "clones", "pairs", "links")}}
 
+    THRESHOLD_STATUS = _lib.THRESHOLD_STATUS                 # info["status"] by name (VDJX_THRESHOLD_FOUND .. _SHALLOW)
+    THRESHOLD_FIELDS = ("values", "distinct", "status", "k", "peaks_all", "peaks", "p1_first", "p1_last", "p2_first", "p2_last", "t_first", "t_last",
+                        "threshold", "y1", "y2", "m", "ymax")
+
+    def lineage_threshold(self, nearest, length, unit=1, max_k=200, peak_shift=5, valley=(1, 2), min_values=10):
+        """vdjx_lineage_threshold: the valley between the two modes of the nearest-neighbour distances.  nearest: int32[n], lineage()'s
+        "nearest" (-1: none); length: uint32[n], the junctions' lengths; unit: 1 for Hamming distances, 2000 under a table -> {"hist":
+        uint32[10001] (items per bin of 0.0001), "density": uint64[10001] (the smoothed counts at the chosen bandwidth k / 1000, scale 2^30),
+        "peaks": uint32[max_k, 2] (all and counted peaks of every bandwidth), "info": dict(values, distinct, status, k, peaks_all, peaks,
+        p1_first, p1_last, p2_first, p2_last, t_first, t_last, threshold, y1, y2, m, ymax)}.  info["status"] indexes THRESHOLD_STATUS;
+        info["threshold"] is in ten-thousandths, lineage()'s max_dist[0] over 10000, and 0 unless the status is 0."""
+        near = np.ascontiguousarray(nearest, np.int32)
+        ln = np.ascontiguousarray(length, np.uint32)
+        if near.ndim != 1 or ln.shape != near.shape or not np.array_equal(near, np.asarray(nearest)) or not np.array_equal(ln, np.asarray(length)):
+            raise VdjxError(f"vdjx_lineage_threshold: nearest int32[n] and length uint32[n], not shapes {np.shape(nearest)} and {np.shape(length)}")
+        ints = (unit, max_k, peak_shift, valley[0], valley[1], min_values)
+        if not all(isinstance(x, (int, np.integer)) and -(1 << 31) <= int(x) < 1 << 31 for x in ints) or int(unit) < 0:
+            raise VdjxError(f"vdjx_lineage_threshold: unit {unit}, max_k {max_k}, peak_shift {peak_shift}, valley {valley}, min_values {min_values}")
+        prm = _lib.ThresholdParams(int(max_k), int(peak_shift), int(valley[0]), int(valley[1]), int(min_values))
+        rows = int(max_k) if 1 <= int(max_k) <= _lib.THRESHOLD_MAX_K else 1          # (a count the library refuses: nothing is written)
+        hist = np.zeros(_lib.THRESHOLD_GRID + 1, np.uint32)
+        dens = np.zeros(_lib.THRESHOLD_GRID + 1, np.uint64)
+        peaks = np.zeros((rows, 2), np.uint32)
+        info = _lib.ThresholdInfo()
+        check(self.L.vdjx_lineage_threshold(self.h, _p(near), _p(ln), near.shape[0], int(unit), C.byref(prm), _p(hist), _p(dens), _p(peaks), C.byref(info)),
+              "vdjx_lineage_threshold")
+        return {"hist": hist, "density": dens, "peaks": peaks, "info": {f: int(getattr(info, f)) for f in self.THRESHOLD_FIELDS}}
+
     TREE_FIELDS = ("members", "clones", "largest_clone", "rounds", "edges", "weight")
 
     def tree(self, contigs, clone, anchor, prio=None):

@@ -5,7 +5,7 @@
  *   vdjer --in <reads> --chain IGH|IGK|IGL --ref-dir <dir> --ins <n> [--t --k --mf --mq --mcs --am --miw --maw
  *         --jc --ws -jext --rf --vk --mrs --rs --ms --e0 --e1 --wo --vf --jf --rms] [--gpus N] [--quant <file>] [--quant-boot <B>] [--quant-seed <s>] [--airr <file>]
  *         [--d-calls] [--cfa <fasta>] [--isotypes <file>] [--clones <file>] [--sample <name>] [--total-count <n>]
- *         [--lineages <file>] [--lineage-dist <x>] [--lineage-model <file>] [--lineage-symmetry avg|min] [--trees <file>] [--tree-support <B>] [--tree-seed <s>] [--mutations <file>]
+ *         [--lineages <file>] [--lineage-dist <x>] [--lineage-model <file>] [--lineage-symmetry avg|min] [--lineage-threshold <file>] [--trees <file>] [--tree-support <B>] [--tree-seed <s>] [--mutations <file>]
  *         [--diversity <file>] [--diversity-depth <n>] [--diversity-boot <B>] [--diversity-seed <s>]
  *         [--selection <file>] [--v-regions <file>] [--targeting <file>]
  *         [--targeting-model <file>] [--targeting-class s|rs] [--targeting-min-sub <n>] [--targeting-min-mut <n>] [--targeting-counts <file>]
@@ -23,7 +23,10 @@
  * --lineages): a 5-mer targeting model in the format --targeting reads; the junctions are then compared under its substitution distance
  * (vdjx_lineage_distance_table, vdjx_lineage_model: Change-O DefineClones --model hh_s5f), --lineage-dist in units of a mean mismatch;
  * --lineage-symmetry avg|min: both directions of a mismatch added (default) or twice the cheaper.  The file must exist beforehand: a run does
- * not read the --targeting-model file it is writing itself.  --trees <file> (with --lineages):
+ * not read the --targeting-model file it is writing itself.  --lineage-threshold <file> (with --lineages): the threshold is chosen from
+ * the distances to the nearest neighbour of a first pair pass (vdjx_lineage_threshold: shazam's findThreshold, the valley between their two
+ * modes) and the pass runs once more with it; the file gets the histogram and the smoothed density; where no valley is found --lineage-dist
+ * stands.  --trees <file> (with --lineages):
  * the tree inside every lineage (vdjx_tree: the minimum spanning tree under the Hamming distance over the members' common window around
  * the junction, rooted at the member closest to its germline V); --tree-support <B> (with --trees): a support column, the share of B
  * delete-half jackknife replicates whose tree has the edge to the parent (vdjx_tree_support), the columns drawn from --tree-seed <s>.
@@ -97,6 +100,7 @@ typedef struct {
 	int lin_num, lin_den;
 	const char *lin_model, *lin_symmetry;  /* --lineage-model <file>: a --targeting file, read by parse() into lin_table (NULL: Hamming); --lineage-symmetry avg|min -> lin_sym */
 	int lin_sym; uint16_t* lin_table; vdjx_lineage_table_info lin_ti;
+	const char* lin_threshold;             /* --lineage-threshold <file>: choose --lineage-dist from the nearest distances (vdjx_lineage_threshold) and write its histogram and density */
 	const char* trees;                     /* --trees <file> (not in the reference): the tree inside every lineage of --lineages, on the device */
 	const char *tree_support, *tree_seed;  /* --tree-support <B>, --tree-seed <s>: the jackknife support of the trees' edges; read into ts_b (0: none) and ts_seed */
 	uint32_t ts_b; uint64_t ts_seed;
@@ -140,6 +144,7 @@ static void usage(void) {
 	                "\t--lineage-dist <largest linked distance as a fraction of the junction length, in [0,1], at most 4 decimals (default: 0.15)>\n"
 	                "\t--lineage-model <file: with --lineages, a 5-mer targeting model as --targeting reads it: link under its substitution distance, --lineage-dist in mean mismatches>\n"
 	                "\t--lineage-symmetry <avg|min: with --lineage-model, add both directions of a mismatch (default: avg) or take twice the cheaper>\n"
+	                "\t--lineage-threshold <file: with --lineages, choose the threshold from the distances to the nearest neighbour (the valley between their two modes; --lineage-dist stands when there is none) and write their histogram and smoothed density>\n"
 	                "\t--trees <file: with --lineages, the minimum spanning tree inside every lineage: parent, distance and depth of every contig>\n"
 	                "\t--tree-support <B: with --trees, a support column from B delete-half jackknife replicates, a whole number in 1 .. 1024>\n"
 	                "\t--tree-seed <seed of the replicates' columns, a whole number below 2^64 (default: 1)>\n"
@@ -315,6 +320,7 @@ static int parse(int argc, char** argv, cli* c) {
 		else if (!strcmp(a, "--lineage-dist")) c->lineage_dist = v;
 		else if (!strcmp(a, "--lineage-model")) c->lin_model = v;
 		else if (!strcmp(a, "--lineage-symmetry")) c->lin_symmetry = v;
+		else if (!strcmp(a, "--lineage-threshold")) c->lin_threshold = v;
 		else if (!strcmp(a, "--trees")) c->trees = v;
 		else if (!strcmp(a, "--tree-support")) c->tree_support = v;
 		else if (!strcmp(a, "--tree-seed")) c->tree_seed = v;
@@ -417,6 +423,7 @@ static int parse(int argc, char** argv, cli* c) {
 			free(w);
 		}
 	}
+	if (c->lin_threshold && !c->lineages) { fprintf(stderr, "--lineage-threshold chooses the threshold of the --lineages table: it needs --lineages <file>\n"); ok = 0; }
 	if (c->trees && !c->lineages) { fprintf(stderr, "--trees writes the tree inside every lineage of the --lineages table: it needs --lineages <file>\n"); ok = 0; }
 	c->ts_b = 0;
 	c->ts_seed = 1;
@@ -838,6 +845,7 @@ typedef struct {
 	const char* lineages; int lin_num, lin_den, lin_done;
 	const uint16_t* lin_table; int lin_sym; unsigned long long lin_walked;      /* --lineage-model: the distance table (NULL: Hamming), its symmetry, the pairs walked */
 	int32_t* lin_clone; vdjx_lineage_info li;
+	const char* lin_thr; vdjx_threshold_info thi; int thr_fallback, thr_passes;    /* --lineage-threshold: the file, what was found, the --lineage-dist numerator it stands in for, the pair passes made */
 	size_t l_contigs, l_eligible;
 	/* --trees: the tree inside every lineage (tree_run, after lineage_run) */
 	const char* trees; vdjx_tree_info ti;
@@ -1349,6 +1357,8 @@ static int clones_table(hook_ud* u, const char* const* ids, const char* contigs,
 static int lineage_run(hook_ud* u, const char* const* ids, const char* contigs, size_t n, int len) {
 	FILE* fp = fopen(u->lineages, "w");
 	if (!fp) { fprintf(stderr, "cannot write %s\n", u->lineages); return -1; }
+	FILE* tfp = u->lin_thr ? fopen(u->lin_thr, "w") : NULL;
+	if (u->lin_thr && !tfp) { fprintf(stderr, "cannot write %s\n", u->lin_thr); fclose(fp); return -1; }
 	const int counted = u->quant || u->clones;
 	const uint32_t B = counted && u->qboot ? u->qb_b : 0;      /* --quant-boot: clone_count_sd */
 	char* cat = (char*) malloc(n * (size_t) VDJX_LINEAGE_MAXLEN + 1);
@@ -1395,6 +1405,41 @@ static int lineage_run(hook_ud* u, const char* const* ids, const char* contigs, 
 	int rc = u->lin_table ? vdjx_lineage_model(u->gx, cat, off, grp, n, &lmp, u->lin_table, u->lin_clone, near, &u->li)
 	                      : vdjx_lineage(u->gx, cat, off, grp, n, &lp, u->lin_clone, near, &u->li);
 	if (rc) fprintf(stderr, "--lineages: %s\n", vdjx_last_error());
+	/* --lineage-threshold: the valley of the nearest distances of that pass (the model: include/vdjx.h, vdjx_lineage_threshold); where one is
+	 * found and it is not the threshold the pass ran with, the pass runs once more with it.  Otherwise --lineage-dist stands */
+	u->thr_fallback = u->lin_num;
+	u->thr_passes = 1;
+	if (!rc && tfp) {
+		const vdjx_threshold_params tp = {200, 5, 1, 2, 10};
+		uint32_t* lens = (uint32_t*) calloc(n + 1, sizeof(uint32_t));
+		uint32_t* hist = (uint32_t*) calloc(VDJX_THRESHOLD_GRID + 1, sizeof(uint32_t));
+		uint64_t* dens = (uint64_t*) calloc(VDJX_THRESHOLD_GRID + 1, sizeof(uint64_t));
+		for (size_t i = 0; i < n; i++) lens[i] = (uint32_t) (off[i + 1] - off[i]);
+		rc = vdjx_lineage_threshold(u->gx, near, lens, n, u->lin_table ? 2000u : 1u, &tp, hist, dens, NULL, &u->thi);
+		if (rc) fprintf(stderr, "--lineage-threshold: %s\n", vdjx_last_error());
+		if (!rc && u->thi.status == VDJX_THRESHOLD_FOUND && (int) u->thi.threshold != u->lin_num) {
+			u->lin_num = (int) u->thi.threshold;           /* (lin_den is 10000, the grid's unit) */
+			const vdjx_lineage_params lp2 = {u->lin_num, u->lin_den};
+			const vdjx_lineage_model_params lmp2 = {u->lin_num, u->lin_den, u->lin_sym};
+			rc = u->lin_table ? vdjx_lineage_model(u->gx, cat, off, grp, n, &lmp2, u->lin_table, u->lin_clone, near, &u->li)
+			                  : vdjx_lineage(u->gx, cat, off, grp, n, &lp2, u->lin_clone, near, &u->li);
+			if (rc) fprintf(stderr, "--lineages: %s\n", vdjx_last_error());
+			u->thr_passes = 2;
+		}
+		if (!rc) {
+			static const char* const names[5] = {"found", "too few values", "no scale", "one mode", "shallow valley"};
+			const vdjx_threshold_info* t = &u->thi;
+			fprintf(tfp, "# status\t%s\n# values\t%u\n# distinct\t%u\n# bandwidth\t%.3f\n", names[t->status <= 4 ? t->status : 0], t->values, t->distinct, t->k / 1000.0);
+			fprintf(tfp, "# peak1\t%.4f\t%.4f\t%llu\n# peak2\t%.4f\t%.4f\t%llu\n", t->p1_first / 10000.0, t->p1_last / 10000.0, (unsigned long long) t->y1,
+			        t->p2_first / 10000.0, t->p2_last / 10000.0, (unsigned long long) t->y2);
+			fprintf(tfp, "# valley\t%.4f\t%.4f\t%llu\n# threshold\t%.4f\n# scale\t%u\n", t->t_first / 10000.0, t->t_last / 10000.0, (unsigned long long) t->m,
+			        u->lin_num / 10000.0, 1u << 30);
+			fputs("dist\tcount\tdensity\n", tfp);
+			for (uint32_t g = 0; g <= VDJX_THRESHOLD_GRID; g++) fprintf(tfp, "%.4f\t%u\t%llu\n", g / 10000.0, hist[g], (unsigned long long) dens[g]);
+		}
+		free(lens); free(hist); free(dens);
+	}
+	if (tfp && fclose(tfp)) { fprintf(stderr, "cannot write %s\n", u->lin_thr); rc = -1; }
 	if (!rc && u->lin_table) u->lin_walked = vdjx_stat(u->gx, "lineage_model_walked");
 	const double unit = u->lin_table ? 2000.0 : 1.0;      /* dist_nearest: in mean mismatches per base under a model */
 	if (!rc) {
@@ -2119,7 +2164,7 @@ int main(int argc, char** argv) {
 	ud.qb_b = c.qb_b; ud.qb_seed = c.qb_seed;
 	ud.gx = gx; ud.p = &c.hp; ud.mg = mg; ud.quant = c.quant; ud.airr = c.airr; ud.vdjf = c.vdj_fasta; ud.d_calls = c.d_calls;
 	ud.cfa = c.cfa; ud.isotypes = c.isotypes; ud.clones = c.clones; ud.total_count = c.total_count;
-	ud.lineages = c.lineages; ud.lin_num = c.lin_num; ud.lin_den = c.lin_den; ud.lin_table = c.lin_table; ud.lin_sym = c.lin_sym; ud.trees = c.trees;
+	ud.lineages = c.lineages; ud.lin_num = c.lin_num; ud.lin_den = c.lin_den; ud.lin_table = c.lin_table; ud.lin_sym = c.lin_sym; ud.lin_thr = c.lin_threshold; ud.trees = c.trees;
 	ud.ts_b = c.ts_b; ud.ts_seed = c.ts_seed; ud.mutations = c.mutations;
 	ud.diversity = c.diversity; ud.dv_depth = c.div_depth; ud.dv_boot = c.div_boot; ud.dv_seed = c.div_seed;
 	ud.selection = c.selection; ud.regs = c.regs; ud.nregs = c.nregs; ud.weight = c.weight; ud.have_regs = c.v_regions != NULL;
@@ -2181,10 +2226,20 @@ int main(int argc, char** argv) {
 		        VDJX_DCALL_WINDOW, ud.d_called, ud.dset ? ud.dset->n : (size_t) 0);
 	if (c.lineages)
 		fprintf(stderr, "lineages: %zu contigs, %zu eligible, %u buckets (largest %u), %llu pairs, %llu links, %u lineages at %d/%d\n", ud.l_contigs, ud.l_eligible,
-		        ud.li.buckets, ud.li.largest_bucket, (unsigned long long) ud.li.pairs, (unsigned long long) ud.li.links, ud.li.clones, c.lin_num, c.lin_den);
+		        ud.li.buckets, ud.li.largest_bucket, (unsigned long long) ud.li.pairs, (unsigned long long) ud.li.links, ud.li.clones, ud.lin_num, ud.lin_den);
 	if (c.lin_model)
 		fprintf(stderr, "lineage model: %s, symmetry %s, mean %.4f, costs %u .. %u, %llu of %llu ordered pairs walked\n", c.lin_model, c.lin_sym ? "min" : "avg",
 		        c.lin_ti.mean, c.lin_ti.min_cost, c.lin_ti.max_cost, ud.lin_walked, 2ull * (unsigned long long) ud.li.pairs);
+	if (c.lin_threshold) {
+		static const char* const why[5] = {"", "too few values", "no scale", "one mode", "shallow valley"};
+		const vdjx_threshold_info* t = &ud.thi;
+		if (t->status == VDJX_THRESHOLD_FOUND)
+			fprintf(stderr, "lineage threshold: %u distances in %u bins, bandwidth %.3f, peaks %.4f %.4f, valley %.4f .. %.4f, threshold %.4f, %d pair passes\n", t->values,
+			        t->distinct, t->k / 1000.0, t->p1_first / 10000.0, t->p2_first / 10000.0, t->t_first / 10000.0, t->t_last / 10000.0, t->threshold / 10000.0, ud.thr_passes);
+		else
+			fprintf(stderr, "lineage threshold: %u distances in %u bins, none (%s), --lineage-dist %.4f stands\n", t->values, t->distinct, why[t->status <= 4 ? t->status : 0],
+			        ud.thr_fallback / 10000.0);
+	}
 	if (c.trees)
 		fprintf(stderr, "trees: %u contigs in %u lineages (largest %u), %llu edges, total distance %llu, %u rounds\n", ud.ti.members, ud.ti.clones, ud.ti.largest_clone,
 		        (unsigned long long) ud.ti.edges, (unsigned long long) ud.ti.weight, ud.ti.rounds);

@@ -790,9 +790,10 @@ int vdjx_mutations(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const 
  *               [(G + 1)][K][VDJX_SEL_GRID].
  *   info        (may be NULL; zeroed first) contigs = n; used: rows with flag 1; no_regions: flag 32; truncated: flag 16; groups = G;
  *               regions = K; chunks: the partial sums of large rows (below), over both regions; large_rows: the rows that had them.
- * NOT modelled: shazam's fitted priors (BAYESIAN_FITTED); its convolution of the members' densities -- a group here is a SHARED sigma, not
- * the distribution of a weighted mean of the members'; IMGT numbering (the regions are the caller's intervals); N-averaged 5-mers; one
- * representative per clone for the sample row (run it on vdjx_consensus_hits' pseudo-contigs for that); the J segment; the comparison of two groups' densities.
+ * A group row here is a SHARED sigma; shazam's group density -- the convolution of the members' densities -- and the comparison of two groups'
+ * densities are vdjx_selection_convolve and vdjx_selection_compare, below.
+ * NOT modelled: shazam's fitted priors (BAYESIAN_FITTED); IMGT numbering (the regions are the caller's intervals); N-averaged 5-mers; one
+ * representative per clone for the sample row (run it on vdjx_consensus_hits' pseudo-contigs for that); the J segment.
  * VDJX_EINVAL (the message names the contig or the record): vdjx_mutations' list for the contigs, the V hits and the limit; n_records is not
  * the number of records given to vdjx_germline_load; an interval of a V record with start > end, start < 1 or end past the record; group[i]
  * >= G; G >= 2^20; out_pdf with G + 1 > 65,536; NULL out_counts or out_stat.  VDJX_ESTATE: no germline set is loaded.  n = 0 returns at
@@ -811,6 +812,61 @@ int vdjx_selection(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const 
                    size_t n_records, const uint32_t* weight /* 1024 * 4, or NULL */, const int32_t* group, uint32_t G,
                    vdjx_sel_counts* out_counts /* n */, vdjx_sel_stat* out_stat /* (n + G + 1) * K, row-major */,
                    double* out_pdf /* NULL, or (G + 1) * K * 4001: the group rows, then the sample row */, vdjx_sel_info* info);
+
+/* ---- BASELINe's group posteriors: the members' own posteriors, convolved; and the comparison of two densities ------------------------------
+ * gives `vdjer --selection-combine mean` and `--selection-test` what shazam's groupBaseline / summarizeBaseline / testBaseline make of the
+ * members' densities: the density of a row is the distribution of the weighted MEAN of its members' independent sigmas, in which every
+ * member counts once, not the posterior of one sigma shared by all of them.  The model in Python: tests/selection_conv_model.py.
+ *   inputs      counts[n]: the count rows vdjx_selection returned (or handmade ones; only obs_r, obs_s, exp_r and exp_s are read); K: the
+ *               regions, 1 or 2; group[n] and G as vdjx_selection takes them.  Rows: the G groups, then all contigs; out_stat[row * K +
+ *               region], out_pdf (may be NULL) [(G + 1)][K][VDJX_SEL_GRID].
+ *   leaves      the contributing members of a row in a region are those vdjx_selection counts in `sequences` (n > 0, exp_r[k] > 0, the sum
+ *               of exp_s > 0), in contig order.  Member i's leaf is its own posterior as a MASS vector m_i[t] = f_t / S, f and S as
+ *               vdjx_selection defines them for a row holding that member alone (the prior times its likelihood); weight 1.
+ *   tree        depends only on the number m of leaves: a row of one is its leaf; a row of m > 1 combines the result of its first
+ *               h = 2^(ceil(log2 m) - 1) leaves (weight h) with the result of the other m - h.  (Rounds of adjacent pairs with an odd last
+ *               entry passed through build this tree, and so does a binary counter over blocks of leaves.)
+ *   combine     (A, a) (+) (B, b) -> (C, a + b): the distribution of (a sigma_A + b sigma_B) / (a + b), put back on the grid by mass-
+ *               conserving linear binning.  With u, v = -2000 .. 2000 (grid index - 2000), den = a + b, num = a u + b v, q = floor(num / den),
+ *               rem = num - q den (integers): the mass A[u] B[v] goes to C[q] with the share (den - rem) / den and to C[q + 1] with rem / den;
+ *               with rem = 0 cell q + 1 gets nothing and is neither read nor written (u = v = 2000: q + 1 is past the grid).  Equivalently
+ *               C[c] = sum over |a u + b v - c den| < den of A[u] B[v] (den - |a u + b v - c den|) / den.  All terms are non-negative; in
+ *               exact arithmetic the sum of C is 1 and its mean the weighted mean of the means.
+ *   root        S' = sum C; pdf_t = C[t] / (0.01 S'); sigma, lower, upper and p_positive from C / S' by vdjx_selection's rules (the quantiles
+ *               are grid points; half of grid point 0 counts as positive).  sequences, x, n, exp_r, exp_s: the members' sums, as there.  A
+ *               row without a contributing member is the prior: sigma 0, p_positive 1/2.
+ *   order       no floating-point atomics; one thread owns an output cell and sums its terms in a register.  a = b: B'[s] = (B[s - 1] / 2 +
+ *               B[s]) + B[s + 1] / 2 first, then C[c] = sum over u ASCENDING of A[u] B'[2c - u], one fused multiply-add per term.  a > b (the
+ *               left side of a tree's combination is never the lighter one): v ascending, inside it u ascending, each term (A[u] B[v]) *
+ *               ((den - |a u + b v - c den|) * (1 / den)).  Two calls give the same bits, with any VDJX_CONV_CELLS.
+ *   info        (may be NULL; zeroed first) members: the contributing members summed over rows and regions; leaves: the leaf densities
+ *               evaluated (members, plus one prior per row and region without a member); combines; groups = G; regions = K; rows = (G + 1)
+ *               K; levels: the deepest tree, ceil(log2 m); batches.
+ * VDJX_EINVAL: K outside 1 .. 2; group[i] >= G; G >= 2^20; n >= 2^20; out_pdf with G + 1 > 65,536; G > 0 without a group array; NULL counts
+ * or out_stat.  n = 0 returns at once with a zeroed info.  Needs no germline set.  Three kernels: k_conv_leaf (a workgroup per leaf),
+ * k_conv_combine (one launch per level of the rows in flight; a workgroup per combination and tile of 256 output cells, both densities in
+ * LDS) and k_conv_finish (a workgroup per row); the host lays out every launch of the call first, nothing is read back in between.  A
+ * density is 32 KB: VDJX_CONV_CELLS (4 .. 2^20, default 32,768 = 1 GB, read per call) is the number held at once.  Whole rows go in batches
+ * (a row of m leaves holds m + m / 2 densities at its first level); a row that does not fit goes alone, in blocks of a power of two of leaves
+ * whose roots meet on a stack the way a binary counter's digits do -- the same tree, so the same bits -- and holds ceil(log2 m) + 3 densities
+ * even where the knob asks for fewer.  Scratch comes from the context's workspace.  Stats: "selconv_us" (host clock), "selconv_combines",
+ * "selconv_batches".
+ *
+ * vdjx_selection_compare (plain host code, needs no device and no context; shazam's testBaseline): pdf holds `rows` densities of
+ * VDJX_SEL_GRID values each (any positive scale: each is divided by its own sum); pair[P][2] names the rows a and b of every comparison.
+ *   p_greater = sum over t ascending of a[t] (sum over s < t of b[s] + b[t] / 2): P(sigma_a > sigma_b) plus half of P(equal); float64, at most 1.
+ *   pvalue = min(1, 2 min(p_greater, 1 - p_greater)).   fdr: Benjamini-Hochberg over the P' comparisons that are not skipped, sorted
+ *   ascending by pvalue with ties in row order: fdr_(i) = min(1, min over j >= i of pvalue_(j) P' / j).   skip (may be NULL): 1 leaves the
+ *   comparison's three values 0 and out of the fdr.   VDJX_EINVAL: a row index >= rows; NULL pdf, pair or out (with P > 0).
+ * NOT modelled: shazam's fitted priors; the FFT resampling of its weighted_conv (the binning here is linear); comparisons between lineages
+ * and groupings other than lineages on vdjer's command line (this call takes any grouping, that one any pair of rows). */
+typedef struct { uint64_t members, leaves, combines; uint32_t groups, regions, rows, levels, batches, pad; } vdjx_selconv_info;   /* 48 bytes */
+typedef struct { double p_greater, pvalue, fdr; } vdjx_sel_test;                                                                /* 24 bytes */
+int vdjx_selection_convolve(vdjx_ctx* ctx, const vdjx_sel_counts* counts, size_t n, uint32_t K /* 1 or 2 */, const int32_t* group, uint32_t G,
+                            vdjx_sel_stat* out_stat /* (G + 1) * K: the groups, then all contigs */,
+                            double* out_pdf /* NULL, or (G + 1) * K * 4001 */, vdjx_selconv_info* info);
+int vdjx_selection_compare(const double* pdf, size_t rows, const uint32_t* pair /* P x 2: row a, row b */, size_t P,
+                           const uint8_t* skip /* NULL, or P: 1 = leave the row empty and out of the fdr */, vdjx_sel_test* out);
 
 /* ---- the sample's own 5-mer targeting model: which 5-mers mutate, and to which base (S5F) ---------------------------------------------
  * gives `vdjer --targeting-model` what shazam's createTargetingModel (createSubstitutionMatrix, createMutabilityMatrix,
@@ -992,6 +1048,7 @@ int vdjx_part_u64(vdjx_ctx* ctx, const void* host_in, size_t n, int elem_bytes, 
  * where no hit was traced, more than 1 where the direction bytes of the hits exceed one launch's).
  * vdjx_mutations' last call: "mutations_cols" (the bytes of each of the three row buffers), "mutations_us" (host clock).
  * vdjx_selection's last call: "selection_chunks" (the partial sums of its large rows), "selection_us" (host clock).
+ * vdjx_selection_convolve's last call: "selconv_combines", "selconv_batches", "selconv_us" (host clock).
  * vdjx_diversity's last call: "diversity_batches", "diversity_us" (host clock).
  * vdjx_targeting_counts' last call: "targeting_units", "targeting_batches", "targeting_us" (host clock).
  * vdjx_consensus' last call: "consensus_units", "consensus_batches", "consensus_us" (host clock).

@@ -407,6 +407,33 @@ def quant_boot_summary(boot):
     return out
 
 
+def selection_compare(pdf, pairs, skip=None):
+    """vdjx_selection_compare (plain C, no GPU; shazam's testBaseline) over densities float64[rows, 4001] (any positive scale) and pairs
+    [P, 2] of rows (a, b) -> dict of float64[P]: p_greater = P(sigma_a > sigma_b) + P(equal) / 2, pvalue = min(1, 2 min(p_greater,
+    1 - p_greater)) and the Benjamini-Hochberg fdr over the pairs.  skip: None, or P flags; a flagged pair stays 0 and out of the fdr"""
+    import ctypes as C
+
+    import numpy as np
+
+    from . import _lib
+    pdf = np.ascontiguousarray(pdf, np.float64)
+    if pdf.ndim != 2 or pdf.shape[1] != 4001:
+        raise ValueError(f"densities of shape [rows, 4001], not {pdf.shape}")
+    pr = np.ascontiguousarray(pairs, np.uint32).reshape(-1, 2)
+    P = pr.shape[0]
+    sk = None if skip is None else np.ascontiguousarray(skip, np.uint8)
+    if sk is not None and sk.shape != (P,):
+        raise ValueError(f"{P} pairs, skip of shape {sk.shape}")
+    out = np.zeros((P, 3), np.float64)
+    L = _lib.lib()
+    rc = L.vdjx_selection_compare(pdf.ctypes.data_as(C.c_void_p), pdf.shape[0], pr.ctypes.data_as(C.c_void_p), P,
+                                  None if sk is None else sk.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p))
+    if rc:
+        L.vdjx_last_error.restype = C.c_char_p
+        raise ValueError(L.vdjx_last_error().decode())
+    return {"p_greater": out[:, 0].copy(), "pvalue": out[:, 1].copy(), "fdr": out[:, 2].copy()}
+
+
 def diversity_weights(clone, count_cells):
     """what `vdjer --diversity` hands to vdjx_diversity, from the lineage of every contig (Context.lineage's "clone"; -1: in none) and the
     printed expected_count cell of every contig ("12.34": two decimals, as the quant table has them) -> (uint64[C] weights, int list of

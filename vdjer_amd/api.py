@@ -879,6 +879,39 @@ class Context:
                 "stat": {f: stat[f].copy() for f in self.SEL_STAT.names if f != "pad"}, "pdf": dens,
                 "info": {f: int(getattr(info, f)) for f in self.SEL_INFO_FIELDS}}
 
+    SELCONV_INFO_FIELDS = ("members", "leaves", "combines", "groups", "regions", "rows", "levels", "batches")
+
+    def selection_convolve(self, counts, regions, group=None, groups=None, pdf: bool = False):
+        """vdjx_selection_convolve: BASELINe's group posteriors -- per group and for all contigs the distribution of the mean of the
+        contributing members' independent sigmas (their own posteriors, convolved).  counts: the "counts" dict selection() returns (or
+        handmade: obs_r, obs_s, exp_r, exp_s of shape [n, 2]; codons and flags are not read); regions: K, 1 or 2; group: int32[n]
+        (negative: in no group) or None; groups: G (None: max(group) + 1) -> {"stat": {field: array[G + 1, K]}, "pdf": float64[G + 1, K,
+        4001] | None, "info": dict}"""
+        n = len(np.asarray(counts["obs_r"]))
+        raw = np.zeros(n, self.SEL_COUNTS)
+        for f in ("obs_r", "obs_s", "exp_r", "exp_s"):
+            a = np.asarray(counts[f])
+            if a.shape != (n, 2):
+                raise VdjxError(f"vdjx_selection_convolve: {n} contigs, {f} of shape {a.shape}")
+            raw[f] = a
+        for f in ("codons", "flags"):
+            if f in counts:
+                raw[f] = np.asarray(counts[f])
+        grp = None if group is None else np.ascontiguousarray(group, np.int32)
+        if grp is not None and grp.shape != (n,):
+            raise VdjxError(f"vdjx_selection_convolve: {n} contigs, group of shape {grp.shape}")
+        g = int(groups) if groups is not None else (int(grp.max()) + 1 if grp is not None and n and int(grp.max()) >= 0 else 0)
+        k = int(regions)
+        if not 0 <= g < 1 << 32 or not 0 <= k < 1 << 32:
+            raise VdjxError(f"vdjx_selection_convolve: {g} groups, {k} regions")
+        refused = g >= 1 << 20 or not 1 <= k <= 2                       # (what the library refuses: nothing is written)
+        stat = np.zeros((1, 1) if refused else (g + 1, k), self.SEL_STAT)
+        dens = (np.zeros(1) if refused or g + 1 > 65536 else np.zeros((g + 1, k, 4001))) if pdf else None
+        info = _lib.SelConvInfo()
+        check(self.L.vdjx_selection_convolve(self.h, _p(raw), n, k, _p(grp), g, _p(stat), _p(dens), C.byref(info)), "vdjx_selection_convolve")
+        return {"stat": {f: stat[f].copy() for f in self.SEL_STAT.names if f != "pad"}, "pdf": dens,
+                "info": {f: int(getattr(info, f)) for f in self.SELCONV_INFO_FIELDS}}
+
     TGT_INFO_FIELDS = ("contigs", "used", "truncated", "units", "positions", "obs_s", "obs_r", "opp_s", "opp_r", "batches")
 
     def targeting_counts(self, contigs, v, limit=None, group=None):

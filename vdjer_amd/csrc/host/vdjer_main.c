@@ -7,7 +7,7 @@
  *         [--d-calls] [--cfa <fasta>] [--isotypes <file>] [--clones <file>] [--sample <name>] [--total-count <n>]
  *         [--lineages <file>] [--lineage-dist <x>] [--lineage-model <file>] [--lineage-symmetry avg|min] [--lineage-threshold <file>] [--trees <file>] [--tree-support <B>] [--tree-seed <s>] [--mutations <file>]
  *         [--diversity <file>] [--diversity-depth <n>] [--diversity-boot <B>] [--diversity-seed <s>]
- *         [--selection <file>] [--v-regions <file>] [--targeting <file>]
+ *         [--selection <file>] [--v-regions <file>] [--targeting <file>] [--selection-combine shared|mean] [--selection-test <file>]
  *         [--targeting-model <file>] [--targeting-class s|rs] [--targeting-min-sub <n>] [--targeting-min-mut <n>] [--targeting-counts <file>]
  *         [--consensus <file>] [--consensus-min-freq <x>]
  * writes ./vdj_contigs.fa and ./vdjer.dot, SAM on stdout, log on stderr; exit 0 on success.  --quant <file>: the contigs' abundances
@@ -40,6 +40,9 @@
  * groupBaseline / summarizeBaseline): observed against expected replacement and silent mutations and the posterior of sigma for every
  * contig, every lineage (with --lineages) and the sample, below --mutations' limit; --v-regions <file>: the CDR1 / CDR2 intervals of the V
  * records, which split every row into fwr and cdr; --targeting <file>: a 5-mer targeting model (default: uniform).
+ * --selection-combine shared|mean (with --selection): the lineage, sample and consensus_sample rows as one sigma shared by the members
+ * (default) or as the mean of the members' independent sigmas, their densities convolved (vdjx_selection_convolve: groupBaseline);
+ * --selection-test <file> (with --selection and --v-regions): cdr against fwr for each of those rows (vdjx_selection_compare: testBaseline).
  * --targeting-model <file>: the sample's own 5-mer targeting model in the format --targeting reads (vdjx_targeting_counts and
  * vdjx_targeting_model: shazam's createTargetingModel), learnt from the V segments below --mutations' limit, a lineage of --lineages over
  * one V record counted once; --targeting-class s|rs: from silent changes only (default) or silent and replacement; --targeting-min-sub
@@ -110,6 +113,8 @@ typedef struct {
 	uint32_t div_depth, div_boot; uint64_t div_seed;
 	const char* selection;                 /* --selection <file> (not in the reference): shazam's BASELINe over the V segment, on the device */
 	const char *v_regions, *targeting;     /* --v-regions <file>, --targeting <file>: read by parse() into regs / nregs and weight (NULL: uniform) */
+	const char *sel_combine, *sel_test;    /* --selection-combine shared|mean (read into sel_mean), --selection-test <file>: cdr against fwr per lineage and sample */
+	int sel_mean;
 	struct vreg_line* regs; size_t nregs;
 	uint32_t* weight;
 	const char* tgt_model;                 /* --targeting-model <file> (not in the reference): shazam's createTargetingModel, on the device */
@@ -155,6 +160,8 @@ static void usage(void) {
 	                "\t--diversity-seed <seed of the draws, a whole number below 2^64 (default: 1)>\n"
 	                "\t--selection <file: selection strength (BASELINe) of the V mutations: observed and expected R / S and the posterior of sigma per contig, lineage (with --lineages) and sample>\n"
 	                "\t--v-regions <file: with --selection, lines `name cdr1_start cdr1_end cdr2_start cdr2_end` (1-based, inclusive, 0 0: none) of the V records: rows fwr and cdr>\n"
+	                "\t--selection-combine <shared|mean: with --selection, the lineage and sample rows as one shared sigma (default) or as BASELINe's mean of the members' sigmas (their densities convolved)>\n"
+	                "\t--selection-test <file: with --selection and --v-regions, cdr against fwr per lineage and sample: P(sigma_cdr > sigma_fwr), two-sided p-value, Benjamini-Hochberg fdr>\n"
 	                "\t--targeting <file: with --selection, 1024 lines `<5-mer> <wA> <wC> <wG> <wT>`, whole numbers below 2^32 (default: uniform)>\n"
 	                "\t--targeting-model <file: the sample's own 5-mer targeting model, in the format --targeting reads, learnt from the V mutations (a lineage of --lineages counted once)>\n"
 	                "\t--targeting-class <s|rs: with --targeting-model, learn from silent changes only (default: s) or from silent and replacement>\n"
@@ -331,6 +338,8 @@ static int parse(int argc, char** argv, cli* c) {
 		else if (!strcmp(a, "--diversity-seed")) c->div_seed_s = v;
 		else if (!strcmp(a, "--selection")) c->selection = v;
 		else if (!strcmp(a, "--v-regions")) c->v_regions = v;
+		else if (!strcmp(a, "--selection-combine")) c->sel_combine = v;
+		else if (!strcmp(a, "--selection-test")) c->sel_test = v;
 		else if (!strcmp(a, "--targeting")) c->targeting = v;
 		else if (!strcmp(a, "--targeting-model")) c->tgt_model = v;
 		else if (!strcmp(a, "--targeting-class")) c->tgt_class = v;
@@ -465,6 +474,11 @@ static int parse(int argc, char** argv, cli* c) {
 	}
 	if (c->v_regions && !c->selection) { fprintf(stderr, "--v-regions is the region map of the --selection table: it needs --selection <file>\n"); ok = 0; }
 	if (c->targeting && !c->selection) { fprintf(stderr, "--targeting is the targeting model of the --selection table: it needs --selection <file>\n"); ok = 0; }
+	if (c->sel_combine && strcmp(c->sel_combine, "shared") && strcmp(c->sel_combine, "mean")) { fprintf(stderr, "--selection-combine must be shared or mean: %s\n", c->sel_combine); ok = 0; }
+	if (c->sel_combine && !c->selection) { fprintf(stderr, "--selection-combine is how the --selection table combines the members of a row: it needs --selection <file>\n"); ok = 0; }
+	if (c->sel_test && !c->selection) { fprintf(stderr, "--selection-test compares the densities of the --selection table: it needs --selection <file>\n"); ok = 0; }
+	if (c->sel_test && !c->v_regions) { fprintf(stderr, "--selection-test compares the cdr rows with the fwr rows: it needs --v-regions <file>\n"); ok = 0; }
+	c->sel_mean = c->sel_combine && !strcmp(c->sel_combine, "mean");
 	if (c->v_regions && c->selection && read_v_regions(c->v_regions, &c->regs, &c->nregs)) ok = 0;
 	if (c->targeting && c->selection && read_targeting("--targeting", c->targeting, &c->weight)) ok = 0;
 	c->cons_num = 6000;
@@ -860,6 +874,7 @@ typedef struct {
 	/* --selection: the selection strength of the V mutations (sel_run, after lineage_run) */
 	const char* selection; const struct vreg_line* regs; size_t nregs; const uint32_t* weight; int have_regs, sel_done;
 	vdjx_sel_info si; double sel_sigma[2]; size_t sel_unmatched;
+	int sel_mean; const char* sel_test; vdjx_selconv_info sci; double sel_msigma[2];      /* --selection-combine mean, --selection-test */
 	/* --targeting-model: the sample's own targeting model (tgt_run, after lineage_run) */
 	const char *tgt_model, *tgt_counts; int tgt_cls, tgt_done; uint64_t tgt_min_sub, tgt_min_mut;
 	vdjx_tgt_info tgi; unsigned tgt_levels[2][4];      /* [substitution, mutability][level 5, 3, 1, 0]: the 5-mers on it */
@@ -1618,12 +1633,54 @@ static void sel_rows(FILE* fp, const char* level, const char* id, const vdjx_sel
 	}
 }
 
+/* --selection-combine mean: the posterior cells of the rows st[rows * K] from the members' densities (vdjx_selection_convolve over the
+ * counts a vdjx_selection call returned); the counts of a row are the same in both, so the whole stat is taken.  The infos add up. */
+static int sel_mean_rows(hook_ud* u, const vdjx_sel_counts* cnt, size_t n, uint32_t K, const int32_t* group, uint32_t G, vdjx_sel_stat* st, double* pdf) {
+	vdjx_selconv_info ci;
+	const int rc = vdjx_selection_convolve(u->gx, cnt, n, K, group, G, st, pdf, &ci);
+	if (rc) { fprintf(stderr, "--selection-combine: %s\n", vdjx_last_error()); return rc; }
+	u->sci.members += ci.members; u->sci.leaves += ci.leaves; u->sci.combines += ci.combines;
+	u->sci.rows += ci.rows; u->sci.batches += ci.batches;
+	if (ci.levels > u->sci.levels) u->sci.levels = ci.levels;
+	return 0;
+}
+
+static double sel_no_minus_zero(double sg) { return sg > -0.00005 && sg < 0.0 ? 0.0 : sg; }
+
+/* --selection-test: cdr against fwr for every lineage, the sample and the consensus sample (vdjx_selection_compare; the densities are the
+ * chosen combine mode's).  st / pdf: the T rows of 2 regions in table order; a side without a contributing sequence leaves the cells empty. */
+static int sel_test_write(const char* path, const char* const* level, char* const* id, size_t T, const vdjx_sel_stat* st, const double* pdf) {
+	FILE* fp = fopen(path, "w");
+	if (!fp) { fprintf(stderr, "cannot write %s\n", path); return -1; }
+	fputs("level\tid\tregion_a\tregion_b\tsigma_a\tsigma_b\tp_greater\tpvalue\tfdr\n", fp);
+	int rc = 0;
+	if (T) {
+		uint32_t* pair = (uint32_t*) malloc(T * 2 * sizeof(uint32_t));
+		uint8_t* skip = (uint8_t*) malloc(T);
+		vdjx_sel_test* out = (vdjx_sel_test*) calloc(T, sizeof(vdjx_sel_test));
+		for (size_t r = 0; r < T; r++) {
+			pair[2 * r] = (uint32_t) (2 * r + 1); pair[2 * r + 1] = (uint32_t) (2 * r);      /* a = cdr (region 1), b = fwr (region 0) */
+			skip[r] = !st[2 * r].sequences || !st[2 * r + 1].sequences;
+		}
+		rc = vdjx_selection_compare(pdf, 2 * T, pair, T, skip, out);
+		if (rc) fprintf(stderr, "--selection-test: %s\n", vdjx_last_error());
+		for (size_t r = 0; r < T && !rc; r++) {
+			if (skip[r]) fprintf(fp, "%s\t%s\tcdr\tfwr\t\t\t\t\t\n", level[r], id[r]);
+			else fprintf(fp, "%s\t%s\tcdr\tfwr\t%.4f\t%.4f\t%.4f\t%.4f\t%.4f\n", level[r], id[r], sel_no_minus_zero(st[2 * r + 1].sigma), sel_no_minus_zero(st[2 * r].sigma),
+			             out[r].p_greater, out[r].pvalue, out[r].fdr);
+		}
+		free(pair); free(skip); free(out);
+	}
+	if (fclose(fp) && !rc) { fprintf(stderr, "cannot write %s\n", path); return -1; }
+	return rc;
+}
+
 static int sel_run(hook_ud* u, const char* const* ids, const char* contigs, size_t n, int len) {
 	FILE* fp = fopen(u->selection, "w");
 	if (!fp) { fprintf(stderr, "cannot write %s\n", u->selection); return -1; }
 	fputs("level\tid\tregion\tsequences\tobs_r\tobs_s\texp_r\texp_s\tsigma\tsigma_lower\tsigma_upper\tp_positive\n", fp);
 	const uint32_t K = u->have_regs ? 2 : 1, G = u->lineages && n ? u->li.clones : 0;
-	int rc = 0;
+	int rc = 0, test_refused = 0;
 	if (n) {
 		const germ_set* g = u->germ;
 		int32_t* cdr = NULL;
@@ -1642,8 +1699,24 @@ static int sel_run(hook_ud* u, const char* const* ids, const char* contigs, size
 		int32_t* lim = mutation_limits(ids, contigs, n, len);
 		vdjx_sel_counts* cnt = (vdjx_sel_counts*) calloc(n + 1, sizeof(vdjx_sel_counts));
 		vdjx_sel_stat* st = (vdjx_sel_stat*) calloc((n + G + 1) * (size_t) K, sizeof(vdjx_sel_stat));
-		rc = vdjx_selection(u->gx, contigs, n, len, u->hv, lim, cdr, g->n, u->weight, G ? u->lin_clone : NULL, G, cnt, st, NULL, &u->si);
+		/* --selection-test: the densities of the lineage and sample rows, and of the consensus sample behind them: T rows of K = 2 */
+		const int with_cs = u->consensus && u->cs_units;
+		const size_t T = (size_t) G + 1 + (with_cs ? 1 : 0);
+		int test = u->sel_test != NULL;
+		if (test && (uint64_t) G + 1 > 65536) {
+			fprintf(stderr, "--selection-test: %u lineages (at most 65535): the test table is not written\n", G);
+			test = 0; test_refused = 1;
+		}
+		double* pdf = test ? (double*) malloc(T * K * VDJX_SEL_GRID * sizeof(double)) : NULL;
+		vdjx_sel_stat* tst = test ? (vdjx_sel_stat*) calloc(T * K, sizeof(vdjx_sel_stat)) : NULL;
+		rc = vdjx_selection(u->gx, contigs, n, len, u->hv, lim, cdr, g->n, u->weight, G ? u->lin_clone : NULL, G, cnt, st, u->sel_mean ? NULL : pdf, &u->si);
 		if (rc) fprintf(stderr, "--selection: %s\n", vdjx_last_error());
+		if (!rc && u->sel_mean) {
+			for (uint32_t k = 0; k < K; k++) u->sel_sigma[k] = sel_no_minus_zero(st[(n + G) * (size_t) K + k].sigma);      /* the selection: line keeps the shared sigma */
+			rc = sel_mean_rows(u, cnt, n, K, G ? u->lin_clone : NULL, G, st + n * (size_t) K, pdf);
+			for (uint32_t k = 0; k < K && !rc; k++) u->sel_msigma[k] = sel_no_minus_zero(st[(n + G) * (size_t) K + k].sigma);
+		}
+		if (!rc && test) memcpy(tst, st + n * (size_t) K, ((size_t) G + 1) * K * sizeof(vdjx_sel_stat));
 		if (!rc) {
 			for (size_t i = 0; i < n; i++) {
 				if (cnt[i].flags & 1) sel_rows(fp, "sequence", ids[i], st + i * K, K);
@@ -1660,8 +1733,11 @@ static int sel_run(hook_ud* u, const char* const* ids, const char* contigs, size
 				const size_t U = u->cs_units;
 				vdjx_sel_counts* cnt2 = (vdjx_sel_counts*) calloc(U + 1, sizeof(vdjx_sel_counts));
 				vdjx_sel_stat* st2 = (vdjx_sel_stat*) calloc((U + 1) * (size_t) K, sizeof(vdjx_sel_stat));
-				rc = vdjx_selection(u->gx, u->cs_pc, U, u->cs_plen, u->cs_hv, NULL, cdr, g->n, u->weight, NULL, 0, cnt2, st2, NULL, NULL);
+				double* pdf2 = test ? pdf + ((size_t) G + 1) * K * VDJX_SEL_GRID : NULL;
+				rc = vdjx_selection(u->gx, u->cs_pc, U, u->cs_plen, u->cs_hv, NULL, cdr, g->n, u->weight, NULL, 0, cnt2, st2, u->sel_mean ? NULL : pdf2, NULL);
 				if (rc) fprintf(stderr, "--selection: %s\n", vdjx_last_error());
+				if (!rc && u->sel_mean) rc = sel_mean_rows(u, cnt2, U, K, NULL, 0, st2 + U * (size_t) K, pdf2);
+				if (!rc && test) memcpy(tst + ((size_t) G + 1) * K, st2 + U * (size_t) K, K * sizeof(vdjx_sel_stat));
 				for (size_t k = 0; k < U && !rc; k++) {
 					char id[32];
 					snprintf(id, sizeof id, "lin_%d", u->cs_un[k].group + 1);
@@ -1672,18 +1748,33 @@ static int sel_run(hook_ud* u, const char* const* ids, const char* contigs, size
 				if (!rc) sel_rows(fp, "consensus_sample", u->sample, st2 + U * (size_t) K, K);
 				free(cnt2); free(st2);
 			}
-			for (uint32_t k = 0; k < K; k++) {
+			for (uint32_t k = 0; k < K && !u->sel_mean; k++) {       /* (mean: kept before the rows were replaced) */
 				const double sg = st[(n + G) * (size_t) K + k].sigma;
 				u->sel_sigma[k] = sg > -0.00005 && sg < 0.0 ? 0.0 : sg;
 			}
 		}
-		free(cdr); free(lim); free(cnt); free(st);
+		if (!rc && test) {
+			const char** level = (const char**) malloc(T * sizeof(char*));
+			char** id = (char**) malloc(T * sizeof(char*));
+			for (size_t r = 0; r < T; r++) {
+				level[r] = r < G ? "lineage" : r == G ? "sample" : "consensus_sample";
+				id[r] = (char*) malloc(r < G ? 32 : strlen(u->sample) + 1);
+				if (r < G) snprintf(id[r], 32, "lin_%zu", r + 1);
+				else strcpy(id[r], u->sample);
+			}
+			rc = sel_test_write(u->sel_test, level, id, T, tst, pdf);
+			for (size_t r = 0; r < T; r++) free(id[r]);
+			free(level); free(id);
+		}
+		free(cdr); free(lim); free(cnt); free(st); free(pdf); free(tst);
+	} else if (u->sel_test) {
+		rc = sel_test_write(u->sel_test, NULL, NULL, 0, NULL, NULL);
 	}
 	u->si.groups = G;
 	u->si.regions = K;
 	if (fclose(fp) && !rc) { fprintf(stderr, "cannot write %s\n", u->selection); return -1; }
 	if (!rc) u->sel_done = 1;
-	return rc;
+	return rc ? rc : test_refused ? -1 : 0;
 }
 
 /* --targeting-model: the sample's own 5-mer targeting model (the model: include/vdjx.h, vdjx_targeting_counts and vdjx_targeting_model),
@@ -2168,6 +2259,7 @@ int main(int argc, char** argv) {
 	ud.ts_b = c.ts_b; ud.ts_seed = c.ts_seed; ud.mutations = c.mutations;
 	ud.diversity = c.diversity; ud.dv_depth = c.div_depth; ud.dv_boot = c.div_boot; ud.dv_seed = c.div_seed;
 	ud.selection = c.selection; ud.regs = c.regs; ud.nregs = c.nregs; ud.weight = c.weight; ud.have_regs = c.v_regions != NULL;
+	ud.sel_mean = c.sel_mean; ud.sel_test = c.sel_test;
 	ud.tgt_model = c.tgt_model; ud.tgt_counts = c.tgt_counts; ud.tgt_cls = c.tgt_cls; ud.tgt_min_sub = c.tgt_min_sub; ud.tgt_min_mut = c.tgt_min_mut;
 	ud.consensus = c.consensus; ud.cons_num = c.cons_num;
 	char sample_buf[4096];
@@ -2266,6 +2358,12 @@ int main(int argc, char** argv) {
 		        (unsigned long long) ud.si.used, (unsigned long long) ud.si.no_regions, ud.si.groups, ud.si.regions, c.targeting ? c.targeting : "uniform", ud.sel_sigma[0]);
 		if (ud.si.regions == 2) fprintf(stderr, " %.4f", ud.sel_sigma[1]);
 		fprintf(stderr, ", %u chunks\n", ud.si.chunks);
+		if (c.sel_mean) {
+			fprintf(stderr, "selection combine: mean, %u rows, %llu densities, %llu combinations, %u levels at most, %u batches, sample sigma %.4f", ud.sci.rows,
+			        (unsigned long long) ud.sci.leaves, (unsigned long long) ud.sci.combines, ud.sci.levels, ud.sci.batches, ud.sel_msigma[0]);
+			if (ud.si.regions == 2) fprintf(stderr, " %.4f", ud.sel_msigma[1]);
+			fputc('\n', stderr);
+		}
 	}
 	if (c.tgt_model)
 		fprintf(stderr, "targeting model: %llu contigs, %llu used, %llu units, %llu positions, %llu S, %llu R, class %s, substitution levels %u/%u/%u/%u, mutability levels %u/%u/%u/%u, %u batches\n",

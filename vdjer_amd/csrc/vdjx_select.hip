@@ -23,12 +23,9 @@
 //                  points), the two quantile indices, sigma and p_positive; one 72-byte stat and, where asked, the density.
 // No float atomics; every sum runs in a fixed order, so two calls with the same VDJX_SEL_CHUNK give the same bits.
 #include "vdjx_vhit.h"
-
-#include <math.h>
+#include "vdjx_selpost.h"
 
 #define SEL_WAVES 4
-#define SEL_T VDJX_SEL_GRID
-#define SEL_PER 16                       // grid points a thread of k_sel_finish owns: 256 * 16 >= 4001
 
 struct SelContig {
 	u32 run_off;                         // V's runs in the pool
@@ -43,7 +40,6 @@ struct SelContig {
 	int cdr[4];                          // 1-based, inclusive; 0, 0: no such interval (all four 0 without a region map)
 	int pad[3];
 };
-struct SelMember { u32 x, n; double lo; };            // a contig in a region: x of n, ln exp_r - ln sum exp_s; n = 0: adds nothing
 struct SelRow {                          // a row in a region
 	u32 start, count;                    // its members in the region's member array
 	u32 sequences;
@@ -53,7 +49,7 @@ struct SelRow {                          // a row in a region
 };
 struct SelItem { u32 start, count, part, region; };    // a chunk of a large row's members
 #define SEL_DIRECT 0xFFFFFFFFu
-static_assert(sizeof(SelContig) == 64 && sizeof(vdjx_sel_counts) == 64 && sizeof(vdjx_sel_stat) == 72 && sizeof(SelMember) == 16 && sizeof(SelRow) == 56,
+static_assert(sizeof(SelContig) == 64 && sizeof(SelRow) == 56,
               "uploaded / returned as they are");
 
 __global__ __launch_bounds__(64 * SEL_WAVES) void k_sel_counts(const char* __restrict__ contigs, u32 n, u32 len, const SelContig* __restrict__ sc,
@@ -133,49 +129,13 @@ __global__ __launch_bounds__(64 * SEL_WAVES) void k_sel_counts(const char* __res
 }
 
 // ---- the posterior -------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double sel_softplus(double z) { return fmax(z, 0.0) + log1p(exp(-fabs(z))); }
-__device__ __forceinline__ double sel_sigma(int t) { return (double) (t - 2000) / 100.0; }
-
-// the members' terms at one grid point, in member order, from 0
-__device__ __forceinline__ double sel_terms(const SelMember* __restrict__ m, u32 count, double sg) {
-	double acc = 0.0;
-	for (u32 k = 0; k < count; k++) {
-		const SelMember e = m[k];            // (uniform across the workgroup)
-		if (e.n == 0) continue;
-		const double z = sg + e.lo;
-		acc += (double) e.x * z - (double) e.n * sel_softplus(z);
-	}
-	return acc;
-}
-
+// (sel_softplus, sel_sigma, sel_terms, the block reductions and the finish of a row: vdjx_selpost.h)
 __global__ __launch_bounds__(256) void k_sel_loglik(const SelMember* __restrict__ members, size_t region_stride, const SelItem* __restrict__ items,
                                                     double* __restrict__ partial) {
 	const SelItem it = items[blockIdx.y];
 	const int t = (int) (blockIdx.x * 256 + threadIdx.x);
 	if (t >= SEL_T) return;              // (the last tile: 161 of 256)
 	partial[(size_t) it.part * SEL_T + (size_t) t] = sel_terms(members + (size_t) it.region * region_stride + it.start, it.count, sel_sigma(t));
-}
-
-__device__ __forceinline__ double sel_shfl_xor(double v, int o) {
-	return __longlong_as_double((long long) vdjx_shfl_xor64((u64) __double_as_longlong(v), o));
-}
-
-// the block's sum / maximum of one value per thread, in a fixed order: inside a wave by a butterfly, the four waves in order
-__device__ __forceinline__ double sel_block_sum(double v, double* red) {
-#pragma unroll
-	for (int o = 32; o >= 1; o >>= 1) v += sel_shfl_xor(v, o);
-	__syncthreads();
-	if ((threadIdx.x & 63u) == 0) red[threadIdx.x >> 6] = v;
-	__syncthreads();
-	return ((red[0] + red[1]) + red[2]) + red[3];
-}
-__device__ __forceinline__ double sel_block_max(double v, double* red) {
-#pragma unroll
-	for (int o = 32; o >= 1; o >>= 1) v = fmax(v, sel_shfl_xor(v, o));
-	__syncthreads();
-	if ((threadIdx.x & 63u) == 0) red[threadIdx.x >> 6] = v;
-	__syncthreads();
-	return fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
 }
 
 __global__ __launch_bounds__(256) void k_sel_finish(const SelMember* __restrict__ members, size_t region_stride, const SelRow* __restrict__ rows,
@@ -204,77 +164,13 @@ __global__ __launch_bounds__(256) void k_sel_finish(const SelMember* __restrict_
 		mx = fmax(mx, l);
 	}
 	mx = sel_block_max(mx, red);         // (its barriers publish ell)
-	// f over 16 consecutive grid points per thread
+	// f over 16 consecutive grid points per thread, then the row's finish
 	const int t0 = (int) tid * SEL_PER;
 	double f[SEL_PER];
-	double loc = 0.0, sw = 0.0, pos = 0.0;
 #pragma unroll
-	for (int j = 0; j < SEL_PER; j++) {
-		const int t = t0 + j;
-		f[j] = t < SEL_T ? exp(ell[t] - mx) : 0.0;
-		loc += f[j];
-		sw += sel_sigma(t) * f[j];
-		pos += t > 2000 ? f[j] : t == 2000 ? 0.5 * f[j] : 0.0;
-	}
-	// the exclusive scan of the threads' totals: the wave's by shuffles, the waves' in order
-	double inc = loc;
-#pragma unroll
-	for (int o = 1; o < 64; o <<= 1) {
-		const long long b = __double_as_longlong(inc);
-		const u32 lo = (u32) __shfl_up((int) (u32) b, o, 64), hi = (u32) __shfl_up((int) (u32) ((u64) b >> 32), o, 64);
-		const double up = __longlong_as_double((long long) ((u64) hi << 32 | lo));
-		if ((int) (tid & 63u) >= o) inc += up;
-	}
-	tot[tid] = inc;
-	__syncthreads();
-	const u32 wv = tid >> 6;
-	double base = 0.0;
-	for (u32 k = 0; k < wv; k++) base += tot[64 * k + 63];
-	const double S = ((tot[63] + tot[127]) + tot[191]) + tot[255];
-	double run = base + (inc - loc);
-	int first[2] = {SEL_T, SEL_T};
-#pragma unroll
-	for (int j = 0; j < SEL_PER; j++) {
-		run += f[j];
-		const double cdf = run / S;
-		const int t = t0 + j;
-		if (t < SEL_T) {
-			if (cdf >= 0.025 && first[0] == SEL_T) first[0] = t;
-			if (cdf >= 0.975 && first[1] == SEL_T) first[1] = t;
-		}
-	}
-#pragma unroll
-	for (int k = 0; k < 2; k++) {
-		int v = first[k];
-#pragma unroll
-		for (int o = 32; o >= 1; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-		if ((tid & 63u) == 0) qidx[k][wv] = v;
-	}
-	const double ssum = sel_block_sum(sw, red);      // (its barriers publish qidx)
-	const double psum = sel_block_sum(pos, red);
-	if (tid == 0) {
-		int qi[2];
-		for (int k = 0; k < 2; k++) qi[k] = min(min(min(qidx[k][0], qidx[k][1]), min(qidx[k][2], qidx[k][3])), SEL_T - 1);
-		vdjx_sel_stat s;
-		s.sequences = rw.sequences;
-		s.pad = 0;
-		s.x = rw.x; s.n = rw.n; s.exp_r = rw.exp_r; s.exp_s = rw.exp_s;
-		s.sigma = ssum / S;
-		s.lower = sel_sigma(qi[0]);
-		s.upper = sel_sigma(qi[1]);
-		s.p_positive = psum / S;
-		out_stat[(size_t) row * K + region] = s;
-	}
-	if (out_pdf && rw.pdf) {
-		double* o = out_pdf + ((size_t) (rw.pdf - 1) * K + region) * SEL_T;
-		const double den = 0.01 * S;
-		__syncthreads();                     // (rw is the workgroup's: all of it comes here)
-#pragma unroll
-		for (int j = 0; j < SEL_PER; j++)
-			if (t0 + j < SEL_T) ell[t0 + j] = f[j] / den;
-		__syncthreads();
-		for (int t = (int) tid; t < SEL_T; t += 256) o[t] = ell[t];      // (through LDS: neighbouring threads store neighbouring doubles)
-	}
+	for (int j = 0; j < SEL_PER; j++) f[j] = t0 + j < SEL_T ? exp(ell[t0 + j] - mx) : 0.0;
+	sel_finish_tail(f, ell, tot, red, qidx, rw.sequences, rw.x, rw.n, rw.exp_r, rw.exp_s, out_stat + (size_t) row * K + region,
+	                out_pdf && rw.pdf ? out_pdf + ((size_t) (rw.pdf - 1) * K + region) * SEL_T : nullptr);
 }
 
 // ---- the host's side -------------------------------------------------------------------------------------------------------------------------
@@ -373,16 +269,8 @@ extern "C" int vdjx_selection(vdjx_ctx* c, const char* contigs, size_t n, int le
 	HIP_TRY(hipGetLastError());
 
 	// the members: per region the contigs in order, then the grouped contigs by group (contig order inside a group)
-	std::vector<u32> gstart(G + 1, 0), gorder;
-	if (G) {
-		for (size_t i = 0; i < n; i++)
-			if (group[i] >= 0) gstart[(u32) group[i] + 1]++;
-		for (u32 g = 0; g < G; g++) gstart[g + 1] += gstart[g];
-		gorder.resize(gstart[G]);
-		std::vector<u32> at(gstart.begin(), gstart.end() - 1);
-		for (size_t i = 0; i < n; i++)
-			if (group[i] >= 0) gorder[at[(u32) group[i]]++] = (u32) i;
-	}
+	std::vector<u32> gstart, gorder;
+	sel_group_order(group, n, G, gstart, gorder);
 	const size_t ng = gorder.size(), stride = n + ng, nrows = n + G + 1;
 	std::vector<SelMember> mem(K * stride);
 	std::vector<SelRow> rows(K * nrows);
@@ -392,15 +280,7 @@ extern "C" int vdjx_selection(vdjx_ctx* c, const char* contigs, size_t n, int le
 	for (size_t i = 0; i < n; i++) used += (out_counts[i].flags & 1u) != 0;
 	for (u32 k = 0; k < K; k++) {
 		SelMember* m = mem.data() + k * stride;
-		for (size_t i = 0; i < n; i++) {
-			const vdjx_sel_counts& r = out_counts[i];
-			u64 ss = 0, es = 0;
-			for (u32 j = 0; j < K; j++) { ss += (u64) r.obs_s[j]; es += r.exp_s[j]; }
-			const u64 x = (u64) r.obs_r[k], nn = x + ss;
-			SelMember e = {0u, 0u, 0.0};
-			if (nn > 0 && r.exp_r[k] > 0 && es > 0) { e.x = (u32) x; e.n = (u32) nn; e.lo = log((double) r.exp_r[k]) - log((double) es); }
-			m[i] = e;
-		}
+		for (size_t i = 0; i < n; i++) m[i] = sel_member(out_counts[i], k, K);
 		for (size_t a = 0; a < ng; a++) m[n + a] = m[gorder[a]];
 		SelRow* rw = rows.data() + k * nrows;
 		for (size_t r = 0; r < nrows; r++) {

@@ -76,9 +76,10 @@ def test_root_scorer(tag):
         assert 0 < info["ones"] < info["n"]               # both verdicts
 
 
-def parse_map(name):
+def parse_map(name, text=None):
+    """the W / P / S rows of a `vdjer_ref map` dump (tests/golden/<name>, or `text` as the binary printed it: tests/ref_live.py)"""
     out = []
-    for l in G.text(name).splitlines():
+    for l in (G.text(name) if text is None else text).splitlines():
         f = l.split("\t")
         if f[0] == "W":
             out.append({"valid": int(f[2]), "n": int(f[3]), "pairs": [], "starts": []})

@@ -492,8 +492,8 @@ int vdjx_dcall(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const int3
  * Defaults (what `vdjer --lineages` uses): num / den = 1500 / 10000, the 0.15 SCOPer documents as a starting point.  It is a parameter of
  * the model, not a tolerance: out_nearest (the table's dist_nearest) is there so that a user can choose their own from its histogram, and
  * vdjx_lineage_threshold, below, chooses it from that histogram on the device.
- * NOT modelled: amino-acid distances (a 5-mer substitution distance: vdjx_lineage_model, below); N as a wildcard; average or complete
- * linkage; clustering across samples; "first gene only" handling of tied V calls (the group is the caller's: `vdjer` keys on the whole
+ * NOT modelled: amino-acid distances (a 5-mer substitution distance: vdjx_lineage_model, below); N as a wildcard; clustering across
+ * samples (complete and average linkage: vdjx_lineage_link, below); "first gene only" handling of tied V calls (the group is the caller's: `vdjer` keys on the whole
  * normalised tie list).
  * VDJX_EINVAL: n >= 2^20, a participating item of 0 or more than VDJX_LINEAGE_MAXLEN bases, offsets that decrease, den < 1, den > 10^6,
  * num < 0, num > den, NULL out_clone.  n = 0 returns at once with a zeroed info.  The (group, L, index) keys are sorted on the host (per
@@ -534,7 +534,7 @@ int vdjx_lineage(vdjx_ctx* ctx, const char* junctions, const uint64_t* off, cons
  *   link        iff D * den <= 2000 * num * L: num / den is still a fraction of the length, now in units of a mean mismatch.
  *   nearest     the smallest D > 0 in the bucket, -1 when there is none (D = 0 iff the junctions are equal and all ACGT).
  * NOT modelled: shazam's NN padding with N-averaged 5-mers at the junction's ends (a position without a full ACGT 5-mer costs the mean);
- * amino-acid distances; any linkage other than single.  (A threshold chosen automatically: vdjx_lineage_threshold, below, unit 2000.)
+ * amino-acid distances.  (Complete and average linkage: vdjx_lineage_link, below.  A threshold chosen automatically: vdjx_lineage_threshold, below, unit 2000.)
  * VDJX_EINVAL, beyond vdjx_lineage's: symmetry not 0 or 1, a NULL table, an off-centre cell of 0.  The host re-indexes the table to the packed
  * rows' code order; a call is five dispatches whatever n is (pack, k_lin_pairs_model, flatten, number, out).  The pair pass first takes the
  * Hamming count h of a pair: every counted position costs at least cmin = 2 * min(1000, smallest cell), so a pair with h * cmin past both the
@@ -548,6 +548,49 @@ int vdjx_lineage_distance_table(const uint32_t* weight /* [1024][4] */, uint16_t
 int vdjx_lineage_model(vdjx_ctx* ctx, const char* junctions, const uint64_t* off, const uint32_t* group, size_t n,
                        const vdjx_lineage_model_params* params, const uint16_t* table /* [1024][4] */, int32_t* out_clone,
                        int32_t* out_nearest, vdjx_lineage_info* info);
+
+/* ---- clonal lineages under complete and average linkage ----------------------------------------------------------------------------------
+ * gives `vdjer --lineages --lineage-link` what Change-O's DefineClones --link single|average|complete and SCOPer's hierarchicalClones(linkage =)
+ * offer against the chaining of single linkage: two unrelated clones of one bucket no longer become one lineage through a run of
+ * intermediates.  All arithmetic is integer; the device's results are bitwise the model's (tests/lineage_link_model.py).
+ *   items, buckets, D(i, j), nearest   vdjx_lineage's (table NULL: D is the Hamming count d, unit = 1) or vdjx_lineage_model's (D the model's
+ *               sum, unit = 2000; params->symmetry is looked at only then).  N never matches.  K = unit * num * L; a pair is linked iff
+ *               D * den <= K.
+ *   clusters    inside a bucket they start as the single items; a cluster's id is its smallest member index in the caller's order.  The
+ *               dissimilarity of two clusters A, B is, under linkage 1 (complete), delta = max D(a, b) over a in A, b in B, and the pair is
+ *               eligible iff delta * den <= K; under linkage 2 (average, UPGMA), S(A, B) = the sum of D(a, b), delta = S / (|A| |B|), eligible
+ *               iff S * den <= K |A| |B|.  Among all eligible pairs with id(A) < id(B) the smallest under the strict order (delta, id(A),
+ *               id(B)) is merged -- under average linkage delta is compared exactly, S1 n2 against S2 n1 --, the merged cluster keeps id(A),
+ *               and this repeats until no pair is eligible.  The Lance-Williams updates are exact integers: max, and S(A u B, C) = S(A, C) +
+ *               S(B, C).  Both linkages are reducible, so stopping at the threshold is cutting the dendrogram at it (cutree(h =),
+ *               fcluster(criterion = 'distance')).  Where distances tie the partition depends on the caller's order of the items: the tie
+ *               rule above is the definition.  Linkage 0 (single) returns bit for bit what vdjx_lineage (table NULL) or vdjx_lineage_model
+ *               returns, and a zeroed link info.
+ *   out_clone   the final clusters numbered in the order of their smallest member.
+ *   info        the single-linkage pass': links and pairs keep their meaning; clones is the final number.
+ *   link        (may be NULL; zeroed first) components: single-linkage components of two and more members; largest_component;
+ *               merges; clones_single: the clones of linkage 0; batches; cells: matrix cells built (m * m for a component of m).
+ * Two facts shape the implementation.  (1) Only linked components need agglomerating: a merge needs at least one linked cross pair (complete:
+ * every cross pair is linked; average: the mean is at most the cut, so some pair is), so the final clusters refine the single-linkage
+ * components and no merge ever crosses two of them.  The device agglomerates per component of the pair pass, never per bucket (the test
+ * model agglomerates whole buckets).  (2) Everything fits 64 bits: a component has at most 4,096 members, so |A| |B| <= 2^22; K <= 2000 *
+ * 10^6 * 255 < 2^39, so K |A| |B| < 2^61; eligibility is tested as S <= floor(K |A| |B| / den), the same predicate for an integer S with no
+ * product of S and den; only eligible pairs are ever ordered, and for them S <= 510,000 * 2^22 < 2^41, so S1 n2 < 2^63.
+ * The device: the members of the components of two and more are laid out in component order (components by their smallest member, members by
+ * index; on the host from the flattened roots, per item) and go in batches of whole components of at most VDJX_LINK_CELLS matrix cells
+ * (default 2^26, 1 .. 2^28, read per call; a component of more cells goes alone; any value gives the same bytes).  Per batch k_link_matrix
+ * (k_link_matrix_model under a table) builds every component's full matrix and k_link_merge agglomerates a component per workgroup, with a
+ * cached best partner per cluster, so that a merge costs the row update and the repair of the caches that pointed at A or B; components of
+ * up to 88 members keep their matrix in LDS.  No floating point, no atomic whose order shows: two calls give the same bits.
+ * VDJX_EINVAL: what vdjx_lineage refuses, with a table what vdjx_lineage_model refuses, a linkage outside 0 .. 2.  VDJX_ELIMIT: under linkage
+ * 1 or 2 a single-linkage component of more than 4,096 members (the message names its size); single linkage has no such limit.
+ * NOT modelled: Ward or median linkage; a dendrogram as output; a threshold per bucket.
+ * Stats: vdjx_lineage's (and vdjx_lineage_model's), "lineage_link_us" (host clock from the roots to the last launch), "lineage_link_cells". */
+typedef struct { int num, den, symmetry, linkage; } vdjx_lineage_link_params;   /* 16 bytes */
+typedef struct { uint32_t components, largest_component, merges, clones_single, batches, reserved; uint64_t cells; } vdjx_lineage_link_info;  /* 32 bytes */
+int vdjx_lineage_link(vdjx_ctx* ctx, const char* junctions, const uint64_t* off, const uint32_t* group, size_t n,
+                      const vdjx_lineage_link_params* params, const uint16_t* table /* [1024][4]; NULL: Hamming */, int32_t* out_clone,
+                      int32_t* out_nearest, vdjx_lineage_info* info, vdjx_lineage_link_info* link);
 
 /* ---- the lineage threshold: the valley between the two modes of the nearest-neighbour distances ----------------------------------------
  * gives `vdjer --lineages --lineage-threshold` what shazam's findThreshold(method = "density") makes of distToNearest before DefineClones

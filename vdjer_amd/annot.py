@@ -90,6 +90,16 @@ def vq_gene(names) -> str:
 
 LINEAGE_NONE = 0xFFFFFFFF                                   # VDJX_LINEAGE_NONE (include/vdjx.h)
 LINEAGE_MAXLEN = 255                                        # VDJX_LINEAGE_MAXLEN
+LINEAGE_LINKAGE = {"single": 0, "complete": 1, "average": 2}    # --lineage-link <name> -> vdjx_lineage_link_params.linkage
+LINEAGE_LINK_NAMES = tuple(LINEAGE_LINKAGE)                 # ... and back: LINEAGE_LINK_NAMES[linkage]
+LINEAGE_LINK_MAX = 4096                                     # members of a single-linkage component under complete or average linkage
+
+
+def parse_lineage_link(text: str):
+    """--lineage-link: single, complete or average -> vdjx_lineage_link_params.linkage; ValueError otherwise"""
+    if text not in LINEAGE_LINKAGE:
+        raise ValueError(f"--lineage-link must be single, complete or average: {text!r}")
+    return LINEAGE_LINKAGE[text]
 
 
 def junction_of(seq_id: str, contig: str):

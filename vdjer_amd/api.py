@@ -985,7 +985,7 @@ class Context:
         non-zero distance inside the bucket, -1: none), "info": dict(items, buckets, largest_bucket, clones, pairs, links)}.
         table: uint16[1024, 4] (annot.lineage_distance_table) -> vdjx_lineage_model instead: the 5-mer substitution distance D, linked when
         D * max_dist[1] <= 2000 * max_dist[0] * L, nearest in the same units; symmetry: "avg" (both directions added) or "min" (twice the
-        smaller).  Without a table the call is vdjx_lineage's and symmetry is not looked at."""
+        smaller).  Without a table the call is vdjx_lineage's and symmetry is not looked at.  (Complete and average linkage: lineage_link.)"""
         enc = [s_ if isinstance(s_, (bytes, bytearray)) else s_.encode() for s_ in junctions]
         n = len(enc)
         grp = np.ascontiguousarray(group, np.uint32)
@@ -1011,6 +1011,42 @@ class Context:
                   "vdjx_lineage_model")
         return {"clone": clone, "nearest": near,
                 "info": {f: int(getattr(info, f)) for f in ("items", "buckets", "largest_bucket", "clones", "pairs", "links")}}
+
+    LINEAGE_LINKAGE = {"single": 0, "complete": 1, "average": 2}      # vdjx_lineage_link_params.linkage
+    LINEAGE_LINK_FIELDS = ("components", "largest_component", "merges", "clones_single", "batches", "cells")
+
+    def lineage_link(self, junctions, group, max_dist=(1500, 10000), nearest: bool = True, table=None, symmetry="avg", link="complete"):
+        """vdjx_lineage_link: lineage()'s arguments, buckets, distances (Hamming, or the 5-mer distance of `table`) and nearest, the clusters
+        cut at the same threshold under another linkage.  link: "complete" or "average" ("single", or the numbers 0 .. 2: 0 gives lineage()'s
+        bits through this entry point) -> lineage()'s result, info["clones"] the final number, and one more key, "link": dict(components,
+        largest_component, merges, clones_single, batches, cells) -- all zero under single linkage."""
+        enc = [s_ if isinstance(s_, (bytes, bytearray)) else s_.encode() for s_ in junctions]
+        n = len(enc)
+        grp = np.ascontiguousarray(group, np.uint32)
+        if grp.shape != (n,):
+            raise VdjxError(f"vdjx_lineage_link: {n} junctions, group of shape {grp.shape}")
+        linkage = self.LINEAGE_LINKAGE.get(link, link) if isinstance(link, str) else link
+        if not isinstance(linkage, (int, np.integer)):
+            raise VdjxError(f"vdjx_lineage_link: link {link!r} (single, complete or average)")
+        tab = None
+        if table is not None:
+            tab = np.ascontiguousarray(table, np.uint16)
+            if tab.shape != (1024, 4) or not np.array_equal(tab, np.asarray(table)):
+                raise VdjxError(f"vdjx_lineage_link: a table of shape {np.shape(table)}, not uint16[1024, 4]")
+        sym = self.LINEAGE_SYMMETRY.get(symmetry, symmetry)
+        if not isinstance(sym, (int, np.integer)):
+            raise VdjxError(f"vdjx_lineage_link: symmetry {symmetry!r} (avg or min)")
+        off = np.zeros(n + 1, np.uint64)
+        off[1:] = np.cumsum([len(e) for e in enc], dtype=np.uint64)
+        clone = np.zeros(n, np.int32)
+        near = np.zeros(n, np.int32) if nearest else None
+        info, linfo = _lib.LineageInfo(), _lib.LineageLinkInfo()
+        prm = _lib.LineageLinkParams(int(max_dist[0]), int(max_dist[1]), int(sym), int(linkage))
+        check(self.L.vdjx_lineage_link(self.h, b"".join(enc), _p(off), _p(grp), n, C.byref(prm), _p(tab), _p(clone), _p(near), C.byref(info),
+                                       C.byref(linfo)), "vdjx_lineage_link")
+        return {"clone": clone, "nearest": near,
+                "info": {f: int(getattr(info, f)) for f in ("items", "buckets", "largest_bucket", "clones", "pairs", "links")},
+                "link": {f: int(getattr(linfo, f)) for f in self.LINEAGE_LINK_FIELDS}}
 
     THRESHOLD_STATUS = _lib.THRESHOLD_STATUS                 # info["status"] by name (VDJX_THRESHOLD_FOUND .. _SHALLOW)
     THRESHOLD_FIELDS = ("values", "distinct", "status", "k", "peaks_all", "peaks", "p1_first", "p1_last", "p2_first", "p2_last", "t_first", "t_last",

@@ -5,7 +5,7 @@
  *   vdjer --in <reads> --chain IGH|IGK|IGL --ref-dir <dir> --ins <n> [--t --k --mf --mq --mcs --am --miw --maw
  *         --jc --ws -jext --rf --vk --mrs --rs --ms --e0 --e1 --wo --vf --jf --rms] [--gpus N] [--quant <file>] [--quant-boot <B>] [--quant-seed <s>] [--airr <file>]
  *         [--d-calls] [--cfa <fasta>] [--isotypes <file>] [--clones <file>] [--sample <name>] [--total-count <n>]
- *         [--lineages <file>] [--lineage-dist <x>] [--lineage-model <file>] [--lineage-symmetry avg|min] [--lineage-threshold <file>] [--trees <file>] [--tree-support <B>] [--tree-seed <s>] [--mutations <file>]
+ *         [--lineages <file>] [--lineage-dist <x>] [--lineage-model <file>] [--lineage-symmetry avg|min] [--lineage-threshold <file>] [--lineage-link single|complete|average] [--trees <file>] [--tree-support <B>] [--tree-seed <s>] [--mutations <file>]
  *         [--diversity <file>] [--diversity-depth <n>] [--diversity-boot <B>] [--diversity-seed <s>]
  *         [--selection <file>] [--v-regions <file>] [--targeting <file>] [--selection-combine shared|mean] [--selection-test <file>]
  *         [--targeting-model <file>] [--targeting-class s|rs] [--targeting-min-sub <n>] [--targeting-min-mut <n>] [--targeting-counts <file>]
@@ -26,7 +26,8 @@
  * not read the --targeting-model file it is writing itself.  --lineage-threshold <file> (with --lineages): the threshold is chosen from
  * the distances to the nearest neighbour of a first pair pass (vdjx_lineage_threshold: shazam's findThreshold, the valley between their two
  * modes) and the pass runs once more with it; the file gets the histogram and the smoothed density; where no valley is found --lineage-dist
- * stands.  --trees <file> (with --lineages):
+ * stands.  --lineage-link single|complete|average (with --lineages): the linkage the lineages are cut at the threshold under
+ * (vdjx_lineage_link: Change-O DefineClones --link); single, the default, is the call without the flag.  --trees <file> (with --lineages):
  * the tree inside every lineage (vdjx_tree: the minimum spanning tree under the Hamming distance over the members' common window around
  * the junction, rooted at the member closest to its germline V); --tree-support <B> (with --trees): a support column, the share of B
  * delete-half jackknife replicates whose tree has the edge to the parent (vdjx_tree_support), the columns drawn from --tree-seed <s>.
@@ -104,6 +105,7 @@ typedef struct {
 	const char *lin_model, *lin_symmetry;  /* --lineage-model <file>: a --targeting file, read by parse() into lin_table (NULL: Hamming); --lineage-symmetry avg|min -> lin_sym */
 	int lin_sym; uint16_t* lin_table; vdjx_lineage_table_info lin_ti;
 	const char* lin_threshold;             /* --lineage-threshold <file>: choose --lineage-dist from the nearest distances (vdjx_lineage_threshold) and write its histogram and density */
+	const char* lin_link; int lin_linkage;  /* --lineage-link single|complete|average -> 0, 1, 2 (vdjx_lineage_link; 0: the two calls above, as without the flag) */
 	const char* trees;                     /* --trees <file> (not in the reference): the tree inside every lineage of --lineages, on the device */
 	const char *tree_support, *tree_seed;  /* --tree-support <B>, --tree-seed <s>: the jackknife support of the trees' edges; read into ts_b (0: none) and ts_seed */
 	uint32_t ts_b; uint64_t ts_seed;
@@ -150,6 +152,7 @@ static void usage(void) {
 	                "\t--lineage-model <file: with --lineages, a 5-mer targeting model as --targeting reads it: link under its substitution distance, --lineage-dist in mean mismatches>\n"
 	                "\t--lineage-symmetry <avg|min: with --lineage-model, add both directions of a mismatch (default: avg) or take twice the cheaper>\n"
 	                "\t--lineage-threshold <file: with --lineages, choose the threshold from the distances to the nearest neighbour (the valley between their two modes; --lineage-dist stands when there is none) and write their histogram and smoothed density>\n"
+	                "\t--lineage-link <single|complete|average: with --lineages, the linkage the lineages are cut at the threshold under (default: single; where distances tie, complete and average depend on the contigs' order)>\n"
 	                "\t--trees <file: with --lineages, the minimum spanning tree inside every lineage: parent, distance and depth of every contig>\n"
 	                "\t--tree-support <B: with --trees, a support column from B delete-half jackknife replicates, a whole number in 1 .. 1024>\n"
 	                "\t--tree-seed <seed of the replicates' columns, a whole number below 2^64 (default: 1)>\n"
@@ -328,6 +331,7 @@ static int parse(int argc, char** argv, cli* c) {
 		else if (!strcmp(a, "--lineage-model")) c->lin_model = v;
 		else if (!strcmp(a, "--lineage-symmetry")) c->lin_symmetry = v;
 		else if (!strcmp(a, "--lineage-threshold")) c->lin_threshold = v;
+		else if (!strcmp(a, "--lineage-link")) c->lin_link = v;
 		else if (!strcmp(a, "--trees")) c->trees = v;
 		else if (!strcmp(a, "--tree-support")) c->tree_support = v;
 		else if (!strcmp(a, "--tree-seed")) c->tree_seed = v;
@@ -433,6 +437,14 @@ static int parse(int argc, char** argv, cli* c) {
 		}
 	}
 	if (c->lin_threshold && !c->lineages) { fprintf(stderr, "--lineage-threshold chooses the threshold of the --lineages table: it needs --lineages <file>\n"); ok = 0; }
+	c->lin_linkage = 0;
+	if (c->lin_link && !c->lineages) { fprintf(stderr, "--lineage-link is the linkage of the --lineages table: it needs --lineages <file>\n"); ok = 0; }
+	if (c->lin_link) {
+		if (!strcmp(c->lin_link, "single")) c->lin_linkage = 0;
+		else if (!strcmp(c->lin_link, "complete")) c->lin_linkage = 1;
+		else if (!strcmp(c->lin_link, "average")) c->lin_linkage = 2;
+		else { fprintf(stderr, "--lineage-link must be single, complete or average: %s\n", c->lin_link); ok = 0; }
+	}
 	if (c->trees && !c->lineages) { fprintf(stderr, "--trees writes the tree inside every lineage of the --lineages table: it needs --lineages <file>\n"); ok = 0; }
 	c->ts_b = 0;
 	c->ts_seed = 1;
@@ -859,6 +871,7 @@ typedef struct {
 	const char* lineages; int lin_num, lin_den, lin_done;
 	const uint16_t* lin_table; int lin_sym; unsigned long long lin_walked;      /* --lineage-model: the distance table (NULL: Hamming), its symmetry, the pairs walked */
 	int32_t* lin_clone; vdjx_lineage_info li;
+	int lin_linkage; vdjx_lineage_link_info lki;      /* --lineage-link: 0 single (the two calls above), 1 complete, 2 average (vdjx_lineage_link) and what it reports */
 	const char* lin_thr; vdjx_threshold_info thi; int thr_fallback, thr_passes;    /* --lineage-threshold: the file, what was found, the --lineage-dist numerator it stands in for, the pair passes made */
 	size_t l_contigs, l_eligible;
 	/* --trees: the tree inside every lineage (tree_run, after lineage_run) */
@@ -1369,6 +1382,18 @@ static int clones_table(hook_ud* u, const char* const* ids, const char* contigs,
  * the index, by first appearance, of its (vgene, jgene) pair as --clones prints them.  A row per contig: clone_id lin_<k>, vgene, jgene,
  * junction_length, dist_nearest (the smallest non-zero distance inside the bucket over the length), clone_size and, when the quant step ran,
  * clone_expected_count: the sum of the members' expected_count as printed (two decimals each), so that the tables add up */
+/* one pair pass at u->lin_num / u->lin_den, under --lineage-link's linkage */
+static int lineage_pass(hook_ud* u, const char* cat, const uint64_t* off, const uint32_t* grp, size_t n, int32_t* near) {
+	const vdjx_lineage_params lp = {u->lin_num, u->lin_den};
+	const vdjx_lineage_model_params lmp = {u->lin_num, u->lin_den, u->lin_sym};
+	const vdjx_lineage_link_params lkp = {u->lin_num, u->lin_den, u->lin_sym, u->lin_linkage};
+	const int rc = u->lin_linkage ? vdjx_lineage_link(u->gx, cat, off, grp, n, &lkp, u->lin_table, u->lin_clone, near, &u->li, &u->lki)
+	             : u->lin_table   ? vdjx_lineage_model(u->gx, cat, off, grp, n, &lmp, u->lin_table, u->lin_clone, near, &u->li)
+	                              : vdjx_lineage(u->gx, cat, off, grp, n, &lp, u->lin_clone, near, &u->li);
+	if (rc) fprintf(stderr, "--lineages: %s\n", vdjx_last_error());
+	return rc;
+}
+
 static int lineage_run(hook_ud* u, const char* const* ids, const char* contigs, size_t n, int len) {
 	FILE* fp = fopen(u->lineages, "w");
 	if (!fp) { fprintf(stderr, "cannot write %s\n", u->lineages); return -1; }
@@ -1415,11 +1440,7 @@ static int lineage_run(hook_ud* u, const char* const* ids, const char* contigs, 
 		off[i + 1] = tot;
 		u->l_contigs++;
 	}
-	const vdjx_lineage_params lp = {u->lin_num, u->lin_den};
-	const vdjx_lineage_model_params lmp = {u->lin_num, u->lin_den, u->lin_sym};
-	int rc = u->lin_table ? vdjx_lineage_model(u->gx, cat, off, grp, n, &lmp, u->lin_table, u->lin_clone, near, &u->li)
-	                      : vdjx_lineage(u->gx, cat, off, grp, n, &lp, u->lin_clone, near, &u->li);
-	if (rc) fprintf(stderr, "--lineages: %s\n", vdjx_last_error());
+	int rc = lineage_pass(u, cat, off, grp, n, near);
 	/* --lineage-threshold: the valley of the nearest distances of that pass (the model: include/vdjx.h, vdjx_lineage_threshold); where one is
 	 * found and it is not the threshold the pass ran with, the pass runs once more with it.  Otherwise --lineage-dist stands */
 	u->thr_fallback = u->lin_num;
@@ -1434,11 +1455,7 @@ static int lineage_run(hook_ud* u, const char* const* ids, const char* contigs, 
 		if (rc) fprintf(stderr, "--lineage-threshold: %s\n", vdjx_last_error());
 		if (!rc && u->thi.status == VDJX_THRESHOLD_FOUND && (int) u->thi.threshold != u->lin_num) {
 			u->lin_num = (int) u->thi.threshold;           /* (lin_den is 10000, the grid's unit) */
-			const vdjx_lineage_params lp2 = {u->lin_num, u->lin_den};
-			const vdjx_lineage_model_params lmp2 = {u->lin_num, u->lin_den, u->lin_sym};
-			rc = u->lin_table ? vdjx_lineage_model(u->gx, cat, off, grp, n, &lmp2, u->lin_table, u->lin_clone, near, &u->li)
-			                  : vdjx_lineage(u->gx, cat, off, grp, n, &lp2, u->lin_clone, near, &u->li);
-			if (rc) fprintf(stderr, "--lineages: %s\n", vdjx_last_error());
+			rc = lineage_pass(u, cat, off, grp, n, near);
 			u->thr_passes = 2;
 		}
 		if (!rc) {
@@ -2255,7 +2272,7 @@ int main(int argc, char** argv) {
 	ud.qb_b = c.qb_b; ud.qb_seed = c.qb_seed;
 	ud.gx = gx; ud.p = &c.hp; ud.mg = mg; ud.quant = c.quant; ud.airr = c.airr; ud.vdjf = c.vdj_fasta; ud.d_calls = c.d_calls;
 	ud.cfa = c.cfa; ud.isotypes = c.isotypes; ud.clones = c.clones; ud.total_count = c.total_count;
-	ud.lineages = c.lineages; ud.lin_num = c.lin_num; ud.lin_den = c.lin_den; ud.lin_table = c.lin_table; ud.lin_sym = c.lin_sym; ud.lin_thr = c.lin_threshold; ud.trees = c.trees;
+	ud.lineages = c.lineages; ud.lin_num = c.lin_num; ud.lin_den = c.lin_den; ud.lin_table = c.lin_table; ud.lin_sym = c.lin_sym; ud.lin_thr = c.lin_threshold; ud.lin_linkage = c.lin_linkage; ud.trees = c.trees;
 	ud.ts_b = c.ts_b; ud.ts_seed = c.ts_seed; ud.mutations = c.mutations;
 	ud.diversity = c.diversity; ud.dv_depth = c.div_depth; ud.dv_boot = c.div_boot; ud.dv_seed = c.div_seed;
 	ud.selection = c.selection; ud.regs = c.regs; ud.nregs = c.nregs; ud.weight = c.weight; ud.have_regs = c.v_regions != NULL;
@@ -2332,6 +2349,9 @@ int main(int argc, char** argv) {
 			fprintf(stderr, "lineage threshold: %u distances in %u bins, none (%s), --lineage-dist %.4f stands\n", t->values, t->distinct, why[t->status <= 4 ? t->status : 0],
 			        ud.thr_fallback / 10000.0);
 	}
+	if (c.lin_linkage)
+		fprintf(stderr, "lineage link: %s, %u components of two and more (largest %u), %u merges, %u lineages of %u under single linkage, %u batches\n", c.lin_link,
+		        ud.lki.components, ud.lki.largest_component, ud.lki.merges, ud.li.clones, ud.lki.clones_single, ud.lki.batches);
 	if (c.trees)
 		fprintf(stderr, "trees: %u contigs in %u lineages (largest %u), %llu edges, total distance %llu, %u rounds\n", ud.ti.members, ud.ti.clones, ud.ti.largest_clone,
 		        (unsigned long long) ud.ti.edges, (unsigned long long) ud.ti.weight, ud.ti.rounds);

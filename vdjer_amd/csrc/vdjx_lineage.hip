@@ -28,8 +28,12 @@
 //                        neither a link nor a nearest and is left; the others walk the set bits of the difference mask, two look-ups each,
 //                        and stop once the running sum is past both.  What is left and where a walk stops changes no result.
 //   vdjx_lineage_distance_table   plain C, no GPU: the targeting weights -> the table (shazam's calcTargetingDistance in thousandths)
+//   vdjx_lineage_link    the same pair pass, then complete or average linkage inside its components, cut at the threshold (include/vdjx.h;
+//                        in Python: tests/lineage_link_model.py): k_link_gather, k_link_matrix / k_link_matrix_model and k_link_merge, below,
+//                        between k_lin_flatten and the scan; the host's share is vdjx_link.h
 #include "vdjx_common.h"
 #include "vdjx_hamming.h"
+#include "vdjx_link.h"
 #include "vdjx_scan.h"
 #include "vdjx_unionfind.h"
 
@@ -233,6 +237,260 @@ __global__ __launch_bounds__(256) void k_lin_out(const u32* __restrict__ root, c
 	out_nearest[i] = r == LIN_NONE || d == LIN_NONE ? -1 : (int32_t) d;
 }
 
+// ---- complete and average linkage (vdjx_lineage_link) ----------------------------------------------------------------------------------
+// Only the single-linkage components of the pair pass are agglomerated (include/vdjx.h says why no merge crosses two of them).  The host
+// puts the rows of the components of two and more in component order (vdjx_link.h) and cuts them into batches; per batch
+//   k_link_matrix / k_link_matrix_model   the full m x m matrix of every component, as work items (component, row block, column slice):
+//                  u[0] the matrix's first cell, u[1] = L | m << 8, u[2] the component's first row.  The loops are lin_item's and
+//                  lin_item_model's, kept apart from them (profiles/hamming_engine_refactor_check.md), without the filter and the early
+//                  exit: a cell holds the true D.  D is symmetric, so the lane of row r writes cell [column][r] and a wave's stores of one
+//                  column are adjacent
+//   k_link_merge   one workgroup per component: the agglomeration under the strict order (delta, id(A), id(B)), local index for id
+// A cell is 4 bytes under complete linkage (a maximum of D's) and 8 under average (a sum of them, below 2^41).
+#define LINK_LDS_M 88u                   // components up to here keep matrix and state in LDS: 88 * 88 * 8 + 88 * 20 = 63,712 bytes, two workgroups a CU
+#define LINK_THREADS 256u
+#define LINK_WAVES (LINK_THREADS / 64u)
+
+struct LinkComp { u32 first, m, base, L; u64 K; };                            // rows [first, first + m) of the component order, cells from base, K = unit num L
+struct LinkState { u64 S; u32 j, size; };                                     // per cluster: its row's smallest eligible key (S, partner j > itself; LIN_NONE: none), size (0: merged into j)
+static_assert(sizeof(LinkComp) == 24 && sizeof(LinkState) == 16, "uploaded as it is");
+
+// one thread per {bases, mask} pair of a row of the component order
+__global__ __launch_bounds__(256) void k_link_gather(const ulonglong2* __restrict__ rows, const u32* __restrict__ row_item, const u32* __restrict__ perm, u32 n_rows,
+                                                     ulonglong2* __restrict__ out, u32* __restrict__ out_item) {
+	const u32 t = blockIdx.x * 256u + threadIdx.x, r = t / LIN_ROW_WORDS, w = t % LIN_ROW_WORDS;
+	if (r >= n_rows) return;
+	const u32 from = perm[r];
+	out[(size_t) r * LIN_ROW_WORDS + w] = rows[(size_t) from * LIN_ROW_WORDS + w];
+	if (w == 0) out_item[r] = row_item[from];
+}
+
+__device__ inline void link_store(void* mat, u32 wide, size_t cell, u32 d) {
+	if (wide) ((u64*) mat)[cell] = d;
+	else ((u32*) mat)[cell] = d;
+}
+
+template <int W>
+__device__ inline void link_item(const HamItem it, const ulonglong2* __restrict__ rows, void* mat, u32 wide, ulonglong2* tile) {
+	const u32 lane = threadIdx.x, myrow = it.row0 + lane, m = it.u[1] >> 8, first = it.u[2];
+	const bool live = myrow < it.row_end;
+	const u32 r = live ? myrow : it.row0;
+	u64 x[W], mk[W];
+#pragma unroll
+	for (int w = 0; w < W; w++) {
+		const ulonglong2 q = rows[(size_t) r * LIN_ROW_WORDS + w];
+		x[w] = q.x;
+		mk[w] = q.y;
+	}
+	for (u32 base = it.col0; base < it.col_end; base += LIN_TILE) {
+		const u32 nc = min(LIN_TILE, it.col_end - base);
+		for (u32 i = lane; i < nc * (u32) W; i += 64u) tile[i] = rows[(size_t) (base + i / (u32) W) * LIN_ROW_WORDS + i % (u32) W];
+		__syncthreads();
+		for (u32 c = 0; c < nc; c++) {
+			u32 d = 0;
+#pragma unroll
+			for (int w = 0; w < W; w++) d += ham_word(x[w], mk[w], tile[c * (u32) W + w]);
+			if (live) link_store(mat, wide, (size_t) it.u[0] + (size_t) (base + c - first) * m + (myrow - first), d);
+		}
+		__syncthreads();
+	}
+}
+
+__global__ __launch_bounds__(64) void k_link_matrix(const HamItem* __restrict__ items, const ulonglong2* __restrict__ rows, void* mat, u32 wide) {
+	__shared__ ulonglong2 tile[LIN_TILE * LIN_ROW_WORDS];
+	const HamItem it = items[blockIdx.x];
+	switch (it.words) {                                    // (W below is the case's constant: HAM_CASES_8 declares it)
+		HAM_CASES_8(link_item<W>(it, rows, mat, wide, tile))
+		default: break;
+	}
+}
+
+template <int W>
+__device__ inline void link_item_model(const HamItem it, const ulonglong2* __restrict__ rows, void* mat, u32 wide, ulonglong2* tile, const uint16_t* tab, u32 sym) {
+	const u32 lane = threadIdx.x, myrow = it.row0 + lane, L = it.u[1] & 0xFFu, m = it.u[1] >> 8, first = it.u[2];
+	const bool live = myrow < it.row_end;
+	const u32 r = live ? myrow : it.row0;
+	u64 x[W], mk[W];
+#pragma unroll
+	for (int w = 0; w < W; w++) {
+		const ulonglong2 q = rows[(size_t) r * LIN_ROW_WORDS + w];
+		x[w] = q.x;
+		mk[w] = q.y;
+	}
+	for (u32 base = it.col0; base < it.col_end; base += LIN_TILE) {
+		const u32 nc = min(LIN_TILE, it.col_end - base);
+		for (u32 i = lane; i < nc * (u32) W; i += 64u) tile[i] = rows[(size_t) (base + i / (u32) W) * LIN_ROW_WORDS + i % (u32) W];
+		__syncthreads();
+		for (u32 c = 0; c < nc; c++) {
+			ulonglong2 q[W];
+#pragma unroll
+			for (int w = 0; w < W; w++) q[w] = tile[c * (u32) W + w];
+			u32 D = 0;
+#pragma unroll
+			for (int w = 0; w < W; w++) {
+				const u64 t = x[w] ^ q[w].x;
+				u64 dm = (((t | (t << 1)) & 0xAAAAAAAAAAAAAAAAull) | mk[w] | q[w].y);              // bit 2k + 1: base k of the word counts
+				if (!dm) continue;
+				const LinWin xa = lin_win(w > 0 ? x[w - 1] : 0ull, x[w], w + 1 < W ? x[w + 1] : 0ull);
+				const LinWin ma = lin_win(w > 0 ? mk[w - 1] : 0ull, mk[w], w + 1 < W ? mk[w + 1] : 0ull);
+				const LinWin xb = lin_win(w > 0 ? q[w - 1].x : 0ull, q[w].x, w + 1 < W ? q[w + 1].x : 0ull);
+				const LinWin mb = lin_win(w > 0 ? q[w - 1].y : 0ull, q[w].y, w + 1 < W ? q[w + 1].y : 0ull);
+				do {
+					const u32 k = ((u32) __ffsll((unsigned long long) dm) >> 1) - 1u, pos = 32u * (u32) w + k;
+					dm &= dm - 1;
+					u32 ab = LIN_MISS, ba = LIN_MISS;
+					if (pos >= 2u && pos + 2u < L) {
+						const u32 bad_a = (u32) (mk[w] >> (2u * k + 1u)) & 1u, bad_b = (u32) (q[w].y >> (2u * k + 1u)) & 1u;
+						if (lin_mer(ma, k) == 0 && !bad_b) ab = tab[lin_mer(xa, k) << 2 | ((u32) (q[w].x >> (2u * k)) & 3u)];
+						if (lin_mer(mb, k) == 0 && !bad_a) ba = tab[lin_mer(xb, k) << 2 | ((u32) (x[w] >> (2u * k)) & 3u)];
+					}
+					D += sym ? 2u * min(ab, ba) : ab + ba;
+				} while (dm);
+			}
+			if (live) link_store(mat, wide, (size_t) it.u[0] + (size_t) (base + c - first) * m + (myrow - first), D);
+		}
+		__syncthreads();
+	}
+}
+
+__global__ __launch_bounds__(64) void k_link_matrix_model(const HamItem* __restrict__ items, const ulonglong2* __restrict__ rows, void* mat, u32 wide,
+                                                          const uint4* __restrict__ table, u32 sym) {
+	__shared__ ulonglong2 tile[LIN_TILE * LIN_ROW_WORDS];
+	__shared__ uint4 tab[LIN_TAB / 8u];
+	for (u32 i = threadIdx.x; i < LIN_TAB / 8u; i += 64u) tab[i] = table[i];
+	__syncthreads();
+	const HamItem it = items[blockIdx.x];
+	switch (it.words) {                                    // (W below is the case's constant: HAM_CASES_8 declares it)
+		HAM_CASES_8(link_item_model<W>(it, rows, mat, wide, tile, (const uint16_t*) tab, sym))
+		default: break;
+	}
+}
+
+// a candidate pair: S over n (n: |A| |B| under average linkage, 1 under complete), the two local indices; j == LIN_NONE: none
+struct LinkKey { u64 S, n; u32 i, j; };
+
+// the strict order (delta, id(A), id(B)), delta compared exactly: only eligible pairs get here, S n < 2^63 (include/vdjx.h)
+__device__ inline bool link_less(const LinkKey a, const LinkKey b) {
+	if (a.j == LIN_NONE || b.j == LIN_NONE) return b.j == LIN_NONE && a.j != LIN_NONE;
+	const u64 l = a.S * b.n, r = b.S * a.n;
+	if (l != r) return l < r;
+	return a.i != b.i ? a.i < b.i : a.j < b.j;
+}
+
+__device__ inline LinkKey link_wave_min(LinkKey k) {
+#pragma unroll
+	for (int s = 32; s >= 1; s >>= 1) {
+		LinkKey o;
+		o.S = (u64) __shfl_xor((long long) k.S, s, 64);
+		o.n = (u64) __shfl_xor((long long) k.n, s, 64);
+		o.i = (u32) __shfl_xor((int) k.i, s, 64);
+		o.j = (u32) __shfl_xor((int) k.j, s, 64);
+		if (link_less(o, k)) k = o;
+	}
+	return k;
+}
+
+// Cell = u32: complete linkage, u64: average.  mat, state and list are the batch's (cells from comps[].base, entries from comps[].first)
+// and used by the components above LINK_LDS_M; the others copy their matrix into LDS.  item: the rows' items in component order; root and
+// flag get every member's final cluster (its smallest member) and whether it is that member
+template <typename Cell>
+__global__ __launch_bounds__(LINK_THREADS) void k_link_merge(const LinkComp* __restrict__ comps, Cell* mat, LinkState* state, u32* list, const u32* __restrict__ item,
+                                                             u32 den, u32* __restrict__ root, u32* __restrict__ flag) {
+	constexpr bool AVG = sizeof(Cell) == 8;
+	__shared__ Cell l_mat[LINK_LDS_M * LINK_LDS_M];
+	__shared__ LinkState l_state[LINK_LDS_M];
+	__shared__ u32 l_list[LINK_LDS_M];
+	__shared__ LinkKey red[LINK_WAVES];
+	__shared__ u32 n_list;
+	const LinkComp cp = comps[blockIdx.x];
+	const u32 m = cp.m, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+	const u64 kd = cp.K / den;                             // complete: eligible iff S <= floor(K / den)
+	Cell* M = mat + cp.base;
+	LinkState* st = state + cp.first;
+	u32* lst = list + cp.first;
+	if (m <= LINK_LDS_M) {
+		for (u32 i = tid; i < m * m; i += LINK_THREADS) l_mat[i] = M[i];
+		M = l_mat;
+		st = l_state;
+		lst = l_list;
+	}
+	for (u32 c = tid; c < m; c += LINK_THREADS) st[c] = {0ull, LIN_NONE, 1u};
+	__syncthreads();
+
+	// the smallest eligible key of row c among the live j > c, by one wave
+	auto scan_row = [&](u32 c) {
+		const u64 nc = st[c].size;
+		LinkKey best = {0ull, 1ull, c, LIN_NONE};
+		for (u32 j = c + 1u + lane; j < m; j += 64u) {
+			const u64 nj = st[j].size;
+			if (!nj) continue;
+			const LinkKey k = {(u64) M[(size_t) c * m + j], AVG ? nc * nj : 1ull, c, j};
+			if (k.S <= (AVG ? cp.K * k.n / den : kd) && link_less(k, best)) best = k;
+		}
+		best = link_wave_min(best);
+		if (lane == 0) { st[c].S = best.S; st[c].j = best.j; }
+	};
+	for (u32 c = wave; c + 1u < m; c += LINK_WAVES) scan_row(c);
+	__syncthreads();
+
+	for (;;) {
+		LinkKey best = {0ull, 1ull, 0u, LIN_NONE};
+		for (u32 c = tid; c < m; c += LINK_THREADS) {
+			const LinkState s = st[c];
+			if (!s.size || s.j == LIN_NONE) continue;
+			const LinkKey k = {s.S, AVG ? (u64) s.size * st[s.j].size : 1ull, c, s.j};
+			if (link_less(k, best)) best = k;
+		}
+		best = link_wave_min(best);
+		if (lane == 0) red[wave] = best;
+		if (tid == 0) n_list = 0;
+		__syncthreads();
+		best = red[0];
+#pragma unroll
+		for (u32 w = 1; w < LINK_WAVES; w++)
+			if (link_less(red[w], best)) best = red[w];
+		if (best.j == LIN_NONE) break;                     // (every thread sees the same four keys)
+		const u32 a = best.i, b = best.j;
+		for (u32 c = tid; c < m; c += LINK_THREADS) {       // Lance-Williams, exact: max, or the sum of the sums
+			if (c == a || c == b || !st[c].size) continue;
+			const Cell va = M[(size_t) a * m + c], vb = M[(size_t) b * m + c], v = AVG ? va + vb : (va > vb ? va : vb);
+			M[(size_t) a * m + c] = v;
+			M[(size_t) c * m + a] = v;
+		}
+		__syncthreads();
+		if (tid == 0) {
+			st[a].size += st[b].size;
+			st[b].size = 0;
+			st[b].j = a;
+		}
+		__syncthreads();
+		// the caches: A's own row and the rows that pointed at A or B are scanned again, a row before A takes its new pair with A if that
+		// is smaller; every other row's cached pair is untouched by the merge
+		const u64 na = st[a].size;
+		for (u32 c = tid; c < b; c += LINK_THREADS) {
+			const LinkState s = st[c];
+			if (!s.size) continue;
+			if (c == a || s.j == a || s.j == b) lst[atomicAdd(&n_list, 1u)] = c;          // (the order of the list shows nowhere: a row's scan is its own)
+			else if (c < a) {
+				const LinkKey k = {(u64) M[(size_t) c * m + a], AVG ? (u64) s.size * na : 1ull, c, a};
+				const LinkKey old = {s.S, s.j == LIN_NONE ? 1ull : AVG ? (u64) s.size * st[s.j].size : 1ull, c, s.j};
+				if (k.S <= (AVG ? cp.K * k.n / den : kd) && link_less(k, old)) { st[c].S = k.S; st[c].j = a; }
+			}
+		}
+		__syncthreads();
+		const u32 nl = n_list;
+		for (u32 k = wave; k < nl; k += LINK_WAVES) scan_row(lst[k]);
+		__syncthreads();
+	}
+	for (u32 c = tid; c < m; c += LINK_THREADS) {
+		u32 r = c;
+		while (!st[r].size) r = st[r].j;
+		const u32 me = item[cp.first + c];
+		root[me] = item[cp.first + r];
+		flag[me] = r == c ? 1u : 0u;
+	}
+}
+
 // the cells of a distance table in the rows' code order: index (v << 2 | y), v the ten bits of a 5-mer as they lie in a packed row (its first
 // base lowest), y the new base, both in vdjx_hamming.h's codes (A0 T1 C2 G3); the caller's table is row 256 a + 64 b + 16 c + 4 d + e, column
 // the new base, in A0 C1 G2 T3
@@ -245,10 +503,102 @@ static void lin_table_reindex(const uint16_t* table, uint16_t* out) {
 	}
 }
 
+// complete (1) or average (2) linkage over the components of the finished pair pass.  d_root: every item's root, from k_lin_flatten; it and
+// d_flag come back with the final clusters of the members of every component of two and more.  The stream is waited for once, for the roots
+static int link_run(const char* fn, vdjx_ctx* c, vdjx_work& wk, const std::vector<LinRow>& ri, u32 n, int num, int den, u32 unit, const uint4* d_table, u32 sym,
+                    int linkage, const ulonglong2* d_rows, const u32* d_row_item, u32* d_root, u32* d_flag, vdjx_lineage_link_info* lk) {
+	hipStream_t st = c->stream;
+	std::vector<u32> root(n);
+	HIP_TRY(hipMemcpyAsync(root.data(), d_root, n * sizeof(u32), hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipStreamSynchronize(st));
+	LinkOrder o;
+	if (!link_order(root.data(), n, o)) { vdjx_set_error("%s: the pair pass left a root that is none", fn); return VDJX_EHIP; }
+	lk->components = (u32) o.size.size();
+	lk->largest_component = o.largest;
+	lk->clones_single = o.clones_single;
+	if (o.largest > LINK_MAX_M) {
+		vdjx_set_error("%s: a single-linkage component of %u junctions (at most %u under complete or average linkage)", fn, o.largest, LINK_MAX_M);
+		return VDJX_ELIMIT;
+	}
+	if (o.size.empty()) return VDJX_OK;
+	const u64 knob = (u64) vdjx_env_num("VDJX_LINK_CELLS", 1ll << 26, 1, 1ll << 28);
+	std::vector<u32> end;
+	link_batches(o.size, knob, end);
+	const u32 total = (u32) o.member.size(), wide = linkage == 2 ? 1u : 0u;
+	std::vector<u32> row_of(n, LIN_NONE), perm(total);
+	for (u32 r = 0; r < (u32) ri.size(); r++) row_of[ri[r].item] = r;
+	for (u32 p = 0; p < total; p++) perm[p] = row_of[o.member[p]];
+	std::vector<LinkComp> comps(o.size.size());
+	std::vector<HamItem> items;
+	std::vector<size_t> item_end;                          // per batch: one past its last work item
+	u64 most = 0;
+	for (size_t b = 0, k = 0; b < end.size(); b++) {
+		u64 cells = 0;
+		for (size_t q = k; q < end[b]; q++) cells += (u64) o.size[q] * o.size[q];
+		const u32 slice = ham_slice_width(cells);
+		u64 base = 0;                                      // (a batch is at most 2^28 cells: the knob's range, or one component of 4,096)
+		for (; k < end[b]; k++) {
+			const u32 m = o.size[k], L = ri[perm[o.first[k]]].len;
+			comps[k] = {o.first[k], m, (u32) base, L, (u64) unit * (u64) num * L};
+			ham_slice_items({o.first[k], m, (L + 31u) / 32u, {(u32) base, L | m << 8, o.first[k]}}, slice, items);
+			base += (u64) m * m;
+		}
+		item_end.push_back(items.size());
+		most = std::max(most, cells);
+		lk->cells += cells;
+	}
+	lk->batches = (u32) end.size();
+
+	u32 *d_perm, *d_item, *d_list;
+	ulonglong2* d_crows;
+	LinkComp* d_comps;
+	HamItem* d_items;
+	LinkState* d_state;
+	u64* d_mat;
+	HIP_TRY(wk.alloc(&d_perm, total));
+	HIP_TRY(wk.alloc(&d_item, total));
+	HIP_TRY(wk.alloc(&d_list, total));
+	HIP_TRY(wk.alloc(&d_crows, (size_t) total * LIN_ROW_WORDS));
+	HIP_TRY(wk.alloc(&d_comps, comps.size()));
+	HIP_TRY(wk.alloc(&d_items, items.size()));
+	HIP_TRY(wk.alloc(&d_state, total));
+	HIP_TRY(wk.alloc(&d_mat, wide ? (size_t) most : (size_t) ((most + 1) / 2)));
+	HIP_TRY(hipMemcpyAsync(d_perm, perm.data(), total * sizeof(u32), hipMemcpyHostToDevice, st));
+	HIP_TRY(hipMemcpyAsync(d_comps, comps.data(), comps.size() * sizeof(LinkComp), hipMemcpyHostToDevice, st));
+	HIP_TRY(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(HamItem), hipMemcpyHostToDevice, st));
+	{
+		vdjx_prof_scope ps(c, "k_link_gather");
+		hipLaunchKernelGGL(k_link_gather, dim3((total * LIN_ROW_WORDS + 255u) / 256u), dim3(256), 0, st, d_rows, d_row_item, (const u32*) d_perm, total, d_crows, d_item);
+	}
+	for (size_t b = 0; b < end.size(); b++) {
+		const size_t i0 = b ? item_end[b - 1] : 0, k0 = b ? end[b - 1] : 0;
+		const u32 ni = (u32) (item_end[b] - i0), nk = (u32) (end[b] - k0);
+		{
+			vdjx_prof_scope ps(c, "k_link_matrix");
+			if (!d_table)
+				hipLaunchKernelGGL(k_link_matrix, dim3(ni), dim3(64), 0, st, (const HamItem*) d_items + i0, (const ulonglong2*) d_crows, (void*) d_mat, wide);
+			else
+				hipLaunchKernelGGL(k_link_matrix_model, dim3(ni), dim3(64), 0, st, (const HamItem*) d_items + i0, (const ulonglong2*) d_crows, (void*) d_mat, wide, d_table, sym);
+		}
+		{
+			vdjx_prof_scope ps(c, "k_link_merge");
+			if (wide)
+				hipLaunchKernelGGL(k_link_merge<u64>, dim3(nk), dim3(LINK_THREADS), 0, st, (const LinkComp*) d_comps + k0, d_mat, d_state, d_list, (const u32*) d_item,
+				                   (u32) den, d_root, d_flag);
+			else
+				hipLaunchKernelGGL(k_link_merge<u32>, dim3(nk), dim3(LINK_THREADS), 0, st, (const LinkComp*) d_comps + k0, (u32*) d_mat, d_state, d_list, (const u32*) d_item,
+				                   (u32) den, d_root, d_flag);
+		}
+	}
+	return VDJX_OK;
+}
+
 // what vdjx_lineage and vdjx_lineage_model share: the checks, the host layout and every dispatch but the pair pass.  table == NULL: the
-// Hamming pass; otherwise the caller's checked table, dmax in units of 2000 a position
+// Hamming pass; otherwise the caller's checked table, dmax in units of 2000 a position.  linkage 1, 2 (vdjx_lineage_link): the components
+// of the pair pass are agglomerated before they are numbered; 0 launches what it always did
 static int lin_run(const char* fn, vdjx_ctx* c, const char* junctions, const uint64_t* off, const uint32_t* group, size_t n, int num, int den,
-                   const uint16_t* table, u32 sym, int32_t* out_clone, int32_t* out_nearest, vdjx_lineage_info* info) {
+                   const uint16_t* table, u32 sym, int32_t* out_clone, int32_t* out_nearest, vdjx_lineage_info* info, int linkage = 0,
+                   vdjx_lineage_link_info* link = nullptr) {
 	if (den < 1 || den > 1000000 || num < 0 || num > den) {
 		vdjx_set_error("%s: threshold %d/%d (den 1 .. 10^6, num 0 .. den)", fn, num, den);
 		return VDJX_EINVAL;
@@ -278,6 +628,7 @@ static int lin_run(const char* fn, vdjx_ctx* c, const char* junctions, const uin
 		c->stats["lineage_work_items"] = 0;
 		c->stats["lineage_us"] = 0;
 		if (table) c->stats["lineage_model_walked"] = c->stats["lineage_model_positions"] = 0;
+		if (linkage) c->stats["lineage_link_us"] = c->stats["lineage_link_cells"] = 0;
 		return VDJX_OK;
 	}
 	std::sort(keys.begin(), keys.end());
@@ -366,6 +717,16 @@ static int lin_run(const char* fn, vdjx_ctx* c, const char* junctions, const uin
 		vdjx_prof_scope ps(c, "k_lin_flatten");
 		hipLaunchKernelGGL(k_lin_flatten, dim3(nb), dim3(256), 0, st, (const u32*) d_parent, (u32) n, d_root, d_flag);
 	}
+	vdjx_lineage_link_info lk;
+	memset(&lk, 0, sizeof lk);
+	if (linkage) {
+		const auto t1 = std::chrono::steady_clock::now();
+		const int rc = link_run(fn, c, wk, ri, (u32) n, num, den, table ? 2000u : 1u, (const uint4*) d_table, sym, linkage, (const ulonglong2*) d_rows,
+		                        (const u32*) d_row_item, d_root, d_flag, &lk);
+		if (rc) return rc;
+		c->stats["lineage_link_us"] = (u64) std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t1).count();
+		c->stats["lineage_link_cells"] = lk.cells;
+	}
 	{
 		vdjx_prof_scope ps(c, "k_lin_number");
 		vdjx_scan_one(st, (const u32*) d_flag, (u32) n, d_number);
@@ -386,6 +747,8 @@ static int lin_run(const char* fn, vdjx_ctx* c, const char* junctions, const uin
 	inf.links = links[0];
 	inf.clones = clones;
 	if (info) *info = inf;
+	lk.merges = linkage ? rows - clones : 0u;              // (every merge makes one cluster of two, and the rows begin as clusters)
+	if (link) *link = lk;
 	c->stats["lineage_work_items"] = items.size();
 	c->stats["lineage_us"] = (u64) std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
 	if (table) {
@@ -446,4 +809,22 @@ extern "C" int vdjx_lineage_distance_table(const uint32_t* weight, uint16_t* tab
 	}
 	if (info) { info->mean = mean; info->min_cost = lo; info->max_cost = hi; }
 	return VDJX_OK;
+}
+
+extern "C" int vdjx_lineage_link(vdjx_ctx* c, const char* junctions, const uint64_t* off, const uint32_t* group, size_t n, const vdjx_lineage_link_params* prm,
+                                 const uint16_t* table, int32_t* out_clone, int32_t* out_nearest, vdjx_lineage_info* info, vdjx_lineage_link_info* link) {
+	if (info) memset(info, 0, sizeof *info);
+	if (link) memset(link, 0, sizeof *link);
+	if (!c || !prm) { vdjx_set_error("vdjx_lineage_link: NULL argument"); return VDJX_EINVAL; }
+	if (prm->linkage < 0 || prm->linkage > 2) { vdjx_set_error("vdjx_lineage_link: linkage %d (0: single, 1: complete, 2: average)", prm->linkage); return VDJX_EINVAL; }
+	if (table) {
+		if (prm->symmetry != 0 && prm->symmetry != 1) { vdjx_set_error("vdjx_lineage_link: symmetry %d (0: avg, 1: min)", prm->symmetry); return VDJX_EINVAL; }
+		for (u32 i = 0; i < LIN_TAB; i++)
+			if (((i >> 6) & 3u) != (i & 3u) && table[i] == 0) {
+				vdjx_set_error("vdjx_lineage_link: the table's cell [%u][%u] is 0 (an off-centre cell is 1 .. 65535)", i >> 2, i & 3u);
+				return VDJX_EINVAL;
+			}
+	}
+	return lin_run("vdjx_lineage_link", c, junctions, off, group, n, prm->num, prm->den, table, table ? (u32) prm->symmetry : 0u, out_clone, out_nearest, info,
+	               prm->linkage, link);
 }

@@ -95,11 +95,11 @@ struct vdjx_arena {
 struct vdjx_shard;
 
 // vdjx_ctx::h_pin: 16 KB of page-locked scratch.  Every synchronous call reads its small numbers back into the first bytes (the
-// largest: stage_gated_reduce's (64 * 16 + 2) * 8 = 8,208); a call that is BEGUN and ended later (vdjx_root_score_graph_begin) keeps
+// largest: stage_gated_reduce's (64 * 16 + 3) * 8 = 8,216); a call that is BEGUN and ended later (vdjx_root_score_graph_begin) keeps
 // its number in a word behind all of those, because other calls run in between (a k-mer build between begin and end
 // overwrote a word at byte 8,192)
 #define VDJX_HPIN_BYTES 16384
-#define VDJX_HPIN_SYNC_BYTES ((64 * 16 + 2) * 8)       // the largest read-back of a synchronous call (vdjx_kmer.hip stage_gated_reduce)
+#define VDJX_HPIN_SYNC_BYTES ((64 * 16 + 3) * 8)       // the largest read-back of a synchronous call (vdjx_kmer.hip stage_gated_reduce)
 #define VDJX_HPIN_ROOT_RUN 3072                        // u32 index: byte 12,288
 static_assert(VDJX_HPIN_ROOT_RUN * 4 >= VDJX_HPIN_SYNC_BYTES + 64 && VDJX_HPIN_ROOT_RUN * 4 + 4 <= VDJX_HPIN_BYTES, "h_pin layout");
 

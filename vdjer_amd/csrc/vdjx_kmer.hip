@@ -8,7 +8,8 @@
 // MFMA applies.
 //
 //   K2a k_gated_hist       per-workgroup LDS histogram of the gated instances' buckets over a slice of the pool, added to the global counts
-//   K2b vdjx_scan_one      exclusive bucket starts (vdjx_scan.h)
+//                          (large one-GPU pools: over one row of 64 records in 16 -- the sampled cut, stage_gated_hist)
+//   K2b vdjx_scan_one      exclusive bucket starts (vdjx_scan.h); after a sampled histogram the starts of the buckets' capacities
 //   K2c k_part_records_g / the LDS-staged partition (vdjx_part.h): tuples {key_lo, key_hi, inst|gated} written as coalesced bucket runs,
 //       k_part             at most 1,024 buckets per pass; more in a second pass inside each coarse bucket (k_seg_hist_g counts the fine
 //                          ones where the histogram's buckets are cut again); positions inside a bucket from cursor bumps
@@ -200,10 +201,15 @@ __device__ inline bool sym_canonical(const ulonglong2 f, int rl, int k, int o, u
 // SYM (short reads, k odd, vdjx_pool::sym): a thread takes a COUPLE of records (2q, 2q+1; R counts couples) and lists the gated
 // offsets of the first; every listed instance stands for itself and its mirror in the second record, and is counted -- and later
 // moved -- once, under the smaller of the two k-mers
-template <bool LONG, bool SYM = false>
+// S > 1 (the sampled cut, stage_gated_hist): the kernel walks Rv = 64 x (sampled rows) VIRTUAL records, row j of them being row
+// j * S + S / 2 of the pool's rows of 64 records (couples) -- the same rows on every call; rpb is then a multiple of 64, so a wave has
+// one row.  *sampled gets their number of gated instances.  Without SAMPLED (S == 1, Rv == R) a virtual record is the record and the
+// kernel is what it was before there was a sample
+template <bool LONG, bool SYM = false, bool SAMPLED = false>
 __global__ __launch_bounds__(HIST_THREADS) void k_gated_hist(const u64* __restrict__ bases, const u64* __restrict__ nmask,
                                                              const u64* __restrict__ lowq, size_t R, int rl, int k, u32 nb_bits,
-                                                             size_t rpb, u32* __restrict__ bucket_cnt, u32 dbg_in) {
+                                                             size_t rpb, u32* __restrict__ bucket_cnt, u32 dbg_in,
+                                                             u32 S, size_t Rv, u32* __restrict__ sampled) {
 #ifdef VDJX_ABLATE                  // profiles/histdbg.py: 1 = loads and gate masks only, 2 = + the listing, 3 = + k-mers and hashes, 4 = all but the flush
 	const u32 dbg = dbg_in;
 #else
@@ -221,13 +227,16 @@ __global__ __launch_bounds__(HIST_THREADS) void k_gated_hist(const u64* __restri
 	uint16_t* wl = (uint16_t*) (wv + (LONG ? 64u * GL_ROW_LONG * 8u : 1024u));
 	const u32 lane = threadIdx.x & 63u;
 	const size_t r0 = (size_t) blockIdx.x * rpb;
-	const size_t r1 = r0 + rpb < R ? r0 + rpb : R;
+	const size_t r1 = SAMPLED ? (r0 + rpb < Rv ? r0 + rpb : Rv) : (r0 + rpb < R ? r0 + rpb : R);
 	const int P = rl - k + 1;
+	static_assert(!(LONG && SAMPLED), "the sample is taken of short reads");
+	u32 wtot = 0;
 	for (size_t rb = r0; rb < r1; rb += HIST_THREADS) {
-		const size_t r = rb + threadIdx.x;
+		const size_t v = rb + threadIdx.x;
+		const size_t r = SAMPLED ? ((((v >> 6) * S + S / 2) << 6) | (v & 63)) : v;
 		u64 G = 0;
 		vdjx_mask3 bad{~0ull, ~0ull, ~0ull};
-		if (r < r1) {
+		if (v < r1 && (!SAMPLED || r < R)) {
 			if (LONG) { bad = load_gate3(lowq, r); stage_row_long(wrow + lane * GL_ROW_LONG, bases, r); }
 			else {
 				const GateView v = load_gate(bases, lowq, SYM ? 2 * r : r);
@@ -243,6 +252,7 @@ __global__ __launch_bounds__(HIST_THREADS) void k_gated_hist(const u64* __restri
 			const u32 total = (u32) __builtin_amdgcn_readlane((int) incl, 63);
 			if (dbg == 1) { sink += incl; continue; }
 			if (!total) continue;                                     // (wave-uniform)
+			if (SAMPLED) wtot += total;
 			u32 at = incl - c;
 			for (u32 gg = g; gg; gg &= gg - 1) wl[at++] = (uint16_t) ((lane << (LONG ? 8 : 6)) | (u32) (ob + __builtin_ctz(gg)));
 			vdjx_wave_lds_fence();                                    // the list and the records are read by OTHER lanes of the wave
@@ -265,6 +275,7 @@ __global__ __launch_bounds__(HIST_THREADS) void k_gated_hist(const u64* __restri
 	__syncthreads();
 	if (dbg) { if (sink == 0x12345u) bucket_cnt[0] = sink; return; }
 	for (u32 i = threadIdx.x; i < NB; i += HIST_THREADS) if (hist[i]) atomicAdd(&bucket_cnt[i], hist[i]);
+	if (SAMPLED && lane == 0 && wtot) atomicAdd(sampled, wtot);
 }
 
 // the bucket of a tuple in a pass of the cut: `mask + 1` buckets from the hash bits above `shift`
@@ -283,8 +294,8 @@ template <typename TUP> struct TupBucket {
 template <typename TUP, bool LONG, bool SYM = false>
 __global__ __launch_bounds__(PART_THREADS) void k_part_records_g(const u64* __restrict__ bases, const u64* __restrict__ nmask,
                                                                  const u64* __restrict__ lowq, size_t R, u64 rec_base, int rl, int k,
-                                                                 u32 shift, u32 nbk, size_t rpb, u32 rr0, u32* __restrict__ gcur,
-                                                                 TUP* __restrict__ out) {
+                                                                 u32 shift, u32 nbk, size_t rpb, u32 rr0, const u32* __restrict__ lim, u32 lsh,
+                                                                 u32* __restrict__ over, u32* __restrict__ gcur, TUP* __restrict__ out) {
 	extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
 	TUP* stage = (TUP*) smem;                                         // (the waves' instance lists live here while the round is counted)
 	u32* desc = (u32*) (smem + PARTR_STAGE_BYTES);
@@ -305,6 +316,7 @@ __global__ __launch_bounds__(PART_THREADS) void k_part_records_g(const u64* __re
 	const size_t r0 = (size_t) blockIdx.x * rpb;            // (SYM: R, rpb, rr and the descriptors count COUPLES of records)
 	const size_t r1 = r0 + rpb < R ? r0 + rpb : R;
 	size_t rs = r0;
+	pr.limits(nbk, lim, lsh, over);
 	while (rs < r1) {
 		const size_t re = rs + rr < r1 ? rs + rr : r1;
 		if (threadIdx.x == 0) s_n = 0;
@@ -357,7 +369,8 @@ __global__ __launch_bounds__(PART_THREADS) void k_part_records_g(const u64* __re
 			__syncthreads();
 			continue;
 		}
-		const u32 n = pr.reserve(nbk, gcur);
+		const u32 n = pr.reserve(nbk, gcur);                          // (PART_DEAD: the sampled cut's buckets are capacities)
+		if (n == PART_DEAD) return;                                   // (uniform)
 		for (u32 i = threadIdx.x; i < n; i += PART_THREADS) {
 			const u32 d = desc[i];
 			const size_t r = rs + (d >> (OB + 10));
@@ -384,13 +397,15 @@ __global__ __launch_bounds__(PART_THREADS) void k_part_records_g(const u64* __re
 // the fine buckets' sizes where the second pass cuts more buckets than the histogram counted: the slices of the pass itself (part_slice)
 template <typename TUP>
 __global__ __launch_bounds__(512) void k_seg_hist_g(const TUP* __restrict__ in, const u32* __restrict__ seg_start, u32 seg_shift, u32 slices,
-                                                    u32 shift, u32 sub_bits, u32* __restrict__ fine_cnt) {
+                                                    u32 shift, u32 sub_bits, u32* __restrict__ fine_cnt, const u32* __restrict__ seg_end,
+                                                    const u32* __restrict__ over) {
 	__shared__ u32 h[PART_MAXB];
+	if (over && *over) return;                                    // (the first pass ran over: its cursors bound nothing that may be read)
 	const u32 nbk = 1u << sub_bits;
 	for (u32 i = threadIdx.x; i < nbk; i += 512) h[i] = 0;
 	__syncthreads();
 	size_t t0, t1;
-	const u32 seg = part_slice(seg_start, seg_shift, slices, t0, t1);
+	const u32 seg = part_slice(seg_start, seg_shift, slices, t0, t1, seg_end);
 	for (size_t t = t0 + threadIdx.x; t < t1; t += 512) {
 		const TUP x = TUP::load(&in[t]);
 		atomicAdd(&h[(u32) (vdjx_bucket_mix(x.lo, x.hi()) >> shift) & (nbk - 1)], 1u);
@@ -495,19 +510,19 @@ __device__ inline u32 rd_count_min(u32* cnt, u64* mn, u32 idx, u64 val, bool act
 // the buckets in descending order of their size class (bit length of the tuple count): the reduce kernel's workgroups differ in
 // length by a factor of sixty, and the longest should not be among the last to start.  One workgroup: counts per class, the
 // classes' places, then every bucket to a place of its class (any order inside a class).
-__global__ __launch_bounds__(1024) void k_bucket_order(const u32* __restrict__ bucket_start, u32 NB, u32* __restrict__ order) {
+__global__ __launch_bounds__(1024) void k_bucket_order(const u32* __restrict__ bucket_start, const u32* __restrict__ bucket_end, u32 NB, u32* __restrict__ order) {
 	__shared__ u32 cls_cnt[33], cls_at[33];
 	if (threadIdx.x < 33) cls_cnt[threadIdx.x] = 0;
 	__syncthreads();
 	for (u32 b = threadIdx.x; b < NB; b += 1024) {
-		const u32 n = bucket_start[b + 1] - bucket_start[b];
+		const u32 n = bucket_end[b] - bucket_start[b];
 		atomicAdd(&cls_cnt[n ? 32u - (u32) __builtin_clz(n) : 0u], 1u);
 	}
 	__syncthreads();
 	if (threadIdx.x == 0) { u32 at = 0; for (int cl = 32; cl >= 0; cl--) { cls_at[cl] = at; at += cls_cnt[cl]; } }
 	__syncthreads();
 	for (u32 b = threadIdx.x; b < NB; b += 1024) {
-		const u32 n = bucket_start[b + 1] - bucket_start[b];
+		const u32 n = bucket_end[b] - bucket_start[b];
 		order[atomicAdd(&cls_at[n ? 32u - (u32) __builtin_clz(n) : 0u], 1u)] = b;
 	}
 }
@@ -519,6 +534,7 @@ __global__ __launch_bounds__(1024) void k_bucket_order(const u32* __restrict__ b
 // gated instance of R, the first one only for low counts: nothing reads it after the prune.)
 template <typename TUP, bool SYM = false>
 __global__ __launch_bounds__(RD_THREADS, sizeof(TUP) == 16 ? RD_WAVES : RD_WAVES / 2) void k_gated_reduce(const TUP* __restrict__ tup, const u32* __restrict__ bucket_start,
+                                                             const u32* __restrict__ bucket_end, const u32* __restrict__ cut_over,
                                                              const u64* __restrict__ bases, const u64* __restrict__ nmask,
                                                              vdjx_qrows quals, int rl, int ob, int k, u64 rec_base,
                                                              u32 mf, u32 cmin, u32 mqq, u32 tlow, SurvOutG so,
@@ -542,9 +558,10 @@ __global__ __launch_bounds__(RD_THREADS, sizeof(TUP) == 16 ? RD_WAVES : RD_WAVES
 	__shared__ unsigned short low_slot[RD_LROWS];
 	__shared__ u32 s_over, s_ndist, s_nlow, s_npq, s_nsurv, s_base, s_nreal;
 	const THI EMPTY = (THI) ~(THI) 0;
+	if (cut_over && *cut_over) return;                          // the sampled cut ran over a bucket: the host cuts again, exactly
 	const u32 b = order ? order[blockIdx.x] : blockIdx.x;
 	const u32 base = bucket_start[b];
-	const u32 n = bucket_start[b + 1] - base;
+	const u32 n = bucket_end[b] - base;                         // (the exact cut: bucket_end = bucket_start + 1)
 	const u32 tid = threadIdx.x;
 	if (n == 0) return;
 	const TUP* T = tup + base;
@@ -816,7 +833,7 @@ __device__ inline u32 ps_h(const PartialS& p) { return (u32) (p.fgh >> INST_BITS
 // i.e. below TLOW instances, where the instances are listed).  All ranks cut the buckets by the canonical k-mer.
 template <typename TUP, bool SYM = false>
 __global__ __launch_bounds__(LG_THREADS, sizeof(TUP) == 16 ? 6 : 3) void k_gated_local(const TUP* __restrict__ tup, const u32* __restrict__ bucket_start,
-                                                            const u64* __restrict__ bases, const u64* __restrict__ nmask, u64 rec_base, int k, int rl, int ob,
+                                                            const u32* __restrict__ bucket_end, const u64* __restrict__ bases, const u64* __restrict__ nmask, u64 rec_base, int k, int rl, int ob,
                                                             u32 tlow, Partial* __restrict__ sparse_g, u32* __restrict__ sparse_ref,
                                                             u32* __restrict__ nd_g, u64* __restrict__ low_inst, u32* __restrict__ g_err,
                                                             const u32* __restrict__ order) {
@@ -832,7 +849,7 @@ __global__ __launch_bounds__(LG_THREADS, sizeof(TUP) == 16 ? 6 : 3) void k_gated
 	const THI EMPTY = (THI) ~(THI) 0;
 	const u32 b = order ? order[blockIdx.x] : blockIdx.x;      // (largest buckets first: k_bucket_order)
 	const u32 base = bucket_start[b];
-	const u32 n = bucket_start[b + 1] - base;
+	const u32 n = bucket_end[b] - base;
 	const u32 tid = threadIdx.x;
 	const u32 om = (1u << ob) - 1u;
 	if (n == 0) { if (tid == 0) nd_g[b] = 0; return; }
@@ -2261,10 +2278,15 @@ struct PoolView { const u64* bases; const u64* nmask; vdjx_qrows quals; int rl; 
 // ==============================================================================================
 // round-2 host driver
 // ==============================================================================================
+#define VDJX_ECUT (-1001)              // (internal) the sampled cut ran over a bucket: cut again with the exact histogram
 template <typename TUP> struct GTuples {
 	TUP* t = nullptr;
 	u32* bucket_start = nullptr;      // [NB+1]
-	u32 NB = 0, N = 0;
+	const u32* bucket_end = nullptr;  // [NB]: bucket b is [bucket_start[b], bucket_end[b]); the exact cut: bucket_start + 1
+	u32* over = nullptr;              // the sampled cut: its overflow word on the device (nullptr: the exact cut)
+	u32 NB = 0, N = 0;                // N: the tuples; after a sampled cut their upper bound (the capacities' total) until stage_gated_reduce has read the count
+	u32 Nsurv = 0;                    // what the survivors' arrays are sized from: N; after a sampled cut the estimate plus the margin of the total
+	u32 S = 1;                        // the row stride of the histogram the cut came from (1: exact)
 };
 
 struct SurvivorsG {
@@ -2286,8 +2308,10 @@ static void dbg_sync(vdjx_ctx* c, const char* what) {
 
 // Phase A, partition: the gated instances of `pool` as tuples grouped by the top T bits of the k-mer hash (T chosen from their
 // number: ~4096 per bucket).  One host read (the tuple count) sizes everything that follows.
-// the histogram of the gated instances over the hash buckets, and their number (one host wait): what the cut below starts from
-struct GatedHist { u32 HB = 0, NBH = 0, N = 0; u32* hstart = nullptr; bool sym = false; };
+// the histogram of the gated instances over the hash buckets, and their number (one host wait): what the cut below starts from.
+// S > 1 (the sampled cut): the histogram saw one row of 64 records in S; N is the ESTIMATE S x (sampled count), hstart the starts of a
+// layout by CAPACITIES (cut_cap below) and cap_total its size
+struct GatedHist { u32 HB = 0, NBH = 0, N = 0; u32* hstart = nullptr; bool sym = false; u32 S = 1, cap_total = 0; };
 // sym: the pool's records come in couples (record, its reverse complement: vdjx_pool::sym) and k is odd: the kernels walk the couples
 // and move one tuple per pair of mirrored instances (k_gated_hist SYM)
 static bool build_sym(const vdjx_pool* pool, int k) {
@@ -2297,8 +2321,33 @@ static bool build_sym(const vdjx_pool* pool, int k) {
 static bool sym_walk_wanted() { static const bool on = !vdjx_env_set("VDJX_NO_SYM_WALK"); return on; }
 // gated tuples per bucket where the caller names no size: about a third are distinct k-mers (RD_SLOTS).  The histogram and the cut ask here
 static size_t gated_bucket_default() { static const size_t v = (size_t) vdjx_env_num("VDJX_GATED_BUCKET", 3072, 1, 1ll << 32); return v; }
+
+// The sampled cut.  The partition needs a layout with room for every bucket and a count per bucket, not exact starts: a histogram over
+// one row in S gives the bucket sizes to within the sampling error, the buckets get CAPACITIES S * h + margin(h), the passes check
+// their cursors against the next bucket's start and the counts are where the cursors end.  A bucket that runs over after all sets a
+// word that the reduce stage's read-back brings down; the build then cuts again with S = 1 (kmer_build_cut_retries).
+//   margin(h) = c * S * sqrt(h + 1) + floor, c and floor twice the worst seen in the calibration runs (profiles/README.md, sampled cut)
+#define CUT_MARGIN_C 16.5f          // measured: 4.91 (10 M pairs, k 35), 4.24 (k 25), 4.20 (private repertoire), 8.25 (1 M pairs)
+#define CUT_MARGIN_FLOOR 264u       // measured: no unseen bucket but at 1 M pairs, where the largest held 132 tuples
+#define CUT_SAMPLE_MIN_RECORDS ((size_t) 1 << 20)      // records (sym: couples) from which the sample is taken unasked
+struct cut_cap {
+	u32 S, floor;
+	float cS;
+	__device__ u32 operator()(u32 h) const { return S * h + (u32) ceilf(cS * sqrtf((float) h + 1.0f)) + floor; }
+};
+static float cut_margin_c() { static const float v = CUT_MARGIN_C * (float) vdjx_env_num("VDJX_CUT_MARGIN", 100, 0, 100000) / 100.0f; return v; }
+// the row stride of a one-GPU build of short reads (VDJX_HIST_SAMPLE: default 16 from CUT_SAMPLE_MIN_RECORDS up; set: that stride at any size, 1 = exact)
+static u32 cut_sample_stride(const vdjx_pool* pool, size_t R) {
+	static const bool given = vdjx_env_set("VDJX_HIST_SAMPLE");
+	static const u32 S = (u32) vdjx_env_num("VDJX_HIST_SAMPLE", 16, 1, 4096);
+	if (pool->W != 2 || S < 2) return 1;
+	if (!given && R < CUT_SAMPLE_MIN_RECORDS) return 1;
+	return (R + 63) / 64 > S / 2 ? S : 1;          // (a pool without a sampled row)
+}
+
+// S: the row stride of the sample (1: every record, the exact histogram); only for W == 2 and the build's own geometry (no per_bucket, no geometry_instances)
 template <typename A>
-int stage_gated_hist(vdjx_ctx* c, A& db, const vdjx_pool* pool, int k, size_t per_bucket, u64 geometry_instances, GatedHist* gh, bool sym = false) {
+int stage_gated_hist(vdjx_ctx* c, A& db, const vdjx_pool* pool, int k, size_t per_bucket, u64 geometry_instances, GatedHist* gh, bool sym = false, u32 S = 1) {
 	hipStream_t st = c->stream;
 	const size_t R = sym ? pool->n_records / 2 : pool->n_records;           // (sym: couples)
 	const int P = pool->rl - k + 1;
@@ -2316,41 +2365,112 @@ int stage_gated_hist(vdjx_ctx* c, A& db, const vdjx_pool* pool, int k, size_t pe
 #else
 	constexpr u32 hist_dbg = 0;
 #endif
-	u32 nblk = (u32) std::min<size_t>(HIST_BLOCKS, (R + 4095) / 4096);
-	if (nblk == 0) nblk = 1;
-	size_t rpb = (R + nblk - 1) / nblk;
-	u32 *hcnt, *hstart;
-	HIP_TRY(db.alloc(&hcnt, NBH));
-	HIP_TRY(db.alloc(&hstart, NBH + 1));
-	HIP_TRY(hipMemsetAsync(hcnt, 0, (size_t) NBH * 4, st));
 	const bool lng = pool->W > 2;
+	if (lng || per_bucket || geometry_instances || (R + 63) / 64 <= S / 2) S = 1;
+	if (S > 1) {
+		// the starts are 32-bit and the scan's sums wrap: the sample is taken only where the capacities' total cannot reach 2^32 whatever
+		// the pool holds -- every offset gated, s <= R * P / S -- by the bound sum sqrt(h + 1) <= sqrt(NBH * (s + NBH)) (decided here, before
+		// anything is launched: the stride a build reports is the stride it ran)
+		const double s_max = (double) NI / S + 64.0 * P, cS = (double) cut_margin_c() * S;
+		if ((double) S * s_max + (double) NBH * (CUT_MARGIN_FLOOR + 1.0) + cS * sqrt((double) NBH * (s_max + NBH)) >= 4.0e9) S = 1;
+	}
+	// the sample: rows S / 2, S / 2 + S, ... of the pool's rows of 64 records; 1,024 virtual records a workgroup (the flush adds what a
+	// workgroup counted, not 2^HB words)
+	const size_t rows = (R + 63) / 64;
+	const size_t Rv = S > 1 ? (rows - S / 2 + S - 1) / S * 64 : R;
+	u32 nblk = S > 1 ? (u32) std::min<size_t>(HIST_BLOCKS, (Rv + 1023) / 1024) : (u32) std::min<size_t>(HIST_BLOCKS, (R + 4095) / 4096);
+	if (nblk == 0) nblk = 1;
+	size_t rpb = (Rv + nblk - 1) / nblk;
+	if (S > 1) rpb = (rpb + 63) / 64 * 64;
+	u32 *hcnt, *hstart, *blk;
+	HIP_TRY(db.alloc(&blk, 2 * (size_t) NBH + 2));        // the starts [NBH + 1] | the sampled count | the counts [NBH]: one read-back, one clear
+	hstart = blk;
+	u32* samp = blk + NBH + 1;
+	hcnt = samp + 1;
+	HIP_TRY(hipMemsetAsync(samp, 0, ((size_t) NBH + 1) * 4, st));
 	const size_t lds_hist = (size_t) NBH * 4 + (HIST_THREADS / 64) * (lng ? GL_WAVE_BYTES_LONG : GL_WAVE_BYTES);
 	HIP_TRY(hipFuncSetAttribute((const void*) k_gated_hist<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_hist));
 	HIP_TRY(hipFuncSetAttribute((const void*) k_gated_hist<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_hist));
 	HIP_TRY(hipFuncSetAttribute((const void*) k_gated_hist<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_hist));
+	HIP_TRY(hipFuncSetAttribute((const void*) k_gated_hist<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_hist));
+	HIP_TRY(hipFuncSetAttribute((const void*) k_gated_hist<false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_hist));
+	const auto launch_hist = [&](u32 nb, size_t per_blk, u32* cnt, u32 stride, size_t rv, u32* sampled) {
+		auto* hist = lng ? k_gated_hist<true> : stride > 1 ? (sym ? k_gated_hist<false, true, true> : k_gated_hist<false, false, true>) : sym ? k_gated_hist<false, true> : k_gated_hist<false>;
+		hipLaunchKernelGGL(hist, dim3(nb), dim3(HIST_THREADS), lds_hist, st, pool->d_bases, pool->d_nmask, pool->d_lowq, R, pool->rl, k, HB, per_blk, cnt, hist_dbg, stride, rv, sampled);
+	};
 	{
 		vdjx_prof_scope ps(c, "k_gated_hist");
-		if (lng) hipLaunchKernelGGL(k_gated_hist<true>, dim3(nblk), dim3(HIST_THREADS), lds_hist, st, pool->d_bases, pool->d_nmask, pool->d_lowq, R, pool->rl, k, HB, rpb, hcnt, hist_dbg);
-		else if (sym) hipLaunchKernelGGL((k_gated_hist<false, true>), dim3(nblk), dim3(HIST_THREADS), lds_hist, st, pool->d_bases, pool->d_nmask, pool->d_lowq, R, pool->rl, k, HB, rpb, hcnt, hist_dbg);
-		else hipLaunchKernelGGL(k_gated_hist<false>, dim3(nblk), dim3(HIST_THREADS), lds_hist, st, pool->d_bases, pool->d_nmask, pool->d_lowq, R, pool->rl, k, HB, rpb, hcnt, hist_dbg);
+		launch_hist(nblk, rpb, hcnt, S, Rv, samp);
 	}
 	dbg_sync(c, "k_gated_hist");
-	vdjx_scan_one(st, hcnt, NBH, hstart);
-	HIP_TRY(hipMemcpyAsync(c->h_pin, hstart + NBH, 4, hipMemcpyDeviceToHost, st));
+	const cut_cap cap{S, CUT_MARGIN_FLOOR, cut_margin_c() * (float) S};
+	if (S > 1 && sync_debug()) {
+		// the margin's calibration (profiles/README.md): the exact histogram beside the sampled one -- the worst shortfall of S * h in units
+		// of S * sqrt(h + 1), the largest bucket the sample saw nothing of, and the layout's size over the tuples' number
+		u32* exact;
+		HIP_TRY(db.alloc(&exact, NBH));
+		HIP_TRY(hipMemsetAsync(exact, 0, (size_t) NBH * 4, st));
+		const u32 nbe = (u32) std::max<size_t>(1, std::min<size_t>(HIST_BLOCKS, (R + 4095) / 4096));
+		launch_hist(nbe, (R + nbe - 1) / nbe, exact, 1u, R, samp);
+		std::vector<u32> he(NBH), hs(NBH);
+		HIP_TRY(hipMemcpyAsync(he.data(), exact, (size_t) NBH * 4, hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipMemcpyAsync(hs.data(), hcnt, (size_t) NBH * 4, hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipStreamSynchronize(st));
+		double worst = 0, n = 0, caps = 0;
+		u32 unseen = 0;
+		for (u32 b = 0; b < NBH; b++) {
+			worst = std::max(worst, ((double) he[b] - (double) S * hs[b]) / ((double) S * sqrt((double) hs[b] + 1.0)));
+			if (!hs[b]) unseen = std::max(unseen, he[b]);
+			n += he[b];
+			caps += (double) S * hs[b] + ceil((double) cap.cS * sqrt((double) hs[b] + 1.0)) + cap.floor;
+		}
+		fprintf(stderr, "[vdjx] sampled cut: S %u, 2^%u buckets, %.0f tuples, worst ratio %.3f, largest unseen bucket %u, capacities / tuples %.3f\n", S, HB, n, worst, unseen, n ? caps / n : 0.0);
+	}
+	if (S > 1) vdjx_scan_one(st, hcnt, NBH, hstart, cap);
+	else vdjx_scan_one(st, hcnt, NBH, hstart);
+	HIP_TRY(hipMemcpyAsync(c->h_pin, hstart + NBH, 8, hipMemcpyDeviceToHost, st));      // (the total and, behind it, the sampled count)
 	HIP_TRY(hipStreamSynchronize(st));
 	HIP_TRY(hipGetLastError());
 #ifdef VDJX_ABLATE
 	if (hist_dbg) return VDJX_ESTATE;             // (a cut histogram sizes nothing: the build stops here, profiles/histdbg.py reads the kernel's time)
 #endif
+	gh->HB = HB; gh->NBH = NBH; gh->hstart = hstart; gh->sym = sym; gh->S = S;
+	if (S > 1) {
+		const u64 s = ((const u32*) c->h_pin)[1], n_est = (u64) S * s;      // (below 2^32, like the capacities' total: see where S is decided)
+		gh->N = (u32) n_est;
+		gh->cap_total = *(const u32*) c->h_pin;
+		return VDJX_OK;
+	}
 	const u32 N = *(const u32*) c->h_pin;
 	c->stats["gated_instances"] = sym ? 2ull * N : N;      // k-mer instances that pass include_kmer (A2:240-259) in this pool (sym: a tuple stands for two)
-	gh->HB = HB; gh->NBH = NBH; gh->N = N; gh->hstart = hstart; gh->sym = sym;
+	gh->N = N;
 	return VDJX_OK;
+}
+
+// what the sampled cut adds up for the reduce stage's read-back: the tuples the cursors counted and the overflow word
+__global__ __launch_bounds__(1024) void k_cut_totals(const u32* __restrict__ bucket_start, const u32* __restrict__ bucket_end, u32 NB,
+                                                     const u32* __restrict__ over, u32* __restrict__ over_out, unsigned long long* __restrict__ total) {
+	__shared__ u32 wsum[16];
+	const u32 b = blockIdx.x * 1024u + threadIdx.x;
+	const u32 n = b < NB ? bucket_end[b] - bucket_start[b] : 0u;
+	const u32 incl = (u32) vdjx_wave_scan_add((int) n);
+	if ((threadIdx.x & 63u) == 63u) wsum[threadIdx.x >> 6] = incl;
+	__syncthreads();
+	if (threadIdx.x == 0) {
+		unsigned long long t = 0;
+		for (u32 w = 0; w < 16; w++) t += wsum[w];
+		if (t) atomicAdd(total, t);
+		if (blockIdx.x == 0) *over_out = *over;
+	}
 }
 
 // the cut: the gated instances as tuples, by bucket.  Bucket bits from the actual number of gated instances; in the sharded build every
 // rank must cut the same buckets, so there the geometry follows a number all ranks agree on (`geometry_instances`: the largest count
 // of any rank when they have compared them, a bound from the stride when they have not)
+// After a sampled histogram (gh.S > 1) the same geometry from the estimate, the buckets laid out by their capacities: every pass checks
+// its runs against the next bucket's start (part_round::reserve), a second pass reads its segments up to the first one's cursors and the
+// buckets end at the last pass's cursors (GTuples::bucket_end).  Beyond 2^15 buckets only the coarse cut is sized by the sample:
+// k_seg_hist_g counts the fine buckets from the first pass's output and the second pass writes dense.
 template <typename TUP, typename A>
 int stage_gated_cut(vdjx_ctx* c, A& db, const vdjx_pool* pool, u64 rec_base, int k, size_t per_bucket, u64 geometry_instances, const GatedHist& gh, GTuples<TUP>* out) {
 	hipStream_t st = c->stream;
@@ -2361,9 +2481,15 @@ int stage_gated_cut(vdjx_ctx* c, A& db, const vdjx_pool* pool, u64 rec_base, int
 	const u32 hb_max = pool->W > 2 ? 14u : 15u;
 	const bool lng = pool->W > 2;
 	const u32 HB = gh.HB, NBH = gh.NBH, N = gh.N;
+	const bool smp = gh.S > 1;
+	const size_t room = smp ? gh.cap_total : N;          // tuples the arrays hold
 	u32* hstart = gh.hstart;
 	size_t rpb;
-	out->N = N;
+	out->N = (u32) room;
+	out->S = gh.S;
+	// (the survivors' arrays: not by the layout's size -- the total's own sampling error is a small part of it; the same margin in the
+	// total's units, and stage_gated_reduce sends a build whose survivors do not fit back to the exact cut)
+	out->Nsurv = smp ? (u32) std::min<u64>(room, (u64) N + (u64) ceil((double) cut_margin_c() * gh.S * sqrt((double) (N / gh.S) + 1.0)) + CUT_MARGIN_FLOOR) : N;
 	const u64 Ng = geometry_instances ? geometry_instances : (u64) N;
 	static const size_t refine = (size_t) vdjx_env_num("VDJX_REFINE_TUPLES", 4096, 1, 1ll << 32);
 	u32 T = 8;
@@ -2379,7 +2505,7 @@ int stage_gated_cut(vdjx_ctx* c, A& db, const vdjx_pool* pool, u64 rec_base, int
 	}
 	const u32 Tt = T + extra;
 	const u32 NBt = 1u << Tt;
-	HIP_TRY(db.alloc(&out->t, (size_t) N + 1));
+	HIP_TRY(db.alloc(&out->t, room + 1));
 	constexpr u32 stage_tuples = PARTR_STAGE_BYTES / (u32) sizeof(TUP);
 	constexpr u32 lds_partr = PARTR_STAGE_BYTES + stage_tuples * 4;
 	// pass geometry: <= 1024 buckets in one pass; otherwise 256 coarse x the rest (large pools: 2^(Tt-10) coarse x 1024)
@@ -2389,10 +2515,15 @@ int stage_gated_cut(vdjx_ctx* c, A& db, const vdjx_pool* pool, u64 rec_base, int
 	u32 nblk2 = (u32) std::min<size_t>(1024, (R + 2047) / 2048);
 	if (nblk2 == 0) nblk2 = 1;
 	rpb = (R + nblk2 - 1) / nblk2;
-	u32* gcur;
+	u32 *gcur, *over = nullptr;
 	HIP_TRY(db.alloc(&gcur, NBc));
+	if (smp) {
+		HIP_TRY(db.alloc(&over, 1));
+		HIP_TRY(hipMemsetAsync(over, 0, 4, st));
+	}
+	out->over = over;
 	TUP* l1 = out->t;
-	if (fbits) HIP_TRY(db.alloc(&l1, (size_t) N + 1));
+	if (fbits) HIP_TRY(db.alloc(&l1, room + 1));
 	{
 		vdjx_prof_scope ps(c, "k_part_records");
 		// records per round: three quarters of the stage at the measured gated fraction, in whole sweeps of the workgroup
@@ -2401,38 +2532,43 @@ int stage_gated_cut(vdjx_ctx* c, A& db, const vdjx_pool* pool, u64 rec_base, int
 		rr = std::max<u64>(PART_THREADS, std::min<u64>(rr / PART_THREADS * PART_THREADS, lng ? 1u << 14 : 1u << 16));      // (the descriptor's record field)
 		auto* part_records = lng ? k_part_records_g<TUP, true> : sym ? k_part_records_g<TUP, false, true> : k_part_records_g<TUP, false>;
 		HIP_TRY(part_launch(st, part_records, nblk2, lds_partr, hstart, NBc, HB - cbits, gcur, l1, pool->d_bases, pool->d_nmask, pool->d_lowq, R, rec_base,
-		                    pool->rl, k, 64 - cbits, NBc, rpb, (u32) rr));
+		                    pool->rl, k, 64 - cbits, NBc, rpb, (u32) rr, smp ? (const u32*) hstart : (const u32*) nullptr, HB - cbits, over));
 	}
 	dbg_sync(c, "k_part_records");
 	u32* tstart;                                   // starts of the final buckets
 	HIP_TRY(db.alloc(&tstart, NBt + 1));
 	out->NB = NBt;
 	out->bucket_start = tstart;
+	out->bucket_end = tstart + 1;
+	const u32* seg_end = smp ? gcur : nullptr;     // (sampled: the coarse buckets end where the first pass's cursors stand)
 	constexpr u32 slices = PART_SLICES;
 	if (extra) {
 		u32* fine_cnt;
 		HIP_TRY(db.alloc(&fine_cnt, NBt));
 		HIP_TRY(hipMemsetAsync(fine_cnt, 0, (size_t) NBt * 4, st));
 		vdjx_prof_scope ps(c, "k_seg_hist");
-		hipLaunchKernelGGL(k_seg_hist_g<TUP>, dim3(NBc * slices), dim3(512), 0, st, l1, hstart, HB - cbits, slices, 64 - Tt, fbits, fine_cnt);
+		hipLaunchKernelGGL(k_seg_hist_g<TUP>, dim3(NBc * slices), dim3(512), 0, st, l1, hstart, HB - cbits, slices, 64 - Tt, fbits, fine_cnt, seg_end, (const u32*) over);
 		vdjx_scan_one(st, fine_cnt, NBt, tstart);
 	} else {
 		hipLaunchKernelGGL(k_pick_u32, dim3((NBt + 1 + 255) / 256), dim3(256), 0, st, hstart, 1u << (HB - Tt), NBt + 1, tstart);
+		if (smp && !fbits) out->bucket_end = gcur;
 	}
 	if (fbits) {
 		u32* gcur2;
 		HIP_TRY(db.alloc(&gcur2, NBt));
+		const bool lim2 = smp && !extra;           // (the fine buckets counted exactly: the second pass writes dense)
+		if (lim2) out->bucket_end = gcur2;
 		vdjx_prof_scope ps(c, "k_part_tuples");
 		HIP_TRY(part_launch(st, k_part<TUP, TupBucket<TUP>, part_segs>, NBc * slices, PART_LDS_BYTES, tstart, NBt, 0u, gcur2, out->t,
-		                    l1, part_segs{hstart, HB - cbits, slices, fbits}, TupBucket<TUP>{64 - Tt, (1u << fbits) - 1u}));
+		                    l1, part_segs{hstart, HB - cbits, slices, fbits, seg_end, lim2 ? (const u32*) tstart : (const u32*) nullptr, over}, TupBucket<TUP>{64 - Tt, (1u << fbits) - 1u}));
 	}
 	return VDJX_OK;
 }
 
 template <typename TUP, typename A>
-int stage_gated_partition(vdjx_ctx* c, A& db, const vdjx_pool* pool, u64 rec_base, int k, size_t per_bucket, u64 geometry_instances, GTuples<TUP>* out, bool sym = false) {
+int stage_gated_partition(vdjx_ctx* c, A& db, const vdjx_pool* pool, u64 rec_base, int k, size_t per_bucket, u64 geometry_instances, GTuples<TUP>* out, bool sym = false, u32 S = 1) {
 	GatedHist gh;
-	int rc = stage_gated_hist(c, db, pool, k, per_bucket, geometry_instances, &gh, sym);
+	int rc = stage_gated_hist(c, db, pool, k, per_bucket, geometry_instances, &gh, sym, S);
 	if (rc) return rc;
 	return stage_gated_cut<TUP>(c, db, pool, rec_base, k, per_bucket, geometry_instances, gh, out);
 }
@@ -2452,13 +2588,13 @@ int bucket_order(vdjx_ctx* c, A& db, const GTuples<TUP>& t, u32** order) {
 	*order = nullptr;
 	if (t.NB < 1024) return VDJX_OK;
 	HIP_TRY(db.alloc(order, t.NB));
-	hipLaunchKernelGGL(k_bucket_order, dim3(1), dim3(1024), 0, c->stream, t.bucket_start, t.NB, *order);
+	hipLaunchKernelGGL(k_bucket_order, dim3(1), dim3(1024), 0, c->stream, t.bucket_start, t.bucket_end, t.NB, *order);
 	return VDJX_OK;
 }
 
 // Phase A, table + prune per bucket
 template <typename TUP, typename A>
-int stage_gated_reduce(vdjx_ctx* c, A& db, const GTuples<TUP>& t, const PoolView& pv, u64 rec_base, int k, int mf, int mq, SurvivorsG* sv, bool sym = false) {
+int stage_gated_reduce(vdjx_ctx* c, A& db, GTuples<TUP>& t, const PoolView& pv, u64 rec_base, int k, int mf, int mq, SurvivorsG* sv, bool sym = false) {
 	hipStream_t st = c->stream;
 	int rc = set_sub_tuples(c);
 	if (rc) return rc;
@@ -2467,33 +2603,40 @@ int stage_gated_reduce(vdjx_ctx* c, A& db, const GTuples<TUP>& t, const PoolView
 	const u32 tlow = 1 + (mqq + 19) / 20;                           // see k_bucket_finalize
 	const u32 cmin = (u32) std::max(mf, 2);
 	const u32 mfu = (u32) std::max(mf, 0);
-	const u32 cap = (sym ? t.N : t.N / 2) + 16;                     // a survivor has at least two gated instances (sym: two survivors per two tuples)
+	const u32 cap = (sym ? t.Nsurv : t.Nsurv / 2) + 16;             // a survivor has at least two gated instances (sym: two survivors per two tuples)
 	u32 *g_err, *n_surv;
 	u64* g_distinct;
 	HIP_TRY(db.alloc(&sv->lo, cap)); HIP_TRY(db.alloc(&sv->hi, cap)); HIP_TRY(db.alloc(&sv->gcnt, cap)); HIP_TRY(db.alloc(&sv->gfirst, cap));
-	HIP_TRY(db.alloc(&g_distinct, 64 * 16 + 2));                     // one block, cleared and read back in one piece: the counters of distinct k-mers | error word, survivors | real survivors
+	HIP_TRY(db.alloc(&g_distinct, 64 * 16 + 3));                     // one block, cleared and read back in one piece: the counters of distinct k-mers | error word, survivors | real survivors, the sampled cut's overflow word | its tuples
 	g_err = (u32*) (g_distinct + 64 * 16);
 	n_surv = g_err + 1;
 	u32* n_real = g_err + 2;
-	HIP_TRY(hipMemsetAsync(g_distinct, 0, (64 * 16 + 2) * 8, st));
+	HIP_TRY(hipMemsetAsync(g_distinct, 0, (64 * 16 + 3) * 8, st));
+	if (t.over) hipLaunchKernelGGL(k_cut_totals, dim3((t.NB + 1023) / 1024), dim3(1024), 0, st, t.bucket_start, t.bucket_end, t.NB, (const u32*) t.over, g_err + 3,
+	                               (unsigned long long*) (g_distinct + 64 * 16 + 2));
 	SurvOutG so{sv->lo, sv->hi, sv->gcnt, sv->gfirst, n_surv, cap, n_real};
 	static const u32 rd_dbg = (u32) vdjx_env_num("VDJX_RD_DBG", 0, 0, 9);        // profiles/reducedbg.py: the kernel stops after a phase (shipped library: 9 only, the tests' way into the rescan)
 	if (t.N) {
 		vdjx_prof_scope ps(c, "k_gated_reduce");
 		u32* order;
 		if ((rc = bucket_order(c, db, t, &order))) return rc;
-		if (sym) hipLaunchKernelGGL((k_gated_reduce<TUP, true>), dim3(t.NB), dim3(RD_THREADS), 0, st, t.t, t.bucket_start, pv.bases, pv.nmask, pv.quals, pv.rl, pv.ob, k, rec_base,
+		if (sym) hipLaunchKernelGGL((k_gated_reduce<TUP, true>), dim3(t.NB), dim3(RD_THREADS), 0, st, t.t, t.bucket_start, t.bucket_end, (const u32*) t.over, pv.bases, pv.nmask, pv.quals, pv.rl, pv.ob, k, rec_base,
 		                            mfu, cmin, mqq, tlow, so, g_distinct, g_err, rd_dbg, (const u32*) order);
-		else hipLaunchKernelGGL(k_gated_reduce<TUP>, dim3(t.NB), dim3(RD_THREADS), 0, st, t.t, t.bucket_start, pv.bases, pv.nmask, pv.quals, pv.rl, pv.ob, k, rec_base,
+		else hipLaunchKernelGGL(k_gated_reduce<TUP>, dim3(t.NB), dim3(RD_THREADS), 0, st, t.t, t.bucket_start, t.bucket_end, (const u32*) t.over, pv.bases, pv.nmask, pv.quals, pv.rl, pv.ob, k, rec_base,
 		                        mfu, cmin, mqq, tlow, so, g_distinct, g_err, rd_dbg, (const u32*) order);
 	}
 	u64* spread = (u64*) c->h_pin;                    // [64 * 16], then ns, err
 	u32* tail = (u32*) (spread + 64 * 16);
-	static_assert((64 * 16 + 2) * 8 == VDJX_HPIN_SYNC_BYTES, "h_pin layout (vdjx_common.h)");
+	static_assert((64 * 16 + 3) * 8 == VDJX_HPIN_SYNC_BYTES, "h_pin layout (vdjx_common.h)");
 	HIP_TRY(hipMemcpyAsync(spread, g_distinct, VDJX_HPIN_SYNC_BYTES, hipMemcpyDeviceToHost, st));      // (one transfer: tail[] = error word, survivors, real survivors)
 	HIP_TRY(hipStreamSynchronize(st));
 	HIP_TRY(hipGetLastError());
 	const u32 ns = tail[1], err = tail[0];
+	if (t.over) {
+		if (tail[3] || ns > cap) return VDJX_ECUT;      // (a bucket ran over -- nothing was reduced -- or the survivors outgrew what the estimate gave them -- none was written past it: the build cuts again, exactly)
+		t.N = (u32) spread[64 * 16 + 2];
+		c->stats["gated_instances"] = sym ? 2ull * t.N : t.N;      // (exact: what the cursors counted, not the estimate)
+	}
 	if (err) { vdjx_set_error("k_gated_reduce: %u buckets could not be split to fit LDS", err); return VDJX_EHIP; }
 	if (ns > cap) { vdjx_set_error("survivor capacity logic failed (%u > %u)", ns, cap); return VDJX_EHIP; }
 	sv->ndist = 0;
@@ -2918,11 +3061,29 @@ int kmer_build_impl2(vdjx_ctx* c, const vdjx_pool* pool, int k, int mf, int mq, 
 	GTuples<TUP> t;
 	const bool sym = build_sym(pool, k);
 	c->stats["kmer_build_sym"] = sym ? 1 : 0;
-	int rc = stage_gated_partition<TUP>(c, db, pool, 0, k, 0, 0, &t, sym);
-	if (rc) return rc;
 	PoolView pv{pool->d_bases, pool->d_nmask, vdjx_qrows{pool->d_quals, pool->d_quals2, pool->q_split, pool->qstride}, pool->rl, pool->ob};
 	SurvivorsG sv;
-	rc = stage_gated_reduce<TUP>(c, db, t, pv, 0, k, mf, mq, &sv, sym);
+	// phase A: the cut from a sampled histogram where the pool is large enough (cut_sample_stride); should a bucket run over the
+	// capacity the sample gave it -- the reduce stage's read-back says so, nothing was reduced -- all of it again from the exact histogram
+	u32 S = cut_sample_stride(pool, sym ? pool->n_records / 2 : pool->n_records);
+	c->stats["kmer_build_cut_retries"] += 0;
+	const vdjx_arena::mark_t cut_mark = db.mark();
+	int rc;
+	for (bool first = true;; first = false) {
+		t = GTuples<TUP>();
+		sv = SurvivorsG();
+		rc = stage_gated_partition<TUP>(c, db, pool, 0, k, 0, 0, &t, sym, S);
+		if (rc) return rc;
+		if (first) c->stats["kmer_build_cut_sample"] = t.S;          // (the stride the build began with: what the histogram ran at)
+		rc = stage_gated_reduce<TUP>(c, db, t, pv, 0, k, mf, mq, &sv, sym);
+		if (rc != VDJX_ECUT || S == 1) break;
+		c->stats["kmer_build_cut_retries"] += 1;
+		fprintf(stderr, "[vdjx] k-mer build: a bucket ran over the capacity its sample of one row in %u gave it; cutting again from the exact histogram\n", S);
+		vdjx_clear_errors();
+		db.release_to(cut_mark);                   // (the stream has been waited for)
+		S = 1;
+	}
+	if (rc == VDJX_ECUT) { vdjx_set_error("k-mer build: the exact cut reports buckets over their capacity"); return VDJX_EHIP; }      // (cannot happen: S == 1 sets no word)
 	if (rc) return rc;
 	vdjx_ri_open_gate(c);          // phase A is done: a begun read-index build of this context runs beside the graph pass (vdjx_rindex.hip)
 	dbg_sync(c, "gated_reduce");
@@ -3150,9 +3311,9 @@ static int shard_local_impl(vdjx_shard* s) {
 		vdjx_prof_scope ps(c, "k_gated_local");
 		u32* order;
 		if ((rc = bucket_order(c, db, t, &order))) return rc;
-		if (s->sym) hipLaunchKernelGGL((k_gated_local<TUP, true>), dim3(t.NB), dim3(LG_THREADS), 0, st, t.t, t.bucket_start, s->pool->d_bases, s->pool->d_nmask, rec_base,
+		if (s->sym) hipLaunchKernelGGL((k_gated_local<TUP, true>), dim3(t.NB), dim3(LG_THREADS), 0, st, t.t, t.bucket_start, t.bucket_end, s->pool->d_bases, s->pool->d_nmask, rec_base,
 		                               s->k, s->pool->rl, s->pool->ob, s->tlow, sparse, sparse_ref, s->nd, s->low_inst, g_err, (const u32*) order);
-		else hipLaunchKernelGGL(k_gated_local<TUP>, dim3(t.NB), dim3(LG_THREADS), 0, st, t.t, t.bucket_start, s->pool->d_bases, s->pool->d_nmask, rec_base,
+		else hipLaunchKernelGGL(k_gated_local<TUP>, dim3(t.NB), dim3(LG_THREADS), 0, st, t.t, t.bucket_start, t.bucket_end, s->pool->d_bases, s->pool->d_nmask, rec_base,
 		                        s->k, s->pool->rl, s->pool->ob, s->tlow, sparse, sparse_ref, s->nd, s->low_inst, g_err, (const u32*) order);
 	}
 	vdjx_scan_one(st, s->nd, s->NBf, s->dstart);

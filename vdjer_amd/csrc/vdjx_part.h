@@ -8,7 +8,8 @@
 // resident) at a time.  Placement inside a bucket is arbitrary (the cursor bumps of the rounds race): what reads the buckets is order-free.
 //
 //   part_round   the bookkeeping of a round: begin, (count,) reserve, (slot,) flush.  k_part_records_g (vdjx_kmer.hip) counts and
-//                places from its own descriptors; everything else of its round is this
+//                places from its own descriptors; everything else of its round is this.  Where the buckets are capacities and not
+//                exact sizes (the k-mer build's sampled cut), limits names where they end and reserve refuses a run past its end
 //   part_slice   the share of a workgroup in a pass over segments; k_seg_hist_g counts the sub-buckets of the same slices
 //   k_part       the streaming pass: T elements in, T elements out, the bucket from a functor on the element, the range from
 //                part_share (one level, or the first of two) or part_segs (the second level)
@@ -27,6 +28,7 @@
 #define PART_SLICES 8u              // workgroups per coarse bucket in the second pass of the tuples (k_seg_hist_g, k_part over part_segs)
 #define PART_NONE 0xFFFFFFFFu       // the bucket of an element that is not there
 #define PART_HOLE 0xFFFFFFFFFFFFFFFFull      // the 8-byte element that the paired-load form of k_part drops
+#define PART_DEAD 0xFFFFFFFFu       // what reserve returns once a bucket of the pass has run over its limit: the workgroup stops
 
 namespace {
 
@@ -63,22 +65,50 @@ __device__ inline void part_store(u64* p, const u64& x) { *p = x; }
 // every one (slot) and stores it there.
 struct part_round {
 	u32 cnt[PART_MAXB], base[PART_MAXB + 1], cur[PART_MAXB], gbase[PART_MAXB], tmp[PART_THREADS];
+	u32 end[PART_MAXB];           // (limits) where the workgroup's buckets end
+	u32* over;
+	u32 dead, stop;
+
+	// Once per workgroup, before its first round, by all threads -- only in a pass whose buckets are laid out by CAPACITIES (the sampled
+	// cut of the k-mer build): bucket i ends before lim[(i + 1) << lsh].  A round with a run that would cross its limit sets the word
+	// `word`, and reserve returns PART_DEAD: the workgroup must write nothing of it (the rounds that fit write where they may; what reads
+	// the pass's output looks at the word first).  The rounds do NOT poll the word: a workgroup goes on until a run of its own would
+	// cross a limit -- every writer checks its own runs, so nothing is written past a limit either way.  The limits stay in LDS: a
+	// workgroup's buckets are the same in all its rounds.  lim == nullptr: the buckets are exact, nothing is checked.
+	// `seen`: a word that says the pass's INPUT is void (an earlier pass ran over; it may be the word this pass sets itself, and then
+	// changes while the kernel runs).  ONE thread reads it, and the answer -- true: the workgroup returns at once, all of it -- is the
+	// same in every thread: waves of one workgroup that read the word for themselves could disagree, and those that went on would
+	// scan and flush counts the others never cleared.
+	__device__ inline bool limits(u32 nbk, const u32* __restrict__ lim, u32 lsh, u32* word, const u32* seen = nullptr) {
+		if (lim) for (u32 i = threadIdx.x; i < nbk; i += PART_THREADS) end[i] = lim[((size_t) i + 1) << lsh];
+		if (threadIdx.x == 0) {
+			over = lim ? word : nullptr;
+			stop = seen ? __hip_atomic_load(seen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+		}
+		__syncthreads();
+		return stop != 0;
+	}
 
 	__device__ inline void begin(u32 nbk) {
 		for (u32 i = threadIdx.x; i < nbk; i += PART_THREADS) cnt[i] = 0;
+		if (threadIdx.x == 0) dead = 0;
 		__syncthreads();
 	}
 	__device__ inline void count(u32 b) { atomicAdd(&cnt[b], 1u); }
 	// after a barrier behind the last count: the buckets' places in the stage and their runs in the output, bucket i's from gcur[i];
-	// returns the number of elements of the round
+	// returns the number of elements of the round, or PART_DEAD (limits)
 	__device__ inline u32 reserve(u32 nbk, u32* __restrict__ gcur) {
 		part_scan(cnt, base, tmp, nbk);
+		u32* const word = over;
 		for (u32 i = threadIdx.x; i < nbk; i += PART_THREADS) {
 			cur[i] = base[i];
-			gbase[i] = cnt[i] ? atomicAdd(&gcur[i], cnt[i]) : 0u;
+			const u32 n = cnt[i];
+			const u32 g = n ? atomicAdd(&gcur[i], n) : 0u;
+			gbase[i] = g;
+			if (word && (u64) g + n > (u64) end[i]) { dead = 1; atomicExch(word, 1u); }
 		}
 		__syncthreads();
-		return base[nbk];
+		return dead ? PART_DEAD : base[nbk];
 	}
 	__device__ inline u32 slot(u32 b) { return atomicAdd(&cur[b], 1u); }
 	// after a barrier behind the last store to the stage: the n staged elements to their runs (the bucket again from the element)
@@ -93,11 +123,11 @@ struct part_round {
 };
 
 // a pass over segments with `slices` workgroups each: workgroup blockIdx.x has slice blockIdx.x % slices of segment blockIdx.x / slices,
-// which is [seg_start[seg << seg_shift], seg_start[(seg + 1) << seg_shift]).  Returns the segment; [t0, t1) is empty for a slice that
-// gets nothing.
-__device__ inline u32 part_slice(const u32* __restrict__ seg_start, u32 seg_shift, u32 slices, size_t& t0, size_t& t1) {
+// which is [seg_start[seg << seg_shift], seg_start[(seg + 1) << seg_shift]) -- or, where the earlier pass filled a layout of capacities,
+// ends at seg_end[seg], the cursor that pass left.  Returns the segment; [t0, t1) is empty for a slice that gets nothing.
+__device__ inline u32 part_slice(const u32* __restrict__ seg_start, u32 seg_shift, u32 slices, size_t& t0, size_t& t1, const u32* __restrict__ seg_end = nullptr) {
 	const u32 seg = blockIdx.x / slices, sl = blockIdx.x % slices;
-	const size_t s0 = seg_start[(size_t) seg << seg_shift], s1 = seg_start[((size_t) seg + 1) << seg_shift];
+	const size_t s0 = seg_start[(size_t) seg << seg_shift], s1 = seg_end ? seg_end[seg] : seg_start[((size_t) seg + 1) << seg_shift];
 	const size_t per = (s1 - s0 + slices - 1) / slices;
 	t0 = s0 + (size_t) sl * per;
 	t1 = t0 + per < s1 ? t0 + per : s1;
@@ -117,15 +147,24 @@ struct part_share {
 		buckets = nbk;
 		return 0;
 	}
+	__device__ inline const u32* limits(size_t) const { return nullptr; }
+	__device__ inline u32* over_word() const { return nullptr; }
 };
-// part_segs: a slice of a segment of an earlier pass, cut into 2^sub_bits buckets with cursors of the segment's own
+// part_segs: a slice of a segment of an earlier pass, cut into 2^sub_bits buckets with cursors of the segment's own.  seg_end: the
+// segments' ends where they are not the next segments' starts (part_slice); lim / over: this pass's own buckets have limits, bucket j
+// of all of them ends before lim[j + 1] (part_round::reserve)
 struct part_segs {
 	const u32* seg_start;
 	u32 seg_shift, slices, sub_bits;
+	const u32* seg_end = nullptr;
+	const u32* lim = nullptr;
+	u32* over = nullptr;
 	__device__ inline size_t span(u32, size_t& t0, size_t& t1, u32& buckets) const {
 		buckets = 1u << sub_bits;
-		return (size_t) part_slice(seg_start, seg_shift, slices, t0, t1) << sub_bits;
+		return (size_t) part_slice(seg_start, seg_shift, slices, t0, t1, seg_end) << sub_bits;
 	}
+	__device__ inline const u32* limits(size_t first) const { return lim ? lim + first : nullptr; }
+	__device__ inline u32* over_word() const { return over; }
 };
 
 // The streaming pass.  key(element) is its bucket among the workgroup's (below the range's number of buckets).  PAIRED: 8-byte elements
@@ -141,7 +180,11 @@ __global__ __launch_bounds__(PART_THREADS) void k_part(const T* __restrict__ in,
 	static_assert(!PAIRED || (std::is_same<T, u64>::value && PER % 2 == 0), "the paired loads are for 8-byte elements");
 	size_t t0, t1;
 	u32 nbk;
-	u32* gc = gcur + range.span(ROUND, t0, t1, nbk);
+	// (the range's word set: the pass before ran over and its cursors bound nothing that may be read, or a workgroup of this pass did and
+	// the rest is for nothing.  span reads starts and cursors only; nothing of the input is touched before the workgroup has decided)
+	const size_t first = range.span(ROUND, t0, t1, nbk);
+	u32* gc = gcur + first;
+	if (pr.limits(nbk, range.limits(first), 0u, range.over_word(), range.over_word())) return;      // (uniform)
 	for (size_t ts = t0; ts < t1; ts += ROUND) {
 		const size_t te = ts + ROUND < t1 ? ts + ROUND : t1;
 		pr.begin(nbk);
@@ -172,6 +215,7 @@ __global__ __launch_bounds__(PART_THREADS) void k_part(const T* __restrict__ in,
 		}
 		__syncthreads();
 		const u32 n = pr.reserve(nbk, gc);
+		if (n == PART_DEAD) return;                                   // (uniform)
 #pragma unroll
 		for (u32 j = 0; j < PER; j++) if (r_b[j] != PART_NONE) part_store(&stage[pr.slot(r_b[j])], r_x[j]);
 		__syncthreads();

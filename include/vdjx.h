@@ -674,8 +674,8 @@ int vdjx_lineage_threshold(vdjx_ctx* ctx, const int32_t* nearest, const uint32_t
  *   info        (may be NULL; zeroed first, every field filled on success) members: participating items; clones; largest_clone: the
  *               members of the largest; edges = members - clones; weight: the sum of every out_dist >= 0; rounds = ceil(log2
  *               largest_clone), the Boruvka passes launched: 0 when no clone has two members.
- * NOT modelled: alignment of members that differ by an indel (the comparison is column by column); inferred intermediate nodes, maximum
- * parsimony or likelihood; Newick output; a germline sequence as a node of its own: the root is an observed contig.
+ * NOT modelled: alignment of members that differ by an indel (the comparison is column by column); maximum parsimony or likelihood; a
+ * germline sequence as a node of its own: the root is an observed contig.  Inferred intermediate nodes and Newick output: vdjx_tree_nj.
  * VDJX_EINVAL: n >= 2^20, len < 1 or len >= 4096, contigs of unequal length (a NUL inside the n*len characters), clone[i] < -1, a member's
  * anchor outside 0 .. len, an empty window (w = 0: a member anchored at 0 and one at len), NULL out_parent / out_dist / out_depth.  n = 0
  * returns at once with a zeroed info.  The (clone, index) keys are sorted on the host (per item), which also computes the windows;
@@ -727,6 +727,62 @@ typedef struct { uint32_t replicates; uint64_t seed; } vdjx_tree_support_params;
 typedef struct { uint32_t members, clones, largest_clone, replicates, batches, rounds; uint64_t edges, matched, full; } vdjx_tree_support_info;   /* 48 bytes */
 int vdjx_tree_support(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const int32_t* clone, const int32_t* anchor,
                       const int32_t* parent, const vdjx_tree_support_params* params, int32_t* out_support, vdjx_tree_support_info* info);
+
+/* ---- neighbour-joining lineage trees with inferred ancestors ---------------------------------------------------------------------------
+ * a minimum spanning tree can only hang observed contigs under observed contigs: two sisters that share three mutations become parent and
+ * child, and the ancestor that carried the three is nowhere.  This call gives `vdjer --trees-nj` what alakazam's buildPhylipLineage and
+ * dowser's getTrees add to a clone table: the unobserved ancestors, branch lengths between them, and (through the command line) a Newick
+ * file.  All arithmetic is integer: the device's results are bitwise the model's (tests/tree_nj_model.py).
+ *   items       contigs, n, len, clone[], anchor[], prio exactly as vdjx_tree takes them; the windows (a, b), w = a + b and the distance
+ *               d(i, j) are as there.
+ *   nodes       inside a lineage of m members the leaves have ids 0 .. m - 1 in ascending caller index; inferred nodes get m, m + 1, ...
+ *               in the order they are made: max(0, m - 2) of them, and for m >= 2 there are 2m - 3 edges.
+ *   joining     D[i][j] = d(i, j) << 16 (64-bit).  While more than three nodes are active, r of them: R[i] = the sum of D[i][k] over
+ *               the active k != i; Q(i, j) = (r - 2) D[i][j] - R[i] - R[j]; the pair with the smallest key (Q, i, j), i < j by node id,
+ *               is joined into a new node u with b_i = floor(((r - 2) D[i][j] + R[i] - R[j]) / (2 (r - 2))) (toward minus infinity),
+ *               b_j = D[i][j] - b_i and D[u][k] = floor((D[i][k] + D[j][k] - D[i][j]) / 2) for every other active k.  The last three
+ *               x < y < z meet in one more node: b_x = floor((D[x][y] + D[x][z] - D[y][z]) / 2), b_y = D[x][y] - b_x, b_z = D[x][z] -
+ *               b_x.  m = 3 is that step alone, m = 2 the one edge of length D[0][1], m = 1 a lone root.  Negative branch lengths are
+ *               kept as computed (as ape's nj does) and counted.  Where distances tie the tree depends on the order of the contigs: the
+ *               key is the definition.
+ *   root        the member with the smallest (prio[i], i), as vdjx_tree's; that leaf is the root of its lineage's tree and its single
+ *               neighbour its only child, so every inferred node has exactly two children.
+ *   ancestors   Fitch parsimony, every window column on its own, the base order A < C < G < T.  A leaf's set is its base if that is one
+ *               of ACGT, else all four: a character that never matches in the distance is a wildcard here, so an N costs branch length
+ *               but never a mutation.  Upward an inferred node's set is the intersection of its children's sets if that is not empty,
+ *               else their union.  The root's set is its leaf set intersected with its child's set if that is not empty, else its leaf
+ *               set; its state the lowest base of it.  Downward a node's state is its parent's state if that lies in its set, else the
+ *               lowest base of its set -- leaves too: a wildcard leaf takes its parent's base.  An inferred node's sequence is its w
+ *               states; a node's mutations the window columns at which its state differs from its parent's.
+ *   outputs     [nodes] each, nodes = vdjx_tree_nj_nodes(clone, n) = n + the sum of max(0, m - 2).  Slots 0 .. n - 1 are the caller's
+ *               items; the inferred nodes follow from slot n, lineage after lineage in ascending clone key, in creation order inside a
+ *               lineage.  out_parent holds slots; out_length the edge to the parent in 1/65536; out_depth the edges to the root;
+ *               out_clone the lineage's key.  A root has parent -1, length 0 and mutations -1; an item with clone = -1 has -1
+ *               everywhere.  out_anc (may be NULL: the mutations are still counted) is [nodes - n][len]: the inferred node's w states
+ *               as characters, NUL from w on.
+ *   info        (may be NULL; zeroed first, every field filled on success) members, clones, largest_clone as vdjx_tree's; internal: the
+ *               inferred nodes; batches; negative: the edges of negative length; edges; joins: the pair joins, the sum of max(0, m - 3);
+ *               cells: the sum of m * m over the lineages of two and more; parsimony: the sum of the mutations; length: of the lengths.
+ * NOT modelled: maximum likelihood; dnapars' search over topologies; the germline as a node of its own; alignment of members that differ
+ * by an indel; support values for this tree; Sankoff costs from a targeting model.
+ * VDJX_EINVAL: everything vdjx_tree refuses, and a NULL output other than out_anc.  VDJX_ELIMIT: a lineage of more than
+ * VDJX_NJ_MAX_MEMBERS members, named with its size before any GPU work.  n = 0 returns at once with a zeroed info.
+ * The host sorts the keys and computes the windows as vdjx_tree does.  The lineages of two and more run in batches of whole lineages of at
+ * most VDJX_NJ_CELLS matrix cells of 8 bytes (1 .. 2^28, the default 2^26, read per call; a lineage of more cells goes alone; any value
+ * gives the same bytes).  A batch is the matrix kernel (a wave per lineage, row block and column slice, storing d << 16), the join kernel
+ * (a workgroup per lineage: the matrix in LDS up to VDJX_NJ_LDS_MEMBERS members -- 32 KiB, four workgroups per CU -- and in global memory
+ * beyond; a fixed m - 3 rounds of a block-wide arg-min in 64-bit integers and a row update, m^3 / 6 evaluations of Q in all) and, after
+ * the host has rooted the edges (O(nodes)), Fitch's two passes (a wave per lineage and 64 columns, a lane per column).  Integer atomics
+ * are sums only: two calls give the same bits.  No floating point; scratch comes from the context's workspace.  Stats: "tree_nj_us" (host
+ * clock), "tree_nj_cells", "tree_nj_joins". */
+#define VDJX_NJ_LDS_MEMBERS  64u        /* the largest lineage whose matrix the join kernel keeps in LDS (the tests run this size and the next) */
+#define VDJX_NJ_MAX_MEMBERS  4096u
+typedef struct { uint32_t members, clones, largest_clone, internal, batches, negative;
+                 uint64_t edges, joins, cells, parsimony; int64_t length; } vdjx_tree_nj_info;                  /* 64 bytes */
+int vdjx_tree_nj_nodes(const int32_t* clone, size_t n, uint64_t* nodes);      /* plain C, no GPU: n + the sum of max(0, m - 2) */
+int vdjx_tree_nj(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const int32_t* clone, const int32_t* anchor, const uint32_t* prio,
+                 int32_t* out_parent, int64_t* out_length, int32_t* out_mutations, int32_t* out_depth, int32_t* out_clone /* each [nodes] */,
+                 char* out_anc /* [nodes - n][len], NUL past w; may be NULL */, vdjx_tree_nj_info* info);
 
 /* ---- germline rows and R/S mutation counts: the contig and its V(D)J germline side by side, classified codon by codon ----------------
  * gives `vdjer --mutations` what Change-O's CreateGermlines and shazam's observedMutations make of V'DJer's output in a second tool: the

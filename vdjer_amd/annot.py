@@ -164,6 +164,49 @@ def tree_inputs(ids, contigs, v, clone):
     return anchor, prio
 
 
+def tree_nj_newick(ids, clone, parent, length):
+    """the trees of Context.tree_nj as `vdjer --trees-newick` writes them: one string per lineage of two and more members, in ascending
+    lineage number.  ids: the n contigs' names; clone: int32[n], the 0-based lineage number of every contig (-1: none), the clone given to
+    tree_nj; parent, length: tree_nj's, [nodes].  The tree is rooted at the root member: (<its one subtree>)'<root id>'; -- children in
+    ascending slot, every node labelled and single-quoted, 'label':%.4f of length / 65536; an inferred node is lin_<k>_a<j>, j from 1
+    in creation order.  Plain Python, no recursion: a lineage may be thousands of nodes deep."""
+    n, nodes = len(ids), len(parent)
+    sizes = {}
+    for k in clone:
+        if int(k) >= 0:
+            sizes[int(k)] = sizes.get(int(k), 0) + 1
+    names = list(ids)
+    for k in sorted(sizes):
+        names += [f"lin_{k + 1}_a{j + 1}" for j in range(max(0, sizes[k] - 2))]
+    if len(names) != nodes:
+        raise ValueError(f"tree_nj_newick: {nodes} nodes, but the clones of the {n} contigs make {len(names)}")
+    kids = [[] for _ in range(nodes)]
+    for s in range(nodes):
+        if int(parent[s]) >= 0:
+            kids[int(parent[s])].append(s)
+    roots = {int(clone[s]): s for s in range(n) if int(clone[s]) >= 0 and int(parent[s]) < 0}
+    out = []
+    for k in sorted(roots):
+        if not kids[roots[k]]:
+            continue
+        text, stack = [], [(roots[k], 0)]
+        while stack:
+            s, at = stack.pop()
+            if at == 0 and kids[s]:
+                text.append("(")
+            if at < len(kids[s]):
+                if at:
+                    text.append(",")
+                stack.append((s, at + 1))
+                stack.append((kids[s][at], 0))
+                continue
+            if kids[s]:
+                text.append(")")
+            text.append(f"'{names[s]}'" + ("" if s == roots[k] else ":%.4f" % (int(length[s]) / 65536)))
+        out.append("".join(text) + ";")
+    return out
+
+
 def mutation_limit(ids, contigs):
     """the limit `vdjer --mutations` hands to vdjx_mutations -> int32[n]: V mutations are counted below the 0-based start of the junction
     (junction_of) plus 3, through the conserved Cys codon: what follows is the CDR3, where the germline row is not the V gene's to

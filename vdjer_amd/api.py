@@ -1115,6 +1115,33 @@ class Context:
         check(self.L.vdjx_tree_support(self.h, raw, n, ln, _p(cl), _p(an), _p(pa), C.byref(params), _p(support), C.byref(info)), "vdjx_tree_support")
         return {"support": support, "info": {f: int(getattr(info, f)) for f in self.TREE_SUPPORT_FIELDS}}
 
+    TREE_NJ_FIELDS = ("members", "clones", "largest_clone", "internal", "batches", "negative", "edges", "joins", "cells", "parsimony", "length")
+
+    def tree_nj(self, contigs, clone, anchor, prio=None, ancestors=True):
+        """vdjx_tree_nj: the neighbour-joining tree of every clone in 16.16 fixed point over the members' common window, rooted at the member
+        of smallest (prio, index), with the inferred nodes' sequences and every edge's mutations by Fitch parsimony.  contigs, clone, anchor,
+        prio as tree() takes them -> {"parent" int32, "length" int64 (1/65536), "mutations", "depth", "clone" int32: [nodes] each -- slots
+        0 .. n - 1 the items, the inferred nodes from n on, lineage after lineage in ascending clone key (-1: no part; a root has parent -1,
+        length 0, mutations -1), "anc": the inferred nodes' windows as str (None with ancestors=False), "info": dict(TREE_NJ_FIELDS)}"""
+        raw, n, ln = self._contig_block(contigs, "vdjx_tree_nj")
+        cl = np.ascontiguousarray(clone, np.int32)
+        an = np.ascontiguousarray(anchor, np.int32)
+        pr = None if prio is None else np.ascontiguousarray(prio, np.uint32)
+        if cl.shape != (n,) or an.shape != (n,) or (pr is not None and pr.shape != (n,)):
+            raise VdjxError(f"vdjx_tree_nj: {n} contigs, clone of shape {cl.shape}, anchor of shape {an.shape}")
+        total = C.c_uint64(0)
+        check(self.L.vdjx_tree_nj_nodes(_p(cl), n, C.byref(total)), "vdjx_tree_nj_nodes")
+        nodes = int(total.value)
+        parent, mutations, depth, out_clone = (np.zeros(nodes, np.int32) for _ in range(4))
+        length = np.zeros(nodes, np.int64)
+        anc = np.zeros((nodes - n, max(ln, 1)), np.uint8) if ancestors else None
+        info = _lib.TreeNjInfo()
+        check(self.L.vdjx_tree_nj(self.h, raw, n, ln, _p(cl), _p(an), _p(pr), _p(parent), _p(length), _p(mutations), _p(depth), _p(out_clone),
+                                  _p(anc), C.byref(info)), "vdjx_tree_nj")
+        return {"parent": parent, "length": length, "mutations": mutations, "depth": depth, "clone": out_clone,
+                "anc": None if anc is None else [row.tobytes().split(b"\0", 1)[0].decode("latin-1") for row in anc],
+                "info": {f: int(getattr(info, f)) for f in self.TREE_NJ_FIELDS}}
+
     DIVERSITY_FIELDS = ("clones", "weighted", "weight", "depth", "replicates", "batches", "path")
 
     def diversity(self, weight, depth, q=None, replicates=200, seed=1, counts=False):

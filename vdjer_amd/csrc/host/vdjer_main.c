@@ -5,7 +5,7 @@
  *   vdjer --in <reads> --chain IGH|IGK|IGL --ref-dir <dir> --ins <n> [--t --k --mf --mq --mcs --am --miw --maw
  *         --jc --ws -jext --rf --vk --mrs --rs --ms --e0 --e1 --wo --vf --jf --rms] [--gpus N] [--quant <file>] [--quant-boot <B>] [--quant-seed <s>] [--airr <file>]
  *         [--d-calls] [--cfa <fasta>] [--isotypes <file>] [--clones <file>] [--sample <name>] [--total-count <n>]
- *         [--lineages <file>] [--lineage-dist <x>] [--lineage-model <file>] [--lineage-symmetry avg|min] [--lineage-threshold <file>] [--lineage-link single|complete|average] [--trees <file>] [--tree-support <B>] [--tree-seed <s>] [--mutations <file>]
+ *         [--lineages <file>] [--lineage-dist <x>] [--lineage-model <file>] [--lineage-symmetry avg|min] [--lineage-threshold <file>] [--lineage-link single|complete|average] [--trees <file>] [--tree-support <B>] [--tree-seed <s>] [--trees-nj <file>] [--trees-newick <file>] [--mutations <file>]
  *         [--diversity <file>] [--diversity-depth <n>] [--diversity-boot <B>] [--diversity-seed <s>]
  *         [--selection <file>] [--v-regions <file>] [--targeting <file>] [--selection-combine shared|mean] [--selection-test <file>]
  *         [--targeting-model <file>] [--targeting-class s|rs] [--targeting-min-sub <n>] [--targeting-min-mut <n>] [--targeting-counts <file>]
@@ -74,6 +74,7 @@
 #include "vdjh.h"
 #include "bamx.h"
 #include "vdjx_mgpu.h"
+#include "vdjx_newick.h"
 #include <errno.h>
 #include <sys/wait.h>
 #include <sys/resource.h>
@@ -107,6 +108,7 @@ typedef struct {
 	const char* lin_threshold;             /* --lineage-threshold <file>: choose --lineage-dist from the nearest distances (vdjx_lineage_threshold) and write its histogram and density */
 	const char* lin_link; int lin_linkage;  /* --lineage-link single|complete|average -> 0, 1, 2 (vdjx_lineage_link; 0: the two calls above, as without the flag) */
 	const char* trees;                     /* --trees <file> (not in the reference): the tree inside every lineage of --lineages, on the device */
+	const char *trees_nj, *trees_newick;   /* --trees-nj <file>, --trees-newick <file> (not in the reference): neighbour-joining trees with inferred ancestors, and their Newick lines */
 	const char *tree_support, *tree_seed;  /* --tree-support <B>, --tree-seed <s>: the jackknife support of the trees' edges; read into ts_b (0: none) and ts_seed */
 	uint32_t ts_b; uint64_t ts_seed;
 	const char* mutations;                 /* --mutations <file> (not in the reference): CreateGermlines / observedMutations, on the device */
@@ -154,6 +156,8 @@ static void usage(void) {
 	                "\t--lineage-threshold <file: with --lineages, choose the threshold from the distances to the nearest neighbour (the valley between their two modes; --lineage-dist stands when there is none) and write their histogram and smoothed density>\n"
 	                "\t--lineage-link <single|complete|average: with --lineages, the linkage the lineages are cut at the threshold under (default: single; where distances tie, complete and average depend on the contigs' order)>\n"
 	                "\t--trees <file: with --lineages, the minimum spanning tree inside every lineage: parent, distance and depth of every contig>\n"
+	                "\t--trees-nj <file: with --lineages, the neighbour-joining tree inside every lineage with its inferred ancestors: a row per node>\n"
+	                "\t--trees-newick <file: with --trees-nj, one Newick line per lineage of two and more members>\n"
 	                "\t--tree-support <B: with --trees, a support column from B delete-half jackknife replicates, a whole number in 1 .. 1024>\n"
 	                "\t--tree-seed <seed of the replicates' columns, a whole number below 2^64 (default: 1)>\n"
 	                "\t--mutations <file: every contig beside its V(D)J germline, and the V segment's replacement / silent / stop mutation counts>\n"
@@ -333,6 +337,8 @@ static int parse(int argc, char** argv, cli* c) {
 		else if (!strcmp(a, "--lineage-threshold")) c->lin_threshold = v;
 		else if (!strcmp(a, "--lineage-link")) c->lin_link = v;
 		else if (!strcmp(a, "--trees")) c->trees = v;
+		else if (!strcmp(a, "--trees-nj")) c->trees_nj = v;
+		else if (!strcmp(a, "--trees-newick")) c->trees_newick = v;
 		else if (!strcmp(a, "--tree-support")) c->tree_support = v;
 		else if (!strcmp(a, "--tree-seed")) c->tree_seed = v;
 		else if (!strcmp(a, "--mutations")) c->mutations = v;
@@ -446,6 +452,8 @@ static int parse(int argc, char** argv, cli* c) {
 		else { fprintf(stderr, "--lineage-link must be single, complete or average: %s\n", c->lin_link); ok = 0; }
 	}
 	if (c->trees && !c->lineages) { fprintf(stderr, "--trees writes the tree inside every lineage of the --lineages table: it needs --lineages <file>\n"); ok = 0; }
+	if (c->trees_nj && !c->lineages) { fprintf(stderr, "--trees-nj writes the neighbour-joining tree inside every lineage of the --lineages table: it needs --lineages <file>\n"); ok = 0; }
+	if (c->trees_newick && !c->trees_nj) { fprintf(stderr, "--trees-newick writes the trees of --trees-nj as Newick lines: it needs --trees-nj <file>\n"); ok = 0; }
 	c->ts_b = 0;
 	c->ts_seed = 1;
 	if (c->tree_support && !c->trees) { fprintf(stderr, "--tree-support adds the support column to the --trees table: it needs --trees <file>\n"); ok = 0; }
@@ -876,6 +884,8 @@ typedef struct {
 	size_t l_contigs, l_eligible;
 	/* --trees: the tree inside every lineage (tree_run, after lineage_run) */
 	const char* trees; vdjx_tree_info ti;
+	/* --trees-nj, --trees-newick: the neighbour-joining trees with inferred ancestors (tree_nj_run, after tree_run) */
+	const char *trees_nj, *trees_newick; vdjx_tree_nj_info tni;
 	/* --tree-support: the jackknife support of the trees' edges (tree_run) */
 	uint32_t ts_b; uint64_t ts_seed; vdjx_tree_support_info tsi;
 	/* --mutations: the germline rows of every contig (mut_run), kept for the --airr table's two alignment cells */
@@ -1575,6 +1585,98 @@ static int tree_run(hook_ud* u, const char* const* ids, const char* contigs, siz
 	return rc;
 }
 
+/* --trees-nj: the neighbour-joining tree inside every lineage, with its inferred ancestors (the model: include/vdjx.h, vdjx_tree_nj; in
+ * Python: tests/tree_nj_model.py).  The clones, anchors and priorities are tree_run's.  A row per node: lineages in number order; inside one
+ * the members in contig order, then the inferred nodes lin_<k>_a<j> (j from 1) in creation order; parent_id and mutations empty for a root;
+ * branch_length = length / 65536; sequence: the node's window -- the observed characters of a member, Fitch's states of an inferred node.  A
+ * contig in no lineage has no row.  --trees-newick: a line per lineage of two and more members, lin_<k>, a tab, the tree (vdjx_newick.h) */
+typedef struct { const char* const* ids; const int32_t* clone; const uint32_t* number; size_t n; } nj_names;
+static void nj_label(FILE* fp, size_t s, void* ud) {
+	const nj_names* q = (const nj_names*) ud;
+	if (s < q->n) fputs(q->ids[s], fp);
+	else fprintf(fp, "lin_%d_a%u", q->clone[s] + 1, q->number[s - q->n] + 1);
+}
+
+static int tree_nj_run(hook_ud* u, const char* const* ids, const char* contigs, size_t n, int len) {
+	FILE* fp = fopen(u->trees_nj, "w");
+	if (!fp) { fprintf(stderr, "cannot write %s\n", u->trees_nj); return -1; }
+	FILE* np = u->trees_newick ? fopen(u->trees_newick, "w") : NULL;
+	if (u->trees_newick && !np) { fprintf(stderr, "cannot write %s\n", u->trees_newick); fclose(fp); return -1; }
+	fputs("clone_id\tnode_id\tparent_id\tbranch_length\tmutations\tdepth\tchildren\tobserved\tsequence\n", fp);
+	int32_t* anchor = (int32_t*) calloc(n + 1, sizeof(int32_t));
+	uint32_t* prio = (uint32_t*) calloc(n + 1, sizeof(uint32_t));
+	const size_t nk = (size_t) u->li.clones + 1;
+	int32_t* before = (int32_t*) malloc(nk * sizeof(int32_t));       /* per lineage: the window's bases before the anchor, and from it on */
+	int32_t* after = (int32_t*) malloc(nk * sizeof(int32_t));
+	size_t* first = (size_t*) calloc(nk + 1, sizeof(size_t));       /* per lineage: where its members start in member[] */
+	size_t* member = (size_t*) calloc(n + 1, sizeof(size_t));
+	for (size_t k = 0; k < nk; k++) before[k] = after[k] = len;
+	for (size_t i = 0; i < n; i++) {
+		const int32_t k = u->lin_clone[i];
+		if (k < 0) continue;
+		const vdjx_annot_hit* v = u->hv + i;
+		const char* jn;
+		size_t jl;
+		anchor[i] = (int32_t) junction_at(ids[i], contigs + i * (size_t) len, len, &jn, &jl);
+		prio[i] = (uint32_t) (v->mismatches + v->ins + v->del);
+		if (anchor[i] < before[k]) before[k] = anchor[i];
+		if (len - anchor[i] < after[k]) after[k] = len - anchor[i];
+		first[k + 1]++;
+	}
+	for (size_t k = 0; k < nk; k++) first[k + 1] += first[k];
+	{
+		size_t* fill = (size_t*) malloc((nk + 1) * sizeof(size_t));
+		for (size_t k = 0; k < nk; k++) fill[k] = first[k];
+		for (size_t i = 0; i < n; i++)
+			if (u->lin_clone[i] >= 0) member[fill[u->lin_clone[i]]++] = i;
+		free(fill);
+	}
+	uint64_t nodes = n;
+	int rc = n ? vdjx_tree_nj_nodes(u->lin_clone, n, &nodes) : 0;
+	const size_t inner = (size_t) (nodes - n);
+	int32_t* out = (int32_t*) calloc(4 * (size_t) nodes + 1, sizeof(int32_t));
+	int32_t *parent = out, *mut = out + nodes, *depth = out + 2 * nodes, *cl = out + 3 * nodes;
+	int64_t* length = (int64_t*) calloc((size_t) nodes + 1, sizeof(int64_t));
+	char* anc = (char*) calloc(inner * (size_t) len + 1, 1);
+	uint32_t* number = (uint32_t*) calloc(inner + 1, sizeof(uint32_t));
+	size_t* kid_off = (size_t*) calloc((size_t) nodes + 2, sizeof(size_t));
+	uint32_t* kid = (uint32_t*) calloc((size_t) nodes + 1, sizeof(uint32_t));
+	if (!rc) rc = vdjx_tree_nj(u->gx, contigs, n, len, u->lin_clone, anchor, prio, parent, length, mut, depth, cl, anc, &u->tni);
+	if (rc) fprintf(stderr, "--trees-nj: %s\n", vdjx_last_error());
+	if (!rc && newick_children(parent, (size_t) nodes, kid_off, kid)) { fprintf(stderr, "--trees-nj: the parents are no forest\n"); rc = -1; }
+	if (!rc) {
+		for (size_t a = 1; a < inner; a++) number[a] = cl[n + a] == cl[n + a - 1] ? number[a - 1] + 1 : 0;
+		const nj_names names = {ids, cl, number, n};
+		size_t slot = n;                                             /* the lineage's first inferred node */
+		for (size_t k = 0; k + 1 < nk; k++) {
+			const size_t m = first[k + 1] - first[k], extra = m > 2 ? m - 2 : 0;
+			const int w = before[k] + after[k];
+			size_t root = 0;
+			for (size_t q = 0; q < m + extra; q++) {
+				const size_t s = q < m ? member[first[k] + q] : slot + (q - m);
+				fprintf(fp, "lin_%zu\t", k + 1);
+				nj_label(fp, s, (void*) &names);
+				fputc('\t', fp);
+				if (parent[s] >= 0) nj_label(fp, (size_t) parent[s], (void*) &names); else root = s;
+				fprintf(fp, "\t%.4f\t", (double) length[s] / 65536.0);
+				if (parent[s] >= 0) fprintf(fp, "%d", mut[s]);
+				fprintf(fp, "\t%d\t%zu\t%c\t%.*s\n", depth[s], kid_off[s + 1] - kid_off[s], q < m ? 'T' : 'F', w,
+				        q < m ? contigs + s * (size_t) len + (anchor[s] - before[k]) : anc + (s - n) * (size_t) len);
+			}
+			if (np && m >= 2) {
+				fprintf(np, "lin_%zu\t", k + 1);
+				if (newick_write(np, root, length, (size_t) nodes, kid_off, kid, nj_label, (void*) &names)) { fprintf(stderr, "--trees-newick: lineage %zu is no tree\n", k + 1); rc = -1; break; }
+				fputc('\n', np);
+			}
+			slot += extra;
+		}
+	}
+	free(anchor); free(prio); free(before); free(after); free(first); free(member); free(out); free(length); free(anc); free(number); free(kid_off); free(kid);
+	if (np && fclose(np)) { fprintf(stderr, "cannot write %s\n", u->trees_newick); fclose(fp); return -1; }
+	if (fclose(fp)) { fprintf(stderr, "cannot write %s\n", u->trees_nj); return -1; }
+	return rc;
+}
+
 /* --mutations: the germline rows and the V mutation counts of every contig (the model: include/vdjx.h, vdjx_mutations; the limit:
  * mutation_limit of vdjer_amd/annot.py).  V mutations are counted below the junction's start + 3, through the conserved Cys codon: what
  * follows is the CDR3.  The D hits of --d-calls are laid into the gap; the rows are kept for the --airr table. */
@@ -1990,6 +2092,7 @@ static int tables(hook_ud* u, const char* const* ids, const char* contigs, size_
 	if (!rc && u->d_calls) rc = dcall_run(u, contigs, n, len);
 	if (!rc && u->lineages) rc = lineage_run(u, ids, contigs, n, len);
 	if (!rc && u->trees) rc = tree_run(u, ids, contigs, n, len);
+	if (!rc && u->trees_nj) rc = tree_nj_run(u, ids, contigs, n, len);
 	if (!rc && u->diversity) rc = diversity_run(u, n);
 	if (!rc && u->mutations) rc = mut_run(u, ids, contigs, n, len);
 	if (!rc && u->consensus) rc = cons_run(u, ids, contigs, n, len);
@@ -2272,7 +2375,7 @@ int main(int argc, char** argv) {
 	ud.qb_b = c.qb_b; ud.qb_seed = c.qb_seed;
 	ud.gx = gx; ud.p = &c.hp; ud.mg = mg; ud.quant = c.quant; ud.airr = c.airr; ud.vdjf = c.vdj_fasta; ud.d_calls = c.d_calls;
 	ud.cfa = c.cfa; ud.isotypes = c.isotypes; ud.clones = c.clones; ud.total_count = c.total_count;
-	ud.lineages = c.lineages; ud.lin_num = c.lin_num; ud.lin_den = c.lin_den; ud.lin_table = c.lin_table; ud.lin_sym = c.lin_sym; ud.lin_thr = c.lin_threshold; ud.lin_linkage = c.lin_linkage; ud.trees = c.trees;
+	ud.lineages = c.lineages; ud.lin_num = c.lin_num; ud.lin_den = c.lin_den; ud.lin_table = c.lin_table; ud.lin_sym = c.lin_sym; ud.lin_thr = c.lin_threshold; ud.lin_linkage = c.lin_linkage; ud.trees = c.trees; ud.trees_nj = c.trees_nj; ud.trees_newick = c.trees_newick;
 	ud.ts_b = c.ts_b; ud.ts_seed = c.ts_seed; ud.mutations = c.mutations;
 	ud.diversity = c.diversity; ud.dv_depth = c.div_depth; ud.dv_boot = c.div_boot; ud.dv_seed = c.div_seed;
 	ud.selection = c.selection; ud.regs = c.regs; ud.nregs = c.nregs; ud.weight = c.weight; ud.have_regs = c.v_regions != NULL;
@@ -2359,6 +2462,10 @@ int main(int argc, char** argv) {
 		fprintf(stderr, "tree support: %u replicates (seed %llu), %llu edges, %llu of %llu kept, %llu in every replicate, %u batches\n", c.ts_b,
 		        (unsigned long long) c.ts_seed, (unsigned long long) ud.tsi.edges, (unsigned long long) ud.tsi.matched,
 		        (unsigned long long) (ud.tsi.edges * c.ts_b), (unsigned long long) ud.tsi.full, ud.tsi.batches);
+	if (c.trees_nj)
+		fprintf(stderr, "trees nj: %u contigs in %u lineages (largest %u), %u inferred nodes, %llu edges, length %.4f, parsimony %llu, %u negative branches, %u batches\n",
+		        ud.tni.members, ud.tni.clones, ud.tni.largest_clone, ud.tni.internal, (unsigned long long) ud.tni.edges, (double) ud.tni.length / 65536.0,
+		        (unsigned long long) ud.tni.parsimony, ud.tni.negative, ud.tni.batches);
 	if (c.isotypes)
 		fprintf(stderr, "isotypes: %zu contigs, %zu called against %zu constant records of %s; table in %s\n", ud.i_contigs, ud.i_called,
 		        ud.cst ? ud.cst->n : (size_t) 0, c.cfa, c.isotypes);

@@ -675,7 +675,8 @@ int vdjx_lineage_threshold(vdjx_ctx* ctx, const int32_t* nearest, const uint32_t
  *               members of the largest; edges = members - clones; weight: the sum of every out_dist >= 0; rounds = ceil(log2
  *               largest_clone), the Boruvka passes launched: 0 when no clone has two members.
  * NOT modelled: alignment of members that differ by an indel (the comparison is column by column); maximum parsimony or likelihood; a
- * germline sequence as a node of its own: the root is an observed contig.  Inferred intermediate nodes and Newick output: vdjx_tree_nj.
+ * germline sequence as a node of its own: the root is an observed contig.  Inferred intermediate nodes and Newick output: vdjx_tree_nj; a
+ * search for the tree of fewest mutations: vdjx_tree_mp.
  * VDJX_EINVAL: n >= 2^20, len < 1 or len >= 4096, contigs of unequal length (a NUL inside the n*len characters), clone[i] < -1, a member's
  * anchor outside 0 .. len, an empty window (w = 0: a member anchored at 0 and one at len), NULL out_parent / out_dist / out_depth.  n = 0
  * returns at once with a zeroed info.  The (clone, index) keys are sorted on the host (per item), which also computes the windows;
@@ -763,7 +764,8 @@ int vdjx_tree_support(vdjx_ctx* ctx, const char* contigs, size_t n, int len, con
  *   info        (may be NULL; zeroed first, every field filled on success) members, clones, largest_clone as vdjx_tree's; internal: the
  *               inferred nodes; batches; negative: the edges of negative length; edges; joins: the pair joins, the sum of max(0, m - 3);
  *               cells: the sum of m * m over the lineages of two and more; parsimony: the sum of the mutations; length: of the lengths.
- * NOT modelled: maximum likelihood; dnapars' search over topologies; the germline as a node of its own; alignment of members that differ
+ * NOT modelled: maximum likelihood; dnapars' search over topologies (vdjx_tree_mp searches by nearest-neighbour interchanges from this
+ * tree); the germline as a node of its own; alignment of members that differ
  * by an indel; support values for this tree; Sankoff costs from a targeting model.
  * VDJX_EINVAL: everything vdjx_tree refuses, and a NULL output other than out_anc.  VDJX_ELIMIT: a lineage of more than
  * VDJX_NJ_MAX_MEMBERS members, named with its size before any GPU work.  n = 0 returns at once with a zeroed info.
@@ -783,6 +785,65 @@ int vdjx_tree_nj_nodes(const int32_t* clone, size_t n, uint64_t* nodes);      /*
 int vdjx_tree_nj(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const int32_t* clone, const int32_t* anchor, const uint32_t* prio,
                  int32_t* out_parent, int64_t* out_length, int32_t* out_mutations, int32_t* out_depth, int32_t* out_clone /* each [nodes] */,
                  char* out_anc /* [nodes - n][len], NUL past w; may be NULL */, vdjx_tree_nj_info* info);
+
+/* ---- maximum-parsimony lineage trees by a search over nearest-neighbour interchanges ---------------------------------------------------
+ * vdjx_tree_nj prints Fitch's parsimony of a tree nobody tried to make parsimonious.  alakazam's buildPhylipLineage runs dnapars and
+ * dowser's getTrees defaults to pratchet: both search over topologies for the tree of fewest mutations.  This call gives `vdjer
+ * --trees-mp` a hill-climbing search of that kind.  It is integer throughout: the device's results are bitwise the model's
+ * (tests/tree_mp_model.py).
+ *   items       contigs, n, len, clone[], anchor[], prio, the windows, the root and the node ids exactly as vdjx_tree_nj's: a lineage of m
+ *               members has the leaves 0 .. m - 1 in ascending caller index and the inferred nodes m .. 2m - 3; the root is the leaf of
+ *               smallest (prio, index) and its single neighbour its only child; every inferred node has two children, kept ascending by
+ *               local id.  The output slots are vdjx_tree_nj's: the items first, the inferred nodes from slot n, lineage after lineage in
+ *               ascending clone key.
+ *   start       start_parent[nodes], in those slots, is the caller's topology; only the entries of lineage members other than the roots
+ *               and of inferred nodes are read.  NULL: the tree vdjx_tree_nj gives the same arguments (that function's own steps are run as far
+ *               as its parents: its bits are the contract).  The ids of the inferred nodes are the start's and never change.
+ *   score       P(T): the sum over the window columns of Fitch's union events.  A leaf's set is its base if that is one of ACGT, else all
+ *               four (vdjx_tree_nj's wildcard rule); an inferred node's set is the intersection of its children's sets if that is not
+ *               empty, otherwise their union, and the column costs 1; at the root the column costs 1 more if the root leaf's set and its
+ *               child's set do not meet.  P(T) equals the sum of the edge mutations of vdjx_tree_nj's two passes on T, wildcards included.
+ *   candidates  (v, k): an inferred node v whose parent p is an inferred node too, k in {0, 1}.  With s p's other child and c = kid[v][k]
+ *               (ascending), the candidate swaps s and c: afterwards v's children are {s, kid[v][1 - k]} and p's {c, v}, both ascending
+ *               again, and the parents of s and c are exchanged.  A lineage of m members has 2 (m - 3); m <= 3 is not searched.
+ *   round       one round of one lineage scores every candidate; the one of smallest key (P, v, k) is applied if its P is below the
+ *               current P, otherwise the lineage is finished.  Where scores tie the key is the definition: the tree depends on the order
+ *               of the contigs.  params.max_rounds caps the scoring rounds of a lineage (0: until it is finished; every move lowers P by at
+ *               least 1, so the search ends on its own).
+ *   finish      Fitch's two passes on the final topology, exactly vdjx_tree_nj's rules: every inferred node's sequence, every node's
+ *               mutations and depth.  There are no separate branch lengths: an edge's length is its mutations.
+ *   outputs     [nodes] each, nodes = vdjx_tree_nj_nodes(clone, n); out_parent holds slots; a root has parent -1, depth 0, mutations -1;
+ *               an item with clone = -1 has -1 everywhere.  out_anc (may be NULL) is [nodes - n][len], NUL from w on.
+ *   info        (may be NULL; zeroed first) members, clones, largest_clone, internal, edges, batches as vdjx_tree_nj's; searched: the
+ *               lineages of four and more members; moved: those with at least one move; moves; rounds: the most scoring rounds any lineage
+ *               had; candidates: the sum over the lineages and their scoring rounds of 2 (m - 3); parsimony_start: P of the start trees;
+ *               parsimony: the sum of the final mutations (= P of the final trees).
+ * NOT modelled: SPR / TBR rearrangements and random restarts (dnapars, pratchet): nearest-neighbour interchanges stop in local optima, and
+ * from a poor start -- a caterpillar -- the search ends far above what it reaches from vdjx_tree_nj's tree; collapsing zero-length edges
+ * into multifurcations; a germline node; Sankoff costs; support values.
+ * VDJX_EINVAL: everything vdjx_tree_nj refuses; params->reserved != 0; a start_parent that is no such tree -- a parent outside the
+ * lineage, a root leaf without exactly one child, an inferred node without exactly two, another leaf with children, a cycle -- named with
+ * the lineage's clone key, before any GPU work.  VDJX_ELIMIT: a lineage of more than VDJX_MP_MAX_MEMBERS members, named with its size
+ * before any GPU work.  n = 0 returns at once with a zeroed info.
+ * Batches are vdjx_tree_nj's (whole lineages under VDJX_NJ_CELLS; any value gives the same bytes).  A batch keeps kid, par, one set byte
+ * per (inferred node, column), P and one int32 per candidate on the device.  A round is two dispatches: the scorer (a wave per lineage
+ * and candidate, 64 columns at a time; a swap at (v, k) changes only the sets of v, p and p's ancestors, so a lane recomputes those two and walks
+ * towards the root against the stored sets of the other children, until a wave-wide ballot says that no lane's set changed; integer
+ * atomicAdd of the wave's sum) and pick-and-apply (a workgroup per lineage still searching: block-wide arg-min of (delta, v, k), one thread
+ * rewires, all rewrite the stored sets along the path).  The host reads one counter per round from page-locked memory.  Then the host
+ * roots the final kid / par and vdjx_tree_nj's Fitch kernel runs unchanged.  Integer atomics are sums only: two calls give the same bits.
+ * No floating point; scratch comes from the context's workspace.  Stats: "tree_mp_us" (host clock over "tree_nj_us"'s span, from after the
+ * argument checks: the key sort, the layout and the start tree included),
+ * "tree_mp_candidates" (candidates scored), "tree_mp_steps" (the node updates the scorer made, counted per candidate and column tile: it
+ * depends on the launch geometry, so it is a stat and no info field; full rescoring would make candidates x (m - 2) per tile). */
+#define VDJX_MP_MAX_MEMBERS VDJX_NJ_MAX_MEMBERS
+typedef struct { uint32_t max_rounds, reserved; } vdjx_tree_mp_params;          /* reserved must be 0 */
+typedef struct { uint32_t members, clones, largest_clone, internal, batches, searched, moved, rounds;
+                 uint64_t edges, moves, candidates, parsimony_start, parsimony; } vdjx_tree_mp_info;           /* 72 bytes */
+int vdjx_tree_mp(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const int32_t* clone, const int32_t* anchor, const uint32_t* prio,
+                 const int32_t* start_parent /* [nodes] or NULL */, const vdjx_tree_mp_params* params /* NULL: {0, 0} */,
+                 int32_t* out_parent, int32_t* out_mutations, int32_t* out_depth, int32_t* out_clone /* each [nodes] */,
+                 char* out_anc /* [nodes - n][len]; may be NULL */, vdjx_tree_mp_info* info);
 
 /* ---- germline rows and R/S mutation counts: the contig and its V(D)J germline side by side, classified codon by codon ----------------
  * gives `vdjer --mutations` what Change-O's CreateGermlines and shazam's observedMutations make of V'DJer's output in a second tool: the

@@ -207,6 +207,14 @@ def tree_nj_newick(ids, clone, parent, length):
     return out
 
 
+def tree_mp_lengths(parent, mutations, clone):
+    """the branch lengths `vdjer --trees-mp` and `--trees-mp-newick` print for Context.tree_mp's result, in tree_nj's unit of 1/65536:
+    an edge's length is its mutations; 0 for a root, -1 for an item in no lineage.  tree_nj_newick takes them as they are."""
+    import numpy as np
+    parent, mutations, clone = (np.asarray(x) for x in (parent, mutations, clone))
+    return np.where(clone < 0, -1, np.where(parent < 0, 0, mutations.astype(np.int64) << 16)).astype(np.int64)
+
+
 def mutation_limit(ids, contigs):
     """the limit `vdjer --mutations` hands to vdjx_mutations -> int32[n]: V mutations are counted below the 0-based start of the junction
     (junction_of) plus 3, through the conserved Cys codon: what follows is the CDR3, where the germline row is not the V gene's to

@@ -1142,6 +1142,39 @@ class Context:
                 "anc": None if anc is None else [row.tobytes().split(b"\0", 1)[0].decode("latin-1") for row in anc],
                 "info": {f: int(getattr(info, f)) for f in self.TREE_NJ_FIELDS}}
 
+    TREE_MP_FIELDS = ("members", "clones", "largest_clone", "internal", "batches", "searched", "moved", "rounds", "edges", "moves", "candidates",
+                      "parsimony_start", "parsimony")
+
+    def tree_mp(self, contigs, clone, anchor, prio=None, start=None, max_rounds=0, ancestors=True, _reserved=0):
+        """vdjx_tree_mp: inside every clone, a search over nearest-neighbour interchanges for the tree of fewest Fitch mutations, from
+        tree_nj's tree (start=None) or from the caller's (start: int32[nodes], parents in tree_nj's slots); max_rounds caps a lineage's
+        scoring rounds (0: until no interchange lowers the total).  contigs, clone, anchor, prio as tree_nj() takes them -> {"parent",
+        "mutations", "depth", "clone" int32: [nodes] each, in tree_nj's slots (a root has parent -1 and mutations -1), "anc": the inferred
+        nodes' windows as str (None with ancestors=False), "info": dict(TREE_MP_FIELDS)}.  An edge's length is its mutations."""
+        raw, n, ln = self._contig_block(contigs, "vdjx_tree_mp")
+        cl = np.ascontiguousarray(clone, np.int32)
+        an = np.ascontiguousarray(anchor, np.int32)
+        pr = None if prio is None else np.ascontiguousarray(prio, np.uint32)
+        if cl.shape != (n,) or an.shape != (n,) or (pr is not None and pr.shape != (n,)):
+            raise VdjxError(f"vdjx_tree_mp: {n} contigs, clone of shape {cl.shape}, anchor of shape {an.shape}")
+        total = C.c_uint64(0)
+        check(self.L.vdjx_tree_nj_nodes(_p(cl), n, C.byref(total)), "vdjx_tree_nj_nodes")
+        nodes = int(total.value)
+        sp = None if start is None else np.ascontiguousarray(start, np.int32)
+        if sp is not None and sp.shape != (nodes,):
+            raise VdjxError(f"vdjx_tree_mp: start of shape {sp.shape} for {nodes} nodes")
+        if not 0 <= int(max_rounds) < 1 << 32:
+            raise VdjxError(f"vdjx_tree_mp: max_rounds {max_rounds}")
+        params = _lib.TreeMpParams(int(max_rounds), int(_reserved))
+        parent, mutations, depth, out_clone = (np.zeros(nodes, np.int32) for _ in range(4))
+        anc = np.zeros((nodes - n, max(ln, 1)), np.uint8) if ancestors else None
+        info = _lib.TreeMpInfo()
+        check(self.L.vdjx_tree_mp(self.h, raw, n, ln, _p(cl), _p(an), _p(pr), _p(sp), C.byref(params), _p(parent), _p(mutations), _p(depth),
+                                  _p(out_clone), _p(anc), C.byref(info)), "vdjx_tree_mp")
+        return {"parent": parent, "mutations": mutations, "depth": depth, "clone": out_clone,
+                "anc": None if anc is None else [row.tobytes().split(b"\0", 1)[0].decode("latin-1") for row in anc],
+                "info": {f: int(getattr(info, f)) for f in self.TREE_MP_FIELDS}}
+
     DIVERSITY_FIELDS = ("clones", "weighted", "weight", "depth", "replicates", "batches", "path")
 
     def diversity(self, weight, depth, q=None, replicates=200, seed=1, counts=False):

@@ -5,7 +5,7 @@
  *   vdjer --in <reads> --chain IGH|IGK|IGL --ref-dir <dir> --ins <n> [--t --k --mf --mq --mcs --am --miw --maw
  *         --jc --ws -jext --rf --vk --mrs --rs --ms --e0 --e1 --wo --vf --jf --rms] [--gpus N] [--quant <file>] [--quant-boot <B>] [--quant-seed <s>] [--airr <file>]
  *         [--d-calls] [--cfa <fasta>] [--isotypes <file>] [--clones <file>] [--sample <name>] [--total-count <n>]
- *         [--lineages <file>] [--lineage-dist <x>] [--lineage-model <file>] [--lineage-symmetry avg|min] [--lineage-threshold <file>] [--lineage-link single|complete|average] [--trees <file>] [--tree-support <B>] [--tree-seed <s>] [--trees-nj <file>] [--trees-newick <file>] [--mutations <file>]
+ *         [--lineages <file>] [--lineage-dist <x>] [--lineage-model <file>] [--lineage-symmetry avg|min] [--lineage-threshold <file>] [--lineage-link single|complete|average] [--trees <file>] [--tree-support <B>] [--tree-seed <s>] [--trees-nj <file>] [--trees-newick <file>] [--trees-mp <file>] [--trees-mp-newick <file>] [--mutations <file>]
  *         [--diversity <file>] [--diversity-depth <n>] [--diversity-boot <B>] [--diversity-seed <s>]
  *         [--selection <file>] [--v-regions <file>] [--targeting <file>] [--selection-combine shared|mean] [--selection-test <file>]
  *         [--targeting-model <file>] [--targeting-class s|rs] [--targeting-min-sub <n>] [--targeting-min-mut <n>] [--targeting-counts <file>]
@@ -109,6 +109,7 @@ typedef struct {
 	const char* lin_link; int lin_linkage;  /* --lineage-link single|complete|average -> 0, 1, 2 (vdjx_lineage_link; 0: the two calls above, as without the flag) */
 	const char* trees;                     /* --trees <file> (not in the reference): the tree inside every lineage of --lineages, on the device */
 	const char *trees_nj, *trees_newick;   /* --trees-nj <file>, --trees-newick <file> (not in the reference): neighbour-joining trees with inferred ancestors, and their Newick lines */
+	const char *trees_mp, *trees_mp_newick;   /* --trees-mp <file>, --trees-mp-newick <file> (not in the reference): those trees after a search for fewer mutations */
 	const char *tree_support, *tree_seed;  /* --tree-support <B>, --tree-seed <s>: the jackknife support of the trees' edges; read into ts_b (0: none) and ts_seed */
 	uint32_t ts_b; uint64_t ts_seed;
 	const char* mutations;                 /* --mutations <file> (not in the reference): CreateGermlines / observedMutations, on the device */
@@ -158,6 +159,8 @@ static void usage(void) {
 	                "\t--trees <file: with --lineages, the minimum spanning tree inside every lineage: parent, distance and depth of every contig>\n"
 	                "\t--trees-nj <file: with --lineages, the neighbour-joining tree inside every lineage with its inferred ancestors: a row per node>\n"
 	                "\t--trees-newick <file: with --trees-nj, one Newick line per lineage of two and more members>\n"
+	                "\t--trees-mp <file: with --lineages, the neighbour-joining tree of every lineage after a search over nearest-neighbour interchanges for fewer mutations: a row per node>\n"
+	                "\t--trees-mp-newick <file: with --trees-mp, one Newick line per lineage of two and more members, lengths in mutations>\n"
 	                "\t--tree-support <B: with --trees, a support column from B delete-half jackknife replicates, a whole number in 1 .. 1024>\n"
 	                "\t--tree-seed <seed of the replicates' columns, a whole number below 2^64 (default: 1)>\n"
 	                "\t--mutations <file: every contig beside its V(D)J germline, and the V segment's replacement / silent / stop mutation counts>\n"
@@ -339,6 +342,8 @@ static int parse(int argc, char** argv, cli* c) {
 		else if (!strcmp(a, "--trees")) c->trees = v;
 		else if (!strcmp(a, "--trees-nj")) c->trees_nj = v;
 		else if (!strcmp(a, "--trees-newick")) c->trees_newick = v;
+		else if (!strcmp(a, "--trees-mp")) c->trees_mp = v;
+		else if (!strcmp(a, "--trees-mp-newick")) c->trees_mp_newick = v;
 		else if (!strcmp(a, "--tree-support")) c->tree_support = v;
 		else if (!strcmp(a, "--tree-seed")) c->tree_seed = v;
 		else if (!strcmp(a, "--mutations")) c->mutations = v;
@@ -454,6 +459,8 @@ static int parse(int argc, char** argv, cli* c) {
 	if (c->trees && !c->lineages) { fprintf(stderr, "--trees writes the tree inside every lineage of the --lineages table: it needs --lineages <file>\n"); ok = 0; }
 	if (c->trees_nj && !c->lineages) { fprintf(stderr, "--trees-nj writes the neighbour-joining tree inside every lineage of the --lineages table: it needs --lineages <file>\n"); ok = 0; }
 	if (c->trees_newick && !c->trees_nj) { fprintf(stderr, "--trees-newick writes the trees of --trees-nj as Newick lines: it needs --trees-nj <file>\n"); ok = 0; }
+	if (c->trees_mp && !c->lineages) { fprintf(stderr, "--trees-mp writes the maximum-parsimony tree inside every lineage of the --lineages table: it needs --lineages <file>\n"); ok = 0; }
+	if (c->trees_mp_newick && !c->trees_mp) { fprintf(stderr, "--trees-mp-newick writes the trees of --trees-mp as Newick lines: it needs --trees-mp <file>\n"); ok = 0; }
 	c->ts_b = 0;
 	c->ts_seed = 1;
 	if (c->tree_support && !c->trees) { fprintf(stderr, "--tree-support adds the support column to the --trees table: it needs --trees <file>\n"); ok = 0; }
@@ -886,6 +893,8 @@ typedef struct {
 	const char* trees; vdjx_tree_info ti;
 	/* --trees-nj, --trees-newick: the neighbour-joining trees with inferred ancestors (tree_nj_run, after tree_run) */
 	const char *trees_nj, *trees_newick; vdjx_tree_nj_info tni;
+	/* --trees-mp, --trees-mp-newick: those trees after the search over nearest-neighbour interchanges (tree_mp_run, after tree_nj_run) */
+	const char *trees_mp, *trees_mp_newick; vdjx_tree_mp_info tmi;
 	/* --tree-support: the jackknife support of the trees' edges (tree_run) */
 	uint32_t ts_b; uint64_t ts_seed; vdjx_tree_support_info tsi;
 	/* --mutations: the germline rows of every contig (mut_run), kept for the --airr table's two alignment cells */
@@ -1597,11 +1606,15 @@ static void nj_label(FILE* fp, size_t s, void* ud) {
 	else fprintf(fp, "lin_%d_a%u", q->clone[s] + 1, q->number[s - q->n] + 1);
 }
 
-static int tree_nj_run(hook_ud* u, const char* const* ids, const char* contigs, size_t n, int len) {
-	FILE* fp = fopen(u->trees_nj, "w");
-	if (!fp) { fprintf(stderr, "cannot write %s\n", u->trees_nj); return -1; }
-	FILE* np = u->trees_newick ? fopen(u->trees_newick, "w") : NULL;
-	if (u->trees_newick && !np) { fprintf(stderr, "cannot write %s\n", u->trees_newick); fclose(fp); return -1; }
+/* mp: --trees-mp, --trees-mp-newick instead -- vdjx_tree_mp from vdjx_tree_nj's tree (the model: tests/tree_mp_model.py); the same rows,
+ * branch_length the node's mutations */
+static int tree_nodes_run(hook_ud* u, const char* const* ids, const char* contigs, size_t n, int len, int mp) {
+	const char *table = mp ? u->trees_mp : u->trees_nj, *lines = mp ? u->trees_mp_newick : u->trees_newick;
+	const char *flag = mp ? "--trees-mp" : "--trees-nj", *flag_lines = mp ? "--trees-mp-newick" : "--trees-newick";
+	FILE* fp = fopen(table, "w");
+	if (!fp) { fprintf(stderr, "cannot write %s\n", table); return -1; }
+	FILE* np = lines ? fopen(lines, "w") : NULL;
+	if (lines && !np) { fprintf(stderr, "cannot write %s\n", lines); fclose(fp); return -1; }
 	fputs("clone_id\tnode_id\tparent_id\tbranch_length\tmutations\tdepth\tchildren\tobserved\tsequence\n", fp);
 	int32_t* anchor = (int32_t*) calloc(n + 1, sizeof(int32_t));
 	uint32_t* prio = (uint32_t*) calloc(n + 1, sizeof(uint32_t));
@@ -1641,9 +1654,13 @@ static int tree_nj_run(hook_ud* u, const char* const* ids, const char* contigs, 
 	uint32_t* number = (uint32_t*) calloc(inner + 1, sizeof(uint32_t));
 	size_t* kid_off = (size_t*) calloc((size_t) nodes + 2, sizeof(size_t));
 	uint32_t* kid = (uint32_t*) calloc((size_t) nodes + 1, sizeof(uint32_t));
-	if (!rc) rc = vdjx_tree_nj(u->gx, contigs, n, len, u->lin_clone, anchor, prio, parent, length, mut, depth, cl, anc, &u->tni);
-	if (rc) fprintf(stderr, "--trees-nj: %s\n", vdjx_last_error());
-	if (!rc && newick_children(parent, (size_t) nodes, kid_off, kid)) { fprintf(stderr, "--trees-nj: the parents are no forest\n"); rc = -1; }
+	if (!rc && !mp) rc = vdjx_tree_nj(u->gx, contigs, n, len, u->lin_clone, anchor, prio, parent, length, mut, depth, cl, anc, &u->tni);
+	if (!rc && mp) {
+		rc = vdjx_tree_mp(u->gx, contigs, n, len, u->lin_clone, anchor, prio, NULL, NULL, parent, mut, depth, cl, anc, &u->tmi);
+		for (size_t s = 0; !rc && s < (size_t) nodes; s++) length[s] = cl[s] < 0 ? -1 : (parent[s] < 0 ? 0 : (int64_t) mut[s] * 65536);      /* an edge's length is its mutations */
+	}
+	if (rc) fprintf(stderr, "%s: %s\n", flag, vdjx_last_error());
+	if (!rc && newick_children(parent, (size_t) nodes, kid_off, kid)) { fprintf(stderr, "%s: the parents are no forest\n", flag); rc = -1; }
 	if (!rc) {
 		for (size_t a = 1; a < inner; a++) number[a] = cl[n + a] == cl[n + a - 1] ? number[a - 1] + 1 : 0;
 		const nj_names names = {ids, cl, number, n};
@@ -1665,17 +1682,19 @@ static int tree_nj_run(hook_ud* u, const char* const* ids, const char* contigs, 
 			}
 			if (np && m >= 2) {
 				fprintf(np, "lin_%zu\t", k + 1);
-				if (newick_write(np, root, length, (size_t) nodes, kid_off, kid, nj_label, (void*) &names)) { fprintf(stderr, "--trees-newick: lineage %zu is no tree\n", k + 1); rc = -1; break; }
+				if (newick_write(np, root, length, (size_t) nodes, kid_off, kid, nj_label, (void*) &names)) { fprintf(stderr, "%s: lineage %zu is no tree\n", flag_lines, k + 1); rc = -1; break; }
 				fputc('\n', np);
 			}
 			slot += extra;
 		}
 	}
 	free(anchor); free(prio); free(before); free(after); free(first); free(member); free(out); free(length); free(anc); free(number); free(kid_off); free(kid);
-	if (np && fclose(np)) { fprintf(stderr, "cannot write %s\n", u->trees_newick); fclose(fp); return -1; }
-	if (fclose(fp)) { fprintf(stderr, "cannot write %s\n", u->trees_nj); return -1; }
+	if (np && fclose(np)) { fprintf(stderr, "cannot write %s\n", lines); fclose(fp); return -1; }
+	if (fclose(fp)) { fprintf(stderr, "cannot write %s\n", table); return -1; }
 	return rc;
 }
+static int tree_nj_run(hook_ud* u, const char* const* ids, const char* contigs, size_t n, int len) { return tree_nodes_run(u, ids, contigs, n, len, 0); }
+static int tree_mp_run(hook_ud* u, const char* const* ids, const char* contigs, size_t n, int len) { return tree_nodes_run(u, ids, contigs, n, len, 1); }
 
 /* --mutations: the germline rows and the V mutation counts of every contig (the model: include/vdjx.h, vdjx_mutations; the limit:
  * mutation_limit of vdjer_amd/annot.py).  V mutations are counted below the junction's start + 3, through the conserved Cys codon: what
@@ -2093,6 +2112,7 @@ static int tables(hook_ud* u, const char* const* ids, const char* contigs, size_
 	if (!rc && u->lineages) rc = lineage_run(u, ids, contigs, n, len);
 	if (!rc && u->trees) rc = tree_run(u, ids, contigs, n, len);
 	if (!rc && u->trees_nj) rc = tree_nj_run(u, ids, contigs, n, len);
+	if (!rc && u->trees_mp) rc = tree_mp_run(u, ids, contigs, n, len);
 	if (!rc && u->diversity) rc = diversity_run(u, n);
 	if (!rc && u->mutations) rc = mut_run(u, ids, contigs, n, len);
 	if (!rc && u->consensus) rc = cons_run(u, ids, contigs, n, len);
@@ -2375,7 +2395,7 @@ int main(int argc, char** argv) {
 	ud.qb_b = c.qb_b; ud.qb_seed = c.qb_seed;
 	ud.gx = gx; ud.p = &c.hp; ud.mg = mg; ud.quant = c.quant; ud.airr = c.airr; ud.vdjf = c.vdj_fasta; ud.d_calls = c.d_calls;
 	ud.cfa = c.cfa; ud.isotypes = c.isotypes; ud.clones = c.clones; ud.total_count = c.total_count;
-	ud.lineages = c.lineages; ud.lin_num = c.lin_num; ud.lin_den = c.lin_den; ud.lin_table = c.lin_table; ud.lin_sym = c.lin_sym; ud.lin_thr = c.lin_threshold; ud.lin_linkage = c.lin_linkage; ud.trees = c.trees; ud.trees_nj = c.trees_nj; ud.trees_newick = c.trees_newick;
+	ud.lineages = c.lineages; ud.lin_num = c.lin_num; ud.lin_den = c.lin_den; ud.lin_table = c.lin_table; ud.lin_sym = c.lin_sym; ud.lin_thr = c.lin_threshold; ud.lin_linkage = c.lin_linkage; ud.trees = c.trees; ud.trees_nj = c.trees_nj; ud.trees_newick = c.trees_newick; ud.trees_mp = c.trees_mp; ud.trees_mp_newick = c.trees_mp_newick;
 	ud.ts_b = c.ts_b; ud.ts_seed = c.ts_seed; ud.mutations = c.mutations;
 	ud.diversity = c.diversity; ud.dv_depth = c.div_depth; ud.dv_boot = c.div_boot; ud.dv_seed = c.div_seed;
 	ud.selection = c.selection; ud.regs = c.regs; ud.nregs = c.nregs; ud.weight = c.weight; ud.have_regs = c.v_regions != NULL;
@@ -2466,6 +2486,10 @@ int main(int argc, char** argv) {
 		fprintf(stderr, "trees nj: %u contigs in %u lineages (largest %u), %u inferred nodes, %llu edges, length %.4f, parsimony %llu, %u negative branches, %u batches\n",
 		        ud.tni.members, ud.tni.clones, ud.tni.largest_clone, ud.tni.internal, (unsigned long long) ud.tni.edges, (double) ud.tni.length / 65536.0,
 		        (unsigned long long) ud.tni.parsimony, ud.tni.negative, ud.tni.batches);
+	if (c.trees_mp)
+		fprintf(stderr, "trees mp: %u contigs in %u lineages (largest %u), %u searched, %u improved, %llu moves in %u rounds, %llu candidates, parsimony %llu -> %llu, %u batches\n",
+		        ud.tmi.members, ud.tmi.clones, ud.tmi.largest_clone, ud.tmi.searched, ud.tmi.moved, (unsigned long long) ud.tmi.moves, ud.tmi.rounds,
+		        (unsigned long long) ud.tmi.candidates, (unsigned long long) ud.tmi.parsimony_start, (unsigned long long) ud.tmi.parsimony, ud.tmi.batches);
 	if (c.isotypes)
 		fprintf(stderr, "isotypes: %zu contigs, %zu called against %zu constant records of %s; table in %s\n", ud.i_contigs, ud.i_called,
 		        ud.cst ? ud.cst->n : (size_t) 0, c.cfa, c.isotypes);

@@ -327,6 +327,10 @@ void vdjx_ri_open_gate(vdjx_ctx* c);      // a begun build that waits for the k-
 bool vdjx_host_block_holds(vdjx_ctx* c, const void* p, size_t bytes);   // [p, p + bytes) inside a block of vdjx_host_alloc (vdjx_core.hip)
 // vdjx_map_emit's pairs left on the device (vdjx_score.hip; *d_pairs valid on the context's stream until the next scorer call)
 int vdjx_map_emit_device(vdjx_ctx* c, const char* contigs, size_t n, int len, uint64_t* offsets, const vdjx_pair** d_pairs);
+// vdjx_tree_nj's topology alone (vdjx_nj.hip): out_parent[nodes] as the public function fills it, by the same steps up to the rooting --
+// no Fitch passes, no other output, no statistic written.  The arguments are vdjx_tree_nj's and are not checked again
+int vdjx_nj_parents(vdjx_ctx* c, const char* contigs, size_t n, int len, const int32_t* clone, const int32_t* anchor, const uint32_t* prio,
+                    int32_t* out_parent);
 
 // scoped workspace allocations out of the context's arena
 struct vdjx_work {

@@ -3,6 +3,7 @@
 //   vdjx_tree_nj   per lineage: the full matrix of window distances in 16.16 fixed point, neighbour joining under the strict order of the
 //                  keys (Q, i, j), the tree rooted at the member of smallest (prio, index), the inferred nodes' sequences and every
 //                  edge's mutations by Fitch parsimony (the model: include/vdjx.h; in Python: tests/tree_nj_model.py)
+//   vdjx_nj_parents   (internal, vdjx_common.h) the same steps as far as the rooted parents, for vdjx_tree_mp's start
 //
 // The host sorts the keys, computes the windows and lays the members out as rows (vdjx_treelay.h, as vdjx_tree does), refuses a lineage of
 // more than 4,096 members and cuts the lineages of two and more into batches of whole lineages of at most VDJX_NJ_CELLS matrix cells
@@ -21,13 +22,13 @@
 //                  subtraction and addition (integers: exact); the new node's R is an integer atomicAdd in LDS (a sum: any order).  The
 //                  loop runs r = m down to 4, a fixed count: no spin-wait, nothing waits for another workgroup.  The edges (a, b, length)
 //                  go out in creation order.
-//   k_nj_fitch     one wave per (lineage, 64 window columns), a lane per column: the column is the fastest index of everything it
-//                  touches.  The up-pass walks the inferred nodes in post-order and writes one set per (node, column) -- a byte -- into
-//                  workspace; the down-pass walks them back, overwrites the set with the state, writes the ancestor's character and
-//                  counts the lanes whose state differs from the parent's: one integer atomicAdd per (node, wave).  The leaves follow.
+//   k_nj_fitch     (vdjx_fitch.h, shared with vdjx_mp.hip) one wave per (lineage, 64 window columns), a lane per column: Fitch's up-pass
+//                  over the inferred nodes in post-order, the down-pass back, then the leaves; a node's mutations by one integer
+//                  atomicAdd per (node, wave).
 // Between k_nj_join and k_nj_fitch only the edges come back: rooting them, the depths and the post-order are O(nodes) on the host
 // (vdjx_nj_host.h).  No floating point.  Scratch comes from the context's workspace.
 #include "vdjx_common.h"
+#include "vdjx_fitch.h"
 #include "vdjx_hamming.h"
 #include "vdjx_link.h"
 #include "vdjx_nj_host.h"
@@ -265,75 +266,17 @@ __global__ __launch_bounds__(T) void k_nj_join(const NjLin* __restrict__ lins, c
 	}
 }
 
-// Fitch: a lineage's rooted tree as the host laid it out.  Nodes are local ids (leaves 0 .. m - 1 = rows first .. first + m - 1, inferred
-// nodes from m on); inferred node v has index node0 + v - m in kid[][2], par[], and in the call's inferred slots (mutations, ancestors)
-struct NjFit { u64 fs_off; u32 first, m, w, node0, root, root_kid, ord_off, pad; };
-static_assert(sizeof(NjFit) == 40, "uploaded as it is");
-struct NjFitItem { u32 lin, col0; };
-
-__device__ inline u32 nj_leaf_set(char ch) { return ch == 'A' ? 1u : ch == 'C' ? 2u : ch == 'G' ? 4u : ch == 'T' ? 8u : 15u; }
-__device__ inline u32 nj_lowest(u32 s) { return (u32) __ffs((int) s) - 1u; }
-
-// one wave per item, a lane per window column.  fs: a byte per (inferred node, column), first the set, then the state.  order[]: the
-// lineage's inferred nodes, children before parents.  leaf_par[row]: a leaf's parent (local id).  mut_row / mut_inf: zeroed by the host.
-__global__ __launch_bounds__(64) void k_nj_fitch(const NjFitItem* __restrict__ items, const NjFit* __restrict__ fits, const char* __restrict__ contigs,
-                                                 const TreeRow* __restrict__ ri, const u32* __restrict__ kid, const u32* __restrict__ par,
-                                                 const u32* __restrict__ order, const u32* __restrict__ leaf_par, uint8_t* __restrict__ fs_all,
-                                                 u32* mut_row, u32* mut_inf, char* __restrict__ anc, u32 len) {
-	const NjFitItem it = items[blockIdx.x];
-	const NjFit q = fits[it.lin];
-	const u32 col = it.col0 + threadIdx.x, m = q.m, inner = m - 2u;      // (m >= 2: the host makes no item for less)
-	const bool live = col < q.w;
-	const u32 cc = live ? col : 0u;
-	uint8_t* fs = fs_all + q.fs_off + cc;                  // + (v - m) * w
-	const u32* ord = order + q.ord_off;
-	auto leaf = [&](u32 p) { return nj_leaf_set(contigs[ri[q.first + p].at + cc]); };
-	auto set_of = [&](u32 v) { return v < m ? leaf(v) : (u32) fs[(size_t) (v - m) * q.w]; };
-	for (u32 t = 0; t < (m > 2u ? inner : 0u); t++) {
-		const u32 v = ord[t], a = set_of(kid[2u * (q.node0 + v - m)]), b = set_of(kid[2u * (q.node0 + v - m) + 1u]);
-		if (live) fs[(size_t) (v - m) * q.w] = (uint8_t) ((a & b) ? (a & b) : (a | b));
-	}
-	const u32 rs = leaf(q.root), cs = set_of(q.root_kid);
-	const u32 rstate = nj_lowest((rs & cs) ? (rs & cs) : rs);
-	for (u32 t = m > 2u ? inner : 0u; t-- > 0u;) {         // parents before children
-		const u32 v = ord[t], p = par[q.node0 + v - m];
-		const u32 ps = p == q.root ? rstate : (u32) fs[(size_t) (p - m) * q.w], s = fs[(size_t) (v - m) * q.w];
-		const u32 st = (s >> ps & 1u) ? ps : nj_lowest(s);
-		if (live) {
-			fs[(size_t) (v - m) * q.w] = (uint8_t) st;
-			if (anc) anc[(size_t) (q.node0 + v - m) * len + col] = "ACGT"[st];
-		}
-		const u64 diff = __ballot(live && st != ps);
-		if (threadIdx.x == 0 && diff) atomicAdd(mut_inf + q.node0 + v - m, (u32) __popcll(diff));
-	}
-	for (u32 p = 0; p < m; p++) {
-		if (p == q.root) continue;
-		const u32 up = leaf_par[q.first + p];
-		const u32 ps = up == q.root ? rstate : (u32) fs[(size_t) (up - m) * q.w], s = leaf(p);
-		const u32 st = (s >> ps & 1u) ? ps : nj_lowest(s);
-		const u64 diff = __ballot(live && st != ps);
-		if (threadIdx.x == 0 && diff) atomicAdd(mut_row + q.first + p, (u32) __popcll(diff));
-	}
-}
-
 extern "C" int vdjx_tree_nj_nodes(const int32_t* clone, size_t n, uint64_t* nodes) {
 	if (!nodes || (n && !clone)) { vdjx_set_error("vdjx_tree_nj_nodes: NULL argument"); return VDJX_EINVAL; }
 	if (!nj_count_nodes(clone, n, nodes)) { vdjx_set_error("vdjx_tree_nj_nodes: a clone below -1 (a key >= 0, or -1 for no part)"); return VDJX_EINVAL; }
 	return VDJX_OK;
 }
 
-extern "C" int vdjx_tree_nj(vdjx_ctx* c, const char* contigs, size_t n, int len, const int32_t* clone, const int32_t* anchor, const uint32_t* prio,
-                            int32_t* out_parent, int64_t* out_length, int32_t* out_mutations, int32_t* out_depth, int32_t* out_clone, char* out_anc,
-                            vdjx_tree_nj_info* info) {
-	static const char* who = "vdjx_tree_nj";
-	if (info) memset(info, 0, sizeof *info);
-	if (!c) { vdjx_set_error("%s: NULL argument", who); return VDJX_EINVAL; }
-	if (n == 0) return VDJX_OK;
-	if (!contigs || !clone || !anchor || !out_parent || !out_length || !out_mutations || !out_depth || !out_clone) {
-		vdjx_set_error("%s: NULL argument", who);
-		return VDJX_EINVAL;
-	}
-	if (int rc = tree_check_contigs(who, contigs, n, len)) return rc;
+// vdjx_tree_nj behind its argument checks.  whole: the public call.  Not whole (vdjx_nj_parents): out_parent alone is written, the batch
+// ends after the rooting, and no statistic is left
+static int nj_run(vdjx_ctx* c, const char* who, const char* contigs, size_t n, int len, const int32_t* clone, const int32_t* anchor, const uint32_t* prio,
+                  int32_t* out_parent, int64_t* out_length, int32_t* out_mutations, int32_t* out_depth, int32_t* out_clone, char* out_anc,
+                  vdjx_tree_nj_info* info, const bool whole) {
 	const auto t0 = std::chrono::steady_clock::now();
 	std::vector<u64> keys;
 	if (int rc = tree_keys(who, n, len, clone, anchor, keys)) return rc;
@@ -359,13 +302,15 @@ extern "C" int vdjx_tree_nj(vdjx_ctx* c, const char* contigs, size_t n, int len,
 		if (q.m >= 3) { inf.internal += q.m - 2; inf.joins += q.m - 3; }
 	}
 	const u64 nodes = (u64) n + inf.internal;
-	for (u64 s = 0; s < nodes; s++) {
-		out_parent[s] = out_mutations[s] = out_depth[s] = out_clone[s] = -1;
-		out_length[s] = -1;
-	}
+	for (u64 s = 0; s < nodes; s++) out_parent[s] = -1;
+	if (whole)
+		for (u64 s = 0; s < nodes; s++) {
+			out_mutations[s] = out_depth[s] = out_clone[s] = -1;
+			out_length[s] = -1;
+		}
 	if (out_anc) memset(out_anc, 0, (size_t) inf.internal * (size_t) len);
 	for (const TreeClone& q : L.clones)
-		if (q.m == 1) {                                       // a lone root
+		if (whole && q.m == 1) {                              // a lone root
 			const u32 i = L.row_item[q.first];
 			out_depth[i] = 0;
 			out_length[i] = 0;
@@ -395,8 +340,10 @@ extern "C" int vdjx_tree_nj(vdjx_ctx* c, const char* contigs, size_t n, int len,
 		}
 		HIP_TRY(hipMemcpyAsync(d_contigs, contigs, n * (size_t) len, hipMemcpyHostToDevice, st));
 		HIP_TRY(hipMemcpyAsync(d_ri, L.ri.data(), ((size_t) rows + 1) * sizeof(TreeRow), hipMemcpyHostToDevice, st));
-		HIP_TRY(hipMemsetAsync(d_mut_row, 0, (size_t) rows * sizeof(u32), st));
-		HIP_TRY(hipMemsetAsync(d_mut_inf, 0, (size_t) (inf.internal ? inf.internal : 1) * sizeof(u32), st));
+		if (whole) {
+			HIP_TRY(hipMemsetAsync(d_mut_row, 0, (size_t) rows * sizeof(u32), st));
+			HIP_TRY(hipMemsetAsync(d_mut_inf, 0, (size_t) (inf.internal ? inf.internal : 1) * sizeof(u32), st));
+		}
 		{
 			vdjx_prof_scope ps(c, "k_nj_pack");
 			hipLaunchKernelGGL(k_nj_pack, dim3((u32) ((L.total + 255) / 256)), dim3(256), 0, st, (const char*) d_contigs, (const TreeRow*) d_ri, rows, (u32) L.total,
@@ -476,6 +423,10 @@ extern "C" int vdjx_tree_nj(vdjx_ctx* c, const char* contigs, size_t n, int len,
 				}
 				const u64 a0 = inf0[big[k]];
 				auto slot = [&](u32 v) { return v < m ? (u64) L.row_item[q.first + v] : (u64) n + a0 + (v - m); };
+				if (!whole) {
+					for (u32 v = 0; v < (u32) t.parent.size(); v++) out_parent[slot(v)] = t.parent[v] < 0 ? -1 : (int32_t) slot((u32) t.parent[v]);
+					continue;
+				}
 				for (u32 v = 0; v < (u32) t.parent.size(); v++) {
 					const u64 s = slot(v);
 					out_clone[s] = clone[L.row_item[q.first]];
@@ -494,6 +445,11 @@ extern "C" int vdjx_tree_nj(vdjx_ctx* c, const char* contigs, size_t n, int len,
 				h_order.insert(h_order.end(), t.order.begin(), t.order.end());
 				for (u32 c0 = 0; c0 < q.w; c0 += 64u) fit_items.push_back({(u32) (k - k0), c0});
 				fs_bytes += (u64) (m - 2u) * q.w;
+			}
+			if (!whole) {                                        // (the stream is idle: the edges' copies were waited for)
+				vdjx_prof_collect(c, false);
+				wk.release_to(mk);
+				continue;
 			}
 			NjFit* d_fits;
 			NjFitItem* d_fit_items;
@@ -524,6 +480,7 @@ extern "C" int vdjx_tree_nj(vdjx_ctx* c, const char* contigs, size_t n, int len,
 			vdjx_prof_collect(c, false);
 			wk.release_to(mk);
 		}
+		if (!whole) return VDJX_OK;
 		std::vector<u32> mut_row(rows), mut_inf((size_t) inf.internal);
 		HIP_TRY(hipMemcpyAsync(mut_row.data(), d_mut_row, (size_t) rows * sizeof(u32), hipMemcpyDeviceToHost, st));
 		if (inf.internal) HIP_TRY(hipMemcpyAsync(mut_inf.data(), d_mut_inf, (size_t) inf.internal * sizeof(u32), hipMemcpyDeviceToHost, st));
@@ -540,9 +497,30 @@ extern "C" int vdjx_tree_nj(vdjx_ctx* c, const char* contigs, size_t n, int len,
 			inf.parsimony += mut_inf[a];
 		}
 	}
+	if (!whole) return VDJX_OK;
 	if (info) *info = inf;
 	c->stats["tree_nj_cells"] = inf.cells;
 	c->stats["tree_nj_joins"] = inf.joins;
 	c->stats["tree_nj_us"] = (u64) std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
 	return VDJX_OK;
+}
+
+extern "C" int vdjx_tree_nj(vdjx_ctx* c, const char* contigs, size_t n, int len, const int32_t* clone, const int32_t* anchor, const uint32_t* prio,
+                            int32_t* out_parent, int64_t* out_length, int32_t* out_mutations, int32_t* out_depth, int32_t* out_clone, char* out_anc,
+                            vdjx_tree_nj_info* info) {
+	static const char* who = "vdjx_tree_nj";
+	if (info) memset(info, 0, sizeof *info);
+	if (!c) { vdjx_set_error("%s: NULL argument", who); return VDJX_EINVAL; }
+	if (n == 0) return VDJX_OK;
+	if (!contigs || !clone || !anchor || !out_parent || !out_length || !out_mutations || !out_depth || !out_clone) {
+		vdjx_set_error("%s: NULL argument", who);
+		return VDJX_EINVAL;
+	}
+	if (int rc = tree_check_contigs(who, contigs, n, len)) return rc;
+	return nj_run(c, who, contigs, n, len, clone, anchor, prio, out_parent, out_length, out_mutations, out_depth, out_clone, out_anc, info, true);
+}
+
+int vdjx_nj_parents(vdjx_ctx* c, const char* contigs, size_t n, int len, const int32_t* clone, const int32_t* anchor, const uint32_t* prio,
+                    int32_t* out_parent) {
+	return nj_run(c, "vdjx_tree_nj", contigs, n, len, clone, anchor, prio, out_parent, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false);
 }

@@ -2,8 +2,12 @@
 on the cases of tests/tree_mp_cases.py (tests/test_tree_mp_cpu.py checks that each reaches the edge it is named for: lineages of 1 .. 5
 members, swaps whose walk is the root step alone and swaps deep in the tree, windows of 1, 64, 65 and 513 columns, a caterpillar of 130
 members, the exported LDS bound and the bound + 1 from the neighbour-joining start, wildcards, all-identical members, thousands of small
-lineages that finish in different rounds), under three values of VDJX_NJ_CELLS, from tree_nj's own parents as the start, with max_rounds
-= 1, without ancestors, two calls, and the refusals.  Every model result is computed once."""
+lineages that finish in different rounds; stride_all and stride_mixed: so many candidates that k_mp_score's grid is one and two waves
+high and a wave walks three column tiles, or tiles 0, 2, 4 and 1, 3, next to lineages of one tile; `widths`: 1 .. 17 tiles in one batch
+under a grid of 7; pick_cat140 and pick_random300: more candidates than k_mp_pick has threads, and moves applied from both sides of
+its first stride), under three values of VDJX_NJ_CELLS with the start given and with vdjx_nj_parents' start (its batch loop), the stride
+cases' trees recounted by a plain Fitch pass, from tree_nj's own parents as the start, with max_rounds = 1, without ancestors, two calls,
+and the refusals.  Every model result is computed once."""
 import functools
 
 import numpy as np
@@ -12,6 +16,7 @@ import pytest
 from tests import tree_mp_cases as K
 from tests import tree_mp_model as M
 from tests import tree_nj_cases as NK
+from tests.tree_model import members_of, windows
 
 pytestmark = pytest.mark.gpu
 ARRAYS = ("parent", "mutations", "depth", "clone")
@@ -71,6 +76,49 @@ def test_any_knob_gives_the_same_bytes(ctx, knob, batches, monkeypatch):
         assert np.array_equal(got[f], _want("mixed")[f])
     assert got["anc"] == _want("mixed")["anc"]
     assert {k: v for k, v in got["info"].items() if k != "batches"} == {k: v for k, v in _want("mixed")["info"].items() if k != "batches"}
+
+
+@pytest.mark.parametrize("knob,batches", [(1, 7), (2500, 3), (None, 1)])
+def test_any_knob_gives_the_same_bytes_from_the_neighbour_joining_start(ctx, knob, batches, monkeypatch):
+    """mixed_random has no start given: vdjx_nj_parents cuts the same batches as the search, so under a small knob it goes round its batch
+    loop several times (with `mixed`, whose start is given, it never runs)"""
+    assert _case("mixed_random")["start"] is None
+    monkeypatch.delenv("VDJX_NJ_CELLS", raising=False)
+    unset = _call(ctx, "mixed_random")
+    if knob is not None:
+        monkeypatch.setenv("VDJX_NJ_CELLS", str(knob))
+    got = _call(ctx, "mixed_random")
+    assert got["info"]["batches"] == batches == _want("mixed_random", knob or 1 << 26)["info"]["batches"] and unset["info"]["batches"] == 1
+    _same(got, _want("mixed_random", knob or 1 << 26), knob)
+    for f in ARRAYS:                                                                  # nothing but info["batches"] moves with the knob
+        assert got[f].tobytes() == unset[f].tobytes() and np.array_equal(got[f], _want("mixed_random")[f])
+    assert got["anc"] == unset["anc"] == _want("mixed_random")["anc"] and got["info"]["moves"] > 0
+    rest = lambda info: {k: v for k, v in info.items() if k != "batches"}
+    assert rest(got["info"]) == rest(unset["info"]) == rest(_want("mixed_random")["info"])
+
+
+@pytest.mark.parametrize("name", ["stride_all", "stride_mixed"])
+def test_the_stride_cases_trees_recounted_by_plain_fitch(ctx, name, monkeypatch):
+    """without the search model: the returned parents of every lineage are a tree, and Fitch's upward pass over it (M.count, all columns
+    in one go: no tiles) gives the lineage's mutations, the call's parsimony and no more than the start's.  This holds for any tree, so a
+    scorer that mis-summed a tile would pass it with the wrong moves: only test_tree_mp_is_the_model tells, which is why both stay"""
+    monkeypatch.delenv("VDJX_NJ_CELLS", raising=False)
+    case, got = _case(name), _call(ctx, name)
+    groups = members_of(case["clone"])
+    total, slot0 = 0, len(case["contigs"])
+    for key in sorted(groups):
+        members, m = groups[key], len(groups[key])
+        slots = members + list(range(slot0, slot0 + max(0, m - 2)))
+        local = {s: v for v, s in enumerate(slots)}
+        root = K.root_of(case, members)
+        par = [-1 if v == root else local.get(int(got["parent"][s]), -2) for v, s in enumerate(slots)]
+        kids = M.tree_of_parents(m, root, par)
+        p = M.count(M.leaf_sets(windows(case["contigs"], members, case["anchor"])[0]), m, root, kids)
+        assert p == sum(int(got["mutations"][s]) for v, s in enumerate(slots) if v != root), (name, key)
+        total += p
+        slot0 += max(0, m - 2)
+    assert total == int(got["mutations"][got["parent"] >= 0].sum()) == got["info"]["parsimony"] <= got["info"]["parsimony_start"]
+    assert got["info"]["parsimony"] < got["info"]["parsimony_start"] and got["info"]["moves"] > 0
 
 
 def test_tree_njs_own_parents_as_the_start_give_the_same_bytes(ctx, monkeypatch):

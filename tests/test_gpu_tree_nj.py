@@ -1,8 +1,12 @@
 """vdjx_tree_nj on the GPU: every output array, the ancestors and every info field against the plain model of tests/tree_nj_model.py,
 exactly -- on the cases of tests/tree_nj_cases.py (tests/test_tree_nj_cpu.py checks that each reaches the edge it is named for: lineages of
 1 .. 5 members, the exported LDS bound and the bound + 1, about 300 members on the global path, windows of 1 word, of 512 bases and of 513,
-shifted anchors, N and lower case, all-identical members, thousands of small lineages interleaved), under three values of VDJX_NJ_CELLS,
-without ancestors, the refusals, a lineage of 4,097 and two calls.  Every model result is computed once."""
+shifted anchors, N and lower case, all-identical members, thousands of small lineages interleaved; `widths`: lineages of 70 members at
+every packed word count from 1 to 17 and at 31, 32 and 33, so every register width of k_nj_matrix, its second LDS tile and the chunked
+path with a full and a partial last chunk; rand_*: distances that are not additive, whose joins halve odd sums and divide with a
+remainder, on the LDS bound, one past it, with a last row block of one row, and at 300 members), under three values of VDJX_NJ_CELLS,
+`widths` a lineage and two lineages per batch, without ancestors, the refusals, a lineage of 4,097 and two calls.  No case has a
+negative branch: no sequence input that gives one is known.  Every model result is computed once."""
 import functools
 
 import numpy as np
@@ -67,6 +71,17 @@ def test_any_knob_gives_the_same_bytes(ctx, knob, batches, monkeypatch):
     for f in ARRAYS:                                                                  # nothing but info["batches"] moves with the knob
         assert np.array_equal(got[f], _want("mixed")[f])
     assert got["anc"] == _want("mixed")["anc"]
+
+
+@pytest.mark.parametrize("knob,batches", [(K.WIDTH_MEMBERS ** 2, 20), (2 * K.WIDTH_MEMBERS ** 2, 10)])
+def test_widths_batch_by_batch_give_the_same_bytes(ctx, knob, batches, monkeypatch):
+    """a lineage, or two, per batch: every batch's rows start at another word of the packed rows and have another word count, and the
+    distances round (in `mixed`, the other case cut into batches, they are whole)"""
+    monkeypatch.setenv("VDJX_NJ_CELLS", str(knob))
+    got = _call(ctx, "widths")
+    assert got["info"]["batches"] == batches == K.batches_under(K.sizes_of(_case("widths")), knob)
+    want = _want("widths")                                                            # (nothing but info["batches"] moves with the knob)
+    _same(got, dict(want, info=dict(want["info"], batches=batches)), knob)
 
 
 def test_without_ancestors_the_counts_are_still_made(ctx, monkeypatch):

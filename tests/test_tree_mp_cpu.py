@@ -1,6 +1,9 @@
 """The model of vdjx_tree_mp (tests/tree_mp_model.py) on the CPU: its two versions against each other, its properties against independent
 recounts and a brute force over every topology, the tie rule on handmade member orders, the floors of the search on the seeded cases, the
-texts of the command line by hand, and that every case of tests/test_gpu_tree_mp.py reaches the edge it is named for.  No GPU."""
+texts of the command line by hand, and that every case of tests/test_gpu_tree_mp.py reaches the edge it is named for -- for the stride
+and pick cases by MP_FILL_WAVES and MP_PICK_T as vdjx_mp.hip defines them: the candidates, the column tiles and the height of
+k_mp_score's grid, the candidate indices of the applied moves -- and that a scorer which never left its first column tile would be
+caught by the stride cases and by no case from before them.  No GPU."""
 import ctypes
 import functools
 import os
@@ -12,7 +15,7 @@ from tests import tree_mp_cases as C
 from tests import tree_mp_model as M
 from tests import tree_nj_cases as K
 from tests import tree_nj_model as N
-from tests.tree_model import members_of, windows
+from tests.tree_model import distance_matrix, members_of, windows
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -49,12 +52,28 @@ def _lineages(case, res):
     return out
 
 
-PROPERTY_CASES = ["m4_cat", "m5_cat", "w65", "cat20", "random_wild", "random_12", "identical_cat", "mixed_random", "one_round"]
+PROPERTY_CASES = ["m4_cat", "m5_cat", "w65", "cat20", "random_wild", "random_12", "identical_cat", "mixed_random", "one_round", "stride_all",
+                  "stride_mixed"]
+STRIDE_CASES = ["stride_all", "stride_mixed", "pick_cat140", "pick_random300", "widths"]      # a wave over several tiles, a thread over several candidates
+OLD_CASES = ["m1", "m2", "m3", "m4_nj", "m4_cat", "m5_nj", "m5_cat", "w1", "w64", "w65", "w513", "cat20", "cat130", "lds_bound", "lds_bound_plus1",
+             "random_wild", "random_12", "identical", "identical_cat", "many_small", "mixed", "mixed_random", "one_round"]     # neither happens in these
+SAMPLE = 300                                               # lineages of a case of thousands that the per-candidate checks look at
+
+
+def _sample_keys(case, seed=1):
+    """every lineage key of a case of up to SAMPLE lineages; of a larger one SAMPLE keys chosen by seed"""
+    keys = sorted(members_of(case["clone"]))
+    if len(keys) <= SAMPLE:
+        return set(keys)
+    return set(keys[i] for i in np.random.default_rng(seed).permutation(len(keys))[:SAMPLE])
 
 
 @pytest.mark.parametrize("name", PROPERTY_CASES)
 def test_no_neighbour_is_better_and_p_never_rises(name):
+    """the recount, the falling trace and the totals on every lineage of every case; the recount of every neighbour of the final tree on
+    every lineage too, except in the stride cases (thousands of lineages), where it is made on SAMPLE lineages chosen by seed"""
     case, res = _case(name), _model(name)
+    sample = _sample_keys(case)
     total = 0
     for key, (m, root, par, kids, leaves) in _lineages(case, res).items():
         p = M.count(leaves, m, root, kids)                                            # an independent full recount of the final tree
@@ -63,6 +82,7 @@ def test_no_neighbour_is_better_and_p_never_rises(name):
         assert all(a[0] > b[0] for a, b in zip(trace, trace[1:])), (name, key)        # every move lowers P
         if m > 3 and not case["max_rounds"]:
             assert trace[-1] == (p, None, None)
+        if m > 3 and not case["max_rounds"] and key in sample:
             for v, k in M.candidates(m, par):
                 p2, k2 = list(par), [list(x) for x in kids]
                 M.swap(p2, k2, v, k)
@@ -101,7 +121,9 @@ def test_p_against_the_brute_force_minimum():
 
 def test_the_two_versions_agree():
     for name in sorted(C.gpu_cases()):
-        if name in ("cat130", "mixed", "many_small"):                                  # a full count per candidate of 65 and 130 leaves: minutes
+        if name in ("cat130", "mixed", "many_small", "pick_cat140", "pick_random300", "widths"):       # a full count per candidate of 65 .. 300 leaves: minutes
+            continue
+        if name in ("stride_all", "stride_mixed"):                                     # thousands of lineages: a sample of them below, not dropped
             continue
         a, b = _run(_case(name), plain=True), _run(_case(name), plain=False)
         assert a["trace"] == b["trace"] and a["info"] == b["info"] and a["anc"] == b["anc"], name
@@ -111,6 +133,14 @@ def test_the_two_versions_agree():
     a, b = _run(small, plain=True), _run(small, plain=False)
     assert a["trace"] == b["trace"] and a["info"] == b["info"] and np.array_equal(a["parent"], b["parent"])
     assert a["info"]["moved"] == 22 and a["info"]["searched"] == 199
+    # the stride cases on SAMPLE of their lineages, chosen by seed: cut out of the case as they are, so the traces are the whole case's
+    for name, start in [("stride_all", C.plain), ("stride_mixed", C.with_caterpillars)]:
+        part = dict({"max_rounds": 0}, **start(C.sample_of(_case(name), SAMPLE, 2)))
+        a, b = _run(part, plain=True), _run(part, plain=False)
+        assert a["trace"] == b["trace"] and a["info"] == b["info"] and a["anc"] == b["anc"], name
+        for f in ("parent", "mutations", "depth", "clone"):
+            assert np.array_equal(a[f], b[f]), (name, f)
+        assert len(a["trace"]) == SAMPLE and all(_model(name)["trace"][key] == t for key, t in a["trace"].items()), name
 
 
 def test_infinite_sites_from_the_nj_start_make_no_move():
@@ -249,3 +279,81 @@ def test_gpu_cases_reach_their_edges():
     assert sizes["mixed"] == K.MIXED_SIZES == sizes["mixed_random"] == sizes["one_round"]
     assert [_run(_case("mixed"), cells_knob=knob, max_rounds=1)["info"]["batches"] for knob in (1, 2500, 1 << 26)] == [7, 3, 1]
     assert _case("one_round")["max_rounds"] == 1 and all(_case(k)["max_rounds"] == 0 for k in names if k != "one_round")
+    # k_mp_score's grid, by the host's formulas and the constants of vdjx_mp.hip.  Every case is one batch (the knob unset)
+    fill, pick = C.kernel_constant("MP_FILL_WAVES"), C.kernel_constant("MP_PICK_T")
+    assert all(_model(k)["info"]["batches"] <= 1 for k in names) and sorted(OLD_CASES + STRIDE_CASES) == names
+    grid = {k: C.scorer_grid(_case(k)) for k in names}
+    for k in OLD_CASES:                                                               # before the stride cases: a wave never took a second tile
+        assert grid[k][0] == 0 or grid[k][2] == max(grid[k][1]), k
+    assert max(grid[k][0] for k in OLD_CASES) == grid["many_small"][0] < fill and max(grid["many_small"][1]) == 2 and max(grid["w513"][1]) == 9
+    n_cand, tiles, grid_y = grid["stride_all"]
+    assert n_cand >= fill and grid_y == 1 and set(tiles) == {3} and len(tiles) == len(sizes["stride_all"]) == 2100 and set(sizes["stride_all"]) == {7}
+    assert _case("stride_all")["start"] is None and (_case("stride_all")["clone"] == -1).sum() == 50
+    n_cand, tiles, grid_y = grid["stride_mixed"]
+    assert fill / 2 <= n_cand < fill and grid_y == 2 and set(tiles) == {1, 2, 3, 4, 5} and set(sizes["stride_mixed"]) == {6, 7, 8}
+    assert _case("stride_mixed")["start"] is not None and len(tiles) == 1200 and min(tiles.count(t) for t in (1, 2, 3, 4, 5)) >= 100
+    for k in ("stride_all", "stride_mixed"):
+        info = _model(k)["info"]
+        assert info["rounds"] >= 5 and info["moves"] >= 1500 and info["moved"] < info["searched"]      # lineages go out round by round
+        first = {int(c): i for i, c in reversed(list(enumerate(_case(k)["clone"]))) if c >= 0}
+        last = {int(c): i for i, c in enumerate(_case(k)["clone"]) if c >= 0}
+        assert sum(last[c] - first[c] + 1 > 8 for c in first) > 0.95 * len(first)                       # interleaved
+    n_cand, tiles, grid_y = grid["widths"]                                            # 20 lineages of 70: 1 .. 17 tiles under waves of every 7th tile
+    assert sorted(K.lineage_words(_case("widths"))) == K.WIDTH_WORDS and sizes["widths"] == [K.WIDTH_MEMBERS] * 20 and _case("widths")["start"] is None
+    assert n_cand == 20 * 2 * (K.WIDTH_MEMBERS - 3) and (min(tiles), max(tiles)) == (1, 17) and 1 < grid_y == -(-fill // n_cand) < max(tiles)
+    assert {t for t in tiles if t < grid_y} and {t for t in tiles if grid_y < t <= 2 * grid_y} and {t for t in tiles if t > 2 * grid_y}
+    assert _model("widths")["info"]["moved"] >= 15 and _model("widths")["info"]["moves"] >= 100           # and moves at nearly every width
+    # k_mp_pick: more candidates than threads, and applied moves on both sides of the first stride
+    applied = {}
+    for k in ("pick_cat140", "pick_random300"):
+        (key, (m, root, par, kids, _)), = _lineages(_case(k), _model(k)).items()
+        applied[k] = [C.candidate_index(m, kids[root][0], v, kk) for _, (v, kk), _ in _model(k)["trace"][key][:-1]]
+        assert M.candidates(m, par) == sorted(M.candidates(m, par)) and len(M.candidates(m, par)) == 2 * (m - 3)
+        assert [C.candidate_index(m, kids[root][0], v, kk) for v, kk in M.candidates(m, par)] == list(range(2 * (m - 3)))
+        assert any(i >= pick for i in applied[k]) and any(i < pick for i in applied[k]), (k, applied[k])
+    assert sizes["pick_cat140"] == [140] and pick < 2 * (140 - 3) <= 2 * pick and _case("pick_cat140")["start"] is not None
+    assert sizes["pick_random300"] == [300] and 2 * pick < 2 * (300 - 3) <= 3 * pick and _case("pick_random300")["start"] is None
+    assert grid["pick_random300"][1:] == ([7], 7) and len(applied["pick_cat140"]) >= 50 and len(applied["pick_random300"]) >= 10
+    for k in OLD_CASES:                                                               # before: no lineage had a candidate for a second stride
+        assert max([0] + [2 * (m - 3) for m in sizes[k]]) < pick, k
+
+
+def _starts(case):
+    """key -> (m, root, leaf sets, local parents, children) of the start tree of every searched lineage, as the model makes them"""
+    out = {}
+    groups = members_of(case["clone"])
+    for key in sorted(groups):
+        members, m = groups[key], len(groups[key])
+        if m > 3:
+            ws = windows(case["contigs"], members, case["anchor"])[0]
+            root = C.root_of(case, members)
+            if case["start"] is None:
+                par, _, _, kids = N.orient(m, N.nj_edges([[int(x) << N.SHIFT for x in row] for row in distance_matrix(ws)]), root)
+            else:
+                par = C.caterpillar(m, root)
+                kids = M.tree_of_parents(m, root, par)
+            out[key] = (m, root, M.leaf_sets(ws), par, kids)
+    return out
+
+
+def test_a_scorer_that_stays_on_its_first_tile_is_caught_by_the_stride_cases_alone():
+    """the mutant: k_mp_score without `col0 += gridDim.y * 64` scores a candidate on the first 64 * grid_y columns of its lineage.  That is
+    M.search on leaves cut to those columns.  On SAMPLE lineages of each stride case (chosen by seed; the whole case has thousands) the
+    moves then differ from the full search's in many lineages; in every case from before, 64 * grid_y columns are the whole window of
+    every lineage, so the mutant computes what the kernel computes and no comparison with the model could tell them apart"""
+    for k in OLD_CASES:
+        n_cand, tiles, grid_y = C.scorer_grid(_case(k))
+        assert all(len(ws[0]) <= 64 * grid_y for ws in C.lineage_windows(_case(k)).values() if len(ws) > 3), k
+    for name in ("stride_all", "stride_mixed"):
+        case = _case(name)
+        n_cand, tiles, grid_y = C.scorer_grid(case)
+        starts, sample = _starts(case), _sample_keys(case, seed=3)
+        caught = cut_lineages = 0
+        for key in sorted(sample):
+            m, root, leaves, par, kids = starts[key]
+            moves = [t[1] for t in M.search(leaves, m, root, par, kids)[2]]
+            assert moves == [t[1] for t in _model(name)["trace"][key]], (name, key)  # (the start is the model's: the full search is its trace)
+            if len(leaves[0]) > 64 * grid_y:
+                cut_lineages += 1
+                caught += [t[1] for t in M.search([x[:64 * grid_y] for x in leaves], m, root, par, kids)[2]] != moves
+        assert cut_lineages >= SAMPLE // 2 and caught >= cut_lineages // 4, (name, cut_lineages, caught)

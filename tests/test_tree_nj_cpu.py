@@ -1,7 +1,9 @@
 """The model of vdjx_tree_nj (tests/tree_nj_model.py) against the generator of infinite-sites lineages (tests/tree_nj_cases.py), whose own
 tree is the independent yardstick; Fitch's total against a brute force over every assignment; the tie rule on hand-written cases; the small
-lineages; vdjx_tree_nj_nodes; annot.tree_nj_newick; the table and the stderr line on a hand-written lineage; and every case of the GPU tests
-reaching the edge it is named for.  No GPU."""
+lineages; vdjx_tree_nj_nodes; annot.tree_nj_newick; the table and the stderr line on a hand-written lineage; the numpy steps against the
+plain ones on the cases whose distances round, up to 129 members; and every case of the GPU tests reaching the edge it is named for, by
+the kernels' own constants and formulas: the word counts of `widths` (every register width, the tiles of 32 columns, the chunked path at
+17, 31, 32 and 33 words), and in rand_* the odd lengths on either side of the LDS bound.  No GPU."""
 import ctypes
 import itertools
 import os
@@ -91,6 +93,23 @@ def test_the_numpy_steps_are_the_plain_ones():
         finally:
             N.PLAIN_MEMBERS = saved
         assert plain == N.nj_edges_numpy(D) and len(plain) == 2 * m - 3
+
+
+@pytest.mark.parametrize("name", ["random_wild", "rand_64", "rand_65", "rand_129"])
+def test_the_numpy_steps_are_the_plain_ones_on_the_cases_that_round(name):
+    """the GPU tests of these cases compare with nj_edges_numpy alone (they are above PLAIN_MEMBERS): here it is held against the
+    dictionary version on the very matrices, whose joins halve odd sums and divide with a remainder.  rand_300 is left to the numpy
+    version: the plain one takes m^3 dictionary reads per join"""
+    case = K.gpu_cases()[name]()
+    ws, _ = windows(case["contigs"], list(range(len(case["contigs"]))), case["anchor"])
+    D = [[int(x) << 16 for x in row] for row in distance_matrix(ws)]
+    saved, N.PLAIN_MEMBERS = N.PLAIN_MEMBERS, 1 << 30
+    try:
+        plain = N.nj_edges(D)
+    finally:
+        N.PLAIN_MEMBERS = saved
+    assert len(ws) > N.PLAIN_MEMBERS and plain == N.nj_edges_numpy(D) and len(plain) == 2 * len(ws) - 3
+    assert any(ln & 1 for _, _, ln in plain) and any(ln % (1 << 16) for _, _, ln in plain)
 
 
 def test_random_windows_stay_within_the_issues_bound():
@@ -229,3 +248,39 @@ def test_gpu_cases_reach_their_edges():
     assert sizes["mixed"] == K.MIXED_SIZES
     assert [K.batches_under(K.MIXED_SIZES, knob) for knob in (1, 2500, 1 << 26)] == [7, 3, 1]
     assert [_model(cases["mixed"], cells_knob=knob)["info"]["batches"] for knob in (1, 2500, 1 << 26)] == [7, 3, 1]
+    # widths: every instantiation nj_item<W> of k_nj_matrix's switch, and the chunked path at one word past it, at one below, at and
+    # one above a whole number of chunks -- each on a lineage whose last row block and last column slice are partial, and whose slices
+    # take more than one LDS tile where the tile holds 32 columns
+    reg, rows, target = K.kernel_constant("vdjx_nj.hip", "NJ_REG_WORDS"), K.kernel_constant("vdjx_hamming.h", "HAM_ROWS"), K.kernel_constant("vdjx_hamming.h", "HAM_TARGET_ITEMS")
+    words = K.lineage_words(cases["widths"])
+    assert sorted(words) == K.WIDTH_WORDS and set(range(1, reg + 1)) <= set(words) and {reg + 1, 2 * reg - 1, 2 * reg, 2 * reg + 1} <= set(words)
+    assert K.window_words(cases["widths"]) == 2 * reg + 1 and len(words) == 20 and (cases["widths"]["clone"] == -1).sum() == 5
+    m = K.WIDTH_MEMBERS
+    assert sizes["widths"] == [m] * 20 and rows < m < 2 * rows and m > bound
+    assert -(-sum(s * s for s in sizes["widths"]) // (rows * target)) <= rows         # ham_slice_width: the slices are 64 columns wide
+    tile_cols = lambda W: 64 if W <= 8 else 32                                        # nj_item's TC
+    assert [min(tile_cols(9), rows - c) for c in range(0, rows, tile_cols(9))] == [32, 32] and m - rows == 6       # tiles of 32, 32 | 6
+    lens = {W: len(windows(cases["widths"]["contigs"], v, cases["widths"]["anchor"])[0][0])
+            for W, v in zip(words, (members_of(cases["widths"]["clone"])[k] for k in sorted(members_of(cases["widths"]["clone"]))))}
+    assert lens[reg] == 32 * reg and lens[2 * reg] == 64 * reg                        # the last word full: no padding bits in the last chunk
+    assert all(32 * (W - 1) < w <= 32 * W for W, w in lens.items()) and sum(w % 32 != 0 for w in lens.values()) == 18
+    first = {int(k): i for i, k in reversed(list(enumerate(cases["widths"]["clone"]))) if k >= 0}
+    last = {int(k): i for i, k in enumerate(cases["widths"]["clone"]) if k >= 0}
+    assert all(last[k] - first[k] + 1 > m for k in first)                             # interleaved
+    # rand_*: distances that are not additive on every path of k_nj_join.  A length that is odd has lost bits to nj_half or to
+    # nj_floor_div's remainder (every distance is a whole multiple of 2^16)
+    assert [sizes[k] for k in ("rand_64", "rand_65", "rand_129", "rand_300")] == [[bound], [bound + 1], [129], [300]]
+    assert 129 > bound and 129 % rows == 1                                            # the global path, the last row block a single row
+    for k in ("rand_64", "rand_65", "rand_129", "rand_300"):
+        res = _model(cases[k])
+        ln = res["length"][res["parent"] >= 0]
+        odd, loose = int((ln & 1).sum()), int((ln % (1 << 16) != 0).sum())
+        assert len(ln) == 2 * sizes[k][0] - 3 and odd >= len(ln) // 4 and loose >= len(ln) // 2, (k, odd, loose)
+        assert res["info"]["negative"] == 0 and "N" in "".join(cases[k]["contigs"])
+    rounding = ("widths", "rand_64", "rand_65", "rand_129", "rand_300", "random_wild", "many_small")
+    for k, c in cases.items():
+        res = _model(c)
+        assert res["info"]["negative"] == 0, k                                        # no case has a negative branch
+        if k not in rounding:                                                         # what the cases above add: nothing is rounded in these,
+            assert not (res["length"][res["clone"] >= 0] % (1 << 16)).any(), k        # and the others that round stay below the LDS bound
+    assert max(sizes["random_wild"] + sizes["many_small"]) <= 40 < bound

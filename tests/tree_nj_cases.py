@@ -2,6 +2,8 @@
 (every new leaf is inserted into a random edge), every edge with 1 .. 3 mutations, each at a window column of its own.  The Hamming
 distance of the leaves is then additive, every value of the fixed-point neighbour joining is a whole multiple of 2^16, and the result has to
 be the generator's own tree: its splits, its branch lengths, its inner nodes' sequences.  The generator is the independent yardstick.
+The second family is random windows (random_windows): not additive, so the halvings and the floor division of the joins drop bits and the
+model alone is the yardstick -- rand_* on both sides of the LDS bound, and `widths`, a lineage per packed word count.
 
 A case is a dict: contigs (equally long str), clone, anchor (int32), prio (uint32), and for the infinite-sites ones "gen": per lineage key
 {"members", "adj" (node -> {node: mutations}), "seq" (node -> window)}, leaves 0 .. m - 1 in member order."""
@@ -16,6 +18,13 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 def header_constant(name):
     """a #define of include/vdjx.h as an int (the CPU tests read the exported bound without loading the library)"""
     with open(os.path.join(HERE, "..", "include", "vdjx.h")) as f:
+        return int(re.search(rf"#define\s+{name}\s+(\d+)u?\b", f.read()).group(1))
+
+
+def kernel_constant(file, name):
+    """a #define with a plain number of vdjer_amd/csrc/<file> as an int: the CPU tests recompute from the kernels' own constants which
+    path a case takes, so a case stops passing for reaching its edge when a constant moves"""
+    with open(os.path.join(HERE, "..", "vdjer_amd", "csrc", file)) as f:
         return int(re.search(rf"#define\s+{name}\s+(\d+)u?\b", f.read()).group(1))
 
 
@@ -152,6 +161,19 @@ def mixed(seed):
     return assemble([infinite_sites_windows(m, rng) for m in MIXED_SIZES], rng, loose=5, shuffle=True)
 
 
+WIDTH_WORDS = list(range(1, 18)) + [31, 32, 33]            # every register width of k_nj_matrix; the chunked path at 17, below, at and above 2 x 16
+WIDTH_MEMBERS = 70                                          # row blocks of 64 and 6, column slices of 64 and 6: tiles of 32, 32 and 6 from 9 words on
+
+
+def widths(seed):
+    """a lineage of WIDTH_MEMBERS members per word count of WIDTH_WORDS, non-additive windows with wildcards, interleaved: 16 and 32 words
+    are full (32 W columns), the others end inside their last word"""
+    rng = np.random.default_rng(seed)
+    cols = [32 * W if W in (16, 32) else 32 * W - 1 - 7 * W % 31 for W in WIDTH_WORDS]
+    lin = [(random_windows(WIDTH_MEMBERS, w, rng, wild=0.05, per_member=0.2), None) for w in cols]
+    return assemble(lin, rng, loose=5, shuffle=True)
+
+
 def batches_under(sizes, knob):
     """the batches of whole lineages (of two and more members, in key order) under a knob of matrix cells: how many"""
     count, cells = 0, 0
@@ -175,6 +197,13 @@ def window_words(case):
     return max((sum(window_of(v, case["anchor"], len(case["contigs"][0]))) + 31) // 32 for v in members_of(case["clone"]).values())
 
 
+def lineage_words(case):
+    """the packed words of every lineage's common window, in key order"""
+    from tests.tree_model import members_of, window_of
+    groups = members_of(case["clone"])
+    return [(sum(window_of(groups[k], case["anchor"], len(case["contigs"][0]))) + 31) // 32 for k in sorted(groups)]
+
+
 def gpu_cases():
     """name -> builder of every case test_gpu_tree_nj.py runs; test_tree_nj_cpu.py checks that each reaches the edge it is named for"""
     bound = header_constant("VDJX_NJ_LDS_MEMBERS")
@@ -191,5 +220,12 @@ def gpu_cases():
         "identical": lambda: identical(7, 19),
         "many_small": lambda: many_small(3000, 20),
         "mixed": lambda: mixed(21),
+        "widths": lambda: widths(23),
+        # distances that are not additive: lengths that are odd and no whole multiple of 2^16 -- on the LDS bound, past it, with a last
+        # row block of one row, and at size on the global path
+        "rand_64": lambda: random_case(bound, 230, 24, wild=0.05),
+        "rand_65": lambda: random_case(bound + 1, 230, 25, wild=0.05),
+        "rand_129": lambda: random_case(129, 300, 26, wild=0.05),
+        "rand_300": lambda: random_case(300, 400, 27, wild=0.05),
     })
     return out

@@ -286,23 +286,39 @@ template <typename TUP> struct TupBucket {
 
 // K2c' pass 1: records -> gated tuples, LDS-staged counting sort into `nbk` coarse buckets (a round of vdjx_part.h: the counting
 // and the placement are this kernel's, the rest is part_round's).
-// A round takes `rr0` records (the host sizes it from the gated fraction the histogram measured, so that the stage fills: with one
-// instance in six gated, rounds sized for the worst case spend their time in barriers); a round whose tuples do not fit is
-// simply retried with half the records.  The gated instances of a round are listed once (dense, see above) as descriptors
-// {record in the round (16 bits), offset (6), bucket (10)}; the placement pass reads the descriptors, not the records' offsets.
+// A round takes `rr0` records (the host sizes it from the gated fraction the histogram measured, so that the round's room fills: with
+// one instance in six gated, rounds sized for the worst case spend their time in barriers); a round whose tuples do not fit is
+// simply retried with half the records.  The gated instances of a round are listed once (dense, see above).
+// Short reads (KEEP): the counting pass makes every instance's TUPLE -- k-mer, canonical side, instance, bucket -- once and leaves it
+// in LDS at its dense position with its bucket beside it; after reserve the placement only sorts {bucket, position} words into bucket
+// order and the copy-out follows them: nothing is cut out, mirrored or hashed a second time and no record is fetched again.  The
+// waves' lists need room of their own then (the tuples arrive while they are read); the sorted words take it over once the round
+// is counted.  LDS: 48 KB lists | PARTR_KEEP_BYTES = ROUND x (tuple + 2), beside part_round's 20.6 KB: 5,200 tuples of 16 bytes.
+// Long reads: the lists fill the stage (88 KB), so the round keeps 4-byte descriptors {record in the round (16 bits), offset (8),
+// bucket (10)} as before, the placement makes the tuples from the records in global memory and part_round::flush hashes them again.
 #define PARTR_STAGE_BYTES 98304u
+#define PARTR_LIST_BYTES (PART_THREADS / 64u * GL_WAVE_BYTES)
+#define PARTR_KEEP_BYTES 93600u
+template <typename TUP, bool LONG> constexpr u32 partr_round() { return LONG ? PARTR_STAGE_BYTES / (u32) sizeof(TUP) : PARTR_KEEP_BYTES / ((u32) sizeof(TUP) + 2u); }
+template <typename TUP, bool LONG> constexpr u32 partr_lds() { return LONG ? PARTR_STAGE_BYTES + partr_round<TUP, true>() * 4u : PARTR_LIST_BYTES + PARTR_KEEP_BYTES; }
 template <typename TUP, bool LONG, bool SYM = false>
 __global__ __launch_bounds__(PART_THREADS) void k_part_records_g(const u64* __restrict__ bases, const u64* __restrict__ nmask,
                                                                  const u64* __restrict__ lowq, size_t R, u64 rec_base, int rl, int k,
                                                                  u32 shift, u32 nbk, size_t rpb, u32 rr0, const u32* __restrict__ lim, u32 lsh,
                                                                  u32* __restrict__ over, u32* __restrict__ gcur, TUP* __restrict__ out) {
 	extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-	TUP* stage = (TUP*) smem;                                         // (the waves' instance lists live here while the round is counted)
-	u32* desc = (u32*) (smem + PARTR_STAGE_BYTES);
+	constexpr bool KEEP = !LONG;
+	constexpr u32 ROUND = partr_round<TUP, LONG>();
+	static_assert(PARTR_LIST_BYTES % 16 == 0 && ROUND * sizeof(TUP) % 8 == 0 && ROUND * 4u <= PARTR_LIST_BYTES && ROUND <= 65536u, "the KEEP layout");
+	static_assert(PART_THREADS / 64u * GL_WAVE_BYTES_LONG <= PARTR_STAGE_BYTES, "the long lists live in the stage");
+	// LONG: the stage (the waves' instance lists live here while the round is counted), then the descriptors
+	// KEEP: the lists / the sorted words, then the tuples at their dense positions, then their buckets
+	TUP* stage = (TUP*) (smem + (KEEP ? PARTR_LIST_BYTES : 0u));
+	u32* desc = (u32*) (smem + (KEEP ? 0u : PARTR_STAGE_BYTES));
+	uint16_t* bkt = (uint16_t*) (stage + ROUND);
 	__shared__ part_round pr;
 	__shared__ u32 s_n;
-	constexpr u32 ROUND = PARTR_STAGE_BYTES / sizeof(TUP);
-	constexpr int OB = LONG ? 8 : 6;                                  // offset bits (descriptor: record in the round << (OB + 10) | offset << 10 | bucket)
+	constexpr int OB = LONG ? 8 : 6;                                  // offset bits (instance: record << OB | offset; LONG descriptor: record in the round << (OB + 10) | offset << 10 | bucket)
 	const int P = rl - k + 1;
 	const u32 rr_min = ROUND / (u32) P;                              // always fits
 	u32 rr = rr0 > rr_min ? rr0 : rr_min;
@@ -313,7 +329,7 @@ __global__ __launch_bounds__(PART_THREADS) void k_part_records_g(const u64* __re
 	ulonglong2* wb = (ulonglong2*) wv;
 	u64* wrow = (u64*) wv;
 	uint16_t* wl = (uint16_t*) (wv + (LONG ? 64u * GL_ROW_LONG * 8u : 1024u));
-	const size_t r0 = (size_t) blockIdx.x * rpb;            // (SYM: R, rpb, rr and the descriptors count COUPLES of records)
+	const size_t r0 = (size_t) blockIdx.x * rpb;            // (SYM: R, rpb, rr and the records in the round count COUPLES of records)
 	const size_t r1 = r0 + rpb < R ? r0 + rpb : R;
 	size_t rs = r0;
 	pr.limits(nbk, lim, lsh, over);
@@ -349,47 +365,64 @@ __global__ __launch_bounds__(PART_THREADS) void k_part_records_g(const u64* __re
 				dbase = (u32) __builtin_amdgcn_readlane((int) dbase, 0);
 				for (u32 i = lane; i < total; i += 64) {
 					const u32 e = wl[i];
+					const u32 o = e & ((1u << OB) - 1u);
 					u64 khi, klo;
-					if (LONG) vdjx_kmer_at_words(wrow + (e >> 8) * GL_ROW_LONG, k, (int) (e & 255u), khi, klo);
-					else if (SYM) (void) sym_canonical(wb[e >> 6], rl, k, (int) (e & 63u), khi, klo);
-					else {
-						const ulonglong2 bb = wb[e >> 6];
-						vdjx_kmer_at_lane(bb.x, bb.y, rl, k, (int) (e & 63u), khi, klo);
+					if constexpr (LONG) {
+						vdjx_kmer_at_words(wrow + (e >> 8) * GL_ROW_LONG, k, (int) o, khi, klo);
+						const u32 b = (u32) (vdjx_bucket_mix(klo, khi) >> shift) & mask;
+						pr.count(b);
+						if (dbase + i < ROUND) desc[dbase + i] = ((loc0 + (e >> OB)) << (OB + 10)) | (o << 10) | b;
+					} else {
+						const u64 r = rec_base + (SYM ? 2 : 1) * (u64) (rs + loc0 + (e >> OB));
+						u64 inst = (r << OB) | (u64) o;
+						const ulonglong2 bb = wb[e >> OB];
+						if (SYM) {
+							// the tuple of the canonical side: this instance, or its mirror in the couple's second record
+							if (sym_canonical(bb, rl, k, (int) o, khi, klo)) inst = ((r + 1) << OB) | (u64) (rl - k - (int) o);
+						} else vdjx_kmer_at_lane(bb.x, bb.y, rl, k, (int) o, khi, klo);
+						const u32 b = (u32) (vdjx_bucket_mix(klo, khi) >> shift) & mask;
+						pr.count(b);
+						if (dbase + i < ROUND) {
+							TUP::store(&stage[dbase + i], TUP::make(klo, khi, inst));
+							bkt[dbase + i] = (uint16_t) b;
+						}
 					}
-					const u32 b = (u32) (vdjx_bucket_mix(klo, khi) >> shift) & mask;
-					pr.count(b);
-					if (dbase + i < ROUND) desc[dbase + i] = ((loc0 + (e >> OB)) << (OB + 10)) | ((e & ((1u << OB) - 1u)) << 10) | b;
 				}
 				vdjx_wave_lds_fence();
 			}
 		}
 		__syncthreads();
-		if (s_n > ROUND) {                                            // (uniform) too many gated instances for the stage
+		if (s_n > ROUND) {                                            // (uniform) too many gated instances for the round's room
 			rr = rr / 2 > rr_min ? rr / 2 : rr_min;
 			__syncthreads();
 			continue;
 		}
 		const u32 n = pr.reserve(nbk, gcur);                          // (PART_DEAD: the sampled cut's buckets are capacities)
 		if (n == PART_DEAD) return;                                   // (uniform)
-		for (u32 i = threadIdx.x; i < n; i += PART_THREADS) {
-			const u32 d = desc[i];
-			const size_t r = rs + (d >> (OB + 10));
-			const u32 o = (d >> 10) & ((1u << OB) - 1u);
-			u64 khi, klo;
-			u64 inst = ((rec_base + (u64) r) << OB) | (u64) o;
-			if (LONG) vdjx_kmer_at_words(bases + r * VDJX_LONG_W, k, (int) o, khi, klo);      // (two words past the last record are readable: pool_alloc)
-			else if (SYM) {
-				// the tuple of the canonical side: this instance, or its mirror in the couple's second record
-				const bool flip = sym_canonical(((const ulonglong2*) bases)[2 * r], rl, k, (int) o, khi, klo);
-				inst = flip ? ((rec_base + 2 * (u64) r + 1) << OB) | (u64) (rl - k - (int) o) : ((rec_base + 2 * (u64) r) << OB) | (u64) o;
-			} else {
-				const ulonglong2 bb = ((const ulonglong2*) bases)[r];
-				vdjx_kmer_at_lane(bb.x, bb.y, rl, k, (int) o, khi, klo);
+		if constexpr (LONG) {
+			for (u32 i = threadIdx.x; i < n; i += PART_THREADS) {
+				const u32 d = desc[i];
+				const size_t r = rs + (d >> (OB + 10));
+				const u32 o = (d >> 10) & ((1u << OB) - 1u);
+				u64 khi, klo;
+				vdjx_kmer_at_words(bases + r * VDJX_LONG_W, k, (int) o, khi, klo);      // (two words past the last record are readable: pool_alloc)
+				TUP::store(&stage[pr.slot(d & 1023u)], TUP::make(klo, khi, ((rec_base + (u64) r) << OB) | (u64) o));
 			}
-			TUP::store(&stage[pr.slot(d & 1023u)], TUP::make(klo, khi, inst));
+			__syncthreads();
+			pr.flush(stage, n, out, TupBucket<TUP>{shift, mask});
+		} else {
+			u32* sorted = desc;                                       // (the lists are done with: the barrier above)
+			for (u32 i = threadIdx.x; i < n; i += PART_THREADS) {
+				const u32 b = bkt[i];
+				sorted[pr.slot(b)] = (b << 16) | i;
+			}
+			__syncthreads();
+			for (u32 j = threadIdx.x; j < n; j += PART_THREADS) {       // part_round::flush, the bucket and the tuple's place from the word
+				const u32 s = sorted[j], b = s >> 16;
+				TUP::store(&out[pr.gbase[b] + (j - pr.base[b])], TUP::load(&stage[s & 0xFFFFu]));
+			}
+			__syncthreads();
 		}
-		__syncthreads();
-		pr.flush(stage, n, out, TupBucket<TUP>{shift, mask});
 		rs = re;
 	}
 }
@@ -2506,8 +2539,6 @@ int stage_gated_cut(vdjx_ctx* c, A& db, const vdjx_pool* pool, u64 rec_base, int
 	const u32 Tt = T + extra;
 	const u32 NBt = 1u << Tt;
 	HIP_TRY(db.alloc(&out->t, room + 1));
-	constexpr u32 stage_tuples = PARTR_STAGE_BYTES / (u32) sizeof(TUP);
-	constexpr u32 lds_partr = PARTR_STAGE_BYTES + stage_tuples * 4;
 	// pass geometry: <= 1024 buckets in one pass; otherwise 256 coarse x the rest (large pools: 2^(Tt-10) coarse x 1024)
 	u32 cbits = Tt, fbits = 0;
 	if (Tt > 10) { cbits = extra ? Tt - 10 : 8; fbits = Tt - cbits; }
@@ -2526,10 +2557,16 @@ int stage_gated_cut(vdjx_ctx* c, A& db, const vdjx_pool* pool, u64 rec_base, int
 	if (fbits) HIP_TRY(db.alloc(&l1, room + 1));
 	{
 		vdjx_prof_scope ps(c, "k_part_records");
-		// records per round: three quarters of the stage at the measured gated fraction, in whole sweeps of the workgroup
+		// records per round at the measured gated fraction.  Long reads: three quarters of the stage, in whole sweeps of the workgroup.
+		// Short reads: seven eighths of the round's room, in whole waves -- a sweep has no barrier inside, a wave without records
+		// falls through it -- so that a round is not a sweep of 1,024 records where a sweep overfills it (k = 25: 13.8 tuples per
+		// couple; every workgroup then counted 1,024 and 512 couples for nothing before its rounds of 256 fitted)
+		const u32 round_tuples = lng ? partr_round<TUP, true>() : partr_round<TUP, false>();
+		const u32 lds_partr = lng ? partr_lds<TUP, true>() : partr_lds<TUP, false>();
 		const u64 NIl = (u64) R * (u64) P;
-		u64 rr = N ? (u64) stage_tuples * 3 / 4 * NIl / ((u64) N * (u64) P) : 1u << 16;
-		rr = std::max<u64>(PART_THREADS, std::min<u64>(rr / PART_THREADS * PART_THREADS, lng ? 1u << 14 : 1u << 16));      // (the descriptor's record field)
+		u64 rr = N ? (lng ? (u64) round_tuples * 3 / 4 : (u64) round_tuples * 7 / 8) * NIl / ((u64) N * (u64) P) : 1u << 16;
+		const u64 rstep = lng ? PART_THREADS : 64u;
+		rr = std::max<u64>(rstep, std::min<u64>(rr / rstep * rstep, lng ? 1u << 14 : 1u << 16));      // (long: the descriptor's record field)
 		auto* part_records = lng ? k_part_records_g<TUP, true> : sym ? k_part_records_g<TUP, false, true> : k_part_records_g<TUP, false>;
 		HIP_TRY(part_launch(st, part_records, nblk2, lds_partr, hstart, NBc, HB - cbits, gcur, l1, pool->d_bases, pool->d_nmask, pool->d_lowq, R, rec_base,
 		                    pool->rl, k, 64 - cbits, NBc, rpb, (u32) rr, smp ? (const u32*) hstart : (const u32*) nullptr, HB - cbits, over));

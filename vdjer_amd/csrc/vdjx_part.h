@@ -7,8 +7,8 @@
 // per pass keep the runs long; more are reached in two passes, the second working inside one segment of the first (a few MB, cache
 // resident) at a time.  Placement inside a bucket is arbitrary (the cursor bumps of the rounds race): what reads the buckets is order-free.
 //
-//   part_round   the bookkeeping of a round: begin, (count,) reserve, (slot,) flush.  k_part_records_g (vdjx_kmer.hip) counts and
-//                places from its own descriptors; everything else of its round is this.  Where the buckets are capacities and not
+//   part_round   the bookkeeping of a round: begin, (count,) reserve, (slot,) flush.  k_part_records_g (vdjx_kmer.hip) counts, places
+//                and -- where it keeps its tuples with their buckets -- copies out itself; the rest of its round is this.  Where the buckets are capacities and not
 //                exact sizes (the k-mer build's sampled cut), limits names where they end and reserve refuses a run past its end
 //   part_slice   the share of a workgroup in a pass over segments; k_seg_hist_g counts the sub-buckets of the same slices
 //   k_part       the streaming pass: T elements in, T elements out, the bucket from a functor on the element, the range from
@@ -64,7 +64,8 @@ __device__ inline void part_store(u64* p, const u64& x) { *p = x; }
 // threads; between them the kernel counts every element of the round once (count) and, after reserve, takes a slot of the stage for
 // every one (slot) and stores it there.
 struct part_round {
-	u32 cnt[PART_MAXB], base[PART_MAXB + 1], cur[PART_MAXB], gbase[PART_MAXB], tmp[PART_THREADS];
+	u32 cnt[PART_MAXB], base[PART_MAXB + 1], cur[PART_MAXB], gbase[PART_MAXB];
+	u32 tmp[PART_THREADS / 64 + 1];                 // (part_scan: the waves' totals and the grand total)
 	u32 end[PART_MAXB];           // (limits) where the workgroup's buckets end
 	u32* over;
 	u32 dead, stop;

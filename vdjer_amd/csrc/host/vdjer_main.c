@@ -1,58 +1,9 @@
 /*
  * vdjer_main.c -- the `vdjer` command line (params.c:74-101, 214-298) over libvdjx (GPU hot path) and
- * vdjh (serial host stage).  Plain C; talks to the GPU only through the C ABI of include/vdjx.h.
+ * vdjh (serial host stage).  Plain C; talks to the GPU only through the C ABI of include/vdjx.h.  The options: vdjer_cli.c (one
+ * table; `vdjer --help` prints it); what a table flag does is said at its step below.
  *
- *   vdjer --in <reads> --chain IGH|IGK|IGL --ref-dir <dir> --ins <n> [--t --k --mf --mq --mcs --am --miw --maw
- *         --jc --ws -jext --rf --vk --mrs --rs --ms --e0 --e1 --wo --vf --jf --rms] [--gpus N] [--quant <file>] [--quant-boot <B>] [--quant-seed <s>] [--airr <file>]
- *         [--d-calls] [--cfa <fasta>] [--isotypes <file>] [--clones <file>] [--sample <name>] [--total-count <n>]
- *         [--lineages <file>] [--lineage-dist <x>] [--lineage-model <file>] [--lineage-symmetry avg|min] [--lineage-threshold <file>] [--lineage-link single|complete|average] [--trees <file>] [--tree-support <B>] [--tree-seed <s>] [--trees-nj <file>] [--trees-newick <file>] [--trees-mp <file>] [--trees-mp-newick <file>] [--mutations <file>]
- *         [--diversity <file>] [--diversity-depth <n>] [--diversity-boot <B>] [--diversity-seed <s>]
- *         [--selection <file>] [--v-regions <file>] [--targeting <file>] [--selection-combine shared|mean] [--selection-test <file>]
- *         [--targeting-model <file>] [--targeting-class s|rs] [--targeting-min-sub <n>] [--targeting-min-mut <n>] [--targeting-counts <file>]
- *         [--consensus <file>] [--consensus-min-freq <x>]
- * writes ./vdj_contigs.fa and ./vdjer.dot, SAM on stdout, log on stderr; exit 0 on success.  --quant <file>: the contigs' abundances
- * (vdjx_quant, RSEM's isoforms.results columns) into <file> as well; --quant-boot <B> (with --quant): B bootstrap replicates of them over the placed
- * pairs (vdjx_quant_boot) drawn from --quant-seed <s>: the columns boot_mean, boot_sd, boot_lower and boot_upper, and in the --lineages table
- * clone_count_sd, the sd over the replicates of a lineage's summed counts.  --airr <file>: the contigs' V/J annotation (vdjx_annotate against
- * the germlines of ig_vdj.fa / --vdjf) as an AIRR Rearrangement TSV; with --d-calls (a flag: no value) the D gene between the V and the
- * J hit as well (vdjx_dcall against the class-D records of the same FASTA), and the N regions around it.  --cfa <fasta>: constant-region sequences; --isotypes <file>: the
- * isotype call of every contig against them (vdjx_isotype); --clones <file>: the per-sample table of the reference's post_process/
- * (collect_vdjer_stats.py | cluster_results.py) from the three device steps (one GPU only).  --lineages <file>: the contigs grouped into
- * clonal lineages (vdjx_lineage: single linkage on the junctions' Hamming distance inside a V gene / J gene / junction length bucket,
- * linked up to --lineage-dist, default 0.15 of the length); with --airr the table gets a clone_id column.  --lineage-model <file> (with
- * --lineages): a 5-mer targeting model in the format --targeting reads; the junctions are then compared under its substitution distance
- * (vdjx_lineage_distance_table, vdjx_lineage_model: Change-O DefineClones --model hh_s5f), --lineage-dist in units of a mean mismatch;
- * --lineage-symmetry avg|min: both directions of a mismatch added (default) or twice the cheaper.  The file must exist beforehand: a run does
- * not read the --targeting-model file it is writing itself.  --lineage-threshold <file> (with --lineages): the threshold is chosen from
- * the distances to the nearest neighbour of a first pair pass (vdjx_lineage_threshold: shazam's findThreshold, the valley between their two
- * modes) and the pass runs once more with it; the file gets the histogram and the smoothed density; where no valley is found --lineage-dist
- * stands.  --lineage-link single|complete|average (with --lineages): the linkage the lineages are cut at the threshold under
- * (vdjx_lineage_link: Change-O DefineClones --link); single, the default, is the call without the flag.  --trees <file> (with --lineages):
- * the tree inside every lineage (vdjx_tree: the minimum spanning tree under the Hamming distance over the members' common window around
- * the junction, rooted at the member closest to its germline V); --tree-support <B> (with --trees): a support column, the share of B
- * delete-half jackknife replicates whose tree has the edge to the parent (vdjx_tree_support), the columns drawn from --tree-seed <s>.
- * --mutations <file>: every contig and its V(D)J germline side by side and the V segment's replacement / silent / stop mutation counts
- * (vdjx_mutations: Change-O CreateGermlines and shazam observedMutations); with --airr the table's sequence_alignment and
- * germline_alignment cells are filled, with --d-calls the D hit's germline is laid into the gap, with --lineages the table gets a clone_id.
- * --diversity <file> (with --lineages and the quant step): the Hill diversity curve of the lineages weighed by their expected counts,
- * orders 0.0 .. 4.0, with the mean and spread of --diversity-boot <B> bootstrap replicates of --diversity-depth <n> draws each
- * (vdjx_diversity: alakazam's alphaDiversity), drawn from --diversity-seed <s>.
- * --selection <file>: the selection strength of the V segment's mutations (vdjx_selection: shazam's expectedMutations / calcBaseline /
- * groupBaseline / summarizeBaseline): observed against expected replacement and silent mutations and the posterior of sigma for every
- * contig, every lineage (with --lineages) and the sample, below --mutations' limit; --v-regions <file>: the CDR1 / CDR2 intervals of the V
- * records, which split every row into fwr and cdr; --targeting <file>: a 5-mer targeting model (default: uniform).
- * --selection-combine shared|mean (with --selection): the lineage, sample and consensus_sample rows as one sigma shared by the members
- * (default) or as the mean of the members' independent sigmas, their densities convolved (vdjx_selection_convolve: groupBaseline);
- * --selection-test <file> (with --selection and --v-regions): cdr against fwr for each of those rows (vdjx_selection_compare: testBaseline).
- * --targeting-model <file>: the sample's own 5-mer targeting model in the format --targeting reads (vdjx_targeting_counts and
- * vdjx_targeting_model: shazam's createTargetingModel), learnt from the V segments below --mutations' limit, a lineage of --lineages over
- * one V record counted once; --targeting-class s|rs: from silent changes only (default) or silent and replacement; --targeting-min-sub
- * <n>, --targeting-min-mut <n>: the observed changes a 5-mer needs for a substitution (50) and a mutability (500) estimate of its own;
- * --targeting-counts <file>: the counts behind the model.  A --selection table of the same run does not read the model being written.
- * --consensus <file> (with --lineages): the consensus V sequence of every lineage, and of every contig in none, beside its germline
- * (vdjx_consensus: shazam's collapseClones, thresholdedFreq), decided column by column below --mutations' limit; --consensus-min-freq <x>:
- * the share of a column's votes its winner needs (default 0.6; 0: the most common symbol); the row's mutation counts are vdjx_mutations' of
- * the consensus; with --selection that table gets a consensus row per unit and one consensus_sample row, one representative per clone.
+ * Writes ./vdj_contigs.fa and ./vdjer.dot, SAM on stdout, log on stderr; exit 0 on success.
  *
  * --in: a BAM with its .bai (extraction as bam_read.c:264-446, restated over zlib in bamx.c), or -- recognised by its
  * content -- the extracted read pool as text, one read per line in extraction order:
@@ -75,6 +26,7 @@
 #include "bamx.h"
 #include "vdjx_mgpu.h"
 #include "vdjx_newick.h"
+#include "vdjer.h"
 #include <errno.h>
 #include <sys/wait.h>
 #include <sys/resource.h>
@@ -82,463 +34,6 @@
 #include <signal.h>
 #include <pthread.h>
 #include <unistd.h>
-
-typedef struct {
-	vdjh_params hp;
-	const char* in;
-	char v_anchors[4096], j_anchors[4096], source_sim_file[4096], vdj_fasta[4096];
-	char v_region[64], c_region[64];       /* set_chain_info, params.c:8-35 (hg38 coordinates); --vr / --cr override */
-	int anchor_mismatches, threads;
-	int gpus;                              /* --gpus N (not in the reference): the k-mer build sharded over N GPUs of this node */
-	const char* quant;                     /* --quant <file> (not in the reference): the RSEM step of demo/quant_demo.bash, on the device */
-	const char *quant_boot_s, *quant_seed_s;      /* --quant-boot <B>, --quant-seed <s>: the bootstrap of the quant table (vdjx_quant_boot); read into qb_b (0: none) and qb_seed */
-	uint32_t qb_b; uint64_t qb_seed;
-	const char* airr;                      /* --airr <file> (not in the reference): the HighV-QUEST step of post_process/, on the device */
-	int d_calls;                           /* --d-calls (not in the reference; no value): d_call, d_cigar and the N regions in the --airr table */
-	const char* cfa;                       /* --cfa <fasta> (not in the reference): the constant-region sequences of --isotypes / --clones */
-	const char* isotypes;                  /* --isotypes <file> (not in the reference): call_isotypes.bash of post_process/, on the device */
-	const char* clones;                    /* --clones <file> (not in the reference): collect_vdjer_stats.py | cluster_results.py */
-	const char* sample;                    /* --sample <name>: the clone table's first column (default: --in's base name up to its first '.') */
-	const char* total_count;               /* --total-count <n>: the clone table's total_count column (default: N/A) */
-	const char* lineages;                  /* --lineages <file> (not in the reference): Change-O DefineClones' grouping of the contigs, on the device */
-	const char* lineage_dist;              /* --lineage-dist <x>: its threshold, a decimal read exactly into lin_num / lin_den (default 1500 / 10000) */
-	int lin_num, lin_den;
-	const char *lin_model, *lin_symmetry;  /* --lineage-model <file>: a --targeting file, read by parse() into lin_table (NULL: Hamming); --lineage-symmetry avg|min -> lin_sym */
-	int lin_sym; uint16_t* lin_table; vdjx_lineage_table_info lin_ti;
-	const char* lin_threshold;             /* --lineage-threshold <file>: choose --lineage-dist from the nearest distances (vdjx_lineage_threshold) and write its histogram and density */
-	const char* lin_link; int lin_linkage;  /* --lineage-link single|complete|average -> 0, 1, 2 (vdjx_lineage_link; 0: the two calls above, as without the flag) */
-	const char* trees;                     /* --trees <file> (not in the reference): the tree inside every lineage of --lineages, on the device */
-	const char *trees_nj, *trees_newick;   /* --trees-nj <file>, --trees-newick <file> (not in the reference): neighbour-joining trees with inferred ancestors, and their Newick lines */
-	const char *trees_mp, *trees_mp_newick;   /* --trees-mp <file>, --trees-mp-newick <file> (not in the reference): those trees after a search for fewer mutations */
-	const char *tree_support, *tree_seed;  /* --tree-support <B>, --tree-seed <s>: the jackknife support of the trees' edges; read into ts_b (0: none) and ts_seed */
-	uint32_t ts_b; uint64_t ts_seed;
-	const char* mutations;                 /* --mutations <file> (not in the reference): CreateGermlines / observedMutations, on the device */
-	const char* diversity;                 /* --diversity <file> (not in the reference): alakazam's alphaDiversity over the lineages, on the device */
-	const char *div_depth_s, *div_boot_s, *div_seed_s;      /* --diversity-depth <n> (read into div_depth; 0: the total expected pairs), --diversity-boot <B>, --diversity-seed <s> */
-	uint32_t div_depth, div_boot; uint64_t div_seed;
-	const char* selection;                 /* --selection <file> (not in the reference): shazam's BASELINe over the V segment, on the device */
-	const char *v_regions, *targeting;     /* --v-regions <file>, --targeting <file>: read by parse() into regs / nregs and weight (NULL: uniform) */
-	const char *sel_combine, *sel_test;    /* --selection-combine shared|mean (read into sel_mean), --selection-test <file>: cdr against fwr per lineage and sample */
-	int sel_mean;
-	struct vreg_line* regs; size_t nregs;
-	uint32_t* weight;
-	const char* tgt_model;                 /* --targeting-model <file> (not in the reference): shazam's createTargetingModel, on the device */
-	const char *tgt_class, *tgt_min_sub_s, *tgt_min_mut_s, *tgt_counts;      /* --targeting-class s|rs (read into tgt_cls), --targeting-min-sub <n>, --targeting-min-mut <n>, --targeting-counts <file> */
-	int tgt_cls; uint64_t tgt_min_sub, tgt_min_mut;
-	const char *consensus, *cons_min_freq; /* --consensus <file> (not in the reference): shazam's collapseClones over the lineages, on the device; --consensus-min-freq <x>: read as --lineage-dist is, into cons_num over 10000 (default 6000) */
-	int cons_num;
-	int have_chain, have_ref;
-} cli;
-
-static void usage(void) {
-	fprintf(stderr, "vdjer \n\t--in <input BAM (with .bai), or the extracted reads as text (see vdjer_main.c)>\n\t--chain <IGH|IGK|IGL>\n\t--ref-dir </path/to/vdjer/ref/dir>\n"
-	                "\t--mf <min node frequency (default: 3)>\n\t--mq <min base quality (default: 90)>\n\t--mcs <min contig score (default: -5)\n"
-	                "\t--t <threads (default: 1)\n\t--am <anchor mismatches (default: 4)\n\t--miw/--maw <min/max window between conserved amino acids>\n"
-	                "\t--jc <conserved J amino acid (W|F)\n\t--ws <window span (default: 486)\n\t--jext <J extension (default: 162)\n"
-	                "\t--ins <expected / median insert length>\n\t--rf <read filter floor (default: 1)\n\t--k <kmer size (default: 35)>\n"
-	                "\t--vk <vregion kmer size (default: 15)>\n\t--mrs <min source node homology score (default: 30)\n"
-	                "\t--rs <read span distance (default: 35)>\n\t--ms <mate span distance (default: 48)>\n"
-	                "\t--e0/--e1 <start/stop position for contig filtering (default: 52/411)>\n\t--wo <window overlap check size>\n"
-	                "\t--gpus <GPUs of this node to shard the k-mer table over (default: 1)>\n"
-	                "\t--quant <file: expected read pairs per contig, an RSEM isoforms.results table (one GPU only)>\n"
-	                "\t--quant-boot <B: with --quant, bootstrap the placed pairs B times (a whole number in 1 .. 1024): boot_mean, boot_sd, boot_lower, boot_upper>\n"
-	                "\t--quant-seed <seed of the --quant-boot draws, a whole number below 2^64 (default: 1)>\n"
-	                "\t--airr <file: V/J calls of every contig against ig_vdj.fa, an AIRR Rearrangement table>\n"
-	                "\t--d-calls (no value; with --airr: the D gene between the V and the J hit against the D records of ig_vdj.fa, and np1 / np2)\n"
-	                "\t--cfa <constant-region FASTA for --isotypes / --clones>\n"
-	                "\t--isotypes <file: isotype call of every contig's last 48 bases against --cfa>\n"
-	                "\t--clones <file: the clustered clone table of this sample (one GPU only)>\n"
-	                "\t--sample <name in the clone table (default: the input's base name up to its first '.')>\n"
-	                "\t--total-count <whole number for the clone table's total_count column (default: N/A)>\n"
-	                "\t--lineages <file: clonal lineages of the contigs, single linkage on the junctions inside a V gene / J gene / length bucket>\n"
-	                "\t--lineage-dist <largest linked distance as a fraction of the junction length, in [0,1], at most 4 decimals (default: 0.15)>\n"
-	                "\t--lineage-model <file: with --lineages, a 5-mer targeting model as --targeting reads it: link under its substitution distance, --lineage-dist in mean mismatches>\n"
-	                "\t--lineage-symmetry <avg|min: with --lineage-model, add both directions of a mismatch (default: avg) or take twice the cheaper>\n"
-	                "\t--lineage-threshold <file: with --lineages, choose the threshold from the distances to the nearest neighbour (the valley between their two modes; --lineage-dist stands when there is none) and write their histogram and smoothed density>\n"
-	                "\t--lineage-link <single|complete|average: with --lineages, the linkage the lineages are cut at the threshold under (default: single; where distances tie, complete and average depend on the contigs' order)>\n"
-	                "\t--trees <file: with --lineages, the minimum spanning tree inside every lineage: parent, distance and depth of every contig>\n"
-	                "\t--trees-nj <file: with --lineages, the neighbour-joining tree inside every lineage with its inferred ancestors: a row per node>\n"
-	                "\t--trees-newick <file: with --trees-nj, one Newick line per lineage of two and more members>\n"
-	                "\t--trees-mp <file: with --lineages, the neighbour-joining tree of every lineage after a search over nearest-neighbour interchanges for fewer mutations: a row per node>\n"
-	                "\t--trees-mp-newick <file: with --trees-mp, one Newick line per lineage of two and more members, lengths in mutations>\n"
-	                "\t--tree-support <B: with --trees, a support column from B delete-half jackknife replicates, a whole number in 1 .. 1024>\n"
-	                "\t--tree-seed <seed of the replicates' columns, a whole number below 2^64 (default: 1)>\n"
-	                "\t--mutations <file: every contig beside its V(D)J germline, and the V segment's replacement / silent / stop mutation counts>\n"
-	                "\t--diversity <file: with --lineages and --quant or --clones, the Hill diversity curve of the lineages, orders 0.0 .. 4.0, bootstrapped>\n"
-	                "\t--diversity-depth <n: draws per bootstrap replicate, a whole number in 1 .. 2147483647 (default: the lineages' total expected pairs)>\n"
-	                "\t--diversity-boot <B: bootstrap replicates, a whole number in 1 .. 4096 (default: 200)>\n"
-	                "\t--diversity-seed <seed of the draws, a whole number below 2^64 (default: 1)>\n"
-	                "\t--selection <file: selection strength (BASELINe) of the V mutations: observed and expected R / S and the posterior of sigma per contig, lineage (with --lineages) and sample>\n"
-	                "\t--v-regions <file: with --selection, lines `name cdr1_start cdr1_end cdr2_start cdr2_end` (1-based, inclusive, 0 0: none) of the V records: rows fwr and cdr>\n"
-	                "\t--selection-combine <shared|mean: with --selection, the lineage and sample rows as one shared sigma (default) or as BASELINe's mean of the members' sigmas (their densities convolved)>\n"
-	                "\t--selection-test <file: with --selection and --v-regions, cdr against fwr per lineage and sample: P(sigma_cdr > sigma_fwr), two-sided p-value, Benjamini-Hochberg fdr>\n"
-	                "\t--targeting <file: with --selection, 1024 lines `<5-mer> <wA> <wC> <wG> <wT>`, whole numbers below 2^32 (default: uniform)>\n"
-	                "\t--targeting-model <file: the sample's own 5-mer targeting model, in the format --targeting reads, learnt from the V mutations (a lineage of --lineages counted once)>\n"
-	                "\t--targeting-class <s|rs: with --targeting-model, learn from silent changes only (default: s) or from silent and replacement>\n"
-	                "\t--targeting-min-sub <n: with --targeting-model, changes a 5-mer needs for its own substitution row, a whole number in 1 .. 4294967295 (default: 50)>\n"
-	                "\t--targeting-min-mut <n: with --targeting-model, changes a 5-mer needs for its own mutability, a whole number in 1 .. 4294967295 (default: 500)>\n"
-	                "\t--targeting-counts <file: with --targeting-model, the observed and opportunity counts per 5-mer and the levels used>\n"
-	                "\t--consensus <file: with --lineages, the consensus V sequence of every lineage (and of every contig in none) beside its germline, and its mutation counts>\n"
-	                "\t--consensus-min-freq <share of a column's votes its winner needs, in [0,1], at most 4 decimals (default: 0.6; 0: the most common)>\n");
-}
-
-static int file_exists(const char* f) { struct stat b; return stat(f, &b) == 0; }
-
-/* --lineage-dist: a decimal in [0, 1] with at most four digits after the point, read exactly (no strtod): at most one digit before the
- * point, at least one digit in all -> its numerator over 10000, or -1 (parse_lineage_dist of vdjer_amd/annot.py) */
-static int lineage_dist_num(const char* s) {
-	const char* dot = strchr(s, '.');
-	const size_t wl = dot ? (size_t) (dot - s) : strlen(s), fl = dot ? strlen(dot + 1) : 0;
-	if (wl + fl == 0 || wl > 1 || fl > 4 || strspn(s, "0123456789") != wl || (dot && strspn(dot + 1, "0123456789") != fl)) return -1;
-	int v = wl ? (s[0] - '0') * 10000 : 0;
-	for (size_t k = 0, scale = 1000; k < fl; k++, scale /= 10) v += (dot[1 + k] - '0') * (int) scale;
-	return v <= 10000 ? v : -1;
-}
-
-/* the whole text as a decimal uint64: digits only, at least one, no overflow -> 0, or -1 */
-static int whole_u64(const char* s, uint64_t* out) {
-	uint64_t x = 0;
-	if (!s[0]) return -1;
-	for (; *s; s++) {
-		if (*s < '0' || *s > '9') return -1;
-		const uint64_t d = (uint64_t) (*s - '0');
-		if (x > (UINT64_MAX - d) / 10) return -1;
-		x = x * 10 + d;
-	}
-	*out = x;
-	return 0;
-}
-
-/* --v-regions: lines `name cdr1_start cdr1_end cdr2_start cdr2_end`, separated by tabs or blanks; '#' lines and blank lines are skipped
- * (read_v_regions of vdjer_amd/annot.py).  The names meet the germline records later (sel_run). */
-typedef struct vreg_line { char* name; int32_t iv[4]; } vreg_line;
-
-static int split_fields(char* line, char** f, int max) {
-	int nf = 0;
-	for (char* t = strtok(line, " \t\r\n"); t; t = strtok(NULL, " \t\r\n")) { if (nf < max) f[nf] = t; nf++; }
-	return nf;
-}
-
-static int read_v_regions(const char* path, vreg_line** out, size_t* n_out) {
-	FILE* fp = fopen(path, "r");
-	if (!fp) { fprintf(stderr, "--v-regions: cannot read %s\n", path); return -1; }
-	char* line = NULL;
-	size_t lcap = 0, n = 0, cap = 0, no = 0;
-	vreg_line* v = NULL;
-	int rc = 0;
-	while (!rc && getline(&line, &lcap, fp) >= 0) {
-		no++;
-		char* f[5];
-		const int nf = split_fields(line, f, 5);
-		if (!nf || f[0][0] == '#') continue;
-		uint64_t x[4] = {0, 0, 0, 0};
-		int bad = nf != 5;
-		for (int k = 0; !bad && k < 4; k++) bad = whole_u64(f[1 + k], &x[k]) || x[k] > 2147483647u;
-		if (bad) { fprintf(stderr, "--v-regions: %s line %zu: expected `name cdr1_start cdr1_end cdr2_start cdr2_end` with whole numbers\n", path, no); rc = -1; break; }
-		for (int k = 0; k < 4; k += 2)
-			if (x[k] > x[k + 1] || (x[k] == 0 && x[k + 1] != 0)) {
-				fprintf(stderr, "--v-regions: %s line %zu: the interval %llu .. %llu (1 <= start <= end, or 0 0)\n", path, no, (unsigned long long) x[k], (unsigned long long) x[k + 1]);
-				rc = -1;
-			}
-		for (size_t q = 0; !rc && q < n; q++)
-			if (!strcmp(v[q].name, f[0])) { fprintf(stderr, "--v-regions: %s line %zu: the name %s is given twice\n", path, no, f[0]); rc = -1; }
-		if (rc) break;
-		if (n + 1 > cap) { cap = cap ? 2 * cap : 256; v = (vreg_line*) realloc(v, cap * sizeof *v); }
-		v[n].name = strdup(f[0]);
-		for (int k = 0; k < 4; k++) v[n].iv[k] = (int32_t) x[k];
-		n++;
-	}
-	free(line);
-	fclose(fp);
-	*out = v;
-	*n_out = n;
-	return rc;
-}
-
-/* --targeting: exactly 1,024 lines `<5-mer> <wA> <wC> <wG> <wT>`, each 5-mer over ACGT once, whole decimal numbers below 2^32; '#' lines and
- * blank lines are skipped (read_targeting of vdjer_amd/annot.py) -> uint32 [1024][4] */
-static int read_targeting(const char* flag, const char* path, uint32_t** out) {
-	FILE* fp = fopen(path, "r");
-	if (!fp) { fprintf(stderr, "%s: cannot read %s\n", flag, path); return -1; }
-	uint32_t* w = (uint32_t*) calloc(4096, sizeof(uint32_t));
-	unsigned char* seen = (unsigned char*) calloc(1024, 1);
-	char* line = NULL;
-	size_t lcap = 0, no = 0, got = 0;
-	int rc = 0;
-	while (getline(&line, &lcap, fp) >= 0) {
-		no++;
-		char* f[5];
-		const int nf = split_fields(line, f, 5);
-		if (!nf || f[0][0] == '#') continue;
-		uint64_t x[4] = {0, 0, 0, 0};
-		int bad = nf != 5 || strlen(f[0]) != 5 || strspn(f[0], "ACGT") != 5;
-		for (int k = 0; !bad && k < 4; k++) bad = whole_u64(f[1 + k], &x[k]) || x[k] > 4294967295ull;
-		if (bad) { fprintf(stderr, "%s: %s line %zu: expected `<5-mer over ACGT> <wA> <wC> <wG> <wT>` with whole numbers below 2^32\n", flag, path, no); rc = -1; break; }
-		int idx = 0;
-		for (int k = 0; k < 5; k++) idx = 4 * idx + (int) (strchr("ACGT", f[0][k]) - "ACGT");
-		if (seen[idx]) { fprintf(stderr, "%s: %s line %zu: the 5-mer %s is given twice\n", flag, path, no, f[0]); rc = -1; break; }
-		seen[idx] = 1;
-		got++;
-		for (int k = 0; k < 4; k++) w[4 * idx + k] = (uint32_t) x[k];
-	}
-	if (!rc && got != 1024) { fprintf(stderr, "%s: %s holds %zu 5-mers, expected every one of the 1024 once\n", flag, path, got); rc = -1; }
-	free(line);
-	free(seen);
-	fclose(fp);
-	if (rc) { free(w); w = NULL; }
-	*out = w;
-	return rc;
-}
-
-/* params.c:214-298: positional "--flag value" pairs; unknown flags only warn */
-static int parse(int argc, char** argv, cli* c) {
-	memset(c, 0, sizeof *c);
-	vdjh_default_params(&c->hp);
-	c->anchor_mismatches = 4;
-	c->threads = 1;
-	c->gpus = 1;
-	for (int i = 1; i < argc; i += 2) {
-		const char* a = argv[i];
-		if (!strcmp(a, "--help")) { usage(); exit(0); }
-		if (!strcmp(a, "--d-calls")) { c->d_calls = 1; i--; continue; }      /* (the one flag without a value) */
-		if (i + 1 >= argc) { fprintf(stderr, "Missing value for param: %s\n", a); usage(); return -1; }
-		const char* v = argv[i + 1];
-		if (!strcmp(a, "--in")) c->in = v;
-		else if (!strcmp(a, "--chain")) {
-			if (vdjh_set_chain(&c->hp, v)) { fprintf(stderr, "%s\n", vdjh_last_error()); return -1; }
-			c->have_chain = 1;
-			const char* vr = !strcmp(v, "IGH") ? "chr14:105566277-106879844" : !strcmp(v, "IGL") ? "chr22:22026076-22922913" : "chr2:89851758-90235368";
-			const char* cr = !strcmp(v, "IGH") ? "chr14:105566277-105939754" : !strcmp(v, "IGL") ? "chr22:22895375-22922913" : "chr2:88857361-88857683";
-			snprintf(c->v_region, sizeof c->v_region, "%s", vr);
-			snprintf(c->c_region, sizeof c->c_region, "%s", cr);
-		}
-		else if (!strcmp(a, "--ref-dir")) {
-			snprintf(c->v_anchors, sizeof c->v_anchors, "%s/v_index", v);
-			snprintf(c->j_anchors, sizeof c->j_anchors, "%s/j_index", v);
-			snprintf(c->source_sim_file, sizeof c->source_sim_file, "%s/v_region.fa", v);
-			snprintf(c->vdj_fasta, sizeof c->vdj_fasta, "%s/ig_vdj.fa", v);
-			c->have_ref = 1;
-		}
-		else if (!strcmp(a, "--mf")) c->hp.min_node_freq = atoi(v);
-		else if (!strcmp(a, "--mq")) c->hp.min_base_quality = atoi(v);
-		else if (!strcmp(a, "--mcs")) c->hp.min_contig_score = (float) atof(v);
-		else if (!strcmp(a, "--t")) c->threads = atoi(v);
-		else if (!strcmp(a, "--gpus")) c->gpus = atoi(v);
-		else if (!strcmp(a, "--quant")) c->quant = v;
-		else if (!strcmp(a, "--quant-boot")) c->quant_boot_s = v;
-		else if (!strcmp(a, "--quant-seed")) c->quant_seed_s = v;
-		else if (!strcmp(a, "--airr")) c->airr = v;
-		else if (!strcmp(a, "--cfa")) c->cfa = v;
-		else if (!strcmp(a, "--isotypes")) c->isotypes = v;
-		else if (!strcmp(a, "--clones")) c->clones = v;
-		else if (!strcmp(a, "--sample")) c->sample = v;
-		else if (!strcmp(a, "--total-count")) c->total_count = v;
-		else if (!strcmp(a, "--lineages")) c->lineages = v;
-		else if (!strcmp(a, "--lineage-dist")) c->lineage_dist = v;
-		else if (!strcmp(a, "--lineage-model")) c->lin_model = v;
-		else if (!strcmp(a, "--lineage-symmetry")) c->lin_symmetry = v;
-		else if (!strcmp(a, "--lineage-threshold")) c->lin_threshold = v;
-		else if (!strcmp(a, "--lineage-link")) c->lin_link = v;
-		else if (!strcmp(a, "--trees")) c->trees = v;
-		else if (!strcmp(a, "--trees-nj")) c->trees_nj = v;
-		else if (!strcmp(a, "--trees-newick")) c->trees_newick = v;
-		else if (!strcmp(a, "--trees-mp")) c->trees_mp = v;
-		else if (!strcmp(a, "--trees-mp-newick")) c->trees_mp_newick = v;
-		else if (!strcmp(a, "--tree-support")) c->tree_support = v;
-		else if (!strcmp(a, "--tree-seed")) c->tree_seed = v;
-		else if (!strcmp(a, "--mutations")) c->mutations = v;
-		else if (!strcmp(a, "--diversity")) c->diversity = v;
-		else if (!strcmp(a, "--diversity-depth")) c->div_depth_s = v;
-		else if (!strcmp(a, "--diversity-boot")) c->div_boot_s = v;
-		else if (!strcmp(a, "--diversity-seed")) c->div_seed_s = v;
-		else if (!strcmp(a, "--selection")) c->selection = v;
-		else if (!strcmp(a, "--v-regions")) c->v_regions = v;
-		else if (!strcmp(a, "--selection-combine")) c->sel_combine = v;
-		else if (!strcmp(a, "--selection-test")) c->sel_test = v;
-		else if (!strcmp(a, "--targeting")) c->targeting = v;
-		else if (!strcmp(a, "--targeting-model")) c->tgt_model = v;
-		else if (!strcmp(a, "--targeting-class")) c->tgt_class = v;
-		else if (!strcmp(a, "--targeting-min-sub")) c->tgt_min_sub_s = v;
-		else if (!strcmp(a, "--targeting-min-mut")) c->tgt_min_mut_s = v;
-		else if (!strcmp(a, "--targeting-counts")) c->tgt_counts = v;
-		else if (!strcmp(a, "--consensus")) c->consensus = v;
-		else if (!strcmp(a, "--consensus-min-freq")) c->cons_min_freq = v;
-		else if (!strcmp(a, "--vf")) snprintf(c->v_anchors, sizeof c->v_anchors, "%s", v);
-		else if (!strcmp(a, "--jf")) snprintf(c->j_anchors, sizeof c->j_anchors, "%s", v);
-		else if (!strcmp(a, "--am")) c->anchor_mismatches = atoi(v);
-		else if (!strcmp(a, "--miw")) c->hp.vj_min_win = atoi(v);
-		else if (!strcmp(a, "--maw")) c->hp.vj_max_win = atoi(v);
-		else if (!strcmp(a, "--jc")) c->hp.j_conserved = v[0];
-		else if (!strcmp(a, "--ws")) c->hp.window_span = atoi(v);
-		else if (!strcmp(a, "-jext")) c->hp.j_extension = atoi(v);        /* sic: params.c:262 */
-		else if (!strcmp(a, "--vdjf")) snprintf(c->vdj_fasta, sizeof c->vdj_fasta, "%s", v);
-		else if (!strcmp(a, "--vr")) snprintf(c->v_region, sizeof c->v_region, "%s", v);
-		else if (!strcmp(a, "--cr")) snprintf(c->c_region, sizeof c->c_region, "%s", v);
-		else if (!strcmp(a, "--ins")) c->hp.insert_len = atoi(v);
-		else if (!strcmp(a, "--rf")) c->hp.read_filter_floor = atoi(v);
-		else if (!strcmp(a, "--k")) c->hp.k = atoi(v);
-		else if (!strcmp(a, "--rms")) snprintf(c->source_sim_file, sizeof c->source_sim_file, "%s", v);
-		else if (!strcmp(a, "--vk")) c->hp.vregion_kmer_size = atoi(v);
-		else if (!strcmp(a, "--mrs")) c->hp.min_source_homology_score = atoi(v);
-		else if (!strcmp(a, "--rs")) c->hp.filter_read_span = atoi(v);
-		else if (!strcmp(a, "--ms")) c->hp.filter_mate_span = atoi(v);
-		else if (!strcmp(a, "--e0")) c->hp.eval_start = atoi(v);
-		else if (!strcmp(a, "--e1")) c->hp.eval_stop = atoi(v);
-		else if (!strcmp(a, "--wo")) c->hp.window_overlap_check_size = atoi(v);
-		else fprintf(stderr, "Invalid param: %s\n", a);
-	}
-	int ok = 1;       /* validate_params, params.c:143-212 */
-	if (!c->in) { fprintf(stderr, "Input must be specified\n"); ok = 0; }
-	else if (!file_exists(c->in)) { fprintf(stderr, "Could not find input file: %s\n", c->in); ok = 0; }
-	if (!c->v_anchors[0]) { fprintf(stderr, "V anchor file must be specified\n"); ok = 0; }
-	else if (!file_exists(c->v_anchors)) { fprintf(stderr, "Could not locate v_index file: %s\n", c->v_anchors); ok = 0; }
-	if (!c->j_anchors[0]) { fprintf(stderr, "J anchor file must be specified\n"); ok = 0; }
-	else if (!file_exists(c->j_anchors)) { fprintf(stderr, "Could not locate j_index file: %s\n", c->j_anchors); ok = 0; }
-	if (!c->source_sim_file[0]) { fprintf(stderr, "source_sim_file file must be specified\n"); ok = 0; }
-	if (c->hp.j_conserved != 'W' && c->hp.j_conserved != 'F') { fprintf(stderr, "Conserved J AA must be W or F: %c\n", c->hp.j_conserved); ok = 0; }
-	if (c->hp.insert_len <= 0) { fprintf(stderr, "insert_len must be specified and > 0\n"); ok = 0; }
-	/* (vdjx_vregion_load's limit, said here: before the input is read, let alone a pool loaded) */
-	if (c->hp.vregion_kmer_size < 2 || c->hp.vregion_kmer_size > 16) { fprintf(stderr, "--vk: vregion k-mer size %d outside [2,16]\n", c->hp.vregion_kmer_size); ok = 0; }
-	c->qb_b = 0;
-	c->qb_seed = 1;
-	if (c->quant_boot_s && !c->quant) { fprintf(stderr, "--quant-boot bootstraps the --quant table: it needs --quant <file>\n"); ok = 0; }
-	if (c->quant_seed_s && !c->quant_boot_s) { fprintf(stderr, "--quant-seed is the seed of the --quant-boot replicates: it needs --quant-boot <B>\n"); ok = 0; }
-	if (c->quant_boot_s) {
-		uint64_t b = 0;
-		if (whole_u64(c->quant_boot_s, &b) || b < 1 || b > 1024) { fprintf(stderr, "--quant-boot must be a whole decimal number in 1 .. 1024: %s\n", c->quant_boot_s); ok = 0; }
-		else c->qb_b = (uint32_t) b;
-	}
-	if (c->quant_seed_s && whole_u64(c->quant_seed_s, &c->qb_seed)) {
-		fprintf(stderr, "--quant-seed must be a whole decimal number below 2^64: %s\n", c->quant_seed_s);
-		ok = 0;
-	}
-	if (c->d_calls && !c->airr) { fprintf(stderr, "--d-calls adds the D call to the --airr table: it needs --airr <file>\n"); ok = 0; }
-	if (c->isotypes && !c->cfa) { fprintf(stderr, "--isotypes needs the constant-region sequences: --cfa <fasta>\n"); ok = 0; }
-	if (c->cfa) {
-		FILE* fp = fopen(c->cfa, "r");
-		if (!fp) { fprintf(stderr, "--cfa: cannot read the constant-region FASTA %s\n", c->cfa); ok = 0; }
-		else fclose(fp);
-	}
-	if (c->total_count && (!c->total_count[0] || strspn(c->total_count, "0123456789") != strlen(c->total_count))) {
-		fprintf(stderr, "--total-count must be a whole decimal number: %s\n", c->total_count);
-		ok = 0;
-	}
-	c->lin_num = 1500;
-	c->lin_den = 10000;
-	if (c->lineage_dist && !c->lineages) { fprintf(stderr, "--lineage-dist is the threshold of the --lineages table: it needs --lineages <file>\n"); ok = 0; }
-	if (c->lineage_dist && (c->lin_num = lineage_dist_num(c->lineage_dist)) < 0) {
-		fprintf(stderr, "--lineage-dist must be a decimal in [0, 1] with at most four digits after the point: %s\n", c->lineage_dist);
-		ok = 0;
-	}
-	c->lin_sym = 0;
-	if (c->lin_model && !c->lineages) { fprintf(stderr, "--lineage-model is the distance model of the --lineages table: it needs --lineages <file>\n"); ok = 0; }
-	if (c->lin_symmetry && !c->lin_model) { fprintf(stderr, "--lineage-symmetry is the symmetry of the --lineage-model distance: it needs --lineage-model <file>\n"); ok = 0; }
-	if (c->lin_symmetry) {
-		if (!strcmp(c->lin_symmetry, "avg")) c->lin_sym = 0;
-		else if (!strcmp(c->lin_symmetry, "min")) c->lin_sym = 1;
-		else { fprintf(stderr, "--lineage-symmetry must be avg (both directions added) or min (twice the cheaper): %s\n", c->lin_symmetry); ok = 0; }
-	}
-	if (c->lin_model && c->lineages) {
-		uint32_t* w = NULL;
-		if (read_targeting("--lineage-model", c->lin_model, &w)) ok = 0;
-		else {
-			c->lin_table = (uint16_t*) calloc(4096, sizeof(uint16_t));
-			if (vdjx_lineage_distance_table(w, c->lin_table, &c->lin_ti)) { fprintf(stderr, "--lineage-model: %s\n", vdjx_last_error()); ok = 0; }
-			free(w);
-		}
-	}
-	if (c->lin_threshold && !c->lineages) { fprintf(stderr, "--lineage-threshold chooses the threshold of the --lineages table: it needs --lineages <file>\n"); ok = 0; }
-	c->lin_linkage = 0;
-	if (c->lin_link && !c->lineages) { fprintf(stderr, "--lineage-link is the linkage of the --lineages table: it needs --lineages <file>\n"); ok = 0; }
-	if (c->lin_link) {
-		if (!strcmp(c->lin_link, "single")) c->lin_linkage = 0;
-		else if (!strcmp(c->lin_link, "complete")) c->lin_linkage = 1;
-		else if (!strcmp(c->lin_link, "average")) c->lin_linkage = 2;
-		else { fprintf(stderr, "--lineage-link must be single, complete or average: %s\n", c->lin_link); ok = 0; }
-	}
-	if (c->trees && !c->lineages) { fprintf(stderr, "--trees writes the tree inside every lineage of the --lineages table: it needs --lineages <file>\n"); ok = 0; }
-	if (c->trees_nj && !c->lineages) { fprintf(stderr, "--trees-nj writes the neighbour-joining tree inside every lineage of the --lineages table: it needs --lineages <file>\n"); ok = 0; }
-	if (c->trees_newick && !c->trees_nj) { fprintf(stderr, "--trees-newick writes the trees of --trees-nj as Newick lines: it needs --trees-nj <file>\n"); ok = 0; }
-	if (c->trees_mp && !c->lineages) { fprintf(stderr, "--trees-mp writes the maximum-parsimony tree inside every lineage of the --lineages table: it needs --lineages <file>\n"); ok = 0; }
-	if (c->trees_mp_newick && !c->trees_mp) { fprintf(stderr, "--trees-mp-newick writes the trees of --trees-mp as Newick lines: it needs --trees-mp <file>\n"); ok = 0; }
-	c->ts_b = 0;
-	c->ts_seed = 1;
-	if (c->tree_support && !c->trees) { fprintf(stderr, "--tree-support adds the support column to the --trees table: it needs --trees <file>\n"); ok = 0; }
-	if (c->tree_seed && !c->tree_support) { fprintf(stderr, "--tree-seed is the seed of the --tree-support replicates: it needs --tree-support <B>\n"); ok = 0; }
-	if (c->tree_support) {
-		uint64_t b = 0;
-		if (whole_u64(c->tree_support, &b) || b < 1 || b > 1024) { fprintf(stderr, "--tree-support must be a whole decimal number in 1 .. 1024: %s\n", c->tree_support); ok = 0; }
-		else c->ts_b = (uint32_t) b;
-	}
-	if (c->tree_seed && whole_u64(c->tree_seed, &c->ts_seed)) {
-		fprintf(stderr, "--tree-seed must be a whole decimal number below 2^64: %s\n", c->tree_seed);
-		ok = 0;
-	}
-	c->div_depth = 0;
-	c->div_boot = 200;
-	c->div_seed = 1;
-	if (c->diversity && !c->lineages) { fprintf(stderr, "--diversity is the diversity of the lineages of the --lineages table: it needs --lineages <file>\n"); ok = 0; }
-	if (c->diversity && !c->quant && !c->clones) {
-		fprintf(stderr, "--diversity weighs the lineages by the quant step's expected counts: it needs --quant <file> or --clones <file>\n");
-		ok = 0;
-	}
-	if (c->div_depth_s && !c->diversity) { fprintf(stderr, "--diversity-depth is the draws of a --diversity replicate: it needs --diversity <file>\n"); ok = 0; }
-	if (c->div_boot_s && !c->diversity) { fprintf(stderr, "--diversity-boot is the number of --diversity replicates: it needs --diversity <file>\n"); ok = 0; }
-	if (c->div_seed_s && !c->diversity) { fprintf(stderr, "--diversity-seed is the seed of the --diversity replicates: it needs --diversity <file>\n"); ok = 0; }
-	if (c->div_depth_s) {
-		uint64_t x = 0;
-		if (whole_u64(c->div_depth_s, &x) || x < 1 || x > 2147483647u) { fprintf(stderr, "--diversity-depth must be a whole decimal number in 1 .. 2147483647: %s\n", c->div_depth_s); ok = 0; }
-		else c->div_depth = (uint32_t) x;
-	}
-	if (c->div_boot_s) {
-		uint64_t x = 0;
-		if (whole_u64(c->div_boot_s, &x) || x < 1 || x > 4096) { fprintf(stderr, "--diversity-boot must be a whole decimal number in 1 .. 4096: %s\n", c->div_boot_s); ok = 0; }
-		else c->div_boot = (uint32_t) x;
-	}
-	if (c->div_seed_s && whole_u64(c->div_seed_s, &c->div_seed)) {
-		fprintf(stderr, "--diversity-seed must be a whole decimal number below 2^64: %s\n", c->div_seed_s);
-		ok = 0;
-	}
-	if (c->v_regions && !c->selection) { fprintf(stderr, "--v-regions is the region map of the --selection table: it needs --selection <file>\n"); ok = 0; }
-	if (c->targeting && !c->selection) { fprintf(stderr, "--targeting is the targeting model of the --selection table: it needs --selection <file>\n"); ok = 0; }
-	if (c->sel_combine && strcmp(c->sel_combine, "shared") && strcmp(c->sel_combine, "mean")) { fprintf(stderr, "--selection-combine must be shared or mean: %s\n", c->sel_combine); ok = 0; }
-	if (c->sel_combine && !c->selection) { fprintf(stderr, "--selection-combine is how the --selection table combines the members of a row: it needs --selection <file>\n"); ok = 0; }
-	if (c->sel_test && !c->selection) { fprintf(stderr, "--selection-test compares the densities of the --selection table: it needs --selection <file>\n"); ok = 0; }
-	if (c->sel_test && !c->v_regions) { fprintf(stderr, "--selection-test compares the cdr rows with the fwr rows: it needs --v-regions <file>\n"); ok = 0; }
-	c->sel_mean = c->sel_combine && !strcmp(c->sel_combine, "mean");
-	if (c->v_regions && c->selection && read_v_regions(c->v_regions, &c->regs, &c->nregs)) ok = 0;
-	if (c->targeting && c->selection && read_targeting("--targeting", c->targeting, &c->weight)) ok = 0;
-	c->cons_num = 6000;
-	if (c->consensus && !c->lineages) { fprintf(stderr, "--consensus is the consensus of every lineage of the --lineages table: it needs --lineages <file>\n"); ok = 0; }
-	if (c->cons_min_freq && !c->consensus) { fprintf(stderr, "--consensus-min-freq is the threshold of the --consensus table: it needs --consensus <file>\n"); ok = 0; }
-	if (c->cons_min_freq && (c->cons_num = lineage_dist_num(c->cons_min_freq)) < 0) {
-		fprintf(stderr, "--consensus-min-freq must be a decimal in [0, 1] with at most four digits after the point: %s\n", c->cons_min_freq);
-		ok = 0;
-	}
-	c->tgt_cls = 0;
-	c->tgt_min_sub = 50;
-	c->tgt_min_mut = 500;
-	if (c->tgt_class && !c->tgt_model) { fprintf(stderr, "--targeting-class is the mutation class of the --targeting-model file: it needs --targeting-model <file>\n"); ok = 0; }
-	if (c->tgt_min_sub_s && !c->tgt_model) { fprintf(stderr, "--targeting-min-sub is a threshold of the --targeting-model file: it needs --targeting-model <file>\n"); ok = 0; }
-	if (c->tgt_min_mut_s && !c->tgt_model) { fprintf(stderr, "--targeting-min-mut is a threshold of the --targeting-model file: it needs --targeting-model <file>\n"); ok = 0; }
-	if (c->tgt_counts && !c->tgt_model) { fprintf(stderr, "--targeting-counts is the counts behind the --targeting-model file: it needs --targeting-model <file>\n"); ok = 0; }
-	if (c->tgt_class) {
-		if (!strcmp(c->tgt_class, "s")) c->tgt_cls = 0;
-		else if (!strcmp(c->tgt_class, "rs")) c->tgt_cls = 1;
-		else { fprintf(stderr, "--targeting-class must be s (silent changes only) or rs (silent and replacement): %s\n", c->tgt_class); ok = 0; }
-	}
-	if (c->tgt_min_sub_s && (whole_u64(c->tgt_min_sub_s, &c->tgt_min_sub) || c->tgt_min_sub < 1 || c->tgt_min_sub > 4294967295ull)) {
-		fprintf(stderr, "--targeting-min-sub must be a whole decimal number in 1 .. 4294967295: %s\n", c->tgt_min_sub_s);
-		ok = 0;
-	}
-	if (c->tgt_min_mut_s && (whole_u64(c->tgt_min_mut_s, &c->tgt_min_mut) || c->tgt_min_mut < 1 || c->tgt_min_mut > 4294967295ull)) {
-		fprintf(stderr, "--targeting-min-mut must be a whole decimal number in 1 .. 4294967295: %s\n", c->tgt_min_mut_s);
-		ok = 0;
-	}
-	if (!ok) { usage(); return -1; }
-	if (c->hp.min_base_quality >= 255) c->hp.min_base_quality = 254;      /* A2:1514-1516 */
-	return 0;
-}
 
 typedef struct { int device; vdjx_ctx* gx; int rc; char err[512]; } init_job;
 static void* init_thread(void* p) {
@@ -861,60 +356,46 @@ static int load_vregion(const char* path, char*** lines, size_t* n) {
 /* hooks onto libvdjx                                                                          */
 /* ------------------------------------------------------------------------------------------ */
 typedef struct {
-	vdjx_ctx* gx; const vdjh_params* p; vdjx_mgpu* mg;
-	const char* quant;                  /* --quant <file>: the table is written after the SAM body */
-	int quant_done;
+	vdjx_ctx* gx; vdjx_mgpu* mg;
+	const cli* c;                       /* the options */
+	int tables_ran;                     /* the SAM body hook ran and tables() ended well (it is called at most once: only when there is a contig) */
 	vdjx_quant_info qi;
-	double* qcnt;                       /* its counts (the --airr table's expected_count) */
-	uint32_t qb_b; uint64_t qb_seed;    /* --quant-boot <B> --quant-seed <s>: the bootstrap (0: none) */
-	double* qboot;                      /* its qb_b x n replicate counts, replicate-major (the --lineages table's clone_count_sd) */
+	double* qcnt;                       /* --quant: its counts (the --airr table's expected_count) */
+	double* qboot;                      /* --quant-boot: its qb_b x n replicate counts, replicate-major (the --lineages table's clone_count_sd) */
 	vdjx_quant_boot_info qbi;
-	const char* airr;                   /* --airr <file>: written after the SAM body (and the quant table) */
-	const char* vdjf;
-	int airr_done;
 	size_t a_contigs, a_v, a_j, a_prod, a_trunc, a_skip_d, a_skip_other;
-	int d_calls;                        /* --d-calls: the D set (the class-D records of vdjf), the windows and the D hits (dcall_run) */
-	struct germ_set* dset; vdjx_annot_hit* hd;
+	struct germ_set* dset; vdjx_annot_hit* hd;          /* --d-calls: the D set (the class-D records of the germline FASTA) and the D hits (dcall_run) */
 	size_t d_contigs, d_windows, d_over, d_called;
 	/* --isotypes / --clones: what the steps above and vdjx_isotype found is kept until the last table is written */
-	const char *cfa, *isotypes, *clones, *sample, *total_count;
 	struct germ_set* germ; vdjx_annot_hit *hv, *hj;      /* the germline records and the V / J hits (annot_run) */
 	struct germ_set* cst; vdjx_annot_hit* hc;            /* the constant records and the isotype hits (iso_run) */
-	int iso_done, clones_done;
 	size_t i_contigs, i_called, c_rows, c_clusters;
 	/* --lineages: the clone of every contig (lineage_run; -1: not eligible), kept for the --airr table's clone_id */
-	const char* lineages; int lin_num, lin_den, lin_done;
-	const uint16_t* lin_table; int lin_sym; unsigned long long lin_walked;      /* --lineage-model: the distance table (NULL: Hamming), its symmetry, the pairs walked */
+	int lin_num;                        /* the threshold's numerator: --lineage-dist's, until --lineage-threshold finds its own */
+	unsigned long long lin_walked;      /* --lineage-model: the pairs walked */
 	int32_t* lin_clone; vdjx_lineage_info li;
-	int lin_linkage; vdjx_lineage_link_info lki;      /* --lineage-link: 0 single (the two calls above), 1 complete, 2 average (vdjx_lineage_link) and what it reports */
-	const char* lin_thr; vdjx_threshold_info thi; int thr_fallback, thr_passes;    /* --lineage-threshold: the file, what was found, the --lineage-dist numerator it stands in for, the pair passes made */
+	vdjx_lineage_link_info lki;         /* --lineage-link: what vdjx_lineage_link reports */
+	vdjx_threshold_info thi; int thr_fallback, thr_passes;    /* --lineage-threshold: what was found, the --lineage-dist numerator it stands in for, the pair passes made */
 	size_t l_contigs, l_eligible;
-	/* --trees: the tree inside every lineage (tree_run, after lineage_run) */
-	const char* trees; vdjx_tree_info ti;
-	/* --trees-nj, --trees-newick: the neighbour-joining trees with inferred ancestors (tree_nj_run, after tree_run) */
-	const char *trees_nj, *trees_newick; vdjx_tree_nj_info tni;
-	/* --trees-mp, --trees-mp-newick: those trees after the search over nearest-neighbour interchanges (tree_mp_run, after tree_nj_run) */
-	const char *trees_mp, *trees_mp_newick; vdjx_tree_mp_info tmi;
-	/* --tree-support: the jackknife support of the trees' edges (tree_run) */
-	uint32_t ts_b; uint64_t ts_seed; vdjx_tree_support_info tsi;
+	vdjx_tree_info ti;                  /* --trees (tree_run, after lineage_run) */
+	vdjx_tree_nj_info tni;              /* --trees-nj (tree_nj_run, after tree_run) */
+	vdjx_tree_mp_info tmi;              /* --trees-mp (tree_mp_run, after tree_nj_run) */
+	vdjx_tree_support_info tsi;         /* --tree-support (tree_run) */
 	/* --mutations: the germline rows of every contig (mut_run), kept for the --airr table's two alignment cells */
-	const char* mutations; int mut_done;
 	uint64_t* mu_off; char *mu_seq, *mu_germ; vdjx_mut_info mi;
 	/* --diversity: the Hill curve of the lineages (diversity_run, after lineage_run) */
-	const char* diversity; uint32_t dv_depth, dv_boot; uint64_t dv_seed;
+	uint32_t dv_depth;                  /* --diversity-depth's, or (0) the total expected pairs once they are known */
 	vdjx_diversity_info dvi; uint64_t dv_weight; double dv_d0, dv_d1, dv_d2;
 	/* --selection: the selection strength of the V mutations (sel_run, after lineage_run) */
-	const char* selection; const struct vreg_line* regs; size_t nregs; const uint32_t* weight; int have_regs, sel_done;
 	vdjx_sel_info si; double sel_sigma[2]; size_t sel_unmatched;
-	int sel_mean; const char* sel_test; vdjx_selconv_info sci; double sel_msigma[2];      /* --selection-combine mean, --selection-test */
+	vdjx_selconv_info sci; double sel_msigma[2];      /* --selection-combine mean */
 	/* --targeting-model: the sample's own targeting model (tgt_run, after lineage_run) */
-	const char *tgt_model, *tgt_counts; int tgt_cls, tgt_done; uint64_t tgt_min_sub, tgt_min_mut;
 	vdjx_tgt_info tgi; unsigned tgt_levels[2][4];      /* [substitution, mutability][level 5, 3, 1, 0]: the 5-mers on it */
 	/* --consensus: the consensus of every lineage (cons_run, after lineage_run); the pseudo-contigs, their hits and first voters are kept for sel_run */
-	const char* consensus; int cons_num, cons_done;
 	vdjx_cons_info ci; uint32_t cs_largest;
 	size_t cs_units; int cs_plen; char* cs_pc; vdjx_annot_hit* cs_hv; vdjx_cons_unit* cs_un; size_t* cs_first;
 } hook_ud;
+
 
 static int h_root_score(void* ud, const char* kmers, size_t n, int k, int thr, uint8_t* out) {
 	hook_ud* u = (hook_ud*) ud;
@@ -925,7 +406,7 @@ static int h_root_score(void* ud, const char* kmers, size_t n, int k, int thr, u
 
 static int h_window_score(void* ud, const char* windows, size_t n, int len, uint8_t* valid) {
 	hook_ud* u = (hook_ud*) ud;
-	const vdjh_params* p = u->p;
+	const vdjh_params* p = &u->c->hp;
 	vdjx_cov_params cp = {p->eval_start, p->eval_stop, p->filter_read_span, p->filter_mate_span, p->insert_len, p->insert_len, p->read_filter_floor};
 	if (u->mg) {                              /* `--gpus N`: every rank maps the windows against its share of the pool */
 		const int rcm = vdjx_mgpu_window_score(u->mg, u->gx, windows, n, len, &cp, valid);
@@ -962,11 +443,11 @@ static int sam_records(void* ud, const char* const* ids, const char* contigs, si
 static int quant_table(hook_ud* u, const char* const* ids, const char* contigs, size_t n, int len) {
 	double* cnt = (double*) calloc(n + 1, sizeof(double));
 	const vdjx_quant_params qp = {10000, 1e-5};
-	const uint32_t B = u->quant ? u->qb_b : 0;
+	const uint32_t B = u->c->quant ? u->c->qb_b : 0;
 	double* st = NULL;                  /* the bootstrap's summary: mean, sd, lower, upper, n each */
 	int rc;
 	if (B) {
-		const vdjx_quant_boot_params bp = {(int) B, u->qb_seed};
+		const vdjx_quant_boot_params bp = {(int) B, u->c->qb_seed};
 		uint32_t* iters = (uint32_t*) calloc(B, sizeof(uint32_t));
 		free(u->qboot);
 		u->qboot = (double*) calloc((size_t) B * n + 1, sizeof(double));
@@ -976,9 +457,9 @@ static int quant_table(hook_ud* u, const char* const* ids, const char* contigs, 
 		if (!rc) vdjx_quant_boot_summary(u->qboot, B, n, st, st + n, st + 2 * n, st + 3 * n);
 	} else rc = vdjx_quant(u->gx, contigs, n, len, &qp, cnt, &u->qi);
 	if (rc) { fprintf(stderr, "%s: %s\n", B ? "vdjx_quant_boot" : "vdjx_quant", vdjx_last_error()); free(cnt); free(st); return rc; }
-	if (!u->quant) { free(u->qcnt); u->qcnt = cnt; u->quant_done = 1; return 0; }      /* (--clones alone: the counts, no table) */
-	FILE* fp = fopen(u->quant, "w");
-	if (!fp) { fprintf(stderr, "cannot write %s\n", u->quant); free(cnt); free(st); return -1; }
+	if (!u->c->quant) { free(u->qcnt); u->qcnt = cnt; return 0; }      /* (--clones alone: the counts, no table) */
+	FILE* fp = fopen(u->c->quant, "w");
+	if (!fp) { fprintf(stderr, "cannot write %s\n", u->c->quant); free(cnt); free(st); return -1; }
 	free(u->qcnt);
 	double sum = 0.0;
 	for (size_t i = 0; i < n; i++) sum += cnt[i];
@@ -992,8 +473,7 @@ static int quant_table(hook_ud* u, const char* const* ids, const char* contigs, 
 	}
 	free(st);
 	u->qcnt = cnt;
-	if (fclose(fp)) { fprintf(stderr, "cannot write %s\n", u->quant); return -1; }
-	u->quant_done = 1;
+	if (fclose(fp)) { fprintf(stderr, "cannot write %s\n", u->c->quant); return -1; }
 	return 0;
 }
 
@@ -1111,7 +591,7 @@ static long junction_at(const char* id, const char* s, int len, const char** jn_
 /* the V / J hits of every contig (vdjx_annotate against the germlines of ig_vdj.fa / --vdjf), kept for the tables */
 static int annot_run(hook_ud* u, const char* contigs, size_t n, int len) {
 	u->germ = (germ_set*) calloc(1, sizeof(germ_set));
-	if (germ_read(u->vdjf, u->germ, u->airr ? "--airr: cannot read the germline FASTA" : u->clones ? "--clones: cannot read the germline FASTA" : u->lineages ? "--lineages: cannot read the germline FASTA" : u->mutations ? "--mutations: cannot read the germline FASTA" : u->selection ? "--selection: cannot read the germline FASTA" : "--targeting-model: cannot read the germline FASTA")) return -1;
+	if (germ_read(u->c->vdj_fasta, u->germ, u->c->airr ? "--airr: cannot read the germline FASTA" : u->c->clones ? "--clones: cannot read the germline FASTA" : u->c->lineages ? "--lineages: cannot read the germline FASTA" : u->c->mutations ? "--mutations: cannot read the germline FASTA" : u->c->selection ? "--selection: cannot read the germline FASTA" : "--targeting-model: cannot read the germline FASTA")) return -1;
 	const germ_set* g = u->germ;
 	for (size_t r = 0; r < g->n; r++) {
 		if (g->cls[r] == 'V' || g->cls[r] == 'J') continue;
@@ -1122,7 +602,7 @@ static int annot_run(hook_ud* u, const char* contigs, size_t n, int len) {
 	const vdjx_annot_params ap = {2, 3, 5, 2, 40, 20};
 	int rc = vdjx_germline_load(u->gx, g->seqs, g->off, g->cls, g->n);
 	if (!rc && n) rc = vdjx_annotate(u->gx, contigs, n, len, &ap, u->hv, u->hj);
-	if (rc) fprintf(stderr, "%s: %s\n", u->airr ? "--airr" : u->clones ? "--clones" : u->lineages ? "--lineages" : u->mutations ? "--mutations" : u->selection ? "--selection" : "--targeting-model", vdjx_last_error());
+	if (rc) fprintf(stderr, "%s: %s\n", u->c->airr ? "--airr" : u->c->clones ? "--clones" : u->c->lineages ? "--lineages" : u->c->mutations ? "--mutations" : u->c->selection ? "--selection" : "--targeting-model", vdjx_last_error());
 	return rc;
 }
 
@@ -1189,16 +669,16 @@ static int airr_table(hook_ud* u, const char* const* ids, const char* contigs, s
 	const germ_set g = *u->germ;
 	const vdjx_annot_hit *hv = u->hv, *hj = u->hj;
 	int rc = 0;
-	FILE* fp = fopen(u->airr, "w");
-	if (!fp) { fprintf(stderr, "cannot write %s\n", u->airr); rc = -1; }
+	FILE* fp = fopen(u->c->airr, "w");
+	if (!fp) { fprintf(stderr, "cannot write %s\n", u->c->airr); rc = -1; }
 	if (fp) {
 		fputs("sequence_id\tsequence\trev_comp\tproductive\tv_call\td_call\tj_call\tsequence_alignment\tgermline_alignment\tjunction\tjunction_aa\t"
 		      "cdr3\tcdr3_aa\tvj_in_frame\tstop_codon\tv_cigar\td_cigar\tj_cigar\tv_score\tv_identity\tv_sequence_start\tv_sequence_end\t"
 		      "v_germline_start\tv_germline_end\tj_score\tj_identity\tj_sequence_start\tj_sequence_end\tj_germline_start\tj_germline_end", fp);
-		if (u->d_calls)
+		if (u->c->d_calls)
 			fputs("\td_score\td_identity\td_sequence_start\td_sequence_end\td_germline_start\td_germline_end\tnp1\tnp1_length\tnp2\tnp2_length", fp);
-		if (u->lineages) fputs("\tclone_id", fp);
-		fputs(u->quant ? "\texpected_count\n" : "\n", fp);
+		if (u->c->lineages) fputs("\tclone_id", fp);
+		fputs(u->c->quant ? "\texpected_count\n" : "\n", fp);
 		for (size_t i = 0; i < n; i++) {
 			const char* s = contigs + i * (size_t) len;
 			const vdjx_annot_hit *v = hv + i, *j = hj + i;
@@ -1221,10 +701,10 @@ static int airr_table(hook_ud* u, const char* const* ids, const char* contigs, s
 			fprintf(fp, "%s\t%.*s\tF\t%c\t", ids[i], len, s, prod ? 'T' : 'F');
 			put_call(fp, v, &g);
 			fputc('\t', fp);
-			if (u->d_calls) put_call(fp, u->hd + i, u->dset);
+			if (u->c->d_calls) put_call(fp, u->hd + i, u->dset);
 			fputc('\t', fp);
 			put_call(fp, j, &g);
-			if (u->mutations) {               /* mut_run's rows: the contig and its germline, column by column */
+			if (u->c->mutations) {               /* mut_run's rows: the contig and its germline, column by column */
 				const int cols = (int) (u->mu_off[i + 1] - u->mu_off[i]);
 				fprintf(fp, "\t%.*s\t%.*s\t", cols, cols ? u->mu_seq + u->mu_off[i] : "", cols, cols ? u->mu_germ + u->mu_off[i] : "");
 			} else fputs("\t\t\t", fp);
@@ -1236,19 +716,18 @@ static int airr_table(hook_ud* u, const char* const* ids, const char* contigs, s
 			fprintf(fp, "\t%c\t%c\t", inframe ? 'T' : 'F', stop ? 'T' : 'F');
 			put_cigar(fp, v, len);
 			fputc('\t', fp);
-			if (u->d_calls) put_cigar(fp, u->hd + i, len);
+			if (u->c->d_calls) put_cigar(fp, u->hd + i, len);
 			fputc('\t', fp);
 			put_cigar(fp, j, len);
 			put_hit(fp, v);
 			put_hit(fp, j);
-			if (u->d_calls) put_np(fp, s, v, u->hd + i, j);
-			if (u->lineages) { if (u->lin_clone[i] >= 0) fprintf(fp, "\tlin_%d", u->lin_clone[i] + 1); else fputc('\t', fp); }
-			if (u->quant) fprintf(fp, "\t%.2f", u->qcnt ? u->qcnt[i] : 0.0);
+			if (u->c->d_calls) put_np(fp, s, v, u->hd + i, j);
+			if (u->c->lineages) { if (u->lin_clone[i] >= 0) fprintf(fp, "\tlin_%d", u->lin_clone[i] + 1); else fputc('\t', fp); }
+			if (u->c->quant) fprintf(fp, "\t%.2f", u->qcnt ? u->qcnt[i] : 0.0);
 			fputc('\n', fp);
 		}
-		if (fclose(fp)) { fprintf(stderr, "cannot write %s\n", u->airr); rc = -1; }
+		if (fclose(fp)) { fprintf(stderr, "cannot write %s\n", u->c->airr); rc = -1; }
 	}
-	if (!rc) u->airr_done = 1;
 	return rc;
 }
 
@@ -1310,19 +789,19 @@ static void vq_gene_of(const vdjx_annot_hit* h, const germ_set* g, slist* out) {
 /* the isotype hits of every contig (vdjx_isotype against the records of --cfa), kept for the tables */
 static int iso_run(hook_ud* u, const char* contigs, size_t n, int len) {
 	u->cst = (germ_set*) calloc(1, sizeof(germ_set));
-	if (germ_read(u->cfa, u->cst, "--cfa: cannot read the constant-region FASTA")) return -1;
+	if (germ_read(u->c->cfa, u->cst, "--cfa: cannot read the constant-region FASTA")) return -1;
 	u->hc = (vdjx_annot_hit*) calloc(n + 1, sizeof(vdjx_annot_hit));
 	const vdjx_isotype_params ip = {2, 3, 5, 2, 48, 48};
 	int rc = vdjx_constant_load(u->gx, u->cst->seqs, u->cst->off, u->cst->n);
 	if (!rc && n) rc = vdjx_isotype(u->gx, contigs, n, len, &ip, u->hc, NULL);
-	if (rc) fprintf(stderr, "%s: %s\n", u->isotypes ? "--isotypes" : "--clones", vdjx_last_error());
+	if (rc) fprintf(stderr, "%s: %s\n", u->c->isotypes ? "--isotypes" : "--clones", vdjx_last_error());
 	for (size_t i = 0; !rc && i < n; i++) { u->i_contigs++; u->i_called += u->hc[i].gene >= 0; }
 	return rc;
 }
 
 static int isotypes_table(hook_ud* u, const char* const* ids, size_t n, int len) {
-	FILE* fp = fopen(u->isotypes, "w");
-	if (!fp) { fprintf(stderr, "cannot write %s\n", u->isotypes); return -1; }
+	FILE* fp = fopen(u->c->isotypes, "w");
+	if (!fp) { fprintf(stderr, "cannot write %s\n", u->c->isotypes); return -1; }
 	fputs("sequence_id\tisotype\tc_call\tc_score\tc_identity\tc_sequence_start\tc_sequence_end\tc_germline_start\tc_germline_end\tc_cigar\n", fp);
 	slist sub;
 	memset(&sub, 0, sizeof sub);
@@ -1337,8 +816,7 @@ static int isotypes_table(hook_ud* u, const char* const* ids, size_t n, int len)
 		fputc('\n', fp);
 	}
 	free(sub.s);
-	if (fclose(fp)) { fprintf(stderr, "cannot write %s\n", u->isotypes); return -1; }
-	u->iso_done = 1;
+	if (fclose(fp)) { fprintf(stderr, "cannot write %s\n", u->c->isotypes); return -1; }
 	return 0;
 }
 
@@ -1346,8 +824,8 @@ static int isotypes_table(hook_ud* u, const char* const* ids, size_t n, int len)
  * sample: a row per contig whose printed expected_count is >= 1, that has a V call and whose junction is found in it with a non-empty
  * translation; a cluster id per distinct (isotype, aa cdr3, vgene, jgene) in order of first appearance */
 static int clones_table(hook_ud* u, const char* const* ids, const char* contigs, size_t n, int len) {
-	FILE* fp = fopen(u->clones, "w");
-	if (!fp) { fprintf(stderr, "cannot write %s\n", u->clones); return -1; }
+	FILE* fp = fopen(u->c->clones, "w");
+	if (!fp) { fprintf(stderr, "cannot write %s\n", u->c->clones); return -1; }
 	fputs("sample\tsequence\tcdr3\texpected_counts\tseq_id\tisotype\tvregion_identity\taa_cdr3\tvgene\tjgene\ttotal_count\tcluster\n", fp);
 	slist sub, vg, jg;
 	memset(&sub, 0, sizeof sub); memset(&vg, 0, sizeof vg); memset(&jg, 0, sizeof jg);
@@ -1382,17 +860,16 @@ static int clones_table(hook_ud* u, const char* const* ids, const char* contigs,
 			if (nkeys + 1 > kcap) { kcap = kcap ? 2 * kcap : 64; keys = (char**) realloc(keys, kcap * sizeof(char*)); }
 			keys[nkeys++] = key;
 		} else free(key);
-		fprintf(fp, "%s\t%.*s\t%s\t%s\t%s\t%s\t", u->sample, len, s, jn, cnt, ids[i], iso);
+		fprintf(fp, "%s\t%.*s\t%s\t%s\t%s\t%s\t", u->c->sample, len, s, jn, cnt, ids[i], iso);
 		if (d > 0) fprintf(fp, "%.2f", 100.0 * ((double) v->matches / d)); else fputs("N/A", fp);
-		fprintf(fp, "\t%s\t%s\t%s\t%s\tcls_%zu\n", aa, sl_str(&vg), jgene, u->total_count ? u->total_count : "N/A", k + 1);
+		fprintf(fp, "\t%s\t%s\t%s\t%s\tcls_%zu\n", aa, sl_str(&vg), jgene, u->c->total_count ? u->c->total_count : "N/A", k + 1);
 		free(aa);
 		u->c_rows++;
 	}
 	u->c_clusters = nkeys;
 	for (size_t k = 0; k < nkeys; k++) free(keys[k]);
 	free(keys); free(sub.s); free(vg.s); free(jg.s);
-	if (fclose(fp)) { fprintf(stderr, "cannot write %s\n", u->clones); return -1; }
-	u->clones_done = 1;
+	if (fclose(fp)) { fprintf(stderr, "cannot write %s\n", u->c->clones); return -1; }
 	return 0;
 }
 
@@ -1401,25 +878,25 @@ static int clones_table(hook_ud* u, const char* const* ids, const char* contigs,
  * the index, by first appearance, of its (vgene, jgene) pair as --clones prints them.  A row per contig: clone_id lin_<k>, vgene, jgene,
  * junction_length, dist_nearest (the smallest non-zero distance inside the bucket over the length), clone_size and, when the quant step ran,
  * clone_expected_count: the sum of the members' expected_count as printed (two decimals each), so that the tables add up */
-/* one pair pass at u->lin_num / u->lin_den, under --lineage-link's linkage */
+/* one pair pass at u->lin_num / u->c->lin_den, under --lineage-link's linkage */
 static int lineage_pass(hook_ud* u, const char* cat, const uint64_t* off, const uint32_t* grp, size_t n, int32_t* near) {
-	const vdjx_lineage_params lp = {u->lin_num, u->lin_den};
-	const vdjx_lineage_model_params lmp = {u->lin_num, u->lin_den, u->lin_sym};
-	const vdjx_lineage_link_params lkp = {u->lin_num, u->lin_den, u->lin_sym, u->lin_linkage};
-	const int rc = u->lin_linkage ? vdjx_lineage_link(u->gx, cat, off, grp, n, &lkp, u->lin_table, u->lin_clone, near, &u->li, &u->lki)
-	             : u->lin_table   ? vdjx_lineage_model(u->gx, cat, off, grp, n, &lmp, u->lin_table, u->lin_clone, near, &u->li)
+	const vdjx_lineage_params lp = {u->lin_num, u->c->lin_den};
+	const vdjx_lineage_model_params lmp = {u->lin_num, u->c->lin_den, u->c->lin_sym};
+	const vdjx_lineage_link_params lkp = {u->lin_num, u->c->lin_den, u->c->lin_sym, u->c->lin_linkage};
+	const int rc = u->c->lin_linkage ? vdjx_lineage_link(u->gx, cat, off, grp, n, &lkp, u->c->lin_table, u->lin_clone, near, &u->li, &u->lki)
+	             : u->c->lin_table   ? vdjx_lineage_model(u->gx, cat, off, grp, n, &lmp, u->c->lin_table, u->lin_clone, near, &u->li)
 	                              : vdjx_lineage(u->gx, cat, off, grp, n, &lp, u->lin_clone, near, &u->li);
 	if (rc) fprintf(stderr, "--lineages: %s\n", vdjx_last_error());
 	return rc;
 }
 
 static int lineage_run(hook_ud* u, const char* const* ids, const char* contigs, size_t n, int len) {
-	FILE* fp = fopen(u->lineages, "w");
-	if (!fp) { fprintf(stderr, "cannot write %s\n", u->lineages); return -1; }
-	FILE* tfp = u->lin_thr ? fopen(u->lin_thr, "w") : NULL;
-	if (u->lin_thr && !tfp) { fprintf(stderr, "cannot write %s\n", u->lin_thr); fclose(fp); return -1; }
-	const int counted = u->quant || u->clones;
-	const uint32_t B = counted && u->qboot ? u->qb_b : 0;      /* --quant-boot: clone_count_sd */
+	FILE* fp = fopen(u->c->lineages, "w");
+	if (!fp) { fprintf(stderr, "cannot write %s\n", u->c->lineages); return -1; }
+	FILE* tfp = u->c->lin_threshold ? fopen(u->c->lin_threshold, "w") : NULL;
+	if (u->c->lin_threshold && !tfp) { fprintf(stderr, "cannot write %s\n", u->c->lin_threshold); fclose(fp); return -1; }
+	const int counted = u->c->quant || u->c->clones;
+	const uint32_t B = counted && u->qboot ? u->c->qb_b : 0;      /* --quant-boot: clone_count_sd */
 	char* cat = (char*) malloc(n * (size_t) VDJX_LINEAGE_MAXLEN + 1);
 	uint64_t* off = (uint64_t*) calloc(n + 1, sizeof(uint64_t));
 	uint32_t* grp = (uint32_t*) calloc(n + 1, sizeof(uint32_t));
@@ -1470,7 +947,7 @@ static int lineage_run(hook_ud* u, const char* const* ids, const char* contigs, 
 		uint32_t* hist = (uint32_t*) calloc(VDJX_THRESHOLD_GRID + 1, sizeof(uint32_t));
 		uint64_t* dens = (uint64_t*) calloc(VDJX_THRESHOLD_GRID + 1, sizeof(uint64_t));
 		for (size_t i = 0; i < n; i++) lens[i] = (uint32_t) (off[i + 1] - off[i]);
-		rc = vdjx_lineage_threshold(u->gx, near, lens, n, u->lin_table ? 2000u : 1u, &tp, hist, dens, NULL, &u->thi);
+		rc = vdjx_lineage_threshold(u->gx, near, lens, n, u->c->lin_table ? 2000u : 1u, &tp, hist, dens, NULL, &u->thi);
 		if (rc) fprintf(stderr, "--lineage-threshold: %s\n", vdjx_last_error());
 		if (!rc && u->thi.status == VDJX_THRESHOLD_FOUND && (int) u->thi.threshold != u->lin_num) {
 			u->lin_num = (int) u->thi.threshold;           /* (lin_den is 10000, the grid's unit) */
@@ -1490,9 +967,9 @@ static int lineage_run(hook_ud* u, const char* const* ids, const char* contigs, 
 		}
 		free(lens); free(hist); free(dens);
 	}
-	if (tfp && fclose(tfp)) { fprintf(stderr, "cannot write %s\n", u->lin_thr); rc = -1; }
-	if (!rc && u->lin_table) u->lin_walked = vdjx_stat(u->gx, "lineage_model_walked");
-	const double unit = u->lin_table ? 2000.0 : 1.0;      /* dist_nearest: in mean mismatches per base under a model */
+	if (tfp && fclose(tfp)) { fprintf(stderr, "cannot write %s\n", u->c->lin_threshold); rc = -1; }
+	if (!rc && u->c->lin_table) u->lin_walked = vdjx_stat(u->gx, "lineage_model_walked");
+	const double unit = u->c->lin_table ? 2000.0 : 1.0;      /* dist_nearest: in mean mismatches per base under a model */
 	if (!rc) {
 		size_t* size = (size_t*) calloc((size_t) u->li.clones + 1, sizeof(size_t));
 		double* sum = (double*) calloc((size_t) u->li.clones + 1, sizeof(double));
@@ -1533,8 +1010,7 @@ static int lineage_run(hook_ud* u, const char* const* ids, const char* contigs, 
 	for (size_t i = 0; i < n; i++) { free(vgs[i]); free(jgs[i]); }
 	for (size_t k = 0; k < nkeys; k++) free(keys[k]);
 	free(keys); free(vgs); free(jgs); free(vg.s); free(jg.s); free(cat); free(off); free(grp); free(near);
-	if (fclose(fp)) { fprintf(stderr, "cannot write %s\n", u->lineages); return -1; }
-	if (!rc) u->lin_done = 1;
+	if (fclose(fp)) { fprintf(stderr, "cannot write %s\n", u->c->lineages); return -1; }
 	return rc;
 }
 
@@ -1545,9 +1021,9 @@ static int lineage_run(hook_ud* u, const char* const* ids, const char* contigs, 
  * that is in no lineage.  --tree-support B: one more column, support, the share of B jackknife replicates whose tree has the edge to
  * parent_id (vdjx_tree_support on vdjx_tree's parents), empty for a root */
 static int tree_run(hook_ud* u, const char* const* ids, const char* contigs, size_t n, int len) {
-	FILE* fp = fopen(u->trees, "w");
-	if (!fp) { fprintf(stderr, "cannot write %s\n", u->trees); return -1; }
-	fprintf(fp, "sequence_id\tclone_id\tparent_id\tdist_parent\tdepth\tchildren\tv_mutations\twindow_start\twindow_length%s\n", u->ts_b ? "\tsupport" : "");
+	FILE* fp = fopen(u->c->trees, "w");
+	if (!fp) { fprintf(stderr, "cannot write %s\n", u->c->trees); return -1; }
+	fprintf(fp, "sequence_id\tclone_id\tparent_id\tdist_parent\tdepth\tchildren\tv_mutations\twindow_start\twindow_length%s\n", u->c->ts_b ? "\tsupport" : "");
 	int32_t* anchor = (int32_t*) calloc(n + 1, sizeof(int32_t));
 	uint32_t* prio = (uint32_t*) calloc(n + 1, sizeof(uint32_t));
 	int32_t* out = (int32_t*) calloc(4 * n + 1, sizeof(int32_t));
@@ -1570,8 +1046,8 @@ static int tree_run(hook_ud* u, const char* const* ids, const char* contigs, siz
 	}
 	int rc = vdjx_tree(u->gx, contigs, n, len, u->lin_clone, anchor, prio, parent, dist, depth, &u->ti);
 	if (rc) fprintf(stderr, "--trees: %s\n", vdjx_last_error());
-	if (!rc && u->ts_b) {
-		const vdjx_tree_support_params tp = {u->ts_b, u->ts_seed};
+	if (!rc && u->c->ts_b) {
+		const vdjx_tree_support_params tp = {u->c->ts_b, u->c->ts_seed};
 		rc = vdjx_tree_support(u->gx, contigs, n, len, u->lin_clone, anchor, parent, &tp, support, &u->tsi);
 		if (rc) fprintf(stderr, "--tree-support: %s\n", vdjx_last_error());
 	}
@@ -1580,17 +1056,17 @@ static int tree_run(hook_ud* u, const char* const* ids, const char* contigs, siz
 			if (parent[i] >= 0) kids[parent[i]]++;
 		for (size_t i = 0; i < n; i++) {
 			const int32_t k = u->lin_clone[i];
-			if (k < 0) { fprintf(fp, "%s\t\t\t\t\t\t\t\t%s\n", ids[i], u->ts_b ? "\t" : ""); continue; }
+			if (k < 0) { fprintf(fp, "%s\t\t\t\t\t\t\t\t%s\n", ids[i], u->c->ts_b ? "\t" : ""); continue; }
 			fprintf(fp, "%s\tlin_%d\t", ids[i], k + 1);
 			if (parent[i] >= 0) fprintf(fp, "%s\t%d", ids[parent[i]], dist[i]); else fputc('\t', fp);
 			fprintf(fp, "\t%d\t%zu\t%u\t%d\t%d", depth[i], kids[i], prio[i], anchor[i] - before[k], before[k] + after[k]);
-			if (u->ts_b && parent[i] >= 0) fprintf(fp, "\t%.4f", (double) support[i] / (double) u->ts_b);
-			else if (u->ts_b) fputc('\t', fp);
+			if (u->c->ts_b && parent[i] >= 0) fprintf(fp, "\t%.4f", (double) support[i] / (double) u->c->ts_b);
+			else if (u->c->ts_b) fputc('\t', fp);
 			fputc('\n', fp);
 		}
 	}
 	free(anchor); free(prio); free(out); free(before); free(after); free(kids);
-	if (fclose(fp)) { fprintf(stderr, "cannot write %s\n", u->trees); return -1; }
+	if (fclose(fp)) { fprintf(stderr, "cannot write %s\n", u->c->trees); return -1; }
 	return rc;
 }
 
@@ -1609,7 +1085,7 @@ static void nj_label(FILE* fp, size_t s, void* ud) {
 /* mp: --trees-mp, --trees-mp-newick instead -- vdjx_tree_mp from vdjx_tree_nj's tree (the model: tests/tree_mp_model.py); the same rows,
  * branch_length the node's mutations */
 static int tree_nodes_run(hook_ud* u, const char* const* ids, const char* contigs, size_t n, int len, int mp) {
-	const char *table = mp ? u->trees_mp : u->trees_nj, *lines = mp ? u->trees_mp_newick : u->trees_newick;
+	const char *table = mp ? u->c->trees_mp : u->c->trees_nj, *lines = mp ? u->c->trees_mp_newick : u->c->trees_newick;
 	const char *flag = mp ? "--trees-mp" : "--trees-nj", *flag_lines = mp ? "--trees-mp-newick" : "--trees-newick";
 	FILE* fp = fopen(table, "w");
 	if (!fp) { fprintf(stderr, "cannot write %s\n", table); return -1; }
@@ -1711,10 +1187,10 @@ static int32_t* mutation_limits(const char* const* ids, const char* contigs, siz
 }
 
 static int mut_run(hook_ud* u, const char* const* ids, const char* contigs, size_t n, int len) {
-	FILE* fp = fopen(u->mutations, "w");
-	if (!fp) { fprintf(stderr, "cannot write %s\n", u->mutations); return -1; }
+	FILE* fp = fopen(u->c->mutations, "w");
+	if (!fp) { fprintf(stderr, "cannot write %s\n", u->c->mutations); return -1; }
 	const germ_set g = *u->germ;
-	const vdjx_annot_hit* hd = u->d_calls ? u->hd : NULL;
+	const vdjx_annot_hit* hd = u->c->d_calls ? u->hd : NULL;
 	u->mu_off = (uint64_t*) calloc(n + 1, sizeof(uint64_t));
 	int32_t* lim = mutation_limits(ids, contigs, n, len);
 	vdjx_mut_row* rows = (vdjx_mut_row*) calloc(n + 1, sizeof(vdjx_mut_row));
@@ -1731,7 +1207,7 @@ static int mut_run(hook_ud* u, const char* const* ids, const char* contigs, size
 	if (!rc) {
 		fputs("sequence_id\tv_call\tj_call\tsequence_alignment\tgermline_alignment\tgermline_alignment_d_mask\tv_germline_codons\tmu_count_v_r\t"
 		      "mu_count_v_s\tmu_count_v_stop\tmu_count_v_na\tmu_freq_v\tmu_count_j", fp);
-		fputs(u->lineages ? "\tclone_id\n" : "\n", fp);
+		fputs(u->c->lineages ? "\tclone_id\n" : "\n", fp);
 		for (size_t i = 0; i < n; i++) {
 			const vdjx_mut_row* r = rows + i;
 			fprintf(fp, "%s\t", ids[i]);
@@ -1746,15 +1222,14 @@ static int mut_run(hook_ud* u, const char* const* ids, const char* contigs, size
 				if (r->v_codons) fprintf(fp, "%.4f", (double) (r->v_r + r->v_s) / (double) (3 * r->v_codons));
 				fprintf(fp, "\t%d", r->j_mis);
 			} else fputs("\t\t\t\t\t\t\t\t\t\t", fp);
-			if (u->lineages) { if (u->lin_clone[i] >= 0) fprintf(fp, "\tlin_%d", u->lin_clone[i] + 1); else fputc('\t', fp); }
+			if (u->c->lineages) { if (u->lin_clone[i] >= 0) fprintf(fp, "\tlin_%d", u->lin_clone[i] + 1); else fputc('\t', fp); }
 			fputc('\n', fp);
 		}
 	}
 	free(lim);
 	free(rows);
 	free(mask);
-	if (fclose(fp) && !rc) { fprintf(stderr, "cannot write %s\n", u->mutations); return -1; }
-	if (!rc) u->mut_done = 1;
+	if (fclose(fp) && !rc) { fprintf(stderr, "cannot write %s\n", u->c->mutations); return -1; }
 	return rc;
 }
 
@@ -1814,23 +1289,23 @@ static int sel_test_write(const char* path, const char* const* level, char* cons
 }
 
 static int sel_run(hook_ud* u, const char* const* ids, const char* contigs, size_t n, int len) {
-	FILE* fp = fopen(u->selection, "w");
-	if (!fp) { fprintf(stderr, "cannot write %s\n", u->selection); return -1; }
+	FILE* fp = fopen(u->c->selection, "w");
+	if (!fp) { fprintf(stderr, "cannot write %s\n", u->c->selection); return -1; }
 	fputs("level\tid\tregion\tsequences\tobs_r\tobs_s\texp_r\texp_s\tsigma\tsigma_lower\tsigma_upper\tp_positive\n", fp);
-	const uint32_t K = u->have_regs ? 2 : 1, G = u->lineages && n ? u->li.clones : 0;
+	const uint32_t K = u->c->have_regs ? 2 : 1, G = u->c->lineages && n ? u->li.clones : 0;
 	int rc = 0, test_refused = 0;
 	if (n) {
 		const germ_set* g = u->germ;
 		int32_t* cdr = NULL;
-		if (u->have_regs) {
+		if (u->c->have_regs) {
 			cdr = (int32_t*) malloc((g->n * 4 + 1) * sizeof(int32_t));
 			for (size_t k = 0; k < g->n * 4; k++) cdr[k] = -1;
 			const char* first = NULL;
-			for (size_t q = 0; q < u->nregs; q++) {
+			for (size_t q = 0; q < u->c->nregs; q++) {
 				int hit = 0;
 				for (size_t r = 0; r < g->n; r++)
-					if (!strcmp(g->names[r], u->regs[q].name)) { memcpy(cdr + 4 * r, u->regs[q].iv, sizeof u->regs[q].iv); hit = 1; }
-				if (!hit && !u->sel_unmatched++) first = u->regs[q].name;
+					if (!strcmp(g->names[r], u->c->regs[q].name)) { memcpy(cdr + 4 * r, u->c->regs[q].iv, sizeof u->c->regs[q].iv); hit = 1; }
+				if (!hit && !u->sel_unmatched++) first = u->c->regs[q].name;
 			}
 			if (u->sel_unmatched) fprintf(stderr, "--v-regions: %zu names match no germline record (the first: %s)\n", u->sel_unmatched, first);
 		}
@@ -1838,18 +1313,18 @@ static int sel_run(hook_ud* u, const char* const* ids, const char* contigs, size
 		vdjx_sel_counts* cnt = (vdjx_sel_counts*) calloc(n + 1, sizeof(vdjx_sel_counts));
 		vdjx_sel_stat* st = (vdjx_sel_stat*) calloc((n + G + 1) * (size_t) K, sizeof(vdjx_sel_stat));
 		/* --selection-test: the densities of the lineage and sample rows, and of the consensus sample behind them: T rows of K = 2 */
-		const int with_cs = u->consensus && u->cs_units;
+		const int with_cs = u->c->consensus && u->cs_units;
 		const size_t T = (size_t) G + 1 + (with_cs ? 1 : 0);
-		int test = u->sel_test != NULL;
+		int test = u->c->sel_test != NULL;
 		if (test && (uint64_t) G + 1 > 65536) {
 			fprintf(stderr, "--selection-test: %u lineages (at most 65535): the test table is not written\n", G);
 			test = 0; test_refused = 1;
 		}
 		double* pdf = test ? (double*) malloc(T * K * VDJX_SEL_GRID * sizeof(double)) : NULL;
 		vdjx_sel_stat* tst = test ? (vdjx_sel_stat*) calloc(T * K, sizeof(vdjx_sel_stat)) : NULL;
-		rc = vdjx_selection(u->gx, contigs, n, len, u->hv, lim, cdr, g->n, u->weight, G ? u->lin_clone : NULL, G, cnt, st, u->sel_mean ? NULL : pdf, &u->si);
+		rc = vdjx_selection(u->gx, contigs, n, len, u->hv, lim, cdr, g->n, u->c->weight, G ? u->lin_clone : NULL, G, cnt, st, u->c->sel_mean ? NULL : pdf, &u->si);
 		if (rc) fprintf(stderr, "--selection: %s\n", vdjx_last_error());
-		if (!rc && u->sel_mean) {
+		if (!rc && u->c->sel_mean) {
 			for (uint32_t k = 0; k < K; k++) u->sel_sigma[k] = sel_no_minus_zero(st[(n + G) * (size_t) K + k].sigma);      /* the selection: line keeps the shared sigma */
 			rc = sel_mean_rows(u, cnt, n, K, G ? u->lin_clone : NULL, G, st + n * (size_t) K, pdf);
 			for (uint32_t k = 0; k < K && !rc; k++) u->sel_msigma[k] = sel_no_minus_zero(st[(n + G) * (size_t) K + k].sigma);
@@ -1865,16 +1340,16 @@ static int sel_run(hook_ud* u, const char* const* ids, const char* contigs, size
 				snprintf(id, sizeof id, "lin_%u", k + 1);
 				sel_rows(fp, "lineage", id, st + (n + k) * (size_t) K, K);
 			}
-			sel_rows(fp, "sample", u->sample, st + (n + G) * (size_t) K, K);
+			sel_rows(fp, "sample", u->c->sample, st + (n + G) * (size_t) K, K);
 			/* --consensus: the units' pseudo-contigs, each on its own and all under a shared sigma -- one representative per clone */
-			if (u->consensus && u->cs_units) {
+			if (u->c->consensus && u->cs_units) {
 				const size_t U = u->cs_units;
 				vdjx_sel_counts* cnt2 = (vdjx_sel_counts*) calloc(U + 1, sizeof(vdjx_sel_counts));
 				vdjx_sel_stat* st2 = (vdjx_sel_stat*) calloc((U + 1) * (size_t) K, sizeof(vdjx_sel_stat));
 				double* pdf2 = test ? pdf + ((size_t) G + 1) * K * VDJX_SEL_GRID : NULL;
-				rc = vdjx_selection(u->gx, u->cs_pc, U, u->cs_plen, u->cs_hv, NULL, cdr, g->n, u->weight, NULL, 0, cnt2, st2, u->sel_mean ? NULL : pdf2, NULL);
+				rc = vdjx_selection(u->gx, u->cs_pc, U, u->cs_plen, u->cs_hv, NULL, cdr, g->n, u->c->weight, NULL, 0, cnt2, st2, u->c->sel_mean ? NULL : pdf2, NULL);
 				if (rc) fprintf(stderr, "--selection: %s\n", vdjx_last_error());
-				if (!rc && u->sel_mean) rc = sel_mean_rows(u, cnt2, U, K, NULL, 0, st2 + U * (size_t) K, pdf2);
+				if (!rc && u->c->sel_mean) rc = sel_mean_rows(u, cnt2, U, K, NULL, 0, st2 + U * (size_t) K, pdf2);
 				if (!rc && test) memcpy(tst + ((size_t) G + 1) * K, st2 + U * (size_t) K, K * sizeof(vdjx_sel_stat));
 				for (size_t k = 0; k < U && !rc; k++) {
 					char id[32];
@@ -1883,10 +1358,10 @@ static int sel_run(hook_ud* u, const char* const* ids, const char* contigs, size
 					if (cnt2[k].flags & 1) sel_rows(fp, "consensus", name, st2 + k * K, K);
 					else fprintf(fp, "consensus\t%s\t\t\t\t\t\t\t\t\t\t\n", name);
 				}
-				if (!rc) sel_rows(fp, "consensus_sample", u->sample, st2 + U * (size_t) K, K);
+				if (!rc) sel_rows(fp, "consensus_sample", u->c->sample, st2 + U * (size_t) K, K);
 				free(cnt2); free(st2);
 			}
-			for (uint32_t k = 0; k < K && !u->sel_mean; k++) {       /* (mean: kept before the rows were replaced) */
+			for (uint32_t k = 0; k < K && !u->c->sel_mean; k++) {       /* (mean: kept before the rows were replaced) */
 				const double sg = st[(n + G) * (size_t) K + k].sigma;
 				u->sel_sigma[k] = sg > -0.00005 && sg < 0.0 ? 0.0 : sg;
 			}
@@ -1896,22 +1371,21 @@ static int sel_run(hook_ud* u, const char* const* ids, const char* contigs, size
 			char** id = (char**) malloc(T * sizeof(char*));
 			for (size_t r = 0; r < T; r++) {
 				level[r] = r < G ? "lineage" : r == G ? "sample" : "consensus_sample";
-				id[r] = (char*) malloc(r < G ? 32 : strlen(u->sample) + 1);
+				id[r] = (char*) malloc(r < G ? 32 : strlen(u->c->sample) + 1);
 				if (r < G) snprintf(id[r], 32, "lin_%zu", r + 1);
-				else strcpy(id[r], u->sample);
+				else strcpy(id[r], u->c->sample);
 			}
-			rc = sel_test_write(u->sel_test, level, id, T, tst, pdf);
+			rc = sel_test_write(u->c->sel_test, level, id, T, tst, pdf);
 			for (size_t r = 0; r < T; r++) free(id[r]);
 			free(level); free(id);
 		}
 		free(cdr); free(lim); free(cnt); free(st); free(pdf); free(tst);
-	} else if (u->sel_test) {
-		rc = sel_test_write(u->sel_test, NULL, NULL, 0, NULL, NULL);
+	} else if (u->c->sel_test) {
+		rc = sel_test_write(u->c->sel_test, NULL, NULL, 0, NULL, NULL);
 	}
 	u->si.groups = G;
 	u->si.regions = K;
-	if (fclose(fp) && !rc) { fprintf(stderr, "cannot write %s\n", u->selection); return -1; }
-	if (!rc) u->sel_done = 1;
+	if (fclose(fp) && !rc) { fprintf(stderr, "cannot write %s\n", u->c->selection); return -1; }
 	return rc ? rc : test_refused ? -1 : 0;
 }
 
@@ -1926,19 +1400,19 @@ static int tgt_run(hook_ud* u, const char* const* ids, const char* contigs, size
 	int rc = 0;
 	if (n) {
 		int32_t* lim = mutation_limits(ids, contigs, n, len);
-		rc = vdjx_targeting_counts(u->gx, contigs, n, len, u->hv, lim, u->lineages ? u->lin_clone : NULL, cnt, &u->tgi);
+		rc = vdjx_targeting_counts(u->gx, contigs, n, len, u->hv, lim, u->c->lineages ? u->lin_clone : NULL, cnt, &u->tgi);
 		free(lim);
 	}
-	if (!rc) rc = vdjx_targeting_model(cnt, u->tgt_cls, u->tgt_min_sub, u->tgt_min_mut, w, lv);
+	if (!rc) rc = vdjx_targeting_model(cnt, u->c->tgt_cls, u->c->tgt_min_sub, u->c->tgt_min_mut, w, lv);
 	if (rc) fprintf(stderr, "--targeting-model: %s\n", vdjx_last_error());
 	if (!rc) {
 		for (int m = 0; m < 1024; m++)
 			for (int t = 0; t < 2; t++) u->tgt_levels[t][lv[2 * m + t] == 5 ? 0 : lv[2 * m + t] == 3 ? 1 : lv[2 * m + t] == 1 ? 2 : 3]++;
-		FILE* fp = fopen(u->tgt_model, "w");
-		if (!fp) { fprintf(stderr, "cannot write %s\n", u->tgt_model); rc = -1; }
+		FILE* fp = fopen(u->c->tgt_model, "w");
+		if (!fp) { fprintf(stderr, "cannot write %s\n", u->c->tgt_model); rc = -1; }
 		else {
-			fprintf(fp, "# targeting model of %s: class %s, min_sub %llu, min_mut %llu\n", u->sample, u->tgt_cls ? "rs" : "s", (unsigned long long) u->tgt_min_sub,
-			        (unsigned long long) u->tgt_min_mut);
+			fprintf(fp, "# targeting model of %s: class %s, min_sub %llu, min_mut %llu\n", u->c->sample, u->c->tgt_cls ? "rs" : "s", (unsigned long long) u->c->tgt_min_sub,
+			        (unsigned long long) u->c->tgt_min_mut);
 			fprintf(fp, "# %llu units, %llu positions, observed %llu S %llu R, opportunities %llu S %llu R\n", (unsigned long long) u->tgi.units,
 			        (unsigned long long) u->tgi.positions, (unsigned long long) u->tgi.obs_s, (unsigned long long) u->tgi.obs_r, (unsigned long long) u->tgi.opp_s,
 			        (unsigned long long) u->tgi.opp_r);
@@ -1947,12 +1421,12 @@ static int tgt_run(hook_ud* u, const char* const* ids, const char* contigs, size
 			for (int m = 0; m < 1024; m++)
 				fprintf(fp, "%c%c%c%c%c\t%u\t%u\t%u\t%u\n", B[m >> 8 & 3], B[m >> 6 & 3], B[m >> 4 & 3], B[m >> 2 & 3], B[m & 3], w[4 * m], w[4 * m + 1], w[4 * m + 2],
 				        w[4 * m + 3]);
-			if (fclose(fp)) { fprintf(stderr, "cannot write %s\n", u->tgt_model); rc = -1; }
+			if (fclose(fp)) { fprintf(stderr, "cannot write %s\n", u->c->tgt_model); rc = -1; }
 		}
 	}
-	if (!rc && u->tgt_counts) {
-		FILE* fp = fopen(u->tgt_counts, "w");
-		if (!fp) { fprintf(stderr, "cannot write %s\n", u->tgt_counts); rc = -1; }
+	if (!rc && u->c->tgt_counts) {
+		FILE* fp = fopen(u->c->tgt_counts, "w");
+		if (!fp) { fprintf(stderr, "cannot write %s\n", u->c->tgt_counts); rc = -1; }
 		else {
 			fputs("kmer", fp);
 			for (int t = 0; t < 4; t++)
@@ -1964,11 +1438,10 @@ static int tgt_run(hook_ud* u, const char* const* ids, const char* contigs, size
 					for (int x = 0; x < 4; x++) fprintf(fp, "\t%llu", (unsigned long long) cnt[(size_t) t * 4096 + 4 * (size_t) m + (size_t) x]);
 				fprintf(fp, "\t%u\t%u\n", lv[2 * m], lv[2 * m + 1]);
 			}
-			if (fclose(fp)) { fprintf(stderr, "cannot write %s\n", u->tgt_counts); rc = -1; }
+			if (fclose(fp)) { fprintf(stderr, "cannot write %s\n", u->c->tgt_counts); rc = -1; }
 		}
 	}
 	free(cnt); free(w); free(lv);
-	if (!rc) u->tgt_done = 1;
 	return rc;
 }
 
@@ -1977,8 +1450,8 @@ static int tgt_run(hook_ud* u, const char* const* ids, const char* contigs, size
  * vdjx_mutations' counts of the unit's pseudo-contig under its synthetic hit (vdjx_consensus_hits), J absent, no limit.  The pseudo-contigs
  * are kept for the --selection table's consensus rows. */
 static int cons_run(hook_ud* u, const char* const* ids, const char* contigs, size_t n, int len) {
-	FILE* fp = fopen(u->consensus, "w");
-	if (!fp) { fprintf(stderr, "cannot write %s\n", u->consensus); return -1; }
+	FILE* fp = fopen(u->c->consensus, "w");
+	if (!fp) { fprintf(stderr, "cannot write %s\n", u->c->consensus); return -1; }
 	fputs("clone_id\tsequence_id\tv_call\tmembers\toff_record\tgermline_start\tgermline_end\tconsensus_alignment\tgermline_alignment\tmin_cover\tundecided\t"
 	      "v_germline_codons\tmu_count_v_r\tmu_count_v_s\tmu_count_v_stop\tmu_count_v_na\tmu_freq_v\n", fp);
 	int rc = 0;
@@ -1997,7 +1470,7 @@ static int cons_run(hook_ud* u, const char* const* ids, const char* contigs, siz
 			cons = (char*) malloc((size_t) cols + 1);
 			germ = (char*) malloc((size_t) cols + 1);
 			cover = (uint32_t*) calloc((size_t) cols + 1, sizeof(uint32_t));
-			const vdjx_cons_params cp = {u->cons_num, 10000};
+			const vdjx_cons_params cp = {u->c->cons_num, 10000};
 			rc = vdjx_consensus(u->gx, contigs, n, len, u->hv, lim, u->lin_clone, &cp, cons, germ, cover, NULL, un, unit, &u->ci);
 		}
 		int plen = 1;
@@ -2044,8 +1517,7 @@ static int cons_run(hook_ud* u, const char* const* ids, const char* contigs, siz
 		} else free(un);
 		free(lim); free(unit); free(cons); free(germ); free(cover); free(rows); free(nohit);
 	}
-	if (fclose(fp) && !rc) { fprintf(stderr, "cannot write %s\n", u->consensus); return -1; }
-	if (!rc) u->cons_done = 1;
+	if (fclose(fp) && !rc) { fprintf(stderr, "cannot write %s\n", u->c->consensus); return -1; }
 	return rc;
 }
 
@@ -2055,8 +1527,8 @@ static int cons_run(hook_ud* u, const char* const* ids, const char* contigs, siz
  * interval (alakazam's alphaDiversity) and the three over d at q = 0 (evenness).  No lineage of weight: the header alone, no device call. */
 #define DIV_ORDERS 41
 static int diversity_run(hook_ud* u, size_t n) {
-	FILE* fp = fopen(u->diversity, "w");
-	if (!fp) { fprintf(stderr, "cannot write %s\n", u->diversity); return -1; }
+	FILE* fp = fopen(u->c->diversity, "w");
+	if (!fp) { fprintf(stderr, "cannot write %s\n", u->c->diversity); return -1; }
 	fputs("q\td_observed\td\td_sd\td_lower\td_upper\te\te_lower\te_upper\n", fp);
 	const size_t nk = u->li.clones;
 	uint64_t* w = (uint64_t*) calloc(nk + 1, sizeof(uint64_t));
@@ -2082,9 +1554,9 @@ static int diversity_run(hook_ud* u, size_t n) {
 	}
 	if (!rc && C) {
 		double q[DIV_ORDERS], obs[DIV_ORDERS], mean[DIV_ORDERS], sd[DIV_ORDERS];
-		double* d = (double*) calloc((size_t) u->dv_boot * DIV_ORDERS, sizeof(double));
+		double* d = (double*) calloc((size_t) u->c->div_boot * DIV_ORDERS, sizeof(double));
 		for (int k = 0; k < DIV_ORDERS; k++) q[k] = (double) k / 10.0;
-		const vdjx_diversity_params dp = {u->dv_boot, u->dv_depth, u->dv_seed};
+		const vdjx_diversity_params dp = {u->c->div_boot, u->dv_depth, u->c->div_seed};
 		rc = vdjx_diversity(u->gx, w, C, q, DIV_ORDERS, &dp, obs, d, mean, sd, NULL, &u->dvi);
 		if (rc) fprintf(stderr, "--diversity: %s\n", vdjx_last_error());
 		if (!rc) {
@@ -2099,29 +1571,29 @@ static int diversity_run(hook_ud* u, size_t n) {
 	}
 	u->dvi.clones = (uint32_t) C;          /* (no lineage of weight: the device was not called) */
 	free(w);
-	if (fclose(fp) && !rc) { fprintf(stderr, "cannot write %s\n", u->diversity); return -1; }
+	if (fclose(fp) && !rc) { fprintf(stderr, "cannot write %s\n", u->c->diversity); return -1; }
 	return rc;
 }
 
 /* the tables after the SAM body: every device step runs once, whichever tables ask for it */
 static int tables(hook_ud* u, const char* const* ids, const char* contigs, size_t n, int len) {
 	int rc = 0;
-	if (!rc && (u->quant || u->clones)) rc = quant_table(u, ids, contigs, n, len);
-	if (!rc && (u->airr || u->clones || u->lineages || u->mutations || u->selection || u->tgt_model)) rc = annot_run(u, contigs, n, len);
-	if (!rc && u->d_calls) rc = dcall_run(u, contigs, n, len);
-	if (!rc && u->lineages) rc = lineage_run(u, ids, contigs, n, len);
-	if (!rc && u->trees) rc = tree_run(u, ids, contigs, n, len);
-	if (!rc && u->trees_nj) rc = tree_nj_run(u, ids, contigs, n, len);
-	if (!rc && u->trees_mp) rc = tree_mp_run(u, ids, contigs, n, len);
-	if (!rc && u->diversity) rc = diversity_run(u, n);
-	if (!rc && u->mutations) rc = mut_run(u, ids, contigs, n, len);
-	if (!rc && u->consensus) rc = cons_run(u, ids, contigs, n, len);
-	if (!rc && u->selection) rc = sel_run(u, ids, contigs, n, len);
-	if (!rc && u->tgt_model) rc = tgt_run(u, ids, contigs, n, len);
-	if (!rc && u->airr) rc = airr_table(u, ids, contigs, n, len);
-	if (!rc && u->cfa && (u->isotypes || u->clones)) rc = iso_run(u, contigs, n, len);
-	if (!rc && u->isotypes) rc = isotypes_table(u, ids, n, len);
-	if (!rc && u->clones) rc = clones_table(u, ids, contigs, n, len);
+	if (!rc && (u->c->quant || u->c->clones)) rc = quant_table(u, ids, contigs, n, len);
+	if (!rc && (u->c->airr || u->c->clones || u->c->lineages || u->c->mutations || u->c->selection || u->c->tgt_model)) rc = annot_run(u, contigs, n, len);
+	if (!rc && u->c->d_calls) rc = dcall_run(u, contigs, n, len);
+	if (!rc && u->c->lineages) rc = lineage_run(u, ids, contigs, n, len);
+	if (!rc && u->c->trees) rc = tree_run(u, ids, contigs, n, len);
+	if (!rc && u->c->trees_nj) rc = tree_nj_run(u, ids, contigs, n, len);
+	if (!rc && u->c->trees_mp) rc = tree_mp_run(u, ids, contigs, n, len);
+	if (!rc && u->c->diversity) rc = diversity_run(u, n);
+	if (!rc && u->c->mutations) rc = mut_run(u, ids, contigs, n, len);
+	if (!rc && u->c->consensus) rc = cons_run(u, ids, contigs, n, len);
+	if (!rc && u->c->selection) rc = sel_run(u, ids, contigs, n, len);
+	if (!rc && u->c->tgt_model) rc = tgt_run(u, ids, contigs, n, len);
+	if (!rc && u->c->airr) rc = airr_table(u, ids, contigs, n, len);
+	if (!rc && u->c->cfa && (u->c->isotypes || u->c->clones)) rc = iso_run(u, contigs, n, len);
+	if (!rc && u->c->isotypes) rc = isotypes_table(u, ids, n, len);
+	if (!rc && u->c->clones) rc = clones_table(u, ids, contigs, n, len);
 	return rc;
 }
 
@@ -2129,7 +1601,95 @@ static int h_sam_body(void* ud, const char* const* ids, const char* contigs, siz
 	hook_ud* u = (hook_ud*) ud;
 	int rc = sam_records(ud, ids, contigs, n, len, out);
 	if (!rc) rc = tables(u, ids, contigs, n, len);
+	if (!rc) u->tables_ran = 1;
 	return rc;
+}
+
+/* a line per table on stderr, behind FINIS */
+static void tables_summary(const hook_ud* u) {
+	const cli* c = u->c;
+	if (c->quant)
+		fprintf(stderr, "quant: %llu pairs placed (%llu once), %llu alignments, %u EM iterations, %s; table in %s\n", (unsigned long long) u->qi.pairs,
+		        (unsigned long long) u->qi.unique_pairs, (unsigned long long) u->qi.alignments, u->qi.iterations,
+		        u->qi.converged ? "converged" : "stopped at the iteration limit", c->quant);
+	if (c->quant && c->qb_b)
+		fprintf(stderr, "quant boot: %u replicates (seed %llu), %llu EM iterations in all (most %u), %u stopped at the iteration limit, %u batches\n", u->qbi.replicates,
+		        (unsigned long long) c->qb_seed, (unsigned long long) u->qbi.iterations, u->qbi.max_iterations, u->qbi.replicates - u->qbi.converged, u->qbi.batches);
+	if (c->airr)
+		fprintf(stderr, "airr: %zu contigs, %zu V called, %zu J called, %zu productive, %zu CIGARs truncated; germline records skipped: %zu D, %zu other; table in %s\n",
+		        u->a_contigs, u->a_v, u->a_j, u->a_prod, u->a_trunc, u->a_skip_d, u->a_skip_other, c->airr);
+	if (c->d_calls)
+		fprintf(stderr, "dcalls: %zu contigs, %zu windows, %zu over %d bases, %zu D called against %zu D records\n", u->d_contigs, u->d_windows, u->d_over,
+		        VDJX_DCALL_WINDOW, u->d_called, u->dset ? u->dset->n : (size_t) 0);
+	if (c->lineages)
+		fprintf(stderr, "lineages: %zu contigs, %zu eligible, %u buckets (largest %u), %llu pairs, %llu links, %u lineages at %d/%d\n", u->l_contigs, u->l_eligible,
+		        u->li.buckets, u->li.largest_bucket, (unsigned long long) u->li.pairs, (unsigned long long) u->li.links, u->li.clones, u->lin_num, c->lin_den);
+	if (c->lin_model)
+		fprintf(stderr, "lineage model: %s, symmetry %s, mean %.4f, costs %u .. %u, %llu of %llu ordered pairs walked\n", c->lin_model, c->lin_sym ? "min" : "avg",
+		        c->lin_ti.mean, c->lin_ti.min_cost, c->lin_ti.max_cost, u->lin_walked, 2ull * (unsigned long long) u->li.pairs);
+	if (c->lin_threshold) {
+		static const char* const why[5] = {"", "too few values", "no scale", "one mode", "shallow valley"};
+		const vdjx_threshold_info* t = &u->thi;
+		if (t->status == VDJX_THRESHOLD_FOUND)
+			fprintf(stderr, "lineage threshold: %u distances in %u bins, bandwidth %.3f, peaks %.4f %.4f, valley %.4f .. %.4f, threshold %.4f, %d pair passes\n", t->values,
+			        t->distinct, t->k / 1000.0, t->p1_first / 10000.0, t->p2_first / 10000.0, t->t_first / 10000.0, t->t_last / 10000.0, t->threshold / 10000.0, u->thr_passes);
+		else
+			fprintf(stderr, "lineage threshold: %u distances in %u bins, none (%s), --lineage-dist %.4f stands\n", t->values, t->distinct, why[t->status <= 4 ? t->status : 0],
+			        u->thr_fallback / 10000.0);
+	}
+	if (c->lin_linkage)
+		fprintf(stderr, "lineage link: %s, %u components of two and more (largest %u), %u merges, %u lineages of %u under single linkage, %u batches\n", c->lin_linkage == 1 ? "complete" : "average",
+		        u->lki.components, u->lki.largest_component, u->lki.merges, u->li.clones, u->lki.clones_single, u->lki.batches);
+	if (c->trees)
+		fprintf(stderr, "trees: %u contigs in %u lineages (largest %u), %llu edges, total distance %llu, %u rounds\n", u->ti.members, u->ti.clones, u->ti.largest_clone,
+		        (unsigned long long) u->ti.edges, (unsigned long long) u->ti.weight, u->ti.rounds);
+	if (c->ts_b)
+		fprintf(stderr, "tree support: %u replicates (seed %llu), %llu edges, %llu of %llu kept, %llu in every replicate, %u batches\n", c->ts_b,
+		        (unsigned long long) c->ts_seed, (unsigned long long) u->tsi.edges, (unsigned long long) u->tsi.matched,
+		        (unsigned long long) (u->tsi.edges * c->ts_b), (unsigned long long) u->tsi.full, u->tsi.batches);
+	if (c->trees_nj)
+		fprintf(stderr, "trees nj: %u contigs in %u lineages (largest %u), %u inferred nodes, %llu edges, length %.4f, parsimony %llu, %u negative branches, %u batches\n",
+		        u->tni.members, u->tni.clones, u->tni.largest_clone, u->tni.internal, (unsigned long long) u->tni.edges, (double) u->tni.length / 65536.0,
+		        (unsigned long long) u->tni.parsimony, u->tni.negative, u->tni.batches);
+	if (c->trees_mp)
+		fprintf(stderr, "trees mp: %u contigs in %u lineages (largest %u), %u searched, %u improved, %llu moves in %u rounds, %llu candidates, parsimony %llu -> %llu, %u batches\n",
+		        u->tmi.members, u->tmi.clones, u->tmi.largest_clone, u->tmi.searched, u->tmi.moved, (unsigned long long) u->tmi.moves, u->tmi.rounds,
+		        (unsigned long long) u->tmi.candidates, (unsigned long long) u->tmi.parsimony_start, (unsigned long long) u->tmi.parsimony, u->tmi.batches);
+	if (c->isotypes)
+		fprintf(stderr, "isotypes: %zu contigs, %zu called against %zu constant records of %s; table in %s\n", u->i_contigs, u->i_called,
+		        u->cst ? u->cst->n : (size_t) 0, c->cfa, c->isotypes);
+	if (c->clones)
+		fprintf(stderr, "clones: %zu rows in %zu clusters, isotypes %s; table in %s\n", u->c_rows, u->c_clusters, c->cfa ? "called" : "N/A (no --cfa)", c->clones);
+	if (c->mutations)
+		fprintf(stderr, "mutations: %llu contigs, %llu aligned, %llu columns, %llu V codons, %llu R, %llu S, %llu stop, %llu unclassified, %u J clipped, %u over 64 runs\n",
+		        (unsigned long long) u->mi.contigs, (unsigned long long) u->mi.aligned, (unsigned long long) u->mi.cols, (unsigned long long) u->mi.v_codons,
+		        (unsigned long long) u->mi.v_r, (unsigned long long) u->mi.v_s, (unsigned long long) u->mi.v_stop, (unsigned long long) u->mi.v_na,
+		        u->mi.clipped, u->mi.truncated);
+	if (c->diversity)
+		fprintf(stderr, "diversity: %u lineages with weight of %u, %llu.%02llu expected pairs, depth %u, %u replicates (seed %llu), richness %.2f, shannon %.4f, simpson %.4f, %u batches\n",
+		        u->dvi.clones, u->li.clones, (unsigned long long) (u->dv_weight / 100), (unsigned long long) (u->dv_weight % 100), u->dv_depth, c->div_boot,
+		        (unsigned long long) c->div_seed, u->dv_d0, u->dv_d1, u->dv_d2, u->dvi.batches);
+	if (c->selection) {
+		fprintf(stderr, "selection: %llu contigs, %llu used, %llu without regions, %u lineages, %u regions, targeting %s, sample sigma %.4f", (unsigned long long) u->si.contigs,
+		        (unsigned long long) u->si.used, (unsigned long long) u->si.no_regions, u->si.groups, u->si.regions, c->targeting ? c->targeting : "uniform", u->sel_sigma[0]);
+		if (u->si.regions == 2) fprintf(stderr, " %.4f", u->sel_sigma[1]);
+		fprintf(stderr, ", %u chunks\n", u->si.chunks);
+		if (c->sel_mean) {
+			fprintf(stderr, "selection combine: mean, %u rows, %llu densities, %llu combinations, %u levels at most, %u batches, sample sigma %.4f", u->sci.rows,
+			        (unsigned long long) u->sci.leaves, (unsigned long long) u->sci.combines, u->sci.levels, u->sci.batches, u->sel_msigma[0]);
+			if (u->si.regions == 2) fprintf(stderr, " %.4f", u->sel_msigma[1]);
+			fputc('\n', stderr);
+		}
+	}
+	if (c->tgt_model)
+		fprintf(stderr, "targeting model: %llu contigs, %llu used, %llu units, %llu positions, %llu S, %llu R, class %s, substitution levels %u/%u/%u/%u, mutability levels %u/%u/%u/%u, %u batches\n",
+		        (unsigned long long) u->tgi.contigs, (unsigned long long) u->tgi.used, (unsigned long long) u->tgi.units, (unsigned long long) u->tgi.positions,
+		        (unsigned long long) u->tgi.obs_s, (unsigned long long) u->tgi.obs_r, c->tgt_cls ? "rs" : "s", u->tgt_levels[0][0], u->tgt_levels[0][1], u->tgt_levels[0][2],
+		        u->tgt_levels[0][3], u->tgt_levels[1][0], u->tgt_levels[1][1], u->tgt_levels[1][2], u->tgt_levels[1][3], u->tgi.batches);
+	if (c->consensus)
+		fprintf(stderr, "consensus: %llu contigs, %llu used, %llu units (largest %u), %llu off the unit's record, %llu columns, %llu undecided, min share %d.%04d, %u batches\n",
+		        (unsigned long long) u->ci.contigs, (unsigned long long) u->ci.used, (unsigned long long) u->ci.units, u->cs_largest, (unsigned long long) u->ci.off_record,
+		        (unsigned long long) u->ci.columns, (unsigned long long) u->ci.undecided, c->cons_num / 10000, c->cons_num % 10000, u->ci.batches);
 }
 
 static void h_status(void* ud, const char* desc) { (void) ud; status(desc); }
@@ -2392,24 +1952,8 @@ int main(int argc, char** argv) {
 
 	hook_ud ud;
 	memset(&ud, 0, sizeof ud);
-	ud.qb_b = c.qb_b; ud.qb_seed = c.qb_seed;
-	ud.gx = gx; ud.p = &c.hp; ud.mg = mg; ud.quant = c.quant; ud.airr = c.airr; ud.vdjf = c.vdj_fasta; ud.d_calls = c.d_calls;
-	ud.cfa = c.cfa; ud.isotypes = c.isotypes; ud.clones = c.clones; ud.total_count = c.total_count;
-	ud.lineages = c.lineages; ud.lin_num = c.lin_num; ud.lin_den = c.lin_den; ud.lin_table = c.lin_table; ud.lin_sym = c.lin_sym; ud.lin_thr = c.lin_threshold; ud.lin_linkage = c.lin_linkage; ud.trees = c.trees; ud.trees_nj = c.trees_nj; ud.trees_newick = c.trees_newick; ud.trees_mp = c.trees_mp; ud.trees_mp_newick = c.trees_mp_newick;
-	ud.ts_b = c.ts_b; ud.ts_seed = c.ts_seed; ud.mutations = c.mutations;
-	ud.diversity = c.diversity; ud.dv_depth = c.div_depth; ud.dv_boot = c.div_boot; ud.dv_seed = c.div_seed;
-	ud.selection = c.selection; ud.regs = c.regs; ud.nregs = c.nregs; ud.weight = c.weight; ud.have_regs = c.v_regions != NULL;
-	ud.sel_mean = c.sel_mean; ud.sel_test = c.sel_test;
-	ud.tgt_model = c.tgt_model; ud.tgt_counts = c.tgt_counts; ud.tgt_cls = c.tgt_cls; ud.tgt_min_sub = c.tgt_min_sub; ud.tgt_min_mut = c.tgt_min_mut;
-	ud.consensus = c.consensus; ud.cons_num = c.cons_num;
-	char sample_buf[4096];
-	if (c.sample) ud.sample = c.sample;
-	else {                                  /* the input's base name up to its first '.' */
-		const char* b = strrchr(c.in, '/');
-		snprintf(sample_buf, sizeof sample_buf, "%s", b ? b + 1 : c.in);
-		sample_buf[strcspn(sample_buf, ".")] = 0;
-		ud.sample = sample_buf;
-	}
+	ud.gx = gx; ud.mg = mg; ud.c = &c;
+	ud.lin_num = c.lin_num; ud.dv_depth = c.div_depth;      /* (run state: their steps write them) */
 	vdjh_hooks hk = {&ud, h_root_score, h_window_score, h_sam_body, vc, nv, jc, nj, h_status};
 	vdjh_stats st;
 	if (vdjh_assemble(&c.hp, &hg, &hk, "vdj_contigs.fa", "vdjer.dot", stdout, &st)) {
@@ -2417,7 +1961,7 @@ int main(int argc, char** argv) {
 		return 1;
 	}
 	/* (no contig: the headers alone) */
-	if (!ud.quant_done && !ud.airr_done && !ud.iso_done && !ud.clones_done && !ud.lin_done && !ud.mut_done && !ud.sel_done && !ud.tgt_done && !ud.cons_done && tables(&ud, NULL, NULL, 0, 0)) return 1;
+	if (!ud.tables_ran && tables(&ud, NULL, NULL, 0, 0)) return 1;
 	fprintf(stderr, "num root nodes: %zu\nProcessed roots: %zu\ncontig_candidates: %zu\nwindows scored: %zu valid: %zu\ncontigs: %zu\n",
 	        st.n_roots, st.n_roots_accepted, st.n_contig_candidates, st.n_windows_scored, st.n_windows_valid, st.n_contigs_out);
 	if (mg) {
@@ -2443,88 +1987,7 @@ int main(int argc, char** argv) {
 		if (g_kid_state[r] != 1) { fprintf(stderr, "rank %d failed\n", r); return 1; }
 	}
 	status("FINIS");
-	if (c.quant)
-		fprintf(stderr, "quant: %llu pairs placed (%llu once), %llu alignments, %u EM iterations, %s; table in %s\n", (unsigned long long) ud.qi.pairs,
-		        (unsigned long long) ud.qi.unique_pairs, (unsigned long long) ud.qi.alignments, ud.qi.iterations,
-		        ud.qi.converged ? "converged" : "stopped at the iteration limit", c.quant);
-	if (c.quant && c.qb_b)
-		fprintf(stderr, "quant boot: %u replicates (seed %llu), %llu EM iterations in all (most %u), %u stopped at the iteration limit, %u batches\n", ud.qbi.replicates,
-		        (unsigned long long) c.qb_seed, (unsigned long long) ud.qbi.iterations, ud.qbi.max_iterations, ud.qbi.replicates - ud.qbi.converged, ud.qbi.batches);
-	if (c.airr)
-		fprintf(stderr, "airr: %zu contigs, %zu V called, %zu J called, %zu productive, %zu CIGARs truncated; germline records skipped: %zu D, %zu other; table in %s\n",
-		        ud.a_contigs, ud.a_v, ud.a_j, ud.a_prod, ud.a_trunc, ud.a_skip_d, ud.a_skip_other, c.airr);
-	if (c.d_calls)
-		fprintf(stderr, "dcalls: %zu contigs, %zu windows, %zu over %d bases, %zu D called against %zu D records\n", ud.d_contigs, ud.d_windows, ud.d_over,
-		        VDJX_DCALL_WINDOW, ud.d_called, ud.dset ? ud.dset->n : (size_t) 0);
-	if (c.lineages)
-		fprintf(stderr, "lineages: %zu contigs, %zu eligible, %u buckets (largest %u), %llu pairs, %llu links, %u lineages at %d/%d\n", ud.l_contigs, ud.l_eligible,
-		        ud.li.buckets, ud.li.largest_bucket, (unsigned long long) ud.li.pairs, (unsigned long long) ud.li.links, ud.li.clones, ud.lin_num, ud.lin_den);
-	if (c.lin_model)
-		fprintf(stderr, "lineage model: %s, symmetry %s, mean %.4f, costs %u .. %u, %llu of %llu ordered pairs walked\n", c.lin_model, c.lin_sym ? "min" : "avg",
-		        c.lin_ti.mean, c.lin_ti.min_cost, c.lin_ti.max_cost, ud.lin_walked, 2ull * (unsigned long long) ud.li.pairs);
-	if (c.lin_threshold) {
-		static const char* const why[5] = {"", "too few values", "no scale", "one mode", "shallow valley"};
-		const vdjx_threshold_info* t = &ud.thi;
-		if (t->status == VDJX_THRESHOLD_FOUND)
-			fprintf(stderr, "lineage threshold: %u distances in %u bins, bandwidth %.3f, peaks %.4f %.4f, valley %.4f .. %.4f, threshold %.4f, %d pair passes\n", t->values,
-			        t->distinct, t->k / 1000.0, t->p1_first / 10000.0, t->p2_first / 10000.0, t->t_first / 10000.0, t->t_last / 10000.0, t->threshold / 10000.0, ud.thr_passes);
-		else
-			fprintf(stderr, "lineage threshold: %u distances in %u bins, none (%s), --lineage-dist %.4f stands\n", t->values, t->distinct, why[t->status <= 4 ? t->status : 0],
-			        ud.thr_fallback / 10000.0);
-	}
-	if (c.lin_linkage)
-		fprintf(stderr, "lineage link: %s, %u components of two and more (largest %u), %u merges, %u lineages of %u under single linkage, %u batches\n", c.lin_link,
-		        ud.lki.components, ud.lki.largest_component, ud.lki.merges, ud.li.clones, ud.lki.clones_single, ud.lki.batches);
-	if (c.trees)
-		fprintf(stderr, "trees: %u contigs in %u lineages (largest %u), %llu edges, total distance %llu, %u rounds\n", ud.ti.members, ud.ti.clones, ud.ti.largest_clone,
-		        (unsigned long long) ud.ti.edges, (unsigned long long) ud.ti.weight, ud.ti.rounds);
-	if (c.ts_b)
-		fprintf(stderr, "tree support: %u replicates (seed %llu), %llu edges, %llu of %llu kept, %llu in every replicate, %u batches\n", c.ts_b,
-		        (unsigned long long) c.ts_seed, (unsigned long long) ud.tsi.edges, (unsigned long long) ud.tsi.matched,
-		        (unsigned long long) (ud.tsi.edges * c.ts_b), (unsigned long long) ud.tsi.full, ud.tsi.batches);
-	if (c.trees_nj)
-		fprintf(stderr, "trees nj: %u contigs in %u lineages (largest %u), %u inferred nodes, %llu edges, length %.4f, parsimony %llu, %u negative branches, %u batches\n",
-		        ud.tni.members, ud.tni.clones, ud.tni.largest_clone, ud.tni.internal, (unsigned long long) ud.tni.edges, (double) ud.tni.length / 65536.0,
-		        (unsigned long long) ud.tni.parsimony, ud.tni.negative, ud.tni.batches);
-	if (c.trees_mp)
-		fprintf(stderr, "trees mp: %u contigs in %u lineages (largest %u), %u searched, %u improved, %llu moves in %u rounds, %llu candidates, parsimony %llu -> %llu, %u batches\n",
-		        ud.tmi.members, ud.tmi.clones, ud.tmi.largest_clone, ud.tmi.searched, ud.tmi.moved, (unsigned long long) ud.tmi.moves, ud.tmi.rounds,
-		        (unsigned long long) ud.tmi.candidates, (unsigned long long) ud.tmi.parsimony_start, (unsigned long long) ud.tmi.parsimony, ud.tmi.batches);
-	if (c.isotypes)
-		fprintf(stderr, "isotypes: %zu contigs, %zu called against %zu constant records of %s; table in %s\n", ud.i_contigs, ud.i_called,
-		        ud.cst ? ud.cst->n : (size_t) 0, c.cfa, c.isotypes);
-	if (c.clones)
-		fprintf(stderr, "clones: %zu rows in %zu clusters, isotypes %s; table in %s\n", ud.c_rows, ud.c_clusters, c.cfa ? "called" : "N/A (no --cfa)", c.clones);
-	if (c.mutations)
-		fprintf(stderr, "mutations: %llu contigs, %llu aligned, %llu columns, %llu V codons, %llu R, %llu S, %llu stop, %llu unclassified, %u J clipped, %u over 64 runs\n",
-		        (unsigned long long) ud.mi.contigs, (unsigned long long) ud.mi.aligned, (unsigned long long) ud.mi.cols, (unsigned long long) ud.mi.v_codons,
-		        (unsigned long long) ud.mi.v_r, (unsigned long long) ud.mi.v_s, (unsigned long long) ud.mi.v_stop, (unsigned long long) ud.mi.v_na,
-		        ud.mi.clipped, ud.mi.truncated);
-	if (c.diversity)
-		fprintf(stderr, "diversity: %u lineages with weight of %u, %llu.%02llu expected pairs, depth %u, %u replicates (seed %llu), richness %.2f, shannon %.4f, simpson %.4f, %u batches\n",
-		        ud.dvi.clones, ud.li.clones, (unsigned long long) (ud.dv_weight / 100), (unsigned long long) (ud.dv_weight % 100), ud.dv_depth, c.div_boot,
-		        (unsigned long long) c.div_seed, ud.dv_d0, ud.dv_d1, ud.dv_d2, ud.dvi.batches);
-	if (c.selection) {
-		fprintf(stderr, "selection: %llu contigs, %llu used, %llu without regions, %u lineages, %u regions, targeting %s, sample sigma %.4f", (unsigned long long) ud.si.contigs,
-		        (unsigned long long) ud.si.used, (unsigned long long) ud.si.no_regions, ud.si.groups, ud.si.regions, c.targeting ? c.targeting : "uniform", ud.sel_sigma[0]);
-		if (ud.si.regions == 2) fprintf(stderr, " %.4f", ud.sel_sigma[1]);
-		fprintf(stderr, ", %u chunks\n", ud.si.chunks);
-		if (c.sel_mean) {
-			fprintf(stderr, "selection combine: mean, %u rows, %llu densities, %llu combinations, %u levels at most, %u batches, sample sigma %.4f", ud.sci.rows,
-			        (unsigned long long) ud.sci.leaves, (unsigned long long) ud.sci.combines, ud.sci.levels, ud.sci.batches, ud.sel_msigma[0]);
-			if (ud.si.regions == 2) fprintf(stderr, " %.4f", ud.sel_msigma[1]);
-			fputc('\n', stderr);
-		}
-	}
-	if (c.tgt_model)
-		fprintf(stderr, "targeting model: %llu contigs, %llu used, %llu units, %llu positions, %llu S, %llu R, class %s, substitution levels %u/%u/%u/%u, mutability levels %u/%u/%u/%u, %u batches\n",
-		        (unsigned long long) ud.tgi.contigs, (unsigned long long) ud.tgi.used, (unsigned long long) ud.tgi.units, (unsigned long long) ud.tgi.positions,
-		        (unsigned long long) ud.tgi.obs_s, (unsigned long long) ud.tgi.obs_r, c.tgt_cls ? "rs" : "s", ud.tgt_levels[0][0], ud.tgt_levels[0][1], ud.tgt_levels[0][2],
-		        ud.tgt_levels[0][3], ud.tgt_levels[1][0], ud.tgt_levels[1][1], ud.tgt_levels[1][2], ud.tgt_levels[1][3], ud.tgi.batches);
-	if (c.consensus)
-		fprintf(stderr, "consensus: %llu contigs, %llu used, %llu units (largest %u), %llu off the unit's record, %llu columns, %llu undecided, min share %d.%04d, %u batches\n",
-		        (unsigned long long) ud.ci.contigs, (unsigned long long) ud.ci.used, (unsigned long long) ud.ci.units, ud.cs_largest, (unsigned long long) ud.ci.off_record,
-		        (unsigned long long) ud.ci.columns, (unsigned long long) ud.ci.undecided, c.cons_num / 10000, c.cons_num % 10000, ud.ci.batches);
+	tables_summary(&ud);
 	fflush(stdout);
 	fflush(stderr);
 	/* the outputs are written; the orderly teardown of a context that holds gigabytes (unmapping the workspaces piece by piece, the

@@ -239,7 +239,9 @@ int vdjx_window_score(vdjx_ctx* ctx, const char* windows, size_t n, int len, con
  *                            to the ranks that own those windows
  * and the owner of a window tests the union of what all ranks found (coverage_is_valid only counts entries, coverage.c:64-130):
  *   vdjx_window_cover        d_lists = the lists as received: source after source, inside a source window after window;
- *                            counts[s*n + w] = entries of window w from source s                                       */
+ *                            counts[s*n + w] = entries of window w from source s; an entry is
+ *                            multiplicity << 32 | pos1 << 16 | pos2, positions in 1 .. len - rl.  Refused ("bad geometry") unless
+ *                            1 <= rl <= VDJX_MAX_READ_LEN, rl < len <= 1024 + rl and nsrc >= 1                          */
 int vdjx_window_pairs(vdjx_ctx* ctx, const char* windows, size_t n, int len, uint32_t* out_entries, uint32_t* out_npairs);
 int vdjx_window_pairs_fetch(vdjx_ctx* ctx, const uint32_t* window_ids, size_t m, void* d_out);
 int vdjx_window_cover(vdjx_ctx* ctx, size_t n, int len, int rl, const vdjx_cov_params* p, const void* d_lists, size_t nsrc,

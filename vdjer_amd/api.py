@@ -514,11 +514,12 @@ class Context:
         check(self.L.vdjx_window_pairs_fetch(self.h, _p(ids), ids.shape[0], C.c_void_p(d_out)), "vdjx_window_pairs_fetch")
 
     def window_cover(self, n: int, ln: int, rl: int, d_lists: int, nsrc: int, counts, ins: int, e0: int = 52, e1: int = 411, rs: int = 35,
-                     ms: int = 48, floor: int = 1) -> np.ndarray:
-        """counts [nsrc, n] (source-major) entries per source and window; d_lists: device pointer to the lists in that order"""
+                     ms: int = 48, floor: int = 1, ins_high: int | None = None) -> np.ndarray:
+        """counts [nsrc, n] (source-major) entries per source and window; d_lists: device pointer to the lists in that order.
+        ins_high: insert_high where it differs from insert_low (= ins)"""
         cnt = _c(counts, np.uint32).reshape(-1)
         assert cnt.shape[0] == nsrc * n
-        cp = CovParams(e0, e1, rs, ms, ins, ins, floor)
+        cp = CovParams(e0, e1, rs, ms, ins, ins if ins_high is None else ins_high, floor)
         valid = np.zeros(n, np.uint8)
         if n:
             check(self.L.vdjx_window_cover(self.h, n, ln, rl, C.byref(cp), C.c_void_p(d_lists), nsrc, _p(cnt), _p(valid)), "vdjx_window_cover")

@@ -1294,7 +1294,13 @@ __global__ __launch_bounds__(MAP_THREADS) void k_window_cover(int len, int rl, v
                                                               const u32* __restrict__ pair_cnt, uint8_t* __restrict__ out_valid,
                                                               u64* __restrict__ dbg) {
 	const long long t_begin = dbg ? clock64() : 0;
-	__shared__ u32 hf[MAP_MAXOFF + 64 + 2];         // histogram of firsts -> inclusive prefix "cum"
+	// histogram of firsts -> inclusive prefix "cum", indexed 0 .. len + 1.  The entry points (make_index_view, vdjx_window_cover) take
+	// len - rl <= MAP_MAXOFF with rl <= VDJX_MAX_READ_LEN, so len + 2 words hold the longest window.
+	constexpr int HF_WORDS = MAP_MAXOFF + VDJX_MAX_READ_LEN + 2;
+	// LDS: (1186 + 8192) words + the three flags below = 37,524 bytes; 4 workgroups of it fit a CU's 160 KiB, as they did with the
+	// 1,090 words of before (a fifth would need 32 KiB each).  The assert holds that occupancy, not just the 64 KiB of a workgroup.
+	static_assert(4 * ((HF_WORDS + COV_WORDS) * 4 + 3 * 4) <= 160 * 1024, "k_window_cover: 4 workgroups per CU need hf + diff + flags <= 40 KiB");
+	__shared__ u32 hf[HF_WORDS];
 	__shared__ int diff[COV_WORDS];
 	__shared__ u32 s_bad, s_ok;
 	__shared__ int s_firstv;
@@ -2106,7 +2112,10 @@ extern "C" int vdjx_window_cover(vdjx_ctx* c, size_t n, int len, int rl, const v
                                  const uint32_t* counts, uint8_t* out_valid) {
 	if (!c || !p || (n && (!counts || !out_valid))) { vdjx_set_error("vdjx_window_cover: NULL argument"); return VDJX_EINVAL; }
 	if (n == 0) return VDJX_OK;
-	if (nsrc == 0 || len <= rl || len - rl > MAP_MAXOFF || rl < 1) { vdjx_set_error("vdjx_window_cover: bad geometry"); return VDJX_EINVAL; }
+	if (nsrc == 0 || len <= rl || len - rl > MAP_MAXOFF || rl < 1 || rl > VDJX_MAX_READ_LEN) {      // (k_window_cover's hf[] is sized by these)
+		vdjx_set_error("vdjx_window_cover: bad geometry");
+		return VDJX_EINVAL;
+	}
 	int rc = cov_params_check(p, "vdjx_window_cover");
 	if (rc) return rc;
 	HIP_TRY(hipSetDevice(c->device));

@@ -715,7 +715,8 @@ int vdjx_tree(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const int32
  *               batches: the groups of whole replicates the device ran side by side (0 when no clone has two members); rounds =
  *               ceil(log2 largest_clone), Boruvka's rounds per batch; edges: the parent[i] >= 0; matched: the sum of the supports; full:
  *               the edges with support = replicates.
- * NOT modelled: support of splits (bipartitions) rather than of edges; the bootstrap with replacement.  An edge whose only differing
+ * NOT modelled: the bootstrap with replacement (support of splits -- bipartitions -- rather than of edges, for the trees with inferred
+ * nodes: vdjx_tree_split_support).  An edge whose only differing
  * columns are all deleted can still appear in a replicate through the index tie-break, so for such edges the support is an upper bound
  * (a 12-member descent with dist_parent = 1 everywhere gave supports between 5/16 and 16/16: informative, not exact).
  * VDJX_EINVAL: everything vdjx_tree refuses; replicates outside 1 .. 1024; a parent[i] that is i, outside -1 .. n-1 or in another clone;
@@ -768,7 +769,7 @@ int vdjx_tree_support(vdjx_ctx* ctx, const char* contigs, size_t n, int len, con
  *               cells: the sum of m * m over the lineages of two and more; parsimony: the sum of the mutations; length: of the lengths.
  * NOT modelled: maximum likelihood; dnapars' search over topologies (vdjx_tree_mp searches by nearest-neighbour interchanges from this
  * tree); the germline as a node of its own; alignment of members that differ
- * by an indel; support values for this tree; Sankoff costs from a targeting model.
+ * by an indel; Sankoff costs from a targeting model.  Support values for this tree: vdjx_tree_split_support.
  * VDJX_EINVAL: everything vdjx_tree refuses, and a NULL output other than out_anc.  VDJX_ELIMIT: a lineage of more than
  * VDJX_NJ_MAX_MEMBERS members, named with its size before any GPU work.  n = 0 returns at once with a zeroed info.
  * The host sorts the keys and computes the windows as vdjx_tree does.  The lineages of two and more run in batches of whole lineages of at
@@ -822,7 +823,8 @@ int vdjx_tree_nj(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const in
  *               parsimony: the sum of the final mutations (= P of the final trees).
  * NOT modelled: SPR / TBR rearrangements and random restarts (dnapars, pratchet): nearest-neighbour interchanges stop in local optima, and
  * from a poor start -- a caterpillar -- the search ends far above what it reaches from vdjx_tree_nj's tree; collapsing zero-length edges
- * into multifurcations; a germline node; Sankoff costs; support values.
+ * into multifurcations; a germline node; Sankoff costs.  Support values: vdjx_tree_split_support (its replicates are neighbour-joining
+ * trees, not searched ones).
  * VDJX_EINVAL: everything vdjx_tree_nj refuses; params->reserved != 0; a start_parent that is no such tree -- a parent outside the
  * lineage, a root leaf without exactly one child, an inferred node without exactly two, another leaf with children, a cycle -- named with
  * the lineage's clone key, before any GPU work.  VDJX_ELIMIT: a lineage of more than VDJX_MP_MAX_MEMBERS members, named with its size
@@ -846,6 +848,65 @@ int vdjx_tree_mp(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const in
                  const int32_t* start_parent /* [nodes] or NULL */, const vdjx_tree_mp_params* params /* NULL: {0, 0} */,
                  int32_t* out_parent, int32_t* out_mutations, int32_t* out_depth, int32_t* out_clone /* each [nodes] */,
                  char* out_anc /* [nodes - n][len]; may be NULL */, vdjx_tree_mp_info* info);
+
+/* ---- split support for the trees with inferred ancestors: the delete-half jackknife around neighbour joining ---------------------------
+ * vdjx_tree_nj and vdjx_tree_mp give a fully resolved tree, and nothing in it says which internal edges the data decides.  This call gives
+ * what dowser's getBootstraps and ape's boot.phylo print on the internal nodes of a Newick tree: for every inferred node, the number of
+ * replicates whose tree has the same split.  vdjx_tree_support's figure counts edges {i, parent[i]} between two items, which a tree with
+ * inferred nodes does not have.  Integer throughout: the device's results are bitwise the model's (tests/tree_split_model.py).  There is
+ * no `vdjer` flag for it yet: the call is reached through this header and vdjer_amd.api / vdjer_amd.annot.
+ *   items       contigs, n, len, clone[], anchor[], prio exactly as vdjx_tree_nj takes them: the same windows (a, b), w = a + b, the same
+ *               local leaf ids 0 .. m - 1 in ascending caller index, the same root (the member of smallest (prio, index)).
+ *   parent      [nodes], nodes = vdjx_tree_nj_nodes(clone, n), in vdjx_tree_nj's slots: the scored tree.  Any rooted binary tree that
+ *               vdjx_tree_mp would accept as start_parent -- vdjx_tree_nj's out_parent, vdjx_tree_mp's, or a handmade one -- checked as
+ *               there and refused with the same kind of message.
+ *   splits      clade(v) of an inferred node v: the members below it.  The tree is rooted at a leaf, so clade(v) is the side of the edge
+ *               (v, parent(v)) without the root member, and two trees over the same members share that bipartition iff they have a node
+ *               of the same clade.  The root's only child (everyone but the root) and the leaves are trivial and not scored: a lineage of m
+ *               members has max(0, m - 3) scored nodes, the internal edges of an unrooted binary tree.
+ *   replicate   r = 1 .. replicates keeps window position q when bit q & 31 of mix64(seed ^ ((uint64_t) r << 32 | q >> 5)) is set:
+ *               vdjx_tree_support's rule bit for bit, the same for every lineage (the same seed deletes the same columns there and
+ *               here).  d_r(i, j) is the distance over the kept positions alone; the replicate's tree is vdjx_tree_nj's joining on
+ *               D = d_r << 16 -- the same key (Q, i, j), the same floors, the same node ids in creation order -- rooted at the same member.
+ *               A replicate that keeps no position of a lineage's window has all distances 0: the key still defines its tree.  Branch
+ *               lengths and Fitch's passes are not computed.
+ *   output      out_support[v], for a scored node v: the number of replicates whose tree has an inferred node with exactly clade(v)
+ *               (equality of sets, not of a hash).  -1 in every other slot: items, the root's child, the nodes of lineages of three and
+ *               fewer, items with clone = -1.  out_rep_parent (may be NULL) is [replicates][nodes]: every replicate's rooted tree in
+ *               vdjx_tree_nj's slots -- what vdjx_tree_nj's joining gives on the kept columns, the lineages of three and fewer included --
+ *               so that a support can be traced to the replicate that made it.
+ *   info        (may be NULL; zeroed first, every field filled on success) members, clones, largest_clone as vdjx_tree_nj's; replicates;
+ *               batches; units: the (replicate, lineage of four and more) pairs; scored: the scored nodes; matched: the sum of the
+ *               supports; full: the scored nodes with support = replicates; joins, cells: vdjx_tree_nj's, summed over the units.
+ * NOT modelled: a parsimony search per replicate (for vdjx_tree_mp's tree the replicates are still neighbour-joining trees); the bootstrap
+ * with replacement; a consensus tree of the replicates.
+ * VDJX_EINVAL: everything vdjx_tree_nj refuses; replicates outside 1 .. 1024; reserved != 0; a parent that vdjx_tree_mp would refuse as a
+ * start; NULL parent, params or out_support.  VDJX_ELIMIT: a lineage of more than VDJX_NJ_MAX_MEMBERS members.  All before any GPU work.
+ * n = 0 returns at once with a zeroed info.
+ * The host lays the lineages out, checks the scored tree and makes its canonical clades (bitsets of ceil(m / 64) 64-bit words over the
+ * local leaf ids) with their signatures, sorted, once per lineage.  The units run replicate-major in batches of whole units of at most
+ * VDJX_NJ_CELLS matrix cells (vdjx_tree_nj's knob, read per call; any value gives the same bytes).  A batch: the pack through the
+ * replicates' kept positions; vdjx_tree_nj's matrix and join kernels unchanged (a unit is a lineage to them); the clades of the join order
+ * (a wave per unit, a lane per word: a join's clade is the union of its two children's, one pass in creation order; complemented within m
+ * bits where it holds the root; in LDS up to 64 members); the look-up (a lane per clade: up to 64 members the one word is searched for,
+ * beyond that the wrap-around sum of mix64(leaf + 1), then the run of equal signatures; a hit counts after all words compare equal: one
+ * integer atomicAdd).  Nothing is read back per batch unless out_rep_parent is given (then the edges, rooted on the host); the supports come
+ * back once.  Sums only: two calls give the same bits.  No floating point; scratch comes from the context's workspace.  Stats:
+ * "tree_split_us" (host clock), "tree_split_units", "tree_split_batches".
+ *
+ * vdjx_tree_split_compare is the match step on the host, exactly (plain C, no GPU): out_shared[v] is 1 or 0 for a scored node v of tree a
+ * -- whether tree b has its clade -- and -1 elsewhere; *shared and *scored (may be NULL) count them.  The Robinson-Foulds distance of two
+ * trees, such as vdjx_tree_nj's and vdjx_tree_mp's, is 2 (scored - shared).  A lineage's root in either tree is its member without a parent;
+ * the clades of both are taken against tree a's root.  Refused (VDJX_EINVAL) with vdjx_tree_mp's messages for a bad start_parent, and when
+ * nodes is not vdjx_tree_nj_nodes(clone, n). */
+typedef struct { uint32_t replicates; uint32_t reserved; uint64_t seed; } vdjx_tree_split_params;               /* 16 bytes; reserved must be 0 */
+typedef struct { uint32_t members, clones, largest_clone, replicates, batches, units;
+                 uint64_t scored, matched, full, joins, cells; } vdjx_tree_split_info;                          /* 64 bytes */
+int vdjx_tree_split_support(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const int32_t* clone, const int32_t* anchor, const uint32_t* prio,
+                            const int32_t* parent /* [nodes] */, const vdjx_tree_split_params* params, int32_t* out_support /* [nodes] */,
+                            int32_t* out_rep_parent /* [replicates][nodes] or NULL */, vdjx_tree_split_info* info);
+int vdjx_tree_split_compare(const int32_t* clone, size_t n, const int32_t* parent_a, const int32_t* parent_b, uint64_t nodes,
+                            int32_t* out_shared /* [nodes] */, uint64_t* shared, uint64_t* scored);
 
 /* ---- germline rows and R/S mutation counts: the contig and its V(D)J germline side by side, classified codon by codon ----------------
  * gives `vdjer --mutations` what Change-O's CreateGermlines and shazam's observedMutations make of V'DJer's output in a second tool: the

@@ -164,13 +164,19 @@ def tree_inputs(ids, contigs, v, clone):
     return anchor, prio
 
 
-def tree_nj_newick(ids, clone, parent, length):
+def tree_nj_newick(ids, clone, parent, length, support=None, replicates=None):
     """the trees of Context.tree_nj as `vdjer --trees-newick` writes them: one string per lineage of two and more members, in ascending
     lineage number.  ids: the n contigs' names; clone: int32[n], the 0-based lineage number of every contig (-1: none), the clone given to
     tree_nj; parent, length: tree_nj's, [nodes].  The tree is rooted at the root member: (<its one subtree>)'<root id>'; -- children in
     ascending slot, every node labelled and single-quoted, 'label':%.4f of length / 65536; an inferred node is lin_<k>_a<j>, j from 1
-    in creation order.  Plain Python, no recursion: a lineage may be thousands of nodes deep."""
+    in creation order.  With support (Context.tree_split_support's, [nodes]) and replicates both given, a scored node (support >= 0) is
+    labelled 'lin_<k>_a<j>/<%.4f of support / replicates>'; without them the strings are what they were.  Plain Python, no recursion: a
+    lineage may be thousands of nodes deep."""
     n, nodes = len(ids), len(parent)
+    if (support is None) != (replicates is None):
+        raise ValueError("tree_nj_newick: support and replicates go together")
+    if support is not None and (len(support) != nodes or int(replicates) < 1):
+        raise ValueError(f"tree_nj_newick: support of {len(support)} entries for {nodes} nodes, {replicates} replicates")
     sizes = {}
     for k in clone:
         if int(k) >= 0:
@@ -180,6 +186,8 @@ def tree_nj_newick(ids, clone, parent, length):
         names += [f"lin_{k + 1}_a{j + 1}" for j in range(max(0, sizes[k] - 2))]
     if len(names) != nodes:
         raise ValueError(f"tree_nj_newick: {nodes} nodes, but the clones of the {n} contigs make {len(names)}")
+    if support is not None:
+        names = [f"{x}/%.4f" % (int(support[s]) / int(replicates)) if s >= n and int(support[s]) >= 0 else x for s, x in enumerate(names)]
     kids = [[] for _ in range(nodes)]
     for s in range(nodes):
         if int(parent[s]) >= 0:
@@ -205,6 +213,28 @@ def tree_nj_newick(ids, clone, parent, length):
             text.append(f"'{names[s]}'" + ("" if s == roots[k] else ":%.4f" % (int(length[s]) / 65536)))
         out.append("".join(text) + ";")
     return out
+
+
+def tree_split_compare(clone, parent_a, parent_b):
+    """vdjx_tree_split_compare (plain C, no GPU): which splits of tree a tree b has.  clone: int32[n] as given to tree_nj; parent_a,
+    parent_b: int32[nodes] in tree_nj's slots (tree_nj's and tree_mp's "parent", say) -> {"shared": int32[nodes] (1 or 0 for an inferred
+    node of tree a other than a root's child, in a lineage of four and more; -1 elsewhere), "info": dict(shared, scored, rf)}; rf =
+    2 (scored - shared) is the Robinson-Foulds distance of the two trees."""
+    import ctypes as C
+
+    import numpy as np
+
+    from . import _lib
+    cl = np.ascontiguousarray(clone, np.int32)
+    pa, pb = np.ascontiguousarray(parent_a, np.int32), np.ascontiguousarray(parent_b, np.int32)
+    if cl.ndim != 1 or pa.ndim != 1 or pb.shape != pa.shape:
+        raise _lib.VdjxError(f"vdjx_tree_split_compare: clone of shape {cl.shape}, parents of shapes {pa.shape} and {pb.shape}")
+    out = np.full(pa.shape[0], -1, np.int32)
+    shared, scored = C.c_uint64(0), C.c_uint64(0)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+    _lib.check(_lib.lib().vdjx_tree_split_compare(ptr(cl), cl.shape[0], ptr(pa), ptr(pb), pa.shape[0], ptr(out), C.byref(shared), C.byref(scored)),
+               "vdjx_tree_split_compare")
+    return {"shared": out, "info": {"shared": int(shared.value), "scored": int(scored.value), "rf": 2 * int(scored.value - shared.value)}}
 
 
 def tree_mp_lengths(parent, mutations, clone):

@@ -1176,6 +1176,38 @@ class Context:
                 "anc": None if anc is None else [row.tobytes().split(b"\0", 1)[0].decode("latin-1") for row in anc],
                 "info": {f: int(getattr(info, f)) for f in self.TREE_MP_FIELDS}}
 
+    TREE_SPLIT_FIELDS = ("members", "clones", "largest_clone", "replicates", "batches", "units", "scored", "matched", "full", "joins", "cells")
+
+    def tree_split_support(self, contigs, clone, anchor, parent, prio=None, replicates=100, seed=1, return_trees=False, _reserved=0):
+        """vdjx_tree_split_support: the delete-half jackknife around neighbour joining.  contigs, clone, anchor, prio as tree_nj() takes
+        them; parent: int32[nodes] in tree_nj's slots, the scored tree (tree_nj's or tree_mp's "parent", or any tree tree_mp takes as a
+        start); replicates: 1 .. 1024; seed: any uint64 (tree_support's keep rule) -> {"support": int32[nodes] (for an inferred node other
+        than a root's child, in a lineage of four and more: the replicates whose neighbour-joining tree has its split; -1 elsewhere),
+        "trees": int32[replicates, nodes] (every replicate's parents in tree_nj's slots; None unless return_trees), "info":
+        dict(TREE_SPLIT_FIELDS)}"""
+        raw, n, ln = self._contig_block(contigs, "vdjx_tree_split_support")
+        cl = np.ascontiguousarray(clone, np.int32)
+        an = np.ascontiguousarray(anchor, np.int32)
+        pr = None if prio is None else np.ascontiguousarray(prio, np.uint32)
+        if cl.shape != (n,) or an.shape != (n,) or (pr is not None and pr.shape != (n,)):
+            raise VdjxError(f"vdjx_tree_split_support: {n} contigs, clone of shape {cl.shape}, anchor of shape {an.shape}")
+        total = C.c_uint64(0)
+        check(self.L.vdjx_tree_nj_nodes(_p(cl), n, C.byref(total)), "vdjx_tree_nj_nodes")
+        nodes = int(total.value)
+        pa = np.ascontiguousarray(parent, np.int32)
+        if pa.shape != (nodes,):
+            raise VdjxError(f"vdjx_tree_split_support: parent of shape {pa.shape} for {nodes} nodes")
+        if not 0 <= int(replicates) < 1 << 32 or not 0 <= int(seed) < 1 << 64:
+            raise VdjxError(f"vdjx_tree_split_support: replicates {replicates}, seed {seed}")
+        b = int(replicates)
+        params = _lib.TreeSplitParams(b, int(_reserved), int(seed))
+        support = np.zeros(nodes, np.int32)
+        trees = np.zeros((b if 1 <= b <= 1024 else 1, nodes), np.int32) if return_trees else None      # (a count the library refuses: nothing is written)
+        info = _lib.TreeSplitInfo()
+        check(self.L.vdjx_tree_split_support(self.h, raw, n, ln, _p(cl), _p(an), _p(pr), _p(pa), C.byref(params), _p(support), _p(trees), C.byref(info)),
+              "vdjx_tree_split_support")
+        return {"support": support, "trees": trees, "info": {f: int(getattr(info, f)) for f in self.TREE_SPLIT_FIELDS}}
+
     DIVERSITY_FIELDS = ("clones", "weighted", "weight", "depth", "replicates", "batches", "path")
 
     def diversity(self, weight, depth, q=None, replicates=200, seed=1, counts=False):

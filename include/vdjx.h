@@ -821,10 +821,10 @@ int vdjx_tree_nj(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const in
  *               lineages of four and more members; moved: those with at least one move; moves; rounds: the most scoring rounds any lineage
  *               had; candidates: the sum over the lineages and their scoring rounds of 2 (m - 3); parsimony_start: P of the start trees;
  *               parsimony: the sum of the final mutations (= P of the final trees).
- * NOT modelled: SPR / TBR rearrangements and random restarts (dnapars, pratchet): nearest-neighbour interchanges stop in local optima, and
- * from a poor start -- a caterpillar -- the search ends far above what it reaches from vdjx_tree_nj's tree; collapsing zero-length edges
- * into multifurcations; a germline node; Sankoff costs.  Support values: vdjx_tree_split_support (its replicates are neighbour-joining
- * trees, not searched ones).
+ * NOT modelled: subtree pruning and regrafting, the rearrangement of dnapars and pratchet (it is vdjx_tree_spr's, below); TBR and random
+ * restarts (modelled nowhere).  Nearest-neighbour interchanges stop in local optima, and from a poor start -- a caterpillar -- the search
+ * ends far above what it reaches from vdjx_tree_nj's tree.  Collapsing zero-length edges into multifurcations; a germline node; Sankoff
+ * costs.  Support values: vdjx_tree_split_support (its replicates are neighbour-joining trees, not searched ones).
  * VDJX_EINVAL: everything vdjx_tree_nj refuses; params->reserved != 0; a start_parent that is no such tree -- a parent outside the
  * lineage, a root leaf without exactly one child, an inferred node without exactly two, another leaf with children, a cycle -- named with
  * the lineage's clone key, before any GPU work.  VDJX_ELIMIT: a lineage of more than VDJX_MP_MAX_MEMBERS members, named with its size
@@ -848,6 +848,55 @@ int vdjx_tree_mp(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const in
                  const int32_t* start_parent /* [nodes] or NULL */, const vdjx_tree_mp_params* params /* NULL: {0, 0} */,
                  int32_t* out_parent, int32_t* out_mutations, int32_t* out_depth, int32_t* out_clone /* each [nodes] */,
                  char* out_anc /* [nodes - n][len]; may be NULL */, vdjx_tree_mp_info* info);
+
+/* ---- maximum-parsimony lineage trees by a search over subtree prunings and regraftings (SPR) --------------------------------------------
+ * vdjx_tree_mp rearranges by nearest-neighbour interchanges only and stops in their local optima.  dnapars (alakazam's buildPhylipLineage)
+ * and pratchet (dowser's getTrees) both prune a subtree and regraft it anywhere else in the tree.  This call is vdjx_tree_mp with that
+ * neighbourhood.  It is integer throughout: the device's results are bitwise the model's (tests/tree_spr_model.py).  There is no `vdjer`
+ * flag for it yet: the call is reached through this header and vdjer_amd.api.
+ *   items, start, score, finish, outputs   exactly vdjx_tree_mp's: contigs, n, len, clone[], anchor[], prio, the windows, the leaf sets with
+ *               a wildcard for anything that is not ACGT, the local ids (leaves 0 .. m - 1, inferred nodes m .. 2m - 3), the root leaf r of
+ *               smallest (prio, index) with its only child, children kept ascending, the output slots, start_parent[nodes] or NULL for
+ *               vdjx_tree_nj's tree, P(T), Fitch's two passes on the final topology.  The ids of the inferred nodes never change.
+ *   candidates  a lineage of m >= 4 members is searched.  A candidate is (c, y).  c, the pruned node, is any node other than r and r's
+ *               child.  With p = parent(c), s p's other child and g = parent(p), T' is the tree without the subtree of c and with p
+ *               dissolved: s takes p's place under g (and is r's child if g = r).  y is the lower end of an edge of T': any node of T'
+ *               other than r and other than s -- the edge above s is the old place.  One c has 2 (m - leaves(c)) - 4 candidates; at m = 4
+ *               these are the nearest-neighbour interchanges.
+ *   apply       with x = parent(y) in T': s replaces p among g's children; p replaces y among x's children (p becomes r's child if x = r);
+ *               p's children become {c, y}; every pair of children is sorted ascending again.  r never moves.
+ *   round       one round of one lineage scores every candidate; the one of smallest key (P, c, y) is applied if its P is below the
+ *               current P, otherwise the lineage is finished.  Where scores tie the key is the definition: the tree depends on the order
+ *               of the contigs (as vdjx_tree_mp's, vdjx_tree_nj's and vdjx_lineage_link's results do).  params.max_rounds caps the scoring
+ *               rounds of a lineage (0: until it is finished; every move lowers P by at least 1, so the search ends on its own).
+ *   info        (may be NULL; zeroed first) the fields and meanings of vdjx_tree_mp_info, but candidates: the sum over the lineages and
+ *               their scoring rounds of that round's candidates, which depend on the tree.
+ * NOT modelled: TBR, which also re-roots the pruned subtree; random restarts and the parsimony ratchet; collapsing zero-length edges into
+ * multifurcations; a germline node; Sankoff costs; a search per jackknife replicate (vdjx_tree_split_support's replicates are
+ * neighbour-joining trees).  A steepest descent is not guaranteed to end below vdjx_tree_mp's tree on every input.
+ * VDJX_EINVAL: everything vdjx_tree_mp refuses, with the same messages under this function's name.  VDJX_ELIMIT: a lineage of more than
+ * VDJX_SPR_MAX_MEMBERS members, named with its clone key and size before any GPU work (the limit is the search's, so it is never met
+ * below four members).  n = 0 returns at once with a zeroed info.
+ * Batches are vdjx_tree_nj's (whole lineages under VDJX_NJ_CELLS; any value gives the same bytes).  A batch keeps kid, par, the root's
+ * child, one up set per (inferred node, column), P and one 64-bit key per node on the device.  Fitch's length of an unrooted tree does
+ * not depend on the root, so P(T after (c, y)) = P(T') + P(subtree c) + #{columns: comb(U'(y), D'(y)) and U(c) do not meet}: U' are the up
+ * sets of T', which differ from the stored ones only on the path from g to r, and D' the down sets, D'(r's child) = r's set, D'(y) =
+ * comb(D'(x), U'(y's sibling)).  The first two terms less P(T) are the same for every y: minus p's union event, plus the changes on that
+ * path and at the root step.  A round is the scorer (a wave per lineage and pruned node, 64 columns at a time: the path walk, then one
+ * pre-order walk of T' that yields every edge's score; a byte per (node, lane) in LDS up to 128 members, in the workspace beyond;
+ * O(m^2 w) per lineage and round) and pick-and-apply (a workgroup per lineage still searching: arg-min of (delta, c, y), one thread
+ * rewires, all rewrite the stored sets along the two changed paths).  The host reads one counter per round from page-locked memory, roots
+ * the final kid / par, and vdjx_tree_nj's Fitch kernel runs unchanged; the search's P must equal the sum of the final mutations
+ * (VDJX_ESTATE otherwise).  Integer atomics are sums only: two calls give the same bits.  No floating point; scratch comes from the
+ * context's workspace.  Stats: "tree_spr_us" (host clock over "tree_mp_us"'s span), "tree_spr_candidates". */
+#define VDJX_SPR_MAX_MEMBERS 1024u
+typedef struct { uint32_t max_rounds, reserved; } vdjx_tree_spr_params;         /* reserved must be 0 */
+typedef struct { uint32_t members, clones, largest_clone, internal, batches, searched, moved, rounds;
+                 uint64_t edges, moves, candidates, parsimony_start, parsimony; } vdjx_tree_spr_info;          /* 72 bytes */
+int vdjx_tree_spr(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const int32_t* clone, const int32_t* anchor, const uint32_t* prio,
+                  const int32_t* start_parent /* [nodes] or NULL */, const vdjx_tree_spr_params* params /* NULL: {0, 0} */,
+                  int32_t* out_parent, int32_t* out_mutations, int32_t* out_depth, int32_t* out_clone /* each [nodes] */,
+                  char* out_anc /* [nodes - n][len]; may be NULL */, vdjx_tree_spr_info* info);
 
 /* ---- split support for the trees with inferred ancestors: the delete-half jackknife around neighbour joining ---------------------------
  * vdjx_tree_nj and vdjx_tree_mp give a fully resolved tree, and nothing in it says which internal edges the data decides.  This call gives
@@ -878,7 +927,8 @@ int vdjx_tree_mp(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const in
  *   info        (may be NULL; zeroed first, every field filled on success) members, clones, largest_clone as vdjx_tree_nj's; replicates;
  *               batches; units: the (replicate, lineage of four and more) pairs; scored: the scored nodes; matched: the sum of the
  *               supports; full: the scored nodes with support = replicates; joins, cells: vdjx_tree_nj's, summed over the units.
- * NOT modelled: a parsimony search per replicate (for vdjx_tree_mp's tree the replicates are still neighbour-joining trees); the bootstrap
+ * NOT modelled: a parsimony search per replicate (for vdjx_tree_mp's and vdjx_tree_spr's trees the replicates are still neighbour-joining
+ * trees); the bootstrap
  * with replacement; a consensus tree of the replicates.
  * VDJX_EINVAL: everything vdjx_tree_nj refuses; replicates outside 1 .. 1024; reserved != 0; a parent that vdjx_tree_mp would refuse as a
  * start; NULL parent, params or out_support.  VDJX_ELIMIT: a lineage of more than VDJX_NJ_MAX_MEMBERS members.  All before any GPU work.

@@ -1176,6 +1176,39 @@ class Context:
                 "anc": None if anc is None else [row.tobytes().split(b"\0", 1)[0].decode("latin-1") for row in anc],
                 "info": {f: int(getattr(info, f)) for f in self.TREE_MP_FIELDS}}
 
+    TREE_SPR_FIELDS = TREE_MP_FIELDS
+
+    def tree_spr(self, contigs, clone, anchor, prio=None, start=None, max_rounds=0, ancestors=True, _reserved=0):
+        """vdjx_tree_spr: tree_mp() with subtree pruning and regrafting as the rearrangement -- inside every clone of four and more, rounds
+        that score every (pruned node, edge to regraft it on) and apply the best while it lowers the Fitch total, from tree_nj's tree
+        (start=None) or from the caller's (start: int32[nodes], parents in tree_nj's slots); max_rounds caps a lineage's scoring rounds
+        (0: until no move lowers the total).  Arguments and result as tree_mp()'s -> {"parent", "mutations", "depth", "clone" int32:
+        [nodes] each, "anc": the inferred nodes' windows as str (None with ancestors=False), "info": dict(TREE_SPR_FIELDS)}; a lineage of
+        more than 1,024 members is refused."""
+        raw, n, ln = self._contig_block(contigs, "vdjx_tree_spr")
+        cl = np.ascontiguousarray(clone, np.int32)
+        an = np.ascontiguousarray(anchor, np.int32)
+        pr = None if prio is None else np.ascontiguousarray(prio, np.uint32)
+        if cl.shape != (n,) or an.shape != (n,) or (pr is not None and pr.shape != (n,)):
+            raise VdjxError(f"vdjx_tree_spr: {n} contigs, clone of shape {cl.shape}, anchor of shape {an.shape}")
+        total = C.c_uint64(0)
+        check(self.L.vdjx_tree_nj_nodes(_p(cl), n, C.byref(total)), "vdjx_tree_nj_nodes")
+        nodes = int(total.value)
+        sp = None if start is None else np.ascontiguousarray(start, np.int32)
+        if sp is not None and sp.shape != (nodes,):
+            raise VdjxError(f"vdjx_tree_spr: start of shape {sp.shape} for {nodes} nodes")
+        if not 0 <= int(max_rounds) < 1 << 32:
+            raise VdjxError(f"vdjx_tree_spr: max_rounds {max_rounds}")
+        params = _lib.TreeSprParams(int(max_rounds), int(_reserved))
+        parent, mutations, depth, out_clone = (np.zeros(nodes, np.int32) for _ in range(4))
+        anc = np.zeros((nodes - n, max(ln, 1)), np.uint8) if ancestors else None
+        info = _lib.TreeSprInfo()
+        check(self.L.vdjx_tree_spr(self.h, raw, n, ln, _p(cl), _p(an), _p(pr), _p(sp), C.byref(params), _p(parent), _p(mutations), _p(depth),
+                                   _p(out_clone), _p(anc), C.byref(info)), "vdjx_tree_spr")
+        return {"parent": parent, "mutations": mutations, "depth": depth, "clone": out_clone,
+                "anc": None if anc is None else [row.tobytes().split(b"\0", 1)[0].decode("latin-1") for row in anc],
+                "info": {f: int(getattr(info, f)) for f in self.TREE_SPR_FIELDS}}
+
     TREE_SPLIT_FIELDS = ("members", "clones", "largest_clone", "replicates", "batches", "units", "scored", "matched", "full", "joins", "cells")
 
     def tree_split_support(self, contigs, clone, anchor, parent, prio=None, replicates=100, seed=1, return_trees=False, _reserved=0):

@@ -32,32 +32,7 @@ static_assert(VDJX_MP_MAX_MEMBERS == NJ_MAX_M, "the header's limit");
 #define MP_STEP_SLOTS 64u                // the step counter is spread over this many words
 #define MP_FILL_WAVES 16384u             // 256 CUs x 4 SIMDs x 16 waves
 
-// NjFit describes a lineage here too: fs_off its first set, node0 its first inferred node among the batch's, ord_off its post-order
-__device__ inline u32 mp_comb(u32 a, u32 b) { return (a & b) ? (a & b) : (a | b); }
-__device__ inline int mp_flag(u32 a, u32 b) { return (a & b) ? 0 : 1; }
-
-__global__ __launch_bounds__(64) void k_mp_up(const NjFitItem* __restrict__ items, const NjFit* __restrict__ fits, const char* __restrict__ contigs,
-                                              const TreeRow* __restrict__ ri, const u32* __restrict__ kid, const u32* __restrict__ order,
-                                              uint8_t* __restrict__ up_all, u32* __restrict__ P) {
-	const NjFitItem it = items[blockIdx.x];
-	const NjFit q = fits[it.lin];
-	const u32 col = it.col0 + threadIdx.x, m = q.m;        // (m >= 2: the host makes no item for less)
-	const bool live = col < q.w;
-	const u32 cc = live ? col : 0u;
-	uint8_t* up = up_all + q.fs_off + cc;                  // + (v - m) * w
-	const u32* ord = order + q.ord_off;
-	auto leaf = [&](u32 p) { return nj_leaf_set(contigs[ri[q.first + p].at + cc]); };
-	auto set_of = [&](u32 v) { return v < m ? leaf(v) : (u32) up[(size_t) (v - m) * q.w]; };
-	u32 events = 0;
-	for (u32 t = 0; t + 2u < m; t++) {
-		const u32 v = ord[t], a = set_of(kid[2u * (q.node0 + v - m)]), b = set_of(kid[2u * (q.node0 + v - m) + 1u]);
-		if (live) up[(size_t) (v - m) * q.w] = (uint8_t) mp_comb(a, b);
-		events += (u32) __popcll(__ballot(live && !(a & b)));
-	}
-	events += (u32) __popcll(__ballot(live && !(leaf(q.root) & set_of(q.root_kid))));
-	if (threadIdx.x == 0 && events) atomicAdd(P + it.lin, events);
-}
-
+// k_mp_up, mp_comb and mp_flag: vdjx_fitch.h (vdjx_spr.hip starts from the same sets)
 // the j-th candidate node of a lineage: the inferred nodes but the root's child, ascending
 __device__ inline u32 mp_cand_node(u32 m, u32 root_kid, u32 j) { return m + j + (m + j >= root_kid ? 1u : 0u); }
 

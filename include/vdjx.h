@@ -769,7 +769,8 @@ int vdjx_tree_support(vdjx_ctx* ctx, const char* contigs, size_t n, int len, con
  *               cells: the sum of m * m over the lineages of two and more; parsimony: the sum of the mutations; length: of the lengths.
  * NOT modelled: maximum likelihood; dnapars' search over topologies (vdjx_tree_mp searches by nearest-neighbour interchanges from this
  * tree); the germline as a node of its own; alignment of members that differ
- * by an indel; Sankoff costs from a targeting model.  Support values for this tree: vdjx_tree_split_support.
+ * by an indel; Sankoff costs from a targeting model (they are vdjx_tree_sankoff's, below).  Support values for this tree:
+ * vdjx_tree_split_support.
  * VDJX_EINVAL: everything vdjx_tree refuses, and a NULL output other than out_anc.  VDJX_ELIMIT: a lineage of more than
  * VDJX_NJ_MAX_MEMBERS members, named with its size before any GPU work.  n = 0 returns at once with a zeroed info.
  * The host sorts the keys and computes the windows as vdjx_tree does.  The lineages of two and more run in batches of whole lineages of at
@@ -824,7 +825,8 @@ int vdjx_tree_nj(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const in
  * NOT modelled: subtree pruning and regrafting, the rearrangement of dnapars and pratchet (it is vdjx_tree_spr's, below); TBR and random
  * restarts (modelled nowhere).  Nearest-neighbour interchanges stop in local optima, and from a poor start -- a caterpillar -- the search
  * ends far above what it reaches from vdjx_tree_nj's tree.  Collapsing zero-length edges into multifurcations; a germline node; Sankoff
- * costs.  Support values: vdjx_tree_split_support (its replicates are neighbour-joining trees, not searched ones).
+ * costs (vdjx_tree_sankoff, below, is this search under a cost matrix).  Support values: vdjx_tree_split_support (its replicates are
+ * neighbour-joining trees, not searched ones).
  * VDJX_EINVAL: everything vdjx_tree_nj refuses; params->reserved != 0; a start_parent that is no such tree -- a parent outside the
  * lineage, a root leaf without exactly one child, an inferred node without exactly two, another leaf with children, a cycle -- named with
  * the lineage's clone key, before any GPU work.  VDJX_ELIMIT: a lineage of more than VDJX_MP_MAX_MEMBERS members, named with its size
@@ -872,7 +874,8 @@ int vdjx_tree_mp(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const in
  *   info        (may be NULL; zeroed first) the fields and meanings of vdjx_tree_mp_info, but candidates: the sum over the lineages and
  *               their scoring rounds of that round's candidates, which depend on the tree.
  * NOT modelled: TBR, which also re-roots the pruned subtree; random restarts and the parsimony ratchet; collapsing zero-length edges into
- * multifurcations; a germline node; Sankoff costs; a search per jackknife replicate (vdjx_tree_split_support's replicates are
+ * multifurcations; a germline node; Sankoff costs (vdjx_tree_sankoff, below, has them for the interchange search, not for SPR); a
+ * search per jackknife replicate (vdjx_tree_split_support's replicates are
  * neighbour-joining trees).  A steepest descent is not guaranteed to end below vdjx_tree_mp's tree on every input.
  * VDJX_EINVAL: everything vdjx_tree_mp refuses, with the same messages under this function's name.  VDJX_ELIMIT: a lineage of more than
  * VDJX_SPR_MAX_MEMBERS members, named with its clone key and size before any GPU work (the limit is the search's, so it is never met
@@ -897,6 +900,79 @@ int vdjx_tree_spr(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const i
                   const int32_t* start_parent /* [nodes] or NULL */, const vdjx_tree_spr_params* params /* NULL: {0, 0} */,
                   int32_t* out_parent, int32_t* out_mutations, int32_t* out_depth, int32_t* out_clone /* each [nodes] */,
                   char* out_anc /* [nodes - n][len]; may be NULL */, vdjx_tree_spr_info* info);
+
+/* ---- weighted (Sankoff) parsimony for the lineage trees ---------------------------------------------------------------------------------
+ * vdjx_tree_nj, vdjx_tree_mp and vdjx_tree_spr count every substitution as 1.  Somatic hypermutation prefers transitions, dnapars takes a
+ * transversion weight, and phangorn's pratchet / optim.parsimony take a cost matrix and run Sankoff's algorithm.  This call is vdjx_tree_mp
+ * with a 4 x 4 cost matrix in place of the unit cost: it scores a rooted tree, optionally runs the same hill climb over nearest-neighbour
+ * interchanges under the weighted score, and reconstructs the ancestors and every edge's cost.  It is integer throughout: the device's
+ * results are bitwise the model's (tests/tree_sankoff_model.py).  There is no `vdjer` flag for it yet: the call is reached through this
+ * header and vdjer_amd.api.
+ *   items, start  exactly vdjx_tree_mp's: contigs, n, len, clone[], anchor[], prio, the windows, the local ids (leaves 0 .. m - 1, inferred
+ *               nodes m .. 2m - 3), the root member r of smallest (prio, index) with its only child, children kept ascending, the output
+ *               slots, start_parent[nodes] or NULL for vdjx_tree_nj's tree, with vdjx_tree_mp's checks.
+ *   cost        cost[16], row-major: c[s][t] is the price of a parent in state s over a child in state t (A 0, C 1, G 2, T 3).  The
+ *               diagonal must be 0 and every off-diagonal cell 1 .. 65535.  The matrix need not be symmetric and need not satisfy the
+ *               triangle inequality: the tree is rooted at r, so the direction is defined.  NULL: every off-diagonal cell 1.  With m <=
+ *               4096 a column costs at most 8189 * 65535 < 2^31: per-column quantities fit 32 bits; totals are 64-bit.
+ *   up pass     per window column.  A child x's message for a parent state s is H_x(s): c[s][b] for a leaf whose character b is one of
+ *               ACGT, 0 for a leaf with any other character (a wildcard, as in vdjx_tree_nj), min_t (c[s][t] + S_x[t]) for an inferred
+ *               node, where S_v[s] = H_k0(s) + H_k1(s) over v's two children.  With x the root's child the column costs H_x(b_r) when r's
+ *               character is ACGT, otherwise min_s H_x(s).  W(T) is the sum over the columns.  With unit costs W(T) is vdjx_tree_mp's P(T).
+ *   down pass   r's state is its base, or for a wildcard the lowest s that minimises H_x(s).  An inferred node x under a parent in state s
+ *               takes the lowest t that minimises c[s][t] + S_x[t]; a leaf takes its base, or its parent's state if it is a wildcard.  An
+ *               edge's cost is the sum over the columns of c[state(parent)][state(child)], its mutations the number of columns where the
+ *               two states differ.  The edge costs sum to W(T).  The ancestors may differ from Fitch's where states tie: Fitch's second
+ *               pass picks from the child's set, this rule may keep the parent's state at equal cost.
+ *   search      params.search = 1: vdjx_tree_mp's candidates (v, k), swap and m <= 3 rule; a round scores every candidate, the one of
+ *               smallest key (W, v, k) is applied if its W is below the current one, otherwise the lineage is finished.  max_rounds as
+ *               vdjx_tree_mp's (every move lowers W by at least 1, so the search ends on its own).  With unit costs the moves and the
+ *               final parents are vdjx_tree_mp's.  params.search = 0 scores and reconstructs the start tree only.
+ *   outputs     [nodes] each.  out_parent, out_mutations, out_depth and out_clone follow vdjx_tree_mp's conventions; out_cost is the cost
+ *               of the edge above the node, -1 for a root and for an item in no lineage.  out_anc (may be NULL) is [nodes - n][len], NUL
+ *               from w on.
+ *   info        (may be NULL; zeroed first) members, clones, largest_clone, internal, batches, edges, moved, moves, rounds as
+ *               vdjx_tree_mp's; searched: the lineages of four and more members under search = 1, 0 under search = 0; candidates: the
+ *               sum over the lineages and their scoring rounds of 2 (m - 3); cost_start: W of the start trees; cost: the sum of out_cost
+ *               over the non-roots (= W of the final trees); mutations: the sum of out_mutations.
+ * NOT modelled: SPR or TBR under costs (vdjx_tree_spr is unit-cost); costs that depend on the 5-mer context or on the column -- Sankoff's
+ * recursion needs a cost that depends on the two states alone, so vdjx_sankoff_costs collapses a targeting model to the centre base; a
+ * germline node; multifurcations; a `vdjer` flag.
+ * VDJX_EINVAL: everything vdjx_tree_mp refuses, with the same messages under this function's name; a cost cell outside the ranges above,
+ * named; params.search above 1; a non-zero reserved word -- all before any GPU work.  VDJX_ELIMIT: a lineage of more than
+ * VDJX_MP_MAX_MEMBERS members.  n = 0 returns at once with a zeroed info.
+ * Batches are vdjx_tree_nj's (whole lineages under VDJX_NJ_CELLS; any value gives the same bytes).  A batch keeps kid, par, W, one int64
+ * per candidate and, per (inferred node, column), the node's message H to its parent: four uint32 in one 16-byte vector, the column the
+ * fastest index (16 bytes x inferred nodes x columns of workspace; a smaller VDJX_NJ_CELLS cuts it).  Keeping H and not S makes a step of
+ * a walk one min-plus product.  The sixteen costs are kernel arguments.  A round is the scorer (a wave per lineage and candidate, 64
+ * columns at a time: a lane recomputes v and p and walks to the root against the stored messages of the other children; the cost shows at
+ * the root only, as the new root term less the stored one; a wave-wide ballot ends a walk early where no lane's message changed) and
+ * pick-and-apply (a workgroup per lineage still searching: block-wide arg-min of (delta in 64 bits, v, k), one thread rewires, all rewrite
+ * the stored messages along the path).  The host reads one counter per round from page-locked memory, roots the final kid / par, and the
+ * down pass (a wave per lineage and 64 columns, parents before children) writes the states, the ancestors and per edge one integer
+ * atomicAdd per wave of its cost (64-bit) and mutations; the search's W must equal the sum of the edge costs (VDJX_ESTATE otherwise).
+ * Integer atomics are sums only: two calls give the same bits.  No floating point on the device; scratch comes from the context's
+ * workspace.  Stats: "tree_sankoff_us" (host clock over "tree_mp_us"'s span), "tree_sankoff_candidates", "tree_sankoff_steps" (the node
+ * updates the scorer made, per candidate and column tile; full rescoring would make candidates x (m - 2) per tile).
+ *
+ * vdjx_sankoff_costs (plain C, no GPU, no context): a targeting model's weights -> such a matrix, by vdjx_lineage_distance_table's recipe.
+ *   weight      uint32 [1024][4] as vdjx_lineage_distance_table takes it (row 256 a + 64 b + 16 c + 4 d + e, column the new base).
+ *   cost        Wc[c][e] = the 64-bit sum over the 256 5-mers with centre c of weight[row][e]; w' = max(Wc, 1) for the twelve cells with
+ *               e != c; S = their sum; d = -log10((double) w' / (double) S) (libm); mean = the twelve d added left to right in index
+ *               order in double, / 12.0; cost[c][e] = floor(1000 * d / mean + 0.5), clamped to 1 .. 65535; the diagonal is 0.  A uniform
+ *               model gives 1000 everywhere.
+ *   info        (may be NULL) mean, and the smallest and largest off-diagonal cell.
+ * VDJX_EINVAL: a NULL weight or cost. */
+typedef struct { uint32_t max_rounds, search, reserved[2]; } vdjx_tree_sankoff_params;      /* 16 bytes; reserved must be 0, search 0 or 1 */
+typedef struct { uint32_t members, clones, largest_clone, internal, batches, searched, moved, rounds;
+                 uint64_t edges, moves, candidates, cost_start, cost, mutations; } vdjx_tree_sankoff_info;     /* 80 bytes */
+typedef struct { double mean; uint32_t min_cost, max_cost; } vdjx_sankoff_costs_info;       /* 16 bytes */
+int vdjx_tree_sankoff(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const int32_t* clone, const int32_t* anchor, const uint32_t* prio,
+                      const uint32_t* cost /* [16] or NULL */, const int32_t* start_parent /* [nodes] or NULL */,
+                      const vdjx_tree_sankoff_params* params /* NULL: {0, 1, {0, 0}} */, int32_t* out_parent, int64_t* out_cost,
+                      int32_t* out_mutations, int32_t* out_depth, int32_t* out_clone /* each [nodes] */,
+                      char* out_anc /* [nodes - n][len]; may be NULL */, vdjx_tree_sankoff_info* info);
+int vdjx_sankoff_costs(const uint32_t* weight /* [1024][4] */, uint32_t* cost /* [16] */, vdjx_sankoff_costs_info* info);
 
 /* ---- split support for the trees with inferred ancestors: the delete-half jackknife around neighbour joining ---------------------------
  * vdjx_tree_nj and vdjx_tree_mp give a fully resolved tree, and nothing in it says which internal edges the data decides.  This call gives

@@ -401,6 +401,27 @@ def lineage_distance_table(weight):
     return table, dict(mean=float(info.mean), min_cost=int(info.min_cost), max_cost=int(info.max_cost))
 
 
+def sankoff_costs(weight):
+    """vdjx_sankoff_costs (plain C, no GPU) over targeting weights -- uint32[1024, 4] as read_targeting returns them, or the path of such a
+    file -> (cost uint32[4, 4] for Context.tree_sankoff(cost=...), info dict(mean, min_cost, max_cost)): the 5-mer weights summed per centre
+    base, -log10 of each substitution's share, normalised to a mean of 1, in thousandths; the diagonal is 0"""
+    import ctypes as C
+
+    import numpy as np
+
+    from . import _lib
+    if isinstance(weight, (str, bytes)) or hasattr(weight, "__fspath__"):
+        weight = read_targeting(weight if isinstance(weight, str) else __import__("os").fsdecode(weight))
+    given = np.asarray(weight)
+    if given.shape != (1024, 4) or given.dtype.kind not in "ui" or (given < 0).any() or (given >= 1 << 32).any():
+        raise ValueError(f"weights of shape {given.shape} and type {given.dtype}: whole numbers below 2^32, [1024, 4]")
+    w = np.ascontiguousarray(given, np.uint32)
+    cost = np.zeros((4, 4), np.uint32)
+    info = _lib.SankoffCostsInfo()
+    _lib.check(_lib.lib().vdjx_sankoff_costs(w.ctypes.data_as(C.c_void_p), cost.ctypes.data_as(C.c_void_p), C.byref(info)), "vdjx_sankoff_costs")
+    return cost, dict(mean=float(info.mean), min_cost=int(info.min_cost), max_cost=int(info.max_cost))
+
+
 THRESHOLD_GRID = 10000                                   # VDJX_THRESHOLD_GRID (include/vdjx.h): the grid is 0 .. 10000 ten-thousandths
 
 

@@ -1209,6 +1209,48 @@ class Context:
                 "anc": None if anc is None else [row.tobytes().split(b"\0", 1)[0].decode("latin-1") for row in anc],
                 "info": {f: int(getattr(info, f)) for f in self.TREE_SPR_FIELDS}}
 
+    TREE_SANKOFF_FIELDS = ("members", "clones", "largest_clone", "internal", "batches", "searched", "moved", "rounds", "edges", "moves",
+                           "candidates", "cost_start", "cost", "mutations")
+
+    def tree_sankoff(self, contigs, clone, anchor, prio=None, cost=None, start=None, search=True, max_rounds=0, ancestors=True, _reserved=0):
+        """vdjx_tree_sankoff: tree_mp() under a cost matrix -- cost: uint32[4, 4], cost[s][t] the price of a parent in state s over a child
+        in state t (A C G T; the diagonal 0, the rest 1 .. 65535; None: all 1, Fitch's count; annot.sankoff_costs makes one from a targeting
+        model).  Inside every clone the weighted cost of tree_nj's tree (start=None) or of the caller's (start: int32[nodes], parents in
+        tree_nj's slots), with search the rounds of nearest-neighbour interchanges that lower it (max_rounds caps a lineage's rounds, 0:
+        until none does), then Sankoff's down pass.  -> {"parent", "mutations", "depth", "clone" int32, "cost" int64: [nodes] each, in
+        tree_nj's slots (a root has parent -1, cost -1 and mutations -1), "anc": the inferred nodes' windows as str (None with
+        ancestors=False), "info": dict(TREE_SANKOFF_FIELDS)}."""
+        raw, n, ln = self._contig_block(contigs, "vdjx_tree_sankoff")
+        cl = np.ascontiguousarray(clone, np.int32)
+        an = np.ascontiguousarray(anchor, np.int32)
+        pr = None if prio is None else np.ascontiguousarray(prio, np.uint32)
+        if cl.shape != (n,) or an.shape != (n,) or (pr is not None and pr.shape != (n,)):
+            raise VdjxError(f"vdjx_tree_sankoff: {n} contigs, clone of shape {cl.shape}, anchor of shape {an.shape}")
+        co = None
+        if cost is not None:
+            given = np.asarray(cost)
+            if given.shape != (4, 4) or given.dtype.kind not in "ui" or (given < 0).any() or (given >= 1 << 32).any():
+                raise VdjxError(f"vdjx_tree_sankoff: cost of shape {given.shape} and type {given.dtype}: whole numbers below 2^32, [4, 4]")
+            co = np.ascontiguousarray(given, np.uint32)
+        total = C.c_uint64(0)
+        check(self.L.vdjx_tree_nj_nodes(_p(cl), n, C.byref(total)), "vdjx_tree_nj_nodes")
+        nodes = int(total.value)
+        sp = None if start is None else np.ascontiguousarray(start, np.int32)
+        if sp is not None and sp.shape != (nodes,):
+            raise VdjxError(f"vdjx_tree_sankoff: start of shape {sp.shape} for {nodes} nodes")
+        if not 0 <= int(max_rounds) < 1 << 32 or not 0 <= int(search) < 1 << 32:
+            raise VdjxError(f"vdjx_tree_sankoff: max_rounds {max_rounds}, search {search}")
+        params = _lib.TreeSankoffParams(int(max_rounds), int(search), (C.c_uint32 * 2)(int(_reserved), 0))
+        parent, mutations, depth, out_clone = (np.zeros(nodes, np.int32) for _ in range(4))
+        out_cost = np.zeros(nodes, np.int64)
+        anc = np.zeros((nodes - n, max(ln, 1)), np.uint8) if ancestors else None
+        info = _lib.TreeSankoffInfo()
+        check(self.L.vdjx_tree_sankoff(self.h, raw, n, ln, _p(cl), _p(an), _p(pr), _p(co), _p(sp), C.byref(params), _p(parent), _p(out_cost),
+                                       _p(mutations), _p(depth), _p(out_clone), _p(anc), C.byref(info)), "vdjx_tree_sankoff")
+        return {"parent": parent, "cost": out_cost, "mutations": mutations, "depth": depth, "clone": out_clone,
+                "anc": None if anc is None else [row.tobytes().split(b"\0", 1)[0].decode("latin-1") for row in anc],
+                "info": {f: int(getattr(info, f)) for f in self.TREE_SANKOFF_FIELDS}}
+
     TREE_SPLIT_FIELDS = ("members", "clones", "largest_clone", "replicates", "batches", "units", "scored", "matched", "full", "joins", "cells")
 
     def tree_split_support(self, contigs, clone, anchor, parent, prio=None, replicates=100, seed=1, return_trees=False, _reserved=0):

@@ -874,7 +874,7 @@ int vdjx_tree_mp(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const in
  *   info        (may be NULL; zeroed first) the fields and meanings of vdjx_tree_mp_info, but candidates: the sum over the lineages and
  *               their scoring rounds of that round's candidates, which depend on the tree.
  * NOT modelled: TBR, which also re-roots the pruned subtree; random restarts and the parsimony ratchet; collapsing zero-length edges into
- * multifurcations; a germline node; Sankoff costs (vdjx_tree_sankoff, below, has them for the interchange search, not for SPR); a
+ * multifurcations; a germline node; Sankoff costs (vdjx_tree_sankoff, below, has them for the interchange search, vdjx_tree_sankoff_spr for this one); a
  * search per jackknife replicate (vdjx_tree_split_support's replicates are
  * neighbour-joining trees).  A steepest descent is not guaranteed to end below vdjx_tree_mp's tree on every input.
  * VDJX_EINVAL: everything vdjx_tree_mp refuses, with the same messages under this function's name.  VDJX_ELIMIT: a lineage of more than
@@ -935,7 +935,7 @@ int vdjx_tree_spr(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const i
  *               vdjx_tree_mp's; searched: the lineages of four and more members under search = 1, 0 under search = 0; candidates: the
  *               sum over the lineages and their scoring rounds of 2 (m - 3); cost_start: W of the start trees; cost: the sum of out_cost
  *               over the non-roots (= W of the final trees); mutations: the sum of out_mutations.
- * NOT modelled: SPR or TBR under costs (vdjx_tree_spr is unit-cost); costs that depend on the 5-mer context or on the column -- Sankoff's
+ * NOT modelled: TBR under costs (SPR under costs is vdjx_tree_sankoff_spr, below); costs that depend on the 5-mer context or on the column -- Sankoff's
  * recursion needs a cost that depends on the two states alone, so vdjx_sankoff_costs collapses a targeting model to the centre base; a
  * germline node; multifurcations; a `vdjer` flag.
  * VDJX_EINVAL: everything vdjx_tree_mp refuses, with the same messages under this function's name; a cost cell outside the ranges above,
@@ -973,6 +973,54 @@ int vdjx_tree_sankoff(vdjx_ctx* ctx, const char* contigs, size_t n, int len, con
                       int32_t* out_mutations, int32_t* out_depth, int32_t* out_clone /* each [nodes] */,
                       char* out_anc /* [nodes - n][len]; may be NULL */, vdjx_tree_sankoff_info* info);
 int vdjx_sankoff_costs(const uint32_t* weight /* [1024][4] */, uint32_t* cost /* [16] */, vdjx_sankoff_costs_info* info);
+
+/* ---- subtree pruning and regrafting under Sankoff costs -----------------------------------------------------------------------------------
+ * vdjx_tree_spr searches by subtree pruning and regrafting but counts every substitution as 1; vdjx_tree_sankoff scores under a cost
+ * matrix but moves by nearest-neighbour interchanges only.  dnapars (with a transversion weight) and phangorn's pratchet /
+ * optim.parsimony (with a cost matrix) rearrange by SPR under that weight.  This call is vdjx_tree_spr's search under
+ * vdjx_tree_sankoff's score.  It is integer throughout: the device's results are bitwise the model's
+ * (tests/tree_sankoff_spr_model.py).  There is no `vdjer` flag for it yet: the call is reached through this header and vdjer_amd.api.
+ *   items, start  exactly vdjx_tree_mp's: contigs, n, len, clone[], anchor[], prio, the windows, the local ids (leaves 0 .. m - 1, inferred
+ *               nodes m .. 2m - 3), the root member r of smallest (prio, index) with its only child, children kept ascending, the output
+ *               slots, start_parent[nodes] or NULL for vdjx_tree_nj's tree, with vdjx_tree_mp's checks; batches under VDJX_NJ_CELLS.
+ *   cost, up pass, down pass, outputs   exactly vdjx_tree_sankoff's: cost[16] (c[s][t]: a parent in state s over a child in state t; the
+ *               diagonal 0, the rest 1 .. 65535; NULL: all 1) and its refusals, the messages H_x(s), S_v, the column cost, W(T), the down
+ *               pass, out_cost, out_mutations, out_anc.
+ *   candidates, apply   exactly vdjx_tree_spr's: a lineage of m >= 4 members is searched; (c, y) with c any node other than r and r's
+ *               child, T' the tree without c's subtree and with p = parent(c) dissolved (s, p's other child, under g = parent(p)), y any
+ *               node of T' other than r and s; the apply rule; params.max_rounds caps a lineage's scoring rounds (0: until finished).
+ *   round       one round of one lineage scores every candidate; the one of smallest key (W, c, y) is applied if its W is below the
+ *               current W, otherwise the lineage is finished.  Every move lowers W by at least 1, so the search ends on its own.  Where
+ *               costs tie the key is the definition.  With unit costs -- and with any matrix whose twelve costs are equal -- the moves
+ *               and the final parents are vdjx_tree_spr's.
+ *   info        (may be NULL; zeroed first) vdjx_tree_sankoff_info; candidates as vdjx_tree_spr counts them (per round, tree-dependent);
+ *               searched: the lineages of four and more members.
+ * With m <= VDJX_SPR_MAX_MEMBERS a column's quantities (messages, E', a candidate's cost, the sums inside a min-plus step) are below
+ * 2046 x 65535 < 2^31 and are kept in 32 bits; totals, deltas and the keys' deltas are 64-bit.
+ * The scorer's identity.  Fitch's root-independence, which vdjx_tree_spr uses, does not hold for an asymmetric matrix.  With H' the
+ * messages of T' -- the stored H except on the path from g to r, where they are recomputed upwards from S'_g = H_s + H_other -- and
+ * E'_y(u) the cheapest cost of everything in T' outside y's subtree plus the edge into a node in state u placed directly above y:
+ *     E'_top(u) = c[b_r][u] for top, r's child in T' (0 for all u where r's character is a wildcard),
+ *     E'_y(u) = min_v (E'_x(v) + H'_z(v) + c[v][u]) for the children y, z of an inferred node x,
+ *     W(T after (c, y)) = sum over the columns of min_u (E'_y(u) + H_c(u) + H'_y(u)).
+ * A round is the scorer (a wave per lineage and pruned node, 64 columns at a time: the path walk, then one pre-order walk of T'; a 16-byte
+ * vector per (node, lane) that holds first H' and then E', in LDS up to 32 members, in the workspace beyond; O(m^2 w) per lineage and
+ * round) and pick-and-apply (a workgroup per lineage still searching: arg-min of (delta in 64 bits, c, y), one thread rewires, all rewrite
+ * the stored messages along the two changed paths).  The host reads one counter per round from page-locked memory, roots the final kid /
+ * par, and vdjx_tree_sankoff's down pass runs unchanged; the search's W must equal the sum of the edge costs (VDJX_ESTATE otherwise).
+ * Integer atomics are sums only: two calls give the same bits.  No floating point; scratch comes from the context's workspace.
+ * NOT modelled: TBR; random restarts and the parsimony ratchet; multifurcations; a germline node; costs that depend on the 5-mer context
+ * or on the column; a `vdjer` flag.
+ * VDJX_EINVAL: everything vdjx_tree_sankoff refuses (but params.search, which this call has not), with the same messages under this
+ * function's name; a non-zero reserved word -- all before any GPU work.  VDJX_ELIMIT: a lineage of more than VDJX_SPR_MAX_MEMBERS
+ * members, refused as vdjx_tree_spr refuses it.  n = 0 returns at once with a zeroed info.
+ * Stats: "tree_sankoff_spr_us" (host clock over "tree_mp_us"'s span), "tree_sankoff_spr_candidates". */
+typedef struct { uint32_t max_rounds, reserved[3]; } vdjx_tree_sankoff_spr_params;   /* 16 bytes; reserved must be 0 */
+int vdjx_tree_sankoff_spr(vdjx_ctx* ctx, const char* contigs, size_t n, int len, const int32_t* clone, const int32_t* anchor,
+                          const uint32_t* prio, const uint32_t* cost /* [16] or NULL */, const int32_t* start_parent /* [nodes] or NULL */,
+                          const vdjx_tree_sankoff_spr_params* params /* NULL: all 0 */, int32_t* out_parent, int64_t* out_cost,
+                          int32_t* out_mutations, int32_t* out_depth, int32_t* out_clone /* each [nodes] */,
+                          char* out_anc /* [nodes - n][len]; may be NULL */, vdjx_tree_sankoff_info* info);
 
 /* ---- split support for the trees with inferred ancestors: the delete-half jackknife around neighbour joining ---------------------------
  * vdjx_tree_nj and vdjx_tree_mp give a fully resolved tree, and nothing in it says which internal edges the data decides.  This call gives

@@ -18,7 +18,7 @@ SYMBOLS = [
     "vdjx_anchor_sets_load", "vdjx_anchor_probe", "vdjx_index_generate", "vdjx_anchor_sets_from_anchors",
     "vdjx_kmer_build", "vdjx_graph_nodes", "vdjx_graph_pre_nodes", "vdjx_graph_export", "vdjx_graph_export_begin", "vdjx_graph_export_end", "vdjx_graph_block_layout", "vdjx_graph_export_block", "vdjx_graph_export_block_begin", "vdjx_graph_free",
     "vdjx_vregion_load", "vdjx_root_score", "vdjx_graph_roots", "vdjx_root_part", "vdjx_root_score_graph", "vdjx_root_score_graph_begin", "vdjx_root_score_graph_end",
-    "vdjx_read_index_build", "vdjx_read_index_build_device", "vdjx_read_index_build_begin", "vdjx_read_index_build_device_begin", "vdjx_read_index_build_end", "vdjx_window_score", "vdjx_window_pairs", "vdjx_window_pairs_fetch", "vdjx_window_cover", "vdjx_map_emit", "vdjx_map_emit_begin", "vdjx_map_emit_end", "vdjx_sam_names_load", "vdjx_sam_text", "vdjx_sam_blocks", "vdjx_sam_merge", "vdjx_rows_scatter", "vdjx_quant", "vdjx_quant_pairs", "vdjx_quant_boot", "vdjx_quant_pairs_boot", "vdjx_quant_boot_summary", "vdjx_germline_load", "vdjx_annotate", "vdjx_constant_load", "vdjx_isotype", "vdjx_dsegment_load", "vdjx_dcall", "vdjx_lineage", "vdjx_lineage_distance_table", "vdjx_lineage_model", "vdjx_lineage_link", "vdjx_threshold_kernel", "vdjx_lineage_threshold", "vdjx_tree", "vdjx_tree_support", "vdjx_tree_nj_nodes", "vdjx_tree_nj", "vdjx_tree_mp", "vdjx_tree_spr", "vdjx_tree_sankoff", "vdjx_sankoff_costs", "vdjx_tree_split_support", "vdjx_tree_split_compare", "vdjx_mutations_layout", "vdjx_mutations", "vdjx_selection", "vdjx_selection_convolve", "vdjx_selection_compare", "vdjx_targeting_counts", "vdjx_targeting_model", "vdjx_consensus_layout", "vdjx_consensus", "vdjx_consensus_hits", "vdjx_diversity", "vdjx_scan_u32", "vdjx_part_u64",
+    "vdjx_read_index_build", "vdjx_read_index_build_device", "vdjx_read_index_build_begin", "vdjx_read_index_build_device_begin", "vdjx_read_index_build_end", "vdjx_window_score", "vdjx_window_pairs", "vdjx_window_pairs_fetch", "vdjx_window_cover", "vdjx_map_emit", "vdjx_map_emit_begin", "vdjx_map_emit_end", "vdjx_sam_names_load", "vdjx_sam_text", "vdjx_sam_blocks", "vdjx_sam_merge", "vdjx_rows_scatter", "vdjx_quant", "vdjx_quant_pairs", "vdjx_quant_boot", "vdjx_quant_pairs_boot", "vdjx_quant_boot_summary", "vdjx_germline_load", "vdjx_annotate", "vdjx_constant_load", "vdjx_isotype", "vdjx_dsegment_load", "vdjx_dcall", "vdjx_lineage", "vdjx_lineage_distance_table", "vdjx_lineage_model", "vdjx_lineage_link", "vdjx_threshold_kernel", "vdjx_lineage_threshold", "vdjx_tree", "vdjx_tree_support", "vdjx_tree_nj_nodes", "vdjx_tree_nj", "vdjx_tree_mp", "vdjx_tree_spr", "vdjx_tree_sankoff", "vdjx_sankoff_costs", "vdjx_tree_sankoff_spr", "vdjx_tree_split_support", "vdjx_tree_split_compare", "vdjx_mutations_layout", "vdjx_mutations", "vdjx_selection", "vdjx_selection_convolve", "vdjx_selection_compare", "vdjx_targeting_counts", "vdjx_targeting_model", "vdjx_consensus_layout", "vdjx_consensus", "vdjx_consensus_hits", "vdjx_diversity", "vdjx_scan_u32", "vdjx_part_u64",
     "vdjx_host_alloc", "vdjx_host_free", "vdjx_host_take_rows",
     "vdjx_stat", "vdjx_profile_enable", "vdjx_profile_only", "vdjx_profile_reset", "vdjx_profile_count", "vdjx_profile_get",
     "vdjx_shard_begin", "vdjx_shard_begin_share", "vdjx_shard_free", "vdjx_shard_record_bytes", "vdjx_shard_count", "vdjx_shard_geometry", "vdjx_shard_symmetric", "vdjx_shard_geometry2", "vdjx_shard_local", "vdjx_shard_local_fill",
@@ -173,6 +173,13 @@ class SankoffCostsInfo(C.Structure):
 
 
 assert C.sizeof(TreeSankoffParams) == 16 and C.sizeof(TreeSankoffInfo) == 80 and C.sizeof(SankoffCostsInfo) == 16      # include/vdjx.h
+
+
+class TreeSankoffSprParams(C.Structure):
+    _fields_ = [("max_rounds", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+assert C.sizeof(TreeSankoffSprParams) == 16                                                        # include/vdjx.h
 
 class TreeSplitParams(C.Structure):
     _fields_ = [("replicates", C.c_uint32), ("reserved", C.c_uint32), ("seed", C.c_uint64)]
@@ -353,6 +360,8 @@ def lib():
     L.vdjx_tree_sankoff.argtypes = [vp, C.c_char_p, sz, i32, vp, vp, vp, vp, vp, C.POINTER(TreeSankoffParams), vp, vp, vp, vp, vp, vp,
                                     C.POINTER(TreeSankoffInfo)]
     L.vdjx_sankoff_costs.argtypes = [vp, vp, C.POINTER(SankoffCostsInfo)]
+    L.vdjx_tree_sankoff_spr.argtypes = [vp, C.c_char_p, sz, i32, vp, vp, vp, vp, vp, C.POINTER(TreeSankoffSprParams), vp, vp, vp, vp, vp, vp,
+                                        C.POINTER(TreeSankoffInfo)]
     L.vdjx_tree_split_support.argtypes = [vp, C.c_char_p, sz, i32, vp, vp, vp, vp, C.POINTER(TreeSplitParams), vp, vp, C.POINTER(TreeSplitInfo)]
     L.vdjx_tree_split_compare.argtypes = [vp, sz, vp, vp, C.c_uint64, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.vdjx_mutations_layout.argtypes = [vp, vp, vp, sz, vp]

@@ -1251,6 +1251,43 @@ class Context:
                 "anc": None if anc is None else [row.tobytes().split(b"\0", 1)[0].decode("latin-1") for row in anc],
                 "info": {f: int(getattr(info, f)) for f in self.TREE_SANKOFF_FIELDS}}
 
+    def tree_sankoff_spr(self, contigs, clone, anchor, prio=None, cost=None, start=None, max_rounds=0, ancestors=True, _reserved=0):
+        """vdjx_tree_sankoff_spr: tree_spr()'s search under tree_sankoff()'s cost -- inside every clone of four and more, rounds that score
+        every (pruned node, edge to regraft it on) under cost (uint32[4, 4] as tree_sankoff() takes it; None: all 1) and apply the best
+        while it lowers the weighted total, from tree_nj's tree (start=None) or from the caller's (start: int32[nodes], parents in
+        tree_nj's slots); max_rounds caps a lineage's scoring rounds (0: until no move lowers the total); then Sankoff's down pass.
+        -> tree_sankoff()'s dict; info["candidates"] counts as tree_spr()'s.  A lineage of more than 1,024 members is refused."""
+        raw, n, ln = self._contig_block(contigs, "vdjx_tree_sankoff_spr")
+        cl = np.ascontiguousarray(clone, np.int32)
+        an = np.ascontiguousarray(anchor, np.int32)
+        pr = None if prio is None else np.ascontiguousarray(prio, np.uint32)
+        if cl.shape != (n,) or an.shape != (n,) or (pr is not None and pr.shape != (n,)):
+            raise VdjxError(f"vdjx_tree_sankoff_spr: {n} contigs, clone of shape {cl.shape}, anchor of shape {an.shape}")
+        co = None
+        if cost is not None:
+            given = np.asarray(cost)
+            if given.shape != (4, 4) or given.dtype.kind not in "ui" or (given < 0).any() or (given >= 1 << 32).any():
+                raise VdjxError(f"vdjx_tree_sankoff_spr: cost of shape {given.shape} and type {given.dtype}: whole numbers below 2^32, [4, 4]")
+            co = np.ascontiguousarray(given, np.uint32)
+        total = C.c_uint64(0)
+        check(self.L.vdjx_tree_nj_nodes(_p(cl), n, C.byref(total)), "vdjx_tree_nj_nodes")
+        nodes = int(total.value)
+        sp = None if start is None else np.ascontiguousarray(start, np.int32)
+        if sp is not None and sp.shape != (nodes,):
+            raise VdjxError(f"vdjx_tree_sankoff_spr: start of shape {sp.shape} for {nodes} nodes")
+        if not 0 <= int(max_rounds) < 1 << 32:
+            raise VdjxError(f"vdjx_tree_sankoff_spr: max_rounds {max_rounds}")
+        params = _lib.TreeSankoffSprParams(int(max_rounds), (C.c_uint32 * 3)(int(_reserved), 0, 0))
+        parent, mutations, depth, out_clone = (np.zeros(nodes, np.int32) for _ in range(4))
+        out_cost = np.zeros(nodes, np.int64)
+        anc = np.zeros((nodes - n, max(ln, 1)), np.uint8) if ancestors else None
+        info = _lib.TreeSankoffInfo()
+        check(self.L.vdjx_tree_sankoff_spr(self.h, raw, n, ln, _p(cl), _p(an), _p(pr), _p(co), _p(sp), C.byref(params), _p(parent), _p(out_cost),
+                                           _p(mutations), _p(depth), _p(out_clone), _p(anc), C.byref(info)), "vdjx_tree_sankoff_spr")
+        return {"parent": parent, "cost": out_cost, "mutations": mutations, "depth": depth, "clone": out_clone,
+                "anc": None if anc is None else [row.tobytes().split(b"\0", 1)[0].decode("latin-1") for row in anc],
+                "info": {f: int(getattr(info, f)) for f in self.TREE_SANKOFF_FIELDS}}
+
     TREE_SPLIT_FIELDS = ("members", "clones", "largest_clone", "replicates", "batches", "units", "scored", "matched", "full", "joins", "cells")
 
     def tree_split_support(self, contigs, clone, anchor, parent, prio=None, replicates=100, seed=1, return_trees=False, _reserved=0):
